@@ -7,6 +7,7 @@
         bench.py --gpus N --steps K --warmup W        # the same, launched by the caller: one rank per GPU (RCCL)
     python bench.py --imgsz 1280                      # the 1280 x 1280 line of the north-star
     python bench.py --gpus 8 --scaling strong --scale m --imgsz 1280 --batch 256   # BASELINE config 3: 256 images split 32 / GPU
+    python bench.py --dump-outputs DIR                # also write the last timed step's outputs to DIR/*.npy (see dump_outputs)
 
 One "step" = one pass of the hot path over one batch of synthetic images already resident in HBM:
 engine forward (all HIP kernels) -> batched HIP NMS (conf 0.25, iou 0.7, max_det 300) -> (N > 1) RCCL all-gather of
@@ -65,7 +66,12 @@ def parse():
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-runs", type=int, default=20, help="CPU baseline sample: runs of --cpu-batch images (~10 s in all)")
     ap.add_argument("--cpu-runs-1t", type=int, default=3, help="the same at ONE thread (the reference's default, ultralytics/__init__.py:7-8)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/*.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 NAMES = {"yolo11": "YOLO11", "yolov8": "YOLOv8", "bsyolo11": "BS-YOLO11"}
@@ -118,6 +124,34 @@ def parity_stats(y, y_ref):
     step = max(1, ds.numel() // 8_000_000)  # torch.quantile caps its input size
     return {"score_max": float(f"{float(ds.max()):.3g}"), "score_p999": float(f"{float(torch.quantile(ds[::step], 0.999)):.3g}"), "score_mean": float(f"{float(ds.mean()):.3g}"),
             "box_max_px": float(f"{float(db.max()):.3g}"), "box_p999_px": float(f"{float(torch.quantile(db, 0.999)):.3g}"), "box_mean_px": float(f"{float(db.mean()):.3g}")}
+
+
+DUMP_BUDGET = 48 << 20  # bytes of detections written by --dump-outputs; the prediction sample adds 12 MB
+DUMP_PRED_SAMPLE = 1 << 20  # elements of the prediction tensor written by --dump-outputs
+
+
+def dump_outputs(out_dir, det, counts, y):
+    """--dump-outputs: the last timed step's results as float .npy files, identical inputs from run to run (seeded weights and images):
+    detections.npy  (N, max_det, 6) float32: what NMS returned per image (x1, y1, x2, y2, conf, cls); rows past counts[i] are padding
+                    and written as zeros.  N = every image of the step (all ranks' after the all-gather), or its first images that fit
+                    DUMP_BUDGET.
+    counts.npy      (N,) float64: detections per image.
+    predictions_sample.npy / predictions_sample_index.npy  (DUMP_PRED_SAMPLE,) float32 / float64: a fixed seeded sample of this rank's
+                    prediction tensor (B, 4 + nc, A) that NMS read, and the flat indices it was taken at (sorted; may repeat).
+    Host copies only (no kernel launch), after the timed region."""
+    import numpy as np
+    import torch
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n = max(1, min(det.shape[0], DUMP_BUDGET // (det[0].numel() * 4)))
+    d, c = det[:n].cpu().float(), counts[:n].cpu().to(torch.int64)
+    d[torch.arange(d.shape[1]).view(1, -1) >= c.view(-1, 1)] = 0.0
+    yh = y.detach().flatten().cpu()
+    idx = torch.randint(0, yh.numel(), (DUMP_PRED_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    np.save(out / "detections.npy", d.numpy())
+    np.save(out / "counts.npy", c.numpy().astype(np.float64))
+    np.save(out / "predictions_sample.npy", yh[idx].float().numpy())
+    np.save(out / "predictions_sample_index.npy", idx.numpy().astype(np.float64))
 
 
 def self_launch(args):
@@ -213,6 +247,7 @@ def main():
     from bs_yolo_amd.parallel import gather_detections_async
     pending = None   # the previous step's detection all-gather, in flight on RCCL's stream
     gathered = None
+    last_y = None    # --dump-outputs: the prediction tensor of the latest step
 
     # Post-processing stream: NMS reads a prediction tensor of its own (the engine allocates `y` per call), so NMS of step i may run
     # beside the forward of step i + 1 -- 64 one-workgroup-per-image kernels next to 256-CU conv launches.  The forward's stream
@@ -233,7 +268,7 @@ def main():
         fstreams.append(torch.cuda.Stream(device=dev))
 
     def step():
-        nonlocal pending, gathered, nstep
+        nonlocal pending, gathered, nstep, last_y
         k = nstep % len(engines)
         nstep += 1
         if k:
@@ -243,6 +278,8 @@ def main():
             post.wait_stream(fstreams[k])
         else:
             y, _ = eng(x, want_raw=False)
+        if args.dump_outputs:
+            last_y = y
         if post is not main and not k:
             post.wait_stream(main)
         with torch.cuda.stream(post):
@@ -316,6 +353,8 @@ def main():
         dt = float(t.item())
     ms_step = dt / args.steps * 1e3
     value = global_batch * args.steps / dt
+    if args.dump_outputs and rank == 0:  # before the profile passes: graph mode's outputs live in a ring that a replay overwrites
+        dump_outputs(args.dump_outputs, *(gathered if use_dist else (det, counts)), last_y)
 
     if rank == 0:
         # ---- roofline of the dominant kernel family: EVERY launch that does dense-conv MFMA work -- the plan's OP_CONV ops

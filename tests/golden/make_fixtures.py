@@ -552,10 +552,64 @@ def config1_fixture():
     print("wrote config1_bus:", pred.shape[0], "detections, letterbox", lb.shape, "shift", shift)
 
 
+def encode_state_dict(sd, seed=0):
+    """A state_dict keyed by reference names -> (codes, arrays), lossless: "synth" = synth_param(name, shape, seed) bit for bit,
+    "scaled" = synth_param(...) times a stored fp32 factor per output row (what fuse() makes of a conv weight), "raw" = the
+    stored array.  Decoded by tests/test_host_logic.py decode_state_dict; every tensor is checked to decode exactly."""
+    codes, arrays = [], {}
+    for i, (k, t) in enumerate(sd.items()):
+        t = t.detach()
+        code = "raw"
+        if t.is_floating_point():
+            base = synth_param(k, t.shape, seed)
+            if torch.equal(t, base):
+                code = "synth"
+            elif t.dim() >= 2 and base.flatten(1).abs().amax(1).gt(0).all():
+                b2, t2 = base.flatten(1), t.flatten(1)
+                j = b2.abs().argmax(1, keepdim=True)
+                f = (t2.gather(1, j).double() / b2.gather(1, j).double()).float()
+                for c in (torch.nextafter(f, f + 1), torch.nextafter(f, f - 1)):  # the quotient can miss by one ulp
+                    f = torch.where((b2 * f == t2).all(1, keepdim=True), f, c)
+                f = f.view(-1)
+                if torch.equal(base * f.view(-1, *[1] * (t.dim() - 1)), t):
+                    code = "scaled"
+                    arrays[f"{i}"] = f.numpy()
+        if code == "raw":
+            arrays[f"{i}"] = t.numpy()
+        codes.append((k, list(t.shape), str(t.dtype)[6:], code))
+    return codes, arrays
+
+
+def live_model_fixture():
+    """What bs_yolo_amd.plugin reads from a live reference DetectionModel (test_plugin_reads_a_live_reference_model): its
+    model.yaml dict and BatchNorm eps, its state_dict before fuse() (synth_param values, seed 0) and the state_dict that
+    BaseModel.fuse() leaves, encoded losslessly by encode_state_dict -- for YOLO11n (stock graph, nc = 80) and for the fork's
+    own graph (cfg/models/11/yolo11.yaml, nc = 12)."""
+    out = {}
+    for tag, m in (("yolo11n", DetectionModel(stock_cfg("yolo11", "n", "detect"), ch=3, nc=80, verbose=False)),
+                   ("bsyolo11", DetectionModel(str(CFG / "11" / "yolo11.yaml"), ch=3, verbose=False))):
+        m.eval()
+        for k, t in m.state_dict().items():
+            if not k.endswith("num_batches_tracked"):
+                t.copy_(synth_param(k, t.shape, 0))
+        eps = next(float(x.eps) for x in m.modules() if isinstance(x, torch.nn.BatchNorm2d))
+        meta = {"yaml": m.yaml, "bn_eps": eps}
+        for part in ("unfused", "fused"):
+            if part == "fused":
+                m.fuse(verbose=False)
+            meta[part], arrays = encode_state_dict(m.state_dict())
+            out.update({f"{tag}_{part}_{k}": v for k, v in arrays.items()})
+        out[f"{tag}_meta"] = json.dumps(meta)
+    np.savez_compressed(HERE / "live_model.npz", **out)
+    print("wrote live_model", {k: sum(c[3] == "raw" for c in json.loads(v)["fused"]) for k, v in out.items() if k.endswith("_meta")})
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1 and sys.argv[1] == "config1":  # BASELINE config 1 on bus.jpg (round 4)
         config1_fixture()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "live_model":  # only the live-model state_dicts of the plugin test
+        live_model_fixture()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "val":  # only the validator-matching vectors
         val_match_fixtures()
@@ -589,3 +643,4 @@ if __name__ == "__main__":
     letterbox_fixtures()
     val_match_fixtures()
     config1_fixture()
+    live_model_fixture()
