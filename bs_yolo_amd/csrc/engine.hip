@@ -476,26 +476,6 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             if (!R.ok || op.src0.C != a.C || op.res.C != a.C) return BSY_ERR_ARG;
             return launch_pmsfa_tail(a, s);
         }
-        case BSY_OP_CHAIN: {
-            ChainArgs a;
-            memset(&a, 0, sizeof(a));
-            a.a0 = R.h(op.src0); a.a1 = R.h(op.src1);
-            a.lda0 = op.src0.ld; a.lda1 = op.src1.buf >= 0 ? op.src1.ld : 0;
-            a.CA0 = op.src0.C; a.CA1 = op.src1.buf >= 0 ? op.src1.C : 0;
-            a.w1 = (const half_t*)(wb + op.w_off); a.b1 = (const float*)(wb + op.b_off); a.N1 = op.heads; a.act1 = op.nl;
-            a.d1 = R.h(op.box[0]); a.ldd1 = op.box[0].buf >= 0 ? op.box[0].ld : 0;
-            a.r1 = R.h(op.box[2]); a.ldr1 = op.box[2].buf >= 0 ? op.box[2].ld : 0;
-            a.keep0 = op.key_dim; a.LC = op.mid_c;
-            a.h2 = R.h(op.box[1]); a.ldh2 = op.box[1].buf >= 0 ? op.box[1].ld : 0; a.CH2 = op.box[1].buf >= 0 ? op.box[1].C : 0;
-            a.w2 = (const half_t*)(wb + op.w2_off); a.b2 = (const float*)(wb + op.b2_off); a.N2 = op.dst.C; a.act2 = op.act;
-            a.d2 = R.h(op.dst); a.ldd2 = op.dst.ld;
-            a.r2 = R.h(op.res); a.ldr2 = op.res.buf >= 0 ? op.res.ld : 0;
-            a.M = (long long)op.B * op.H * op.W;
-            if (!R.ok) return BSY_ERR_ARG;
-            if (op.up0 || op.up1 || (op.box[0].buf >= 0 && op.box[0].C != a.N1) || (op.box[2].buf >= 0 && op.box[2].C != a.N1) || (op.res.buf >= 0 && op.res.C != a.N2))
-                BSY_FAIL(BSY_ERR_ARG, "chain: inconsistent views");
-            return launch_chain(a, s);
-        }
         case BSY_OP_COPY: {
             const half_t* src = R.h(op.src0);
             half_t* dst = R.h(op.dst);
@@ -799,17 +779,6 @@ extern "C" int bsy_plan_autotune(bsy_plan* p, void* const* ext, int n_ext, bsy_s
             if (best_of[c] < best) { best = best_of[c]; best_cfg = cand[c]; }
         if (rc != BSY_OK) break;
         op.tuned_cfg = best_cfg + 1;
-        // runner-up within 12 %: the host re-times the two IN PLACE (bsy_plan_profile passes of the whole forward) and keeps the one
-        // that is faster where it runs -- back-to-back launches of one layer see its operands in the caches, the forward does not
-        // (two runners-up: reserved0 and, for conv ops unused, head_dim hold them as id + 1)
-        float alt = 1e30f, alt2 = 1e30f;
-        op.reserved0 = 0;
-        op.head_dim = 0;
-        for (int c = 0; c < nc; ++c) {
-            if (cand[c] == best_cfg || best_of[c] > 1.12f * best) continue;
-            if (best_of[c] < alt) { alt2 = alt; op.head_dim = op.reserved0; alt = best_of[c]; op.reserved0 = cand[c] + 1; }
-            else if (best_of[c] < alt2) { alt2 = best_of[c]; op.head_dim = cand[c] + 1; }
-        }
         a.cfg = best_cfg;
         rc = launch_conv(a, s);
     }
@@ -822,14 +791,6 @@ extern "C" int bsy_plan_autotune(bsy_plan* p, void* const* ext, int n_ext, bsy_s
 extern "C" int bsy_plan_get_tuning(bsy_plan* p, int32_t* out, int n) {
     if (!p || !out || n != (int)p->ops.size()) BSY_FAIL(BSY_ERR_ARG, "plan_get_tuning: bad argument");
     for (int i = 0; i < n; ++i) out[i] = p->ops[i].kind == BSY_OP_CONV ? p->ops[i].tuned_cfg - 1 : -1;
-    return BSY_OK;
-}
-
-// HOST array out[n_ops]: the rank-th runner-up (1 or 2) of the last bsy_plan_autotune for each op it timed (-1 = none within 12 % of
-// the winner, not a conv, or not timed by that call).
-extern "C" int bsy_plan_get_tuning_alt(bsy_plan* p, int rank, int32_t* out, int n) {
-    if (!p || !out || n != (int)p->ops.size() || rank < 1 || rank > 2) BSY_FAIL(BSY_ERR_ARG, "plan_get_tuning_alt: bad argument");
-    for (int i = 0; i < n; ++i) out[i] = p->ops[i].kind == BSY_OP_CONV ? (rank == 1 ? p->ops[i].reserved0 : p->ops[i].head_dim) - 1 : -1;
     return BSY_OK;
 }
 
@@ -956,11 +917,7 @@ extern "C" int bsy_plan_autotune_in_place(bsy_plan* p, void* const* ext, int n_e
         }
     }
     for (size_t i = 0; i < n; ++i)
-        if (!cand[i].empty()) {
-            p->ops[i].tuned_cfg = best_c[i] + 1;
-            p->ops[i].reserved0 = 0;
-            p->ops[i].head_dim = 0;
-        }
+        if (!cand[i].empty()) p->ops[i].tuned_cfg = best_c[i] + 1;
     return BSY_OK;
 }
 

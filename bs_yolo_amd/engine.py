@@ -27,7 +27,7 @@ class YoloEngine:
                  fuse_bneck: Optional[bool] = None, fuse_head: Optional[bool] = None, fuse_dwpw: Optional[bool] = None,
                  merge_c3k: Optional[bool] = None, fuse_msca: Optional[bool] = None, fuse_tail: Optional[bool] = None,
                  max_plans: Optional[int] = None, precision: str = "fp16", graph: Optional[bool] = None, graph_ring: int = 3,
-                 latency: Optional[bool] = None, fuse_pmsfa: Optional[bool] = None, fuse_chain: Optional[bool] = None):
+                 latency: Optional[bool] = None, fuse_pmsfa: Optional[bool] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("bs_yolo_amd needs a ROCm GPU (there is no CPU fallback)")
         self.cfg = cfg
@@ -57,11 +57,10 @@ class YoloEngine:
         # second level: the same layer (channels, kernel, stride, epilogue) at a similar size (pixel count within a factor of
         # two) reuses the winner without timing -- rect batches differ from each other by a few rows or columns
         self._tune_family: Dict[tuple, int] = {}
-        self.tune_stats = {"timed_ops": 0, "cached_ops": 0, "family_ops": 0, "autotune_calls": 0, "in_place_flips": 0}
-        # how conv configurations are timed (see _autotune): "1" every candidate in place (default), "3" one layer at a time
-        # (bsy_plan_autotune) + its top three re-timed in place, "0" one layer at a time only
+        self.tune_stats = {"timed_ops": 0, "cached_ops": 0, "family_ops": 0, "autotune_calls": 0}
+        # how conv configurations are timed (see _autotune): "1" every candidate in place (default), anything else one layer
+        # at a time (bsy_plan_autotune)
         self.tune_mode = os.environ.get("BSY_TUNE_IN_PLACE", "1")
-        self.tune_in_place = self.tune_mode == "3"
         self._tune_file = os.environ.get("BSY_TUNE_CACHE")
         if self._tune_file and os.path.exists(self._tune_file):
             try:
@@ -102,7 +101,6 @@ class YoloEngine:
         self.fuse_msca = fuse_msca
         self.fuse_tail = fuse_tail
         self.fuse_pmsfa = fuse_pmsfa
-        self.fuse_chain = fuse_chain
         self._packed = Plan(cfg, 1, 64, 64, **self._fuse_kw())
         blob = pack_plan_weights(self._packed, state_dict, bn_eps)
         self.weight_bytes = len(blob)
@@ -130,7 +128,7 @@ class YoloEngine:
         return dict(fuse_stem=self.fuse_stem, fuse_bneck=self.fuse_bneck, fuse_head=self.fuse_head, fuse_dwpw=self.fuse_dwpw,
                     merge_c3k=self.merge_c3k, fuse_msca=self.fuse_msca, fuse_tail=self.fuse_tail, precision=self.precision,
                     lanes=True if getattr(self, "graph", False) else None, latency=getattr(self, "latency", False),
-                    fuse_pmsfa=self.fuse_pmsfa, fuse_chain=self.fuse_chain)
+                    fuse_pmsfa=self.fuse_pmsfa)
 
     # -- plans --------------------------------------------------------------------------------------------------
     def plan_for(self, B: int, H: int, W: int, in_dtype: torch.dtype, out_dtype: torch.dtype):
@@ -210,42 +208,8 @@ class YoloEngine:
         else:
             L.check(L.lib.bsy_plan_autotune(h, ext, n, C.c_void_p(stream)))
         if todo:
-            nops = len(plan.ops)
             out = (C.c_int32 * nops)()
             L.check(L.lib.bsy_plan_get_tuning(h, out, nops))
-            if self.tune_in_place:
-                # Second opinion for near-ties: bsy_plan_autotune launches one layer back to back (operands in L2 / Infinity Cache);
-                # here winner and runner-up of every newly tuned op are timed where they run -- serial profile passes of the whole
-                # forward, all winners then all runner-ups, best of three each -- and the faster one is kept
-                def passes(k=3):
-                    best = [1e30] * nops
-                    ms = (C.c_float * nops)()
-                    for _ in range(k):
-                        L.check(L.lib.bsy_plan_profile(h, ext, n, C.c_void_p(stream), ms))
-                        best = [min(b_, float(t)) for b_, t in zip(best, ms)]
-                    return best
-                t_cur, flips = None, 0
-                for rank in (1, 2):
-                    alt = (C.c_int32 * nops)()
-                    L.check(L.lib.bsy_plan_get_tuning_alt(h, rank, alt, nops))
-                    idx = [i for i, sg in enumerate(plan.conv_sigs) if sg is not None and sg not in self._tune_cache and alt[i] >= 0 and out[i] >= 0]
-                    if not idx:
-                        break
-                    if t_cur is None:
-                        t_cur = passes()
-                    sel = (C.c_int32 * nops)(*([-1] * nops))
-                    for i in idx:
-                        sel[i] = alt[i]
-                    L.check(L.lib.bsy_plan_set_tuning(h, sel, nops))
-                    t_alt = passes()
-                    for i in idx:
-                        if t_alt[i] < t_cur[i]:
-                            out[i], t_cur[i] = alt[i], t_alt[i]
-                            flips += 1
-                        sel[i] = out[i]
-                    L.check(L.lib.bsy_plan_set_tuning(h, sel, nops))
-                if flips:
-                    self.tune_stats["in_place_flips"] = self.tune_stats.get("in_place_flips", 0) + flips
             for sg, c in zip(plan.conv_sigs, out):
                 if sg is not None and c >= 0:
                     self._tune_cache.setdefault(sg, int(c))

@@ -91,12 +91,7 @@ enum bsy_op_kind {
                             * [q1 | q2] = conv2(p1).  aux_off = (weights, bias) byte offsets of conv2 (f32 [25][heads]), conv3 (f32 [49][key_dim])
                             * and conv4 (packed 1x1); heads / key_dim = row lengths of the two depthwise weight tensors.  C in {32, 64, 128};
                             * the same bits as the three launches it replaces                                              */
-    BSY_OP_CHAIN = 21,     /* two 1x1 Conv modules chained per pixel as one launch (round 4, csrc/chain1x1.hip; nn/modules/conv.py:149-151 twice):
-                            * stage 1 = act(W1 [src0 | src1] + b1) (+ box[2] as shortcut operand), heads = its output channels, w_off / b_off;
-                            * box[0] = its HBM output view (buf < 0: not written: nobody else reads it); its channels [key_dim, key_dim + mid_c)
-                            * stay in LDS and are the LAST mid_c input channels of stage 2 = act2(W2 [box[1] | kept] + b2) (+ res) -> dst,
-                            * w2_off / b2_off, nl = 1 when stage 1 has SiLU, act = stage 2's.  C3k2.cv1 -> C3k.cv1|cv2, C2PSA.cv1 -> qkv,
-                            * C3k.cv3 -> C3k2.cv2, ffn[1] -> C2PSA.cv2 (block.py:3796-3815, :4429-4468); the same bits as the two launches    */
+    /* 21: retired (the chained-1x1 launch of round 4, removed); not reused */
     BSY_OP_ELA = 15        /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
@@ -201,12 +196,9 @@ int bsy_plan_get_tuning(bsy_plan* p, int32_t* out, int n_ops);
  * the heuristic configuration -- an id from a stale or foreign tune cache), -1 = not a conv op or not preset.  Launches nothing; `ext` as
  * for bsy_plan_run.  bs_yolo_amd/engine.py drops the entries reported 0 from its tune cache before timing. */
 int bsy_plan_check_tuning(bsy_plan* p, void* const* ext, int n_ext, int32_t* valid, int n_ops);
-/* HOST array out[n_ops]: the rank-th runner-up (1 or 2) of the last bsy_plan_autotune per op (-1: none within 12 % of the winner).  The
- * host side re-times winner and runners-up in place with bsy_plan_profile and keeps the fastest (bs_yolo_amd/engine.py). */
-int bsy_plan_get_tuning_alt(bsy_plan* p, int rank, int32_t* out, int n_ops);
-/* The same decision taken in place: candidate k of every untuned conv op runs in pass k of the whole forward (serial, events around every op,
- * `rounds` passes per k), the fastest configuration per op is recorded.  Costs max(#candidates) x rounds forwards; what bs_yolo_amd/engine.py
- * uses by default (BSY_TUNE_IN_PLACE=0: bsy_plan_autotune). */
+/* bsy_plan_autotune's decision taken in place: candidate k of every untuned conv op runs in pass k of the whole forward (serial, events
+ * around every op, `rounds` passes per k), the fastest configuration per op is recorded.  Costs max(#candidates) x rounds forwards; what
+ * bs_yolo_amd/engine.py uses by default (BSY_TUNE_IN_PLACE=0: bsy_plan_autotune). */
 int bsy_plan_autotune_in_place(bsy_plan* p, void* const* ext, int n_ext, bsy_stream stream, int rounds);
 /* Test aid: plans created with BSY_PLAN_GUARD=<bytes> in the environment keep a guard band of that many bytes (0xA5) behind
  * every workspace buffer; this call synchronises the device and reports the first buffer whose band was written (an
