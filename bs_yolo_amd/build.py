@@ -38,6 +38,7 @@ SOURCES = {
     "val_match.hip": ["-ffp-contract=off"],
     "val_ap.hip": ["-ffp-contract=off"],
     "sahi.hip": ["-ffp-contract=off"],
+    "tta.hip": [],  # default contraction, as ATen's bilinear kernel is built; the merge turns it off with a pragma
     "ref32.hip": ["-ffp-contract=off", "-fno-vectorize"],  # loop vectoriser: packed f32 math in attn32_kernel otherwise
     "conv32_mfma.hip": ["-ffp-contract=off", "-fno-vectorize"],  # the same flags: its SiLU must be ref32.hip's bit for bit
     "conv32x_mfma.hip": ["-fno-vectorize"],  # fp32x mode: split-f16 operands on the fp16 matrix pipe

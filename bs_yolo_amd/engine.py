@@ -17,6 +17,8 @@ from typing import Dict, List, Mapping, Optional, Tuple
 import torch
 
 from . import lib as L
+from . import ops as O
+from . import tta as T
 from .plan import Plan
 from .weights import BN_EPS, adopt_offsets, pack_plan_weights
 
@@ -91,6 +93,8 @@ class YoloEngine:
         self._last_done = None
         self._last_stream = None
         self.graph_stats = {"captures": 0, "replays": 0, "eager": 0}
+        self._tta_geom: Dict[Tuple[int, int], list] = {}  # (H, W) -> tta.Pass list (forward_augment)
+        self._tta_bufs: "OrderedDict[Tuple, torch.Tensor]" = OrderedDict()  # scaled TTA inputs per (pass, B, PH, PW, dtype), LRU
         self.autotune = ((os.environ.get("BSY_AUTOTUNE", "1") != "0") if autotune is None else bool(autotune)) and precision == "fp16"
         # pack once with a throw-away plan (op list structure does not depend on the input size)
         self.fuse_stem = fuse_stem  # None: BSY_FUSE_STEM env (default on); False keeps layers 0 and 1 as two launches
@@ -342,9 +346,64 @@ class YoloEngine:
         return [(o["name"], int(c)) for o, c in zip(plan.ops, out) if c >= 0]
 
     def __call__(self, im, augment=False, visualize=False, embed=None, want_raw=True):
-        if augment or visualize or embed:
-            raise NotImplementedError("augment/visualize/embed fall back to the reference graph (tasks.py:134-164)")
+        if augment:  # tasks.py:134-136: augment wins over visualize / embed
+            return self.forward_augment(im)
+        if visualize or embed:
+            raise NotImplementedError("visualize/embed fall back to the reference graph (tasks.py:137-164)")
         return self.forward(im, want_raw)
+
+    def tta_geometry(self, H: int, W: int):
+        """The TTA passes of an (H, W) input (bs_yolo_amd/tta.py), their windows from the plans' detection levels."""
+        hit = self._tta_geom.get((H, W))
+        if hit is None:
+            levels = lambda h, w: Plan(self.cfg, 1, h, w, **self._fuse_kw()).meta["levels"]  # noqa: E731
+            hit = self._tta_geom[(H, W)] = T.geometry(H, W, int(max(self.meta["strides"])), levels)
+        return hit
+
+    def forward_augment(self, im: torch.Tensor):
+        """DetectionModel._predict_augment (nn/tasks.py:354-370) -> (y, None): three forwards at the scaled sizes, the scaled inputs
+        made by bsy_scale_img, the passes clipped / descaled / concatenated by ONE bsy_tta_merge on the current stream.  A Segment
+        graph returns its single-scale forward, as the reference reverts for every class but DetectionModel (:356-358)."""
+        with self._lock:
+            if self.meta["nm"]:
+                return self.forward(im)
+            if im.device != self.device:
+                raise ValueError(f"input on {im.device}, engine on {self.device}")
+            if im.dtype not in (torch.float16, torch.float32) or im.dim() != 4 or im.shape[1] != 3:
+                raise TypeError("input must be a BCHW fp16 or fp32 image tensor")
+            im = im.contiguous()
+            B, _, H, W = im.shape
+            passes = self.tta_geometry(H, W)
+            cur = torch.cuda.current_stream(self.device)
+            if self._last_done is not None and self._last_stream != cur.cuda_stream:
+                cur.wait_event(self._last_done)  # the scaled-input buffers may still be read by a forward on another stream
+            # every scaled input first, back to back: the second resize finds the image still in the cache, not behind a forward
+            xs = []
+            for i, p in enumerate(passes):
+                xi = im
+                if p.ratio != 1.0 or p.flip:
+                    # persistent per pass and shape: graph mode keys its captures by the input pointer (and no allocator churn)
+                    key = (i, B, p.padded[0], p.padded[1], im.dtype)
+                    buf = self._tta_bufs.get(key)
+                    if buf is None:
+                        while len(self._tta_bufs) >= 3 * max(self.max_plans, 1):  # rect batches: bounded like the plans
+                            self._tta_bufs.popitem(last=False)
+                        buf = self._tta_bufs[key] = torch.empty((B, 3) + p.padded, dtype=im.dtype, device=self.device)
+                    self._tta_bufs.move_to_end(key)
+                    xi = O.scale_img(im, p.ratio, p.flip, int(max(self.meta["strides"])), out=buf)
+                xs.append(xi)
+            ys = []
+            for xi in xs:
+                y, _ = self.forward(xi, want_raw=False)
+                if self.graph and len(passes) > self.graph_ring:
+                    y = y.clone()  # a ring shorter than the pass count could hand out one slot twice
+                ys.append(y)
+            y = O.tta_merge(ys, [p.window for p in passes], [p.ratio for p in passes], [p.flip for p in passes], (H, W))
+            if self._last_done is None:
+                self._last_done = torch.cuda.Event()
+            self._last_done.record(cur)
+            self._last_stream = cur.cuda_stream
+            return y, None
 
     def profile(self, im: torch.Tensor):
         """Per-op device time (ms) of one forward, measured with HIP events on the current stream."""
@@ -384,6 +443,7 @@ class YoloEngine:
         for _, h in self._plans.values():
             L.lib.bsy_plan_destroy(h)
         self._plans.clear()
+        self._tta_bufs.clear()
         if self._h:
             L.lib.bsy_engine_destroy(self._h)
             self._h = C.c_void_p()

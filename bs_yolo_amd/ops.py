@@ -251,3 +251,39 @@ def detect_decode(box: Sequence[torch.Tensor], cls: Sequence[torch.Tensor], hw: 
     L.check(L.lib.bsy_detect_decode(bp, ldb, cp, ldc, mp, ldm, hh, ww, st, nl, B, nc, nm, _p(y), L.dtype_code(out_dtype),
                                     _stream(y)))
     return y
+
+
+def scale_img(x: torch.Tensor, ratio: float, flip: Optional[int] = None, gs: int = 32,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scale_img(x.flip(flip) if flip else x, ratio, gs=gs) (utils/torch_utils.py:430-442) in one launch (bsy_scale_img): x (B,C,H,W)
+    fp16 / fp32 -> (B,C,PH,PW) of the same dtype.  Unlike the reference, ratio 1.0 with a flip still writes a new tensor."""
+    from .tta import scaled_size
+    assert x.is_contiguous() and x.dim() == 4 and x.dtype in (torch.float16, torch.float32)
+    B, Cc, H, W = x.shape
+    (oh, ow), (ph, pw) = scaled_size(H, W, ratio, gs)
+    if out is None:
+        out = torch.empty((B, Cc, ph, pw), dtype=x.dtype, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (B, Cc, ph, pw) and out.dtype == x.dtype
+    L.check(L.lib.bsy_scale_img(_p(x), L.dtype_code(x.dtype), B, Cc, H, W, oh, ow, ph, pw, int(flip or 0), _p(out), _stream(x)))
+    return out
+
+
+def tta_merge(ys: Sequence[torch.Tensor], windows: Sequence[tuple], scales: Sequence[float], flips: Sequence[Optional[int]],
+              img_hw: tuple, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """_descale_pred + _clip_augmented + torch.cat(y, -1) (nn/tasks.py:366-391) in one launch (bsy_tta_merge): ys[p] (B,no,A_p) of one
+    dtype, windows[p] = the kept anchors [begin, end) -> (B, no, sum of the window lengths)."""
+    n = len(ys)
+    y0 = ys[0]
+    B, no = y0.shape[:2]
+    for y in ys:
+        assert y.is_contiguous() and y.dim() == 3 and tuple(y.shape[:2]) == (B, no) and y.dtype == y0.dtype and y.device == y0.device
+    total = sum(e - b for b, e in windows)
+    if out is None:
+        out = torch.empty((B, no, total), dtype=y0.dtype, device=y0.device)
+    assert out.is_contiguous() and tuple(out.shape) == (B, no, total) and out.dtype == y0.dtype
+    i32 = C.c_int32
+    L.check(L.lib.bsy_tta_merge((C.c_void_p * n)(*[y.data_ptr() for y in ys]), (i32 * n)(*[y.shape[2] for y in ys]),
+                                (i32 * n)(*[b for b, _ in windows]), (i32 * n)(*[e for _, e in windows]),
+                                (C.c_float * n)(*[float(s) for s in scales]), (i32 * n)(*[int(f or 0) for f in flips]), n, B, no,
+                                int(img_hw[0]), int(img_hw[1]), L.dtype_code(y0.dtype), _p(out), _stream(out)))
+    return out

@@ -6,8 +6,10 @@ Three hooks, each using an extension point the reference already has (see INTEGR
                            (``m.forward = m.forward_fuse``, nn/tasks.py:215) -- so that AutoBackend's in-memory branch
                            (nn/autobackend.py:136-147, call at :524) reaches the engine.  The graph comes from
                            ``model.yaml`` (the dict parse_model consumed, nn/tasks.py:313-321) and the weights from
-                           ``model.state_dict()``.  Anything the engine does not cover (training mode, augment / visualize /
-                           embed (tasks.py:134-164), CPU tensors, unsupported modules) goes to the original forward.
+                           ``model.state_dict()``.  ``augment=True`` on a ``DetectionModel`` runs the engine's test-time
+                           augmentation (tasks.py:354-370; ``tta="reference"`` opts out).  Anything else the engine does not cover
+                           (training mode, visualize / embed / profile (tasks.py:137-164), augment on other model classes, CPU
+                           tensors, unsupported modules) goes to the original forward.
   install(model)           per-module hook (the fallback level for graphs `accelerate` does not cover: a custom block, an
                            unknown head).  Rebinds ``forward`` on every ``Conv`` / ``DWConv`` INSTANCE (nn/modules/conv.py:133-151,
                            :224-229) -- again the reference's own idiom, ``m.forward = m.forward_fuse`` (nn/tasks.py:215) -- so
@@ -110,7 +112,8 @@ def graph_support(cfg: dict) -> dict:
 FP32_MODES = {"engine_fp32x": "fp32x", "engine_fp32": "fp32", "engine": "fp16", "reference": None}
 
 
-def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_inputs: Optional[str] = None):
+def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_inputs: Optional[str] = None,
+               tta: Optional[str] = None):
     """Install the engine behind ``model.forward``.  Returns the same model object.
 
     fp32_inputs: what an fp32 image tensor gets (the reference's ``predict()`` default is ``half=False``,
@@ -129,17 +132,24 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     engine: there the reference itself computes in fp16.
 
     Graphs only some precisions can run (``graph_support``): calls in a precision the engine does not take go straight to the
-    reference forward -- decided here, once, not by a failing engine build on every call."""
+    reference forward -- decided here, once, not by a failing engine build on every call.
+
+    tta: what ``augment=True`` (test-time augmentation, nn/tasks.py:354-370) gets on a ``DetectionModel``: ``"engine"`` (default)
+    the engine's three scaled passes + HIP glue (YoloEngine.forward_augment), in whichever precision the call runs;
+    ``"reference"`` the original forward.  ``BSY_TTA`` overrides the default; ``state["tta_calls"]`` counts engine TTA calls."""
     import os
     cfg = cfg_of(model)
     support = graph_support(cfg)
     orig_forward = model.forward
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
-             "support": support, "failed": set()}
+             "tta_calls": 0, "support": support, "failed": set()}
     fp32_mode = fp32_inputs or os.environ.get("BSY_FP32_INPUTS", "engine_fp32x")
     if fp32_mode not in FP32_MODES:
         raise ValueError(f"fp32_inputs must be one of {sorted(FP32_MODES)}, not {fp32_mode!r}")
     prec32 = FP32_MODES[fp32_mode]  # engine precision fp32 images run in (None: the reference forward)
+    tta_mode = tta or os.environ.get("BSY_TTA", "engine")
+    if tta_mode not in ("engine", "reference"):
+        raise ValueError(f"tta must be 'engine' or 'reference', not {tta_mode!r}")
 
     def _engine_for(dev: torch.device, precision: str = "fp16") -> YoloEngine:
         key = (dev.index or 0, _weights_version(model))
@@ -164,7 +174,15 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
         visualize = kwargs.get("visualize", False)
         embed = kwargs.get("embed", None)
         profile = kwargs.get("profile", False)
-        if (self.training or augment or visualize or embed or profile or args or not isinstance(x, torch.Tensor)
+        # augment=True: the engine's TTA for exactly the class the reference runs it for (tasks.py:356-358: DetectionModel, not
+        # end2end), and then visualize / embed / profile are ignored as predict() does (tasks.py:134-136); anything else keeps its
+        # own forward (which reverts to single-scale or augments in torch)
+        if augment:
+            if tta_mode != "engine" or type(self).__name__ != "DetectionModel" or getattr(self, "end2end", False):
+                state["fallbacks"] += 1
+                return orig_forward(x, *args, **kwargs)
+            visualize = embed = profile = False
+        if (self.training or visualize or embed or profile or args or not isinstance(x, torch.Tensor)
                 or not _on_device(x) or x.dim() != 4 or x.dtype not in (torch.float16, torch.float32)
                 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32 or x.shape[0] == 0):
             state["fallbacks"] += 1
@@ -185,7 +203,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
                 "(the fp16 product path, ~3x faster again, |dscore| up to 6e-3), reference (the original forward); predict(half=True) "
                 "runs the fp16 path.", precision, fp32_mode)
         try:
-            y, raws = _engine_for(x.device, precision)(x)
+            y, raws = _engine_for(x.device, precision)(x, augment=bool(augment))
         except (_L.BsyError, NotImplementedError, AssertionError) as e:  # a shape / graph the engine rejects: the reference runs it
             if verbose:
                 print(f"bs_yolo_amd: falling back to the reference forward ({e})")
@@ -194,6 +212,8 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
             state["fallbacks"] += 1
             return orig_forward(x, *args, **kwargs)
         state["fp32_calls" if want32 else "engine_calls"] += 1
+        if augment:
+            state["tta_calls"] += 1
         return y, raws
 
     model.forward = types.MethodType(forward, model)

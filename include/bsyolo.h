@@ -424,6 +424,25 @@ int bsy_sahi_merge(const float* det, const int32_t* counts, const float* shift, 
                    float full_h, float* out, int32_t* out_count, int max_out, void* workspace, size_t workspace_bytes,
                    bsy_stream stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Test-time augmentation (predict / val with augment=True): the glue of DetectionModel._predict_augment (nn/tasks.py:354-370)
+ * around the engine's forwards.  Both are HBM-bound element maps, bitwise deterministic, no atomics.
+ * bsy_scale_img: scale_img(x.flip(flip) if flip else x, ratio, gs) (utils/torch_utils.py:430-442): in (B, C, H, W) f16 / f32 ->
+ *   out (B, C, PH, PW) of the same dtype; columns < OW of rows < OH are F.interpolate(size=(OH, OW), mode="bilinear",
+ *   align_corners=False) as ATen's device kernel computes it (fp32 arithmetic, one rounding), the rest is the pad value 0.447.
+ *   flip 0 = none, 2 = up-down, 3 = left-right (mirrored reads).  The caller computes OH, OW, PH, PW with the reference's
+ *   Python expressions (bs_yolo_amd/tta.py).
+ * bsy_tta_merge: _descale_pred (:372-380) + _clip_augmented (:382-391) + torch.cat(y, -1) in one launch.  src: HOST array of n
+ *   device pointers to the passes' predictions (B, no, A[p]) of dtype `dtype`; out (B, no, sum of (a_end - a_begin)) takes each
+ *   pass's window [a_begin[p], a_end[p]) in pass order, rows 0..3 times the fp32 reciprocal of scale[p] (rounded to the dtype),
+ *   then x = img_w - x for flip 3 or y = img_h - y for flip 2 (rounded again); rows >= 4 copied.  All arrays HOST, n <= 8.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BSY_TTA_MAX_PASSES 8
+int bsy_scale_img(const void* in, int dtype, int B, int C, int H, int W, int OH, int OW, int PH, int PW, int flip, void* out,
+                  bsy_stream stream);
+int bsy_tta_merge(const void* const* src, const int32_t* A, const int32_t* a_begin, const int32_t* a_end, const float* scale,
+                  const int32_t* flip, int n, int B, int no, int img_h, int img_w, int dtype, void* out, bsy_stream stream);
+
 const char* bsy_last_error(void);
 int bsy_version(void);
 
