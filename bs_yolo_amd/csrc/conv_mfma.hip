@@ -1684,8 +1684,7 @@ static int launch_cfg(const ConvK& k, hipStream_t s) {
     constexpr int TM = WM * MT * 32, TN = WN * NT * 32;
     ConvK p = k;
     p.ntn = ceil_div(k.Cout, TN);
-    const int nsl = k.nsl_c * k.nsl_t;
-    if (nsl > 1 && (!ALIGNED || (k.cb_per % BK))) BSY_FAIL(BSY_ERR_ARG, "conv: split-K needs an aligned configuration whose K-step divides the channel slices");
+    const int nsl = k.nsl_c * k.nsl_t;  // split-K: conv_cfg_valid admits only aligned rows whose BK divides the channel slices
     const long long nblk = (long long)ceil_div(k.M, TM) * p.ntn * (nsl > 1 ? nsl : 1);
     if (nblk <= 0 || nblk > 0x7fffffffLL) BSY_FAIL(BSY_ERR_ARG, "conv: grid %lld out of range", nblk);
     hipLaunchKernelGGL((conv_mfma_kernel<KS, WM, WN, MT, NT, STAGES, ALIGNED, BK>), dim3((unsigned)nblk), dim3(64 * WM * WN), 0, s, p);
@@ -1720,66 +1719,123 @@ int conv_korder(const ConvArgs& a) {
     return (a.stride == 2 && !(Cin & 63) && !(a.C0 & 63)) ? 2 : 1;
 }
 
-// Configuration ids: tile << 4 | variant.
-//   tile   : 0 = 256 px x 32 couts, 1 = 256 x 64, 2 = 128 x 128, 3 = 128 x 64 (4 waves); 4 = 256 x 128 (8 waves);
-//            5 = 64 x 128, 6 = 64 x 64 (4 waves; small tiles = many resident workgroups for the latency-bound thin-K layers);
-//            7 = 256 x 256 (8 waves, wave tile 64 x 128: half the L2->LDS bytes per FLOP of 128 x 128);
-//            8 = 128 x 128, 9 = 128 x 64 persistent 1x1 kernel (4 compute + 4 store waves, tiles walked per workgroup);
-//            10 = 8x16 px x 128 couts (2-stage weight ring), 11 = 8x16 px x 64 couts (variant 1: 3 stages, 2: 2 stages, 3: 4 stages):
-//            patch-based 3x3 stride-1 kernel; 12 / 13 = the same with 6x20-pixel tiles (maps whose width is a multiple of 20);
-//            14 / 15 = weights-resident streaming 1x1 kernel, 128 px x 128 / 64 couts (variant 1: 4-stage pixel ring, 2: 3 stages)
-//   variant: 0 = generic (per-lane K bookkeeping, flat DMA, BK 32, 3 stages), 1 = aligned BK 32 / 3 stages,
-//            2 = aligned BK 32 / 2 stages, 3 = aligned BK 64 / 2 stages; + 4 on the implicit-GEMM tiles of a layer whose K walk is
-//            chunk-major (conv_korder != 0): part of the id so that ids recorded before round 3 for the packed order on such a
-//            layer are recognised as stale (invalid -> heuristic)
+// Kernel configuration id: tile << 4 | variant, + 4 (the chunk-major bit) on an implicit-GEMM tile of a layer whose K walk is chunk-major
+// (conv_korder != 0), so that ids recorded before round 3 for the packed order on such a layer are recognised as stale (invalid ->
+// heuristic).  kConvCfgs has one row per id the library launches (a 64-cout patch id has a second one with the box-branch tail):
+// conv_cfg_valid, conv_candidates and launch_conv read what an id is from there.
+enum ConvFam { CONV_GEMM, CONV_PERSIST, CONV_WRES, CONV_PATCH, CONV_TAIL };
+struct ConvCfg {
+    int id; ConvFam fam;     // id without the chunk-major bit
+    int tm, tn, stages, bk;  // pixel tile x cout tile, DMA ring depth (K-steps), K-step (channels)
+    bool aligned;            // 32-channel-aligned operands; false: generic (per-lane K bookkeeping, flat DMA)
+    int tw, nfr;             // patch tile width: 16 (8 x 16 px) or 20 (6 x 20 px); weights-resident: most A fragments per wave built for
+    int (*launch[2])(const ConvK&, hipStream_t);  // implicit GEMM: by ksize 1 / 3; the other families run one ksize, from [0]
+};
+template <int WM, int WN, int MT, int NT, int S, bool AL, int BK> constexpr ConvCfg gemm_row(int id) {
+    return {id, CONV_GEMM, WM * MT * 32, WN * NT * 32, S, BK, AL, 0, 0, {launch_cfg<1, WM, WN, MT, NT, S, AL, BK>, launch_cfg<3, WM, WN, MT, NT, S, AL, BK>}};
+}
+template <int WM, int WN, int MT, int NT, int S, int BK> constexpr ConvCfg persist_row(int id) {
+    return {id, CONV_PERSIST, WM * MT * 32, WN * NT * 32, S, BK, true, 0, 0, {launch_persist<WM, WN, MT, NT, S, BK>}};
+}
+template <int NT, int S, int NFR> static int launch_wres_nfr(const ConvK& k, hipStream_t s) {  // 16 fragments where they hold K
+    return NT * ((k.C0 + k.C1) / 16) <= 16 ? launch_wres<NT, S, 16>(k, s) : launch_wres<NT, S, NFR>(k, s);
+}
+template <int NT, int S, int NFR> constexpr ConvCfg wres_row(int id) {
+    return {id, CONV_WRES, 128, 64 * NT, S, 32, true, 0, NFR, {launch_wres_nfr<NT, S, NFR>}};
+}
+template <int NT, int S, int TW, bool TAIL = false> constexpr ConvCfg patch_row(int id) {
+    return {id, TAIL ? CONV_TAIL : CONV_PATCH, TW == 16 ? 8 * 16 : 6 * 20, 64 * NT, S, 32, true, TW, 0, {launch_patch<NT, S, 2, TW, TAIL>}};
+}
+// gemm_row<WM, WN, MT, NT, STAGES, ALIGNED, BK>(id), variant 0 = generic (BK 32, 3 stages), 1 = aligned BK 32 / 3 stages, 2 = aligned
+// BK 32 / 2 stages, 3 = aligned BK 64 / 2 stages.  conv_candidates' sweep walks the implicit-GEMM and persistent rows in this order.
+static const ConvCfg kConvCfgs[] = {
+    gemm_row<4, 1, 2, 1, 3, false, 32>(0x00),  // 256 px x 32 couts (4 waves)
+    gemm_row<4, 1, 2, 1, 3, true, 32>(0x01),
+    gemm_row<4, 1, 2, 1, 2, true, 32>(0x02),
+    gemm_row<4, 1, 2, 1, 2, true, 64>(0x03),
+    gemm_row<4, 1, 2, 2, 3, false, 32>(0x10),  // 256 x 64 (4 x 1 waves: all 64 couts in one wave, what the DFL decoder needs)
+    gemm_row<4, 1, 2, 2, 3, true, 32>(0x11),
+    gemm_row<4, 1, 2, 2, 2, true, 32>(0x12),
+    gemm_row<4, 1, 2, 2, 2, true, 64>(0x13),
+    gemm_row<2, 2, 2, 2, 3, false, 32>(0x20),  // 128 x 128
+    gemm_row<2, 2, 2, 2, 3, true, 32>(0x21),
+    gemm_row<2, 2, 2, 2, 2, true, 32>(0x22),
+    gemm_row<2, 2, 2, 2, 2, true, 64>(0x23),
+    gemm_row<2, 2, 2, 1, 3, false, 32>(0x30),  // 128 x 64
+    gemm_row<2, 2, 2, 1, 3, true, 32>(0x31),
+    gemm_row<2, 2, 2, 1, 2, true, 32>(0x32),
+    gemm_row<2, 2, 2, 1, 2, true, 64>(0x33),
+    gemm_row<4, 2, 2, 2, 3, true, 32>(0x41),   // 256 x 128 (8 waves), aligned variants only
+    gemm_row<4, 2, 2, 2, 2, true, 32>(0x42),
+    gemm_row<4, 2, 2, 2, 2, true, 64>(0x43),   //   (96 KiB of LDS)
+    gemm_row<1, 4, 2, 1, 3, false, 32>(0x50),  // 64 x 128: small tiles = many resident workgroups for the latency-bound thin-K layers
+    gemm_row<1, 4, 2, 1, 3, true, 32>(0x51),
+    gemm_row<1, 4, 2, 1, 2, true, 32>(0x52),
+    gemm_row<1, 4, 2, 1, 2, true, 64>(0x53),
+    gemm_row<2, 2, 1, 1, 3, false, 32>(0x60),  // 64 x 64, likewise
+    gemm_row<2, 2, 1, 1, 3, true, 32>(0x61),
+    gemm_row<2, 2, 1, 1, 2, true, 32>(0x62),
+    gemm_row<2, 2, 1, 1, 2, true, 64>(0x63),
+    gemm_row<4, 2, 2, 4, 3, true, 32>(0x71),   // 256 x 256 (8 waves, wave tile 64 x 128: half the L2->LDS bytes per FLOP of 128 x 128)
+    gemm_row<4, 2, 2, 4, 2, true, 32>(0x72),
+    gemm_row<4, 2, 2, 4, 2, true, 64>(0x73),   //   (128 KiB of LDS)
+    persist_row<2, 2, 2, 2, 3, 32>(0x81),      // persistent 1x1 kernel (4 compute + 4 store waves, tiles walked per workgroup): 128 x 128
+    persist_row<2, 2, 2, 2, 2, 32>(0x82),
+    persist_row<2, 2, 2, 2, 2, 64>(0x83),
+    persist_row<2, 2, 2, 1, 3, 32>(0x91),      // 128 x 64
+    persist_row<2, 2, 2, 1, 2, 32>(0x92),
+    persist_row<2, 2, 2, 1, 2, 64>(0x93),
+    patch_row<2, 2, 16>(0xA1),                 // patch-based 3x3 stride-1 kernel <NT, STAGES, TW>: 8 x 16 px x 128 couts
+    patch_row<1, 3, 16>(0xB1),                 // 64 couts
+    patch_row<1, 2, 16>(0xB2),
+    patch_row<1, 4, 16>(0xB3),
+    patch_row<2, 2, 20>(0xC1),                 // 6 x 20 px x 128 couts
+    patch_row<1, 3, 20>(0xD1),
+    patch_row<1, 2, 20>(0xD2),
+    patch_row<1, 4, 20>(0xD3),
+    patch_row<1, 3, 16, true>(0xB1),           // + box-branch tail (ConvArgs::tail_wgt: the 1x1 conv and DFL decoder after the 3x3 conv)
+    patch_row<1, 2, 16, true>(0xB2),
+    patch_row<1, 4, 16, true>(0xB3),
+    patch_row<1, 3, 20, true>(0xD1),
+    patch_row<1, 2, 20, true>(0xD2),
+    patch_row<1, 4, 20, true>(0xD3),
+    wres_row<2, 4, 24>(0xE1),                  // weights-resident streaming 1x1 kernel <NT, STAGES, NFR>: 128 px x 128 couts (NFR 32 would spill)
+    wres_row<2, 3, 24>(0xE2),
+    wres_row<1, 4, 32>(0xF1),                  // 128 px x 64 couts
+    wres_row<1, 3, 32>(0xF2),
+};
+
+static const ConvCfg* conv_cfg_row(int cfg, bool tail) {
+    for (const ConvCfg& r : kConvCfgs) if (r.id == (cfg & ~4) && (r.fam == CONV_TAIL) == tail) return &r;
+    return nullptr;
+}
+
 bool conv_cfg_valid(const ConvArgs& a, int cfg) {
-    const int Cin = a.C0 + a.C1, tile = cfg >> 4, var = cfg & 3, kbit = (cfg >> 2) & 3;
-    const int ko = conv_korder(a);
-    if (cfg < 0 || tile > 15 || kbit > 1) return false;
-    // the id's chunk-major bit must say what the layer's shape says (implicit-GEMM tiles; the other kernels have one order each)
-    if (tile < 8 && kbit != (ko ? 1 : 0)) return false;
-    if (tile >= 8 && kbit) return false;
-    if (ko && tile < 8 && var < 1) return false;
-    if (ko == 1 && tile < 8 && var == 3) return false;  // 32-channel chunks: a 64-deep K-step would pair the halves of two chunks
-    if (a.tail_wgt) {  // box-branch tail: the 64-cout patch tiles only (validity of the 3x3 conv itself: the same op without tail / decoder)
-        if (tile != 11 && tile != 13) return false;
-        ConvArgs b = a;
-        b.tail_wgt = nullptr; b.tail_bias = nullptr; b.epi = 0;
-        return a.epi == 3 && a.Cout == 64 && !a.res && conv_cfg_valid(b, cfg);
-    }
-    if (a.epi && tile >= 8) return false;           // fused decoder: implicit-GEMM kernel only
-    if (a.nsl_c * a.nsl_t > 1) {                    // split-K: implicit-GEMM tiles, aligned variants, K-step dividing the channel slices
-        const int cbp = Cin / (a.nsl_c > 0 ? a.nsl_c : 1);
-        if (tile >= 8 || var < 1 || (var == 3 && (cbp & 63)) || (cbp & 31)) return false;
-    }
-    if (tile >= 14) {  // weights-resident streaming 1x1 kernel (14: 128-cout tiles, 15: 64-cout tiles; variant 1: 4-stage pixel ring, 2: 3 stages)
-        const int K = Cin, nt = tile == 14 ? 2 : 1, stages = var == 1 ? 4 : 3;
-        return a.ksize == 1 && a.stride == 1 && (var == 1 || var == 2) && !(Cin & 31) && !(a.C0 & 31) && !a.out_f32 && !a.res && !(a.Cout & 7) &&
-               !(a.ldd & 7) && !((uintptr_t)a.dst & 15) && a.dst_scale <= 1 && nt * (K / 16) <= (nt == 2 ? 24 : 32) && K / 32 >= stages - 1 &&  // (128-cout tiles with 32 fragments spill: not built)
-              
-               (tile == 14 ? a.Cout > 64 : true);
-    }
-    if (a.epi == 3 && tile != 1) return false;      // DFL needs all 64 box couts in one wave: the 256 x 64 tile (4 x 1 waves, NT 2)
-    if (tile >= 12) {  // 6x20-pixel patch tiles
-        ConvArgs b = a;
-        return conv_cfg_valid(b, ((tile - 2) << 4) | var);
-    }
-    if (tile >= 10) {  // patch-based 3x3 stride-1 kernel (TN 128 / 64): sums chunk-major over 32-channel chunks = K walk 1
-        return ko == 1 && (var == 1 || ((var == 2 || var == 3) && tile == 11)) && a.ksize == 3 && a.stride == 1 && a.pad == 1 && !a.C1 && !a.up0 && !(a.C0 & 31) && !a.out_f32 &&
-               !(a.Cout & 7) && !(a.ldd & 7) && !((uintptr_t)a.dst & 15) && a.dst_scale <= 1 &&
-               (!a.res || (!(a.ldr & 7) && !((uintptr_t)a.res & 15))) && (tile == 10 ? a.Cout > 64 : true);
-    }
-    if (tile >= 8) {  // persistent 1x1 kernel with store waves
-        const bool aligned_ = !(Cin & 31) && !(a.C0 & 31), aligned64_ = !(Cin & 63) && !(a.C0 & 63);
-        return a.ksize == 1 && aligned_ && var >= 1 && (var != 3 || aligned64_) && !a.out_f32 && !a.res && !(a.Cout & 7) && a.Cout <= 1024 &&
-               !(a.ldd & 7) && !((uintptr_t)a.dst & 15) && a.dst_scale <= 1 && a.stride == 1;
-    }
-    if (tile == 7 && ((a.Cout & 255) || var < 1)) return false;  // 256x256: whole 256-cout tiles only (variant 3: BK 64, 128 KiB of LDS)
+    const ConvCfg* r = conv_cfg_row(cfg, a.tail_wgt != nullptr);
+    if (!r) return false;
+    const int Cin = a.C0 + a.C1, ko = conv_korder(a), nsl = a.nsl_c * a.nsl_t;
     const bool aligned = !(Cin & 31) && !(a.C0 & 31), aligned64 = !(Cin & 63) && !(a.C0 & 63);
-    if (var >= 1 && !aligned) return false;
-    if (var == 3 && !aligned64) return false;
-    if (tile == 4 && var < 1) return false;  // 8-wave 256 x 128: aligned variants only (3 = BK 64, 96 KiB of LDS)
-    return true;
+    if ((r->aligned && !aligned) || (r->bk == 64 && !aligned64)) return false;
+    if (r->fam == CONV_GEMM) {
+        if (!(cfg & 4) != !ko) return false;  // the id's chunk-major bit must say what the layer's shape says
+        // a chunk-major walk needs aligned operands; on 32-channel chunks a 64-deep K-step would pair the halves of two chunks
+        if (ko && (!r->aligned || (ko == 1 && r->bk == 64))) return false;
+        if (nsl > 1 && (!r->aligned || (Cin / (a.nsl_c > 0 ? a.nsl_c : 1)) % r->bk)) return false;  // split-K: K-steps within a slice
+        if (a.epi == 3 && (r->tm != 256 || r->tn != 64)) return false;  // DFL needs all 64 box couts in one wave
+        return r->tn != 256 || !(a.Cout & 255);                          // whole 256-cout tiles only
+    }
+    // the other kernels: one K walk each (no chunk-major bit), no split-K, no fused decoder but the tail's, fp16 output in 16-byte stores
+    if ((cfg & 4) || nsl > 1 || (r->fam == CONV_TAIL ? (a.epi != 3 || a.Cout != 64 || a.res) : a.epi != 0)) return false;
+    if (a.out_f32 || (a.Cout & 7) || (a.ldd & 7) || ((uintptr_t)a.dst & 15) || a.dst_scale > 1) return false;
+    if (r->fam == CONV_PERSIST || r->fam == CONV_WRES) {  // the streaming 1x1 kernels
+        if (a.ksize != 1 || a.stride != 1 || a.res) return false;
+        if (r->fam == CONV_PERSIST) return a.Cout <= PERSIST_MAX_COUT;  // the bias vector stays in LDS
+        // weights-resident: K fits the row's register fragments and the pixel ring; 128-cout tiles only past 64 couts
+        return (r->tn / 64) * (Cin / 16) <= r->nfr && Cin / 32 >= r->stages - 1 && (r->tn != 128 || a.Cout > 64);
+    }
+    // patch (+ tail): 3x3 stride 1, one source, no upsample; sums chunk-major over 32-channel chunks = K walk 1
+    return ko == 1 && a.ksize == 3 && a.stride == 1 && a.pad == 1 && !a.C1 && !a.up0 && (!a.res || (!(a.ldr & 7) && !((uintptr_t)a.res & 15))) &&
+           (r->tn != 128 || a.Cout > 64);
 }
 
 int conv_candidates(const ConvArgs& a, int* out, int max_out) {
@@ -1788,46 +1844,44 @@ int conv_candidates(const ConvArgs& a, int* out, int max_out) {
     const long long M = (long long)a.B * a.OH * a.OW;
     const int tile = a.epi == 3 ? 1 : (a.Cout > 64 ? 2 : (a.Cout > 32 ? 1 : 0));  // heuristic default: widest cout tile that is not wasted
     const int ko = conv_korder(a), km = ko ? 4 : 0;
+    // 6x20 tiles where they need fewer tiles than 8x16 ones (20 x 20 maps: 4 instead of 6 per image)
+    const bool t20 = ceil_div(a.W, 20) * ceil_div(a.H, 6) < ceil_div(a.W, 16) * ceil_div(a.H, 8);
     int n = 0;
-    auto add = [&](int t, int v) {
-        const int c = (t << 4) | v;
+    auto add = [&](int c) {
         for (int i = 0; i < n; ++i) if (out[i] == c) return;
         if (n < max_out && conv_cfg_valid(a, c)) out[n++] = c;
     };
-    if (a.tail_wgt) {  // 3x3 conv + 1x1 + DFL: the four 64-cout patch configurations
-        if (ceil_div(a.W, 20) * ceil_div(a.H, 6) < ceil_div(a.W, 16) * ceil_div(a.H, 8)) { add(13, 2); add(13, 1); add(13, 3); }
-        add(11, 2); add(11, 1); add(11, 3); add(13, 2); add(13, 1); add(13, 3);
+    if (a.tail_wgt) {  // 3x3 conv + 1x1 + DFL: the 64-cout patch configurations
+        if (t20) { add(0xD2); add(0xD1); add(0xD3); }
+        add(0xB2); add(0xB1); add(0xB3); add(0xD2); add(0xD1); add(0xD3);
         return n;
     }
     if (!aligned) {
-        add(tile, 0);
-        if (a.Cout > 32) { add(3, 0); add(6, 0); }
-        if (a.Cout > 64) add(5, 0);
+        add(tile << 4);
+        if (a.Cout > 32) { add(0x30); add(0x60); }
+        if (a.Cout > 64) add(0x50);
         return n;
     }
     // heuristic first (what an un-tuned plan runs: the r01 measurements' usual winners), then the exhaustive
     // (tile x variant) sweep the autotuner times.  Every candidate of a layer sums in the layer's K walk (conv_cfg_valid).
-    // 6x20 tiles where they need fewer tiles than 8x16 ones (20 x 20 maps: 4 instead of 6 per image)
-    const bool t20 = ceil_div(a.W, 20) * ceil_div(a.H, 6) < ceil_div(a.W, 16) * ceil_div(a.H, 8);
     const bool patch_ok = !getenv("BSY_NO_PATCH");
-    if (!a.epi && a.ksize == 3 && a.stride == 1 && a.H >= 16 && a.W >= 16 && patch_ok) add(t20 ? 13 : 11, 2);  // patch kernel
+    if (!a.epi && a.ksize == 3 && a.stride == 1 && a.H >= 16 && a.W >= 16 && patch_ok) add(t20 ? 0xD2 : 0xB2);  // patch kernel
     const int vbest = (aligned64 && ko != 1) ? 3 : 1;  // 64-deep K-steps where the K walk allows them
-    if (!a.epi && !(a.Cout & 255) && aligned64 && ko != 1 && M >= 16384) add(7, 3 | km);  // 256 x 256, 64-deep K-steps
-    add(tile, vbest | km);
-    static const int tn[10] = {32, 64, 128, 64, 128, 128, 64, 256, 128, 64};
-    for (int t = 0; t < 10; ++t) {
-        if (tn[t] >= 2 * round_up(a.Cout, 32)) continue;      // more than half of the cout tile would be padding
-        if (tn[t] == 32 && a.Cout > 32) continue;               // 32-wide tiles re-read the pixels once per 32 couts
-        if (t == 4 && (a.Cout < 128 || M < 32768)) continue;    // 8-wave 256x128 only for wide, large layers
-        if (t == 7 && M < 16384) continue;
-        if (t >= 8 && (M < 65536 || getenv("BSY_NO_PERSIST"))) continue;                      // persistent tiles need several tiles per workgroup
-        for (int v = 1; v <= 3; ++v) add(t, v | (t < 8 ? km : 0));
+    if (!a.epi && !(a.Cout & 255) && aligned64 && ko != 1 && M >= 16384) add(0x73 | km);  // 256 x 256, 64-deep K-steps
+    add(tile << 4 | vbest | km);
+    for (const ConvCfg& r : kConvCfgs) {
+        if ((r.fam != CONV_GEMM && r.fam != CONV_PERSIST) || !r.aligned) continue;
+        if (r.tn >= 2 * round_up(a.Cout, 32)) continue;                           // more than half of the cout tile would be padding
+        if (r.tn == 32 && a.Cout > 32) continue;                                    // 32-wide tiles re-read the pixels once per 32 couts
+        if (r.tm == 256 && r.tn == 128 && (a.Cout < 128 || M < 32768)) continue;    // 8-wave 256x128 only for wide, large layers
+        if (r.tn == 256 && M < 16384) continue;
+        if (r.fam == CONV_PERSIST && (M < 65536 || getenv("BSY_NO_PERSIST"))) continue;  // persistent tiles need several tiles per workgroup
+        add(r.id | (r.fam == CONV_GEMM ? km : 0));
     }
-    if (a.ksize == 1 && M >= 65536 && !getenv("BSY_NO_WRES")) { add(14, 1); add(14, 2); add(15, 1); add(15, 2); }  // HBM-bound 1x1 layers
-    if (a.H >= 16 && a.W >= 16 && patch_ok) {  // 3x3 s1 patch kernel
-        add(10, 1); add(11, 1); add(11, 2); add(11, 3);
-        if (t20) { add(12, 1); add(13, 1); add(13, 2); add(13, 3); }
-    }
+    if (a.ksize == 1 && M >= 65536 && !getenv("BSY_NO_WRES"))  // HBM-bound 1x1 layers
+        for (const ConvCfg& r : kConvCfgs) if (r.fam == CONV_WRES) add(r.id);
+    if (a.H >= 16 && a.W >= 16 && patch_ok)  // 3x3 s1 patch kernel
+        for (const ConvCfg& r : kConvCfgs) if (r.fam == CONV_PATCH && (r.tw == 16 || t20)) add(r.id);
     return n;
 }
 
@@ -1899,62 +1953,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
         if (conv_candidates(a, list, BSY_CONV_MAX_CFG) <= 0) BSY_FAIL(BSY_ERR_ARG, "conv: no kernel configuration for this shape");
         cfg = list[0];
     }
-    const int tile = cfg >> 4, var = cfg & 3;
     k.korder = conv_korder(a);
-    // tile: 0 = 256x32, 1 = 256x64, 2 = 128x128, 3 = 128x64, 4 = 256x128 (8 waves), 5 = 64x128, 6 = 64x64
-    // var : 0 = generic BK32 S3, 1 = aligned BK32 S3, 2 = aligned BK32 S2, 3 = aligned BK64 S2
-#define BSY_VAR(KS_, WM_, WN_, MT_, NT_)                                                  \
-    do {                                                                                  \
-        if (var == 0) return launch_cfg<KS_, WM_, WN_, MT_, NT_, 3, false, 32>(k, s);     \
-        if (var == 1) return launch_cfg<KS_, WM_, WN_, MT_, NT_, 3, true, 32>(k, s);      \
-        if (var == 2) return launch_cfg<KS_, WM_, WN_, MT_, NT_, 2, true, 32>(k, s);      \
-        return launch_cfg<KS_, WM_, WN_, MT_, NT_, 2, true, 64>(k, s);                    \
-    } while (0)
-#define BSY_TILE(KS_)                                                                     \
-    do {                                                                                  \
-        if (k.tail_wgt && tile == 13 && var == 1) return launch_patch<1, 3, 2, 20, true>(k, s); \
-        if (k.tail_wgt && tile == 13 && var == 3) return launch_patch<1, 4, 2, 20, true>(k, s); \
-        if (k.tail_wgt && tile == 13) return launch_patch<1, 2, 2, 20, true>(k, s);       \
-        if (k.tail_wgt && tile == 11 && var == 1) return launch_patch<1, 3, 2, 16, true>(k, s); \
-        if (k.tail_wgt && tile == 11 && var == 3) return launch_patch<1, 4, 2, 16, true>(k, s); \
-        if (k.tail_wgt) return launch_patch<1, 2, 2, 16, true>(k, s);                     \
-        if (tile >= 14) {                                                                 \
-            const int fr = (tile == 14 ? 2 : 1) * (Cin / 16);                             \
-            if (tile == 14 && var == 1) { if (fr <= 16) return launch_wres<2, 4, 16>(k, s); return launch_wres<2, 4, 24>(k, s); } \
-            if (tile == 14) { if (fr <= 16) return launch_wres<2, 3, 16>(k, s); return launch_wres<2, 3, 24>(k, s); } \
-            if (var == 1) { if (fr <= 16) return launch_wres<1, 4, 16>(k, s); return launch_wres<1, 4, 32>(k, s); } \
-            if (fr <= 16) return launch_wres<1, 3, 16>(k, s);                             \
-            return launch_wres<1, 3, 32>(k, s);                                           \
-        }                                                                                 \
-        if (tile == 12) return launch_patch<2, 2, 2, 20>(k, s);                           \
-        if (tile == 13 && var == 1) return launch_patch<1, 3, 2, 20>(k, s);               \
-        if (tile == 13 && var == 3) return launch_patch<1, 4, 2, 20>(k, s);               \
-        if (tile == 13) return launch_patch<1, 2, 2, 20>(k, s);                           \
-        if (tile == 10) return launch_patch<2, 2, 2>(k, s);                               \
-        if (tile == 11 && var == 1) return launch_patch<1, 3, 2>(k, s);                   \
-        if (tile == 11 && var == 3) return launch_patch<1, 4, 2>(k, s);                   \
-        if (tile == 11) return launch_patch<1, 2, 2>(k, s);                               \
-        if (tile == 8 && var == 1) return launch_persist<2, 2, 2, 2, 3, 32>(k, s);        \
-        if (tile == 8 && var == 2) return launch_persist<2, 2, 2, 2, 2, 32>(k, s);        \
-        if (tile == 8) return launch_persist<2, 2, 2, 2, 2, 64>(k, s);                    \
-        if (tile == 9 && var == 1) return launch_persist<2, 2, 2, 1, 3, 32>(k, s);        \
-        if (tile == 9 && var == 2) return launch_persist<2, 2, 2, 1, 2, 32>(k, s);        \
-        if (tile == 9) return launch_persist<2, 2, 2, 1, 2, 64>(k, s);                    \
-        if (tile == 0) BSY_VAR(KS_, 4, 1, 2, 1);                                          \
-        if (tile == 1) BSY_VAR(KS_, 4, 1, 2, 2);                                          \
-        if (tile == 2) BSY_VAR(KS_, 2, 2, 2, 2);                                          \
-        if (tile == 3) BSY_VAR(KS_, 2, 2, 2, 1);                                          \
-        if (tile == 5) BSY_VAR(KS_, 1, 4, 2, 1);                                          \
-        if (tile == 6) BSY_VAR(KS_, 2, 2, 1, 1);                                          \
-        if (tile == 7 && var == 3) return launch_cfg<KS_, 4, 2, 2, 4, 2, true, 64>(k, s); \
-        if (tile == 7 && var == 1) return launch_cfg<KS_, 4, 2, 2, 4, 3, true, 32>(k, s); \
-        if (tile == 7) return launch_cfg<KS_, 4, 2, 2, 4, 2, true, 32>(k, s);             \
-        if (var == 1) return launch_cfg<KS_, 4, 2, 2, 2, 3, true, 32>(k, s);              \
-        if (var == 3) return launch_cfg<KS_, 4, 2, 2, 2, 2, true, 64>(k, s);              \
-        return launch_cfg<KS_, 4, 2, 2, 2, 2, true, 32>(k, s);                            \
-    } while (0)
-    if (a.ksize == 1) BSY_TILE(1);
-    BSY_TILE(3);
-#undef BSY_TILE
-#undef BSY_VAR
+    const ConvCfg* r = conv_cfg_row(cfg, a.tail_wgt != nullptr);
+    return r->launch[r->fam == CONV_GEMM && a.ksize == 3](k, s);
 }
