@@ -31,8 +31,8 @@ struct BneckK {
     half_t* dst;        // y view
     const half_t *w1, *w2;
     const float *b1, *b2;
-    int B, H, W, lds, ldd, Kpad1, Kpad2, act, tiles_x, tiles_y, ntiles;
-    unsigned magic_x, magic_y;
+    int B, H, W, lds, ldd, Kpad1, Kpad2, act;
+    TileGrid grid;
 };
 
 template <int C, int CH>
@@ -85,12 +85,8 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
     const half_t* rbase = sx + ((ty2 + 2) * BN_XC + tx2 + 2) * XS + 4 * lh;  // residual: the pixel's own input entry
 
     auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const int r = (int)__umulhi((unsigned)tile, p.magic_x);
-        const int tx = tile - r * p.tiles_x;
-        n = (int)__umulhi((unsigned)r, p.magic_y);
-        const int ty = r - n * p.tiles_y;
-        oy0 = ty * BN_TH;
-        ox0 = tx * BN_TW;
+        const TileIdx t = tile_index(p.grid, tile);
+        n = t.n; oy0 = t.ty * BN_TH; ox0 = t.tx * BN_TW;
     };
     half8 pre[NLOAD];
     int nn = 0, noy0 = 0, nox0 = 0;
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
     // Retire the weight / bias loads HERE: left pending, the compiler waits for them at their first use inside the tile
     // loop with vmcnt(0) -- on every iteration, which then also waits for the prefetch issued just before.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.ntiles);  // XCD-aware tile order (common.h)
+    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.grid.ntiles);  // XCD-aware tile order (common.h)
     int tile = tw.tile;
     if (tile < tw.end) fetch(tile);
     for (; tile < tw.end; tile += tw.step) {
@@ -267,12 +263,8 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
     half_t* obase = sout + (pt * 32 + lrow) * LDO + 32 * ct + 4 * lh;
 
     auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const int r = (int)__umulhi((unsigned)tile, p.magic_x);
-        const int tx = tile - r * p.tiles_x;
-        n = (int)__umulhi((unsigned)r, p.magic_y);
-        const int ty = r - n * p.tiles_y;
-        oy0 = ty * BN_TH;
-        ox0 = tx * BN_TW;
+        const TileIdx t = tile_index(p.grid, tile);
+        n = t.n; oy0 = t.ty * BN_TH; ox0 = t.tx * BN_TW;
     };
     half8 pre[NLOAD];
     int nn = 0, noy0 = 0, nox0 = 0;
@@ -288,7 +280,7 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
     };
 
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): retire the weight loads here, not inside the tile loop
-    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.ntiles);  // XCD-aware tile order (common.h)
+    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.grid.ntiles);  // XCD-aware tile order (common.h)
     int tile = tw.tile;
     if (tile < tw.end) fetch(tile);
     for (; tile < tw.end; tile += tw.step) {
@@ -369,21 +361,15 @@ int launch_bneck_fused(const BneckArgs& a, hipStream_t s) {
     BneckK k;
     k.src = a.src; k.dst = a.dst; k.w1 = (const half_t*)a.w1; k.w2 = (const half_t*)a.w2; k.b1 = a.b1; k.b2 = a.b2;
     k.B = a.B; k.H = a.H; k.W = a.W; k.lds = a.lds; k.ldd = a.ldd; k.Kpad1 = a.Kpad1; k.Kpad2 = a.Kpad2; k.act = a.act;
-    k.tiles_x = ceil_div(a.W, BN_TW); k.tiles_y = ceil_div(a.H, BN_TH);
-    if (k.tiles_x < 2) k.tiles_x = 2;  // keep the multiply-high divisions exact (magic for 1 would be 2^32); the extra
-    if (k.tiles_y < 2) k.tiles_y = 2;  // tiles lie outside the map and store nothing
-    const long long nt = (long long)a.B * k.tiles_x * k.tiles_y;
-    if (nt * (k.tiles_x > k.tiles_y ? k.tiles_x : k.tiles_y) >= (1LL << 32)) BSY_FAIL(BSY_ERR_ARG, "bottleneck: tile count out of range");
-    k.ntiles = (int)nt;
-    k.magic_x = (unsigned)(((1ULL << 32) + k.tiles_x - 1) / k.tiles_x);
-    k.magic_y = (unsigned)(((1ULL << 32) + k.tiles_y - 1) / k.tiles_y);
+    const int rc = make_tile_grid(k.grid, a.B, a.H, a.W, BN_TH, BN_TW, "bottleneck");
+    if (rc != BSY_OK) return rc;
     if (a.C == 64) {
-        const int grid = k.ntiles < 256 ? k.ntiles : 256;  // one 512-thread workgroup (143 KiB of LDS) per CU
+        const int grid = k.grid.ntiles < 256 ? k.grid.ntiles : 256;  // one 512-thread workgroup (143 KiB of LDS) per CU
         hipLaunchKernelGGL((bneck_fused_wide_kernel<64, 32>), dim3(grid), dim3(512), 0, s, k);
         HIP_TRY(hipGetLastError());
         return BSY_OK;
     }
-    const int grid = k.ntiles < 768 ? k.ntiles : 768;  // 3 workgroups per CU
+    const int grid = k.grid.ntiles < 768 ? k.grid.ntiles : 768;  // 3 workgroups per CU
     hipLaunchKernelGGL((bneck_fused_kernel<32, 16>), dim3(grid), dim3(256), 0, s, k);
     HIP_TRY(hipGetLastError());
     return BSY_OK;

@@ -12,24 +12,6 @@
 // percent of the BS-YOLO forward; the kernels are written for clarity and coalescing, not tuned.
 #include "common.h"
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t bo_rsrc_t;
-__device__ __forceinline__ bo_rsrc_t bo_make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ half8 bo_load16(bo_rsrc_t r, unsigned voff) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 u; half8 h; } v;
-    v.u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0);
-    return v.h;
-}
-#else
-typedef int bo_rsrc_t;
-__device__ __forceinline__ bo_rsrc_t bo_make_rsrc(const void*, unsigned) { return 0; }
-__device__ __forceinline__ half8 bo_load16(bo_rsrc_t, unsigned) { return half8{0, 0, 0, 0, 0, 0, 0, 0}; }
-#endif
-#define BO_OOB 0xFFFFFFF0u
-
 // ---------------------------------------------------------------------------------------------------------------------
 // depthwise kh x kw, stride s, pad (kh/2, kw/2).  thread = (image, output pixel, 8-channel chunk); weights f32
 // [kh*kw][wld] (wld = channels of the whole weight tensor: a launch may cover a channel sub-range of it).
@@ -49,7 +31,7 @@ __global__ __launch_bounds__(256) void dwconv_generic_kernel(const half_t* __res
     t /= OW;
     const int oy = (int)(t % OH);
     const int n = (int)(t / OH);
-    const bo_rsrc_t rs = bo_make_rsrc(src, span);
+    const bsy_rsrc_t rs = make_rsrc(src, span);
     float acc[8];
     {
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + c), b1 = *reinterpret_cast<const f32x4*>(bias + c + 4);
@@ -63,8 +45,8 @@ __global__ __launch_bounds__(256) void dwconv_generic_kernel(const half_t* __res
         for (int dx = 0; dx < kw; ++dx) {
             const int ix = ix0 + dx;
             const unsigned off = (rowok && (unsigned)ix < (unsigned)W)
-                                     ? 2u * ((unsigned)((n * H + iy) * W + ix) * (unsigned)lds_ + (unsigned)c) : BO_OOB;
-            const half8 v = bo_load16(rs, off);
+                                     ? 2u * ((unsigned)((n * H + iy) * W + ix) * (unsigned)lds_ + (unsigned)c) : BSY_OOB;
+            const half8 v = buf_load16<half8>(rs, off);
             const float* wp = w + (size_t)(dy * kw + dx) * wld + c;
             const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp), w1 = *reinterpret_cast<const f32x4*>(wp + 4);
             fma_mix8(acc, v, w0, w1);  // v_fma_mix_f32 per element (common.h)
@@ -96,7 +78,7 @@ __global__ __launch_bounds__(256) void dwconv_win_kernel(const half_t* __restric
     t /= OWG;
     const int oy = (int)(t % OH);
     const int n = (int)(t / OH);
-    const bo_rsrc_t rs = bo_make_rsrc(src, span);
+    const bsy_rsrc_t rs = make_rsrc(src, span);
     float acc[DWG_PX][8];
     {
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + c), b1 = *reinterpret_cast<const f32x4*>(bias + c + 4);
@@ -110,7 +92,7 @@ __global__ __launch_bounds__(256) void dwconv_win_kernel(const half_t* __restric
 #pragma unroll
     for (int q = 0; q < NWIN; ++q) {
         const int ix = ix0 + q;
-        coloff[q] = (unsigned)ix < (unsigned)W ? 2u * ((unsigned)ix * (unsigned)lds_ + (unsigned)c) : BO_OOB;
+        coloff[q] = (unsigned)ix < (unsigned)W ? 2u * ((unsigned)ix * (unsigned)lds_ + (unsigned)c) : BSY_OOB;
     }
     const unsigned rowbytes = 2u * (unsigned)W * (unsigned)lds_;
     for (int dy = 0; dy < kh; ++dy) {
@@ -119,7 +101,7 @@ __global__ __launch_bounds__(256) void dwconv_win_kernel(const half_t* __restric
         const unsigned rb = (unsigned)(n * H + iy) * rowbytes;
         half8 win[NWIN];
 #pragma unroll
-        for (int q = 0; q < NWIN; ++q) win[q] = bo_load16(rs, (rowok && coloff[q] != BO_OOB) ? rb + coloff[q] : BO_OOB);
+        for (int q = 0; q < NWIN; ++q) win[q] = buf_load16<half8>(rs, (rowok && coloff[q] != BSY_OOB) ? rb + coloff[q] : BSY_OOB);
 #pragma unroll
         for (int dx = 0; dx < KW; ++dx) {
             const float* wp = w + (size_t)(dy * KW + dx) * wld + c;
@@ -169,7 +151,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const half_t* __restri
     const int c0 = cg * NCH * 8;                     // first channel of this workgroup
     const int nch = min(NCH, (C - c0) >> 3);         // chunks that exist (the last channel group may be narrower)
     const int oy0 = ty * DWT_TH, ox0 = tx * TW;
-    const bo_rsrc_t rs = bo_make_rsrc(src, span);
+    const bsy_rsrc_t rs = make_rsrc(src, span);
     for (int i = tid; i < (K * K + 1) * NCH * 8; i += 256) {
         const int row = i / (NCH * 8), c = i - row * (NCH * 8);
         sw[i] = c < nch * 8 ? (row < K * K ? w[(size_t)row * wld + c0 + c] : bias[c0 + c]) : 0.f;
@@ -178,7 +160,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const half_t* __restri
         const int ch = i % NCH, px = (i / NCH) % PW, py = i / (NCH * PW);
         const int y = oy0 - K / 2 + py, x = ox0 - K / 2 + px;
         const bool ok = ch < nch && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-        const half8 v = bo_load16(rs, ok ? 2u * ((unsigned)((n * H + y) * W + x) * (unsigned)lds_ + (unsigned)(c0 + ch * 8)) : BO_OOB);
+        const half8 v = buf_load16<half8>(rs, ok ? 2u * ((unsigned)((n * H + y) * W + x) * (unsigned)lds_ + (unsigned)(c0 + ch * 8)) : BSY_OOB);
         *reinterpret_cast<half8*>(sp + (py * PW + px) * PXS + ch * 8) = v;
     }
     if (ident_c0 > 0) {
@@ -641,7 +623,7 @@ __global__ __launch_bounds__(256) void msca_mix_kernel(const MixK k, int B, int 
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float sg = 1.0f / (1.0f + __expf(-k.lg[i][(size_t)n * k.ldl[i] + c + j]));
+            const float sg = sigmoid_f(k.lg[i][(size_t)n * k.ldl[i] + c + j]);
             w[i][j] = __expf(sg);  // sigmoid output is in (0, 1): no max subtraction needed
             den[j] += w[i][j];
         }
@@ -788,7 +770,7 @@ __global__ __launch_bounds__(256) void ela_gate_kernel(float* __restrict__ scrat
     for (int i = tid; i < L * gsz; i += 256) {
         const int l = i / gsz, c = c0 + (i - l * gsz);
         const float z = (sv[i] - mu) * rstd * gnw[c] + gnb[c];
-        gate[(size_t)l * C + c] = 1.0f / (1.0f + __expf(-z));
+        gate[(size_t)l * C + c] = sigmoid_f(z);
     }
     if (dir == 0) {  // channel gate: the Conv1d sees a length-1 sequence -> only its centre tap contributes
         // global mean = mean of the row means (rows have equal length).  Round 3: the sum over the rows is dealt to 256 / gsz slots per
@@ -806,7 +788,7 @@ __global__ __launch_bounds__(256) void ela_gate_kernel(float* __restrict__ scrat
             float gmv = 0.f;
             for (int q = 0; q < nsl; ++q) gmv += sv[q * gsz + tid];
             gmv /= (float)H;
-            base[(size_t)(2 * (H + W) + 1) * C + c] = 1.0f / (1.0f + __expf(-(wch[(size_t)c * k + (k - 1) / 2] * gmv)));
+            base[(size_t)(2 * (H + W) + 1) * C + c] = sigmoid_f(wch[(size_t)c * k + (k - 1) / 2] * gmv);
         }
     }
 }

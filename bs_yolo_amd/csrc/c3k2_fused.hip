@@ -35,8 +35,8 @@ struct C3k2K {
     half_t* dst;
     const half_t *w1, *wa, *wb, *w4;  // packed [CoutPad][Kpad] (cv1, m.cv1, m.cv2, cv2)
     const float *b1, *ba, *bb, *b4;
-    int B, H, W, lds, ldd, K1, Ka, Kb, K4, tiles_x, tiles_y, ntiles;
-    unsigned magic_x, magic_y;
+    int B, H, W, lds, ldd, K1, Ka, Kb, K4;
+    TileGrid grid;
 };
 
 // 4 waves, THREE workgroups per CU (48 KiB of LDS each, round 3; two of 71 KiB before).  The block's SiLU evaluations (38 k per 128
@@ -105,12 +105,8 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
 
     // Tile-independent lane constants: nothing that depends only on the lane is recomputed per tile.
     auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const int r = (int)__umulhi((unsigned)tile, p.magic_x);
-        const int tx = tile - r * p.tiles_x;
-        n = (int)__umulhi((unsigned)r, p.magic_y);
-        const int ty = r - n * p.tiles_y;
-        oy0 = ty * CK_TH;
-        ox0 = tx * CK_TW;
+        const TileIdx t = tile_index(p.grid, tile);
+        n = t.n; oy0 = t.ty * CK_TH; ox0 = t.tx * CK_TW;
     };
     // S1 jobs of this wave (compile-time job list per wave, lane-constant entries): job A = y1 on patch pixel tile `wave`;
     // job B = y1 on pixel tile 4 (wave 0) or y0 on output pixel tile wave - 1 (waves 1, 2); wave 3 has no job B
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
     const int a1off = (lrow & (CH - 1)) * WAS + 8 * lh;
 
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): retire the weight loads here, not inside the tile loop (bneck_fused.hip)
-    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.ntiles);  // XCD-aware tile order (common.h)
+    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.grid.ntiles);  // XCD-aware tile order (common.h)
     int tile = tw.tile;
     if (tile < tw.end) fetch(tile);
     __syncthreads();  // weights and biases visible
@@ -301,15 +297,9 @@ int launch_c3k2_fused(const C3k2Args& a, hipStream_t s) {
     bsy_conv_packed_dims(a.C / 2, a.C, 3, &cp, &k.Ka);
     bsy_conv_packed_dims(a.C, a.C / 2, 3, &cp, &k.Kb);
     bsy_conv_packed_dims(a.C2, 3 * a.C, 1, &cp, &k.K4);
-    k.tiles_x = ceil_div(a.W, CK_TW); k.tiles_y = ceil_div(a.H, CK_TH);
-    if (k.tiles_x < 2) k.tiles_x = 2;  // keep the multiply-high divisions exact; the extra tiles lie outside the map
-    if (k.tiles_y < 2) k.tiles_y = 2;
-    const long long nt = (long long)a.B * k.tiles_x * k.tiles_y;
-    if (nt * (k.tiles_x > k.tiles_y ? k.tiles_x : k.tiles_y) >= (1LL << 32)) BSY_FAIL(BSY_ERR_ARG, "c3k2: tile count out of range");
-    k.ntiles = (int)nt;
-    k.magic_x = (unsigned)(((1ULL << 32) + k.tiles_x - 1) / k.tiles_x);
-    k.magic_y = (unsigned)(((1ULL << 32) + k.tiles_y - 1) / k.tiles_y);
-    const int grid = k.ntiles < 768 ? k.ntiles : 768;  // three 256-thread workgroups (48 KiB of LDS each) per CU
+    const int rc = make_tile_grid(k.grid, a.B, a.H, a.W, CK_TH, CK_TW, "c3k2");
+    if (rc != BSY_OK) return rc;
+    const int grid = k.grid.ntiles < 768 ? k.grid.ntiles : 768;  // three 256-thread workgroups (48 KiB of LDS each) per CU
     hipLaunchKernelGGL((c3k2_fused_kernel<64, 32, 128>), dim3(grid), dim3(256), 0, s, k);
     HIP_TRY(hipGetLastError());
     return BSY_OK;

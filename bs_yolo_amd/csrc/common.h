@@ -354,6 +354,34 @@ __device__ __forceinline__ void fma_mix8(float (&a)[8], const half8& v, const f3
     a[6] = fma_mix_lo(x.u[3], w1[2], a[6]); a[7] = fma_mix_hi(x.u[3], w1[3], a[7]);
 }
 
+// Loads through a buffer descriptor (round 3): a lane whose voffset is out of range (>= num_records = `bytes`) receives ZEROS, so
+// padding taps, pixels past the map, couts past Cout and K tails need neither a branch around the load nor a zero-initialised
+// destination, and the address is a 32-bit offset instead of a 64-bit pointer per lane.  The host pass only needs the launch stubs.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __amdgpu_buffer_rsrc_t bsy_rsrc_t;
+__device__ __forceinline__ bsy_rsrc_t make_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
+}
+// 16 bytes at base + voff as T (half8, f32x4)
+template <typename T>
+__device__ __forceinline__ T buf_load16(bsy_rsrc_t r, unsigned voff) {
+    static_assert(sizeof(T) == 16, "buf_load16: 16-byte type");
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    union { u32x4 u; T t; } v;
+    v.u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0);
+    return v.t;
+}
+#else
+typedef int bsy_rsrc_t;
+__device__ __forceinline__ bsy_rsrc_t make_rsrc(const void*, unsigned) { return 0; }
+template <typename T>
+__device__ __forceinline__ T buf_load16(bsy_rsrc_t, unsigned) { return T{}; }
+#endif
+// voffsets out of range for every descriptor (num_records < 2^32 - 32): BSY_OOB for a single 16-byte read, BSY_OOB_PAIR for a
+// 32-byte piece read as two halves at voff and voff + 16 (the second half stays out of range)
+#define BSY_OOB 0xFFFFFFF0u
+#define BSY_OOB_PAIR 0xFFFFFFE0u
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for vmcnt(0) -- every global load and STORE the
 // wave has in flight -- so in a persistent tile loop each barrier after a prefetch or behind the tile's output stores exposed a
 // full HBM round trip (round 3, SQ counters of the fused kernels: 44-60 % of the wave cycles spent waiting).  Registers filled
@@ -362,6 +390,13 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+}
+
+// XCD-aware, bijective block remap: blocks that share an XCD (bid % 8) get consecutive logical tiles, so the cout tiles of one
+// pixel tile re-read the pixel operand from that XCD's L2.
+__device__ __forceinline__ int xcd_remap(int bid, int nb) {
+    const int q = nb >> 3, r = nb & 7, x = bid & 7;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
 
 // Tile walk of a persistent workgroup, XCD-aware.  Workgroup b of a grid of G lands on XCD b % 8 (round-robin dispatch): with the
@@ -381,6 +416,39 @@ __device__ __forceinline__ TileWalk xcd_tile_walk(int b, int G, int ntiles) {
     return TileWalk{start + i, gx, start + q + (x < r ? 1 : 0)};
 }
 
+// Tile grid of a persistent fused kernel: B images x tiles_y x tiles_x tiles, tile index = (n * tiles_y + ty) * tiles_x + tx.  The
+// kernel divides by multiply-high with host-made magics; a kernel-argument struct holds these five fields last, in this order.
+struct TileGrid {
+    int tiles_x, tiles_y, ntiles;
+    unsigned magic_x, magic_y;  // ceil(2^32 / tiles_x), ceil(2^32 / tiles_y): exact quotients for tile < 2^32 / divisor
+};
+// Grid of th x tw tiles over B images of H x W (H, W positive).  Each side is padded to at least two tiles, as the magic for
+// divisor 1 would be 2^32; the extra tiles lie outside the map and store nothing.
+static inline int make_tile_grid(TileGrid& g, int B, int H, int W, int th, int tw, const char* who) {
+    g.tiles_x = ceil_div(W, tw);
+    g.tiles_y = ceil_div(H, th);
+    if (g.tiles_x < 2) g.tiles_x = 2;
+    if (g.tiles_y < 2) g.tiles_y = 2;
+    const long long nt = (long long)B * g.tiles_x * g.tiles_y;
+    if (nt <= 0 || nt * (g.tiles_x > g.tiles_y ? g.tiles_x : g.tiles_y) >= (1LL << 32))
+        BSY_FAIL(BSY_ERR_ARG, "%s: tile count out of range", who);
+    g.ntiles = (int)nt;
+    g.magic_x = (unsigned)(((1ULL << 32) + g.tiles_x - 1) / g.tiles_x);
+    g.magic_y = (unsigned)(((1ULL << 32) + g.tiles_y - 1) / g.tiles_y);
+    return BSY_OK;
+}
+struct TileIdx {
+    int n, ty, tx;
+};
+__device__ __forceinline__ TileIdx tile_index(const TileGrid& g, int tile) {
+    TileIdx t;
+    const int r = (int)__umulhi((unsigned)tile, g.magic_x);
+    t.tx = tile - r * g.tiles_x;
+    t.n = (int)__umulhi((unsigned)r, g.magic_y);
+    t.ty = r - t.n * g.tiles_y;
+    return t;
+}
+
 // An MFMA accumulator tile (32 couts x 32 pixels, lane = pixel) that STARTS at the bias of its rows (round 3: every conv kernel of the
 // fp16 path accumulates bias + sum instead of adding the bias in its epilogue -- one VALU instruction less per activation in
 // kernels whose SIMDs are ~80 % busy issuing SiLU; all kernels do it alike, so fused and un-fused launches still agree bit for bit).
@@ -397,12 +465,16 @@ __device__ __forceinline__ void acc_bias(f32x16& acc, const float* bias, int lh)
 
 // SiLU in fp32: x * sigmoid(x) = x / (1 + 2^(-x*log2 e)); v_exp_f32 + v_rcp_f32 (1 ulp each) -- the result is rounded
 // to fp16 right after, so the IEEE-division expansion (~10 VALU) would buy nothing.  exp2 overflow -> inf -> rcp -> 0.
-// The product passes through an empty asm: where a conversion to f16 follows directly, the compiler otherwise folds the final
-// multiply and the conversion into v_fma_mixlo/hi_f16 -- ONE rounding of the exact product -- in some kernels and not in others
-// (it did in c3k2_fused.hip's Bottleneck stage, not in bneck_fused.hip: 2 pixels in 1000 differed by one f16 ulp).  Every
-// kernel rounds twice (f32, then f16), so fused and unfused launches agree bit for bit.
+__device__ __forceinline__ float silu_rcp(float x) {
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+}
+// The fp16 path's SiLU: the product passes through an empty asm.  Where a conversion to f16 follows directly, the compiler
+// otherwise folds the final multiply and the conversion into v_fma_mixlo/hi_f16 -- ONE rounding of the exact product -- in some
+// kernels and not in others (it did in c3k2_fused.hip's Bottleneck stage, not in bneck_fused.hip: 2 pixels in 1000 differed by
+// one f16 ulp).  Every kernel rounds twice (f32, then f16), so fused and unfused launches agree bit for bit.  Kernels that keep
+// the result in f32 (conv32x_mfma.hip) call silu_rcp: there the asm only costs, turning `act ? silu(t) : t` into branches.
 __device__ __forceinline__ float silu_f(float x) {
-    float r = x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+    float r = silu_rcp(x);
     asm("" : "+v"(r));
     return r;
 }
@@ -422,3 +494,8 @@ __device__ __forceinline__ f32x4 silu4_f(f32x4 x) {
     for (int i = 0; i < 4; ++i) r[i] = silu_f(x[i]);
     return r;
 }
+// SiLU of the exact fp32 mode (ref32.hip, conv32_mfma.hip): the scalar and the MFMA kernels return the same bits only while both
+// evaluate this the same way, so every user is built with -ffp-contract=off -fno-vectorize (build.py).
+__device__ __forceinline__ float silu32(float x) { return x / (1.0f + expf(-x)); }
+// Sigmoid of the fp16 path's gates and of the Detect decoders (the fused head epilogues of conv_mfma.hip and detect.hip must agree)
+__device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + __expf(-v)); }

@@ -23,28 +23,9 @@
 #include "common.h"
 
 namespace {
-__device__ __forceinline__ float silu32m(float x) { return x / (1.0f + expf(-x)); }  // = ref32.hip silu32
-
 // Staging loads go through buffer descriptors (round 3): an offset past the view's range returns zeros, so padding taps, pixels
 // past M, couts past Cout and the K tail need neither a branch around the load nor a zero-initialised destination -- the K-step's
 // address arithmetic (32-bit offsets, no per-step division) shrank from ~150 to ~60 VALU instructions.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t c32_rsrc_t;
-__device__ __forceinline__ c32_rsrc_t c32_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 c32_load(c32_rsrc_t r, unsigned voff) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 u; f32x4 f; } v;
-    v.u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0);
-    return v.f;
-}
-#else
-typedef int c32_rsrc_t;
-__device__ __forceinline__ c32_rsrc_t c32_rsrc(const void*, unsigned) { return 0; }
-__device__ __forceinline__ f32x4 c32_load(c32_rsrc_t, unsigned) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-#endif
-#define C32_OOB 0xFFFFFFE0u  // (+16 for the second half of a piece stays out of range)
 
 // FIRST: the image conv (BCHW image, f16 or f32, 3 channels).  Every tap is widened to 4 k values (3 real channels + 1 zero, in
 // the pixel operand AND in the weight rows fetched for them; an 8-k piece = two taps), so K = 8 ceil(k^2 / 2) and the real products
@@ -92,8 +73,8 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void conv32_mfma_kernel(const
     int tap = 0, c8 = gq, tkh = 0, tkw = 0;  // this thread's 8-channel piece of the current K-step: k = (tap = (tkh, tkw), 8 c8 ..)
     while (c8 >= Cin8) { c8 -= Cin8; ++tap; if (++tkw == a.ks) { tkw = 0; ++tkh; } }
     const int H0 = a.H >> a.up0, W0 = a.W >> a.up0, H1 = a.H >> a.up1, W1 = a.W >> a.up1;
-    const c32_rsrc_t rs0 = c32_rsrc(a.src0, FIRST ? 0u : (unsigned)((((long long)a.B * H0 * W0 - 1) * a.ld0 + a.C0) * 4));
-    const c32_rsrc_t rsw = c32_rsrc(a.w, (unsigned)((long long)(FIRST ? a.ks * a.ks * 3 : K) * a.Cout * 4));
+    const bsy_rsrc_t rs0 = make_rsrc(a.src0, FIRST ? 0u : (unsigned)((((long long)a.B * H0 * W0 - 1) * a.ld0 + a.C0) * 4));
+    const bsy_rsrc_t rsw = make_rsrc(a.w, (unsigned)((long long)(FIRST ? a.ks * a.ks * 3 : K) * a.Cout * 4));
 
     f32x4 pv[2][2], wv[WPT];
     auto load_step = [&](int kt) {
@@ -130,9 +111,9 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void conv32_mfma_kernel(const
                         pv[it][1] = *reinterpret_cast<const f32x4*>(p + 4);
                     }
                 } else {
-                    const unsigned o0 = ok ? 4u * ((unsigned)((pn[it] * H0 + (iy >> a.up0)) * W0 + (ix >> a.up0)) * (unsigned)a.ld0 + (unsigned)c) : C32_OOB;
-                    pv[it][0] = c32_load(rs0, o0);
-                    pv[it][1] = c32_load(rs0, o0 + 16u);
+                    const unsigned o0 = ok ? 4u * ((unsigned)((pn[it] * H0 + (iy >> a.up0)) * W0 + (ix >> a.up0)) * (unsigned)a.ld0 + (unsigned)c) : BSY_OOB_PAIR;
+                    pv[it][0] = buf_load16<f32x4>(rs0, o0);
+                    pv[it][1] = buf_load16<f32x4>(rs0, o0 + 16u);
                 }
             }
         }
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void conv32_mfma_kernel(const
                 if (k < K && (k & 3) < 3 && (k >> 2) < a.ks * a.ks && n0 + col < a.Cout)
                     wv[j] = *reinterpret_cast<const f32x4*>(a.w + (size_t)((k >> 2) * 3 + (k & 3)) * a.Cout + n0 + col);
             } else {
-                wv[j] = c32_load(rsw, (k < K && n0 + col < a.Cout) ? 4u * ((unsigned)k * (unsigned)a.Cout + (unsigned)(n0 + col)) : C32_OOB);
+                wv[j] = buf_load16<f32x4>(rsw, (k < K && n0 + col < a.Cout) ? 4u * ((unsigned)k * (unsigned)a.Cout + (unsigned)(n0 + col)) : BSY_OOB_PAIR);
             }
         }
         c8 += 4;
@@ -225,7 +206,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void conv32_mfma_kernel(const
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu32m(t) : t;
+                    v[e] = a.act ? silu32(t) : t;
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);

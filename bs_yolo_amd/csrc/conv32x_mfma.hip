@@ -25,24 +25,6 @@
 #include "common.h"
 
 namespace {
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t cx_rsrc_t;
-__device__ __forceinline__ cx_rsrc_t cx_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 cx_load(cx_rsrc_t r, unsigned voff) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 u; f32x4 f; } v;
-    v.u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0);
-    return v.f;
-}
-#else
-typedef int cx_rsrc_t;
-__device__ __forceinline__ cx_rsrc_t cx_rsrc(const void*, unsigned) { return 0; }
-__device__ __forceinline__ f32x4 cx_load(cx_rsrc_t, unsigned) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-#endif
-#define CX_OOB 0xFFFFFFE0u
-
 typedef __fp16 pk2_t __attribute__((ext_vector_type(2)));
 union H8 {
     half8 h;
@@ -60,8 +42,6 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, H8& hi, H
         lo.p[j] = __builtin_amdgcn_cvt_pkrtz(r0, r1);
     }
 }
-
-__device__ __forceinline__ float silu_x(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 
 // Epilogue of one 32-pixel block of a wave's accumulator tiles (lane = pixel, registers = couts) through a WAVE-PRIVATE LDS tile
 // [32 pixels][NT * 32 + 4] floats: each lane parks its pixel's activated couts, then the wave reads the tile back row-wise, so that a
@@ -84,7 +64,7 @@ __device__ __forceinline__ void epilogue_block(f32x16 (&acc)[NT][PB], const int 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float t = acc[an][b][4 * q + e];
-                v[e] = a.act ? silu_x(t) : t;
+                v[e] = a.act ? silu_rcp(t) : t;
             }
             *reinterpret_cast<f32x4*>(wl + lj * RS + an * 32 + 8 * q + 4 * lh) = v;
         }
@@ -145,9 +125,9 @@ __global__ __launch_bounds__(256, 2) void conv32x_mfma_kernel(const Conv32Args a
     int tap = 0, c8 = gq, tkh = 0, tkw = 0;
     while (c8 >= Cin8) { c8 -= Cin8; ++tap; if (++tkw == a.ks) { tkw = 0; ++tkh; } }
     const int H0 = a.H >> a.up0, W0 = a.W >> a.up0, H1 = a.H >> a.up1, W1 = a.W >> a.up1;
-    const cx_rsrc_t rs0 = cx_rsrc(a.src0, (unsigned)((((long long)a.B * H0 * W0 - 1) * a.ld0 + a.C0) * 4));
+    const bsy_rsrc_t rs0 = make_rsrc(a.src0, (unsigned)((((long long)a.B * H0 * W0 - 1) * a.ld0 + a.C0) * 4));
     const unsigned plane_bytes = (unsigned)a.Cout * (unsigned)a.wx_kpad * 2u;
-    const cx_rsrc_t rwh = cx_rsrc(a.wx_hi, plane_bytes), rwl = cx_rsrc(a.wx_lo, plane_bytes);
+    const bsy_rsrc_t rwh = make_rsrc(a.wx_hi, plane_bytes), rwl = make_rsrc(a.wx_lo, plane_bytes);
 
     f32x4 pv[2][2], wvh[WPT], wvl[WPT];
     auto load_step = [&](int kt) {
@@ -168,9 +148,9 @@ __global__ __launch_bounds__(256, 2) void conv32x_mfma_kernel(const Conv32Args a
                     pv[it][1] = *reinterpret_cast<const f32x4*>(p + 4);
                 }
             } else {
-                const unsigned o0 = ok ? 4u * ((unsigned)((pn[it] * H0 + (iy >> a.up0)) * W0 + (ix >> a.up0)) * (unsigned)a.ld0 + (unsigned)c) : CX_OOB;
-                pv[it][0] = cx_load(rs0, o0);
-                pv[it][1] = cx_load(rs0, o0 + 16u);
+                const unsigned o0 = ok ? 4u * ((unsigned)((pn[it] * H0 + (iy >> a.up0)) * W0 + (ix >> a.up0)) * (unsigned)a.ld0 + (unsigned)c) : BSY_OOB_PAIR;
+                pv[it][0] = buf_load16<f32x4>(rs0, o0);
+                pv[it][1] = buf_load16<f32x4>(rs0, o0 + 16u);
             }
         }
 #pragma unroll
@@ -178,9 +158,9 @@ __global__ __launch_bounds__(256, 2) void conv32x_mfma_kernel(const Conv32Args a
             const int id = tid + 256 * j;
             const int row = id >> 2, q = id & 3;  // cout row of the tile, 8-k piece of the K-step
             const bool ok = (WPIECES >= 256 || id < WPIECES) && n0 + row < a.Cout;  // k < Kpad always: the planes are padded to 32
-            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)(kt * BK + 8 * q)) : CX_OOB;
-            wvh[j] = cx_load(rwh, off);
-            wvl[j] = cx_load(rwl, off);
+            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)(kt * BK + 8 * q)) : BSY_OOB_PAIR;
+            wvh[j] = buf_load16<f32x4>(rwh, off);
+            wvl[j] = buf_load16<f32x4>(rwl, off);
         }
         c8 += 4;
         while (c8 >= Cin8) { c8 -= Cin8; ++tap; if (++tkw == a.ks) { tkw = 0; ++tkh; } }
@@ -277,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void conv32x_mfma_kernel(const Conv32Args a
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu_x(t) : t;
+                    v[e] = a.act ? silu_rcp(t) : t;
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);
@@ -312,10 +292,7 @@ __global__ __launch_bounds__(512, 2) void conv32x_big_kernel(const Conv32Args a,
     const int wm = wave / WN, wn = wave % WN;
     const int prow0 = wm * (TM / WM);
     const int lj = lane & 31, lh = lane >> 5;
-    // XCD-aware remap (conv_mfma.hip xcd_remap): blocks that share an XCD take consecutive tiles, so the cout tiles of one pixel tile
-    // read the pixels from that XCD's L2
-    const int nb = gridDim.x, bq = nb >> 3, br = nb & 7, bx = blockIdx.x & 7;
-    const int wg = (bx < br ? bx * (bq + 1) : br * (bq + 1) + (bx - br) * bq) + (blockIdx.x >> 3);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);  // XCD-aware (common.h)
     const int tn_idx = wg % ntn, tm_idx = wg / ntn;
     const int m0 = tm_idx * TM, n0 = tn_idx * TN;
     const int Cin = a.C0 + a.C1, Cin8 = Cin >> 3;
@@ -339,10 +316,10 @@ __global__ __launch_bounds__(512, 2) void conv32x_big_kernel(const Conv32Args a,
     int tap = 0, c8 = gq, tkh = 0, tkw = 0;
     while (c8 >= Cin8) { c8 -= Cin8; ++tap; if (++tkw == a.ks) { tkw = 0; ++tkh; } }
     const int H0 = a.H >> a.up0, W0 = a.W >> a.up0, H1 = a.H >> a.up1, W1 = a.W >> a.up1;
-    const cx_rsrc_t rs0 = cx_rsrc(a.src0, (unsigned)((((long long)a.B * H0 * W0 - 1) * a.ld0 + a.C0) * 4));
-    const cx_rsrc_t rs1 = cx_rsrc(a.C1 ? a.src1 : a.src0, a.C1 ? (unsigned)((((long long)a.B * H1 * W1 - 1) * a.ld1 + a.C1) * 4) : 0u);
+    const bsy_rsrc_t rs0 = make_rsrc(a.src0, (unsigned)((((long long)a.B * H0 * W0 - 1) * a.ld0 + a.C0) * 4));
+    const bsy_rsrc_t rs1 = make_rsrc(a.C1 ? a.src1 : a.src0, a.C1 ? (unsigned)((((long long)a.B * H1 * W1 - 1) * a.ld1 + a.C1) * 4) : 0u);
     const unsigned plane_bytes = (unsigned)a.Cout * (unsigned)a.wx_kpad * 2u;
-    const cx_rsrc_t rwh = cx_rsrc(a.wx_hi, plane_bytes), rwl = cx_rsrc(a.wx_lo, plane_bytes);
+    const bsy_rsrc_t rwh = make_rsrc(a.wx_hi, plane_bytes), rwl = make_rsrc(a.wx_lo, plane_bytes);
 
     f32x4 pv[PPT][2], wvh[WPTR], wvl[WPTR];
     auto load_step = [&](int kt) {
@@ -353,12 +330,12 @@ __global__ __launch_bounds__(512, 2) void conv32x_big_kernel(const Conv32Args a,
             const int iy = piy[it] + tkh, ix = pix_[it] + tkw;
             const bool ok = kvalid && pok[it] && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
             // two concat operands: the piece's source differs from lane to lane -> one load from each descriptor, the other out of range
-            const unsigned o0 = (ok && !s1) ? 4u * ((unsigned)((pn[it] * H0 + (iy >> a.up0)) * W0 + (ix >> a.up0)) * (unsigned)a.ld0 + (unsigned)c) : CX_OOB;
-            pv[it][0] = cx_load(rs0, o0);
-            pv[it][1] = cx_load(rs0, o0 + 16u);
+            const unsigned o0 = (ok && !s1) ? 4u * ((unsigned)((pn[it] * H0 + (iy >> a.up0)) * W0 + (ix >> a.up0)) * (unsigned)a.ld0 + (unsigned)c) : BSY_OOB_PAIR;
+            pv[it][0] = buf_load16<f32x4>(rs0, o0);
+            pv[it][1] = buf_load16<f32x4>(rs0, o0 + 16u);
             if (a.C1) {  // uniform
-                const unsigned o1 = (ok && s1) ? 4u * ((unsigned)((pn[it] * H1 + (iy >> a.up1)) * W1 + (ix >> a.up1)) * (unsigned)a.ld1 + (unsigned)(c - a.C0)) : CX_OOB;
-                const f32x4 q0 = cx_load(rs1, o1), q1 = cx_load(rs1, o1 + 16u);
+                const unsigned o1 = (ok && s1) ? 4u * ((unsigned)((pn[it] * H1 + (iy >> a.up1)) * W1 + (ix >> a.up1)) * (unsigned)a.ld1 + (unsigned)(c - a.C0)) : BSY_OOB_PAIR;
+                const f32x4 q0 = buf_load16<f32x4>(rs1, o1), q1 = buf_load16<f32x4>(rs1, o1 + 16u);
                 if (s1) { pv[it][0] = q0; pv[it][1] = q1; }
             }
         }
@@ -367,16 +344,16 @@ __global__ __launch_bounds__(512, 2) void conv32x_big_kernel(const Conv32Args a,
             const int id = tid + 512 * j;
             const int row = id / CPR, q = id % CPR;
             const bool ok = n0 + row < a.Cout;
-            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)(kt * BK + 8 * q)) : CX_OOB;
-            wvh[j] = cx_load(rwh, off);
-            wvl[j] = cx_load(rwl, off);
+            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)(kt * BK + 8 * q)) : BSY_OOB_PAIR;
+            wvh[j] = buf_load16<f32x4>(rwh, off);
+            wvl[j] = buf_load16<f32x4>(rwl, off);
         }
         if (WPT == 0) {  // TN 128, BK 16: 256 pieces per plane
             const int row = tid / CPR, q = tid % CPR;
             const bool ok = tid < WPIECES && n0 + row < a.Cout;
-            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)(kt * BK + 8 * q)) : CX_OOB;
-            wvh[0] = cx_load(rwh, off);
-            wvl[0] = cx_load(rwl, off);
+            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)(kt * BK + 8 * q)) : BSY_OOB_PAIR;
+            wvh[0] = buf_load16<f32x4>(rwh, off);
+            wvl[0] = buf_load16<f32x4>(rwl, off);
         }
         c8 += CPR;
         while (c8 >= Cin8) { c8 -= Cin8; ++tap; if (++tkw == a.ks) { tkw = 0; ++tkh; } }
@@ -475,7 +452,7 @@ __global__ __launch_bounds__(512, 2) void conv32x_big_kernel(const Conv32Args a,
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu_x(t) : t;
+                    v[e] = a.act ? silu_rcp(t) : t;
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);
@@ -522,9 +499,9 @@ __global__ __launch_bounds__(256, 2) void conv32x_patch_kernel(const Conv32Args 
     const int img = t / tiles_y;
     const int y0 = tyi * TH, x0 = txi * TW, n0 = tn_idx * TN;
     const int Cin = a.C0, nchunk = Cin / CK;
-    const cx_rsrc_t rs0 = cx_rsrc(a.src0, (unsigned)((((long long)a.B * a.H * a.W - 1) * a.ld0 + a.C0) * 4));
+    const bsy_rsrc_t rs0 = make_rsrc(a.src0, (unsigned)((((long long)a.B * a.H * a.W - 1) * a.ld0 + a.C0) * 4));
     const unsigned plane_bytes = (unsigned)a.Cout * (unsigned)a.wx_kpad * 2u;
-    const cx_rsrc_t rwh = cx_rsrc(a.wx_hi, plane_bytes), rwl = cx_rsrc(a.wx_lo, plane_bytes);
+    const bsy_rsrc_t rwh = make_rsrc(a.wx_hi, plane_bytes), rwl = make_rsrc(a.wx_lo, plane_bytes);
 
     // patch pieces of this thread: piece id -> (patch pixel, 8-channel group); offset of the pixel in the source (or out of range)
     unsigned poff[PPT];
@@ -533,15 +510,15 @@ __global__ __launch_bounds__(256, 2) void conv32x_patch_kernel(const Conv32Args 
         const int id = tid + 256 * j, pp = id / CPR, q = id % CPR;
         const int iy = y0 - 1 + pp / PW, ix = x0 - 1 + pp % PW;
         const bool ok = pp < NPP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        poff[j] = ok ? 4u * ((unsigned)((img * a.H + iy) * a.W + ix) * (unsigned)a.ld0 + 8u * q) : CX_OOB;
+        poff[j] = ok ? 4u * ((unsigned)((img * a.H + iy) * a.W + ix) * (unsigned)a.ld0 + 8u * q) : BSY_OOB_PAIR;
     }
     f32x4 pv[PPT][2], wvh[WPT], wvl[WPT];
     auto load_patch = [&](int c) {
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
-            const unsigned o = poff[j] == CX_OOB ? CX_OOB : poff[j] + 4u * (unsigned)(c * CK);
-            pv[j][0] = cx_load(rs0, o);
-            pv[j][1] = cx_load(rs0, o + 16u);
+            const unsigned o = poff[j] == BSY_OOB_PAIR ? BSY_OOB_PAIR : poff[j] + 4u * (unsigned)(c * CK);
+            pv[j][0] = buf_load16<f32x4>(rs0, o);
+            pv[j][1] = buf_load16<f32x4>(rs0, o + 16u);
         }
     };
     auto store_patch = [&]() {
@@ -565,9 +542,9 @@ __global__ __launch_bounds__(256, 2) void conv32x_patch_kernel(const Conv32Args 
             const int id = tid + 256 * j;
             const int q = id % CPR, row = (id / CPR) % TN, tp = id / (CPR * TN);
             const bool ok = id < WPIECES && n0 + row < a.Cout;
-            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)((tap0 + tp) * Cin + c * CK + 8 * q)) : CX_OOB;
-            wvh[j] = cx_load(rwh, off);
-            wvl[j] = cx_load(rwl, off);
+            const unsigned off = ok ? 2u * ((unsigned)(n0 + row) * (unsigned)a.wx_kpad + (unsigned)((tap0 + tp) * Cin + c * CK + 8 * q)) : BSY_OOB_PAIR;
+            wvh[j] = buf_load16<f32x4>(rwh, off);
+            wvl[j] = buf_load16<f32x4>(rwl, off);
         }
     };
     auto store_w = [&](int st) {
@@ -664,7 +641,7 @@ __global__ __launch_bounds__(256, 2) void conv32x_patch_kernel(const Conv32Args 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float tt = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu_x(tt) : tt;
+                    v[e] = a.act ? silu_rcp(tt) : tt;
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);

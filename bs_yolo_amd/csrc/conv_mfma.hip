@@ -87,26 +87,12 @@ __device__ __forceinline__ void dma16(const void* g, half_t* lds_wave_base) {
 // write ZEROS to LDS -- that is how padded taps / rows past M / K padding are filled, with no zero page and no 64-bit
 // per-lane pointer arithmetic (the scalar K-step displacement rides in soff).
 #if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t bsy_rsrc_t;
-__device__ __forceinline__ bsy_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ void dma16_buf(bsy_rsrc_t r, unsigned voff, unsigned soff, half_t* lds_wave_base) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
 }
 #else
-typedef int bsy_rsrc_t;
-__device__ __forceinline__ bsy_rsrc_t make_rsrc(const void*, unsigned) { return 0; }
 __device__ __forceinline__ void dma16_buf(bsy_rsrc_t, unsigned, unsigned, half_t*) {}
 #endif
-#define BSY_OOB 0xFFFFFFF0u  // voffset that is out of range for every descriptor (num_records < 2^32 - 16)
-
-__device__ __forceinline__ int xcd_remap(int bid, int nb) {
-    // XCD-aware, bijective block remap: blocks that share an XCD (bid % 8) get consecutive logical tiles, so the
-    // cout tiles of one pixel tile re-read the pixel operand from that XCD's L2.
-    const int q = nb >> 3, r = nb & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 template <int MT, int NT>
 __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[NT][MT], int m0, int n0, int wm, int wn,
@@ -307,7 +293,7 @@ __device__ __forceinline__ void conv_epilogue_head(const ConvK& p, f32x16 (&acc)
                         const int c = c0 + e;
                         if (!mv || c >= p.Cout) continue;
                         const float v = acc[a][b][4 * g + e];
-                        const float sg = 1.0f / (1.0f + __expf(-v));
+                        const float sg = sigmoid_f(v);
                         const size_t yi = ybase + (size_t)(4 + c) * p.A;
                         if (p.y_f32) head_store<float>(p.y, yi, sg); else head_store<half_t>(p.y, yi, sg);
                         if (p.raw) {
@@ -344,7 +330,7 @@ __device__ __forceinline__ void conv_epilogue_cls_lds(const ConvK& p, f32x16 (&a
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float v = acc[a][b][4 * g + e];
-                    stile[(c + e) * LDP + prow] = (half_t)(1.0f / (1.0f + __expf(-v)));
+                    stile[(c + e) * LDP + prow] = (half_t)sigmoid_f(v);
                 }
             }
         }

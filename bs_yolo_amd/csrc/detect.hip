@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
         yp[(size_t)3 * p.A] = (T)((y2 - y1) * st);
     }
     const float* cr = scls + a * cst;
-    for (int c = part; c < p.nc; c += 4) yp[(size_t)(4 + c) * p.A] = (T)(1.0f / (1.0f + __expf(-cr[c])));
+    for (int c = part; c < p.nc; c += 4) yp[(size_t)(4 + c) * p.A] = (T)sigmoid_f(cr[c]);
     for (int c = part; c < p.nm; c += 4) yp[(size_t)(4 + p.nc + c) * p.A] = (T)cr[p.nc + c];
 }
 

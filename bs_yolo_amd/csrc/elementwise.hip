@@ -16,26 +16,9 @@ __device__ __forceinline__ half8 hmax8(half8 a, half8 b) {
 #define DW_PX 2   // output pixels per thread along x
 #define DW_RY 8   // output rows per thread: a rolling 3-row register window -> 2 vector loads per output instead of 9,
                   // and the 9 x 8 weights are fetched once per 16 outputs
-// Loads go through a buffer descriptor: a lane whose pixel lies outside the image gets voffset = out-of-range and
+// Loads go through a buffer descriptor (common.h buf_load16): a lane whose pixel lies outside the image gets voffset = out-of-range and
 // receives zeros -- the conv's zero padding without a branch per load (the flat-load version spent more instructions
 // on exec-mask juggling and 64-bit addresses than on the 9 FMAs per output).
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t dw_rsrc_t;
-__device__ __forceinline__ dw_rsrc_t dw_make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ half8 dw_load16(dw_rsrc_t r, unsigned voff) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 u; half8 h; } v;
-    v.u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0);
-    return v.h;
-}
-#else
-typedef int dw_rsrc_t;
-__device__ __forceinline__ dw_rsrc_t dw_make_rsrc(const void*, unsigned) { return 0; }
-__device__ __forceinline__ half8 dw_load16(dw_rsrc_t, unsigned) { return half8{0, 0, 0, 0, 0, 0, 0, 0}; }
-#endif
-#define DW_OOB 0xFFFFFFF0u
 
 // a[j] = fma(f32(v[j]), w[j], a[j]) for the 8 channels of a piece, one v_fma_mix_f32 each (same order per element as before:
 // top, mid, bot of column kw = 0, 1, 2)
@@ -72,13 +55,13 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const half_t* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) { bs[j] = b0[j]; bs[4 + j] = b1[j]; }
     }
-    const dw_rsrc_t rs = dw_make_rsrc(src, span);
+    const bsy_rsrc_t rs = make_rsrc(src, span);
     // byte offsets of the 4 window columns inside a row (or out-of-range), row part added per row
     unsigned coloff[DW_PX + 2];
 #pragma unroll
     for (int q = 0; q < DW_PX + 2; ++q) {
         const int ix = x0 + q - 1;
-        coloff[q] = (unsigned)ix < (unsigned)W ? 2u * ((unsigned)ix * (unsigned)lds_ + (unsigned)c) : DW_OOB;
+        coloff[q] = (unsigned)ix < (unsigned)W ? 2u * ((unsigned)ix * (unsigned)lds_ + (unsigned)c) : BSY_OOB;
     }
     const unsigned rowbytes = 2u * (unsigned)W * (unsigned)lds_;
     auto load_row = [&](int iy, half8 (&r)[DW_PX + 2]) {
@@ -86,7 +69,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const half_t* __restrict
         const unsigned rb = (unsigned)(n * H + iy) * rowbytes;
 #pragma unroll
         for (int q = 0; q < DW_PX + 2; ++q)
-            r[q] = dw_load16(rs, (rowok && coloff[q] != DW_OOB) ? rb + coloff[q] : DW_OOB);
+            r[q] = buf_load16<half8>(rs, (rowok && coloff[q] != BSY_OOB) ? rb + coloff[q] : BSY_OOB);
     };
     half8 top[DW_PX + 2], mid[DW_PX + 2], bot[DW_PX + 2];
     load_row(y0 - 1, top);

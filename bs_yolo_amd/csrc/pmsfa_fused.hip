@@ -23,24 +23,6 @@
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t pf_rsrc_t;
-__device__ __forceinline__ pf_rsrc_t pf_make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ half8 pf_load16(pf_rsrc_t r, unsigned voff) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 u; half8 h; } v;
-    v.u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0);
-    return v.h;
-}
-#else
-typedef int pf_rsrc_t;
-__device__ __forceinline__ pf_rsrc_t pf_make_rsrc(const void*, unsigned) { return 0; }
-__device__ __forceinline__ half8 pf_load16(pf_rsrc_t, unsigned) { return half8{0, 0, 0, 0, 0, 0, 0, 0}; }
-#endif
-#define PF_OOB 0xFFFFFFF0u
-
 constexpr int pf_max(int a, int b) { return a > b ? a : b; }
 
 // __launch_bounds__(256, 2): left to itself the compiler took 228 VGPRs + 32 AGPRs = 260 > 256, ONE workgroup per CU (a persistent grid of
@@ -90,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void pmsfa_tail_kernel(const PmsfaArgs a, i
     constexpr int NLD = NPX * NP1 / 256;
     constexpr int RW = NPX / 4, PCS = C / 8;  // phase 4: rows per wave, 16-byte pieces per row
     constexpr int NOUT = RW * PCS / 64;       // output pieces per lane
-    const pf_rsrc_t rs = pf_make_rsrc(a.P, spanP);
+    const bsy_rsrc_t rs = make_rsrc(a.P, spanP);
     auto load_patch = [&](half8 (&pv)[NPATCH], int tile) {
         int t = tile;
         const int tx = t % tiles_x; t /= tiles_x;
@@ -103,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void pmsfa_tail_kernel(const PmsfaArgs a, i
             const int ch = id % NP1, px = (id / NP1) % P1W, py = id / (NP1 * P1W);
             const int y = oy0 - 5 + py, x = ox0 - 5 + px;
             const bool ok = id < P1H * P1W * NP1 && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            pv[i] = pf_load16(rs, ok ? 2u * ((unsigned)((n * H + y) * W + x) * (unsigned)a.ldp + (unsigned)(ch * 8)) : PF_OOB);
+            pv[i] = buf_load16<half8>(rs, ok ? 2u * ((unsigned)((n * H + y) * W + x) * (unsigned)a.ldp + (unsigned)(ch * 8)) : BSY_OOB);
         }
     };
 

@@ -11,7 +11,6 @@
 #include "common.h"
 
 namespace {
-__device__ __forceinline__ float silu32(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float sigmoid32(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---- dense conv, k x k, stride 1 / 2, up to two concatenated sources (each optionally read through nearest x2) ----------

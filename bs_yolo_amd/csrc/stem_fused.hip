@@ -39,8 +39,8 @@ struct StemK {
     const half_t* w1;
     const float* b1;
     half_t* dst;
-    int B, H, W, OH0, OW0, OH1, OW1, ldd, Kpad1, act, tiles_x, tiles_y, ntiles;
-    unsigned magic_x, magic_y;  // ceil(2^32 / tiles_x), ceil(2^32 / tiles_y): exact quotients for tile < 2^32 / divisor
+    int B, H, W, OH0, OW0, OH1, OW1, ldd, Kpad1, act;
+    TileGrid grid;
 };
 
 // f32 images: the prefetched patch items are twice as wide; at three workgroups per CU (168 VGPRs) the kernel spilled 13 registers -> two
@@ -91,13 +91,9 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 3) void stem_fused_kernel
     }
     const int e1base = (2 * (2 * mt1 + (lrow >> 4))) * ST_C0W + (lrow & 15);  // layer-1 lane pixel -> patch entry of tap (0, 0)
 
-    auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {  // divisions by multiply-high (host-made magics)
-        const int r = (int)__umulhi((unsigned)tile, p.magic_x);
-        const int tx = tile - r * p.tiles_x;
-        n = (int)__umulhi((unsigned)r, p.magic_y);
-        const int ty = r - n * p.tiles_y;
-        oy0 = ty * ST_TH;
-        ox0 = tx * ST_TW;
+    auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
+        const TileIdx t = tile_index(p.grid, tile);
+        n = t.n; oy0 = t.ty * ST_TH; ox0 = t.tx * ST_TW;
     };
     ImgItem<T> pre[ST_NLOAD];
     int nn = 0, noy0 = 0, nox0 = 0;  // coordinates of the tile whose patch is in `pre`
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 3) void stem_fused_kernel
     // Retire the weight / bias loads HERE: left pending, the compiler waits for them at their first use inside the tile
     // loop with vmcnt(0) -- on every iteration, which then also waits for the prefetch issued just before.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.ntiles);  // XCD-aware tile order (common.h)
+    const TileWalk tw = xcd_tile_walk(blockIdx.x, gridDim.x, p.grid.ntiles);  // XCD-aware tile order (common.h)
     int tile = tw.tile;
     if (tile < tw.end) fetch(tile);
     for (; tile < tw.end; tile += tw.step) {
@@ -207,7 +203,7 @@ bool stem_fused_supported(int C0, int C1, int H, int W) {
 template <typename T>
 static int launch_t(const StemArgs& a, const StemK& k, hipStream_t s) {
     const int slots = sizeof(T) == 4 ? 512 : 768;      // 3 workgroups per CU (register-limited: a fourth needs <= 128 VGPRs and spills 61; f32 images: 2), tiles dealt round-robin
-    const int grid = k.ntiles < slots ? k.ntiles : slots;
+    const int grid = k.grid.ntiles < slots ? k.grid.ntiles : slots;
     if (a.C0 == 32) hipLaunchKernelGGL((stem_fused_kernel<T, 32, 64>), dim3(grid), dim3(256), 0, s, k);
     else hipLaunchKernelGGL((stem_fused_kernel<T, 16, 32>), dim3(grid), dim3(256), 0, s, k);
     HIP_TRY(hipGetLastError());
@@ -228,20 +224,8 @@ int launch_stem_fused(const StemArgs& a, hipStream_t s) {
     k.img = a.img; k.w0 = (const half_t*)a.w0; k.b0 = a.b0; k.w1 = (const half_t*)a.w1; k.b1 = a.b1; k.dst = a.dst;
     k.B = a.B; k.H = a.H; k.W = a.W; k.OH0 = OH0; k.OW0 = OW0; k.OH1 = OH1; k.OW1 = OW1; k.ldd = a.ldd; k.Kpad1 = a.Kpad1;
     k.act = a.act;
-    k.tiles_x = ceil_div(OW1, ST_TW); k.tiles_y = ceil_div(OH1, ST_TH);
-    const long long nt = (long long)a.B * k.tiles_x * k.tiles_y;
-    if (nt <= 0 || nt > 0x7fffffffLL) BSY_FAIL(BSY_ERR_ARG, "stem: tile count out of range");
-    k.ntiles = (int)nt;
-    if (k.tiles_x < 2 || k.tiles_y < 2) {
-        // magic for divisor 1 would be 2^32: keep the kernel's multiply-high path by padding the tile grid instead
-        if (k.tiles_x < 2) k.tiles_x = 2;
-        if (k.tiles_y < 2) k.tiles_y = 2;
-        k.ntiles = a.B * k.tiles_x * k.tiles_y;  // the extra tiles lie outside the map: nothing is stored for them
-    }
-    if ((long long)k.ntiles * (k.tiles_x > k.tiles_y ? k.tiles_x : k.tiles_y) >= (1LL << 32))
-        BSY_FAIL(BSY_ERR_ARG, "stem: tile count out of range");
-    k.magic_x = (unsigned)(((1ULL << 32) + k.tiles_x - 1) / k.tiles_x);
-    k.magic_y = (unsigned)(((1ULL << 32) + k.tiles_y - 1) / k.tiles_y);
+    const int rc = make_tile_grid(k.grid, a.B, OH1, OW1, ST_TH, ST_TW, "stem");
+    if (rc != BSY_OK) return rc;
     if (a.img_dtype == BSY_F16) return launch_t<half_t>(a, k, s);
     if (a.img_dtype == BSY_F32) return launch_t<float>(a, k, s);
     BSY_FAIL(BSY_ERR_ARG, "stem: image dtype %d unsupported", a.img_dtype);
