@@ -33,6 +33,7 @@ SOURCES = {
     "attention.hip": [],
     "detect.hip": [],
     "nms.hip": ["-ffp-contract=off"],
+    "obb.hip": ["-ffp-contract=off"],
     "letterbox.hip": ["-ffp-contract=off"],
     "masks.hip": ["-ffp-contract=off"],
     "val_match.hip": ["-ffp-contract=off"],

@@ -313,8 +313,12 @@ struct DecodeArgs {
     int nl, B, nc, nm, A;
     void* y;
     int y_dtype;
+    int ne;  // OBB angle channels (0 / 1): msk[l] then holds the angle logits and nm is 0
 };
 int launch_decode(const DecodeArgs& a, hipStream_t s);
+// bsy_nms's candidate keys (nms.hip steps 1-2) for another consumer: filter + sort, the prediction left untouched
+int nms_candidates(void* pred, int pred_dtype, int B, int nc, int C, int A, float conf_thres, const int32_t* classes, int n_classes,
+                   int multi_label, int cap, unsigned long long* keys, int32_t* cand_count, hipStream_t s);
 int launch_nhwc2nchw(const half_t* src, int ld, int B, int C, int hw, void* out, int out_dtype, hipStream_t s);
 int launch_raw_nchw(const float* box, int ldb, const float* cls, int ldc, int B, int h, int w, int nc, void* out,
                     int out_dtype, hipStream_t s);

@@ -19,14 +19,18 @@ struct DecodeK {
     int h[3], w[3], a0[3];  // a0 = first anchor index of the level
     float stride[3];
     int nl, B, nc, nm, A;
+    int ne;  // ROT: angle channels (1), read through the msk slots
 };
 
 // One workgroup = 64 consecutive anchors of one (image, level).  Their logits are contiguous in HBM
 // ([64][64] box floats, [64][ldc] class floats), so they are staged through LDS with coalesced 16-byte loads and then
 // read column-wise (row stride padded by one dword -> conflict-free); outputs are written one channel at a time,
 // 64 consecutive anchors per wave-store.
+// ROT (OBB head, head.py:211-227): the msk slots carry the angle logits; theta = (sigmoid - 0.25) * pi (head.py:216), the box
+// is dist2rbox (utils/tal.py:404-423) times the stride, and theta is written as row 4 + nc.  The Detect / Segment instances
+// (ROT = false) are the kernel as it was.
 #define DEC_TA 64
-template <typename T>
+template <typename T, bool ROT>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restrict__ y) {
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     const int tid = threadIdx.x;
@@ -42,7 +46,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
     const int la0 = t * DEC_TA;
     const int na = min(DEC_TA, hw - la0);
     if (na <= 0) return;
-    const int nch = p.nc + p.nm;
+    const int nx = ROT ? p.ne : p.nm;      // rows read through the msk slots
+    const int nch = p.nc + nx;
     const int cst = nch + 1;               // padded row stride of the class/mask tile
     float* sbox = dsm;                     // [64][65]
     float* scls = dsm + DEC_TA * 65;       // [64][nc+nm+1]
@@ -66,16 +71,16 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
             for (int e = 0; e < 4; ++e)
                 if (4 * q + e < p.nc) d[e] = v[e];
         }
-        if (p.nm) {
+        if (nx) {
             const float* mp = p.msk[l] + pix0 * p.ldm[l];
-            const int nqm = (p.nm + 3) >> 2;
+            const int nqm = (nx + 3) >> 2;
             for (int i = tid; i < na * nqm; i += 256) {
                 const int r = i / nqm, q = i - r * nqm;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(mp + (size_t)r * p.ldm[l] + 4 * q);
                 float* d = scls + r * cst + p.nc + 4 * q;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (4 * q + e < p.nm) d[e] = v[e];
+                    if (4 * q + e < nx) d[e] = v[e];
             }
         }
     }
@@ -99,7 +104,21 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
     if (a >= na) return;
     const int la = la0 + a;
     T* yp = y + (size_t)b * (4 + nch) * p.A + p.a0[l] + la;
-    if (part == 0) {
+    if (ROT) {
+        if (part == 0) {
+            const float ax = (float)(la % p.w[l]) + 0.5f, ay = (float)(la / p.w[l]) + 0.5f;
+            const float lt0 = sd[a * 4 + 0], lt1 = sd[a * 4 + 1], rb0 = sd[a * 4 + 2], rb1 = sd[a * 4 + 3];
+            const float th = (sigmoid_f(scls[a * cst + p.nc]) - 0.25f) * 3.14159265358979323846f;
+            const float c = cosf(th), s = sinf(th);
+            const float xf = (rb0 - lt0) / 2.0f, yf = (rb1 - lt1) / 2.0f;
+            const float st = p.stride[l];
+            yp[0] = (T)((xf * c - yf * s + ax) * st);
+            yp[(size_t)p.A] = (T)((xf * s + yf * c + ay) * st);
+            yp[(size_t)2 * p.A] = (T)((lt0 + rb0) * st);
+            yp[(size_t)3 * p.A] = (T)((lt1 + rb1) * st);
+            yp[(size_t)(4 + p.nc) * p.A] = (T)th;
+        }
+    } else if (part == 0) {
         const float ax = (float)(la % p.w[l]) + 0.5f, ay = (float)(la / p.w[l]) + 0.5f;
         const float x1 = ax - sd[a * 4 + 0], y1 = ay - sd[a * 4 + 1], x2 = ax + sd[a * 4 + 2], y2 = ay + sd[a * 4 + 3];
         const float st = p.stride[l];
@@ -115,6 +134,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
 
 int launch_decode(const DecodeArgs& a, hipStream_t s) {
     if (a.nl < 1 || a.nl > 3 || a.nc < 1 || a.B < 1) BSY_FAIL(BSY_ERR_ARG, "decode: bad sizes");
+    if (a.ne < 0 || a.ne > 1 || (a.ne && a.nm)) BSY_FAIL(BSY_ERR_ARG, "decode: ne = %d with nm = %d (one angle, no mask coefficients)", a.ne, a.nm);
+    const int nx = a.nm + a.ne;  // rows read through the msk slots
     DecodeK k;
     int A = 0;
     for (int l = 0; l < 3; ++l) {
@@ -124,27 +145,31 @@ int launch_decode(const DecodeArgs& a, hipStream_t s) {
         k.h[l] = on ? a.h[l] : 0; k.w[l] = on ? a.w[l] : 0; k.stride[l] = on ? a.stride[l] : 0.f;
         k.a0[l] = A;
         if (on) {
-            if (!a.box[l] || !a.cls[l] || (a.ldb[l] & 3) || ((uintptr_t)a.box[l] & 15) || (a.nm && !a.msk[l]))
+            if (!a.box[l] || !a.cls[l] || (a.ldb[l] & 3) || ((uintptr_t)a.box[l] & 15) || (nx && !a.msk[l]))
                 BSY_FAIL(BSY_ERR_ARG, "decode: level %d bad layout", l);
             A += a.h[l] * a.w[l];
         }
     }
     if (a.A && a.A != A) BSY_FAIL(BSY_ERR_ARG, "decode: anchor count mismatch (%d vs %d)", a.A, A);
-    k.nl = a.nl; k.B = a.B; k.nc = a.nc; k.nm = a.nm; k.A = A;
+    k.nl = a.nl; k.B = a.B; k.nc = a.nc; k.nm = a.nm; k.A = A; k.ne = a.ne;
     int tiles = 0;
     for (int l = 0; l < a.nl; ++l) {
         tiles += (a.h[l] * a.w[l] + DEC_TA - 1) / DEC_TA;
         if ((a.ldc[l] & 3) || a.ldc[l] < ((a.nc + 3) & ~3) || ((uintptr_t)a.cls[l] & 15) ||
-            (a.nm && ((a.ldm[l] & 3) || a.ldm[l] < ((a.nm + 3) & ~3) || ((uintptr_t)a.msk[l] & 15))))
+            (nx && ((a.ldm[l] & 3) || a.ldm[l] < ((nx + 3) & ~3) || ((uintptr_t)a.msk[l] & 15))))
             BSY_FAIL(BSY_ERR_ARG, "decode: level %d class/mask rows must be 16-byte aligned multiples of 4 floats", l);
     }
     dim3 grid(tiles, a.B);
-    const size_t lds = (size_t)DEC_TA * (65 + (a.nc + a.nm + 1) + 4) * sizeof(float);
-    if (lds > 64 * 1024) BSY_FAIL(BSY_ERR_ARG, "decode: nc + nm = %d too large", a.nc + a.nm);
-    if (a.y_dtype == BSY_F16)
-        hipLaunchKernelGGL(decode_kernel<half_t>, grid, dim3(256), lds, s, k, (half_t*)a.y);
+    const size_t lds = (size_t)DEC_TA * (65 + (a.nc + nx + 1) + 4) * sizeof(float);
+    if (lds > 64 * 1024) BSY_FAIL(BSY_ERR_ARG, "decode: nc + nm = %d too large", a.nc + nx);
+    if (a.y_dtype == BSY_F16 && a.ne)
+        hipLaunchKernelGGL((decode_kernel<half_t, true>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+    else if (a.y_dtype == BSY_F32 && a.ne)
+        hipLaunchKernelGGL((decode_kernel<float, true>), grid, dim3(256), lds, s, k, (float*)a.y);
+    else if (a.y_dtype == BSY_F16)
+        hipLaunchKernelGGL((decode_kernel<half_t, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32)
-        hipLaunchKernelGGL(decode_kernel<float>, grid, dim3(256), lds, s, k, (float*)a.y);
+        hipLaunchKernelGGL((decode_kernel<float, false>), grid, dim3(256), lds, s, k, (float*)a.y);
     else
         BSY_FAIL(BSY_ERR_ARG, "decode: y dtype %d unsupported", a.y_dtype);
     HIP_TRY(hipGetLastError());

@@ -592,10 +592,11 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
         case BSY_OP_DECODE: {
             DecodeArgs a;
             memset(&a, 0, sizeof(a));
-            a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A;
+            a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A; a.ne = op.ne;
+            const bool extra = op.nm || op.ne;  // mask coefficients (Segment) or angle logits (OBB) in the msk slots
             for (int l = 0; l < op.nl && l < 3; ++l) {
-                a.box[l] = R.f(op.box[l]); a.cls[l] = R.f(op.cls[l]); a.msk[l] = op.nm ? R.f(op.msk[l]) : nullptr;
-                a.ldb[l] = op.box[l].ld; a.ldc[l] = op.cls[l].ld; a.ldm[l] = op.nm ? op.msk[l].ld : 0;
+                a.box[l] = R.f(op.box[l]); a.cls[l] = R.f(op.cls[l]); a.msk[l] = extra ? R.f(op.msk[l]) : nullptr;
+                a.ldb[l] = op.box[l].ld; a.ldc[l] = op.cls[l].ld; a.ldm[l] = extra ? op.msk[l].ld : 0;
                 a.h[l] = op.lvl_h[l]; a.w[l] = op.lvl_w[l]; a.stride[l] = op.lvl_stride[l];
             }
             a.y = R.base(op.dst); a.y_dtype = op.out_dtype;

@@ -383,6 +383,27 @@ extern "C" int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A,
     return BSY_OK;
 }
 
+int nms_candidates(void* pred, int pred_dtype, int B, int nc, int C, int A, float conf_thres, const int32_t* classes, int n_classes,
+                   int multi_label, int cap, unsigned long long* keys, int32_t* cand_count, hipStream_t s) {
+    NmsK k = {};
+    k.pred = pred; k.B = B; k.nc = nc; k.nm = C - 4 - nc; k.A = A; k.C = C;
+    k.conf = conf_thres; k.classes = classes; k.n_classes = classes ? n_classes : 0; k.multi_label = multi_label;
+    k.in_place = 0; k.cap = cap; k.keys = keys; k.cand_count = cand_count;
+    HIP_TRY(hipMemsetAsync(cand_count, 0, (size_t)B * 4, s));
+    dim3 g1((A + 255) / 256, B);
+    if (pred_dtype == BSY_F16) {
+        if (!multi_label && !(A & 3) && !((uintptr_t)pred & 7))
+            hipLaunchKernelGGL(nms_filter4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);
+        else
+            hipLaunchKernelGGL(nms_filter_kernel<half_t>, g1, dim3(256), 0, s, k);
+    } else {
+        hipLaunchKernelGGL(nms_filter_kernel<float>, g1, dim3(256), 0, s, k);
+    }
+    hipLaunchKernelGGL(nms_sort_kernel, dim3(B), dim3(1024), 0, s, k);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}
+
 __global__ void scale_boxes_kernel(float* det, const int32_t* counts, int B, int max_det, int row, const float* gain,
                                    const float* pad_x, const float* pad_y, const float* h0, const float* w0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

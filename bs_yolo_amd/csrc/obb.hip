@@ -1,0 +1,272 @@
+// Rotated NMS and the OBB postprocess tail for gfx950, no host synchronisation.  Compile with -ffp-contract=off: probiou must
+// round like the fp32 CPU reference, one operation at a time (no FMA contraction).
+//
+// Replaces non_max_suppression(..., rotated=True) (utils/ops.py:241-297) with nms_rotated (:146-164) and batch_probiou
+// (utils/metrics.py:261-278, :327-358), and the per-image tail of OBBPredictor.postprocess (models/yolo/obb/predict.py:48-49).
+// bsy_nms_rotated, whole batch per launch:
+//   1. nms_candidates (nms.hip): bsy_nms's confidence / class filter and key sort, score descending, ties by ascending index;
+//      the prediction stays xywhr (no xyxy conversion).
+//   2. obb_gather_kernel   (thread = sorted candidate < max_nms): the class-offset centre and the covariance terms of
+//      _get_covariance_matrix, computed once per candidate into the workspace.
+//   3. obb_suppress_kernel (workgroup = 256 sorted candidates of one image): FAST-NMS -- candidate i is kept iff
+//      probiou(j, i) < thr for EVERY earlier j, suppressed j included (ious.triu_(1).max(0) < thr).  No decision depends on
+//      another decision, so every candidate is tested independently: earlier candidates are staged through LDS 256 at a time,
+//      a lane stops once its candidate is suppressed and the workgroup once all of its lanes are.
+//   4. obb_compact_kernel  (workgroup = image): order-preserving compaction of the kept flags, cut at max_det (exact: the
+//      decisions of the first max_det kept candidates do not depend on the ones after them).
+#include "common.h"
+
+typedef unsigned long long u64;
+
+struct ObbK {
+    const void* pred;
+    int B, nc, ne, A, C;  // C = 4 + nc + ne
+    float iou;
+    int agnostic, multi_label, max_det;
+    int nmax;             // records per image: min(max_nms, candidates the filter can produce)
+    float max_wh;
+    int cap;              // keys per image
+    const u64* keys;
+    const int32_t* cand_count;
+    float* cov;           // (B, nmax, 8): x + off, y + off, a, b, c, clamp(a b - c^2, 0), -, -
+    float* rows;          // (B, nmax, 8): x, y, w, h, conf, cls, anchor (int bits), -
+    int32_t* keep;        // (B, nmax)
+    float* out;
+    int32_t* counts;
+};
+
+__device__ __forceinline__ int obb_n(const ObbK& p, int b) {
+    const int n = p.cand_count[b];
+    return n < p.nmax ? n : p.nmax;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void obb_gather_kernel(const ObbK p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= obb_n(p, b)) return;
+    const T* pb = reinterpret_cast<const T*>(p.pred) + (size_t)b * p.C * p.A;
+    const u64 k = p.keys[(size_t)b * p.cap + i];
+    const float score = __uint_as_float((unsigned)(k >> 32));
+    const unsigned idx = ~(unsigned)(k & 0xffffffffull);
+    int anchor, cls = 0;
+    if (p.multi_label) {
+        anchor = (int)(idx / (unsigned)p.nc);
+        cls = (int)(idx - (unsigned)anchor * p.nc);
+    } else {
+        anchor = (int)idx;  // best class = first maximum (ops.py:274 cls.max(1))
+        const T* cp = pb + (size_t)4 * p.A + anchor;
+        float best = (float)cp[0];
+        for (int c = 1; c < p.nc; ++c) {
+            const float s = (float)cp[(size_t)c * p.A];
+            if (s > best) { best = s; cls = c; }
+        }
+    }
+    const float x = (float)pb[anchor], y = (float)pb[(size_t)p.A + anchor];
+    const float w = (float)pb[(size_t)2 * p.A + anchor], h = (float)pb[(size_t)3 * p.A + anchor];
+    // theta = the last column of the candidate's row (ops.py:292 x[:, -1:]): the last extra row, the class index without one
+    const float th = p.ne ? (float)pb[(size_t)(p.C - 1) * p.A + anchor] : (float)cls;
+    const float off = (float)cls * (p.agnostic ? 0.0f : p.max_wh);
+    // _get_covariance_matrix (metrics.py:272-278): (w^2 / 12, h^2 / 12, theta) -> a cos^2 + b sin^2, a sin^2 + b cos^2, (a - b) cos sin
+    const float ga = (w * w) / 12.0f, gb = (h * h) / 12.0f;
+    const float cs = cosf(th), sn = sinf(th);
+    const float cos2 = cs * cs, sin2 = sn * sn;
+    const float ca = ga * cos2 + gb * sin2, cb = ga * sin2 + gb * cos2, cc = ((ga - gb) * cs) * sn;
+    const float d = ca * cb - cc * cc;
+    float* cv = p.cov + ((size_t)b * p.nmax + i) * 8;
+    float* rw = p.rows + ((size_t)b * p.nmax + i) * 8;
+    *reinterpret_cast<f32x4*>(cv) = f32x4{x + off, y + off, ca, cb};
+    *reinterpret_cast<f32x4*>(cv + 4) = f32x4{cc, d < 0.0f ? 0.0f : d, 0.0f, 0.0f};  // clamp_(0) keeps a NaN
+    *reinterpret_cast<f32x4*>(rw) = f32x4{x, y, w, h};
+    *reinterpret_cast<f32x4*>(rw + 4) = f32x4{score, (float)cls, __int_as_float(anchor), 0.0f};
+}
+
+// batch_probiou (metrics.py:342-358) of obb1 = j and obb2 = i, the reference's operation order; (x, y, a, b, c, det) as gathered
+__device__ __forceinline__ float probiou(const f32x4 j0, const float jc, const float jd, const f32x4 i0, const float ic, const float id) {
+    const float eps = 1e-7f;
+    const float x1 = j0[0], y1 = j0[1], a1 = j0[2], b1 = j0[3];
+    const float x2 = i0[0], y2 = i0[1], a2 = i0[2], b2 = i0[3];
+    const float sa = a1 + a2, sb = b1 + b2, sc = jc + ic;
+    const float dy = y1 - y2, dx = x1 - x2;
+    const float core = sa * sb - sc * sc;
+    const float t1 = ((sa * (dy * dy) + sb * (dx * dx)) / (core + eps)) * 0.25f;
+    const float t2 = (((sc * (x2 - x1)) * dy) / (core + eps)) * 0.5f;
+    const float t3 = logf(core / (4.0f * sqrtf(jd * id) + eps) + eps) * 0.5f;
+    float bd = t1 + t2 + t3;
+    bd = bd < eps ? eps : (bd > 100.0f ? 100.0f : bd);  // clamp(eps, 100); a NaN stays NaN
+    const float hd = sqrtf(1.0f - expf(-bd) + eps);
+    return 1.0f - hd;
+}
+
+#define OBB_TILE 256
+__global__ __launch_bounds__(OBB_TILE) void obb_suppress_kernel(const ObbK p) {
+    __shared__ f32x4 s0[OBB_TILE];  // x, y, a, b of the staged earlier candidates
+    __shared__ float s1[OBB_TILE][2];  // c, det
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = obb_n(p, b);
+    const int i0 = blockIdx.x * OBB_TILE;
+    if (i0 >= n) return;  // uniform over the workgroup
+    const int i = i0 + tid;
+    const bool have = i < n;
+    f32x4 me0 = {0.f, 0.f, 0.f, 0.f};
+    float mc = 0.f, md = 0.f;
+    if (have) {
+        const float* cv = p.cov + ((size_t)b * p.nmax + i) * 8;
+        me0 = *reinterpret_cast<const f32x4*>(cv);
+        mc = cv[4]; md = cv[5];
+    }
+    // the column max over j < i includes the zeros of triu_(1): a candidate survives only if 0 < thr as well
+    bool alive = have && (0.0f < p.iou);
+    for (int t0 = 0; t0 <= i0; t0 += OBB_TILE) {  // tiles of earlier candidates, this workgroup's own chunk last
+        __syncthreads();  // the previous tile has been read by every lane
+        const int j = t0 + tid;
+        if (j < n) {
+            const float* cv = p.cov + ((size_t)b * p.nmax + j) * 8;
+            s0[tid] = *reinterpret_cast<const f32x4*>(cv);
+            s1[tid][0] = cv[4];
+            s1[tid][1] = cv[5];
+        }
+        if (!__syncthreads_or(alive)) break;
+        const int lim = i - t0 < OBB_TILE ? i - t0 : OBB_TILE;  // j < i (and j < n, as i < n)
+        for (int jj = 0; alive && jj < lim; ++jj)
+            if (!(probiou(s0[jj], s1[jj][0], s1[jj][1], me0, mc, md) < p.iou)) alive = false;
+    }
+    if (have) p.keep[(size_t)b * p.nmax + i] = alive ? 1 : 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void obb_compact_kernel(const ObbK p) {
+    __shared__ int wsum[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = obb_n(p, b);
+    const int row = 6 + p.ne;
+    const T* pb = reinterpret_cast<const T*>(p.pred) + (size_t)b * p.C * p.A;
+    float* ob = p.out + (size_t)b * p.max_det * row;
+    int base = 0;  // kept so far (the same value in every lane)
+    for (int c0 = 0; c0 < n && base < p.max_det; c0 += 1024) {
+        const int i = c0 + tid;
+        const bool k = i < n && p.keep[(size_t)b * p.nmax + i] != 0;
+        const u64 m = __ballot(k);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, tot = 0;
+        for (int w = 0; w < 16; ++w) {
+            before += w < wave ? wsum[w] : 0;
+            tot += wsum[w];
+        }
+        const int slot = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (k && slot < p.max_det) {
+            const float* r = p.rows + ((size_t)b * p.nmax + i) * 8;
+            float* o = ob + (size_t)slot * row;
+#pragma unroll
+            for (int e = 0; e < 6; ++e) o[e] = r[e];
+            const int anchor = __float_as_int(r[6]);
+            for (int e = 0; e < p.ne; ++e) o[6 + e] = (float)pb[(size_t)(4 + p.nc + e) * p.A + anchor];
+        }
+        base += tot;
+        __syncthreads();  // wsum is rewritten by the next chunk
+    }
+    if (tid == 0) p.counts[b] = base < p.max_det ? base : p.max_det;
+}
+
+static long long obb_pow2(long long v) {
+    long long q = 2;
+    while (q < v) q <<= 1;
+    return q;
+}
+
+static size_t obb_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+extern "C" size_t bsy_nms_rotated_workspace_bytes(int B, int A, int nc, int multi_label, int max_nms) {
+    if (B <= 0 || A <= 0 || nc <= 0 || max_nms <= 0) return 0;
+    const long long per = (multi_label && nc > 1) ? (long long)A * nc : (long long)A;
+    const size_t cap = (size_t)obb_pow2(per), nmax = (size_t)(per < max_nms ? per : max_nms);
+    return 256 + obb_align((size_t)B * 4) + obb_align((size_t)B * cap * 8) + 2 * obb_align((size_t)B * nmax * 32) +
+           obb_align((size_t)B * nmax * 4);
+}
+
+extern "C" int bsy_nms_rotated(void* pred, int pred_dtype, int B, int nc, int ne, int A, float conf_thres, float iou_thres,
+                               const int32_t* classes, int n_classes, int agnostic, int multi_label, int max_det, int max_nms,
+                               float max_wh, float* out, int32_t* counts, void* workspace, size_t workspace_bytes,
+                               bsy_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!pred || !out || !counts || !workspace) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: null pointer");
+    if (B <= 0 || nc <= 0 || ne < 0 || A <= 0) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: bad sizes B=%d nc=%d ne=%d A=%d", B, nc, ne, A);
+    if (!(conf_thres >= 0.f && conf_thres <= 1.f))
+        BSY_FAIL(BSY_ERR_ARG, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
+    if (!(iou_thres >= 0.f && iou_thres <= 1.f))
+        BSY_FAIL(BSY_ERR_ARG, "Invalid IoU %g, valid values are between 0.0 and 1.0", iou_thres);
+    if (max_det <= 0 || max_det > 4096) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: max_det %d out of range (1..4096)", max_det);
+    if (max_nms <= 0) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: max_nms must be positive");
+    if (pred_dtype != BSY_F16 && pred_dtype != BSY_F32) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: dtype %d unsupported", pred_dtype);
+    if ((long long)A * nc > 0x7fffffffLL || (long long)B * (4 + nc + ne) * A > 0x7fffffffffffLL)
+        BSY_FAIL(BSY_ERR_ARG, "nms_rotated: A*nc too large");
+    multi_label = (multi_label && nc > 1) ? 1 : 0;  // ops.py:239
+    const size_t need = bsy_nms_rotated_workspace_bytes(B, A, nc, multi_label, max_nms);
+    if (workspace_bytes < need) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: workspace %zu < %zu bytes", workspace_bytes, need);
+    const long long per = multi_label ? (long long)A * nc : (long long)A;
+    ObbK k = {};
+    k.pred = pred; k.B = B; k.nc = nc; k.ne = ne; k.A = A; k.C = 4 + nc + ne;
+    k.iou = iou_thres; k.agnostic = agnostic; k.multi_label = multi_label; k.max_det = max_det;
+    k.nmax = (int)(per < max_nms ? per : max_nms); k.max_wh = max_wh; k.cap = (int)obb_pow2(per);
+    uintptr_t w = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    int32_t* cand = (int32_t*)w;
+    w += obb_align((size_t)B * 4);
+    u64* keys = (u64*)w;
+    w += obb_align((size_t)B * k.cap * 8);
+    k.cov = (float*)w;
+    w += obb_align((size_t)B * k.nmax * 32);
+    k.rows = (float*)w;
+    w += obb_align((size_t)B * k.nmax * 32);
+    k.keep = (int32_t*)w;
+    k.keys = keys; k.cand_count = cand; k.out = out; k.counts = counts;
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * max_det * (6 + ne) * sizeof(float), s));
+    const int rc = nms_candidates(pred, pred_dtype, B, nc, k.C, A, conf_thres, classes, classes ? n_classes : 0, multi_label, k.cap,
+                                  keys, cand, s);
+    if (rc != BSY_OK) return rc;
+    dim3 grid((k.nmax + OBB_TILE - 1) / OBB_TILE, B);
+    if (pred_dtype == BSY_F16) {
+        hipLaunchKernelGGL(obb_gather_kernel<half_t>, grid, dim3(OBB_TILE), 0, s, k);
+        hipLaunchKernelGGL(obb_suppress_kernel, grid, dim3(OBB_TILE), 0, s, k);
+        hipLaunchKernelGGL(obb_compact_kernel<half_t>, dim3(B), dim3(1024), 0, s, k);
+    } else {
+        hipLaunchKernelGGL(obb_gather_kernel<float>, grid, dim3(OBB_TILE), 0, s, k);
+        hipLaunchKernelGGL(obb_suppress_kernel, grid, dim3(OBB_TILE), 0, s, k);
+        hipLaunchKernelGGL(obb_compact_kernel<float>, dim3(B), dim3(1024), 0, s, k);
+    }
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}
+
+__global__ void obb_scale_kernel(float* det, const int32_t* counts, int max_det, int row, const float* gain, const float* pad_x,
+                                 const float* pad_y, const float* h0, const float* w0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= max_det || i >= counts[b]) return;
+    float* o = det + ((size_t)b * max_det + i) * row;
+    const float pi = 3.14159265358979323846f, half_pi = 1.57079632679489661923f;  // math.pi, math.pi / 2 as fp32 scalars
+    const float x = o[0], y = o[1], w = o[2], h = o[3], t = o[row - 1];
+    // regularize_rboxes (ops.py:785-790): swap w / h when h >= w; torch's remainder: fmod, then + pi where it is negative
+    const bool wide = w > h;
+    const float wr = wide ? w : h, hr = wide ? h : w;
+    float r = fmodf(wide ? t : t + half_pi, pi);
+    if (r != 0.0f && r < 0.0f) r += pi;
+    // scale_boxes(xywh=True) (ops.py:120-127): pad off x and y only, all four divided by the gain; clip_boxes (:331-334)
+    const float g = gain[b], ww = w0[b], hh = h0[b];
+    const float xs = (x - pad_x[b]) / g, ys = (y - pad_y[b]) / g, ws = wr / g, hs = hr / g;
+    o[0] = fminf(fmaxf(xs, 0.f), ww);
+    o[1] = fminf(fmaxf(ys, 0.f), hh);
+    o[2] = fminf(fmaxf(ws, 0.f), ww);
+    o[3] = fminf(fmaxf(hs, 0.f), hh);
+    o[row - 1] = r;
+}
+
+extern "C" int bsy_obb_scale(float* det, const int32_t* counts, int B, int max_det, int row, const float* gain, const float* pad_x,
+                             const float* pad_y, const float* h0, const float* w0, bsy_stream stream) {
+    if (!det || !counts || !gain || !pad_x || !pad_y || !h0 || !w0 || B <= 0 || max_det <= 0 || row < 7)
+        BSY_FAIL(BSY_ERR_ARG, "obb_scale: bad argument");
+    dim3 grid((max_det + 127) / 128, B);
+    hipLaunchKernelGGL(obb_scale_kernel, grid, dim3(128), 0, (hipStream_t)stream, det, counts, max_det, row, gain, pad_x, pad_y, h0,
+                       w0);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}

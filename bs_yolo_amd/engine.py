@@ -269,6 +269,9 @@ class YoloEngine:
             if self.meta["nm"]:
                 raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(3)] if want_raw else [None] * 3
                 return y, (raws, y[:, 4 + self.meta["nc"]:], torch.cat([o[1][2] for o in outs]))
+            if self.meta["ne"]:
+                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(3)] if want_raw else [None] * 3
+                return y, (raws, y[:, 4 + self.meta["nc"]:])
             return y, ([torch.cat([o[1][l] for o in outs]) for l in range(3)] if want_raw else [None] * 3)
         with self._lock:  # plan table, arena and launch order are shared state
             return self._forward_one(im, want_raw, B, H, W)
@@ -278,7 +281,7 @@ class YoloEngine:
         m = plan.meta
 
         def outputs():
-            y = torch.empty((B, 4 + m["nc"] + m["nm"], m["A"]), dtype=im.dtype, device=self.device)
+            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
             raws: List[Optional[torch.Tensor]] = [None, None, None]
             if want_raw:
                 raws = [torch.empty((B, m["no"], lh, lw), dtype=im.dtype, device=self.device) for lh, lw in m["levels"]]
@@ -337,6 +340,8 @@ class YoloEngine:
         self._last_stream = stream
         if m["nm"]:  # Segment.forward (head.py:197): (cat(y, mc), (raw, mc, proto)); y already carries the mc rows
             return y, (raws, y[:, 4 + m["nc"]:], proto)
+        if m["ne"]:  # OBB.forward (head.py:223): (cat(y, angle), (raw, angle)); y already carries the angle row
+            return y, (raws, y[:, 4 + m["nc"]:])
         return y, raws
 
     def tuning(self, B, H, W, dtype=torch.float16):
@@ -363,9 +368,9 @@ class YoloEngine:
     def forward_augment(self, im: torch.Tensor):
         """DetectionModel._predict_augment (nn/tasks.py:354-370) -> (y, None): three forwards at the scaled sizes, the scaled inputs
         made by bsy_scale_img, the passes clipped / descaled / concatenated by ONE bsy_tta_merge on the current stream.  A Segment
-        graph returns its single-scale forward, as the reference reverts for every class but DetectionModel (:356-358)."""
+        graph (and an OBB one) returns its single-scale forward, as the reference reverts for every class but DetectionModel (:356-358)."""
         with self._lock:
-            if self.meta["nm"]:
+            if self.meta["nm"] or self.meta["ne"]:
                 return self.forward(im)
             if im.device != self.device:
                 raise ValueError(f"input on {im.device}, engine on {self.device}")
@@ -411,7 +416,7 @@ class YoloEngine:
         B, _, H, W = im.shape
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
         m = plan.meta
-        y = torch.empty((B, 4 + m["nc"] + m["nm"], m["A"]), dtype=im.dtype, device=self.device)
+        y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
         ext, n = self._ext(im, y, [None, None, None])
         ms = (C.c_float * len(plan.ops))()
         stream = torch.cuda.current_stream(self.device).cuda_stream

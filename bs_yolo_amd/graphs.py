@@ -101,6 +101,8 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
         head.append([fam["detect_from"], 1, "Detect", ["nc"]])
     elif task == "segment":
         head.append([fam["detect_from"], 1, "Segment", ["nc", 32, 256]])
+    elif task == "obb":  # cfg/models/11/yolo11-obb.yaml:47, v8/yolov8-obb.yaml:46
+        head.append([fam["detect_from"], 1, "OBB", ["nc", 1]])
     else:
         raise ValueError(task)
     return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"], "head": head}

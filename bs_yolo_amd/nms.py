@@ -56,18 +56,55 @@ def nms_batched(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, class
     return det, counts
 
 
+def nms_rotated_batched(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False,
+                        multi_label=False, max_det=300, nc=0, max_nms=30000, max_wh=7680):
+    """non_max_suppression(rotated=True) (utils/ops.py:241-297 with nms_rotated :146-164), device-resident:
+    (det (B, max_det, 6+ne) fp32 rows [x, y, w, h, conf, cls, extra...], counts (B,) int32).  The prediction is not modified.
+    Suppression is the reference's fast-NMS (a candidate is dropped by ANY higher-scored candidate it overlaps, suppressed or
+    not), which keeps fewer boxes than greedy NMS on chains of overlaps.  No host synchronisation."""
+    if not prediction.is_cuda:
+        raise RuntimeError("bs_yolo_amd.nms needs a GPU tensor (no CPU fallback)")
+    if prediction.dim() != 3:
+        raise ValueError("prediction must be (B, 4+nc+ne, A)")
+    prediction = prediction.contiguous()
+    B, Cc, A = prediction.shape
+    nc = nc or (Cc - 4)
+    ne = Cc - nc - 4
+    dev = prediction.device
+    cls_t = None
+    if classes is not None:
+        cls_t = torch.as_tensor(list(classes), dtype=torch.int32, device=dev)
+    ml = bool(multi_label) and nc > 1
+    ws = _workspace(dev, L.lib.bsy_nms_rotated_workspace_bytes(B, A, nc, int(ml), int(max_nms)))
+    det = torch.empty((B, max_det, 6 + ne), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(L.lib.bsy_nms_rotated(C.c_void_p(prediction.data_ptr()), L.dtype_code(prediction.dtype), B, nc, ne, A,
+                                  float(conf_thres), float(iou_thres),
+                                  C.c_void_p(cls_t.data_ptr()) if cls_t is not None else None,
+                                  int(cls_t.numel()) if cls_t is not None else 0, int(bool(agnostic)), int(ml), int(max_det),
+                                  int(max_nms), float(max_wh), C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                  C.c_void_p(ws.data_ptr()), ws.numel(), stream))
+    return det, counts
+
+
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
                         labels=(), max_det=300, nc=0, max_time_img=0.05, max_nms=30000, max_wh=7680, in_place=True,
                         rotated=False) -> List[torch.Tensor]:
-    """Reference signature (utils/ops.py:167-182) -> list of (n_i, 6+nm) tensors in the prediction's dtype."""
+    """Reference signature (utils/ops.py:167-182) -> list of (n_i, 6+nm) tensors in the prediction's dtype.  rotated=True runs
+    bsy_nms_rotated; as in the reference, `labels` and `in_place` do not apply to it (ops.py:242, :256)."""
     assert 0 <= conf_thres <= 1, f"Invalid Confidence threshold {conf_thres}, valid values are between 0.0 and 1.0"
     assert 0 <= iou_thres <= 1, f"Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0"
     if isinstance(prediction, (list, tuple)):
         prediction = prediction[0]
-    if rotated or (labels is not None and len(labels)) or prediction.shape[-1] == 6:
-        raise NotImplementedError("rotated / autolabel / end2end NMS stay on the reference implementation")
-    det, counts = nms_batched(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc, max_nms,
-                              max_wh, in_place)
+    if prediction.shape[-1] == 6 or (not rotated and labels is not None and len(labels)):
+        raise NotImplementedError("autolabel / end2end NMS stay on the reference implementation")
+    if rotated:
+        det, counts = nms_rotated_batched(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc,
+                                          max_nms, max_wh)
+    else:
+        det, counts = nms_batched(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc, max_nms,
+                                  max_wh, in_place)
     n = counts.tolist()  # the only host sync
     # the reference yields rows in the prediction's dtype (ops.py:310 x[i]); empty images are fp32 zeros((0, 6+nm))
     out = []
@@ -80,6 +117,16 @@ def scale_boxes_batched(det: torch.Tensor, counts: torch.Tensor, img1_shape, img
     """scale_boxes + clip_boxes (utils/ops.py:92-127, :319-337) for a whole batch, in place on `det` (B, max_det, row).
     The gain / pad per image are computed on the host exactly as the reference does (Python round())."""
     B, max_det, row = det.shape
+    t = scale_params(B, img1_shape, img0_shapes, ratio_pads, det.device)
+    stream = C.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)
+    L.check(L.lib.bsy_scale_boxes(C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()), B, max_det, row,
+                                  C.c_void_p(t[0].data_ptr()), C.c_void_p(t[1].data_ptr()), C.c_void_p(t[2].data_ptr()),
+                                  C.c_void_p(t[3].data_ptr()), C.c_void_p(t[4].data_ptr()), stream))
+    return det
+
+
+def scale_params(B: int, img1_shape, img0_shapes, ratio_pads, dev) -> torch.Tensor:
+    """(5, B) f32 device tensor of gain, pad_x, pad_y, h0, w0 per image: scale_boxes' host arithmetic (utils/ops.py:110-118)."""
     gains, pxs, pys, h0s, w0s = [], [], [], [], []
     for b in range(B):
         h0, w0 = img0_shapes[b][:2]
@@ -89,10 +136,4 @@ def scale_boxes_batched(det: torch.Tensor, counts: torch.Tensor, img1_shape, img
         else:
             gain, pad = ratio_pads[b][0][0], ratio_pads[b][1]
         gains.append(gain); pxs.append(pad[0]); pys.append(pad[1]); h0s.append(h0); w0s.append(w0)
-    dev = det.device
-    t = torch.tensor([gains, pxs, pys, h0s, w0s], dtype=torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    L.check(L.lib.bsy_scale_boxes(C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()), B, max_det, row,
-                                  C.c_void_p(t[0].data_ptr()), C.c_void_p(t[1].data_ptr()), C.c_void_p(t[2].data_ptr()),
-                                  C.c_void_p(t[3].data_ptr()), C.c_void_p(t[4].data_ptr()), stream))
-    return det
+    return torch.tensor([gains, pxs, pys, h0s, w0s], dtype=torch.float32, device=dev)

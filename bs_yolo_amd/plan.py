@@ -662,8 +662,8 @@ class Plan:
                              lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype, mfma_flops=fl))
         self.flops += fl
 
-    def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0):
-        """head.py:21-148 (+ Segment :175-197)."""
+    def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0):
+        """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels)."""
         ch = [t.C for t in xs]
         c2, c3 = max(16, ch[0] // 4, 64), max(ch[0], min(nc, 100))
         boxes, clss, msks = [], [], []
@@ -671,8 +671,9 @@ class Plan:
         a0 = [sum(t.H * t.W for t in xs[:i]) for i in range(len(xs))]
         strides = [float(self.H // t.H) for t in xs]
         # Detect without mask coefficients: the last conv of every branch decodes in its epilogue (conv_mfma.hip
-        # conv_epilogue_head) -- no f32 logit maps, no decode launch, no raw-map transposes
-        fused = self.fuse_head and nm == 0 and len(xs) <= 3
+        # conv_epilogue_head) -- no f32 logit maps, no decode launch, no raw-map transposes.  An OBB head's box decode needs the
+        # angle of its cv4 branch (tal.py:404-423 dist2rbox), so OBB always takes the decode launch
+        fused = self.fuse_head and nm == 0 and ne == 0 and len(xs) <= 3
         # every (level, branch) chain is independent until the decoder: give each its own lane so the engine runs them
         # concurrently (the 40x40 / 20x20 chains are far too small to fill 256 CUs on their own)
         for i, x in enumerate(xs):
@@ -708,13 +709,23 @@ class Plan:
                 t = self.conv(f"{name}.cv4.{i}.0", x, c4, 3, 1)
                 t = self.conv(f"{name}.cv4.{i}.1", t, c4, 3, 1)
                 msks.append(self.conv(f"{name}.cv4.{i}.2", t, nm, 1, 1, act=False, plain=True, out_f32=True))
+            if ne:
+                # OBB.cv4 (head.py:208-209): Conv(x, c4, 3) -> Conv(c4, c4, 3) -> Conv2d(c4, ne, 1), on lanes of their own as Segment's.
+                # The angle logits land in an f32 map 8 channels wide (zero weights and bias past `ne`): the conv kernels write cout
+                # in 8-channel pieces and the decoder reads 16-byte rows; it passes them in the msk slots with nm = 0
+                self._lane = 2 * len(xs) + i
+                c4 = max(ch[0] // 4, ne)
+                t = self.conv(f"{name}.cv4.{i}.0", x, c4, 3, 1)
+                t = self.conv(f"{name}.cv4.{i}.1", t, c4, 3, 1)
+                msks.append(self.conv(f"{name}.cv4.{i}.2", t, make_divisible(ne, 8), 1, 1, act=False, plain=True, out_f32=True,
+                                      real=(ne, 0)))
         self._lane = 0
-        self.meta.update(A=A, nc=nc, nm=nm, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
+        self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
         if fused:
             return
-        self.ops.append(dict(kind=L.OP_DECODE, join=1, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=nm, A=A, box=boxes,
+        self.ops.append(dict(kind=L.OP_DECODE, join=1, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=nm, ne=ne, A=A, box=boxes,
                              cls=clss, msk=msks, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs], lvl_stride=strides,
-                             dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm, 0, 0), out_dtype=self.out_dtype,
+                             dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne, 0, 0), out_dtype=self.out_dtype,
                              name=name + ".decode"))
         for i in range(len(xs)):
             self.ops.append(dict(kind=L.OP_RAW_NCHW, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=0, A=A,
@@ -722,7 +733,7 @@ class Plan:
                                  lvl_stride=strides, level=i,
                                  dst=T(L.BSY_EXT_BASE + self.EXT_RAW0 + i, 0, 0, 64 + nc, 0, 0),
                                  out_dtype=self.out_dtype, name=f"{name}.raw{i}"))
-        self.meta.update(A=A, nc=nc, nm=nm, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
+        self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
 
     # ---- graph walk (nn/tasks.py:138-165 + :940-1105) -----------------------------------------------------------
     def _build(self):
@@ -827,7 +838,7 @@ class Plan:
                 assert all(isinstance(t, T) for t in x)
                 y = list(x)
                 cout = sum(t.C for t in x)
-            elif m in ("Detect", "Segment"):
+            elif m in ("Detect", "Segment", "OBB"):
                 xs = x if isinstance(x, list) else [x]
                 assert all(isinstance(t, T) for t in xs)
                 if m == "Segment":  # head.py:175-197; npr scaled like parse_model does (tasks.py:1082-1083)
@@ -835,6 +846,11 @@ class Plan:
                     npr = make_divisible(min(args[2], max_ch) * width, 8)
                     self.proto(name + ".proto", xs[0], npr, nm)
                     self.detect(name, xs, args[0], legacy, nm=nm)
+                elif m == "OBB":  # head.py:200-227, args [nc, ne] (+ the channel list parse_model appends, tasks.py:1075)
+                    ne = args[1] if len(args) > 1 and not isinstance(args[1], (list, tuple)) else 1
+                    if ne != 1:
+                        raise NotImplementedError(f"OBB with ne = {ne}: dist2rbox (utils/tal.py:404-423) decodes one angle")
+                    self.detect(name, xs, args[0], legacy, ne=ne)
                 else:
                     self.detect(name, xs, args[0], legacy)
                 y, cout = None, 0
@@ -995,6 +1011,7 @@ class Plan:
             o.heads, o.key_dim, o.head_dim, o.scale = d.get("heads", 0), d.get("key_dim", 0), d.get("head_dim", 0), \
                 d.get("scale", 0.0)
             o.nl, o.nc, o.nm, o.A = d.get("nl", 0), d.get("nc", 0), d.get("nm", 0), d.get("A", 0)
+            o.ne = d.get("ne", 0)
             for j in range(3):
                 o.box[j] = v(d["box"][j] if j < len(d.get("box", [])) else None)
                 o.cls[j] = v(d["cls"][j] if j < len(d.get("cls", [])) else None)

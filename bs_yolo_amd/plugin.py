@@ -42,7 +42,7 @@ from .engine import YoloEngine
 from .plan import Plan
 from .weights import BN_EPS
 
-SUPPORTED_HEADS = ("Detect", "Segment")
+SUPPORTED_HEADS = ("Detect", "Segment", "OBB")
 
 
 def _on_device(t) -> bool:
@@ -575,11 +575,17 @@ def uninstall(model) -> int:
     return n
 
 
-def install_nms(ops_module):
-    """ops_module = ultralytics.utils.ops.  GPU tensors go to the HIP NMS; everything else to the original."""
+def install_nms(ops_module, rotated: bool = False):
+    """ops_module = ultralytics.utils.ops.  GPU tensors go to the HIP NMS; everything else to the original.
+    rotated=True also takes the OBB calls (``rotated=True``, obb/predict.py:33-41) onto bsy_nms_rotated -- the working path for the
+    fork, whose own rotated NMS raises NameError (utils/ops.py:14 leaves batch_probiou unimported); by default they stay on the
+    original."""
     orig = ops_module.non_max_suppression
     if getattr(orig, "_bsy", False):
-        return orig
+        if getattr(orig, "_bsy_rotated", False) == bool(rotated):
+            return orig
+        orig = orig._bsy_orig  # installed before with the other `rotated` choice: wrap the original again
+    take_rotated = bool(rotated)
 
     def non_max_suppression(prediction, *args, **kwargs):
         p = prediction[0] if isinstance(prediction, (list, tuple)) else prediction
@@ -587,12 +593,13 @@ def install_nms(ops_module):
         # labels (5), max_det, nc, max_time_img, max_nms, max_wh, in_place, rotated (12)
         rotated = kwargs.get("rotated", False) or (len(args) > 12 and args[12])
         labels = kwargs.get("labels", ()) or (args[5] if len(args) > 5 else ())
-        if (not isinstance(p, torch.Tensor)) or (not _on_device(p)) or rotated or len(labels) or p.shape[-1] == 6 \
-                or p.dtype not in (torch.float16, torch.float32):
+        if (not isinstance(p, torch.Tensor)) or (not _on_device(p)) or (rotated and not take_rotated) \
+                or (len(labels) and not rotated) or p.shape[-1] == 6 or p.dtype not in (torch.float16, torch.float32):
             return orig(prediction, *args, **kwargs)
         return _nms.non_max_suppression(prediction, *args, **kwargs)
 
     non_max_suppression._bsy = True
+    non_max_suppression._bsy_rotated = take_rotated
     non_max_suppression._bsy_orig = orig
     ops_module.non_max_suppression = non_max_suppression
     return non_max_suppression

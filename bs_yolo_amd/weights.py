@@ -243,7 +243,7 @@ def synth_state_dict(plan: Plan, seed: int = 0, cls_gain: float = 0.1, cls_bias:
             elif ".cv2." in r.name:
                 sd[r.name + ".bias"] = torch.rand(r.cout, generator=g) + 0.5
             else:
-                sd[r.name + ".bias"] = torch.rand(r.cout, generator=g) * 0.4 - 0.2
+                sd[r.name + ".bias"] = torch.rand(r.real_cout or r.cout, generator=g) * 0.4 - 0.2
             continue
         cin = 1 if r.kind == "dw" else (r.real_cin or r.cin)
         fan = cin * r.k * r.k

@@ -140,7 +140,8 @@ typedef struct bsy_op {
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
                              * by two f16 planes [Cout][K rounded up to 32] (hi, lo), each part padded to 256 bytes */
-    int32_t reserved0;
+    int32_t ne;             /* DECODE: angle channels (OBB head, head.py:200-227): 0 or 1.  With ne = 1 (and nm = 0) msk[l] is the level's
+                             * f32 angle-logit map; y gets the dist2rbox boxes (utils/tal.py:404-423) and the angle as row 4 + nc */
     int32_t ksplit;         /* CONV, latency-mode plans (round 4): 0 = off; else (channel slices) | (tap slices) << 8 of the layer's K walk.  The
                              * slices are computed by separate workgroups of one launch into f32 slabs in the workspace buffer box[0]
                              * (slices x B x OH x OW x round_up(Cout, 32) floats) and summed IN SLICE ORDER by a second launch that applies
@@ -336,6 +337,31 @@ int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A, float conf
             const int32_t* classes, int n_classes, int agnostic, int multi_label, int max_det, int max_nms,
             float max_wh, int in_place, float* out, int32_t* counts, void* workspace, size_t workspace_bytes,
             bsy_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * non_max_suppression(..., rotated=True) (utils/ops.py:241-297) with nms_rotated (:146-164) and batch_probiou
+ * (utils/metrics.py:261-278, :327-358), whole batch, no host sync (csrc/obb.hip).
+ *   pred      : (B, 4+nc+ne, A) f16/f32, xywh boxes + class scores + ne extra rows; theta = the LAST column of a
+ *               candidate's row (x[:, -1:], ops.py:292), i.e. the last extra row (the class index when ne = 0).
+ *               Never modified (rotated boxes are not converted to xyxy).
+ *   Candidates: the filter and key sort of bsy_nms (score descending, ties by ascending index), at most max_nms.
+ *   Suppression is FAST-NMS, not greedy: sorted candidate i is kept iff probiou(j, i) < iou_thres for EVERY j < i,
+ *               suppressed j included (ious.triu_(1).max(0) < thr); a NaN probiou suppresses, iou_thres = 0 keeps
+ *               nothing.  probiou in fp32 in the reference's operation order, precise logf/expf/sqrtf/cosf/sinf, on
+ *               (x + cls*max_wh, y + cls*max_wh, w, h, theta) (offset 0 when agnostic).
+ *   out       : (B, max_det, 6+ne) f32 rows [x, y, w, h, conf, cls, extra...], rows >= counts[b] are zero
+ *   workspace : DEVICE scratch of at least bsy_nms_rotated_workspace_bytes(...) bytes
+ * --------------------------------------------------------------------------------------------------------- */
+size_t bsy_nms_rotated_workspace_bytes(int B, int A, int nc, int multi_label, int max_nms);
+int bsy_nms_rotated(void* pred, int pred_dtype, int B, int nc, int ne, int A, float conf_thres, float iou_thres,
+                    const int32_t* classes, int n_classes, int agnostic, int multi_label, int max_det, int max_nms,
+                    float max_wh, float* out, int32_t* counts, void* workspace, size_t workspace_bytes, bsy_stream stream);
+/* OBBPredictor.postprocess's per-image tail (models/yolo/obb/predict.py:48-49) in place on bsy_nms_rotated's rows
+ * (row >= 7, theta in the last column): regularize_rboxes (ops.py:775-791: w / h swapped when h >= w, theta' =
+ * (w > h ? theta : theta + pi/2) mod pi as torch's fp32 remainder), then scale_boxes(xywh=True) (pad off x and y only,
+ * all four divided by gain) and clip_boxes (columns 0 / 2 to [0, w0], 1 / 3 to [0, h0]).  gain / pads as bsy_scale_boxes. */
+int bsy_obb_scale(float* det, const int32_t* counts, int B, int max_det, int row, const float* gain, const float* pad_x,
+                  const float* pad_y, const float* h0, const float* w0, bsy_stream stream);
 
 /* scale_boxes + clip_boxes (utils/ops.py:92-127, :319-337) applied to all rows of `out` in place:
  * per image b: gain[b], pad_x[b], pad_y[b] (HOST-computed with Python round()), orig shape (h0[b], w0[b]). */
