@@ -34,6 +34,7 @@ SOURCES = {
     "detect.hip": [],
     "nms.hip": ["-ffp-contract=off"],
     "obb.hip": ["-ffp-contract=off"],
+    "topk.hip": [],
     "letterbox.hip": ["-ffp-contract=off"],
     "masks.hip": ["-ffp-contract=off"],
     "val_match.hip": ["-ffp-contract=off"],

@@ -287,3 +287,27 @@ def tta_merge(ys: Sequence[torch.Tensor], windows: Sequence[tuple], scales: Sequ
                                 (C.c_float * n)(*[float(s) for s in scales]), (i32 * n)(*[int(f or 0) for f in flips]), n, B, no,
                                 int(img_hw[0]), int(img_hw[1]), L.dtype_code(y0.dtype), _p(out), _stream(out)))
     return out
+
+
+def end2end_topk(pred: torch.Tensor, max_det: int = 300, out: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """v10Detect.postprocess(pred.permute(0, 2, 1), max_det, nc) (nn/modules/head.py:151-172) in two launches (bsy_end2end_topk):
+    pred (B, 4+nc, A) fp16 / fp32 on the device -> (B, min(max_det, A), 6) fp32 rows [box, score, class].  Ties go to the lower
+    anchor, then the lower class (include/bsyolo.h).  No host synchronisation; `out` / `workspace` may be preallocated (graph capture)."""
+    if not pred.is_cuda:
+        raise RuntimeError("bs_yolo_amd.ops.end2end_topk needs a GPU tensor (no CPU fallback)")
+    if pred.dim() != 3 or pred.shape[1] < 5:
+        raise ValueError("pred must be (B, 4+nc, A)")
+    pred = pred.contiguous()
+    B, Cc, A = pred.shape
+    nc = Cc - 4
+    K = min(int(max_det), A)
+    nbytes = L.lib.bsy_end2end_topk_workspace_bytes(B, A, nc, int(max_det))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=pred.device)
+    if out is None:
+        out = torch.empty((B, K, 6), dtype=torch.float32, device=pred.device)
+    assert out.is_contiguous() and tuple(out.shape) == (B, K, 6) and out.dtype == torch.float32
+    L.check(L.lib.bsy_end2end_topk(_p(pred), L.dtype_code(pred.dtype), B, nc, A, int(max_det), _p(out), _p(workspace),
+                                   workspace.numel() * workspace.element_size(), _stream(pred)))
+    return out

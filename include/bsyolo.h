@@ -363,6 +363,24 @@ int bsy_nms_rotated(void* pred, int pred_dtype, int B, int nc, int ne, int A, fl
 int bsy_obb_scale(float* det, const int32_t* counts, int B, int max_det, int row, const float* gain, const float* pad_x,
                   const float* pad_y, const float* h0, const float* w0, bsy_stream stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * v10Detect.postprocess (nn/modules/head.py:151-172), the NMS-free end-to-end top-k, whole batch, no host sync and no
+ * allocation (csrc/topk.hip): safe inside a captured graph.
+ *   pred      : (B, 4+nc, A) f16/f32 contiguous, boxes (any 4-value format, copied as stored) + class scores.
+ *   K         : min(max_det, A).  Stage 1 keeps the K anchors with the highest best-class score; stage 2 keeps the K
+ *               highest of those anchors' K x nc class scores.  An anchor may appear once per class; a class score of
+ *               an anchor that missed stage 1 never appears (this is not a global top-K over A x nc).
+ *   Ties      : deterministic -- higher score first, then lower anchor index, then lower class index (torch's topk
+ *               leaves the order of equal values unspecified).  Scores are compared as stored (f16 values for an f16
+ *               prediction); NaN ranks above +inf, -0 equals +0.  The rows carry the scores as stored.
+ *   out       : (B, K, 6) f32 rows [box0..box3, score, class], score-descending.
+ *   Bounds    : 1 <= max_det <= 4096, B <= 65535, A * nc <= 2^30; anything else is BSY_ERR_ARG before any launch.
+ *   workspace : DEVICE scratch of at least bsy_end2end_topk_workspace_bytes(...) bytes.
+ * --------------------------------------------------------------------------------------------------------- */
+size_t bsy_end2end_topk_workspace_bytes(int B, int A, int nc, int max_det);
+int bsy_end2end_topk(const void* pred, int pred_dtype, int B, int nc, int A, int max_det, float* out, void* workspace,
+                     size_t workspace_bytes, bsy_stream stream);
+
 /* scale_boxes + clip_boxes (utils/ops.py:92-127, :319-337) applied to all rows of `out` in place:
  * per image b: gain[b], pad_x[b], pad_y[b] (HOST-computed with Python round()), orig shape (h0[b], w0[b]). */
 int bsy_scale_boxes(float* det, const int32_t* counts, int B, int max_det, int row, const float* gain,
