@@ -321,6 +321,8 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(const NmsK p) {
     if (tid == 0) p.counts[b] = sh_i[1];
 }
 
+#define NMS_MAX_DET 4096  // the kept boxes live in LDS: 20 bytes each (bsy_nms sizes the launch)
+
 static int next_pow2(long long v) {
     long long p = 2;
     while (p < v) p <<= 1;
@@ -346,7 +348,7 @@ extern "C" int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A,
         BSY_FAIL(BSY_ERR_ARG, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
     if (!(iou_thres >= 0.f && iou_thres <= 1.f))
         BSY_FAIL(BSY_ERR_ARG, "Invalid IoU %g, valid values are between 0.0 and 1.0", iou_thres);
-    if (max_det <= 0 || max_det > 4096) BSY_FAIL(BSY_ERR_ARG, "nms: max_det %d out of range (1..4096)", max_det);
+    if (max_det <= 0 || max_det > NMS_MAX_DET) BSY_FAIL(BSY_ERR_ARG, "nms: max_det %d out of range (1..%d)", max_det, NMS_MAX_DET);
     if (max_nms <= 0) BSY_FAIL(BSY_ERR_ARG, "nms: max_nms must be positive");
     if (pred_dtype != BSY_F16 && pred_dtype != BSY_F32) BSY_FAIL(BSY_ERR_ARG, "nms: dtype %d unsupported", pred_dtype);
     if ((long long)A * nc > 0x7fffffffLL) BSY_FAIL(BSY_ERR_ARG, "nms: A*nc too large");
@@ -367,6 +369,15 @@ extern "C" int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A,
     HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * max_det * (6 + nm) * sizeof(float), s));
     dim3 g1((A + 255) / 256, B);
     const size_t lds = 12 * 8 + 4 * 4 + ((size_t)256 * 5 + (size_t)max_det * 5) * 4;
+    // 112 + (1280 + 5 * max_det) * 4 bytes: 87 152 at the ABI's max_det = 4096.  Above 64 KiB a launch needs the function
+    // attribute (gfx950 has 160 KiB of LDS per CU); it is set once per process, for the bound's size.
+    static bool attr_set = false;
+    if (!attr_set) {
+        const int lds_max = (int)(12 * 8 + 4 * 4 + ((size_t)256 * 5 + (size_t)NMS_MAX_DET * 5) * 4);
+        HIP_TRY(hipFuncSetAttribute((const void*)nms_greedy_kernel<half_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        HIP_TRY(hipFuncSetAttribute((const void*)nms_greedy_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        attr_set = true;
+    }
     if (pred_dtype == BSY_F16) {
         if (!multi_label && !(A & 3) && !((uintptr_t)pred & 7))
             hipLaunchKernelGGL(nms_filter4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);

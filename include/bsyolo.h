@@ -328,6 +328,8 @@ int bsy_detect_decode(const float* const* box, const int* ldb, const float* cons
  *   classes   : optional DEVICE int32 list of class ids to keep (:278-279), n_classes = 0 -> all
  *   out       : (B, max_det, 6+nm) f32 rows [x1,y1,x2,y2,conf,cls,masks...], rows >= counts[b] are zero
  *   counts    : (B) int32 kept detections per image
+ *   max_det   : 1 .. 4096, BSY_ERR_ARG outside.  The kept boxes are held in LDS, 112 + (1280 + 5 * max_det) * 4 bytes per
+ *               image's workgroup (87 152 at 4096; launches above 64 KiB are enabled by a function attribute)
  *   workspace : DEVICE scratch of at least bsy_nms_workspace_bytes(...) bytes
  * Arithmetic is fp32 whatever the input dtype (matches the fp32 CPU reference); ties in score are broken by
  * ascending candidate index.  The reference's wall-clock bail-out (:238,:312-314) is deliberately absent.

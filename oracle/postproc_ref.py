@@ -184,3 +184,115 @@ def process_mask_native(protos, masks_in, bboxes, shape):  # utils/ops.py:696-70
     masks = scale_masks(masks[None], shape)[0]
     masks = crop_mask(masks, bboxes)
     return masks.gt_(0.0)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# float64 restatement of the mask functions, with a per-pixel error bound (tests/test_postprocess_edges.py)
+# ------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24  # fp32 unit roundoff
+
+
+def _src_index(n_in: int, n_out: int, fused: bool = True):
+    """aten's area_pixel_compute_source_index (align_corners=False, size given): the source coordinate and the two
+    weights are part of the operation's definition and are fp32 for fp32 / fp16 tensors, so they are computed in
+    fp32 here as well and only then widened.  `fused`: scale * (dst + 0.5) - 0.5 rounded once (a fused multiply-add,
+    what ATen's builds do -- the CPU kernels here reproduce it bit for bit) or after each operation (what
+    csrc/masks.hip does, compiled with -ffp-contract=off); the two coordinates differ by at most one fp32 ulp."""
+    f = np.float32
+    scale = f(n_in) / f(n_out)
+    d = np.arange(n_out, dtype=np.float32) + f(0.5)
+    s = (np.float64(scale) * d.astype(np.float64) - 0.5).astype(np.float32) if fused else scale * d - f(0.5)
+    s = np.maximum(s, f(0))
+    i0 = s.astype(np.int64)
+    i1 = i0 + (i0 < n_in - 1)
+    l1 = s - i0.astype(np.float32)
+    l0 = f(1) - l1
+    return i0, i1, l0.astype(np.float64), l1.astype(np.float64)
+
+
+def bilinear64(src: np.ndarray, oh: int, ow: int, fused: bool = True) -> np.ndarray:
+    """F.interpolate(src, (oh, ow), mode="bilinear", align_corners=False) over the last two axes, float64 sums."""
+    y0, y1, ly0, ly1 = _src_index(src.shape[-2], oh, fused)
+    x0, x1, lx0, lx1 = _src_index(src.shape[-1], ow, fused)
+    top, bot = src[..., y0, :], src[..., y1, :]
+    return (ly0[:, None] * (lx0 * top[..., x0] + lx1 * top[..., x1]) +
+            ly1[:, None] * (lx0 * bot[..., x0] + lx1 * bot[..., x1]))
+
+
+def crop_inside(boxes: torch.Tensor, h: int, w: int) -> np.ndarray:
+    """crop_mask's (n, h, w) in-box predicate, fp32 comparisons as the reference makes them (utils/ops.py:656-660)."""
+    x1, y1, x2, y2 = torch.chunk(boxes.float()[:, :, None], 4, 1)
+    r = torch.arange(w, dtype=x1.dtype)[None, None, :]
+    c = torch.arange(h, dtype=x1.dtype)[None, :, None]
+    return ((r >= x1) * (r < x2) * (c >= y1) * (c < y2)).numpy().astype(bool)
+
+
+def _lowres64(protos, masks_in):
+    """(n, mh, mw) float64 masks, S = sum_k |c_k p_k| and the fp32 dot-product bound (nm + 2) * 2^-24 * S, which holds
+    for any summation order (fused or not) of an nm-term fp32 dot product."""
+    c, mh, mw = protos.shape
+    P = protos.detach().double().numpy().reshape(c, -1)  # fp16 prototypes: the reference upcasts them (protos.float())
+    Cf = masks_in.detach().double().numpy()
+    low = (Cf @ P).reshape(-1, mh, mw)
+    S = (np.abs(Cf) @ np.abs(P)).reshape(-1, mh, mw)
+    return low, S, (c + 2) * U32 * S
+
+
+def process_mask64(protos, masks_in, bboxes, shape, upsample=False, fused=True):
+    """process_mask in float64 -> (v, e): the pre-threshold value per output pixel and a bound on what an fp32
+    implementation may differ from it.  The crop arithmetic on the boxes is the reference's own fp32 (bboxes.clone(),
+    *= mw / iw).  e = e_low without the resize, interp(e_low) + 8 * 2^-24 * interp(S) with it.  Where the crop zeroes
+    every contributing pixel, v = e = 0 exactly: such a pixel is known to be 0, not ambiguous (see classify_masks)."""
+    c, mh, mw = protos.shape
+    ih, iw = shape
+    low, S, e_low = _lowres64(protos, masks_in)
+    db = bboxes.detach().float().clone()
+    db[:, 0] *= mw / iw
+    db[:, 2] *= mw / iw
+    db[:, 3] *= mh / ih
+    db[:, 1] *= mh / ih
+    inside = crop_inside(db, mh, mw)
+    low, S, e_low = low * inside, S * inside, e_low * inside
+    if not upsample:
+        return low, e_low
+    return bilinear64(low, ih, iw, fused), bilinear64(e_low, ih, iw, fused) + 8 * U32 * bilinear64(S, ih, iw, fused)
+
+
+def _window64(mh, mw, shape, padding=True):
+    gain = min(mh / shape[0], mw / shape[1])
+    pad = [mw - shape[1] * gain, mh - shape[0] * gain]
+    if padding:
+        pad[0] /= 2
+        pad[1] /= 2
+    top, left = (int(pad[1]), int(pad[0])) if padding else (0, 0)
+    return top, left, int(mh - pad[1]), int(mw - pad[0])
+
+
+def scale_masks64(masks, shape, padding=True, fused=True):
+    """scale_masks in float64 -> (v, e) with e = 8 * 2^-24 * interp(|masks|) (four products, three sums)."""
+    m = masks.detach().double().numpy()
+    top, left, bottom, right = _window64(m.shape[-2], m.shape[-1], shape, padding)
+    m = m[..., top:bottom, left:right]
+    return bilinear64(m, shape[0], shape[1], fused), 8 * U32 * bilinear64(np.abs(m), shape[0], shape[1], fused)
+
+
+def process_mask_native64(protos, masks_in, bboxes, shape, fused=True):
+    """process_mask_native in float64 -> (v, e); the crop (boxes in output pixels, fp32 comparisons) comes last."""
+    c, mh, mw = protos.shape
+    low, S, e_low = _lowres64(protos, masks_in)
+    top, left, bottom, right = _window64(mh, mw, shape, True)
+    w = (slice(None), slice(top, bottom), slice(left, right))
+    v = bilinear64(low[w], shape[0], shape[1], fused)
+    e = bilinear64(e_low[w], shape[0], shape[1], fused) + 8 * U32 * bilinear64(S[w], shape[0], shape[1], fused)
+    inside = crop_inside(bboxes.detach().float(), shape[0], shape[1])
+    return v * inside, e * inside
+
+
+def classify_masks(got, v, e):
+    """Compare a 0/1 mask with the float64 reference: (number of mismatching pixels that are NOT ambiguous, number of
+    mismatching pixels, ambiguous share of the case).  A pixel is ambiguous iff |v| <= e and e > 0; e == 0 means the
+    crop removed every contribution, the value is exactly 0 in any arithmetic and the mask must be 0."""
+    got = np.asarray(got)
+    amb = (np.abs(v) <= e) & (e > 0)
+    diff = (got != 0) != (v > 0)
+    return int((diff & ~amb).sum()), int(diff.sum()), float(amb.mean())

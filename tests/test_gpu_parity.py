@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN
+from postproc_helpers import nms_compare as _nms_compare, nms_compare_fp16 as _nms_compare_fp16, rand_pred as _rand_pred
 
 pytestmark = pytest.mark.gpu
 
@@ -1537,20 +1538,6 @@ def test_ap_per_class_golden_and_large():
     assert e[5].shape == (2, 10) and not e[5].any() and e[11].shape == (0, 1000) and list(e[6]) == [1, 3]
 
 
-def _nms_compare(pred, kw):
-    ref_in = pred.clone()
-    ref = PP.non_max_suppression(ref_in, **kw)
-    dpred = pred.clone().to(DEV)
-    got = HN.non_max_suppression(dpred, **kw)
-    torch.cuda.synchronize()
-    assert len(got) == len(ref)
-    if kw.get("in_place", True):
-        assert torch.equal(dpred[:, :4].cpu(), ref_in[:, :4])  # same in-place xywh->xyxy mutation
-    for b, (g_, r_) in enumerate(zip(got, ref)):
-        assert tuple(g_.shape) == tuple(r_.shape), (b, g_.shape, r_.shape)
-        assert torch.equal(g_.cpu(), r_), f"image {b}"
-
-
 def test_nms_golden_cases():
     z = np.load(GOLDEN / "nms.npz")
     for tag, kw, n_out in json.loads(str(z["cases"])):
@@ -1564,19 +1551,6 @@ def test_nms_golden_cases():
             exp = z[f"{tag}.out{i}"]
             assert tuple(r.shape) == exp.shape, (tag, i, r.shape, exp.shape)
             assert np.array_equal(r.cpu().numpy(), exp), f"{tag}[{i}]"
-
-
-def _rand_pred(B, nc, A, nm, seed, dup=True):
-    g = torch.Generator().manual_seed(seed)
-    base = max(A // 6, 1)
-    c = torch.rand(B, 2, base, generator=g) * 600 + 20
-    wh = torch.rand(B, 2, base, generator=g) * 120 + 8
-    rep = (A + base - 1) // base
-    box = torch.cat((c, wh), 1).repeat(1, 1, rep)[:, :, :A] + torch.randn(B, 4, A, generator=g) * (3.0 if dup else 50.0)
-    box[:, 2:] = box[:, 2:].abs() + 1
-    cls = torch.rand(B, nc, A, generator=g) ** 4
-    parts = [box, cls] + ([torch.randn(B, nm, A, generator=g)] if nm else [])
-    return torch.cat(parts, 1)
 
 
 @pytest.mark.parametrize("kw", [
@@ -1613,18 +1587,7 @@ def test_nms_large_candidate_set_and_cap():
 def test_nms_fp16_prediction():
     """fp16 predictions: boxes are converted in fp16 (as the reference's in-place op does), decisions in fp32."""
     pred = _rand_pred(2, 12, 2000, 0, 13).half()
-    kw = dict(conf_thres=0.25, iou_thres=0.7)
-    dpred = pred.clone().to(DEV)
-    got = HN.non_max_suppression(dpred, **kw)
-    torch.cuda.synchronize()
-    ref_in = pred.clone()
-    tp = ref_in.transpose(-1, -2)
-    tp[..., :4] = PP.xywh2xyxy(tp[..., :4])  # fp16 arithmetic on the CPU
-    assert torch.equal(dpred[:, :4].cpu(), ref_in[:, :4])
-    ref = PP.non_max_suppression(ref_in.float(), boxes_xyxy=True, **kw)
-    for g_, r_ in zip(got, ref):
-        assert g_.dtype == torch.float16
-        assert torch.equal(g_.float().cpu(), r_.half().float())
+    _nms_compare_fp16(pred, dict(conf_thres=0.25, iou_thres=0.7))
 
 
 def test_nms_properties_at_full_size():
@@ -1675,6 +1638,11 @@ def test_process_mask_matches_oracle(upsample, pdtype):
     assert got.shape == ref.shape and got.dtype == torch.float32
     mism = (got.cpu() != ref).float().mean().item()
     assert mism < 2e-4, mism
+    # ... and where they are: every pixel that differs from the float64 value's sign lies inside the fp32 error band of zero
+    # (oracle.postproc_ref.process_mask64; fused=False: masks.hip rounds the source coordinate after each operation)
+    v, e = PP.process_mask64(protos, coef, boxes, (ih, iw), upsample, fused=False)
+    bad, ndiff, amb = PP.classify_masks(got.cpu().numpy(), v, e)
+    assert bad == 0 and amb <= 1e-4, (bad, ndiff, amb)
     # empty input: (0, h, w)
     e = HM.process_mask(protos.to(DEV), coef[:0].to(DEV), boxes[:0].to(DEV), (ih, iw), upsample)
     assert e.shape[0] == 0
@@ -2107,6 +2075,9 @@ def test_process_mask_native_and_scale_masks_match_reference_golden():
             w16 = PP.process_mask_native(ph.float(), coef, boxes, shape).numpy().astype(np.uint8)
             d16 = g16.cpu().numpy() != w16
             assert d16.mean() < 1e-4, (ci, d16.mean())
+            v, e = PP.process_mask_native64(ph, coef, boxes, shape, fused=False)  # classified: mismatches only inside the fp32 band of zero
+            bad, ndiff, amb = PP.classify_masks(g16.cpu().numpy(), v, e)
+            assert bad == 0 and amb <= 1e-4, (ci, bad, ndiff, amb)
             s16 = HM.scale_masks(ph[None, :2].to(DEV), shape)
             assert s16.dtype == torch.float16
             np.testing.assert_allclose(s16.float().cpu().numpy(), PP.scale_masks(ph[None, :2].float(), shape).numpy(), rtol=0, atol=2e-3)
