@@ -38,6 +38,7 @@ SOURCES = {
     "letterbox.hip": ["-ffp-contract=off"],
     "masks.hip": ["-ffp-contract=off"],
     "val_match.hip": ["-ffp-contract=off"],
+    "val_masks.hip": ["-ffp-contract=off"],
     "val_ap.hip": ["-ffp-contract=off"],
     "sahi.hip": ["-ffp-contract=off"],
     "tta.hip": [],  # default contraction, as ATen's bilinear kernel is built; the merge turns it off with a pragma

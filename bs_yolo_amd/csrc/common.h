@@ -319,6 +319,10 @@ int launch_decode(const DecodeArgs& a, hipStream_t s);
 // bsy_nms's candidate keys (nms.hip steps 1-2) for another consumer: filter + sort, the prediction left untouched
 int nms_candidates(void* pred, int pred_dtype, int B, int nc, int C, int A, float conf_thres, const int32_t* classes, int n_classes,
                    int multi_label, int cap, unsigned long long* keys, int32_t* cand_count, hipStream_t s);
+// val_match.hip: the validator's matching rule on an IoU matrix (B, Lmax, max_det) made elsewhere (val_masks.hip); arguments as
+// bsy_val_match's, already validated by the caller
+int val_match_from_iou(const float* iou, const float* det, int row, const int32_t* counts, int B, int max_det, const float* gt_cls,
+                       const int32_t* gt_counts, int Lmax, const float* iouv_host, int n_iou, unsigned char* out, hipStream_t s);
 int launch_nhwc2nchw(const half_t* src, int ld, int B, int C, int hw, void* out, int out_dtype, hipStream_t s);
 int launch_raw_nchw(const float* box, int ldb, const float* cls, int ldc, int B, int h, int w, int nc, void* out,
                     int out_dtype, hipStream_t s);

@@ -15,6 +15,7 @@
 //   4. obb_compact_kernel  (workgroup = image): order-preserving compaction of the kept flags, cut at max_det (exact: the
 //      decisions of the first max_det kept candidates do not depend on the ones after them).
 #include "common.h"
+#include "probiou.h"
 
 typedef unsigned long long u64;
 
@@ -66,37 +67,16 @@ __global__ __launch_bounds__(256) void obb_gather_kernel(const ObbK p) {
     // theta = the last column of the candidate's row (ops.py:292 x[:, -1:]): the last extra row, the class index without one
     const float th = p.ne ? (float)pb[(size_t)(p.C - 1) * p.A + anchor] : (float)cls;
     const float off = (float)cls * (p.agnostic ? 0.0f : p.max_wh);
-    // _get_covariance_matrix (metrics.py:272-278): (w^2 / 12, h^2 / 12, theta) -> a cos^2 + b sin^2, a sin^2 + b cos^2, (a - b) cos sin
-    const float ga = (w * w) / 12.0f, gb = (h * h) / 12.0f;
-    const float cs = cosf(th), sn = sinf(th);
-    const float cos2 = cs * cs, sin2 = sn * sn;
-    const float ca = ga * cos2 + gb * sin2, cb = ga * sin2 + gb * cos2, cc = ((ga - gb) * cs) * sn;
-    const float d = ca * cb - cc * cc;
+    const ObbCov g = obb_covariance(w, h, th);  // probiou.h
     float* cv = p.cov + ((size_t)b * p.nmax + i) * 8;
     float* rw = p.rows + ((size_t)b * p.nmax + i) * 8;
-    *reinterpret_cast<f32x4*>(cv) = f32x4{x + off, y + off, ca, cb};
-    *reinterpret_cast<f32x4*>(cv + 4) = f32x4{cc, d < 0.0f ? 0.0f : d, 0.0f, 0.0f};  // clamp_(0) keeps a NaN
+    *reinterpret_cast<f32x4*>(cv) = f32x4{x + off, y + off, g.a, g.b};
+    *reinterpret_cast<f32x4*>(cv + 4) = f32x4{g.c, g.det, 0.0f, 0.0f};
     *reinterpret_cast<f32x4*>(rw) = f32x4{x, y, w, h};
     *reinterpret_cast<f32x4*>(rw + 4) = f32x4{score, (float)cls, __int_as_float(anchor), 0.0f};
 }
 
-// batch_probiou (metrics.py:342-358) of obb1 = j and obb2 = i, the reference's operation order; (x, y, a, b, c, det) as gathered
-__device__ __forceinline__ float probiou(const f32x4 j0, const float jc, const float jd, const f32x4 i0, const float ic, const float id) {
-    const float eps = 1e-7f;
-    const float x1 = j0[0], y1 = j0[1], a1 = j0[2], b1 = j0[3];
-    const float x2 = i0[0], y2 = i0[1], a2 = i0[2], b2 = i0[3];
-    const float sa = a1 + a2, sb = b1 + b2, sc = jc + ic;
-    const float dy = y1 - y2, dx = x1 - x2;
-    const float core = sa * sb - sc * sc;
-    const float t1 = ((sa * (dy * dy) + sb * (dx * dx)) / (core + eps)) * 0.25f;
-    const float t2 = (((sc * (x2 - x1)) * dy) / (core + eps)) * 0.5f;
-    const float t3 = logf(core / (4.0f * sqrtf(jd * id) + eps) + eps) * 0.5f;
-    float bd = t1 + t2 + t3;
-    bd = bd < eps ? eps : (bd > 100.0f ? 100.0f : bd);  // clamp(eps, 100); a NaN stays NaN
-    const float hd = sqrtf(1.0f - expf(-bd) + eps);
-    return 1.0f - hd;
-}
-
+// probiou(j, i) of probiou.h: batch_probiou (metrics.py:342-358) of obb1 = j and obb2 = i on (x, y, a, b, c, det) as gathered
 #define OBB_TILE 256
 __global__ __launch_bounds__(OBB_TILE) void obb_suppress_kernel(const ObbK p) {
     __shared__ f32x4 s0[OBB_TILE];  // x, y, a, b of the staged earlier candidates

@@ -12,7 +12,35 @@
 // reaches t), so one pass finds (l*, IoU*) per detection and each threshold is an atomicMin per label.
 // Exact IoU ties between two labels of one detection are an implementation accident in the reference (unstable argsort);
 // here the lower label index wins.  Compiled with -ffp-contract=off: the IoU must round exactly like the fp32 torch ops.
+//
+// The rule has two halves.  The first, (l*, IoU*) per detection, depends on the task: box_iou here (val_match_kernel), probiou
+// with the label as obb1 for OBBValidator._process_batch (models/yolo/obb/val.py:79; val_match_rotated_kernel), or an IoU matrix
+// made elsewhere -- the segment validator's mask_iou, csrc/val_masks.hip -- read back by val_match_iou_kernel.  The second,
+// val_settle, is the same for all three.
 #include "common.h"
+#include "probiou.h"
+
+constexpr int VAL_DPT = 4;  // detections per thread: max_det <= 1024, 256 threads
+
+// Second half of the rule: each threshold is an atomicMin per label over the detections that chose it.  best / bl: this thread's
+// detections tid + 256 j; winner: Lmax ints of LDS; every thread of the workgroup calls it.
+__device__ __forceinline__ void val_settle(const float (&best)[VAL_DPT], const int (&bl)[VAL_DPT], int* winner, const int nl,
+                                           const float* iouv, const int n_iou, const int max_det, unsigned char* out, const int tid) {
+    for (int i = 0; i < n_iou; ++i) {
+        for (int l = tid; l < nl; l += 256) winner[l] = 0x7fffffff;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < VAL_DPT; ++j)
+            if (bl[j] >= 0 && best[j] >= iouv[i]) atomicMin(&winner[bl[j]], tid + 256 * j);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < VAL_DPT; ++j) {
+            const int d = tid + 256 * j;
+            if (d < max_det) out[(size_t)d * n_iou + i] = (bl[j] >= 0 && best[j] >= iouv[i] && winner[bl[j]] == d) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+}
 
 struct ValK {
     const float* det;
@@ -33,7 +61,7 @@ __global__ __launch_bounds__(256) void val_match_kernel(const ValK p) {
     const float* gt = p.gt + (size_t)b * p.Lmax * 4;
     const float* gtc = p.gtc + (size_t)b * p.Lmax;
     unsigned char* out = p.out + (size_t)b * p.max_det * p.n_iou;
-    constexpr int DPT = 4;  // detections per thread: max_det <= 1024
+    constexpr int DPT = VAL_DPT;
     float best[DPT];
     int bl[DPT];
 #pragma unroll
@@ -55,20 +83,7 @@ __global__ __launch_bounds__(256) void val_match_kernel(const ValK p) {
             }
         }
     }
-    for (int i = 0; i < p.n_iou; ++i) {
-        for (int l = tid; l < nl; l += 256) winner[l] = 0x7fffffff;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < DPT; ++j)
-            if (bl[j] >= 0 && best[j] >= p.iouv[i]) atomicMin(&winner[bl[j]], tid + 256 * j);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < DPT; ++j) {
-            const int d = tid + 256 * j;
-            if (d < p.max_det) out[(size_t)d * p.n_iou + i] = (bl[j] >= 0 && best[j] >= p.iouv[i] && winner[bl[j]] == d) ? 1 : 0;
-        }
-        __syncthreads();
-    }
+    val_settle(best, bl, winner, nl, p.iouv, p.n_iou, p.max_det, out, tid);
 }
 
 extern "C" int bsy_val_match(const float* det, int row, const int32_t* counts, int B, int max_det, const float* gt_boxes,
@@ -82,6 +97,145 @@ extern "C" int bsy_val_match(const float* det, int row, const int32_t* counts, i
     k.row = row; k.max_det = max_det; k.Lmax = Lmax; k.n_iou = n_iou;
     for (int i = 0; i < 16; ++i) k.iouv[i] = i < n_iou ? iouv_host[i] : 2.f;
     hipLaunchKernelGGL(val_match_kernel, dim3(B), dim3(256), (size_t)Lmax * sizeof(int), (hipStream_t)stream, k);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}
+
+// ---- the rule on an IoU matrix (B, Lmax, max_det) made elsewhere ------------------------------------------------------------
+struct ValIouK {
+    const float* iou;
+    const float* det;
+    const int32_t* counts;
+    const float* gtc;
+    const int32_t* gt_counts;
+    unsigned char* out;
+    int row, max_det, Lmax, n_iou;
+    float iouv[16];
+};
+
+__global__ __launch_bounds__(256) void val_match_iou_kernel(const ValIouK p) {
+    extern __shared__ int winner[];  // [Lmax]
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nd = min(p.counts[b], p.max_det), nl = min(p.gt_counts[b], p.Lmax);
+    const float* det = p.det + (size_t)b * p.max_det * p.row;
+    const float* iou = p.iou + (size_t)b * p.Lmax * p.max_det;
+    const float* gtc = p.gtc + (size_t)b * p.Lmax;
+    float best[VAL_DPT], cls[VAL_DPT];
+    int bl[VAL_DPT];
+#pragma unroll
+    for (int j = 0; j < VAL_DPT; ++j) {
+        const int d = tid + 256 * j;
+        best[j] = 0.f;
+        bl[j] = -1;
+        cls[j] = d < nd ? det[(size_t)d * p.row + 5] : 0.f;
+    }
+    for (int l = 0; l < nl; ++l) {
+        const float c = gtc[l];
+#pragma unroll
+        for (int j = 0; j < VAL_DPT; ++j) {
+            const int d = tid + 256 * j;
+            if (d >= nd || c != cls[j]) continue;
+            const float v = iou[(size_t)l * p.max_det + d];
+            if (v > best[j]) { best[j] = v; bl[j] = l; }
+        }
+    }
+    val_settle(best, bl, winner, nl, p.iouv, p.n_iou, p.max_det, p.out + (size_t)b * p.max_det * p.n_iou, tid);
+}
+
+int val_match_from_iou(const float* iou, const float* det, int row, const int32_t* counts, int B, int max_det, const float* gt_cls,
+                       const int32_t* gt_counts, int Lmax, const float* iouv_host, int n_iou, unsigned char* out, hipStream_t s) {
+    ValIouK k;
+    k.iou = iou; k.det = det; k.counts = counts; k.gtc = gt_cls; k.gt_counts = gt_counts; k.out = out;
+    k.row = row; k.max_det = max_det; k.Lmax = Lmax; k.n_iou = n_iou;
+    for (int i = 0; i < 16; ++i) k.iouv[i] = i < n_iou ? iouv_host[i] : 2.f;
+    hipLaunchKernelGGL(val_match_iou_kernel, dim3(B), dim3(256), (size_t)Lmax * sizeof(int), s, k);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}
+
+// ---- rotated boxes: batch_probiou(gt, det), the label is obb1 --------------------------------------------------------------
+struct ValRotK {
+    const float* det;
+    const int32_t* counts;
+    const float* gt;  // (B, Lmax, 5) xywhr
+    const float* gtc;
+    const int32_t* gt_counts;
+    unsigned char* out;
+    float* iou_out;   // (B, Lmax, max_det) or nullptr
+    int row, max_det, Lmax, n_iou;
+    float iouv[16];
+};
+
+__global__ __launch_bounds__(256) void val_match_rotated_kernel(const ValRotK p) {
+    extern __shared__ int winner[];    // [Lmax]
+    __shared__ f32x4 s0[256];          // x, y, a, b of the staged labels
+    __shared__ float s1[256][3];       // c, det, class
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nd = min(p.counts[b], p.max_det), nl = min(p.gt_counts[b], p.Lmax);
+    const float* det = p.det + (size_t)b * p.max_det * p.row;
+    const float* gt = p.gt + (size_t)b * p.Lmax * 5;
+    const float* gtc = p.gtc + (size_t)b * p.Lmax;
+    float* io = p.iou_out ? p.iou_out + (size_t)b * p.Lmax * p.max_det : nullptr;
+    f32x4 d0[VAL_DPT];
+    float dc[VAL_DPT], dd[VAL_DPT], cls[VAL_DPT], best[VAL_DPT];
+    int bl[VAL_DPT];
+#pragma unroll
+    for (int j = 0; j < VAL_DPT; ++j) {
+        const int d = tid + 256 * j;
+        best[j] = 0.f;
+        bl[j] = -1;
+        d0[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dc[j] = dd[j] = cls[j] = 0.f;
+        if (d < nd) {
+            const float* r = det + (size_t)d * p.row;
+            const ObbCov g = obb_covariance(r[2], r[3], r[6]);
+            d0[j] = f32x4{r[0], r[1], g.a, g.b};
+            dc[j] = g.c;
+            dd[j] = g.det;
+            cls[j] = r[5];
+        }
+    }
+    for (int t0 = 0; t0 < nl; t0 += 256) {
+        __syncthreads();  // the previous tile has been read by every thread
+        if (t0 + tid < nl) {
+            const float* r = gt + (size_t)(t0 + tid) * 5;
+            const ObbCov g = obb_covariance(r[2], r[3], r[4]);
+            s0[tid] = f32x4{r[0], r[1], g.a, g.b};
+            s1[tid][0] = g.c;
+            s1[tid][1] = g.det;
+            s1[tid][2] = gtc[t0 + tid];
+        }
+        __syncthreads();
+        const int lim = nl - t0 < 256 ? nl - t0 : 256;
+        for (int jj = 0; jj < lim; ++jj) {
+            const f32x4 g0 = s0[jj];
+            const float gc = s1[jj][0], gd = s1[jj][1], c = s1[jj][2];
+#pragma unroll
+            for (int j = 0; j < VAL_DPT; ++j) {
+                const int d = tid + 256 * j;
+                if (d >= nd) continue;
+                const float v = probiou(g0, gc, gd, d0[j], dc[j], dd[j]);
+                if (io) io[(size_t)(t0 + jj) * p.max_det + d] = v;
+                if (c == cls[j] && v > best[j]) { best[j] = v; bl[j] = t0 + jj; }
+            }
+        }
+    }
+    val_settle(best, bl, winner, nl, p.iouv, p.n_iou, p.max_det, p.out + (size_t)b * p.max_det * p.n_iou, tid);
+}
+
+extern "C" int bsy_val_match_rotated(const float* det, int row, const int32_t* counts, int B, int max_det, const float* gt_rboxes,
+                                     const float* gt_cls, const int32_t* gt_counts, int Lmax, const float* iouv_host, int n_iou,
+                                     unsigned char* out, float* iou_out, bsy_stream stream) {
+    if (!det || !counts || !gt_rboxes || !gt_cls || !gt_counts || !iouv_host || !out)
+        BSY_FAIL(BSY_ERR_ARG, "val_match_rotated: null pointer");
+    if (B <= 0 || max_det <= 0 || max_det > 1024 || row < 7 || Lmax <= 0 || Lmax > 8192 || n_iou <= 0 || n_iou > 16)
+        BSY_FAIL(BSY_ERR_ARG, "val_match_rotated: bad sizes (row >= 7, max_det <= 1024, Lmax <= 8192, n_iou <= 16)");
+    ValRotK k;
+    k.det = det; k.counts = counts; k.gt = gt_rboxes; k.gtc = gt_cls; k.gt_counts = gt_counts; k.out = out; k.iou_out = iou_out;
+    k.row = row; k.max_det = max_det; k.Lmax = Lmax; k.n_iou = n_iou;
+    for (int i = 0; i < 16; ++i) k.iouv[i] = i < n_iou ? iouv_host[i] : 2.f;
+    if (iou_out) HIP_TRY(hipMemsetAsync(iou_out, 0, (size_t)B * Lmax * max_det * sizeof(float), (hipStream_t)stream));
+    hipLaunchKernelGGL(val_match_rotated_kernel, dim3(B), dim3(256), (size_t)Lmax * sizeof(int), (hipStream_t)stream, k);
     HIP_TRY(hipGetLastError());
     return BSY_OK;
 }

@@ -24,8 +24,9 @@ Three hooks, each using an extension point the reference already has (see INTEGR
   install_nms(ops_module)  ``ultralytics.utils.ops.non_max_suppression`` is looked up as a module attribute on every
                            call (models/yolo/detect/predict.py:25, detect/val.py:95): replacing the attribute suffices.
   install_masks(ops_module) same for ``ultralytics.utils.ops.process_mask`` (models/yolo/segment/predict.py:53).
-  install_val_metrics(v)   rebinds ``DetectionValidator._process_batch`` (models/yolo/detect/val.py:209-228) on a validator
-                           instance: true-positive matching on the device.
+  install_val_metrics(v)   rebinds ``_process_batch`` on a Detection / Segmentation / OBB validator instance
+                           (models/yolo/detect/val.py:209-228, segment/val.py:173-217, obb/val.py:53-80): true-positive matching
+                           on box IoU, mask IoU or probiou on the device.
   install_preprocess(p)    rebinds ``BasePredictor.preprocess`` (engine/predictor.py:116-134) on a predictor instance so
                            lists of HWC BGR uint8 images are letterboxed on the device.
 """
@@ -647,14 +648,23 @@ def install_masks(ops_module):
 
 
 def install_val_metrics(validator):
-    """validator = a DetectionValidator instance: its per-image `_process_batch` (models/yolo/detect/val.py:209-228:
-    box_iou + match_predictions, numpy on the host in the reference) goes to the device kernel for CUDA detections."""
+    """validator = a DetectionValidator, SegmentationValidator or OBBValidator instance: its per-image `_process_batch`
+    (models/yolo/detect/val.py:209-228, segment/val.py:173-217, obb/val.py:53-80: an IoU matrix + match_predictions, numpy on the
+    host in the reference) goes to the device kernels for CUDA detections.  The rebound method takes the segment validator's full
+    signature and dispatches on the CALL, not on the class: masks=True -> mask IoU; 5-column labels (xywhr) -> probiou; everything
+    else -> box IoU.  CPU tensors and more than 1024 detections go to the original method with the arguments they came with."""
     from . import val as _val
     orig = validator._process_batch
 
-    def _process_batch(self, detections, gt_bboxes, gt_cls):
+    def _process_batch(self, detections, gt_bboxes, gt_cls, pred_masks=None, gt_masks=None, overlap=False, masks=False):
         if not (isinstance(detections, torch.Tensor) and _on_device(detections)) or detections.shape[0] > 1024:
+            if masks:
+                return orig(detections, gt_bboxes, gt_cls, pred_masks, gt_masks, overlap, masks=True)
             return orig(detections, gt_bboxes, gt_cls)
+        if masks:
+            return _val.process_batch_masks(detections, gt_cls, pred_masks, gt_masks, overlap, self.iouv)
+        if gt_bboxes.dim() == 2 and gt_bboxes.shape[1] == 5:
+            return _val.process_batch_rotated(detections, gt_bboxes, gt_cls, self.iouv)
         return _val.process_batch(detections, gt_bboxes, gt_cls, self.iouv)
 
     validator._process_batch = types.MethodType(_process_batch, validator)

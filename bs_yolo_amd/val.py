@@ -3,6 +3,11 @@
   * match_batched / process_batch -- which detections are true positives at each IoU threshold: mirrors
     DetectionValidator._process_batch (models/yolo/detect/val.py:209-228) = utils/metrics.py:52-70 box_iou +
     engine/validator.py:222-258 match_predictions, for a whole batch in one launch (csrc/val_match.hip).
+  * pack_masks / pack_label_map / match_masks_batched / process_batch_masks -- SegmentationValidator._process_batch(..., masks=True)
+    (models/yolo/segment/val.py:204-217): mask_iou (utils/metrics.py:220-236) on 64-bit bit planes, bit-identical to the reference's
+    fp32 matmul form for 0 / 1 masks, then the same matching (csrc/val_masks.hip).
+  * match_rotated_batched / process_batch_rotated -- OBBValidator._process_batch (models/yolo/obb/val.py:79-80): batch_probiou with
+    the label as obb1, then the same matching (csrc/val_match.hip, csrc/probiou.h).
   * ap_per_class -- utils/metrics.py:620-706 (+ compute_ap :588-617): ranking, cumulative TP / FP, the 1000-point P / R
     curves and the 101-point interpolated AP per class and threshold on the device in float64 (csrc/val_ap.hip); only the
     max-F1 operating point (a box filter over a (nc, 1000) array) is taken on the host, with numpy as the reference does.
@@ -10,7 +15,7 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -62,6 +67,184 @@ def process_batch(detections: torch.Tensor, gt_bboxes: torch.Tensor, gt_cls: tor
     one = torch.tensor([n], dtype=torch.int32, device=dev)
     m = torch.tensor([int(gt_bboxes.shape[0])], dtype=torch.int32, device=dev)
     return match_batched(det, one, gt_bboxes.unsqueeze(0), gt_cls.reshape(1, -1), m, iouv)[0]
+
+
+class PackedMasks(NamedTuple):
+    """0 / 1 masks as bit planes: planes (..., ceil(H W / 64)) int64 words (bit p & 63 of word p >> 6 = pixel p, tail bits zero),
+    areas (...) int32 = set pixels, hw = H * W."""
+    planes: torch.Tensor
+    areas: torch.Tensor
+    hw: int
+
+
+def _mask_input(t: torch.Tensor) -> torch.Tensor:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError("bs_yolo_amd.val: masks must live on the GPU (no CPU fallback)")
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8) if t.is_contiguous() else t.to(torch.uint8)
+    if t.dtype not in (torch.float32, torch.float16, torch.uint8):
+        raise TypeError(f"masks of dtype {t.dtype}: float32, float16, uint8 or bool")
+    return t.contiguous()
+
+
+def pack_masks(masks: torch.Tensor) -> PackedMasks:
+    """masks (..., H, W) float32 / float16 / uint8 / bool on the device, non-zero = set -> PackedMasks with the leading dimensions
+    kept (one launch for all of them)."""
+    m = _mask_input(masks)
+    lead, hw = tuple(m.shape[:-2]), int(m.shape[-2]) * int(m.shape[-1])
+    n = int(np.prod(lead)) if lead else 1
+    words = (hw + 63) // 64
+    planes = torch.empty(lead + (words,), dtype=torch.int64, device=m.device)
+    areas = torch.zeros(lead, dtype=torch.int32, device=m.device)
+    if n and hw:
+        stream = torch.cuda.current_stream(m.device).cuda_stream
+        L.check(L.lib.bsy_pack_masks(C.c_void_p(m.data_ptr()), L.dtype_code(m.dtype), n, hw, 0, C.c_void_p(planes.data_ptr()),
+                                     C.c_void_p(areas.data_ptr()), C.c_void_p(stream)))
+    return PackedMasks(planes, areas, hw)
+
+
+def pack_label_map(index_map: torch.Tensor, nl: int) -> PackedMasks:
+    """The overlap_mask=True label form (segment/val.py:205-209): index_map (1, H, W) or (H, W) in which the value l + 1 marks label l
+    -> the nl label planes (nl, words), in one pass over the map."""
+    m = _mask_input(index_map)
+    if m.dim() == 3 and m.shape[0] == 1:
+        m = m[0]
+    if m.dim() != 2:
+        raise ValueError("pack_label_map: one (1, H, W) or (H, W) index map")
+    hw = int(m.shape[0]) * int(m.shape[1])
+    words = (hw + 63) // 64
+    planes = torch.empty((nl, words), dtype=torch.int64, device=m.device)
+    areas = torch.zeros((nl,), dtype=torch.int32, device=m.device)
+    if nl and hw:
+        stream = torch.cuda.current_stream(m.device).cuda_stream
+        L.check(L.lib.bsy_pack_masks(C.c_void_p(m.data_ptr()), L.dtype_code(m.dtype), nl, hw, 1, C.c_void_p(planes.data_ptr()),
+                                     C.c_void_p(areas.data_ptr()), C.c_void_p(stream)))
+    return PackedMasks(planes, areas, hw)
+
+
+def _labels(det, gt_cls, gt_counts, Lmax):
+    gc = torch.full((det.shape[0], Lmax), -1.0, dtype=torch.float32, device=det.device)
+    if gt_cls.shape[1]:
+        gc.copy_(gt_cls.to(det.device, torch.float32))
+    return gc, gt_counts.to(det.device, torch.int32).contiguous()
+
+
+def match_masks_batched(det: torch.Tensor, counts: torch.Tensor, pred_planes: PackedMasks, gt_planes: PackedMasks,
+                        gt_cls: torch.Tensor, gt_counts: torch.Tensor, iouv=None, iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """det (B, max_det, >=6) fp32 (the class column is read) + counts (B); pred_planes = PackedMasks of (B, max_det, H, W)
+    predictions, gt_planes = PackedMasks of (B, Lmax, H, W) labels at the same resolution; gt_cls (B, Lmax), gt_counts (B)
+    -> (B, max_det, n_iou) bool (rows past counts[b] are False).  iou_out (B, max(Lmax, 1), max_det) fp32, when given, receives
+    mask_iou(gt, pred), zero outside the counts."""
+    if iouv is None:
+        iouv = torch.linspace(0.5, 0.95, 10)
+    B, max_det, row = det.shape
+    assert det.is_cuda and det.dtype == torch.float32 and det.is_contiguous()
+    pp, pa, gp, ga = pred_planes.planes, pred_planes.areas, gt_planes.planes, gt_planes.areas
+    words = int(pp.shape[-1])
+    if tuple(pp.shape) != (B, max_det, words) or pred_planes.hw != gt_planes.hw or gp.dim() != 3 or gp.shape[0] != B:
+        raise ValueError("match_masks_batched: pred planes (B, max_det, words) and gt planes (B, Lmax, words) of one resolution")
+    Lmax = max(int(gp.shape[1]), 1)
+    if not gp.shape[1]:
+        gp = torch.zeros((B, 1, words), dtype=torch.int64, device=det.device)
+        ga = torch.zeros((B, 1), dtype=torch.int32, device=det.device)
+    gc, gt_counts = _labels(det, gt_cls, gt_counts, Lmax)
+    counts = counts.to(det.device, torch.int32).contiguous()
+    arr, n = _iouv_host(iouv)
+    out = torch.empty((B, max_det, n), dtype=torch.uint8, device=det.device)
+    ws, nbytes = None, 0
+    if iou_out is None:
+        nbytes = L.lib.bsy_val_match_masks_workspace_bytes(B, max_det, Lmax)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=det.device)
+    else:
+        assert iou_out.is_cuda and iou_out.dtype == torch.float32 and iou_out.is_contiguous() and tuple(iou_out.shape) == (B, Lmax, max_det)
+    stream = torch.cuda.current_stream(det.device).cuda_stream
+    L.check(L.lib.bsy_val_match_masks(
+        C.c_void_p(det.data_ptr()), row, C.c_void_p(counts.data_ptr()), B, max_det, C.c_void_p(pp.contiguous().data_ptr()),
+        C.c_void_p(pa.contiguous().data_ptr()), C.c_void_p(gp.contiguous().data_ptr()), C.c_void_p(ga.contiguous().data_ptr()), words,
+        C.c_void_p(gc.data_ptr()), C.c_void_p(gt_counts.data_ptr()), Lmax, arr, n, C.c_void_p(out.data_ptr()),
+        C.c_void_p(iou_out.data_ptr()) if iou_out is not None else None, C.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes,
+        C.c_void_p(stream)))
+    return out.bool()
+
+
+def match_rotated_batched(det: torch.Tensor, counts: torch.Tensor, gt_rboxes: torch.Tensor, gt_cls: torch.Tensor,
+                          gt_counts: torch.Tensor, iouv=None, iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """det (B, max_det, >=7) fp32 rows [x, y, w, h, conf, cls, theta, ...] + counts (B); gt_rboxes (B, Lmax, 5) xywhr in the same
+    frame, gt_cls (B, Lmax), gt_counts (B) -> (B, max_det, n_iou) bool (rows past counts[b] are False).  iou_out (B, max(Lmax, 1),
+    max_det) fp32, when given, receives batch_probiou(gt, det), zero outside the counts."""
+    if iouv is None:
+        iouv = torch.linspace(0.5, 0.95, 10)
+    B, max_det, row = det.shape
+    assert det.is_cuda and det.dtype == torch.float32 and det.is_contiguous()
+    Lmax = max(int(gt_rboxes.shape[1]), 1)
+    gb = torch.zeros((B, Lmax, 5), dtype=torch.float32, device=det.device)
+    if gt_rboxes.shape[1]:
+        gb.copy_(gt_rboxes.to(det.device, torch.float32))
+    gc, gt_counts = _labels(det, gt_cls, gt_counts, Lmax)
+    counts = counts.to(det.device, torch.int32).contiguous()
+    arr, n = _iouv_host(iouv)
+    out = torch.empty((B, max_det, n), dtype=torch.uint8, device=det.device)
+    if iou_out is not None:
+        assert iou_out.is_cuda and iou_out.dtype == torch.float32 and iou_out.is_contiguous() and tuple(iou_out.shape) == (B, Lmax, max_det)
+    stream = torch.cuda.current_stream(det.device).cuda_stream
+    L.check(L.lib.bsy_val_match_rotated(C.c_void_p(det.data_ptr()), row, C.c_void_p(counts.data_ptr()), B, max_det,
+                                        C.c_void_p(gb.data_ptr()), C.c_void_p(gc.data_ptr()), C.c_void_p(gt_counts.data_ptr()), Lmax,
+                                        arr, n, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(iou_out.data_ptr()) if iou_out is not None else None, C.c_void_p(stream)))
+    return out.bool()
+
+
+def label_planes(gt_masks: torch.Tensor, nl: int, overlap: bool, shape) -> PackedMasks:
+    """The label side of SegmentationValidator._process_batch (segment/val.py:205-212) as planes at the predictions' (H, W):
+    overlap -> nl masks from the index map; another resolution -> the reference's own F.interpolate(bilinear) and > 0.5, on the
+    device (ATen's kernel, not restated)."""
+    shape = tuple(int(v) for v in shape)
+    if tuple(gt_masks.shape[1:]) == shape:
+        return pack_label_map(gt_masks, nl) if overlap else pack_masks(gt_masks)
+    if overlap:
+        index = torch.arange(nl, device=gt_masks.device).view(nl, 1, 1) + 1
+        gt_masks = torch.where(gt_masks.repeat(nl, 1, 1) == index, 1.0, 0.0)
+    if not gt_masks.is_floating_point():
+        gt_masks = gt_masks.float()
+    gt_masks = torch.nn.functional.interpolate(gt_masks[None], shape, mode="bilinear", align_corners=False)[0]
+    return pack_masks(gt_masks.gt_(0.5))
+
+
+def process_batch_masks(detections: torch.Tensor, gt_cls: torch.Tensor, pred_masks: torch.Tensor, gt_masks: torch.Tensor,
+                        overlap: bool = False, iouv=None, iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Drop-in for SegmentationValidator._process_batch(..., masks=True) (one image): detections (N, >=6), gt_cls (M,), pred_masks
+    (N, H, W) 0 / 1, gt_masks (M, h, w) 0 / 1 or, with overlap, the (1, h, w) index map -> (N, n_iou) bool on detections.device."""
+    n, nl = int(detections.shape[0]), int(gt_cls.shape[0])
+    dev = detections.device
+    niou = 10 if iouv is None else len(iouv)
+    if n == 0 or nl == 0:
+        return torch.zeros((n, niou), dtype=torch.bool, device=dev)
+    if n > 1024:
+        raise ValueError("process_batch_masks: more than 1024 detections per image")
+    pp = pack_masks(pred_masks)
+    gp = label_planes(gt_masks, nl, overlap, pred_masks.shape[1:])
+    det = detections[:, :6].float().contiguous().unsqueeze(0)
+    one = torch.tensor([n], dtype=torch.int32, device=dev)
+    m = torch.tensor([nl], dtype=torch.int32, device=dev)
+    return match_masks_batched(det, one, PackedMasks(pp.planes[None], pp.areas[None], pp.hw),
+                               PackedMasks(gp.planes[None], gp.areas[None], gp.hw), gt_cls.reshape(1, -1), m, iouv, iou_out)[0]
+
+
+def process_batch_rotated(detections: torch.Tensor, gt_bboxes: torch.Tensor, gt_cls: torch.Tensor, iouv=None,
+                          iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Drop-in for OBBValidator._process_batch (one image): detections (N, >=7) rows [x, y, w, h, conf, cls, ..., theta] (the
+    angle is the LAST column, obb/val.py:79), gt_bboxes (M, 5) xywhr, gt_cls (M,) -> (N, n_iou) bool on detections.device."""
+    n = int(detections.shape[0])
+    dev = detections.device
+    niou = 10 if iouv is None else len(iouv)
+    if n == 0 or gt_bboxes.shape[0] == 0:
+        return torch.zeros((n, niou), dtype=torch.bool, device=dev)
+    if n > 1024:
+        raise ValueError("process_batch_rotated: more than 1024 detections per image")
+    det = torch.cat([detections[:, :6], detections[:, -1:]], 1).float().contiguous().unsqueeze(0)
+    one = torch.tensor([n], dtype=torch.int32, device=dev)
+    m = torch.tensor([int(gt_bboxes.shape[0])], dtype=torch.int32, device=dev)
+    return match_rotated_batched(det, one, gt_bboxes.unsqueeze(0), gt_cls.reshape(1, -1), m, iouv, iou_out)[0]
 
 
 def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, on_plot=None, save_dir=None, names=None, eps=1e-16, prefix="",

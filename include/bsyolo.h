@@ -428,6 +428,33 @@ int bsy_val_match(const float* det, int row, const int32_t* counts, int B, int m
                   const float* gt_cls, const int32_t* gt_counts, int Lmax, const float* iouv, int n_iou,
                   unsigned char* out, bsy_stream stream);
 
+/* Validator matching for the two other tasks; the rule and its tie-break are bsy_val_match's (csrc/val_match.hip).  Every entry
+ * takes a stream, allocates nothing and does not synchronise with the host.  iou_out, where not NULL, is DEVICE (B, Lmax, max_det)
+ * f32 and receives the class-unmasked IoU matrix (rows past gt_counts[b] and columns past counts[b] are zero).
+ *
+ * bsy_pack_masks: 0 / 1 masks as bit planes (csrc/val_masks.hip).  label_map == 0: masks (n, hw) f16 / f32 / u8 (a bool tensor is
+ *   u8), non-zero = set -> planes (n, ceil(hw / 64)) uint64, bit (p & 63) of word (p >> 6) = pixel p, tail bits zero; areas (n)
+ *   int32 = set pixels.  label_map != 0: masks is ONE (hw) index map in which the value l + 1 marks label l (the overlap_mask=True
+ *   form, models/yolo/segment/val.py:205-209) -> the n label planes and areas.  hw <= 2^24.
+ * bsy_val_match_masks: SegmentationValidator._process_batch(..., masks=True) (segment/val.py:204-217): mask_iou
+ *   (utils/metrics.py:220-236) as popcount(gt & pred) over the planes -- bit-identical to the reference's fp32 matmul form for
+ *   0 / 1 masks -- then the matching.  det / counts / gt_cls / gt_counts / iouv / out as bsy_val_match (det supplies the class
+ *   column only); pred_planes (B, max_det, words) + pred_areas (B, max_det), gt_planes (B, Lmax, words) + gt_areas (B, Lmax) as
+ *   bsy_pack_masks writes them, gt at the predictions' resolution.  Without iou_out the matrix lives in `workspace`
+ *   (bsy_val_match_masks_workspace_bytes); with it the workspace may be NULL.  max_det <= 1024, Lmax <= 8192, words <= 2^18.
+ * bsy_val_match_rotated: OBBValidator._process_batch (models/yolo/obb/val.py:79-80): batch_probiou(gt, det), the label is obb1
+ *   (the formula is not bit-symmetric), then the matching.  det (B, max_det, row >= 7) f32 rows [x y w h conf cls theta ...],
+ *   gt_rboxes (B, Lmax, 5) f32 xywhr. */
+int bsy_pack_masks(const void* masks, int dtype, int n, int hw, int label_map, uint64_t* planes, int32_t* areas, bsy_stream stream);
+size_t bsy_val_match_masks_workspace_bytes(int B, int max_det, int Lmax);
+int bsy_val_match_masks(const float* det, int row, const int32_t* counts, int B, int max_det, const uint64_t* pred_planes,
+                        const int32_t* pred_areas, const uint64_t* gt_planes, const int32_t* gt_areas, int words,
+                        const float* gt_cls, const int32_t* gt_counts, int Lmax, const float* iouv, int n_iou, unsigned char* out,
+                        float* iou_out, void* workspace, size_t workspace_bytes, bsy_stream stream);
+int bsy_val_match_rotated(const float* det, int row, const int32_t* counts, int B, int max_det, const float* gt_rboxes,
+                          const float* gt_cls, const int32_t* gt_counts, int Lmax, const float* iouv, int n_iou, unsigned char* out,
+                          float* iou_out, bsy_stream stream);
+
 /* ap_per_class + compute_ap (utils/metrics.py:620-706, :588-617) without the plots and the max-F1 pick (host side).
  * tp (N, T) uint8, conf (N) f32 in [0, 1], pred_cls (N) f32 -- the concatenated statistics DetectionValidator.get_stats
  * (models/yolo/detect/val.py:160-170) hands to DetMetrics.process; classes / nt: DEVICE (nc) = np.unique(target_cls,
