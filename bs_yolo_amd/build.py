@@ -22,7 +22,11 @@ COMMON = ["-fno-slp-vectorize"]
 # DESIGN.md section 7), and it buys nothing measurable anywhere (the headline forward: 3.572 vs 3.580 ms, three runs each)
 SOURCES = {
     "err.cpp": [],
-    "conv_mfma.hip": [],
+    "conv_gemm.hip": [],
+    "conv_stream1x1.hip": [],
+    "conv_patch.hip": [],
+    "dwpw_fused.hip": [],
+    "conv_select.hip": [],
     "conv_first.hip": [],
     "stem_fused.hip": [],
     "bneck_fused.hip": [],

@@ -13,7 +13,7 @@
 //     through an LDS tile as coalesced 16-byte stores;
 //   * conv 1's weights live in registers as MFMA A fragments for the whole launch (72 VGPRs), conv 2's in LDS.
 // K order (tap-major, channels ascending, 16 per MFMA) and the epilogue arithmetic (f16(SiLU) then + residual in f32)
-// equal conv_mfma.hip's, so the result is bit-identical to the two-launch path.
+// equal conv_gemm.hip's, so the result is bit-identical to the two-launch path.
 #include "common.h"
 
 #define BN_TH 8
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
 // fragments no longer fit registers: 36 K-steps), 8 waves, one workgroup per CU (143 KiB of LDS):
 //   conv 1: 6 MFMA pixel tiles of the hidden patch on waves 0-5, 36 K-steps each;
 //   conv 2: 4 pixel tiles x 2 cout tiles on the 8 waves, 18 K-steps each, + shortcut from the input patch.
-// Lane-constant address arithmetic is hoisted out of the tile loop (c3k2_fused.hip).  K walks (conv_mfma.hip conv_korder: conv 1 with its
+// Lane-constant address arithmetic is hoisted out of the tile loop (c3k2_fused.hip).  K walks (conv_select.hip conv_korder: conv 1 with its
 // 64 input channels chunk-major over two 32-channel chunks, conv 2 one chunk) and epilogue arithmetic equal the conv kernels': bit-identical
 // to the two-launch path through any of their configurations.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
             acc_bias(acc, sb1, lh);
 #pragma unroll
             for (int ks = 0; ks < KSA; ++ks) {
-                // the layer's K walk (conv_mfma.hip conv_korder: 3x3, Cin % 32 == 0 -> chunk-major, 32-channel chunks): chunk, tap, 16-wide half
+                // the layer's K walk (conv_select.hip conv_korder: 3x3, Cin % 32 == 0 -> chunk-major, 32-channel chunks): chunk, tap, 16-wide half
                 const int chunk = ks / 18, tap = (ks % 18) >> 1, k0 = tap * C + 32 * chunk + 16 * (ks & 1), ch0 = (k0 % C) / 8;  // compile-time
                 const half8 bf = *reinterpret_cast<const half8*>(xb + ((tap / 3) * BN_XC + tap % 3) * XS + ch0 * 8);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(a1base + k0), bf, acc, 0, 0, 0);

@@ -17,7 +17,7 @@
 // All weights stay on chip for the whole launch (cv1's and m.cv2's in LDS; m.cv1's and each wave's 32 output channels of
 // cv2 as MFMA A fragments in registers).  K orders (channels
 // ascending for the 1x1 convs, tap-major for the 3x3 convs) and the epilogue arithmetic (f16(SiLU), shortcut added in f32)
-// equal conv_mfma.hip's / bneck_fused.hip's, so the block returns bit for bit what the three-launch path returns.
+// equal conv_gemm.hip's / bneck_fused.hip's, so the block returns bit for bit what the three-launch path returns.
 #include "common.h"
 
 #define CK_TH 4

@@ -61,7 +61,7 @@ struct ConvArgs {
     float lvl_stride;
     void* raw;
     int raw_f32, rawC;
-    // Box-branch tail (3x3 conv + the branch's last 1x1 conv + DFL decode in one launch; conv_mfma.hip conv3x3_patch_kernel<.., TAIL>):
+    // Box-branch tail (3x3 conv + the branch's last 1x1 conv + DFL decode in one launch; conv_patch.hip conv3x3_patch_kernel<.., TAIL>):
     // this op is the 3x3 conv (Cout = 64, its map never reaches HBM), tail_wgt / tail_bias the packed 64 -> 64 1x1 conv, epi = 3 and
     // the decoder fields above describe what the tail writes.  nullptr: no tail.
     const half_t* tail_wgt;
@@ -263,7 +263,7 @@ int launch_gap32(const float* src, int lds_, int B, int H, int W, int C, float* 
 int launch_mul32(const float* x, int ldx, const float* y, int ldy, long long npix, int C, float* dst, int ldd, hipStream_t s);
 int launch_ela32(const ElaArgs& a, const float* src, float* dst, hipStream_t s);  // a.src / a.dst unused
 
-// Fused DWConv 3x3 (+SiLU) -> Conv 1x1 (+act) (conv_mfma.hip: dwpw_fused_kernel)
+// Fused DWConv 3x3 (+SiLU) -> Conv 1x1 (+act) (dwpw_fused.hip: dwpw_fused_kernel)
 struct DwPwArgs {
     const half_t* src;
     int lds;
@@ -505,5 +505,5 @@ __device__ __forceinline__ f32x4 silu4_f(f32x4 x) {
 // SiLU of the exact fp32 mode (ref32.hip, conv32_mfma.hip): the scalar and the MFMA kernels return the same bits only while both
 // evaluate this the same way, so every user is built with -ffp-contract=off -fno-vectorize (build.py).
 __device__ __forceinline__ float silu32(float x) { return x / (1.0f + expf(-x)); }
-// Sigmoid of the fp16 path's gates and of the Detect decoders (the fused head epilogues of conv_mfma.hip and detect.hip must agree)
+// Sigmoid of the fp16 path's gates and of the Detect decoders (the fused head epilogues of conv_kernels.h and detect.hip must agree)
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + __expf(-v)); }

@@ -8,7 +8,7 @@
 // kernels return the same bits (tests/test_gpu_parity.py::test_conv32_mfma_equals_scalar), which is also what makes results
 // independent of which of them a shape is routed to.  Peak 157 TFLOP/s (64 FLOP/clk/SIMD), 1/16 of the fp16 MFMA rate.
 //
-// GEMM view as in conv_mfma.hip: D[cout][pixel] = sum_k W[k][cout] * P[pixel][k]; A operand = weights (rows = cout), B operand =
+// GEMM view as in conv_gemm.hip: D[cout][pixel] = sum_k W[k][cout] * P[pixel][k]; A operand = weights (rows = cout), B operand =
 // pixels (cols = pixel) => a lane owns ONE pixel and groups of 4 consecutive couts.  Workgroup = 4 waves (2 x 2), tile 128 pixels
 // x (64 NT) couts, K-step = 32 k values; wave tile 64 pixels x 32 NT couts = 2 x NT accumulator tiles of 32 x 32.
 // Staging: global_load_dwordx4 -> registers -> LDS, double-buffered (one barrier per K-step); an f32 K-step is 16 x 4 x 64

@@ -8,7 +8,7 @@
 //   * the contraction runs on v_mfma_f32_32x32x16_f16 with K = 9 taps x 4 = 36 padded to 48 -- weights packed like every
 //     other conv ([CoutPad][Kpad], k = (kh, kw, c)) but with the zero 4th input channel, held in registers as the A
 //     operand; a lane's B fragment is two taps = two 8-byte LDS reads at compile-time offsets;
-//   * epilogue as conv_mfma.hip: the tile goes through LDS so every store is a coalesced 16-byte piece.
+//   * epilogue as conv_gemm.hip: the tile goes through LDS so every store is a coalesced 16-byte piece.
 #include "image_conv.h"
 
 #define CF_TH 4

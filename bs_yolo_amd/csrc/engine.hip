@@ -737,7 +737,7 @@ extern "C" int bsy_plan_graph_launch(bsy_plan* p, void* const* ext, int n_ext, b
 // Per-op autotuning of the conv kernel configuration (tile shape / K-step / ring depth): runs the plan once, timing
 // every valid configuration of every conv op with HIP events on `stream` (1 warm-up + 3 timed launches each) and
 // records the fastest in the plan.  All configurations of a layer are bit-identical in their results: the K walk is a function of the
-// layer's shape (conv_mfma.hip conv_korder), never of the configuration.
+// layer's shape (conv_select.hip conv_korder), never of the configuration.
 extern "C" int bsy_plan_autotune(bsy_plan* p, void* const* ext, int n_ext, bsy_stream stream) {
     if (!p || (n_ext && !ext)) BSY_FAIL(BSY_ERR_ARG, "plan_autotune: bad argument");
     p->drop_graphs();

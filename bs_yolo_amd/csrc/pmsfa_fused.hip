@@ -2,7 +2,7 @@
 // Reference: /root/reference/ultralytics/nn/modules/block.py:3035-3054
 //     conv1_out = conv1(x);  p1, p2 = conv1_out.chunk(2);  conv2_out = conv2(p1) [5x5 depthwise];  q1, q2 = conv2_out.chunk(2)
 //     conv3_out = conv3(q1) [7x7 depthwise];  out = conv4(cat([conv3_out, q2, p2])) + x
-// conv1 (a dense 3x3, the patch kernel of conv_mfma.hip) stays its own launch and writes P = [p1 | p2].  The unfused plan then runs
+// conv1 (a dense 3x3, the patch kernel of conv_patch.hip) stays its own launch and writes P = [p1 | p2].  The unfused plan then runs
 // three launches that move the map five times (5x5: read p1, write Q; 7x7: read Q, write S; 1x1: read [S | p2] and x, write): at
 // 160 x 160 x 32 channels and 64 images 52 + 63 + 82 us for ~0.9 GB of traffic.  Here a workgroup owns a TH x TW pixel tile:
 //   phase 1  p1 of the tile + a halo of 5 pixels -> LDS (row-contiguous 16-byte buffer loads, zero padding = out-of-range result)
@@ -18,7 +18,7 @@
 // Arithmetic = the unfused kernels', step for step: depthwise taps in (dy, dx) order as f32 FMAs on f16 inputs starting at the bias
 // (bsyolo_ops.hip dwconv_tile_kernel), SiLU in f32 and one rounding to f16 per intermediate map, conv4's K walk in ascending
 // 16-channel MFMA steps from accumulators that start at the bias, activation rounded to f16 BEFORE the shortcut is added
-// (conv_mfma.hip conv_epilogue_lds) -- the fused and the unfused plan return the same bits (tests/test_gpu_parity.py).
+// (conv_kernels.h conv_epilogue_lds) -- the fused and the unfused plan return the same bits (tests/test_gpu_parity.py).
 #include "common.h"
 
 namespace {

@@ -15,7 +15,7 @@
 //   * workgroups are persistent (grid = 3 per CU) and fetch the next tile's image patch into registers before they
 //     start computing the current one, so HBM latency hides under the MFMA / LDS work; stores go through an LDS tile
 //     as coalesced 16-byte pieces.
-// Accumulation order (K ascending in 16-wide MFMA steps, k = (kh, kw, c)) equals conv_first.hip's and conv_mfma.hip's,
+// Accumulation order (K ascending in 16-wide MFMA steps, k = (kh, kw, c)) equals conv_first.hip's and conv_gemm.hip's,
 // so the result is bit-identical to the unfused pair (tests/test_gpu_parity.py::test_stem_fused_matches_unfused).
 #include "image_conv.h"
 

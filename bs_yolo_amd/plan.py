@@ -253,7 +253,7 @@ class Plan:
         assert all(t.H == H and t.W == W and (t.f32 == self.f32_mode) for t in srcs)
         cin = sum(t.C for t in srcs)
         if not self.f32_mode and any(t.C % 8 or t.coff % 8 for t in srcs):
-            # csrc/conv_mfma.hip reads its sources in 16-byte (8-channel) pieces; a block whose hidden width is 12 or 20 channels
+            # csrc/conv_gemm.hip reads its sources in 16-byte (8-channel) pieces; a block whose hidden width is 12 or 20 channels
             # (a C2f / C3k2 of 24 or 40) is refused here rather than at the first launch
             raise NotImplementedError(f"{name}: source channels / offsets {[(t.C, t.coff) for t in srcs]} are not multiples of 8 (fp16 path)")
         p = k // 2
@@ -338,7 +338,7 @@ class Plan:
         return dst
 
     def dwpw(self, name: str, src: T, cout: int, real: Tuple[int, int] = (0, 0)) -> T:
-        """nn.Sequential(DWConv(c, c, 3), Conv(c, cout, 1)) (head.py:49-57): one fused launch where conv_mfma.hip's
+        """nn.Sequential(DWConv(c, c, 3), Conv(c, cout, 1)) (head.py:49-57): one fused launch where dwpw_fused.hip's
         dwpw_fused_kernel takes the widths, else the two ordinary launches.  real = the modules' own (cout, cin) where `cout` / `src`
         are padded to a multiple of 8."""
         if not (self.fuse_dwpw and dwpw_supported(src.C, cout) and not src.up):
@@ -648,7 +648,7 @@ class Plan:
 
     def _box_tail(self, name: str, i: int, src: T, level: int, a0: int, A: int, nc: int, stride: float):
         """cv2.i.1 (3x3, 64 -> 64, SiLU) + cv2.i.2 (1x1, 64 -> 64 box logits) + DFL / dist2bbox (head.py:49-57, :141-146) as ONE
-        conv op: the patch kernel's TAIL form (conv_mfma.hip) multiplies its activated fp16 tile with the 1x1 weights straight from
+        conv op: the patch kernel's TAIL form (conv_patch.hip) multiplies its activated fp16 tile with the 1x1 weights straight from
         LDS and decodes the accumulators -- bit for bit what the two launches produce, without the 64-channel map's round trip."""
         n1, n2 = f"{name}.cv2.{i}.1", f"{name}.cv2.{i}.2"
         k1 = self._wrec(n1, name=n1, kind="conv", cout=64, cin=src.C, k=3, perm=None)
@@ -670,7 +670,7 @@ class Plan:
         A = sum(t.H * t.W for t in xs)
         a0 = [sum(t.H * t.W for t in xs[:i]) for i in range(len(xs))]
         strides = [float(self.H // t.H) for t in xs]
-        # Detect without mask coefficients: the last conv of every branch decodes in its epilogue (conv_mfma.hip
+        # Detect without mask coefficients: the last conv of every branch decodes in its epilogue (conv_kernels.h
         # conv_epilogue_head) -- no f32 logit maps, no decode launch, no raw-map transposes.  An OBB head's box decode needs the
         # angle of its cv4 branch (tal.py:404-423 dist2rbox), so OBB always takes the decode launch
         fused = self.fuse_head and nm == 0 and ne == 0 and len(xs) <= 3

@@ -4,7 +4,7 @@
                      BaseModel.fuse, nn/tasks.py:209-215): W' = diag(g / sqrt(var + eps)) W,  b' = beta - g mu / sqrt(var + eps).
                      Accepts either an un-fused state_dict (conv.weight + bn.*) or an already fused one
                      (conv.weight + conv.bias), which is what a reference model holds after AutoBackend's fuse().
-  * pack layouts  -- conv   : fp16 [CoutPad128][Kpad32], K order (kh, kw, cin)  (conv_mfma.hip), bias fp32 [CoutPad128]
+  * pack layouts  -- conv   : fp16 [CoutPad128][Kpad32], K order (kh, kw, cin)  (conv_gemm.hip), bias fp32 [CoutPad128]
                      first  : same as conv with cin = 3 (K = 27 -> 32)  (conv_first.hip)
                      dw     : fp32 [9][C] (elementwise.hip)
 """

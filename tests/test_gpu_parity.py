@@ -45,7 +45,7 @@ def h16(t):
 
 
 # ------------------------------------------------------------------------------------------------------------
-# implicit-GEMM conv (conv_mfma.hip)
+# implicit-GEMM conv (conv_gemm.hip)
 # ------------------------------------------------------------------------------------------------------------
 CONV_CASES = [
     # B, H, W, cin, cout, k, s, act, res, f32
@@ -301,7 +301,7 @@ PATCH_CASES = [
 
 @pytest.mark.parametrize("case", PATCH_CASES)
 def test_conv_patch_kernel_matches_oracle(case, monkeypatch):
-    """3x3 stride-1 patch kernel (conv_mfma.hip, tiles 10/11 = 8x16-pixel tiles, 12/13 = 6x20) against the fp32 reference and against the implicit-GEMM
+    """3x3 stride-1 patch kernel (conv_patch.hip, tiles 10/11 = 8x16-pixel tiles, 12/13 = 6x20) against the fp32 reference and against the implicit-GEMM
     kernel, which walks K in the same order for these layers (conv_korder: chunk-major over 32-channel chunks): bit for bit."""
     B, H, W, cin, cout, cfg, use_res = case
     g = torch.Generator().manual_seed(cfg * 1000 + cin)
@@ -333,6 +333,8 @@ PERSIST_CASES = [
     # tiles 14 / 15 = weights-resident streaming 1x1 kernel (128 x 128 / 128 x 64 tiles; variant 1: 4-stage pixel ring, 2: 3 stages)
     (70, 40, 40, 128, 128, 0xe1), (70, 40, 40, 192, 256, 0xe2), (33, 37, 41, 96, 72, 0xe1), (9, 80, 80, 256, 256, 0xf1),           # (K = 256 on the 128-cout tile would need 32 fragments: not built)
     (70, 40, 40, 512, 128, 0xf1), (33, 37, 41, 128, 72, 0xf2), (3, 7, 5, 128, 64, 0xf1), (300, 16, 16, 160, 136, 0xe2),
+    # K past 16 fragments per wave: the rows' own fragment counts (24 at 128 couts, 32 at 64); the cases above run 0xe1 / 0xf2 in their 16-fragment form
+    (70, 40, 40, 192, 128, 0xe1), (70, 40, 40, 512, 64, 0xf2),
 ]
 
 
@@ -360,7 +362,7 @@ def test_conv_persistent_1x1_matches_one_tile_per_workgroup(case, monkeypatch):
 
 
 KORDER_CASES = [
-    # B, H, W, cin, cout, k, stride, K walk (conv_mfma.hip conv_korder: 0 packed order, 1 / 2 chunk-major over 32- / 64-channel chunks)
+    # B, H, W, cin, cout, k, stride, K walk (conv_select.hip conv_korder: 0 packed order, 1 / 2 chunk-major over 32- / 64-channel chunks)
     (2, 40, 40, 128, 128, 3, 2, 2),       # model.3's shape class
     (1, 33, 31, 64, 256, 3, 2, 2),        # odd extents; the 256 x 256 tile applies
     (2, 20, 20, 256, 256, 3, 2, 2),       # 4 chunks x 9 taps
@@ -368,13 +370,14 @@ KORDER_CASES = [
     (2, 24, 24, 96, 64, 3, 1, 1),         # stride 1: the patch kernel's order, three chunks
     (2, 24, 40, 128, 128, 3, 1, 1),       # stride 1, Cin % 64 == 0: still 32-channel chunks (no 64-deep K-steps)
     (2, 16, 16, 96, 128, 1, 1, 0),        # 1x1: one tap, one order
+    (2, 16, 16, 128, 256, 1, 1, 0),       # 1x1, Cin % 64 == 0, whole 256-cout tiles: the 64-deep K-steps and the 256 x 256 tile at ksize 1
     (2, 12, 10, 24, 32, 3, 1, 0),         # unaligned channel count: generic variant only
 ]
 
 
 @pytest.mark.parametrize("case", KORDER_CASES)
 def test_conv_every_configuration_of_a_layer_is_bit_identical(case, monkeypatch):
-    """The K walk of a conv is a function of its shape (conv_mfma.hip conv_korder), not of the kernel configuration: every id the
+    """The K walk of a conv is a function of its shape (conv_select.hip conv_korder), not of the kernel configuration: every id the
     library accepts for a layer -- implicit-GEMM tiles with BK 32 / 64 and 2 / 3 stages, patch tiles, persistent tiles -- returns
     the same bits (round-2 VERDICT: results must not depend on what the autotuner timed), and ids of another walk (recorded by an
     older tune cache) are rejected."""
@@ -396,7 +399,8 @@ def test_conv_every_configuration_of_a_layer_is_bit_identical(case, monkeypatch)
             monkeypatch.setenv("BSY_CONV_CFG", str(cfg))
             try:
                 out = O.conv2d_nhwc(xd, wp, bp, cout, k, s, True)
-            except L.BsyError:
+            except L.BsyError as e:  # refused by conv_cfg_valid -- never by a family launcher that lacks an id the table accepts
+                assert "is not valid for this shape" in str(e), (hex(cfg), str(e))
                 continue
             accepted.append(cfg)
             assert torch.equal(out, base), hex(cfg)
@@ -943,7 +947,7 @@ def test_predict_pipeline_config1_end_to_end():
 @pytest.mark.parametrize("scale,shape", [("n", (1, 32, 32)), ("s", (3, 96, 224)), ("s", (2, 160, 32)), ("n", (5, 64, 416)), ("s", (16, 320, 320))])
 def test_engine_tuned_equals_untuned_bit_for_bit(scale, shape):
     """Results do not depend on what the autotuner timed (round-2 VERDICT 3): every kernel configuration that is valid for a layer
-    sums in that layer's K walk (conv_mfma.hip conv_korder), so a tuned engine -- patch / persistent / big-tile kernels wherever
+    sums in that layer's K walk (conv_select.hip conv_korder), so a tuned engine -- patch / persistent / big-tile kernels wherever
     they won on THIS box -- returns bit for bit what the heuristic plan (autotune off) returns, and two separately tuned engines
     agree with each other, through both tuners."""
     m = R.Model("yolo11", scale, 80, "detect")
@@ -1226,9 +1230,14 @@ def test_engine_no_harmful_reads_past_the_weight_blob(fam, scale, nc, task, shap
         e.close()
 
 
-@pytest.mark.parametrize("fam,scale,nc,shape", [("yolo11", "s", 80, (2, 640, 640)), ("yolo11", "n", 80, (3, 512, 544)), ("yolov8", "n", 80, (1, 512, 512)),
-                                                ("bsyolo11", "n", 12, (1, 640, 512))])
-def test_engine_box_branch_tail_is_bit_identical(fam, scale, nc, shape, monkeypatch):
+# the un-tuned plan runs the tail on the 2-stage rows (0xB2 / 0xD2); the last six cases preset every tail row of the table in turn
+TAIL_CASES = [pytest.param(*c, None, id=f"{c[0]}-{c[1]}-{c[2]}-shape{i}") for i, c in enumerate([
+    ("yolo11", "s", 80, (2, 640, 640)), ("yolo11", "n", 80, (3, 512, 544)), ("yolov8", "n", 80, (1, 512, 512)), ("bsyolo11", "n", 12, (1, 640, 512))])]
+TAIL_CASES += [pytest.param("yolo11", "n", 80, (3, 512, 544), c, id=f"yolo11-n-80-cfg{c:#04x}") for c in (0xB1, 0xB2, 0xB3, 0xD1, 0xD2, 0xD3)]
+
+
+@pytest.mark.parametrize("fam,scale,nc,shape,tail_cfg", TAIL_CASES)
+def test_engine_box_branch_tail_is_bit_identical(fam, scale, nc, shape, tail_cfg, monkeypatch):
     """cv2.i.1 + cv2.i.2 + DFL in one launch (conv3x3_patch_kernel TAIL) against the two launches: y and the raw maps bit for bit, f16 and
     f32 outputs, 8x16 and 6x20 tiles, ragged tile rows / columns.  Every level is at least 16 pixels high and wide, so the un-tuned plan
     runs the separate 3x3 conv on the patch kernel too (the heuristic's condition): same K walk on both sides; smaller maps are
@@ -1245,6 +1254,16 @@ def test_engine_box_branch_tail_is_bit_identical(fam, scale, nc, shape, monkeypa
         eng = YoloEngine(cfg, sd, autotune=False)
         plan = eng.plan_for(B, H, W, torch.float16, torch.float16)[0]
         assert sum(1 for o in plan.ops if o["kind"] == L.OP_CONV and o.get("mid_c")) == (3 if tail == "1" else 0)
+        if tail == "1" and tail_cfg is not None:  # the three tail ops of both plans (f16 and f32 inputs) on this configuration
+            import ctypes as C
+            for dt in (torch.float16, torch.float32):
+                pl, h = eng.plan_for(B, H, W, dt, dt)
+                want = [tail_cfg if o["kind"] == L.OP_CONV and o.get("mid_c") else -1 for o in pl.ops]
+                assert sum(1 for c in want if c >= 0) == 3
+                L.check(L.lib.bsy_plan_set_tuning(h, (C.c_int32 * len(want))(*want), len(want)))
+                got = (C.c_int32 * len(want))()
+                L.check(L.lib.bsy_plan_get_tuning(h, got, len(want)))
+                assert [g for g, c in zip(got, want) if c >= 0] == [tail_cfg] * 3
         y16, r16 = eng(x.half().to(DEV))
         y32, r32 = eng(x.to(DEV))
         torch.cuda.synchronize()

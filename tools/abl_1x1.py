@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
-"""Ablations of one HBM-bound 1x1 layer (model.4.cv2 of YOLO11s: 192 -> 256 @ 80 x 80, B = 64) under BSY_CONV_DBG (set in the environment:
-1 = no DMA, 4 = no epilogue) for a list of configurations.  usage: BSY_CONV_DBG=<n> python tools/abl_1x1.py [cin cout H]"""
+"""Ablations of one HBM-bound 1x1 layer (model.4.cv2 of YOLO11s: 192 -> 256 @ 80 x 80, B = 64) for a list of configurations.  The shipped
+library has no ablation switch; the implicit-GEMM kernel (conv_gemm.hip, configuration 0x41 below) takes one at COMPILE time, -DBSY_ABLATE=<n>:
+1 = no DMA, 4 = no epilogue, 5 = both (results are WRONG under them).  Build a variant library and point BSY_LIB at it:
+    tools/build_variant.sh abl1 conv_gemm.hip "-DBSY_ABLATE=1"
+    BSY_LIB=bs_yolo_amd/libbsyolo_abl1.so python tools/abl_1x1.py [cin cout H]
+Without BSY_LIB the shipped library runs: the baseline the ablated times are read against."""
 import os, sys
 from pathlib import Path
 import torch
@@ -12,7 +16,7 @@ x = (torch.randn(64, H, H, cin, device=dev) * 0.5).half()
 w = torch.randn(cout, cin, 1, 1) * (2.0 / cin) ** 0.5
 wp, bp = O.pack_conv_weight(w, torch.zeros(cout), dev)
 mb = 64 * H * H * (cin + cout) * 2 / 1e6
-print("BSY_CONV_DBG =", os.environ.get("BSY_CONV_DBG", "0"), f"{cin}->{cout} @{H}: {mb:.0f} MB")
+print("BSY_LIB =", os.environ.get("BSY_LIB", "(shipped library)"), f"{cin}->{cout} @{H}: {mb:.0f} MB")
 for cfg in (0x41, 0x82, 0xe1, 0xe2):
     os.environ["BSY_CONV_CFG"] = str(cfg)
     try:

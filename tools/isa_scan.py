@@ -16,7 +16,8 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 PACKED_OK = ()  # kernels allowed to carry hand-written packed f32 arithmetic: none
 
 
-def disassemble(obj: Path) -> str:
+def _code_object(obj: Path, tool: str, *args: str) -> str:
+    """Output of an llvm tool run on the gfx950 code object bundled in a host object file ("" for a unit without kernels)."""
     with tempfile.TemporaryDirectory() as td:
         fat, co = Path(td) / "fat.bin", Path(td) / "dev.co"
         r = subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(obj)], capture_output=True, text=True)
@@ -26,7 +27,16 @@ def disassemble(obj: Path) -> str:
             raise RuntimeError(r.stderr)
         subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", f"--targets={TARGET}",
                         f"--output={co}"], check=True, capture_output=True)
-        return subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout
+        return subprocess.run([str(LLVM / tool), *args, str(co)], check=True, capture_output=True, text=True).stdout
+
+
+def disassemble(obj: Path) -> str:
+    return _code_object(obj, "llvm-objdump", "-d")
+
+
+def notes(obj: Path) -> str:
+    """The code object's metadata note (amdhsa.kernels: register counts, LDS and scratch sizes per kernel)."""
+    return _code_object(obj, "llvm-readelf", "--notes")
 
 
 def kernels(asm: str):
