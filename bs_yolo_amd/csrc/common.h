@@ -316,9 +316,6 @@ struct DecodeArgs {
     int ne;  // OBB angle channels (0 / 1): msk[l] then holds the angle logits and nm is 0
 };
 int launch_decode(const DecodeArgs& a, hipStream_t s);
-// bsy_nms's candidate keys (nms.hip steps 1-2) for another consumer: filter + sort, the prediction left untouched
-int nms_candidates(void* pred, int pred_dtype, int B, int nc, int C, int A, float conf_thres, const int32_t* classes, int n_classes,
-                   int multi_label, int cap, unsigned long long* keys, int32_t* cand_count, hipStream_t s);
 // val_match.hip: the validator's matching rule on an IoU matrix (B, Lmax, max_det) made elsewhere (val_masks.hip); arguments as
 // bsy_val_match's, already validated by the caller
 int val_match_from_iou(const float* iou, const float* det, int row, const int32_t* counts, int B, int max_det, const float* gt_cls,

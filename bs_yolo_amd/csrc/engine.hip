@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "postproc.h"
 
 struct bsy_engine {
     int device = 0;
@@ -91,7 +92,7 @@ extern "C" int bsy_engine_load_weights(bsy_engine* e, const void* host_blob, siz
     // (tests compare a poisoned engine with a plain one; round 1 found such a read in the flat-DMA path by accident, 8ab4d40).
     // Reads past the blob whose values are discarded (padding rows of a cout tile) stay invisible by design.
     const char* g = getenv("BSY_WEIGHT_GUARD");
-    const size_t guard = g ? ((size_t)atoll(g) + 255) & ~(size_t)255 : 0;
+    const size_t guard = g ? align256((size_t)atoll(g)) : 0;
     if (hipMalloc(&e->weights, bytes + 256 + guard) != hipSuccess) BSY_FAIL(BSY_ERR_ALLOC, "load_weights: hipMalloc(%zu) failed", bytes);
     HIP_TRY(hipMemcpy(e->weights, host_blob, bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset((char*)e->weights + bytes, guard ? 0x7C : 0, 256 + guard));
@@ -129,14 +130,14 @@ extern "C" int bsy_plan_create(bsy_engine* e, const bsy_op* ops, int n_ops, cons
     // bsy_plan_check_guards reports the first band a kernel wrote into (an out-of-bounds store).
     {
         const char* g = getenv("BSY_PLAN_GUARD");
-        p->guard = g ? ((size_t)atoll(g) + 255) & ~(size_t)255 : 0;
+        p->guard = g ? align256((size_t)atoll(g)) : 0;
     }
     size_t off = 0;
     for (int i = 0; i < n_bufs; ++i) {
         if (buf_bytes[i] < 0) { delete p; BSY_FAIL(BSY_ERR_ARG, "plan_create: negative buffer size"); }
         p->buf_off.push_back(off);
         p->buf_size.push_back((size_t)buf_bytes[i]);
-        off += (((size_t)buf_bytes[i] + 255) & ~(size_t)255) + p->guard;
+        off += align256((size_t)buf_bytes[i]) + p->guard;
     }
     p->workspace_bytes = off + 256;
     if (hipMalloc((void**)&p->workspace, p->workspace_bytes) != hipSuccess) {
@@ -150,7 +151,7 @@ extern "C" int bsy_plan_create(bsy_engine* e, const bsy_op* ops, int n_ops, cons
         BSY_FAIL(BSY_ERR_HIP, "plan_create: hipMemset failed");
     }
     for (int i = 0; i < n_bufs && p->guard; ++i)
-        if (hipMemset(p->workspace + p->buf_off[i] + ((p->buf_size[i] + 255) & ~(size_t)255), 0xA5, p->guard) != hipSuccess) {
+        if (hipMemset(p->workspace + p->buf_off[i] + align256(p->buf_size[i]), 0xA5, p->guard) != hipSuccess) {
             (void)hipFree(p->workspace);
             delete p;
             BSY_FAIL(BSY_ERR_HIP, "plan_create: guard memset failed");
@@ -214,7 +215,7 @@ extern "C" int bsy_plan_check_guards(bsy_plan* p, int32_t* bad_buf, int64_t* bad
     HIP_TRY(hipDeviceSynchronize());
     std::vector<unsigned char> host(p->guard);
     for (size_t i = 0; i < p->buf_off.size(); ++i) {
-        HIP_TRY(hipMemcpy(host.data(), p->workspace + p->buf_off[i] + ((p->buf_size[i] + 255) & ~(size_t)255), p->guard, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(host.data(), p->workspace + p->buf_off[i] + align256(p->buf_size[i]), p->guard, hipMemcpyDeviceToHost));
         for (size_t k = 0; k < p->guard; ++k)
             if (host[k] != 0xA5) {
                 *bad_buf = (int32_t)i;
@@ -259,9 +260,6 @@ struct Resolver {
 
 // fp32 correctness mode (bsy_op.prec == 1): same op records, f32 views, kernels of ref32.hip.  DECODE and RAW_NCHW consume f32
 // logit maps in both modes and fall through to the common path.
-// Byte offsets of the two f16 weight planes an fp32x plan's conv record carries behind its f32 matrix (weights.py pack_record):
-// [f32 K x Cout][pad to 256][hi: Cout x Kpad f16][pad to 256][lo: Cout x Kpad f16], Kpad = K rounded up to 32.
-static inline size_t fp32x_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 int run_op_f32(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, bool& handled) {
     const char* wb = (const char*)p->eng->weights;
@@ -286,8 +284,10 @@ int run_op_f32(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, 
             if (op.out_f32 >= 2) BSY_FAIL(BSY_ERR_ARG, "fp32 mode: fused Detect decoder ops are not part of fp32 plans");
             if (!R.ok) return BSY_ERR_ARG;
             if (op.prec == 2) {  // fp32x: split-f16 planes behind the f32 matrix; shapes the kernel does not take stay exact
+                // byte offsets of the two f16 weight planes the record carries behind its f32 matrix (weights.py pack_record):
+                // [f32 K x Cout][pad to 256][hi: Cout x Kpad f16][pad to 256][lo: Cout x Kpad f16], Kpad = K rounded up to 32
                 const size_t K = (size_t)a.ks * a.ks * (a.C0 + a.C1), kpad = (K + 31) & ~(size_t)31;
-                const size_t hi_off = fp32x_align(K * a.Cout * 4), lo_off = hi_off + fp32x_align((size_t)a.Cout * kpad * 2);
+                const size_t hi_off = align256(K * a.Cout * 4), lo_off = hi_off + align256((size_t)a.Cout * kpad * 2);
                 a.wx_hi = (const half_t*)(wb + op.w_off + hi_off);
                 a.wx_lo = (const half_t*)(wb + op.w_off + lo_off);
                 a.wx_kpad = (int)kpad;

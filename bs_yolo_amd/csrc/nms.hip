@@ -2,23 +2,22 @@
 // round exactly like the fp32 CPU reference (inter / (area_i + area_j - inter) > thr, no FMA contraction).
 //
 // Replaces utils/ops.py:167-316 (non_max_suppression), :416-433 (xywh2xyxy) and the greedy suppression the reference
-// delegates to torchvision.ops.nms (:296).  Three kernels per call, whole batch each:
+// delegates to torchvision.ops.nms (:296).  Three kernels per call, whole batch each (the shared pieces are postproc.h's):
 //   1. nms_filter_kernel  (thread = anchor): xywh->xyxy in the prediction dtype (optionally written back, as the
 //      reference mutates its input :243-244); confidence filter -- best class (:273-275) or multi-label expansion
 //      (:270-272) --; optional class filter (:278-279); survivors are appended as 64-bit keys
 //      (fp32 score bits << 32 | ~candidate_index): ONE descending sort gives "score descending, ties by ascending
 //      candidate index", which is the order torchvision's sort + the reference's max_nms argsort produce.
-//   2. nms_sort_kernel    (block = image): bitonic sort of the keys (LDS up to 8192 keys, else in global memory).
+//   2. key_sort_kernel    (block = image): bitonic sort of the keys (LDS up to 8192 keys, else in global memory).  The
+//      library's ONE sort of 64-bit keys: launch_key_sort also serves sahi.hip.
 //   3. nms_greedy_kernel  (block = image): walks the sorted candidates 256 at a time.  Each candidate is first
 //      tested against the boxes already kept (LDS), then the survivors of the chunk are resolved among themselves
-//      by a parallel fixed point on the chunk's 256x256 overlap bitmask (keep = every overlapping earlier candidate
-//      is suppressed; suppressed = some overlapping earlier candidate is kept) -- identical to the sequential greedy
-//      order, without 256 serial steps.  Stops at max_det kept (:297 `i[:max_det]`).
+//      by greedy_resolve_256 -- identical to the sequential greedy order, without 256 serial steps.  Stops at max_det
+//      kept (:297 `i[:max_det]`).
+// Steps 1-2 are nms_candidates, which obb.hip's rotated NMS starts from as well; nms_check_args is shared with it too.
 // The class offset `boxes + cls * max_wh` (:289-295) is applied in fp32 exactly as on the CPU.  Input fp16 is
 // upcast to fp32 (the fp16 reference path overflows 7680*cls; we follow the fp32 CPU reference instead).
-#include "common.h"
-
-typedef unsigned long long u64;
+#include "postproc.h"
 
 struct NmsK {
     void* pred;
@@ -69,21 +68,17 @@ __global__ __launch_bounds__(256) void nms_filter_kernel(const NmsK p) {
             if (!ok) continue;
             const int pos = atomicAdd(p.cand_count + b, 1);
             const unsigned idx = (unsigned)a * (unsigned)p.nc + (unsigned)c;
-            keys[pos] = ((u64)__float_as_uint(s) << 32) | (u64)(~idx);
+            keys[pos] = score_key(s, idx);
         }
     } else {
-        float best = (float)cp[0];
-        int bc = 0;
-        for (int c = 1; c < p.nc; ++c) {
-            const float s = (float)cp[(size_t)c * p.A];
-            if (s > best) { best = s; bc = c; }
-        }
+        float best;
+        const int bc = first_max_class(cp, p.A, p.nc, best);
         if (!(best > p.conf)) return;
         bool ok = p.n_classes == 0;
         for (int k = 0; k < p.n_classes; ++k) ok |= (p.classes[k] == bc);
         if (!ok) return;
         const int pos = atomicAdd(p.cand_count + b, 1);
-        keys[pos] = ((u64)__float_as_uint(best) << 32) | (u64)(~(unsigned)a);
+        keys[pos] = score_key(best, (unsigned)a);
     }
 }
 
@@ -126,50 +121,27 @@ __global__ __launch_bounds__(256) void nms_filter4_kernel(const NmsK p) {
         for (int k = 0; k < p.n_classes; ++k) ok |= (p.classes[k] == bc[j]);
         if (!ok) continue;
         const int pos = atomicAdd(p.cand_count + b, 1);
-        keys[pos] = ((u64)__float_as_uint(s) << 32) | (u64)(~(unsigned)(a0 + j));
+        keys[pos] = score_key(s, (unsigned)(a0 + j));
     }
 }
 
-#define SORT_LDS_KEYS 8192
-__global__ __launch_bounds__(1024) void nms_sort_kernel(const NmsK p) {
+// Segment b = keys[b * stride ..), counts[b] keys, sorted descending in place (launch_key_sort, postproc.h).
+__global__ __launch_bounds__(1024) void key_sort_kernel(u64* keys_all, int stride, const int32_t* counts) {
     __shared__ u64 sk[SORT_LDS_KEYS];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const int n = p.cand_count[b];
+    const int n = counts[b];
     if (n <= 1) return;
-    int np2 = 2;
-    while (np2 < n) np2 <<= 1;
-    u64* keys = p.keys + (size_t)b * p.cap;
+    const int np2 = pow2_at_least(n);
+    u64* keys = keys_all + (size_t)b * stride;
     if (np2 <= SORT_LDS_KEYS) {
         for (int i = tid; i < np2; i += nt) sk[i] = i < n ? keys[i] : 0ull;
         __syncthreads();
-        for (int k = 2; k <= np2; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < np2; i += nt) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const u64 x = sk[i], y = sk[l];
-                        const bool desc = (i & k) == 0;  // descending overall
-                        if (desc ? (x < y) : (x > y)) { sk[i] = y; sk[l] = x; }
-                    }
-                }
-                __syncthreads();
-            }
+        block_bitonic_desc(sk, np2);
         for (int i = tid; i < n; i += nt) keys[i] = sk[i];
     } else {
-        for (int i = n + tid; i < np2; i += nt) keys[i] = 0ull;  // cap is a power of two >= np2
+        for (int i = n + tid; i < np2; i += nt) keys[i] = 0ull;  // stride is a power of two >= np2
         __syncthreads();
-        for (int k = 2; k <= np2; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < np2; i += nt) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const u64 x = keys[i], y = keys[l];
-                        const bool desc = (i & k) == 0;
-                        if (desc ? (x < y) : (x > y)) { keys[i] = y; keys[l] = x; }
-                    }
-                }
-                __syncthreads();
-            }
+        block_bitonic_desc(keys, np2);
     }
 }
 
@@ -186,7 +158,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void nms_greedy_kernel(const NmsK p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // layout: 64-bit words first, then ints, then floats (the host sizes it in bsy_nms)
-    u64* keepw = reinterpret_cast<u64*>(smem_raw);       // [4]
+    u64* keepw = reinterpret_cast<u64*>(smem_raw);       // [4]  keepw / supw / alw / sh_i[0]: greedy_resolve_256's
     u64* supw = keepw + 4;                               // [4]
     u64* alw = supw + 4;                                 // [4]
     int* sh_i = reinterpret_cast<int*>(alw + 4);         // [4]: [0] = undecided count, [1] = n_kept
@@ -203,6 +175,7 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(const NmsK p) {
     if (n > p.max_nms) n = p.max_nms;
     const int row = 6 + p.nm;
     float* ob = p.out + (size_t)b * p.max_det * row;
+    const GreedyLds sh = {keepw, supw, alw, sh_i};
     if (tid == 0) sh_i[1] = 0;
     __syncthreads();
 
@@ -215,20 +188,7 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(const NmsK p) {
         float score = 0.f, area = 0.f;
         int cls = 0, anchor = 0;
         if (have) {
-            const u64 k = keys[i];
-            score = __uint_as_float((unsigned)(k >> 32));
-            const unsigned idx = ~(unsigned)(k & 0xffffffffull);
-            if (p.multi_label) { anchor = (int)(idx / (unsigned)p.nc); cls = (int)(idx - (unsigned)anchor * p.nc); }
-            else {
-                anchor = (int)idx;
-                // best class = first maximum (ops.py:274 cls.max(1))
-                const T* cp = pb + (size_t)4 * p.A + anchor;
-                float best = (float)cp[0];
-                for (int c = 1; c < p.nc; ++c) {
-                    const float s = (float)cp[(size_t)c * p.A];
-                    if (s > best) { best = s; cls = c; }
-                }
-            }
+            decode_score_key(keys[i], p.nc, p.multi_label, pb, p.A, score, anchor, cls);
             load_xyxy<T>(pb, p.A, anchor, p.in_place != 0, bx);
             const float off = (float)cls * (p.agnostic ? 0.0f : p.max_wh);
 #pragma unroll
@@ -243,64 +203,11 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(const NmsK p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) cbox[4 * tid + e] = obx[e];
         carea[tid] = area;
-        if (tid < 4) { keepw[tid] = 0ull; supw[tid] = 0ull; }
-        __syncthreads();
-        // overlap bitmask of this candidate with EARLIER candidates of the chunk that survived phase A
-        const u64 aliveb = __ballot(alive);
-        if (lane == 0) alw[wave] = aliveb;
-        __syncthreads();
-        u64 alivew[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) alivew[w] = alw[w];
-        u64 mrow[4] = {0ull, 0ull, 0ull, 0ull};
-        if (alive) {
-            for (int j = 0; j < tid; ++j) {
-                if (!((alivew[j >> 6] >> (j & 63)) & 1ull)) continue;
-                if (iou_gt(cbox + 4 * j, carea[j], obx, area, p.iou)) mrow[j >> 6] |= 1ull << (j & 63);
-            }
-        }
-        // fixed point: state per candidate 0 = undecided, 1 = keep, 2 = suppressed
-        int state = alive ? 0 : 2;
-        if (!alive) atomicOr(&supw[wave], 1ull << lane);
-        for (int it = 0; it < 257; ++it) {
-            if (tid == 0) sh_i[0] = 0;
-            __syncthreads();
-            u64 kw[4], sw[4];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { kw[w] = keepw[w]; sw[w] = supw[w]; }
-            int ns = state;
-            if (state == 0) {
-                bool hit = false, pending = false;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    hit |= (mrow[w] & kw[w]) != 0ull;
-                    pending |= (mrow[w] & ~(kw[w] | sw[w])) != 0ull;
-                }
-                if (hit) ns = 2;
-                else if (!pending) ns = 1;
-            }
-            __syncthreads();  // everyone has read keepw/supw
-            if (ns != state) {
-                if (ns == 1) atomicOr(&keepw[wave], 1ull << lane);
-                else atomicOr(&supw[wave], 1ull << lane);
-                state = ns;
-            }
-            if (state == 0) atomicAdd(&sh_i[0], 1);
-            __syncthreads();
-            if (sh_i[0] == 0) break;
-            __syncthreads();
-        }
+        // the chunk's survivors among themselves
+        u64 mrow[4], kw[4];
+        const int state = greedy_resolve_256(alive, [&](int j) { return iou_gt(cbox + 4 * j, carea[j], obx, area, p.iou); }, sh, mrow, kw);
         // append kept candidates in order
-        u64 kw[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) kw[w] = keepw[w];
-        int before = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += __popcll(kw[w]);
-        }
-        before += __popcll(kw[wave] & ((1ull << lane) - 1ull));
-        const int slot = n_kept + before;
+        const int slot = n_kept + kept_rank<4>(kw, wave, kw[wave], lane);
         if (state == 1 && slot < p.max_det) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) kbox[4 * slot + e] = obx[e];
@@ -321,20 +228,63 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(const NmsK p) {
     if (tid == 0) p.counts[b] = sh_i[1];
 }
 
-#define NMS_MAX_DET 4096  // the kept boxes live in LDS: 20 bytes each (bsy_nms sizes the launch)
-
-static int next_pow2(long long v) {
-    long long p = 2;
-    while (p < v) p <<= 1;
-    return (int)p;
+int launch_key_sort(u64* keys, int stride, const int32_t* counts, int segments, hipStream_t s) {
+    hipLaunchKernelGGL(key_sort_kernel, dim3(segments), dim3(1024), 0, s, keys, stride, counts);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
 }
+
+// The one place that chooses a filter kernel: the 4-anchor form needs f16, best-class keys, A % 4 == 0 and 8-byte rows.
+int nms_candidates(void* pred, int pred_dtype, int B, int nc, int C, int A, float conf_thres, const int32_t* classes, int n_classes,
+                   int multi_label, int in_place, int cap, u64* keys, int32_t* cand_count, hipStream_t s) {
+    NmsK k = {};
+    k.pred = pred; k.B = B; k.nc = nc; k.nm = C - 4 - nc; k.A = A; k.C = C;
+    k.conf = conf_thres; k.classes = classes; k.n_classes = classes ? n_classes : 0; k.multi_label = multi_label;
+    k.in_place = in_place; k.cap = cap; k.keys = keys; k.cand_count = cand_count;
+    HIP_TRY(hipMemsetAsync(cand_count, 0, (size_t)B * 4, s));
+    if (pred_dtype == BSY_F16 && !multi_label && !(A & 3) && !((uintptr_t)pred & 7))
+        hipLaunchKernelGGL(nms_filter4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);
+    else
+        dispatch_dtype(pred_dtype, [&](auto t) {
+            hipLaunchKernelGGL(nms_filter_kernel<decltype(t)>, dim3((A + 255) / 256, B), dim3(256), 0, s, k);
+        });
+    return launch_key_sort(keys, cap, cand_count, B, s);
+}
+
+int nms_check_args(const char* op, const char* extra, const void* pred, const void* out, const void* counts, const void* workspace,
+                   int pred_dtype, int B, int nc, int n_extra, int A, float conf_thres, float iou_thres, int max_det, int max_nms) {
+    if (!pred || !out || !counts || !workspace) BSY_FAIL(BSY_ERR_ARG, "%s: null pointer", op);
+    if (B <= 0 || nc <= 0 || n_extra < 0 || A <= 0)
+        BSY_FAIL(BSY_ERR_ARG, "%s: bad sizes B=%d nc=%d %s=%d A=%d", op, B, nc, extra, n_extra, A);
+    if (!(conf_thres >= 0.f && conf_thres <= 1.f))  // the two texts of the reference's asserts (ops.py:218-219)
+        BSY_FAIL(BSY_ERR_ARG, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
+    if (!(iou_thres >= 0.f && iou_thres <= 1.f))
+        BSY_FAIL(BSY_ERR_ARG, "Invalid IoU %g, valid values are between 0.0 and 1.0", iou_thres);
+    if (max_det <= 0 || max_det > NMS_MAX_DET) BSY_FAIL(BSY_ERR_ARG, "%s: max_det %d out of range (1..%d)", op, max_det, NMS_MAX_DET);
+    if (max_nms <= 0) BSY_FAIL(BSY_ERR_ARG, "%s: max_nms must be positive", op);
+    if (pred_dtype != BSY_F16 && pred_dtype != BSY_F32) BSY_FAIL(BSY_ERR_ARG, "%s: dtype %d unsupported", op, pred_dtype);
+    if ((long long)A * nc > 0x7fffffffLL) BSY_FAIL(BSY_ERR_ARG, "%s: A*nc too large", op);
+    return BSY_OK;
+}
+
+// Workspace: per-image candidate counts, then `cap` keys per image.  With a null workspace only the returned size means anything.
+static size_t nms_carve(void* workspace, int B, size_t cap, NmsK& k) {
+    Carver c(workspace);
+    c.align();
+    k.cand_count = c.take<int32_t>(B);
+    c.align();
+    k.keys = c.take<u64>((size_t)B * cap);
+    return c.need;
+}
+
+// nms_greedy_kernel's LDS: 112 + (1280 + 5 * max_det) * 4 bytes, 87 152 at the ABI's max_det = 4096
+static size_t nms_greedy_lds(int max_det) { return 12 * 8 + 4 * 4 + ((size_t)256 * 5 + (size_t)max_det * 5) * 4; }
 
 extern "C" size_t bsy_nms_workspace_bytes(int B, int A, int nc, int multi_label, int max_nms) {
     (void)max_nms;
     if (B <= 0 || A <= 0 || nc <= 0) return 0;
-    const long long per = (multi_label && nc > 1) ? (long long)A * nc : (long long)A;
-    const size_t cap = (size_t)next_pow2(per);
-    return 256 + (size_t)B * 4 + (size_t)B * cap * 8 + 256;
+    NmsK measured;
+    return nms_carve(nullptr, B, (size_t)pow2_at_least((multi_label && nc > 1) ? (long long)A * nc : (long long)A), measured);
 }
 
 extern "C" int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A, float conf_thres, float iou_thres,
@@ -342,16 +292,8 @@ extern "C" int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A,
                        float max_wh, int in_place, float* out, int32_t* counts, void* workspace, size_t workspace_bytes,
                        bsy_stream stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (!pred || !out || !counts || !workspace) BSY_FAIL(BSY_ERR_ARG, "nms: null pointer");
-    if (B <= 0 || nc <= 0 || nm < 0 || A <= 0) BSY_FAIL(BSY_ERR_ARG, "nms: bad sizes B=%d nc=%d nm=%d A=%d", B, nc, nm, A);
-    if (!(conf_thres >= 0.f && conf_thres <= 1.f))
-        BSY_FAIL(BSY_ERR_ARG, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
-    if (!(iou_thres >= 0.f && iou_thres <= 1.f))
-        BSY_FAIL(BSY_ERR_ARG, "Invalid IoU %g, valid values are between 0.0 and 1.0", iou_thres);
-    if (max_det <= 0 || max_det > NMS_MAX_DET) BSY_FAIL(BSY_ERR_ARG, "nms: max_det %d out of range (1..%d)", max_det, NMS_MAX_DET);
-    if (max_nms <= 0) BSY_FAIL(BSY_ERR_ARG, "nms: max_nms must be positive");
-    if (pred_dtype != BSY_F16 && pred_dtype != BSY_F32) BSY_FAIL(BSY_ERR_ARG, "nms: dtype %d unsupported", pred_dtype);
-    if ((long long)A * nc > 0x7fffffffLL) BSY_FAIL(BSY_ERR_ARG, "nms: A*nc too large");
+    const int bad = nms_check_args("nms", "nm", pred, out, counts, workspace, pred_dtype, B, nc, nm, A, conf_thres, iou_thres, max_det, max_nms);
+    if (bad != BSY_OK) return bad;
     multi_label = (multi_label && nc > 1) ? 1 : 0;  // ops.py:239
     const size_t need = bsy_nms_workspace_bytes(B, A, nc, multi_label, max_nms);
     if (workspace_bytes < need) BSY_FAIL(BSY_ERR_ARG, "nms: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -360,57 +302,25 @@ extern "C" int bsy_nms(void* pred, int pred_dtype, int B, int nc, int nm, int A,
     k.conf = conf_thres; k.iou = iou_thres; k.classes = classes; k.n_classes = classes ? n_classes : 0;
     k.agnostic = agnostic; k.multi_label = multi_label; k.max_det = max_det; k.max_nms = max_nms; k.max_wh = max_wh;
     k.in_place = in_place;
-    k.cap = next_pow2(multi_label ? (long long)A * nc : (long long)A);
-    uintptr_t w = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    k.cand_count = (int32_t*)w;
-    k.keys = (u64*)(((w + (size_t)B * 4) + 255) & ~(uintptr_t)255);
+    k.cap = (int)pow2_at_least(multi_label ? (long long)A * nc : (long long)A);
+    nms_carve(workspace, B, (size_t)k.cap, k);
     k.out = out; k.counts = counts;
-    HIP_TRY(hipMemsetAsync(k.cand_count, 0, (size_t)B * 4, s));
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * max_det * (6 + nm) * sizeof(float), s));
-    dim3 g1((A + 255) / 256, B);
-    const size_t lds = 12 * 8 + 4 * 4 + ((size_t)256 * 5 + (size_t)max_det * 5) * 4;
-    // 112 + (1280 + 5 * max_det) * 4 bytes: 87 152 at the ABI's max_det = 4096.  Above 64 KiB a launch needs the function
-    // attribute (gfx950 has 160 KiB of LDS per CU); it is set once per process, for the bound's size.
+    // Above 64 KiB of LDS a launch needs the function attribute (gfx950 has 160 KiB per CU); it is set once per process, for the
+    // bound's size.
     static bool attr_set = false;
     if (!attr_set) {
-        const int lds_max = (int)(12 * 8 + 4 * 4 + ((size_t)256 * 5 + (size_t)NMS_MAX_DET * 5) * 4);
+        const int lds_max = (int)nms_greedy_lds(NMS_MAX_DET);
         HIP_TRY(hipFuncSetAttribute((const void*)nms_greedy_kernel<half_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         HIP_TRY(hipFuncSetAttribute((const void*)nms_greedy_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         attr_set = true;
     }
-    if (pred_dtype == BSY_F16) {
-        if (!multi_label && !(A & 3) && !((uintptr_t)pred & 7))
-            hipLaunchKernelGGL(nms_filter4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);
-        else
-            hipLaunchKernelGGL(nms_filter_kernel<half_t>, g1, dim3(256), 0, s, k);
-        hipLaunchKernelGGL(nms_sort_kernel, dim3(B), dim3(1024), 0, s, k);
-        hipLaunchKernelGGL(nms_greedy_kernel<half_t>, dim3(B), dim3(256), lds, s, k);
-    } else {
-        hipLaunchKernelGGL(nms_filter_kernel<float>, g1, dim3(256), 0, s, k);
-        hipLaunchKernelGGL(nms_sort_kernel, dim3(B), dim3(1024), 0, s, k);
-        hipLaunchKernelGGL(nms_greedy_kernel<float>, dim3(B), dim3(256), lds, s, k);
-    }
-    HIP_TRY(hipGetLastError());
-    return BSY_OK;
-}
-
-int nms_candidates(void* pred, int pred_dtype, int B, int nc, int C, int A, float conf_thres, const int32_t* classes, int n_classes,
-                   int multi_label, int cap, unsigned long long* keys, int32_t* cand_count, hipStream_t s) {
-    NmsK k = {};
-    k.pred = pred; k.B = B; k.nc = nc; k.nm = C - 4 - nc; k.A = A; k.C = C;
-    k.conf = conf_thres; k.classes = classes; k.n_classes = classes ? n_classes : 0; k.multi_label = multi_label;
-    k.in_place = 0; k.cap = cap; k.keys = keys; k.cand_count = cand_count;
-    HIP_TRY(hipMemsetAsync(cand_count, 0, (size_t)B * 4, s));
-    dim3 g1((A + 255) / 256, B);
-    if (pred_dtype == BSY_F16) {
-        if (!multi_label && !(A & 3) && !((uintptr_t)pred & 7))
-            hipLaunchKernelGGL(nms_filter4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);
-        else
-            hipLaunchKernelGGL(nms_filter_kernel<half_t>, g1, dim3(256), 0, s, k);
-    } else {
-        hipLaunchKernelGGL(nms_filter_kernel<float>, g1, dim3(256), 0, s, k);
-    }
-    hipLaunchKernelGGL(nms_sort_kernel, dim3(B), dim3(1024), 0, s, k);
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * max_det * (6 + nm) * sizeof(float), s));
+    const int rc = nms_candidates(pred, pred_dtype, B, nc, k.C, A, conf_thres, classes, k.n_classes, multi_label, in_place, k.cap, k.keys,
+                                  k.cand_count, s);
+    if (rc != BSY_OK) return rc;
+    dispatch_dtype(pred_dtype, [&](auto t) {
+        hipLaunchKernelGGL(nms_greedy_kernel<decltype(t)>, dim3(B), dim3(256), nms_greedy_lds(max_det), s, k);
+    });
     HIP_TRY(hipGetLastError());
     return BSY_OK;
 }

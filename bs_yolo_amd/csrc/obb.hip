@@ -4,20 +4,18 @@
 // Replaces non_max_suppression(..., rotated=True) (utils/ops.py:241-297) with nms_rotated (:146-164) and batch_probiou
 // (utils/metrics.py:261-278, :327-358), and the per-image tail of OBBPredictor.postprocess (models/yolo/obb/predict.py:48-49).
 // bsy_nms_rotated, whole batch per launch:
-//   1. nms_candidates (nms.hip): bsy_nms's confidence / class filter and key sort, score descending, ties by ascending index;
-//      the prediction stays xywhr (no xyxy conversion).
+//   1. nms_candidates (nms.hip, declared in postproc.h): bsy_nms's confidence / class filter and key sort, score descending, ties
+//      by ascending index; the prediction stays xywhr (no xyxy conversion).  The argument checks are nms.hip's nms_check_args.
 //   2. obb_gather_kernel   (thread = sorted candidate < max_nms): the class-offset centre and the covariance terms of
 //      _get_covariance_matrix, computed once per candidate into the workspace.
 //   3. obb_suppress_kernel (workgroup = 256 sorted candidates of one image): FAST-NMS -- candidate i is kept iff
 //      probiou(j, i) < thr for EVERY earlier j, suppressed j included (ious.triu_(1).max(0) < thr).  No decision depends on
 //      another decision, so every candidate is tested independently: earlier candidates are staged through LDS 256 at a time,
 //      a lane stops once its candidate is suppressed and the workgroup once all of its lanes are.
-//   4. obb_compact_kernel  (workgroup = image): order-preserving compaction of the kept flags, cut at max_det (exact: the
-//      decisions of the first max_det kept candidates do not depend on the ones after them).
-#include "common.h"
+//   4. obb_compact_kernel  (workgroup = image): order-preserving compaction of the kept flags (postproc.h block_kept_rank), cut
+//      at max_det (exact: the decisions of the first max_det kept candidates do not depend on the ones after them).
+#include "postproc.h"
 #include "probiou.h"
-
-typedef unsigned long long u64;
 
 struct ObbK {
     const void* pred;
@@ -27,8 +25,8 @@ struct ObbK {
     int nmax;             // records per image: min(max_nms, candidates the filter can produce)
     float max_wh;
     int cap;              // keys per image
-    const u64* keys;
-    const int32_t* cand_count;
+    u64* keys;
+    int32_t* cand_count;
     float* cov;           // (B, nmax, 8): x + off, y + off, a, b, c, clamp(a b - c^2, 0), -, -
     float* rows;          // (B, nmax, 8): x, y, w, h, conf, cls, anchor (int bits), -
     int32_t* keep;        // (B, nmax)
@@ -46,22 +44,9 @@ __global__ __launch_bounds__(256) void obb_gather_kernel(const ObbK p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (i >= obb_n(p, b)) return;
     const T* pb = reinterpret_cast<const T*>(p.pred) + (size_t)b * p.C * p.A;
-    const u64 k = p.keys[(size_t)b * p.cap + i];
-    const float score = __uint_as_float((unsigned)(k >> 32));
-    const unsigned idx = ~(unsigned)(k & 0xffffffffull);
-    int anchor, cls = 0;
-    if (p.multi_label) {
-        anchor = (int)(idx / (unsigned)p.nc);
-        cls = (int)(idx - (unsigned)anchor * p.nc);
-    } else {
-        anchor = (int)idx;  // best class = first maximum (ops.py:274 cls.max(1))
-        const T* cp = pb + (size_t)4 * p.A + anchor;
-        float best = (float)cp[0];
-        for (int c = 1; c < p.nc; ++c) {
-            const float s = (float)cp[(size_t)c * p.A];
-            if (s > best) { best = s; cls = c; }
-        }
-    }
+    float score;
+    int anchor, cls;
+    decode_score_key(p.keys[(size_t)b * p.cap + i], p.nc, p.multi_label, pb, p.A, score, anchor, cls);
     const float x = (float)pb[anchor], y = (float)pb[(size_t)p.A + anchor];
     const float w = (float)pb[(size_t)2 * p.A + anchor], h = (float)pb[(size_t)3 * p.A + anchor];
     // theta = the last column of the candidate's row (ops.py:292 x[:, -1:]): the last extra row, the class index without one
@@ -116,7 +101,7 @@ __global__ __launch_bounds__(OBB_TILE) void obb_suppress_kernel(const ObbK p) {
 template <typename T>
 __global__ __launch_bounds__(1024) void obb_compact_kernel(const ObbK p) {
     __shared__ int wsum[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int n = obb_n(p, b);
     const int row = 6 + p.ne;
     const T* pb = reinterpret_cast<const T*>(p.pred) + (size_t)b * p.C * p.A;
@@ -125,15 +110,8 @@ __global__ __launch_bounds__(1024) void obb_compact_kernel(const ObbK p) {
     for (int c0 = 0; c0 < n && base < p.max_det; c0 += 1024) {
         const int i = c0 + tid;
         const bool k = i < n && p.keep[(size_t)b * p.nmax + i] != 0;
-        const u64 m = __ballot(k);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            tot += wsum[w];
-        }
-        const int slot = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        int tot;
+        const int slot = base + block_kept_rank<16>(k, wsum, tot);
         if (k && slot < p.max_det) {
             const float* r = p.rows + ((size_t)b * p.nmax + i) * 8;
             float* o = ob + (size_t)slot * row;
@@ -148,20 +126,24 @@ __global__ __launch_bounds__(1024) void obb_compact_kernel(const ObbK p) {
     if (tid == 0) p.counts[b] = base < p.max_det ? base : p.max_det;
 }
 
-static long long obb_pow2(long long v) {
-    long long q = 2;
-    while (q < v) q <<= 1;
-    return q;
+// Workspace: bsy_nms's candidate counts and keys, then nmax records per image.  With a null workspace only the returned size
+// means anything.
+static size_t obb_carve(void* workspace, int B, size_t cap, size_t nmax, ObbK& k) {
+    Carver c(workspace);
+    c.align();
+    k.cand_count = c.take<int32_t>(B, true);
+    k.keys = c.take<u64>((size_t)B * cap, true);
+    k.cov = c.take<float>((size_t)B * nmax * 8, true);
+    k.rows = c.take<float>((size_t)B * nmax * 8, true);
+    k.keep = c.take<int32_t>((size_t)B * nmax, true);
+    return c.need;
 }
-
-static size_t obb_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 extern "C" size_t bsy_nms_rotated_workspace_bytes(int B, int A, int nc, int multi_label, int max_nms) {
     if (B <= 0 || A <= 0 || nc <= 0 || max_nms <= 0) return 0;
     const long long per = (multi_label && nc > 1) ? (long long)A * nc : (long long)A;
-    const size_t cap = (size_t)obb_pow2(per), nmax = (size_t)(per < max_nms ? per : max_nms);
-    return 256 + obb_align((size_t)B * 4) + obb_align((size_t)B * cap * 8) + 2 * obb_align((size_t)B * nmax * 32) +
-           obb_align((size_t)B * nmax * 4);
+    ObbK measured;
+    return obb_carve(nullptr, B, (size_t)pow2_at_least(per), (size_t)(per < max_nms ? per : max_nms), measured);
 }
 
 extern "C" int bsy_nms_rotated(void* pred, int pred_dtype, int B, int nc, int ne, int A, float conf_thres, float iou_thres,
@@ -169,17 +151,10 @@ extern "C" int bsy_nms_rotated(void* pred, int pred_dtype, int B, int nc, int ne
                                float max_wh, float* out, int32_t* counts, void* workspace, size_t workspace_bytes,
                                bsy_stream stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (!pred || !out || !counts || !workspace) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: null pointer");
-    if (B <= 0 || nc <= 0 || ne < 0 || A <= 0) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: bad sizes B=%d nc=%d ne=%d A=%d", B, nc, ne, A);
-    if (!(conf_thres >= 0.f && conf_thres <= 1.f))
-        BSY_FAIL(BSY_ERR_ARG, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
-    if (!(iou_thres >= 0.f && iou_thres <= 1.f))
-        BSY_FAIL(BSY_ERR_ARG, "Invalid IoU %g, valid values are between 0.0 and 1.0", iou_thres);
-    if (max_det <= 0 || max_det > 4096) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: max_det %d out of range (1..4096)", max_det);
-    if (max_nms <= 0) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: max_nms must be positive");
-    if (pred_dtype != BSY_F16 && pred_dtype != BSY_F32) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: dtype %d unsupported", pred_dtype);
-    if ((long long)A * nc > 0x7fffffffLL || (long long)B * (4 + nc + ne) * A > 0x7fffffffffffLL)
-        BSY_FAIL(BSY_ERR_ARG, "nms_rotated: A*nc too large");
+    const int bad = nms_check_args("nms_rotated", "ne", pred, out, counts, workspace, pred_dtype, B, nc, ne, A, conf_thres, iou_thres, max_det,
+                                   max_nms);
+    if (bad != BSY_OK) return bad;
+    if ((long long)B * (4 + nc + ne) * A > 0x7fffffffffffLL) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: A*nc too large");
     multi_label = (multi_label && nc > 1) ? 1 : 0;  // ops.py:239
     const size_t need = bsy_nms_rotated_workspace_bytes(B, A, nc, multi_label, max_nms);
     if (workspace_bytes < need) BSY_FAIL(BSY_ERR_ARG, "nms_rotated: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -187,32 +162,19 @@ extern "C" int bsy_nms_rotated(void* pred, int pred_dtype, int B, int nc, int ne
     ObbK k = {};
     k.pred = pred; k.B = B; k.nc = nc; k.ne = ne; k.A = A; k.C = 4 + nc + ne;
     k.iou = iou_thres; k.agnostic = agnostic; k.multi_label = multi_label; k.max_det = max_det;
-    k.nmax = (int)(per < max_nms ? per : max_nms); k.max_wh = max_wh; k.cap = (int)obb_pow2(per);
-    uintptr_t w = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    int32_t* cand = (int32_t*)w;
-    w += obb_align((size_t)B * 4);
-    u64* keys = (u64*)w;
-    w += obb_align((size_t)B * k.cap * 8);
-    k.cov = (float*)w;
-    w += obb_align((size_t)B * k.nmax * 32);
-    k.rows = (float*)w;
-    w += obb_align((size_t)B * k.nmax * 32);
-    k.keep = (int32_t*)w;
-    k.keys = keys; k.cand_count = cand; k.out = out; k.counts = counts;
+    k.nmax = (int)(per < max_nms ? per : max_nms); k.max_wh = max_wh; k.cap = (int)pow2_at_least(per);
+    obb_carve(workspace, B, (size_t)k.cap, (size_t)k.nmax, k);
+    k.out = out; k.counts = counts;
     HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * max_det * (6 + ne) * sizeof(float), s));
-    const int rc = nms_candidates(pred, pred_dtype, B, nc, k.C, A, conf_thres, classes, classes ? n_classes : 0, multi_label, k.cap,
-                                  keys, cand, s);
+    const int rc = nms_candidates(pred, pred_dtype, B, nc, k.C, A, conf_thres, classes, classes ? n_classes : 0, multi_label, 0, k.cap,
+                                  k.keys, k.cand_count, s);
     if (rc != BSY_OK) return rc;
-    dim3 grid((k.nmax + OBB_TILE - 1) / OBB_TILE, B);
-    if (pred_dtype == BSY_F16) {
-        hipLaunchKernelGGL(obb_gather_kernel<half_t>, grid, dim3(OBB_TILE), 0, s, k);
+    const dim3 grid((k.nmax + OBB_TILE - 1) / OBB_TILE, B);
+    dispatch_dtype(pred_dtype, [&](auto t) {
+        hipLaunchKernelGGL(obb_gather_kernel<decltype(t)>, grid, dim3(OBB_TILE), 0, s, k);
         hipLaunchKernelGGL(obb_suppress_kernel, grid, dim3(OBB_TILE), 0, s, k);
-        hipLaunchKernelGGL(obb_compact_kernel<half_t>, dim3(B), dim3(1024), 0, s, k);
-    } else {
-        hipLaunchKernelGGL(obb_gather_kernel<float>, grid, dim3(OBB_TILE), 0, s, k);
-        hipLaunchKernelGGL(obb_suppress_kernel, grid, dim3(OBB_TILE), 0, s, k);
-        hipLaunchKernelGGL(obb_compact_kernel<float>, dim3(B), dim3(1024), 0, s, k);
-    }
+        hipLaunchKernelGGL(obb_compact_kernel<decltype(t)>, dim3(B), dim3(1024), 0, s, k);
+    });
     HIP_TRY(hipGetLastError());
     return BSY_OK;
 }

@@ -13,10 +13,10 @@
 //     1. sahi_gather_kernel  clamp / validity test / shift per detection; survivors appended as 64-bit keys
 //                            (~class : score bits : ~flat index) -> ONE descending sort gives class ascending, score
 //                            descending, ties by ascending flat index.
-//     2. sahi_sort_kernel    bitonic sort (one workgroup; LDS up to 8192 keys, global memory above).
+//     2. launch_key_sort     nms.hip's key sort on one segment (LDS up to 8192 keys, global memory above).
 //     3. sahi_greedy_kernel  sahi's greedy_nmm keep/merge assignment, 256 candidates at a time: against the boxes kept
 //                            so far (first kept box of the same class with metric >= thr becomes the keeper), then
-//                            inside the chunk by the same parallel fixed point as nms_greedy_kernel.
+//                            inside the chunk by postproc.h's greedy_resolve_256, as nms_greedy_kernel does.
 //     4. sahi_merge_kernel   one wavefront per kept box walks its members in score order and applies has_match
 //                            (float64, metric > thr against the GROWING box) + box union / max score.
 //     3'. sahi_nmm_kernel   (postprocess NMM) sahi's non-greedy `nmm` assignment: the predictions of a class take turns in score
@@ -25,9 +25,7 @@
 //                            none).  Members remember the turn that assigned them: the merge walks them in (turn, ascending
 //                            score) order -- the order sahi's lists are appended in.
 // No host synchronisation anywhere; `out_count` stays on the device.
-#include "common.h"
-
-typedef unsigned long long u64;
+#include "postproc.h"
 
 // --------------------------------------------------------------------------------------------------------------------
 // tiles
@@ -153,38 +151,6 @@ __global__ __launch_bounds__(256) void sahi_gather_kernel(const SahiK p) {
     p.keys[pos] = ((u64)(0xFFFFu - (cls & 0xFFFFu)) << 48) | ((u64)__float_as_uint(d[4]) << 16) | (u64)(0xFFFFu - (unsigned)f);
 }
 
-#define SAHI_SORT_LDS 8192
-__global__ __launch_bounds__(1024) void sahi_sort_kernel(const SahiK p) {
-    __shared__ u64 sk[SAHI_SORT_LDS];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int n = p.n_cand[0];
-    if (n <= 1) return;
-    int np2 = 2;
-    while (np2 < n) np2 <<= 1;
-    u64* keys = p.keys;
-    const bool in_lds = np2 <= SAHI_SORT_LDS;
-    u64* a = in_lds ? sk : keys;
-    for (int i = tid; i < np2; i += nt) {
-        if (in_lds) sk[i] = i < n ? keys[i] : 0ull;
-        else if (i >= n) keys[i] = 0ull;  // cap >= np2
-    }
-    __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += nt) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const u64 x = a[i], y = a[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (x < y) : (x > y)) { a[i] = y; a[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    if (in_lds)
-        for (int i = tid; i < n; i += nt) keys[i] = sk[i];
-}
-
 // greedy_nmm's float32 test of a kept box against a candidate: "matched" unless metric < thr (NaN -> matched).
 __device__ __forceinline__ bool nmm_matched(const float* kb, float ka, const float* cb, float ca, int metric, float thr) {
     const float xx1 = fmaxf(cb[0], kb[0]), yy1 = fmaxf(cb[1], kb[1]);
@@ -197,12 +163,13 @@ __device__ __forceinline__ bool nmm_matched(const float* kb, float ka, const flo
 
 __global__ __launch_bounds__(256) void sahi_greedy_kernel(const SahiK p) {
     __shared__ u64 keepw[4], supw[4], alw[4];
-    __shared__ int sh_i[4];  // [0] undecided, [1] n_kept, [2] first kept slot that can share a class with this chunk
+    __shared__ int sh_i[4];  // [0] undecided (greedy_resolve_256), [1] n_kept, [2] first kept slot that can share a class with this chunk
     __shared__ float cbox[256 * 4];
     __shared__ float carea[256];
     __shared__ int ccls[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = p.n_cand[0];
+    const GreedyLds sh = {keepw, supw, alw, sh_i};
     if (tid == 0) { sh_i[1] = 0; sh_i[2] = 0; }
     __syncthreads();
 
@@ -248,60 +215,12 @@ __global__ __launch_bounds__(256) void sahi_greedy_kernel(const SahiK p) {
         for (int e = 0; e < 4; ++e) cbox[4 * tid + e] = bx[e];
         carea[tid] = area;
         ccls[tid] = mcls;
-        if (tid < 4) { keepw[tid] = 0ull; supw[tid] = 0ull; }
-        const u64 aliveb = __ballot(alive);
-        if (lane == 0) alw[wave] = aliveb;
-        __syncthreads();
-        u64 alivew[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) alivew[w] = alw[w];
-        u64 mrow[4] = {0ull, 0ull, 0ull, 0ull};
-        if (alive)
-            for (int j = 0; j < tid; ++j) {
-                if (!((alivew[j >> 6] >> (j & 63)) & 1ull) || ccls[j] != mcls) continue;
-                if (nmm_matched(cbox + 4 * j, carea[j], bx, area, p.metric, p.thr)) mrow[j >> 6] |= 1ull << (j & 63);
-            }
-        int state = alive ? 0 : 2;  // 0 undecided, 1 keep, 2 suppressed
-        if (!alive) atomicOr(&supw[wave], 1ull << lane);
-        for (int it = 0; it < 257; ++it) {
-            if (tid == 0) sh_i[0] = 0;
-            __syncthreads();
-            u64 kw[4], sw[4];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { kw[w] = keepw[w]; sw[w] = supw[w]; }
-            int ns = state;
-            if (state == 0) {
-                bool hit = false, pending = false;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    hit |= (mrow[w] & kw[w]) != 0ull;
-                    pending |= (mrow[w] & ~(kw[w] | sw[w])) != 0ull;
-                }
-                if (hit) ns = 2;
-                else if (!pending) ns = 1;
-            }
-            __syncthreads();
-            if (ns != state) {
-                if (ns == 1) atomicOr(&keepw[wave], 1ull << lane);
-                else atomicOr(&supw[wave], 1ull << lane);
-                state = ns;
-            }
-            if (state == 0) atomicAdd(&sh_i[0], 1);
-            __syncthreads();
-            if (sh_i[0] == 0) break;
-            __syncthreads();
-        }
-        u64 kw[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) kw[w] = keepw[w];
+        u64 mrow[4], kw[4];
+        const int state = greedy_resolve_256(
+            alive, [&](int j) { return ccls[j] == mcls && nmm_matched(cbox + 4 * j, carea[j], bx, area, p.metric, p.thr); }, sh, mrow, kw);
         // kept candidates take the next slots in order
         if (state == 1) {
-            int before = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w)
-                if (w < wave) before += __popcll(kw[w]);
-            before += __popcll(kw[wave] & ((1ull << lane) - 1ull));
-            const int slot = n_kept + before;
+            const int slot = n_kept + kept_rank<4>(kw, wave, kw[wave], lane);
 #pragma unroll
             for (int e = 0; e < 4; ++e) p.kbox[(size_t)slot * 4 + e] = bx[e];
             p.karea[slot] = area;
@@ -321,13 +240,7 @@ __global__ __launch_bounds__(256) void sahi_greedy_kernel(const SahiK p) {
                     const u64 m = mrow[w] & kw[w];
                     if (m) jj = 64 * w + __ffsll((long long)m) - 1;
                 }
-                int before = 0;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    if (64 * w + 64 <= jj) before += __popcll(kw[w]);
-                    else if (64 * w <= jj) before += __popcll(kw[w] & ((1ull << (jj & 63)) - 1ull));
-                }
-                keep_slot = n_kept + before;
+                keep_slot = n_kept + kept_rank<4>(kw, jj >> 6, kw[jj >> 6], jj & 63);
             }
             p.keeper[i] = keep_slot;
             atomicMax(p.klast + keep_slot, i);
@@ -345,8 +258,8 @@ __global__ __launch_bounds__(256) void sahi_greedy_kernel(const SahiK p) {
 // sahi's non-greedy nmm (sahi/postprocess/combine.py `nmm`, restated in oracle/sahi_ref.py nmm()).  One workgroup: the
 // assignment is a chain over the predictions in score order; every turn is parallel over the other boxes of the class.
 __global__ __launch_bounds__(1024) void sahi_nmm_kernel(const SahiK p) {
-    __shared__ int sh_end, sh_cnt[16], sh_base;
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int sh_end, sh_cnt[16];
+    const int tid = threadIdx.x, nt = blockDim.x;
     const int n = p.n_cand[0];
     for (int i = tid; i < n; i += nt) {
         const u64 k = p.keys[i];
@@ -395,29 +308,19 @@ __global__ __launch_bounds__(1024) void sahi_nmm_kernel(const SahiK p) {
         __syncthreads();  // position i + 1 reads what this turn assigned
     }
     // kept slots in position order (class ascending, score descending): chunked prefix count of iskeep
-    if (tid == 0) sh_base = 0;
-    __syncthreads();
+    int base = 0;  // kept so far (the same value in every thread)
     for (int c0 = 0; c0 < n; c0 += nt) {
         const int i = c0 + tid;
         const bool kp = i < n && p.iskeep[i];
-        const u64 b = __ballot(kp);
-        if (lane == 0) sh_cnt[wave] = __popcll(b);
-        __syncthreads();
-        int before = sh_base;
-        for (int w = 0; w < wave; ++w) before += sh_cnt[w];
+        int tot;
+        const int slot = base + block_kept_rank<16>(kp, sh_cnt, tot);
         if (kp) {
-            const int slot = before + __popcll(b & ((1ull << lane) - 1ull));
             p.keeper[i] = slot;
             p.kpos[slot] = i;
             p.klast[slot] = i;
         }
-        __syncthreads();
-        if (tid == 0) {
-            int t = sh_base;
-            for (int w = 0; w < nt / 64; ++w) t += sh_cnt[w];
-            sh_base = t;
-        }
-        __syncthreads();
+        base += tot;
+        __syncthreads();  // sh_cnt is rewritten by the next chunk; the last one publishes keeper / klast to the loop below
     }
     for (int i = tid; i < n; i += nt)
         if (!p.iskeep[i]) {
@@ -426,8 +329,8 @@ __global__ __launch_bounds__(1024) void sahi_nmm_kernel(const SahiK p) {
             atomicMax(p.klast + slot, i);
         }
     if (tid == 0) {
-        p.n_cand[1] = sh_base;
-        *p.out_count = sh_base < p.max_out ? sh_base : p.max_out;
+        p.n_cand[1] = base;
+        *p.out_count = base < p.max_out ? base : p.max_out;
     }
 }
 
@@ -513,16 +416,31 @@ __global__ __launch_bounds__(256) void sahi_merge_kernel(const SahiK p) {
     }
 }
 
-static int sahi_cap(long long n) {
-    long long c = 2;
-    while (c < n) c <<= 1;
-    return (int)c;
+// Workspace: the two counters, then per-candidate arrays of `cap` entries (21 words each).  With a null workspace only the
+// returned size means anything.
+static size_t sahi_carve(void* workspace, size_t cap, SahiK& p) {
+    Carver c(workspace);
+    p.n_cand = c.take<int32_t>(64);
+    p.keys = c.take<u64>(cap);
+    p.fbox = c.take<float>(cap * 4);
+    p.sbox = c.take<float>(cap * 4);
+    p.kbox = c.take<float>(cap * 4);
+    // the NMM assignment keeps no box copies: its four per-position arrays live in kbox
+    p.assigned = (int32_t*)p.kbox; p.turn = p.assigned + cap; p.iskeep = p.turn + cap; p.mcls = p.iskeep + cap;
+    p.sscore = c.take<float>(cap);
+    p.karea = c.take<float>(cap);
+    p.scls = c.take<int32_t>(cap);
+    p.keeper = c.take<int32_t>(cap);
+    p.kcls = c.take<int32_t>(cap);
+    p.kpos = c.take<int32_t>(cap);
+    p.klast = c.take<int32_t>(cap);
+    return c.need;
 }
 
-// per-candidate words: keys 2, fbox 4, sbox 4, sscore 1, scls 1, keeper 1, kbox 4, karea 1, kcls 1, kpos 1, klast 1
 extern "C" size_t bsy_sahi_merge_workspace_bytes(int T, int max_det) {
     if (T <= 0 || max_det <= 0) return 0;
-    return (size_t)sahi_cap((long long)T * max_det) * 21 * 4 + 256;
+    SahiK measured;
+    return sahi_carve(nullptr, (size_t)pow2_at_least((long long)T * max_det), measured);
 }
 
 extern "C" int bsy_sahi_merge(const float* det, const int32_t* counts, const float* shift, int T, int max_det, int row,
@@ -541,28 +459,14 @@ extern "C" int bsy_sahi_merge(const float* det, const int32_t* counts, const flo
     p.T = T; p.max_det = max_det; p.row = row;
     p.metric = match_metric; p.thr = match_threshold; p.agnostic = class_agnostic; p.do_merge = do_merge;
     p.full_w = full_w; p.full_h = full_h;
-    p.cap = sahi_cap((long long)T * max_det);
-    const size_t cap = (size_t)p.cap;
-    unsigned char* w = (unsigned char*)workspace;
-    p.n_cand = (int32_t*)w; w += 256;
-    p.keys = (u64*)w; w += cap * 8;
-    p.fbox = (float*)w; w += cap * 16;
-    p.sbox = (float*)w; w += cap * 16;
-    p.kbox = (float*)w;  // the NMM assignment keeps no box copies: its four per-position arrays live here
-    p.assigned = (int32_t*)w; p.turn = p.assigned + cap; p.iskeep = p.turn + cap; p.mcls = p.iskeep + cap;
-    w += cap * 16;
-    p.sscore = (float*)w; w += cap * 4;
-    p.karea = (float*)w; w += cap * 4;
-    p.scls = (int32_t*)w; w += cap * 4;
-    p.keeper = (int32_t*)w; w += cap * 4;
-    p.kcls = (int32_t*)w; w += cap * 4;
-    p.kpos = (int32_t*)w; w += cap * 4;
-    p.klast = (int32_t*)w; w += cap * 4;
+    p.cap = (int)pow2_at_least((long long)T * max_det);
+    sahi_carve(workspace, (size_t)p.cap, p);
     p.out = out; p.out_count = out_count; p.max_out = max_out;
     HIP_TRY(hipMemsetAsync(p.n_cand, 0, 256, s));
     const int slots = T * max_det;
     hipLaunchKernelGGL(sahi_gather_kernel, dim3((slots + 255) / 256), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(sahi_sort_kernel, dim3(1), dim3(1024), 0, s, p);
+    const int rc = launch_key_sort(p.keys, p.cap, p.n_cand, 1, s);  // one segment: its count is n_cand[0]
+    if (rc != BSY_OK) return rc;
     if (do_merge == 2) hipLaunchKernelGGL(sahi_nmm_kernel, dim3(1), dim3(1024), 0, s, p);
     else hipLaunchKernelGGL(sahi_greedy_kernel, dim3(1), dim3(256), 0, s, p);
     hipLaunchKernelGGL(sahi_merge_kernel, dim3(256), dim3(256), 0, s, p);

@@ -7,14 +7,13 @@
 //                   on 64-bit keys (score key << 32 | ~anchor) finds the K-th key, one pass collects the K anchors (LDS);
 //        stage 2 -- the K highest of the K x nc gathered class scores (:170): the gathered keys (score key << 32 |
 //                   ~(anchor * nc + class)) go to the workspace, a second radix select finds the K-th, the K winners are
-//                   collected into LDS and bitonic-sorted descending; row j = [box of the anchor, score, class] (:172).
+//                   collected into LDS and sorted descending (postproc.h block_bitonic_desc); row j = [box of the anchor, score,
+//                   class] (:172).
 // Keys are unique (the anchor / anchor-class index is in the low word), so "key >= K-th key" selects exactly K, and the order
 // is total: higher score first, then lower anchor index, then lower class -- torch's topk leaves equal values in an unspecified
 // order.  The selection compares the stored scores (f16 predictions: the f16 values, as the reference's half model does).
 // The radix select walks 8-bit digits from the top; a digit whose bin holds exactly the keys still needed ends it early.
-#include "common.h"
-
-typedef unsigned long long u64;
+#include "postproc.h"
 
 #define TOPK_MAX_K 4096  // max_det bound: the stage-2 winners are sorted in LDS
 #define TOPK_THREADS 1024
@@ -210,22 +209,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_select_kernel(const TopkK p
                 if (pos < (unsigned)K) sk[pos] = kk[j];
             }
     }
-    int np2 = 1;
+    int np2 = 1;  // (K = 1: nothing to sort)
     while (np2 < K) np2 <<= 1;
     for (int i = K + tid; i < np2; i += TOPK_THREADS) sk[i] = 0ull;  // sorts last: no real key is 0
     __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += TOPK_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const u64 x = sk[i], y = sk[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (x < y) : (x > y)) { sk[i] = y; sk[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
+    block_bitonic_desc(sk, np2);
 
     float* ob = p.out + (size_t)b * K * 6;
     for (int j = tid; j < K; j += TOPK_THREADS) {
@@ -244,12 +232,20 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_select_kernel(const TopkK p
     }
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// Workspace: one score key per anchor, then the K x nc stage-2 keys of every image.  With a null workspace only the returned size
+// means anything.
+static size_t topk_carve(void* workspace, int B, int A, int nc, size_t K, TopkK& k) {
+    Carver c(workspace);
+    c.align();
+    k.amax = c.take<unsigned>((size_t)B * A, true);
+    k.gath = c.take<u64>((size_t)B * K * nc, true);
+    return c.need;
+}
 
 extern "C" size_t bsy_end2end_topk_workspace_bytes(int B, int A, int nc, int max_det) {
     if (B <= 0 || A <= 0 || nc <= 0 || max_det <= 0) return 0;
-    const size_t K = (size_t)(max_det < A ? max_det : A);
-    return 256 + align256((size_t)B * A * 4) + align256((size_t)B * K * nc * 8);
+    TopkK measured;
+    return topk_carve(nullptr, B, A, nc, (size_t)(max_det < A ? max_det : A), measured);
 }
 
 extern "C" int bsy_end2end_topk(const void* pred, int pred_dtype, int B, int nc, int A, int max_det, float* out, void* workspace,
@@ -265,21 +261,17 @@ extern "C" int bsy_end2end_topk(const void* pred, int pred_dtype, int B, int nc,
     hipStream_t s = (hipStream_t)stream;
     TopkK k;
     k.pred = pred; k.B = B; k.nc = nc; k.A = A; k.K = max_det < A ? max_det : A;
-    const uintptr_t w = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    k.amax = (unsigned*)w;
-    k.gath = (u64*)(w + align256((size_t)B * A * 4));
+    topk_carve(workspace, B, A, nc, (size_t)k.K, k);
     k.out = out;
-    const dim3 g1((A + 255) / 256, B);
-    if (pred_dtype == BSY_F16) {
-        if (!(A & 3) && !((uintptr_t)pred & 7))
-            hipLaunchKernelGGL(topk_amax4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);
-        else
-            hipLaunchKernelGGL(topk_amax_kernel<half_t>, g1, dim3(256), 0, s, k);
-        hipLaunchKernelGGL(topk_select_kernel<half_t>, dim3(B), dim3(TOPK_THREADS), 0, s, k);
-    } else {
-        hipLaunchKernelGGL(topk_amax_kernel<float>, g1, dim3(256), 0, s, k);
-        hipLaunchKernelGGL(topk_select_kernel<float>, dim3(B), dim3(TOPK_THREADS), 0, s, k);
-    }
+    if (pred_dtype == BSY_F16 && !(A & 3) && !((uintptr_t)pred & 7))
+        hipLaunchKernelGGL(topk_amax4_kernel, dim3((A / 4 + 255) / 256, B), dim3(256), 0, s, k);
+    else
+        dispatch_dtype(pred_dtype, [&](auto t) {
+            hipLaunchKernelGGL(topk_amax_kernel<decltype(t)>, dim3((A + 255) / 256, B), dim3(256), 0, s, k);
+        });
+    dispatch_dtype(pred_dtype, [&](auto t) {
+        hipLaunchKernelGGL(topk_select_kernel<decltype(t)>, dim3(B), dim3(TOPK_THREADS), 0, s, k);
+    });
     HIP_TRY(hipGetLastError());
     return BSY_OK;
 }

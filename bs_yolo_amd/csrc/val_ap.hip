@@ -13,9 +13,8 @@
 //          interpolation integrated by the trapezoid rule (:609-612);  prec_values = np.interp(x, mrec, mpre) at IoU 0.5 (:682).
 //      np.interp is restated as numpy computes it: last knot <= x, exact hits return the knot, else slope * (x - xp) + fp.
 // The max-F1 operating point (:690-706: a box filter over a (nc, 1000) array) stays on the host (bs_yolo_amd/val.py).
-#include "common.h"
+#include "postproc.h"
 
-typedef unsigned long long u64;
 #define AP_MAXT 16
 
 struct ApK {
@@ -162,15 +161,9 @@ __global__ __launch_bounds__(256) void ap_class_kernel(const ApK p) {
     }
 }
 
-static int ap_pow2(int n) {
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 extern "C" size_t bsy_ap_workspace_bytes(int N, int T) {
     if (N <= 0 || T <= 0) return 0;
-    return (size_t)ap_pow2(N) * 8 + (size_t)N * T * 16 + (size_t)N * 8 + 256;
+    return (size_t)pow2_at_least(N) * 8 + (size_t)N * T * 16 + (size_t)N * 8 + 256;
 }
 
 extern "C" int bsy_ap_per_class(const uint8_t* tp, const float* conf, const float* pred_cls, int N, int T, const int32_t* classes,
@@ -184,7 +177,7 @@ extern "C" int bsy_ap_per_class(const uint8_t* tp, const float* conf, const floa
     if (!workspace || workspace_bytes < bsy_ap_workspace_bytes(N, T)) BSY_FAIL(BSY_ERR_ARG, "ap_per_class: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     ApK p;
-    p.tp = tp; p.conf = conf; p.pred_cls = pred_cls; p.N = N; p.T = T; p.Np2 = ap_pow2(N);
+    p.tp = tp; p.conf = conf; p.pred_cls = pred_cls; p.N = N; p.T = T; p.Np2 = pow2_at_least(N);
     p.classes = classes; p.nt = nt; p.nc = nc; p.x101 = x101; p.x1000 = x1000; p.eps = eps;
     unsigned char* w = (unsigned char*)workspace;
     p.keys = (u64*)w; w += (size_t)p.Np2 * 8;

@@ -419,8 +419,7 @@ class YoloEngine:
         y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
         ext, n = self._ext(im, y, [None, None, None])
         ms = (C.c_float * len(plan.ops))()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.check(L.lib.bsy_plan_profile(h, ext, n, C.c_void_p(stream), ms))
+        L.check(L.lib.bsy_plan_profile(h, ext, n, L.stream_ptr(self.device), ms))
         return [(o["name"], o["kind"], float(t)) for o, t in zip(plan.ops, ms)], plan
 
     def check_guards(self):

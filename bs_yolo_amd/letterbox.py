@@ -70,7 +70,7 @@ def preprocess(ims: List, imgsz=(640, 640), half=True, pt=True, stride=32, devic
     hw = torch.tensor([[t.shape[0], t.shape[1]] for t in dimgs], dtype=torch.int32).to(dev)
     geom = torch.tensor([[g[2], g[3], g[4], g[5]] for g in geoms], dtype=torch.int32).to(dev)
     out = torch.empty((B, 3, H2, W2), dtype=torch.float16 if half else torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = L.stream_ptr(dev)
     L.check(L.lib.bsy_letterbox(C.c_void_p(ptrs.data_ptr()), C.c_void_p(hw.data_ptr()), C.c_void_p(geom.data_ptr()), B,
                                 H2, W2, C.c_void_p(out.data_ptr()), L.dtype_code(out.dtype), stream))
     # keep the sources alive until the kernel has consumed them

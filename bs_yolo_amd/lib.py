@@ -177,6 +177,11 @@ def check(rc: int) -> None:
         raise BsyError(f"libbsyolo_hip: {lib.bsy_last_error().decode(errors='replace')} (status {rc})")
 
 
+def stream_ptr(device) -> C.c_void_p:
+    """torch's current stream on `device`, as the C ABI's bsy_stream argument."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def dtype_code(t) -> int:
     import torch
     if t == torch.float16:

@@ -29,7 +29,7 @@ def process_mask(protos: torch.Tensor, masks_in: torch.Tensor, bboxes: torch.Ten
     coef = masks_in.to(torch.float32).contiguous()
     boxes = bboxes.to(torch.float32).contiguous()
     low = torch.empty((n, mh, mw), dtype=torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = L.stream_ptr(dev)
     L.check(L.lib.bsy_process_mask(C.c_void_p(protos.data_ptr()), L.dtype_code(protos.dtype), c, mh, mw,
                                    C.c_void_p(coef.data_ptr()), coef.shape[1], C.c_void_p(boxes.data_ptr()),
                                    boxes.shape[1], n, ih, iw, int(bool(upsample)), C.c_void_p(low.data_ptr()),
@@ -61,7 +61,7 @@ def scale_masks(masks: torch.Tensor, shape, padding: bool = True) -> torch.Tenso
     if N * Cc == 0:
         return out
     m = masks.contiguous()
-    stream = C.c_void_p(torch.cuda.current_stream(masks.device).cuda_stream)
+    stream = L.stream_ptr(masks.device)
     L.check(L.lib.bsy_scale_masks(C.c_void_p(m.data_ptr()), L.dtype_code(m.dtype), N * Cc, mh, mw, top, left, bottom, right, oh, ow,
                                   C.c_void_p(out.data_ptr()), stream))
     return out
@@ -84,7 +84,7 @@ def process_mask_native(protos: torch.Tensor, masks_in: torch.Tensor, bboxes: to
     coef = masks_in.to(torch.float32).contiguous()
     boxes = bboxes.to(torch.float32).contiguous()
     low = torch.empty((n, mh, mw), dtype=torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = L.stream_ptr(dev)
     L.check(L.lib.bsy_process_mask_native(C.c_void_p(protos.data_ptr()), L.dtype_code(protos.dtype), c, mh, mw,
                                           C.c_void_p(coef.data_ptr()), coef.shape[1], C.c_void_p(boxes.data_ptr()), boxes.shape[1], n,
                                           top, left, bottom, right, oh, ow, C.c_void_p(low.data_ptr()), C.c_void_p(out.data_ptr()),

@@ -23,36 +23,46 @@ def _workspace(device, nbytes: int) -> torch.Tensor:
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def nms_batched(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False,
-                multi_label=False, max_det=300, nc=0, max_nms=30000, max_wh=7680, in_place=True):
-    """Device-resident result: (det (B, max_det, 6+nm) fp32, counts (B,) int32).  No host synchronisation."""
+def _check_input(prediction: torch.Tensor, shape_doc: str):
     if not prediction.is_cuda:
         raise RuntimeError("bs_yolo_amd.nms needs a GPU tensor (no CPU fallback)")
     if prediction.dim() != 3:
-        raise ValueError("prediction must be (B, 4+nc+nm, A)")
-    if not prediction.is_contiguous():
-        if in_place:
-            raise ValueError("in_place NMS needs a contiguous (B, C, A) prediction")
-        prediction = prediction.contiguous()
+        raise ValueError(f"prediction must be {shape_doc}")
+
+
+def _prologue(prediction: torch.Tensor, classes, multi_label, max_det, nc, workspace_bytes, max_nms):
+    """What the two batched entry points share once `prediction` is checked and contiguous (each has its own rule for that): nc and
+    the extra rows' count, the class filter tensor (the caller holds it across the launch), the effective multi_label (utils/ops.py:239), outputs and workspace."""
     B, Cc, A = prediction.shape
     nc = nc or (Cc - 4)
-    nm = Cc - nc - 4
+    nx = Cc - nc - 4
     dev = prediction.device
-    cls_t = None
-    if classes is not None:
-        cls_t = torch.as_tensor(list(classes), dtype=torch.int32, device=dev)
+    cls_t = torch.as_tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
     ml = bool(multi_label) and nc > 1
-    nbytes = L.lib.bsy_nms_workspace_bytes(B, A, nc, int(ml), int(max_nms))
-    ws = _workspace(dev, nbytes)
-    det = torch.empty((B, max_det, 6 + nm), dtype=torch.float32, device=dev)
+    ws = _workspace(dev, workspace_bytes(B, A, nc, int(ml), int(max_nms)))
+    det = torch.empty((B, max_det, 6 + nx), dtype=torch.float32, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    return B, nc, nx, A, cls_t, ml, det, counts, ws
+
+
+def _cls_args(cls_t: Optional[torch.Tensor]):
+    return (C.c_void_p(cls_t.data_ptr()), int(cls_t.numel())) if cls_t is not None else (None, 0)
+
+
+def nms_batched(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False,
+                multi_label=False, max_det=300, nc=0, max_nms=30000, max_wh=7680, in_place=True):
+    """Device-resident result: (det (B, max_det, 6+nm) fp32, counts (B,) int32).  No host synchronisation."""
+    _check_input(prediction, "(B, 4+nc+nm, A)")
+    if not prediction.is_contiguous():
+        if in_place:  # the boxes are rewritten in the caller's tensor: a copy would hide that
+            raise ValueError("in_place NMS needs a contiguous (B, C, A) prediction")
+        prediction = prediction.contiguous()
+    B, nc, nm, A, cls_t, ml, det, counts, ws = _prologue(prediction, classes, multi_label, max_det, nc,
+                                                            L.lib.bsy_nms_workspace_bytes, max_nms)
     L.check(L.lib.bsy_nms(C.c_void_p(prediction.data_ptr()), L.dtype_code(prediction.dtype), B, nc, nm, A,
-                          float(conf_thres), float(iou_thres),
-                          C.c_void_p(cls_t.data_ptr()) if cls_t is not None else None,
-                          int(cls_t.numel()) if cls_t is not None else 0, int(bool(agnostic)), int(ml), int(max_det),
+                          float(conf_thres), float(iou_thres), *_cls_args(cls_t), int(bool(agnostic)), int(ml), int(max_det),
                           int(max_nms), float(max_wh), int(bool(in_place)), C.c_void_p(det.data_ptr()),
-                          C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), stream))
+                          C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(prediction.device)))
     return det, counts
 
 
@@ -62,29 +72,14 @@ def nms_rotated_batched(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.4
     (det (B, max_det, 6+ne) fp32 rows [x, y, w, h, conf, cls, extra...], counts (B,) int32).  The prediction is not modified.
     Suppression is the reference's fast-NMS (a candidate is dropped by ANY higher-scored candidate it overlaps, suppressed or
     not), which keeps fewer boxes than greedy NMS on chains of overlaps.  No host synchronisation."""
-    if not prediction.is_cuda:
-        raise RuntimeError("bs_yolo_amd.nms needs a GPU tensor (no CPU fallback)")
-    if prediction.dim() != 3:
-        raise ValueError("prediction must be (B, 4+nc+ne, A)")
-    prediction = prediction.contiguous()
-    B, Cc, A = prediction.shape
-    nc = nc or (Cc - 4)
-    ne = Cc - nc - 4
-    dev = prediction.device
-    cls_t = None
-    if classes is not None:
-        cls_t = torch.as_tensor(list(classes), dtype=torch.int32, device=dev)
-    ml = bool(multi_label) and nc > 1
-    ws = _workspace(dev, L.lib.bsy_nms_rotated_workspace_bytes(B, A, nc, int(ml), int(max_nms)))
-    det = torch.empty((B, max_det, 6 + ne), dtype=torch.float32, device=dev)
-    counts = torch.empty((B,), dtype=torch.int32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _check_input(prediction, "(B, 4+nc+ne, A)")
+    prediction = prediction.contiguous()  # never written: a copy is fine
+    B, nc, ne, A, cls_t, ml, det, counts, ws = _prologue(prediction, classes, multi_label, max_det, nc,
+                                                            L.lib.bsy_nms_rotated_workspace_bytes, max_nms)
     L.check(L.lib.bsy_nms_rotated(C.c_void_p(prediction.data_ptr()), L.dtype_code(prediction.dtype), B, nc, ne, A,
-                                  float(conf_thres), float(iou_thres),
-                                  C.c_void_p(cls_t.data_ptr()) if cls_t is not None else None,
-                                  int(cls_t.numel()) if cls_t is not None else 0, int(bool(agnostic)), int(ml), int(max_det),
+                                  float(conf_thres), float(iou_thres), *_cls_args(cls_t), int(bool(agnostic)), int(ml), int(max_det),
                                   int(max_nms), float(max_wh), C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                  C.c_void_p(ws.data_ptr()), ws.numel(), stream))
+                                  C.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(prediction.device)))
     return det, counts
 
 
@@ -118,7 +113,7 @@ def scale_boxes_batched(det: torch.Tensor, counts: torch.Tensor, img1_shape, img
     The gain / pad per image are computed on the host exactly as the reference does (Python round())."""
     B, max_det, row = det.shape
     t = scale_params(B, img1_shape, img0_shapes, ratio_pads, det.device)
-    stream = C.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)
+    stream = L.stream_ptr(det.device)
     L.check(L.lib.bsy_scale_boxes(C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()), B, max_det, row,
                                   C.c_void_p(t[0].data_ptr()), C.c_void_p(t[1].data_ptr()), C.c_void_p(t[2].data_ptr()),
                                   C.c_void_p(t[3].data_ptr()), C.c_void_p(t[4].data_ptr()), stream))

@@ -21,7 +21,7 @@ def scale_batched(det: torch.Tensor, counts: torch.Tensor, img1_shape, img0_shap
     images and clipped.  Gain / pads per image from the host, with the reference's Python arithmetic (round())."""
     B, max_det, row = det.shape
     t = scale_params(B, img1_shape, img0_shapes, ratio_pads, det.device)
-    stream = C.c_void_p(torch.cuda.current_stream(det.device).cuda_stream)
+    stream = L.stream_ptr(det.device)
     L.check(L.lib.bsy_obb_scale(C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()), B, max_det, row,
                                 C.c_void_p(t[0].data_ptr()), C.c_void_p(t[1].data_ptr()), C.c_void_p(t[2].data_ptr()),
                                 C.c_void_p(t[3].data_ptr()), C.c_void_p(t[4].data_ptr()), stream))

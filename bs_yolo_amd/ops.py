@@ -14,7 +14,7 @@ from . import lib as L
 
 
 def _stream(t: torch.Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    return L.stream_ptr(t.device)
 
 
 def _p(t: Optional[torch.Tensor]):

@@ -87,7 +87,7 @@ def slice_image(image, bboxes: Sequence[Sequence[int]], half: bool = True, swap_
             raise ValueError(f"slice {[x0, y0, x1, y1]} leaves the {W} x {H} image")
     boxes = torch.tensor(np.asarray(bboxes, dtype=np.int32)).to(dev)
     out = torch.empty((len(bboxes), 3, th, tw), dtype=torch.float16 if half else torch.float32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = L.stream_ptr(dev)
     L.check(L.lib.bsy_slice_tiles(C.c_void_p(img.data_ptr()), H, W, 3 * W, C.c_void_p(boxes.data_ptr()), len(bboxes), th,
                                   tw, int(bool(swap_rb)), C.c_void_p(out.data_ptr()), L.dtype_code(out.dtype), stream))
     out._bsy_keepalive = (img, boxes)
@@ -118,7 +118,7 @@ def postprocess(det: torch.Tensor, counts: torch.Tensor, shifts, postprocess_typ
     n = torch.zeros((), dtype=torch.int32, device=dev)
     ws = _workspace(dev, L.lib.bsy_sahi_merge_workspace_bytes(T, max_det))
     fh, fw = (float(full_shape[0]), float(full_shape[1])) if full_shape is not None else (0.0, 0.0)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = L.stream_ptr(dev)
     L.check(L.lib.bsy_sahi_merge(C.c_void_p(det.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(sh.data_ptr()), T,
                                  max_det, row, METRICS[match_metric], float(match_threshold), int(bool(class_agnostic)),
                                  _POSTPROCESS[postprocess_type], fw, fh, C.c_void_p(out.data_ptr()),

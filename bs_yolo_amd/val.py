@@ -46,10 +46,10 @@ def match_batched(det: torch.Tensor, counts: torch.Tensor, gt_boxes: torch.Tenso
     gt_counts = gt_counts.to(det.device, torch.int32).contiguous()
     arr, n = _iouv_host(iouv)
     out = torch.empty((B, max_det, n), dtype=torch.uint8, device=det.device)
-    stream = torch.cuda.current_stream(det.device).cuda_stream
+    stream = L.stream_ptr(det.device)
     L.check(L.lib.bsy_val_match(C.c_void_p(det.data_ptr()), row, C.c_void_p(counts.data_ptr()), B, max_det,
                                 C.c_void_p(gb.data_ptr()), C.c_void_p(gc.data_ptr()), C.c_void_p(gt_counts.data_ptr()), Lmax,
-                                arr, n, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+                                arr, n, C.c_void_p(out.data_ptr()), stream))
     return out.bool()
 
 
@@ -97,9 +97,9 @@ def pack_masks(masks: torch.Tensor) -> PackedMasks:
     planes = torch.empty(lead + (words,), dtype=torch.int64, device=m.device)
     areas = torch.zeros(lead, dtype=torch.int32, device=m.device)
     if n and hw:
-        stream = torch.cuda.current_stream(m.device).cuda_stream
+        stream = L.stream_ptr(m.device)
         L.check(L.lib.bsy_pack_masks(C.c_void_p(m.data_ptr()), L.dtype_code(m.dtype), n, hw, 0, C.c_void_p(planes.data_ptr()),
-                                     C.c_void_p(areas.data_ptr()), C.c_void_p(stream)))
+                                     C.c_void_p(areas.data_ptr()), stream))
     return PackedMasks(planes, areas, hw)
 
 
@@ -116,9 +116,9 @@ def pack_label_map(index_map: torch.Tensor, nl: int) -> PackedMasks:
     planes = torch.empty((nl, words), dtype=torch.int64, device=m.device)
     areas = torch.zeros((nl,), dtype=torch.int32, device=m.device)
     if nl and hw:
-        stream = torch.cuda.current_stream(m.device).cuda_stream
+        stream = L.stream_ptr(m.device)
         L.check(L.lib.bsy_pack_masks(C.c_void_p(m.data_ptr()), L.dtype_code(m.dtype), nl, hw, 1, C.c_void_p(planes.data_ptr()),
-                                     C.c_void_p(areas.data_ptr()), C.c_void_p(stream)))
+                                     C.c_void_p(areas.data_ptr()), stream))
     return PackedMasks(planes, areas, hw)
 
 
@@ -157,13 +157,13 @@ def match_masks_batched(det: torch.Tensor, counts: torch.Tensor, pred_planes: Pa
         ws = torch.empty(nbytes, dtype=torch.uint8, device=det.device)
     else:
         assert iou_out.is_cuda and iou_out.dtype == torch.float32 and iou_out.is_contiguous() and tuple(iou_out.shape) == (B, Lmax, max_det)
-    stream = torch.cuda.current_stream(det.device).cuda_stream
+    stream = L.stream_ptr(det.device)
     L.check(L.lib.bsy_val_match_masks(
         C.c_void_p(det.data_ptr()), row, C.c_void_p(counts.data_ptr()), B, max_det, C.c_void_p(pp.contiguous().data_ptr()),
         C.c_void_p(pa.contiguous().data_ptr()), C.c_void_p(gp.contiguous().data_ptr()), C.c_void_p(ga.contiguous().data_ptr()), words,
         C.c_void_p(gc.data_ptr()), C.c_void_p(gt_counts.data_ptr()), Lmax, arr, n, C.c_void_p(out.data_ptr()),
         C.c_void_p(iou_out.data_ptr()) if iou_out is not None else None, C.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes,
-        C.c_void_p(stream)))
+        stream))
     return out.bool()
 
 
@@ -186,11 +186,11 @@ def match_rotated_batched(det: torch.Tensor, counts: torch.Tensor, gt_rboxes: to
     out = torch.empty((B, max_det, n), dtype=torch.uint8, device=det.device)
     if iou_out is not None:
         assert iou_out.is_cuda and iou_out.dtype == torch.float32 and iou_out.is_contiguous() and tuple(iou_out.shape) == (B, Lmax, max_det)
-    stream = torch.cuda.current_stream(det.device).cuda_stream
+    stream = L.stream_ptr(det.device)
     L.check(L.lib.bsy_val_match_rotated(C.c_void_p(det.data_ptr()), row, C.c_void_p(counts.data_ptr()), B, max_det,
                                         C.c_void_p(gb.data_ptr()), C.c_void_p(gc.data_ptr()), C.c_void_p(gt_counts.data_ptr()), Lmax,
                                         arr, n, C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(iou_out.data_ptr()) if iou_out is not None else None, C.c_void_p(stream)))
+                                        C.c_void_p(iou_out.data_ptr()) if iou_out is not None else None, stream))
     return out.bool()
 
 
@@ -281,7 +281,7 @@ def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, on_plot=None, save_
         d_p, d_r, d_pv = (torch.empty((nc, 1000), dtype=torch.float64, device=dev) for _ in range(3))
         d_np = torch.zeros((nc,), dtype=torch.int32, device=dev)
         ws = torch.empty(L.lib.bsy_ap_workspace_bytes(N, T), dtype=torch.uint8, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = L.stream_ptr(dev)
         L.check(L.lib.bsy_ap_per_class(C.c_void_p(t_tp.data_ptr()), C.c_void_p(t_conf.data_ptr()), C.c_void_p(t_cls.data_ptr()), N, T,
                                        C.c_void_p(d_cls.data_ptr()), C.c_void_p(d_nt.data_ptr()), nc, C.c_void_p(d_x101.data_ptr()),
                                        C.c_void_p(d_x1000.data_ptr()), float(eps), C.c_void_p(d_ap.data_ptr()),

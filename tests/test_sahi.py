@@ -204,10 +204,12 @@ def _merge_both(det, counts, shifts, full, **kw):
     dict(postprocess_type="NMM", match_metric="IOU", match_threshold=0.2, class_agnostic=True),
     dict(postprocess_type="LSNMS", match_metric="IOU", match_threshold=0.5),  # runs as NMS
 ])
-@pytest.mark.parametrize("T,max_det,n_obj,seed", [(1, 8, 3, 0), (4, 16, 12, 1), (12, 100, 150, 2), (70, 300, 1200, 3)])
+@pytest.mark.parametrize("T,max_det,n_obj,seed", [(1, 8, 3, 0), (4, 16, 12, 1), (12, 100, 150, 2), (70, 300, 1200, 3),
+                                                  (2, 128, 600, 12), (70, 300, 4000, 4)])
 def test_sahi_merge_bit_exact(T, max_det, n_obj, seed, kw):
     """Keep set, merge order, union boxes, scores, classes and output order equal the oracle's bit for bit, from one chunk
-    (<= 256 candidates) to BASELINE config 5's 70 x 300 slots (> 8192 candidates: the global-memory sort)."""
+    (<= 256 candidates) to BASELINE config 5's 70 x 300 slots.  Valid candidates of the six cases: 1, 5, 235, 3318 (neither a
+    multiple of the 256-candidate chunk), exactly 256 (one full chunk), and 10794 (> 8192: the key sort's global-memory path)."""
     det, counts, shifts, full = _tile_dets(T, max_det, n_obj, seed)
     ref, got = _merge_both(det, counts, shifts, full, **kw)
     assert got.shape == ref.shape, (got.shape, ref.shape)

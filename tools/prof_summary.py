@@ -28,7 +28,7 @@ for r in rows:
     key = n.split("<")[0].split("(")[0].replace("void ", "")
     if key.startswith("_Z"):
         for k in CONV + ("dwconv3x3", "sppf_pool", "attention", "decode", "nms_filter",
-                  "nms_sort", "nms_greedy", "raw_nchw"):
+                  "key_sort", "nms_greedy", "raw_nchw"):
             if k in key:
                 key = k if k.endswith("_kernel") else k + "_kernel"
     d = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
