@@ -304,12 +304,12 @@ struct AttnArgs {
 int launch_attention(const AttnArgs& a, hipStream_t s);
 
 struct DecodeArgs {
-    const float* box[3];
-    const float* cls[3];
-    const float* msk[3];
-    int ldb[3], ldc[3], ldm[3];
-    int h[3], w[3];
-    float stride[3];
+    const float* box[BSY_MAX_LEVELS];
+    const float* cls[BSY_MAX_LEVELS];
+    const float* msk[BSY_MAX_LEVELS];
+    int ldb[BSY_MAX_LEVELS], ldc[BSY_MAX_LEVELS], ldm[BSY_MAX_LEVELS];
+    int h[BSY_MAX_LEVELS], w[BSY_MAX_LEVELS];
+    float stride[BSY_MAX_LEVELS];
     int nl, B, nc, nm, A;
     void* y;
     int y_dtype;

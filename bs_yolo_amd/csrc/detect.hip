@@ -12,12 +12,12 @@
 #include "common.h"
 
 struct DecodeK {
-    const float* box[3];
-    const float* cls[3];
-    const float* msk[3];
-    int ldb[3], ldc[3], ldm[3];
-    int h[3], w[3], a0[3];  // a0 = first anchor index of the level
-    float stride[3];
+    const float* box[BSY_MAX_LEVELS];
+    const float* cls[BSY_MAX_LEVELS];
+    const float* msk[BSY_MAX_LEVELS];
+    int ldb[BSY_MAX_LEVELS], ldc[BSY_MAX_LEVELS], ldm[BSY_MAX_LEVELS];
+    int h[BSY_MAX_LEVELS], w[BSY_MAX_LEVELS], a0[BSY_MAX_LEVELS];  // a0 = first anchor index of the level
+    float stride[BSY_MAX_LEVELS];
     int nl, B, nc, nm, A;
     int ne;  // ROT: angle channels (1), read through the msk slots
 };
@@ -29,8 +29,12 @@ struct DecodeK {
 // ROT (OBB head, head.py:211-227): the msk slots carry the angle logits; theta = (sigmoid - 0.25) * pi (head.py:216), the box
 // is dist2rbox (utils/tal.py:404-423) times the stride, and theta is written as row 4 + nc.  The Detect / Segment instances
 // (ROT = false) are the kernel as it was.
+// HALVES (heads of more than three levels: the P2 / P6 graphs): the DFL sums run in the order of the fused head's epilogue
+// (conv_kernels.h dfl_decode_store: bins 0-3, 8-11 and bins 4-7, 12-15 as two partial sums, then their sum), so that a plan with
+// the decode launch returns the bits of the same plan with the fused head.  Heads of up to three levels keep the sequential sums
+// their outputs have always had (HALVES = false is the kernel as it was).
 #define DEC_TA 64
-template <typename T, bool ROT>
+template <typename T, bool ROT, bool HALVES>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restrict__ y) {
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     const int tid = threadIdx.x;
@@ -38,7 +42,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
     // which level / tile
     int l = 0, t = blockIdx.x;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < BSY_MAX_LEVELS; ++i) {
         const int nt = i < p.nl ? (p.h[i] * p.w[i] + DEC_TA - 1) / DEC_TA : 0;
         if (i == l && t >= nt && i + 1 < p.nl) { t -= nt; l = i + 1; }
     }
@@ -92,11 +96,26 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
 #pragma unroll
         for (int i = 1; i < 16; ++i) m = fmaxf(m, v[i]);
         float den = 0.f, num = 0.f;
+        if (HALVES) {
+            float den1 = 0.f, num1 = 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float e = __expf(v[i] - m);
-            den += e;
-            num += e * (float)i;
+            for (int i = 0; i < 8; ++i) {
+                const int b0 = (i & 3) + 8 * (i >> 2), b1 = b0 + 4;
+                const float e0 = __expf(v[b0] - m), e1 = __expf(v[b1] - m);
+                den += e0;
+                num += e0 * (float)b0;
+                den1 += e1;
+                num1 += e1 * (float)b1;
+            }
+            den += den1;
+            num += num1;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float e = __expf(v[i] - m);
+                den += e;
+                num += e * (float)i;
+            }
         }
         sd[a * 4 + part] = num / den;
     }
@@ -133,12 +152,12 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
 }
 
 int launch_decode(const DecodeArgs& a, hipStream_t s) {
-    if (a.nl < 1 || a.nl > 3 || a.nc < 1 || a.B < 1) BSY_FAIL(BSY_ERR_ARG, "decode: bad sizes");
+    if (a.nl < 1 || a.nl > BSY_MAX_LEVELS || a.nc < 1 || a.B < 1) BSY_FAIL(BSY_ERR_ARG, "decode: bad sizes");
     if (a.ne < 0 || a.ne > 1 || (a.ne && a.nm)) BSY_FAIL(BSY_ERR_ARG, "decode: ne = %d with nm = %d (one angle, no mask coefficients)", a.ne, a.nm);
     const int nx = a.nm + a.ne;  // rows read through the msk slots
     DecodeK k;
     int A = 0;
-    for (int l = 0; l < 3; ++l) {
+    for (int l = 0; l < BSY_MAX_LEVELS; ++l) {
         const bool on = l < a.nl;
         k.box[l] = on ? a.box[l] : nullptr; k.cls[l] = on ? a.cls[l] : nullptr; k.msk[l] = on ? a.msk[l] : nullptr;
         k.ldb[l] = on ? a.ldb[l] : 0; k.ldc[l] = on ? a.ldc[l] : 0; k.ldm[l] = on ? a.ldm[l] : 0;
@@ -162,14 +181,19 @@ int launch_decode(const DecodeArgs& a, hipStream_t s) {
     dim3 grid(tiles, a.B);
     const size_t lds = (size_t)DEC_TA * (65 + (a.nc + nx + 1) + 4) * sizeof(float);
     if (lds > 64 * 1024) BSY_FAIL(BSY_ERR_ARG, "decode: nc + nm = %d too large", a.nc + nx);
+    const bool halves = a.nl > 3;  // (an OBB head has at most three levels: plan.py)
     if (a.y_dtype == BSY_F16 && a.ne)
-        hipLaunchKernelGGL((decode_kernel<half_t, true>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+        hipLaunchKernelGGL((decode_kernel<half_t, true, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32 && a.ne)
-        hipLaunchKernelGGL((decode_kernel<float, true>), grid, dim3(256), lds, s, k, (float*)a.y);
+        hipLaunchKernelGGL((decode_kernel<float, true, false>), grid, dim3(256), lds, s, k, (float*)a.y);
+    else if (a.y_dtype == BSY_F16 && halves)
+        hipLaunchKernelGGL((decode_kernel<half_t, false, true>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+    else if (a.y_dtype == BSY_F32 && halves)
+        hipLaunchKernelGGL((decode_kernel<float, false, true>), grid, dim3(256), lds, s, k, (float*)a.y);
     else if (a.y_dtype == BSY_F16)
-        hipLaunchKernelGGL((decode_kernel<half_t, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+        hipLaunchKernelGGL((decode_kernel<half_t, false, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32)
-        hipLaunchKernelGGL((decode_kernel<float, false>), grid, dim3(256), lds, s, k, (float*)a.y);
+        hipLaunchKernelGGL((decode_kernel<float, false, false>), grid, dim3(256), lds, s, k, (float*)a.y);
     else
         BSY_FAIL(BSY_ERR_ARG, "decode: y dtype %d unsupported", a.y_dtype);
     HIP_TRY(hipGetLastError());

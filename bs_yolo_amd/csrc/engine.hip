@@ -594,7 +594,7 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             memset(&a, 0, sizeof(a));
             a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A; a.ne = op.ne;
             const bool extra = op.nm || op.ne;  // mask coefficients (Segment) or angle logits (OBB) in the msk slots
-            for (int l = 0; l < op.nl && l < 3; ++l) {
+            for (int l = 0; l < op.nl && l < BSY_MAX_LEVELS; ++l) {
                 a.box[l] = R.f(op.box[l]); a.cls[l] = R.f(op.cls[l]); a.msk[l] = extra ? R.f(op.msk[l]) : nullptr;
                 a.ldb[l] = op.box[l].ld; a.ldc[l] = op.cls[l].ld; a.ldm[l] = extra ? op.msk[l].ld : 0;
                 a.h[l] = op.lvl_h[l]; a.w[l] = op.lvl_w[l]; a.stride[l] = op.lvl_stride[l];
@@ -605,7 +605,7 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
         }
         case BSY_OP_RAW_NCHW: {
             const int l = op.level;
-            if (l < 0 || l > 2) BSY_FAIL(BSY_ERR_ARG, "raw_nchw: level %d", l);
+            if (l < 0 || l >= BSY_MAX_LEVELS) BSY_FAIL(BSY_ERR_ARG, "raw_nchw: level %d", l);
             // optional output: silently skipped when the slot is not bound
             if (op.dst.buf >= BSY_EXT_BASE && (op.dst.buf - BSY_EXT_BASE >= R.n_ext || !R.ext[op.dst.buf - BSY_EXT_BASE]))
                 return BSY_OK;
@@ -1118,7 +1118,7 @@ extern "C" int bsy_detect_decode(const float* const* box, const int* ldb, const 
                                  const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
                                  const float* lvl_stride, int nl, int B, int nc, int nm, void* y, int y_dtype,
                                  bsy_stream stream) {
-    if (!box || !ldb || !cls || !ldc || !lvl_h || !lvl_w || !lvl_stride || !y || nl < 1 || nl > 3)
+    if (!box || !ldb || !cls || !ldc || !lvl_h || !lvl_w || !lvl_stride || !y || nl < 1 || nl > BSY_MAX_LEVELS)
         BSY_FAIL(BSY_ERR_ARG, "detect_decode: bad argument");
     if (nm && (!msk || !ldm)) BSY_FAIL(BSY_ERR_ARG, "detect_decode: mask inputs missing");
     DecodeArgs a;

@@ -113,6 +113,8 @@ class YoloEngine:
         self.meta = dict(self._packed.meta)
         self.nc = self.meta["nc"]
         self.stride = torch.tensor(self.meta["strides"])
+        self.nl = len(self.meta["levels"])  # detection levels: 3, or 4 on the P2 / P6 graphs
+        self.max_stride = int(max(self.meta["strides"]))  # inputs are multiples of it: 32, 64 on a P6 graph
         self.names = {i: f"{i}" for i in range(self.nc)}
 
     def load_weights(self, state_dict: Mapping[str, torch.Tensor], bn_eps: float = BN_EPS) -> None:
@@ -141,8 +143,9 @@ class YoloEngine:
         if hit is not None:
             self._plans.move_to_end(key)
             return hit
-        if H % 32 or W % 32:
-            raise ValueError(f"input {H}x{W} must be a multiple of the max stride 32 (utils/checks.py:120-172)")
+        gs = self.max_stride
+        if H % gs or W % gs:
+            raise ValueError(f"input {H}x{W} must be a multiple of the max stride {gs} (utils/checks.py:120-172)")
         plan = Plan(self.cfg, B, H, W, L.dtype_code(in_dtype), L.dtype_code(out_dtype), **self._fuse_kw())
         adopt_offsets(plan, self._packed)
         ops = plan.c_ops()
@@ -245,8 +248,9 @@ class YoloEngine:
         return hit
 
     def _ext(self, im, y, raws, proto=None):
-        ptrs = [im.data_ptr(), y.data_ptr()] + [r.data_ptr() if r is not None else None for r in raws]
-        ptrs.append(proto.data_ptr() if proto is not None else None)
+        # slot order of Plan: image, y, raw maps of levels 0-2, proto, then the fourth level's raw map (Plan.EXT_RAW3)
+        raws = [r.data_ptr() if r is not None else None for r in raws]
+        ptrs = [im.data_ptr(), y.data_ptr()] + raws[:3] + [proto.data_ptr() if proto is not None else None] + raws[3:]
         return (C.c_void_p * len(ptrs))(*ptrs), len(ptrs)
 
     def forward(self, im: torch.Tensor, want_raw: bool = True):
@@ -258,6 +262,8 @@ class YoloEngine:
         B, Cc, H, W = im.shape
         if Cc != 3:
             raise ValueError("expected 3 input channels")
+        if H % self.max_stride or W % self.max_stride:  # (before any plan of this size is built: the graph walk asserts on such maps)
+            raise ValueError(f"input {H}x{W} must be a multiple of the max stride {self.max_stride} (utils/checks.py:120-172)")
         # the kernels keep element offsets in 32 bits: split batches whose largest activation would exceed 2^31
         # elements (e.g. 256 x 1280x1280) into equal chunks -- images are independent
         big = self._max_view_elems(H, W)
@@ -266,13 +272,14 @@ class YoloEngine:
             step = -(-B // n_chunks)
             outs = [self.forward(im[i:i + step], want_raw) for i in range(0, B, step)]
             y = torch.cat([o[0] for o in outs])
+            nl = self.nl
             if self.meta["nm"]:
-                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(3)] if want_raw else [None] * 3
+                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
                 return y, (raws, y[:, 4 + self.meta["nc"]:], torch.cat([o[1][2] for o in outs]))
             if self.meta["ne"]:
-                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(3)] if want_raw else [None] * 3
+                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
                 return y, (raws, y[:, 4 + self.meta["nc"]:])
-            return y, ([torch.cat([o[1][l] for o in outs]) for l in range(3)] if want_raw else [None] * 3)
+            return y, ([torch.cat([o[1][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl)
         with self._lock:  # plan table, arena and launch order are shared state
             return self._forward_one(im, want_raw, B, H, W)
 
@@ -282,7 +289,7 @@ class YoloEngine:
 
         def outputs():
             y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
-            raws: List[Optional[torch.Tensor]] = [None, None, None]
+            raws: List[Optional[torch.Tensor]] = [None] * len(m["levels"])
             if want_raw:
                 raws = [torch.empty((B, m["no"], lh, lw), dtype=im.dtype, device=self.device) for lh, lw in m["levels"]]
             proto = None
@@ -362,7 +369,7 @@ class YoloEngine:
         hit = self._tta_geom.get((H, W))
         if hit is None:
             levels = lambda h, w: Plan(self.cfg, 1, h, w, **self._fuse_kw()).meta["levels"]  # noqa: E731
-            hit = self._tta_geom[(H, W)] = T.geometry(H, W, int(max(self.meta["strides"])), levels)
+            hit = self._tta_geom[(H, W)] = T.geometry(H, W, self.max_stride, levels)
         return hit
 
     def forward_augment(self, im: torch.Tensor):
@@ -395,7 +402,7 @@ class YoloEngine:
                             self._tta_bufs.popitem(last=False)
                         buf = self._tta_bufs[key] = torch.empty((B, 3) + p.padded, dtype=im.dtype, device=self.device)
                     self._tta_bufs.move_to_end(key)
-                    xi = O.scale_img(im, p.ratio, p.flip, int(max(self.meta["strides"])), out=buf)
+                    xi = O.scale_img(im, p.ratio, p.flip, self.max_stride, out=buf)
                 xs.append(xi)
             ys = []
             for xi in xs:
@@ -417,7 +424,7 @@ class YoloEngine:
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
         m = plan.meta
         y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
-        ext, n = self._ext(im, y, [None, None, None])
+        ext, n = self._ext(im, y, [None] * len(m["levels"]))
         ms = (C.c_float * len(plan.ops))()
         L.check(L.lib.bsy_plan_profile(h, ext, n, L.stream_ptr(self.device), ms))
         return [(o["name"], o["kind"], float(t)) for o, t in zip(plan.ops, ms)], plan

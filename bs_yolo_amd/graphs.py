@@ -1,8 +1,9 @@
 """Stock model descriptions in the reference's yaml-dict schema (what ``model.yaml`` holds on a live reference model).
 
 The reference ships these graphs as cfg/models/11/yolo11-seg.yaml:15-47 (stock YOLO11 backbone+neck),
-cfg/models/v8/yolov8-seg.yaml:15-46, cfg/models/v5/yolov5.yaml:14-50 and cfg/models/11/yolo11.yaml:15-52 (the modified BS-YOLO
-graph, family "bsyolo11").  They are
+cfg/models/v8/yolov8-seg.yaml:15-46, cfg/models/v5/yolov5.yaml:14-50, cfg/models/11/yolo11.yaml:15-52 (the modified BS-YOLO
+graph, family "bsyolo11") and the four-level variants cfg/models/v8/yolov8-p2.yaml, v8/yolov8-p6.yaml (+ yolov8-seg-p6.yaml) and
+v5/yolov5-p6.yaml (families "yolov8-p2", "yolov8-p6", "yolov5-p6").  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -90,7 +91,65 @@ _YOLOV5 = {
     "detect_from": [17, 20, 23],
 }
 
-_FAMILIES = {"yolo11": _YOLO11, "yolov8": _YOLOV8, "bsyolo11": _BSYOLO11, "yolov5": _YOLOV5}
+# Four-level heads.  cfg/models/v8/yolov8-p2.yaml:14-45: the YOLOv8 backbone, a neck that goes one step further up to stride 4,
+# Detect on (P2, P3, P4, P5)
+_YOLOV8_P2 = {
+    "scales": _YOLOV8["scales"],
+    "backbone": _YOLOV8["backbone"],
+    "head": [
+        _UP, _cat(6), [-1, 3, "C2f", [512]],
+        _UP, _cat(4), [-1, 3, "C2f", [256]],
+        _UP, _cat(2), [-1, 3, "C2f", [128]],
+        [-1, 1, "Conv", [128, 3, 2]], _cat(15), [-1, 3, "C2f", [256]],
+        [-1, 1, "Conv", [256, 3, 2]], _cat(12), [-1, 3, "C2f", [512]],
+        [-1, 1, "Conv", [512, 3, 2]], _cat(9), [-1, 3, "C2f", [1024]],
+    ],
+    "detect_from": [18, 21, 24, 27],
+}
+
+# cfg/models/v8/yolov8-p6.yaml:14-47 (and yolov8-seg-p6.yaml, the same graph under a Segment head): a 768-channel stride-32 stage, a
+# stride-64 stage before SPPF, C2 blocks (not C2f) in the neck, the head on (P3, P4, P5, P6)
+_YOLOV8_P6 = {
+    "scales": _YOLOV8["scales"],
+    "backbone": [
+        [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "Conv", [128, 3, 2]], [-1, 3, "C2f", [128, True]],
+        [-1, 1, "Conv", [256, 3, 2]], [-1, 6, "C2f", [256, True]], [-1, 1, "Conv", [512, 3, 2]],
+        [-1, 6, "C2f", [512, True]], [-1, 1, "Conv", [768, 3, 2]], [-1, 3, "C2f", [768, True]],
+        [-1, 1, "Conv", [1024, 3, 2]], [-1, 3, "C2f", [1024, True]], [-1, 1, "SPPF", [1024, 5]],
+    ],
+    "head": [
+        _UP, _cat(8), [-1, 3, "C2", [768, False]],
+        _UP, _cat(6), [-1, 3, "C2", [512, False]],
+        _UP, _cat(4), [-1, 3, "C2", [256, False]],
+        [-1, 1, "Conv", [256, 3, 2]], _cat(17), [-1, 3, "C2", [512, False]],
+        [-1, 1, "Conv", [512, 3, 2]], _cat(14), [-1, 3, "C2", [768, False]],
+        [-1, 1, "Conv", [768, 3, 2]], _cat(11), [-1, 3, "C2", [1024, False]],
+    ],
+    "detect_from": [20, 23, 26, 29],
+}
+
+# cfg/models/v5/yolov5-p6.yaml:14-53: YOLOv5u with the same two extra stages, a 1x1 Conv before every upsample
+_YOLOV5_P6 = {
+    "scales": _YOLOV5["scales"],
+    "backbone": [
+        [-1, 1, "Conv", [64, 6, 2, 2]], [-1, 1, "Conv", [128, 3, 2]], [-1, 3, "C3", [128]],
+        [-1, 1, "Conv", [256, 3, 2]], [-1, 6, "C3", [256]], [-1, 1, "Conv", [512, 3, 2]],
+        [-1, 9, "C3", [512]], [-1, 1, "Conv", [768, 3, 2]], [-1, 3, "C3", [768]],
+        [-1, 1, "Conv", [1024, 3, 2]], [-1, 3, "C3", [1024]], [-1, 1, "SPPF", [1024, 5]],
+    ],
+    "head": [
+        [-1, 1, "Conv", [768, 1, 1]], _UP, _cat(8), [-1, 3, "C3", [768, False]],
+        [-1, 1, "Conv", [512, 1, 1]], _UP, _cat(6), [-1, 3, "C3", [512, False]],
+        [-1, 1, "Conv", [256, 1, 1]], _UP, _cat(4), [-1, 3, "C3", [256, False]],
+        [-1, 1, "Conv", [256, 3, 2]], _cat(20), [-1, 3, "C3", [512, False]],
+        [-1, 1, "Conv", [512, 3, 2]], _cat(16), [-1, 3, "C3", [768, False]],
+        [-1, 1, "Conv", [768, 3, 2]], _cat(12), [-1, 3, "C3", [1024, False]],
+    ],
+    "detect_from": [23, 26, 29, 32],
+}
+
+_FAMILIES = {"yolo11": _YOLO11, "yolov8": _YOLOV8, "bsyolo11": _BSYOLO11, "yolov5": _YOLOV5,
+             "yolov8-p2": _YOLOV8_P2, "yolov8-p6": _YOLOV8_P6, "yolov5-p6": _YOLOV5_P6}
 
 
 def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str = "detect") -> dict:

@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ["BSY_LIB"]) if os.environ.get("BSY_LIB") else PKG / "
 
 BSY_F16, BSY_F32, BSY_U8 = 0, 1, 2
 BSY_EXT_BASE = 0x100000
+BSY_MAX_LEVELS = 4  # include/bsyolo.h: length of bsy_op's per-level arrays
 (OP_CONV_FIRST, OP_CONV, OP_DWCONV, OP_SPPF_POOL, OP_ATTN, OP_DECODE, OP_RAW_NCHW, OP_NHWC2NCHW, OP_STEM, OP_BNECK, OP_DWCONV_G, OP_COPY, OP_GAP, OP_MSCA_MIX, OP_MUL, OP_ELA, OP_DWPW, OP_MSCA_SPATIAL, OP_C3K2, OP_S2D, OP_PMSFA_TAIL, OP_CHAIN) = range(22)
 # OP_CHAIN (21): retired kind, kept in the unpacking only because bench.py still names it; plans never contain it
 
@@ -51,9 +52,10 @@ class Op(C.Structure):
         ("heads", C.c_int32), ("key_dim", C.c_int32), ("head_dim", C.c_int32),
         ("scale", C.c_float),
         ("nl", C.c_int32), ("nc", C.c_int32), ("nm", C.c_int32), ("A", C.c_int32),
-        ("box", View * 3), ("cls", View * 3), ("msk", View * 3),
-        ("lvl_h", C.c_int32 * 3), ("lvl_w", C.c_int32 * 3),
-        ("lvl_stride", C.c_float * 3),
+        ("box", View * BSY_MAX_LEVELS), ("cls", View * BSY_MAX_LEVELS),
+        ("lvl_h", C.c_int32 * BSY_MAX_LEVELS), ("lvl_w", C.c_int32 * BSY_MAX_LEVELS),
+        ("lvl_stride", C.c_float * BSY_MAX_LEVELS),
+        ("reserved2", C.c_int32),
         ("in_dtype", C.c_int32), ("out_dtype", C.c_int32),
         ("level", C.c_int32),
         ("lane", C.c_int32), ("tuned_cfg", C.c_int32), ("join", C.c_int32),
@@ -61,6 +63,7 @@ class Op(C.Structure):
         ("w2_off", C.c_int64), ("b2_off", C.c_int64),
         ("aux_off", C.c_int64 * 18),
         ("prec", C.c_int32), ("ne", C.c_int32), ("ksplit", C.c_int32), ("reserved1", C.c_int32),
+        ("msk", View * BSY_MAX_LEVELS),  # behind the fields that keep their offsets (include/bsyolo.h)
     ]
 
 

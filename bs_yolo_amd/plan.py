@@ -135,6 +135,13 @@ class Plan:
 
     EXT_IMG, EXT_Y, EXT_RAW0 = 0, 1, 2  # external slots: image, prediction, raw level maps (2,3,4), proto (5)
     EXT_PROTO = 5
+    EXT_RAW3 = 6  # the fourth level's raw map (P2 / P6 heads): behind the proto slot, so that slots 0-5 stay what they were
+
+    @classmethod
+    def ext_raw(cls, level: int) -> int:
+        """External slot of level `level`'s raw map."""
+        assert 0 <= level < L.BSY_MAX_LEVELS
+        return cls.EXT_RAW0 + level if level < 3 else cls.EXT_RAW3 + level - 3
 
     def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16,
                  fuse_stem: Optional[bool] = None, fuse_bneck: Optional[bool] = None, fuse_head: Optional[bool] = None,
@@ -452,6 +459,22 @@ class Plan:
                 self.bottleneck(f"{name}.m.{i}", src, dst, shortcut, (3, 3), 0.5)
         return self.conv(name + ".cv2", cat, c2, 1, 1)
 
+    def c2(self, name: str, x, c2: int, n: int, shortcut: bool) -> T:
+        """block.py:3277-3292 (C2): cv2(cat(m(a), b)) with [a | b] = cv1(x), m = n x Bottleneck(c, c, k=(3,3), e=1).  cv2 reads
+        the two halves as a virtual concat (a two-source conv): m's output in a buffer of its own, b where cv1 left it."""
+        xs = [x] if isinstance(x, T) else list(x)
+        c = int(c2 * 0.5)
+        if c % 8 and not self.f32_mode:
+            raise NotImplementedError(f"{name}: C2 with a hidden width of {c} channels is not on the fp16 path (multiples of 8)")
+        ab = self.alloc(2 * c, xs[0].H, xs[0].W)
+        self.conv(name + ".cv1", xs, 2 * c, 1, 1, dst=ab)
+        cur = ab.slice(0, c)
+        for i in range(n):
+            out = self.alloc(c, xs[0].H, xs[0].W)
+            self.bottleneck(f"{name}.m.{i}", cur, out, shortcut, (3, 3), 1.0)
+            cur = out
+        return self.conv(name + ".cv2", [cur, ab.slice(c, c)], c2, 1, 1)
+
     def pmsfa(self, name: str, x: T, dst: T):
         """block.py:3035-3054.  conv1 -> P = [p1 | p2]; depthwise 5x5 on p1 -> Q = [q1 | q2]; the depthwise 7x7 runs on ALL
         of Q with weights extended by an identity kernel for the q2 half (weights.py kind "dwg_ext": exact pass-through,
@@ -638,7 +661,7 @@ class Plan:
         """Last 1x1 conv of a Detect branch with the decoder fused into its epilogue (out_f32 = mode 2 / 3)."""
         key = self._wrec(name, name=name, kind="plain", cout=cout, cin=src.C, k=1, perm=None, real_cin=real_cin)
         y = T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc, 0, 0)
-        raw = T(L.BSY_EXT_BASE + self.EXT_RAW0 + level, 0, 0, 64 + nc, 0, 0)
+        raw = T(L.BSY_EXT_BASE + self.ext_raw(level), 0, 0, 64 + nc, 0, 0)
         self.ops.append(dict(kind=L.OP_CONV, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, src1=None, dst=y, res=None,
                              ksize=1, stride=1, pad=0, act=0, out_f32=mode, wkey=key, dst_scale=1, name=name, cout=cout,
                              lane=self._lane, nl=cout, nc=nc, nm=0, A=A, box=[raw], cls=[], msk=[], level=level,
@@ -654,7 +677,7 @@ class Plan:
         k1 = self._wrec(n1, name=n1, kind="conv", cout=64, cin=src.C, k=3, perm=None)
         k2 = self._wrec(n2, name=n2, kind="plain", cout=64, cin=64, k=1, perm=None)
         y = T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc, 0, 0)
-        raw = T(L.BSY_EXT_BASE + self.EXT_RAW0 + level, 0, 0, 64 + nc, 0, 0)
+        raw = T(L.BSY_EXT_BASE + self.ext_raw(level), 0, 0, 64 + nc, 0, 0)
         fl = 2 * self.B * src.H * src.W * 64 * (9 * src.C + 64)
         self.ops.append(dict(kind=L.OP_CONV, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, src1=None, dst=y, res=None,
                              ksize=3, stride=1, pad=1, act=1, out_f32=3, wkey=k1, wkey2=k2, mid_c=64, dst_scale=1, name=n1 + "+2",
@@ -664,6 +687,10 @@ class Plan:
 
     def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0):
         """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels)."""
+        if not 1 <= len(xs) <= L.BSY_MAX_LEVELS:
+            raise NotImplementedError(f"{name}: a head on {len(xs)} levels (1 to {L.BSY_MAX_LEVELS} are accelerated)")
+        if ne and len(xs) > 3:
+            raise NotImplementedError(f"{name}: an OBB head on {len(xs)} levels (the reference ships none) is not accelerated")
         ch = [t.C for t in xs]
         c2, c3 = max(16, ch[0] // 4, 64), max(ch[0], min(nc, 100))
         boxes, clss, msks = [], [], []
@@ -673,7 +700,8 @@ class Plan:
         # Detect without mask coefficients: the last conv of every branch decodes in its epilogue (conv_kernels.h
         # conv_epilogue_head) -- no f32 logit maps, no decode launch, no raw-map transposes.  An OBB head's box decode needs the
         # angle of its cv4 branch (tal.py:404-423 dist2rbox), so OBB always takes the decode launch
-        fused = self.fuse_head and nm == 0 and ne == 0 and len(xs) <= 3
+        # Four levels (P2 / P6 graphs) fuse the same way: every fused op carries its own level, first anchor and stride
+        fused = self.fuse_head and nm == 0 and ne == 0
         # every (level, branch) chain is independent until the decoder: give each its own lane so the engine runs them
         # concurrently (the 40x40 / 20x20 chains are far too small to fill 256 CUs on their own)
         for i, x in enumerate(xs):
@@ -731,7 +759,7 @@ class Plan:
             self.ops.append(dict(kind=L.OP_RAW_NCHW, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=0, A=A,
                                  box=boxes, cls=clss, msk=[], lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs],
                                  lvl_stride=strides, level=i,
-                                 dst=T(L.BSY_EXT_BASE + self.EXT_RAW0 + i, 0, 0, 64 + nc, 0, 0),
+                                 dst=T(L.BSY_EXT_BASE + self.ext_raw(i), 0, 0, 64 + nc, 0, 0),
                                  out_dtype=self.out_dtype, name=f"{name}.raw{i}"))
         self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
 
@@ -759,7 +787,7 @@ class Plan:
             n = max(round(n * depth), 1) if n > 1 else n
             if f != -1:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
-            if m in ("Conv", "C3k2", "C2f", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv"):
+            if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv"):
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m == "Conv":
                     k = args[1] if len(args) > 1 else 1
@@ -804,6 +832,9 @@ class Plan:
                 elif m == "C2f":
                     shortcut = bool(args[1]) if len(args) > 1 else False
                     y = self.c2f(name, x, c2, n, shortcut, 0.5, "c2f")
+                elif m == "C2":  # the necks of yolov8-p6.yaml / yolov8-seg-p6.yaml
+                    shortcut = bool(args[1]) if len(args) > 1 else True
+                    y = self.c2(name, x, c2, n, shortcut)
                 elif m == "SPPF":
                     assert isinstance(x, T) and (len(args) < 2 or args[1] == 5)
                     y = self.sppf(name, x, c2)
@@ -1012,7 +1043,7 @@ class Plan:
                 d.get("scale", 0.0)
             o.nl, o.nc, o.nm, o.A = d.get("nl", 0), d.get("nc", 0), d.get("nm", 0), d.get("A", 0)
             o.ne = d.get("ne", 0)
-            for j in range(3):
+            for j in range(L.BSY_MAX_LEVELS):
                 o.box[j] = v(d["box"][j] if j < len(d.get("box", [])) else None)
                 o.cls[j] = v(d["cls"][j] if j < len(d.get("cls", [])) else None)
                 o.msk[j] = v(d["msk"][j] if j < len(d.get("msk", [])) else None)

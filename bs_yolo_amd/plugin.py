@@ -97,17 +97,31 @@ def _weights_version(model) -> tuple:
     return (n, ver, ptr)
 
 
-def graph_support(cfg: dict) -> dict:
-    """Which engine precisions can run this yaml graph: {"fp16": bool, "fp32": bool} (the fp32 / fp32x modes also take PMSFA widths
-    that are not multiples of 8 channels, e.g. BS-YOLO at a width multiple of 0.1875).  Decided once, on the host, from the plan alone."""
-    out = {}
+def _graph_facts(cfg: dict):
+    """(graph_support(cfg), max_stride(cfg)) from one plan per precision."""
+    out, gs = {}, 0
     for prec in ("fp16", "fp32"):
         try:
-            Plan(cfg, 1, 64, 64, precision=prec)
+            gs = int(max(Plan(cfg, 1, 64, 64, precision=prec).meta["strides"]))  # the same in every precision that builds
             out[prec] = True
         except (NotImplementedError, AssertionError):
             out[prec] = False
-    return out
+    return out, gs
+
+
+def graph_support(cfg: dict) -> dict:
+    """Which engine precisions can run this yaml graph: {"fp16": bool, "fp32": bool} (the fp32 / fp32x modes also take PMSFA widths
+    that are not multiples of 8 channels, e.g. BS-YOLO at a width multiple of 0.1875).  Decided once, on the host, from the plan alone."""
+    return _graph_facts(cfg)[0]
+
+
+def max_stride(cfg: dict) -> int:
+    """int(max(model.stride)) of a yaml graph (32; 64 with a P6 head): what the engine's inputs must be multiples of.  Raises
+    NotImplementedError for a graph no precision can run."""
+    gs = _graph_facts(cfg)[1]
+    if not gs:
+        raise NotImplementedError("the graph is not on the accelerated path in any precision")
+    return gs
 
 
 FP32_MODES = {"engine_fp32x": "fp32x", "engine_fp32": "fp32", "engine": "fp16", "reference": None}
@@ -140,7 +154,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     ``"reference"`` the original forward.  ``BSY_TTA`` overrides the default; ``state["tta_calls"]`` counts engine TTA calls."""
     import os
     cfg = cfg_of(model)
-    support = graph_support(cfg)
+    support, gs = _graph_facts(cfg)  # gs: a P6 graph takes multiples of 64; anything else goes to the reference forward, as non-multiples of 32 do
     orig_forward = model.forward
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
              "tta_calls": 0, "support": support, "failed": set()}
@@ -185,7 +199,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
             visualize = embed = profile = False
         if (self.training or visualize or embed or profile or args or not isinstance(x, torch.Tensor)
                 or not _on_device(x) or x.dim() != 4 or x.dtype not in (torch.float16, torch.float32)
-                or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32 or x.shape[0] == 0):
+                or x.shape[1] != 3 or x.shape[2] % gs or x.shape[3] % gs or x.shape[0] == 0):
             state["fallbacks"] += 1
             return orig_forward(x, *args, **kwargs)
         precision = "fp16" if x.dtype == torch.float16 else prec32
@@ -368,7 +382,7 @@ def _block_spec(m):
                 and L.lib.bsy_c3k2_fused_supported(m.cv1.conv.in_channels, m.c, m.cv2.conv.out_channels) == 1):
             return "c3k2"
     if name in ("Detect", "Segment"):
-        if (getattr(m, "reg_max", 0) == 16 and 1 <= getattr(m, "nl", 0) <= 3 and not getattr(m, "export", False)
+        if (getattr(m, "reg_max", 0) == 16 and 1 <= getattr(m, "nl", 0) <= _L.BSY_MAX_LEVELS and not getattr(m, "export", False)
                 and getattr(m, "format", None) is None and hasattr(m, "_inference")):
             return "detect"
     return None

@@ -137,7 +137,8 @@ def get_sliced_prediction(image, detection_model, slice_height: int = 640, slice
     tiles (B, 3, h, w) -> (pred (B, 4+nc, A), ...)).  Returns (det (K, 6) fp32 [x1 y1 x2 y2 score cls] in image
     pixels, tile boxes).  `conf` is sahi's model_confidence_threshold; iou / max_det are the per-tile NMS settings of
     the predictor (cfg/default.yaml).  `imgsz`: letterbox every slice to this model input size (the reference's flow: sahi hands
-    each slice to the ultralytics predictor); None = feed the slices natively when their size is a multiple of 32, else imgsz 640.
+    each slice to the ultralytics predictor); None = feed the slices natively when their size is a multiple of the model's largest stride
+    (`detection_model.max_stride`: 64 for a P6 graph; 32 where the model does not say), else imgsz 640.
     Slices larger than the image shrink to it (get_slice_bboxes)."""
     dev = detection_model.device if hasattr(detection_model, "device") else torch.device("cuda:0")
     img = _as_device_image(image, dev)
@@ -154,7 +155,8 @@ def get_sliced_prediction(image, detection_model, slice_height: int = 640, slice
     # Native tiles (the slice IS the model input: one kernel cuts all of them) when no imgsz is asked for and the slice size suits the
     # model's stride; otherwise every slice goes through the predictor's letterbox to `imgsz` and its boxes back through scale_boxes
     # -- what sahi's ultralytics wrapper does with EVERY slice (detect-sahi.py's 800 x 800 slices reach the model at imgsz 640)
-    native = imgsz is None and th % 32 == 0 and tw % 32 == 0
+    gs = int(getattr(detection_model, "max_stride", 32))
+    native = imgsz is None and th % gs == 0 and tw % gs == 0
     for i in range(s, e, step):
         chunk = bboxes[i:min(i + step, e)]
         if native:
@@ -165,7 +167,7 @@ def get_sliced_prediction(image, detection_model, slice_height: int = 640, slice
             crops = [img[b[1]:b[3], b[0]:b[2]] for b in chunk]
             if not bgr:  # preprocess flips BGR -> RGB (predictor.py:127); an RGB source is flipped back first
                 crops = [c.flip(-1) for c in crops]
-            tiles = preprocess(crops, imgsz=(size, size), half=half, device=dev)
+            tiles = preprocess(crops, imgsz=(size, size), half=half, stride=gs, device=dev)
         pred = detection_model(tiles, want_raw=False)[0] if hasattr(detection_model, "plan_for") else detection_model(tiles)[0]
         d, c = nms_batched(pred, conf, iou, max_det=max_det, in_place=True)
         if not native:
@@ -181,8 +183,8 @@ def get_sliced_prediction(image, detection_model, slice_height: int = 640, slice
     shifts = [[b[0], b[1]] for b in bboxes]
     if perform_standard_pred and T > 1:  # sahi adds a full-image prediction to the slices'
         from .letterbox import preprocess
-        size = imgsz or max(slice_height, slice_width)
-        full = preprocess([img if bgr else img.flip(-1)], imgsz=(size, size), half=half, device=dev)
+        size = imgsz or -(-max(slice_height, slice_width) // gs) * gs  # (a multiple of the model's stride: 800 -> 832 on a P6 graph)
+        full = preprocess([img if bgr else img.flip(-1)], imgsz=(size, size), half=half, stride=gs, device=dev)
         pred = detection_model(full, want_raw=False)[0] if hasattr(detection_model, "plan_for") else detection_model(full)[0]
         d, c = nms_batched(pred, conf, iou, max_det=max_det, in_place=True)
         scale_boxes_batched(d, c, full.shape[2:], [(H, W)])

@@ -49,6 +49,9 @@ typedef struct bsy_plan bsy_plan;
  * buf >= BSY_EXT_BASE : external pointer slot (buf - BSY_EXT_BASE) supplied to bsy_plan_run
  * buf <  0            : absent                                                                          */
 #define BSY_EXT_BASE 0x100000
+/* Detection levels a head may read (P3-P5 stock graphs: 3; the P2 and P6 variants, cfg/models/v8/yolov8-p2.yaml / yolov8-p6.yaml /
+ * v5/yolov5-p6.yaml: 4): the length of every per-level array below and of bsy_detect_decode's inputs. */
+#define BSY_MAX_LEVELS 4
 typedef struct bsy_view {
     int32_t buf, ld, coff, C;
 } bsy_view;
@@ -119,11 +122,15 @@ typedef struct bsy_op {
     int64_t w_off, b_off;   /* byte offsets into the engine's weight blob (packed f16 weights / f32 bias) */
     int32_t heads, key_dim, head_dim; /* ATTN */
     float scale;            /* ATTN softmax scale */
-    /* DECODE / RAW_NCHW: per-level inputs */
+    /* DECODE / RAW_NCHW: per-level inputs (nl entries used).  The arrays hold BSY_MAX_LEVELS entries; box, cls and the lvl_* arrays
+     * grew where they were, msk[] moved to the end of the record and one reserved word fills what is left of its place, so every
+     * field that is not a per-level array has the offset it had with three-entry arrays.  sizeof(bsy_op) grew from 560 to 624:
+     * callers recompile against this header (bsy_sizeof_op) */
     int32_t nl, nc, nm, A;  /* levels, classes, mask coeffs, total anchors */
-    bsy_view box[3], cls[3], msk[3];
-    int32_t lvl_h[3], lvl_w[3];
-    float lvl_stride[3];
+    bsy_view box[BSY_MAX_LEVELS], cls[BSY_MAX_LEVELS];
+    int32_t lvl_h[BSY_MAX_LEVELS], lvl_w[BSY_MAX_LEVELS];
+    float lvl_stride[BSY_MAX_LEVELS];
+    int32_t reserved2;
     int32_t in_dtype, out_dtype; /* CONV_FIRST input dtype; DECODE/RAW output dtype */
     int32_t level;          /* RAW_NCHW: which level; output = external slot in dst.buf */
     int32_t lane;           /* 0 = caller's stream; k > 0 = plan-owned side stream k (independent op chains, e.g. the
@@ -148,6 +155,7 @@ typedef struct bsy_op {
                              * activation and shortcut: deterministic, independent of the batch and of the tile configuration.  The host
                              * chooses the factors from the layer's SHAPE only (bs_yolo_amd/plan.py split_factors), never from the batch. */
     int32_t reserved1;
+    bsy_view msk[BSY_MAX_LEVELS]; /* DECODE: per-level mask-coefficient (Segment) or angle-logit (OBB) maps; see box[] above */
 } bsy_op;
 
 int bsy_sizeof_op(void); /* sizeof(bsy_op) of the library: a host binding that mirrors the record (bs_yolo_amd/lib.py) checks it at load */
@@ -171,7 +179,11 @@ int bsy_plan_create_arena(bsy_engine* e, const bsy_op* ops, int n_ops, const int
                           int64_t arena_bytes, bsy_plan** out);
 size_t bsy_engine_arena_bytes(const bsy_engine* e);
 void bsy_plan_destroy(bsy_plan* p);
-/* ext: HOST array of n_ext device pointers bound to the external slots (input image, y, raw maps ...). */
+/* ext: HOST array of n_ext device pointers bound to the external slots (input image, y, raw maps ...).
+ * Slot layout of the plans bs_yolo_amd/plan.py writes: 0 image, 1 prediction y, 2 / 3 / 4 raw maps of levels 0 / 1 / 2, 5 Segment
+ * prototypes, 6 raw map of level 3 (four-level heads only; behind the proto slot so that slots 0-5 are what they were with three
+ * levels).  Raw-map and proto slots are optional outputs: NULL, or n_ext too short to reach them, skips the store.  A three-level
+ * plan reads at most 6 slots, a four-level one 7. */
 int bsy_plan_run(bsy_plan* p, void* const* ext, int n_ext, bsy_stream stream);
 /* The same forward as ONE graph launch: the first call with a given set of external pointers captures bsy_plan_run on `stream`
  * (thread-local capture; side lanes become graph edges) and instantiates it, later calls with the same pointers replay it -- one
@@ -315,7 +327,13 @@ int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim,
 
 /* Detect._inference (head.py:100-131) + DFL (block.py:58-77) + make_anchors/dist2bbox (utils/tal.py:371-395).
  * box[l]: f32 (B*h*w, ldb) 64 DFL logits; cls[l]: f32 (B*h*w, ldc) nc logits; msk[l]: f32 nm coeffs or NULL.
- * y: (B, 4+nc+nm, A) of y_dtype. */
+ * y: (B, 4+nc+nm, A) of y_dtype.  HOST arrays of nl entries each, 1 <= nl <= BSY_MAX_LEVELS; the levels' anchors follow each other
+ * in y in the order given (A = sum of h*w).
+ * The DFL expectation is a sum of 16 f32 terms per box side, and its order depends on nl: with nl <= 3 the terms are added in bin
+ * order, as this entry point always has; with nl == 4 they are added as two partial sums (bins 0-3, 8-11 and bins 4-7, 12-15) that
+ * are then added, which is the order of the engine's fused head epilogue, so that a four-level plan returns the same bits with the
+ * decode launch (BSY_OP_DECODE, this kernel) as with the fused head.  The same logits can therefore give boxes that differ in the
+ * last f32 bit between a call with three levels and one with four. */
 int bsy_detect_decode(const float* const* box, const int* ldb, const float* const* cls, const int* ldc,
                       const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
                       const float* lvl_stride, int nl, int B, int nc, int nm, void* y, int y_dtype, bsy_stream stream);
