@@ -34,6 +34,7 @@ SOURCES = {
     "bsyolo_ops.hip": [],
     "pmsfa_fused.hip": [],
     "elementwise.hip": [],
+    "pool_down.hip": ["-ffp-contract=off"],  # the average must round like ATen's: ordered fp32 sum, one product, one rounding
     "attention.hip": [],
     "detect.hip": [],
     "nms.hip": ["-ffp-contract=off"],

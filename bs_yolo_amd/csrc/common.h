@@ -291,6 +291,9 @@ struct DwArgs {
 };
 int launch_dwconv(const DwArgs& a, hipStream_t s);
 int launch_sppf_pool(half_t* buf, int ld, int B, int H, int W, int C, hipStream_t s);
+// pool_down.hip: src / dst = first element of the buffers, soff / doff = first channel of the views; dtype BSY_F16 / BSY_F32
+int launch_pool_down(const void* src, int lds_, int soff, void* dst, int ldd, int doff, int B, int H, int W, int C, int mode, int dtype,
+                     hipStream_t s);
 int launch_s2d(const void* img, int img_dtype, int B, int H, int W, half_t* dst, int ldd, hipStream_t s);
 
 struct AttnArgs {
@@ -314,6 +317,8 @@ struct DecodeArgs {
     void* y;
     int y_dtype;
     int ne;  // OBB angle channels (0 / 1): msk[l] then holds the angle logits and nm is 0
+    int halves;  // 1: the DFL sums run in the fused head epilogue's order at every level count (a Detect plan whose decode launch stands
+                 // in for the fused head, bsy_op.act); 0: that order for heads of four levels only, bin order up to three
 };
 int launch_decode(const DecodeArgs& a, hipStream_t s);
 // val_match.hip: the validator's matching rule on an IoU matrix (B, Lmax, max_det) made elsewhere (val_masks.hip); arguments as

@@ -32,7 +32,9 @@ struct DecodeK {
 // HALVES (heads of more than three levels: the P2 / P6 graphs): the DFL sums run in the order of the fused head's epilogue
 // (conv_kernels.h dfl_decode_store: bins 0-3, 8-11 and bins 4-7, 12-15 as two partial sums, then their sum), so that a plan with
 // the decode launch returns the bits of the same plan with the fused head.  Heads of up to three levels keep the sequential sums
-// their outputs have always had (HALVES = false is the kernel as it was).
+// their outputs have always had (HALVES = false is the kernel as it was) -- in the stand-alone entry point, in Segment / OBB plans
+// and in the fp32-storage modes, which have no fused form; a Detect plan of the fp16 path whose decode launch stands in for the
+// fused head (fuse_head off) asks for HALVES at any level count (DecodeArgs.halves), so that switch, too, returns the fused bits.
 #define DEC_TA 64
 template <typename T, bool ROT, bool HALVES>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restrict__ y) {
@@ -181,7 +183,7 @@ int launch_decode(const DecodeArgs& a, hipStream_t s) {
     dim3 grid(tiles, a.B);
     const size_t lds = (size_t)DEC_TA * (65 + (a.nc + nx + 1) + 4) * sizeof(float);
     if (lds > 64 * 1024) BSY_FAIL(BSY_ERR_ARG, "decode: nc + nm = %d too large", a.nc + nx);
-    const bool halves = a.nl > 3;  // (an OBB head has at most three levels: plan.py)
+    const bool halves = a.nl > 3 || a.halves;  // (an OBB head has at most three levels: plan.py)
     if (a.y_dtype == BSY_F16 && a.ne)
         hipLaunchKernelGGL((decode_kernel<half_t, true, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32 && a.ne)

@@ -314,6 +314,12 @@ int run_op_f32(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, 
             if (!R.ok) return BSY_ERR_ARG;
             return launch_sppf32(b, op.src0.ld, op.B, op.H, op.W, op.src0.C, s);
         }
+        case BSY_OP_POOL_DOWN: {
+            const char* src = R.base(op.src0);
+            char* dst = R.base(op.dst);
+            if (!R.ok || op.src0.C != op.dst.C) return BSY_ERR_ARG;
+            return launch_pool_down(src, op.src0.ld, op.src0.coff, dst, op.dst.ld, op.dst.coff, op.B, op.H, op.W, op.src0.C, op.level, BSY_F32, s);
+        }
         case BSY_OP_ATTN: {
             const float* q = R.f(op.src0);
             float* o = R.f(op.dst);
@@ -581,6 +587,12 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             if (!R.ok) return BSY_ERR_ARG;
             return launch_sppf_pool(b, op.src0.ld, op.B, op.H, op.W, op.src0.C, s);
         }
+        case BSY_OP_POOL_DOWN: {
+            const char* src = R.base(op.src0);
+            char* dst = R.base(op.dst);
+            if (!R.ok || op.src0.C != op.dst.C) return BSY_ERR_ARG;
+            return launch_pool_down(src, op.src0.ld, op.src0.coff, dst, op.dst.ld, op.dst.coff, op.B, op.H, op.W, op.src0.C, op.level, BSY_F16, s);
+        }
         case BSY_OP_ATTN: {
             AttnArgs a;
             a.qkv = R.h(op.src0); a.ld = op.src0.ld; a.B = op.B; a.N = op.H * op.W; a.heads = op.heads;
@@ -593,6 +605,7 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             DecodeArgs a;
             memset(&a, 0, sizeof(a));
             a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A; a.ne = op.ne;
+            a.halves = op.act && !op.nm && !op.ne;  // DECODE: act = the fused head epilogue's DFL order (include/bsyolo.h)
             const bool extra = op.nm || op.ne;  // mask coefficients (Segment) or angle logits (OBB) in the msk slots
             for (int l = 0; l < op.nl && l < BSY_MAX_LEVELS; ++l) {
                 a.box[l] = R.f(op.box[l]); a.cls[l] = R.f(op.cls[l]); a.msk[l] = extra ? R.f(op.msk[l]) : nullptr;
@@ -1103,6 +1116,11 @@ extern "C" int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C,
 extern "C" int bsy_sppf_pool(void* buf, int ld, int B, int H, int W, int C, bsy_stream stream) {
     if (!buf) BSY_FAIL(BSY_ERR_ARG, "sppf_pool: null pointer");
     return launch_sppf_pool((half_t*)buf, ld, B, H, W, C, (hipStream_t)stream);
+}
+
+extern "C" int bsy_pool_down(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
+                             bsy_stream stream) {
+    return launch_pool_down(x, ldx, xoff, y, ldy, yoff, B, H, W, C, mode, dtype, (hipStream_t)stream);
 }
 
 extern "C" int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale,

@@ -3,7 +3,8 @@
 The reference ships these graphs as cfg/models/11/yolo11-seg.yaml:15-47 (stock YOLO11 backbone+neck),
 cfg/models/v8/yolov8-seg.yaml:15-46, cfg/models/v5/yolov5.yaml:14-50, cfg/models/11/yolo11.yaml:15-52 (the modified BS-YOLO
 graph, family "bsyolo11") and the four-level variants cfg/models/v8/yolov8-p2.yaml, v8/yolov8-p6.yaml (+ yolov8-seg-p6.yaml) and
-v5/yolov5-p6.yaml (families "yolov8-p2", "yolov8-p6", "yolov5-p6").  They are
+v5/yolov5-p6.yaml (families "yolov8-p2", "yolov8-p6", "yolov5-p6"), and the YOLOv9 (GELAN) graphs cfg/models/v9/yolov9{t,s,m,c}.yaml and
+yolov9c-seg.yaml (family "yolov9": literal widths per size, no scales table).  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -148,12 +149,61 @@ _YOLOV5_P6 = {
     "detect_from": [23, 26, 29, 32],
 }
 
+
+
+# YOLOv9 (GELAN), cfg/models/v9/yolov9{t,s,m,c}.yaml:7-41: one layout for all four sizes -- stem, four ELAN stages with a
+# downsampling block in front of each, SPPELAN, a PAN neck of four more ELAN blocks -- and no `scales:` table: every size is its own
+# file with literal widths.  Per size: the two stem widths; the block of layer 2 (t / s: ELAN1, m / c: RepNCSPELAN4) with its
+# arguments; the downsampling block (t / s / m: AConv, c: ADown); [c2, c3, c4] of the P3 / P4 / P5 stages (the neck reuses them);
+# RepCSP's repeat count; SPPELAN's [c2, c3]; the widths of the two downsampling blocks of the neck.
+_V9_SIZES = {
+    "t": dict(stem=(16, 32), l2=("ELAN1", [32, 32, 16]), down="AConv", stages=([64, 64, 32], [96, 96, 48], [128, 128, 64]), n=3,
+              spp=[128, 64], neck_down=(48, 64)),
+    "s": dict(stem=(32, 64), l2=("ELAN1", [64, 64, 32]), down="AConv", stages=([128, 128, 64], [192, 192, 96], [256, 256, 128]), n=3,
+              spp=[256, 128], neck_down=(96, 128)),
+    "m": dict(stem=(32, 64), l2=("RepNCSPELAN4", [128, 128, 64, 1]), down="AConv",
+              stages=([240, 240, 120], [360, 360, 180], [480, 480, 240]), n=1, spp=[480, 240], neck_down=(180, 240)),
+    "c": dict(stem=(64, 128), l2=("RepNCSPELAN4", [256, 128, 64, 1]), down="ADown",
+              stages=([512, 256, 128], [512, 512, 256], [512, 512, 256]), n=1, spp=[512, 256], neck_down=(256, 512)),
+}
+
+
+def _yolov9(size: str) -> dict:
+    z = _V9_SIZES[size]
+    p3, p4, p5 = ([-1, 1, "RepNCSPELAN4", a + [z["n"]]] for a in z["stages"])
+    down = lambda c: [-1, 1, z["down"], [c]]
+    n3 = list(p3)
+    if size == "c":  # yolov9c.yaml:29: the neck's P3 block is [256, 256, 128, 1], the backbone's [512, 256, 128, 1]
+        n3 = [-1, 1, "RepNCSPELAN4", [256, 256, 128, 1]]
+    return {
+        "backbone": [
+            [-1, 1, "Conv", [z["stem"][0], 3, 2]], [-1, 1, "Conv", [z["stem"][1], 3, 2]], [-1, 1, z["l2"][0], list(z["l2"][1])],
+            down(z["stages"][0][0] if size != "c" else 256), p3, down(z["stages"][1][0]), p4, down(z["stages"][2][0]), p5,
+            [-1, 1, "SPPELAN", list(z["spp"])],
+        ],
+        "head": [
+            _UP, _cat(6), list(p4),
+            _UP, _cat(4), n3,
+            down(z["neck_down"][0]), _cat(12), list(p4),
+            down(z["neck_down"][1]), _cat(9), list(p5),
+        ],
+        "detect_from": [15, 18, 21],
+    }
+
+
 _FAMILIES = {"yolo11": _YOLO11, "yolov8": _YOLOV8, "bsyolo11": _BSYOLO11, "yolov5": _YOLOV5,
              "yolov8-p2": _YOLOV8_P2, "yolov8-p6": _YOLOV8_P6, "yolov5-p6": _YOLOV5_P6}
 
 
 def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str = "detect") -> dict:
-    """e.g. stock_cfg("yolo11", "s") == what the reference builds for 'yolo11s.yaml' upstream."""
+    """e.g. stock_cfg("yolo11", "s") == what the reference builds for 'yolo11s.yaml' upstream; stock_cfg("yolov9", "c", task="segment")
+    == 'yolov9c-seg.yaml' (family "yolov9": scale is one of t / s / m / c, segment exists for c only; the dict has no `scales`)."""
+    if family == "yolov9":
+        if scale not in _V9_SIZES or task not in ("detect", "segment") or (task == "segment" and scale != "c"):
+            raise ValueError(f"yolov9: scale {scale!r} / task {task!r} (detect: t, s, m, c; segment: c)")
+        fam = copy.deepcopy(_yolov9(scale))
+        head = fam["head"] + [[fam["detect_from"], 1, "Detect", ["nc"]] if task == "detect" else [fam["detect_from"], 1, "Segment", ["nc", 32, 256]]]
+        return {"nc": nc, "backbone": fam["backbone"], "head": head}
     fam = copy.deepcopy(_FAMILIES[family])
     head = list(fam["head"])
     if task == "detect":

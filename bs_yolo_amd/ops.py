@@ -220,6 +220,22 @@ def sppf_pool_nhwc(x1: torch.Tensor) -> torch.Tensor:
     return buf
 
 
+def pool_down_nhwc(x: torch.Tensor, mode: int, C: Optional[int] = None, coff: int = 0, out: Optional[torch.Tensor] = None,
+                   out_coff: int = 0) -> torch.Tensor:
+    """The pooling front end of AConv / ADown (block.py:3692-3723) on channels [coff, coff + C) of x (B,H,W,ld), fp16 or fp32, H and W
+    even.  mode 0: avg_pool2d(x, 2, 1) on an (B,H,W) map whose last row and column are zero; mode 1: max_pool2d(avg_pool2d(x, 2, 1),
+    3, 2, 1) on (B,H/2,W/2).  Written into channels [out_coff, out_coff + C) of `out` (a new C-channel tensor when None)."""
+    assert x.is_contiguous() and x.dim() == 4
+    B, H, W, ld = x.shape
+    C = ld - coff if C is None else C
+    if out is None:
+        out = torch.empty((B, H // 2, W // 2, C) if mode else (B, H, W, C), dtype=x.dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype == x.dtype
+    L.check(L.lib.bsy_pool_down(_p(x), ld, coff, _p(out), out.shape[-1], out_coff, B, H, W, C, int(mode), L.dtype_code(x.dtype),
+                                _stream(x)))
+    return out
+
+
 def attention_nhwc(qkv: torch.Tensor, heads: int, key_dim: int, head_dim: int, scale: float) -> torch.Tensor:
     """qkv (B,N,heads*(2kd+hd)) fp16 in [q|k|v] (all-heads-contiguous) order -> (B,N,heads*hd) (block.py:4279-4286)."""
     B, N, ld = qkv.shape

@@ -147,8 +147,15 @@ class Plan:
                  fuse_stem: Optional[bool] = None, fuse_bneck: Optional[bool] = None, fuse_head: Optional[bool] = None,
                  fuse_dwpw: Optional[bool] = None, merge_c3k: Optional[bool] = None, fuse_msca: Optional[bool] = None,
                  fuse_tail: Optional[bool] = None, precision: str = "fp16", lanes: Optional[bool] = None, latency: bool = False,
-                 fuse_pmsfa: Optional[bool] = None):
+                 fuse_pmsfa: Optional[bool] = None, repconv: str = "refconv"):
         self.cfg, self.B, self.H, self.W = cfg, B, H, W
+        # What RepBottleneck.cv1 (YOLOv9's RepCSP, block.py:3634-3641) is in the model at hand: "refconv", the fork's own RepConv
+        # (block.py:793-816: one bare 3x3 conv whose kernel is weight + convmap(weight); no BN, no bias, no activation) -- what every
+        # yaml-built model holds --, or "repvgg", upstream's (conv.py:296-397: SiLU(conv3x3 + conv1x1), each with BN; folds into one
+        # biased 3x3) -- what an upstream-pickled checkpoint unpickles.  plugin.accelerate tells them apart by the state-dict keys.
+        if repconv not in ("refconv", "repvgg"):
+            raise ValueError(f"repconv must be 'refconv' or 'repvgg', not {repconv!r}")
+        self.repconv = repconv
         # latency mode (round 4; fp16 path): long-K conv layers with few tiles per image run split-K (split_factors below)
         self.latency = bool(latency) and precision == "fp16"
         if precision not in ("fp16", "fp32", "fp32x"):
@@ -365,10 +372,13 @@ class Plan:
         self.ops.append(dict(kind=L.OP_COPY, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, dst=dst, name=name, lane=self._lane))
 
     # ---- module expansions -----------------------------------------------------------------------------------
-    def bottleneck(self, name: str, x: T, dst: T, shortcut: bool, k=(3, 3), e=0.5):
-        """block.py:3405-3419: x + cv2(cv1(x))."""
+    def bottleneck(self, name: str, x: T, dst: T, shortcut: bool, k=(3, 3), e=0.5, rep: bool = False):
+        """block.py:3405-3419: x + cv2(cv1(x)).  rep: a RepBottleneck (:3634-3641) -- cv1 is a RepConv, in the form self.repconv names: one
+        3x3 conv either way once the host has folded it (weights.py kinds "refconv": no activation, zero bias; "repvgg": SiLU).  The
+        one-launch Bottleneck kernel computes SiLU after cv1 and is built for e = 0.5, so it serves neither (a RepBottleneck has e = 1)."""
         c_ = int(dst.real * e)
-        if (self.fuse_bneck and tuple(k) == (3, 3) and shortcut and x.C == dst.C and not x.up and not x.f32 and x.cmap is None and dst.cmap is None
+        cv1 = dict(act=self.repconv == "repvgg", wkind=self.repconv) if rep else {}
+        if (not rep and self.fuse_bneck and tuple(k) == (3, 3) and shortcut and x.C == dst.C and not x.up and not x.f32 and x.cmap is None and dst.cmap is None
                 and bneck_supported(x.C, c_)):
             # one launch, hidden map kept in LDS (csrc/bneck_fused.hip)
             k1 = self._wrec(name + ".cv1", name=name + ".cv1", kind="conv", cout=c_, cin=x.C, k=3, perm=None)
@@ -385,18 +395,19 @@ class Plan:
             # real_cin, as Detect's class branch does for nc-dependent widths) -- SiLU(0) = 0 there, the real channels are unchanged
             c8 = make_divisible(c_, 8)
             if x.cmap is not None or dst.cmap is not None:  # inside a block whose chunks are padded pieces themselves (c2f below)
-                t = self.conv(name + ".cv1", x, c8, k[0], 1, dst=self.alloc(c8, x.H, x.W).padded([(c8, c_)]))
+                t = self.conv(name + ".cv1", x, c8, k[0], 1, dst=self.alloc(c8, x.H, x.W).padded([(c8, c_)]), **cv1)
                 self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res)
                 return
-            t = self.conv(name + ".cv1", x, c8, k[0], 1, real=(c_, 0))
+            t = self.conv(name + ".cv1", x, c8, k[0], 1, real=(c_, 0), **cv1)
             self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res, real=(0, c_))
             return
-        t = self.conv(name + ".cv1", x, c_, k[0], 1)
+        t = self.conv(name + ".cv1", x, c_, k[0], 1, **cv1)
         self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res)
 
-    def c3k(self, name: str, x, dst: T, n: int, shortcut: bool, k=(3, 3)):
+    def c3k(self, name: str, x, dst: T, n: int, shortcut: bool, k=(3, 3), rep: bool = False):
         """block.py:3320-3334 + :3807-3815: cv3(cat(m(cv1 x), cv2 x)), m = n x Bottleneck(c_, c_, k=(3,3), e=1); C3 itself
-        (YOLOv5u) is the same with k = ((1,1), (3,3)) and may read a two-operand Concat."""
+        (YOLOv5u) is the same with k = ((1,1), (3,3)) and may read a two-operand Concat.  rep: RepCSP (:3644-3651), the same block
+        over RepBottlenecks."""
         cr = int(dst.real * 0.5)  # the module's hidden width
         x0 = x if isinstance(x, T) else x[0]
         # fp16 path, hidden width not a multiple of 8 (a C3k of 12 / 20 / 24 channels ...): both halves of the concat are zero-padded pieces
@@ -416,7 +427,7 @@ class Plan:
             self.conv(name + ".cv2", x, c_, 1, 1, dst=cat.slice(c_, c_))
         for i in range(n):
             out = cat.slice(0, c_) if i == n - 1 else new()
-            self.bottleneck(f"{name}.m.{i}", cur, out, shortcut, k, 1.0)
+            self.bottleneck(f"{name}.m.{i}", cur, out, shortcut, k, 1.0, rep=rep)
             cur = out
         self.conv(name + ".cv3", cat, dst.C, 1, 1, dst=dst)
 
@@ -594,13 +605,77 @@ class Plan:
                              name=name, lane=self._lane))
         return dst
 
-    def sppf(self, name: str, x: T, c2: int) -> T:
-        """block.py:3114-3149."""
-        c_ = x.C // 2
+    def sppf(self, name: str, x: T, c2: int, c_: Optional[int] = None, last: str = "cv2") -> T:
+        """block.py:3114-3149.  SPPELAN (:3726-3743) is the same dataflow with the hidden width c_ from the yaml and the last conv
+        named cv5."""
+        c_ = x.C // 2 if c_ is None else c_
         cat = self.alloc(4 * c_, x.H, x.W)
         self.conv(name + ".cv1", x, c_, 1, 1, dst=cat.slice(0, c_))
         self.ops.append(dict(kind=L.OP_SPPF_POOL, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=cat.slice(0, c_), name=name + ".m"))
-        return self.conv(name + ".cv2", cat, c2, 1, 1)
+        return self.conv(name + "." + last, cat, c2, 1, 1)
+
+    # ---- YOLOv9 (GELAN) blocks --------------------------------------------------------------------------------------
+    def pool_down(self, name: str, src: T, mode: int) -> T:
+        """The pooling in front of AConv / ADown's convs (csrc/pool_down.hip).  mode 0: avg_pool2d(src, 2, 1) on an H x W map with a zero
+        last row and column; mode 1: max_pool2d(avg_pool2d(src, 2, 1), 3, 2, 1) on H/2 x W/2."""
+        assert not src.up and src.f32 == self.f32_mode and src.cmap is None
+        if src.H % 2 or src.W % 2 or src.H < 2 or src.W < 2:
+            raise NotImplementedError(f"{name}: a {src.H} x {src.W} map (the pooling front end takes even sizes)")
+        v = 4 if self.f32_mode else 8
+        if src.C % v or src.coff % v:
+            raise NotImplementedError(f"{name}: {src.C} channels at offset {src.coff} are not multiples of {v}")
+        OH, OW = (src.H // 2, src.W // 2) if mode else (src.H, src.W)
+        dst = self.alloc(src.C, OH, OW)
+        self.ops.append(dict(kind=L.OP_POOL_DOWN, H=src.H, W=src.W, OH=OH, OW=OW, src0=src, dst=dst, level=mode, name=name, lane=self._lane))
+        return dst
+
+    def aconv(self, name: str, x: T, c2: int) -> T:
+        """block.py:3692-3703: cv1(avg_pool2d(x, 2, 1, 0, False, True)), cv1 = Conv 3x3 s2 p1.  Over the zero-bordered H x W map the conv
+        reads what it reads from the (H-1) x (W-1) pooled map and its padding: an ordinary even-sized stride-2 conv."""
+        return self.conv(name + ".cv1", self.pool_down(name + ".pool", x, 0), c2, 3, 2)
+
+    def adown(self, name: str, x: T, c2: int) -> T:
+        """block.py:3706-3723: the same average pool, chunk(2, 1); cat(cv1(first half), cv2(max_pool2d(second half, 3, 2, 1))).  The
+        halves read disjoint channels: one launch each, the two convs write the halves of one buffer."""
+        h, c = x.C // 2, c2 // 2
+        if x.C % 2 or c2 % 2 or ((h % 8 or c % 8) and not self.f32_mode):
+            raise NotImplementedError(f"{name}: ADown halves of {h} -> {c} channels are not on the fp16 path (multiples of 8)")
+        a = self.pool_down(name + ".avg", x.slice(0, h), 0)
+        b = self.pool_down(name + ".max", x.slice(h, h), 1)
+        out = self.alloc(c2, x.H // 2, x.W // 2)
+        self.conv(name + ".cv1", a, c, 3, 2, dst=out.slice(0, c))
+        self.conv(name + ".cv2", b, c, 1, 1, dst=out.slice(c, c))
+        return out
+
+    def elan(self, name: str, x, c2: int, c3: int, c4: int, n: int, rep: bool) -> T:
+        """block.py:3654-3676 RepNCSPELAN4 (rep) / :3679-3689 ELAN1: cv4(cat(y0, y1, cv2(y1), cv3(cv2(y1)))), [y0 | y1] = cv1(x); cv2 / cv3
+        are RepCSP -> Conv 3x3 (rep) or one Conv 3x3.  One concat buffer of c3 + 2 c4 channels, every stage a slice of it."""
+        xs = [x] if isinstance(x, T) else list(x)
+        h = c3 // 2
+        if c3 % 2:
+            raise NotImplementedError(f"{name}: cv1's {c3} channels do not chunk into two halves")
+        # fp16 path, a chunk or branch width that is no multiple of 8 (yolov9m's P4 stage: 360 -> 180 + 180, branches of 180): every piece
+        # of the concat is carried on the next multiple of 8 with zero weights and bias in the padding, as c2f / c3k do (T.cmap)
+        pad = not self.f32_mode and bool(h % 8 or c4 % 8)
+        h8, c8 = (make_divisible(h, 8), make_divisible(c4, 8)) if pad else (h, c4)
+        H, W = xs[0].H, xs[0].W
+        cat = self.alloc(2 * h8 + 2 * c8, H, W)
+        if pad:
+            cat = cat.padded([(h8, h), (h8, h), (c8, c4), (c8, c4)])
+        self.conv(name + ".cv1", xs, 2 * h8, 1, 1, dst=cat.slice(0, 2 * h8))
+        src = cat.slice(h8, h8)
+        for j, cv in enumerate(("cv2", "cv3")):
+            dst = cat.slice(2 * h8 + j * c8, c8)
+            if rep:
+                t = self.alloc(c8, H, W)
+                if pad:
+                    t = t.padded([(c8, c4)])
+                self.c3k(f"{name}.{cv}.0", src, t, n, True, (3, 3), rep=True)
+                self.conv(f"{name}.{cv}.1", t, c8, 3, 1, dst=dst)
+            else:
+                self.conv(f"{name}.{cv}", src, c8, 3, 1, dst=dst)
+            src = dst
+        return self.conv(name + ".cv4", cat, c2, 1, 1)
 
     def c2psa(self, name: str, x: T, c2: int, n: int) -> T:
         """block.py:4429-4468 with PSABlock :4348-4383 and Attention :4235-4288."""
@@ -751,7 +826,11 @@ class Plan:
         self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
         if fused:
             return
+        # a Detect head that takes the decode launch on the fp16 path does so because fuse_head is off: the launch then sums the DFL in
+        # the fused epilogue's order (act = 1), so the switch returns the fused plan's bits at three levels as it does at four.  Segment,
+        # OBB and the fp32-storage modes have no fused form and keep the order their outputs have always had
         self.ops.append(dict(kind=L.OP_DECODE, join=1, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=nm, ne=ne, A=A, box=boxes,
+                             act=int(not self.f32_mode and nm == 0 and ne == 0),
                              cls=clss, msk=msks, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs], lvl_stride=strides,
                              dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne, 0, 0), out_dtype=self.out_dtype,
                              name=name + ".decode"))
@@ -841,6 +920,23 @@ class Plan:
                 else:
                     assert isinstance(x, T)
                     y = self.c2psa(name, x, c2, n)
+                cout = c2
+            elif m in ("RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN"):
+                # tasks.py:995-1023: c2 scaled like a Conv's, the other arguments literal, no repeat count inserted (n stays 1)
+                c2 = make_divisible(min(args[0], max_ch) * width, 8)
+                if m in ("RepNCSPELAN4", "ELAN1"):
+                    rep = m == "RepNCSPELAN4"
+                    y = self.elan(name, x, c2, args[1], args[2], (args[3] if len(args) > 3 else 1) if rep else 0, rep)
+                else:
+                    assert isinstance(x, T)
+                    if m == "SPPELAN":
+                        if len(args) > 2 and args[2] != 5:
+                            raise NotImplementedError(f"{name}: SPPELAN with k = {args[2]} (the pool kernel is built for 5)")
+                        if args[1] % 8 and not self.f32_mode:
+                            raise NotImplementedError(f"{name}: SPPELAN with a hidden width of {args[1]} channels is not on the fp16 path (multiples of 8)")
+                        y = self.sppf(name, x, c2, args[1], "cv5")
+                    else:
+                        y = self.aconv(name, x, c2) if m == "AConv" else self.adown(name, x, c2)
                 cout = c2
             elif m == "MSCAAttention":  # tasks.py:1052-1054
                 assert isinstance(x, T)
@@ -1050,7 +1146,7 @@ class Plan:
                 o.lvl_h[j] = d["lvl_h"][j] if j < len(d.get("lvl_h", [])) else 0
                 o.lvl_w[j] = d["lvl_w"][j] if j < len(d.get("lvl_w", [])) else 0
                 o.lvl_stride[j] = d["lvl_stride"][j] if j < len(d.get("lvl_stride", [])) else 0.0
-            o.in_dtype, o.out_dtype, o.level = d.get("in_dtype", 0), d.get("out_dtype", 0), d.get("level", 0)
+            o.in_dtype, o.out_dtype, o.level = d.get("in_dtype", 0), d.get("out_dtype", 0), d.get("level", 0)  # POOL_DOWN: level = mode
             o.lane, o.join, o.tuned_cfg = d.get("lane", 0), d.get("join", 0), 0
             o.prec = (2 if self.split_f16 else 1) if self.f32_mode else 0
             o.ksplit = d.get("ksplit", 0)

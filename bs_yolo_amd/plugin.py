@@ -41,7 +41,7 @@ from . import lib as _L
 from . import nms as _nms
 from .engine import YoloEngine
 from .plan import Plan
-from .weights import BN_EPS
+from .weights import BN_EPS, repconv_form
 
 SUPPORTED_HEADS = ("Detect", "Segment", "OBB")
 
@@ -157,7 +157,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     support, gs = _graph_facts(cfg)  # gs: a P6 graph takes multiples of 64; anything else goes to the reference forward, as non-multiples of 32 do
     orig_forward = model.forward
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
-             "tta_calls": 0, "support": support, "failed": set()}
+             "tta_calls": 0, "support": support, "failed": set(), "repconv": None}
     fp32_mode = fp32_inputs or os.environ.get("BSY_FP32_INPUTS", "engine_fp32x")
     if fp32_mode not in FP32_MODES:
         raise ValueError(f"fp32_inputs must be one of {sorted(FP32_MODES)}, not {fp32_mode!r}")
@@ -181,7 +181,11 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
             # makes a later in-place update (EMA, load_state_dict, a training step) or a .half()/.to() rebuild the engine
             sd = {k: v.detach().float().cpu() for k, v in model.state_dict().items()}
             state["rebuilds"] += 1
-            state[slot] = YoloEngine(cfg, sd, device=dev.index or 0, bn_eps=model_bn_eps(model), precision=precision)
+            # YOLOv9: the fork's own RepConv or upstream's (an upstream-pickled checkpoint), told apart by the keys -- at every build,
+            # so a rebuild after a weight reload or a fuse() sees the form the model holds now
+            state["repconv"] = repconv_form(sd)
+            state[slot] = YoloEngine(cfg, sd, device=dev.index or 0, bn_eps=model_bn_eps(model), precision=precision,
+                                     repconv=state["repconv"])
         return state[slot]
 
     def forward(self, x, *args, **kwargs):

@@ -10,6 +10,7 @@
 """
 from __future__ import annotations
 
+import re
 from typing import Dict, Mapping
 
 import numpy as np
@@ -38,6 +39,45 @@ def fold_conv_bn(sd: Mapping[str, torch.Tensor], prefix: str, eps: float = BN_EP
     else:
         b = _f32(sd[prefix + ".conv.bias"])
     return w, b
+
+
+def fold_refconv(sd: Mapping[str, torch.Tensor], prefix: str):
+    """(weight, bias) fp32 of the fork's RepConv (block.py:793-816), the form every yaml-built RepBottleneck.cv1 has: a bare conv whose
+    kernel is weight + convmap(weight), convmap a 3x3 conv over the co * ci two-dimensional kernels with one group each and no bias
+    (:813-815).  No BatchNorm, no bias, no activation: the bias is zero."""
+    w = _f32(sd[prefix + ".weight"])
+    co, ci, kh, kw = w.shape
+    cm = _f32(sd[prefix + ".convmap.weight"])
+    assert tuple(cm.shape[:2]) == (co * ci, 1), (prefix, tuple(cm.shape))
+    k = w + torch.nn.functional.conv2d(w.view(1, co * ci, kh, kw), cm, None, 1, cm.shape[-1] // 2, 1, co * ci).view_as(w)
+    return k, torch.zeros(co)
+
+
+def fold_repvgg(sd: Mapping[str, torch.Tensor], prefix: str, eps: float = BN_EPS):
+    """(weight, bias) fp32 of upstream's RepConv (conv.py:296-397; what an upstream-pickled YOLOv9 checkpoint holds): SiLU(conv1(x) +
+    conv2(x)), a 3x3 and a 1x1 Conv with BatchNorm each, folded as get_equivalent_kernel_bias does (:328-369) -- every branch folded
+    with its BN, the 1x1 kernel padded to the centre tap, kernels and biases added.  A model that went through fuse() holds the
+    result as conv.weight / conv.bias and is taken as it is.  (The optional identity-BN branch, bn=True, is not built by RepBottleneck.)"""
+    if prefix + ".conv1.conv.weight" not in sd:
+        return _f32(sd[prefix + ".conv.weight"]), _f32(sd[prefix + ".conv.bias"])
+    if prefix + ".bn.weight" in sd:
+        raise NotImplementedError(f"{prefix}: RepConv with an identity BatchNorm branch (bn=True) is not folded")
+    w3, b3 = fold_conv_bn(sd, prefix + ".conv1", eps)
+    w1, b1 = fold_conv_bn(sd, prefix + ".conv2", eps)
+    assert w3.shape[-1] == 3 and w1.shape[-1] == 1, (prefix, tuple(w3.shape), tuple(w1.shape))
+    return w3 + torch.nn.functional.pad(w1, [1, 1, 1, 1]), b3 + b1
+
+
+_REPVGG_KEY = re.compile(r"\.cv[23]\.0\.m\.\d+\.cv1\.(conv1\.conv|conv)\.weight$")
+
+
+def repconv_form(sd: Mapping[str, torch.Tensor]) -> str:
+    """Which RepConv a model's RepBottlenecks (RepNCSPELAN4.cv2.0 / cv3.0, a RepCSP each) hold, from its state-dict keys: a
+    `convmap.weight` -> "refconv" (the fork's own, every yaml-built model); `cv1.conv1.conv.weight`, or after fuse() `cv1.conv.weight`
+    under a RepBottleneck -> "repvgg" (upstream's, an upstream-pickled checkpoint).  A model without RepBottlenecks: "refconv", unused."""
+    if any(k.endswith(".convmap.weight") for k in sd):
+        return "refconv"
+    return "repvgg" if any(_REPVGG_KEY.search(k) for k in sd) else "refconv"
 
 
 def _align(n: int, a: int = 256) -> int:
@@ -83,6 +123,10 @@ def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f3
     elif r.kind == "conv2":  # two Conv modules on the same input, stacked along cout (plan.py conv(name2=...))
         (w, b), (w2, b2) = fold_conv_bn(sd, r.name, eps), fold_conv_bn(sd, r.post, eps)
         w, b = torch.cat([w, w2]), torch.cat([b, b2])
+    elif r.kind == "refconv":
+        w, b = fold_refconv(sd, r.name)
+    elif r.kind == "repvgg":
+        w, b = fold_repvgg(sd, r.name, eps)
     else:
         w, b = fold_conv_bn(sd, r.name, eps)
     if r.rows is not None or r.cols is not None:
@@ -122,7 +166,7 @@ def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f3
                 w3[:, (dy * 2 + dx) * 3:(dy * 2 + dx) * 3 + 3] = w[:, :, dy::2, dx::2]
         w = w3
         r = WRec(name=r.name, kind="conv", cout=cout, cin=16, k=3)
-    if r.kind in ("conv", "conv2", "plain", "first", "first_s2d", "deconv"):
+    if r.kind in ("conv", "conv2", "plain", "first", "first_s2d", "deconv", "refconv", "repvgg"):
         cout, cin, k = r.cout, r.cin, r.k
         assert tuple(w.shape) == (cout, cin, k, k), (r.name, tuple(w.shape), (cout, cin, k, k))
         if r.perm is not None:
@@ -247,6 +291,20 @@ def synth_state_dict(plan: Plan, seed: int = 0, cls_gain: float = 0.1, cls_bias:
             continue
         cin = 1 if r.kind == "dw" else (r.real_cin or r.cin)
         fan = cin * r.k * r.k
+        if r.kind == "refconv":  # block.py:793-816: a buffer `weight` and the per-kernel 3x3 map over it
+            co = r.real_cout or r.cout
+            sd[r.name + ".weight"] = torch.randn(co, cin, r.k, r.k, generator=g) * (2.0 / fan) ** 0.5
+            sd[r.name + ".convmap.weight"] = torch.randn(co * cin, 1, 3, 3, generator=g) * (2.0 / 9) ** 0.5 * 0.25
+            continue
+        if r.kind == "repvgg":  # conv.py:296-397, un-fused: a 3x3 and a 1x1 Conv + BN
+            co = r.real_cout or r.cout
+            for nm, kk in ((r.name + ".conv1", 3), (r.name + ".conv2", 1)):
+                sd[nm + ".conv.weight"] = torch.randn(co, cin, kk, kk, generator=g) * (2.0 / (cin * kk * kk)) ** 0.5
+                sd[nm + ".bn.weight"] = torch.rand(co, generator=g) * 0.6 + 0.7
+                sd[nm + ".bn.bias"] = torch.rand(co, generator=g) * 0.6 - 0.3
+                sd[nm + ".bn.running_mean"] = torch.rand(co, generator=g) * 0.6 - 0.3
+                sd[nm + ".bn.running_var"] = torch.rand(co, generator=g) + 0.5
+            continue
         # kind "conv2": two modules of half the width each, drawn in the order the unmerged plan draws them
         for nm, co in (((r.name, (r.real_cout or r.cout) // 2), (r.post, (r.real_cout or r.cout) // 2)) if r.kind == "conv2" else ((r.name, r.real_cout or r.cout),)):
             sd[nm + ".conv.weight"] = torch.randn(co, cin, r.k, r.k, generator=g) * (2.0 / fan) ** 0.5

@@ -62,7 +62,7 @@ enum bsy_op_kind {
     BSY_OP_DWCONV = 2,     /* depthwise 3x3 s1 + bias (+SiLU) (+residual)                                     */
     BSY_OP_SPPF_POOL = 3,  /* three chained MaxPool2d(5,1,2) -> channel slices of the SPPF concat buffer      */
     BSY_OP_ATTN = 4,       /* softmax(q^T k * scale) v, per (image, head); MFMA flash-style                   */
-    BSY_OP_DECODE = 5,     /* Detect._inference: DFL + dist2bbox + sigmoid -> (B, 4+nc+nm, A)                 */
+    BSY_OP_DECODE = 5,     /* Detect._inference: DFL + dist2bbox + sigmoid -> (B, 4+nc+nm, A); DFL summation order: `act`      */
     BSY_OP_RAW_NCHW = 6,   /* raw per-level head maps NHWC f32 -> BCHW (the `x` list Detect.forward returns)  */
     BSY_OP_NHWC2NCHW = 7,  /* NHWC f16 view -> BCHW tensor (Segment protos, block.py:80-97 output)            */
     BSY_OP_STEM = 8,       /* layers 0 + 1 fused: image -> Conv 3x3 s2 (3 -> mid_c) -> Conv 3x3 s2 (mid_c -> dst.C);
@@ -95,6 +95,10 @@ enum bsy_op_kind {
                             * and conv4 (packed 1x1); heads / key_dim = row lengths of the two depthwise weight tensors.  C in {32, 64, 128};
                             * the same bits as the three launches it replaces                                              */
     /* 21: retired (the chained-1x1 launch of round 4, removed); not reused */
+    BSY_OP_POOL_DOWN = 22, /* pooling front end of YOLOv9's AConv / ADown (block.py:3692-3723; csrc/pool_down.hip): src0 (H x W, even) -> dst,
+                            * f16 views (f32 in the fp32-storage modes).  `level` carries the MODE (the field is otherwise RAW_NCHW's):
+                            * 0: dst (H x W) = avg_pool2d(src0, 2, 1) in rows / columns 0 .. H-2 / W-2, its last row and column ZERO;
+                            * 1: dst (H/2 x W/2) = max_pool2d(avg_pool2d(src0, 2, 1), 3, 2, 1)                             */
     BSY_OP_ELA = 15        /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
@@ -110,7 +114,8 @@ typedef struct bsy_op {
     bsy_view dst;           /* dst.C = Cout */
     bsy_view res;           /* residual added AFTER the activation (Bottleneck / PSABlock shortcut); buf<0 if none */
     int32_t ksize, stride, pad;
-    int32_t act;            /* 0 identity, 1 SiLU */
+    int32_t act;            /* 0 identity, 1 SiLU.  DECODE (nm = ne = 0): 1 = the DFL sums run in the fused head epilogue's order whatever the
+                             * level count, so that a Detect plan with the decode launch returns the bits of the plan with the fused head */
     int32_t out_f32;        /* output mode.  0: dst f16.  1: dst f32 (final head convs feeding BSY_OP_DECODE).
                              * 2 / 3: fused Detect decoder -- the conv is the last layer of a class (2) / box (3) branch
                              * of level `level` and writes rows of the prediction tensor directly: dst = y view
@@ -132,7 +137,7 @@ typedef struct bsy_op {
     float lvl_stride[BSY_MAX_LEVELS];
     int32_t reserved2;
     int32_t in_dtype, out_dtype; /* CONV_FIRST input dtype; DECODE/RAW output dtype */
-    int32_t level;          /* RAW_NCHW: which level; output = external slot in dst.buf */
+    int32_t level;          /* RAW_NCHW: which level; output = external slot in dst.buf.  POOL_DOWN: the mode (0 / 1) */
     int32_t lane;           /* 0 = caller's stream; k > 0 = plan-owned side stream k (independent op chains, e.g. the
                              * per-level Detect branches, run concurrently; forked from lane 0 at first use) */
     int32_t tuned_cfg;      /* conv: 1 + configuration id recorded by bsy_plan_autotune (0 = heuristic) */
@@ -142,7 +147,7 @@ typedef struct bsy_op {
     int64_t aux_off[18];    /* MSCA_SPATIAL: (weights, bias) byte offsets of its nine depthwise convs */
     int32_t prec;           /* 0: the fp16-storage product path.  1: fp32 correctness mode -- every workspace view is NHWC f32,
                              * dense conv weights are f32 [k*k*Cin][Cout], arithmetic is fp32 (csrc/ref32.hip); kinds CONV_FIRST,
-                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ELA.
+                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ELA, POOL_DOWN.
                              * 2: fp32x mode -- storage and every non-conv kernel as in mode 1; dense convs (CONV) multiply on the
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
@@ -318,6 +323,16 @@ int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C, const floa
 /* SPPF pooling (block.py:3145-3149): x1 = buf[..., 0:C]; writes m(x1), m(m(x1)), m(m(m(x1))) to channel slices
  * [C:2C], [2C:3C], [3C:4C] of the same NHWC buffer (ld >= 4C). */
 int bsy_sppf_pool(void* buf, int ld, int B, int H, int W, int C, bsy_stream stream);
+
+/* Pooling front end of AConv / ADown (block.py:3692-3723), NHWC views of `dtype` (BSY_F16 / BSY_F32) storage: x, y = first element of
+ * the BUFFERS, xoff / yoff = first channel of the C-channel views inside rows of ldx / ldy channels.
+ * mode 0: y (B,H,W) = avg_pool2d(x, 2, 1, 0, False, True) on rows 0..H-2 / columns 0..W-2, ZEROS in the last row and column (written, not
+ *         assumed): Conv 3x3 s2 p1 over y equals the same conv over the (H-1) x (W-1) pooled map.
+ * mode 1: y (B,H/2,W/2) = max_pool2d(avg_pool2d(x, 2, 1), 3, 2, 1), padding -inf; the pooled map is not stored.
+ * The average is ((x00 + x01) + x10) + x11 in fp32, times 0.25, rounded once to `dtype` (before the max): ATen's bits in both dtypes.
+ * H, W even and >= 2; C, ldx, ldy, xoff, yoff multiples of 8 (f16) / 4 (f32); anything else is BSY_ERR_ARG. */
+int bsy_pool_down(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
+                  bsy_stream stream);
 
 /* Attention core (block.py:4267-4286): qkv NHWC f16 with channel order [q(all heads) | k(all heads) | v(all heads)],
  * out[pixel][head*head_dim + d] = sum_j softmax_j(q_i . k_j * scale) v_j[d].  key_dim in {16, 32, 48, 64}, head_dim in {32, 64, 96, 128}
