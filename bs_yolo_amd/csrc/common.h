@@ -303,8 +303,13 @@ struct AttnArgs {
     float scale;
     half_t* out;
     int ldo;
+    // pe (block.py:4286 `+ self.pe(v)`) folded into the epilogue: depthwise 3x3 + bias on v over the H x W map (H * W = N), added to
+    // the attention output as dwconv3x3_kernel<false, true> adds it.  pe_w f32 [9][heads * head_dim], pe_b f32 [heads * head_dim]; null: no pe
+    int H = 0, W = 0;
+    const float* pe_w = nullptr;
+    const float* pe_b = nullptr;
 };
-int launch_attention(const AttnArgs& a, hipStream_t s);
+int launch_attention(const AttnArgs& a, hipStream_t s, int impl = 0);  // impl 0 auto / 1 resident / 2 streaming (attention.hip)
 
 struct DecodeArgs {
     const float* box[BSY_MAX_LEVELS];

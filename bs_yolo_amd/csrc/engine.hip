@@ -598,6 +598,10 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             a.qkv = R.h(op.src0); a.ld = op.src0.ld; a.B = op.B; a.N = op.H * op.W; a.heads = op.heads;
             a.key_dim = op.key_dim; a.head_dim = op.head_dim; a.scale = op.scale;
             a.out = R.h(op.dst); a.ldo = op.dst.ld;
+            if (op.act) {  // ATTN: act = pe folded into the epilogue, w_off / b_off = its depthwise weights (include/bsyolo.h)
+                a.H = op.H; a.W = op.W;
+                a.pe_w = (const float*)(wb + op.w_off); a.pe_b = (const float*)(wb + op.b_off);
+            }
             if (!R.ok) return BSY_ERR_ARG;
             return launch_attention(a, s);
         }
@@ -1130,6 +1134,17 @@ extern "C" int bsy_attention(const void* qkv, int ld, int B, int N, int heads, i
     a.qkv = (const half_t*)qkv; a.ld = ld; a.B = B; a.N = N; a.heads = heads; a.key_dim = key_dim; a.head_dim = head_dim;
     a.scale = scale; a.out = (half_t*)out; a.ldo = ldo;
     return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int bsy_attention_pe(const void* qkv, int ld, int B, int H, int W, int heads, int key_dim, int head_dim, float scale,
+                                const float* pe_w, const float* pe_b, void* out, int ldo, int impl, bsy_stream stream) {
+    if (!qkv || !out || (pe_w && !pe_b)) BSY_FAIL(BSY_ERR_ARG, "attention_pe: null pointer");
+    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffff) BSY_FAIL(BSY_ERR_ARG, "attention_pe: bad map size");
+    AttnArgs a;
+    a.qkv = (const half_t*)qkv; a.ld = ld; a.B = B; a.N = H * W; a.heads = heads; a.key_dim = key_dim; a.head_dim = head_dim;
+    a.scale = scale; a.out = (half_t*)out; a.ldo = ldo;
+    a.H = H; a.W = W; a.pe_w = pe_w; a.pe_b = pe_w ? pe_b : nullptr;
+    return launch_attention(a, (hipStream_t)stream, impl);
 }
 
 extern "C" int bsy_detect_decode(const float* const* box, const int* ldb, const float* const* cls, const int* ldc,

@@ -245,6 +245,28 @@ def attention_nhwc(qkv: torch.Tensor, heads: int, key_dim: int, head_dim: int, s
     return out
 
 
+def attention_pe_nhwc(qkv: torch.Tensor, heads: int, key_dim: int, head_dim: int, scale: float,
+                      pe_w: Optional[torch.Tensor] = None, pe_b: Optional[torch.Tensor] = None, impl: int = 0,
+                      out: Optional[torch.Tensor] = None, out_coff: int = 0) -> torch.Tensor:
+    """qkv (B,H,W,heads*(2kd+hd)) fp16 in [q|k|v] order -> attention + pe(v) (B,H,W,heads*hd) in one launch (block.py:4279-4286).
+    pe_w (heads*hd,1,3,3) / pe_b (heads*hd): Attention.pe's folded depthwise conv; None runs the attention alone.  impl 0 auto /
+    1 resident / 2 streaming kernel form.  `out` (B,H,W,ld >= out_coff + heads*hd): written at channel out_coff, the rest untouched."""
+    assert qkv.is_contiguous() and qkv.dim() == 4
+    B, H, W, ld = qkv.shape
+    Cc = heads * head_dim
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=torch.float16, device=qkv.device)
+    assert out.is_contiguous() and out.dtype == torch.float16 and out.shape[:3] == qkv.shape[:3]
+    wp = bp = None
+    if pe_w is not None:
+        wp = pe_w.detach().float().cpu().view(Cc, 9).t().contiguous().to(qkv.device)
+        bp = pe_b.detach().float().contiguous().to(qkv.device)
+    dst = out.view(-1)[out_coff:] if out_coff else out
+    L.check(L.lib.bsy_attention_pe(_p(qkv), ld, B, H, W, heads, key_dim, head_dim, float(scale), _p(wp), _p(bp), _p(dst),
+                                   out.shape[-1], int(impl), _stream(qkv)))
+    return out
+
+
 def detect_decode(box: Sequence[torch.Tensor], cls: Sequence[torch.Tensor], hw: Sequence[tuple],
                   strides: Sequence[float], nc: int, out_dtype=torch.float32,
                   msk: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:

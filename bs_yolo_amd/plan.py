@@ -147,7 +147,7 @@ class Plan:
                  fuse_stem: Optional[bool] = None, fuse_bneck: Optional[bool] = None, fuse_head: Optional[bool] = None,
                  fuse_dwpw: Optional[bool] = None, merge_c3k: Optional[bool] = None, fuse_msca: Optional[bool] = None,
                  fuse_tail: Optional[bool] = None, precision: str = "fp16", lanes: Optional[bool] = None, latency: bool = False,
-                 fuse_pmsfa: Optional[bool] = None, repconv: str = "refconv"):
+                 fuse_pmsfa: Optional[bool] = None, repconv: str = "refconv", fuse_attn_pe: Optional[bool] = None):
         self.cfg, self.B, self.H, self.W = cfg, B, H, W
         # What RepBottleneck.cv1 (YOLOv9's RepCSP, block.py:3634-3641) is in the model at hand: "refconv", the fork's own RepConv
         # (block.py:793-816: one bare 3x3 conv whose kernel is weight + convmap(weight); no BN, no bias, no activation) -- what every
@@ -165,7 +165,7 @@ class Plan:
         self.f32_mode = precision in ("fp32", "fp32x")
         self.split_f16 = precision == "fp32x"
         if self.f32_mode:
-            fuse_stem = fuse_bneck = fuse_head = fuse_dwpw = merge_c3k = fuse_msca = fuse_tail = fuse_pmsfa = False
+            fuse_stem = fuse_bneck = fuse_head = fuse_dwpw = merge_c3k = fuse_msca = fuse_tail = fuse_pmsfa = fuse_attn_pe = False
         self.in_dtype, self.out_dtype = in_dtype, out_dtype
         self.fuse_stem = (os.environ.get("BSY_FUSE_STEM", "1") != "0") if fuse_stem is None else bool(fuse_stem)
         self.fuse_bneck = (os.environ.get("BSY_FUSE_BNECK", "1") != "0") if fuse_bneck is None else bool(fuse_bneck)
@@ -178,6 +178,8 @@ class Plan:
         self.fuse_tail = (os.environ.get("BSY_FUSE_TAIL", "1") != "0") if fuse_tail is None else bool(fuse_tail)
         # PMSFA's depthwise 5x5 -> depthwise 7x7 -> 1x1 + shortcut as one launch (round 4, csrc/pmsfa_fused.hip)
         self.fuse_pmsfa = (os.environ.get("BSY_FUSE_PMSFA", "1") != "0") if fuse_pmsfa is None else bool(fuse_pmsfa)
+        # Attention.pe (depthwise 3x3 on v + the attention output) in the attention kernel's epilogue (csrc/attention.hip)
+        self.fuse_attn_pe = (os.environ.get("BSY_FUSE_ATTN_PE", "1") != "0") if fuse_attn_pe is None else bool(fuse_attn_pe)
         self.buf_bytes: List[int] = []
         self.ops: List[dict] = []
         self.wrecs: "OrderedDict[str, WRec]" = OrderedDict()
@@ -700,11 +702,18 @@ class Plan:
             pn = f"{name}.m.{i}"
             qkv = self.conv(pn + ".attn.qkv", b, nh * per, 1, 1, act=False, perm=perm)
             att = self.alloc(c, x.H, x.W)
-            self.ops.append(dict(kind=L.OP_ATTN, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=qkv, dst=att, heads=nh, key_dim=kd,
-                                 head_dim=hd, scale=float(kd ** -0.5), name=pn + ".attn"))
             N = x.H * x.W
             self.flops += 2 * self.B * nh * N * N * (kd + hd)
-            xo = self.dwconv(pn + ".attn.pe", qkv.slice(2 * nh * kd, c), act=False, res=att)  # v@attn^T + pe(v)
+            if self.fuse_attn_pe:  # v@attn^T + pe(v) in one launch: the same weight record and the same bits as the two below
+                key = self._wrec(pn + ".attn.pe", name=pn + ".attn.pe", kind="dw", cout=c, cin=1, k=3, real_cout=0)
+                self.ops.append(dict(kind=L.OP_ATTN, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=qkv, dst=att, heads=nh, key_dim=kd,
+                                     head_dim=hd, scale=float(kd ** -0.5), act=1, wkey=key, name=pn + ".attn+pe", lane=self._lane))
+                self.flops += 2 * self.B * N * c * 9
+                xo = att
+            else:
+                self.ops.append(dict(kind=L.OP_ATTN, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=qkv, dst=att, heads=nh, key_dim=kd,
+                                     head_dim=hd, scale=float(kd ** -0.5), name=pn + ".attn"))
+                xo = self.dwconv(pn + ".attn.pe", qkv.slice(2 * nh * kd, c), act=False, res=att)  # v@attn^T + pe(v)
             self.conv(pn + ".attn.proj", xo, c, 1, 1, act=False, dst=b, res=b)                # b = b + proj(.)
             f = self.conv(pn + ".ffn.0", b, 2 * c, 1, 1)
             self.conv(pn + ".ffn.1", f, c, 1, 1, act=False, dst=b, res=b)                     # b = b + ffn(b)

@@ -61,7 +61,8 @@ enum bsy_op_kind {
     BSY_OP_CONV = 1,       /* implicit-GEMM conv k in {1,3}, s in {1,2}, MFMA f16, fused bias/SiLU/residual   */
     BSY_OP_DWCONV = 2,     /* depthwise 3x3 s1 + bias (+SiLU) (+residual)                                     */
     BSY_OP_SPPF_POOL = 3,  /* three chained MaxPool2d(5,1,2) -> channel slices of the SPPF concat buffer      */
-    BSY_OP_ATTN = 4,       /* softmax(q^T k * scale) v, per (image, head); MFMA flash-style                   */
+    BSY_OP_ATTN = 4,       /* softmax(q^T k * scale) v, per (image, head); MFMA flash-style.  act = 1 (fp16 path): + pe(v) in
+                            * the same launch, w_off / b_off = pe's depthwise f32 [9][C] / [C] (the bits of ATTN then DWCONV) */
     BSY_OP_DECODE = 5,     /* Detect._inference: DFL + dist2bbox + sigmoid -> (B, 4+nc+nm, A); DFL summation order: `act`      */
     BSY_OP_RAW_NCHW = 6,   /* raw per-level head maps NHWC f32 -> BCHW (the `x` list Detect.forward returns)  */
     BSY_OP_NHWC2NCHW = 7,  /* NHWC f16 view -> BCHW tensor (Segment protos, block.py:80-97 output)            */
@@ -339,6 +340,13 @@ int bsy_pool_down(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, 
  * (the stock scales: 32 / 64; other width multiples give e.g. one head of 48 / 96, block.py:4253-4258); BSY_ERR_ARG otherwise. */
 int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale, void* out,
                   int ldo, bsy_stream stream);
+/* The same over an H x W map (N = H * W) with Attention.pe folded into the epilogue (block.py:4286): out = attention + pe(v), pe a
+ * depthwise 3x3 (zero padding) + bias on the v channels, pe_w f32 [9][heads * head_dim] (tap-major, as bsy_dwconv3x3), pe_b f32
+ * [heads * head_dim] -- bit for bit what bsy_attention followed by bsy_dwconv3x3(v, act 0, res = attention output) returns.
+ * pe_w NULL: no pe (= bsy_attention).  impl 0: the kernel form is chosen from the shape; 1: resident form (all keys of
+ * an (image, head) in LDS; BSY_ERR_ARG where they do not fit: more than 512 keys at 32 / 64); 2: streaming form (any N). */
+int bsy_attention_pe(const void* qkv, int ld, int B, int H, int W, int heads, int key_dim, int head_dim, float scale,
+                     const float* pe_w, const float* pe_b, void* out, int ldo, int impl, bsy_stream stream);
 
 /* Detect._inference (head.py:100-131) + DFL (block.py:58-77) + make_anchors/dist2bbox (utils/tal.py:371-395).
  * box[l]: f32 (B*h*w, ldb) 64 DFL logits; cls[l]: f32 (B*h*w, ldc) nc logits; msk[l]: f32 nm coeffs or NULL.
