@@ -310,6 +310,7 @@ struct AttnArgs {
     const float* pe_b = nullptr;
 };
 int launch_attention(const AttnArgs& a, hipStream_t s, int impl = 0);  // impl 0 auto / 1 resident / 2 streaming (attention.hip)
+bool attention_supported(int key_dim, int head_dim);
 
 struct DecodeArgs {
     const float* box[BSY_MAX_LEVELS];

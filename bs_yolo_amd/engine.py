@@ -19,18 +19,18 @@ import torch
 from . import lib as L
 from . import ops as O
 from . import tta as T
-from .plan import Plan
+from .plan import SWITCHES, Plan
 from .weights import BN_EPS, adopt_offsets, pack_plan_weights, repconv_form
 
 
 class YoloEngine:
     def __init__(self, cfg: dict, state_dict: Mapping[str, torch.Tensor], device: int = 0, bn_eps: float = BN_EPS,
-                 autotune: Optional[bool] = None, fuse_stem: Optional[bool] = None,
-                 fuse_bneck: Optional[bool] = None, fuse_head: Optional[bool] = None, fuse_dwpw: Optional[bool] = None,
-                 merge_c3k: Optional[bool] = None, fuse_msca: Optional[bool] = None, fuse_tail: Optional[bool] = None,
-                 max_plans: Optional[int] = None, precision: str = "fp16", graph: Optional[bool] = None, graph_ring: int = 3,
-                 latency: Optional[bool] = None, fuse_pmsfa: Optional[bool] = None, repconv: Optional[str] = None,
-                 fuse_attn_pe: Optional[bool] = None):
+                 autotune: Optional[bool] = None, max_plans: Optional[int] = None, precision: str = "fp16", graph: Optional[bool] = None,
+                 graph_ring: int = 3, latency: Optional[bool] = None, repconv: Optional[str] = None, **switches: Optional[bool]):
+        """switches: the fusion switches of plan.SWITCHES (fuse_stem=False, ...), handed to every plan; None or absent = the switch's
+        environment variable, on where that is unset."""
+        if not set(switches) <= set(SWITCHES):
+            raise TypeError(f"YoloEngine() got an unexpected keyword argument {sorted(set(switches) - set(SWITCHES))[0]!r}")
         if not torch.cuda.is_available():
             raise RuntimeError("bs_yolo_amd needs a ROCm GPU (there is no CPU fallback)")
         self.cfg = cfg
@@ -97,18 +97,10 @@ class YoloEngine:
         self._tta_geom: Dict[Tuple[int, int], list] = {}  # (H, W) -> tta.Pass list (forward_augment)
         self._tta_bufs: "OrderedDict[Tuple, torch.Tensor]" = OrderedDict()  # scaled TTA inputs per (pass, B, PH, PW, dtype), LRU
         self.autotune = ((os.environ.get("BSY_AUTOTUNE", "1") != "0") if autotune is None else bool(autotune)) and precision == "fp16"
-        # pack once with a throw-away plan (op list structure does not depend on the input size)
-        self.fuse_stem = fuse_stem  # None: BSY_FUSE_STEM env (default on); False keeps layers 0 and 1 as two launches
-        self.fuse_bneck = fuse_bneck
-        self.fuse_head = fuse_head
-        self.fuse_dwpw = fuse_dwpw
-        self.merge_c3k = merge_c3k
-        self.fuse_msca = fuse_msca
-        self.fuse_tail = fuse_tail
-        self.fuse_pmsfa = fuse_pmsfa
-        self.fuse_attn_pe = fuse_attn_pe
+        self.switches = dict(switches)
         # YOLOv9 graphs: which RepConv the RepBottlenecks hold (Plan's `repconv`); None reads it off the state dict's keys
         self.repconv = repconv or repconv_form(state_dict)
+        # pack once with a throw-away plan (op list structure does not depend on the input size)
         self._packed = Plan(cfg, 1, 64, 64, **self._fuse_kw())
         blob = pack_plan_weights(self._packed, state_dict, bn_eps)
         self.weight_bytes = len(blob)
@@ -135,10 +127,7 @@ class YoloEngine:
             L.check(L.lib.bsy_engine_load_weights(self._h, buf, len(blob)))
 
     def _fuse_kw(self):
-        return dict(fuse_stem=self.fuse_stem, fuse_bneck=self.fuse_bneck, fuse_head=self.fuse_head, fuse_dwpw=self.fuse_dwpw,
-                    merge_c3k=self.merge_c3k, fuse_msca=self.fuse_msca, fuse_tail=self.fuse_tail, precision=self.precision,
-                    lanes=True if getattr(self, "graph", False) else None, latency=getattr(self, "latency", False),
-                    fuse_pmsfa=self.fuse_pmsfa, repconv=self.repconv, fuse_attn_pe=self.fuse_attn_pe)
+        return dict(self.switches, precision=self.precision, lanes=True if self.graph else None, latency=self.latency, repconv=self.repconv)
 
     # -- plans --------------------------------------------------------------------------------------------------
     def plan_for(self, B: int, H: int, W: int, in_dtype: torch.dtype, out_dtype: torch.dtype):
@@ -234,21 +223,10 @@ class YoloEngine:
                     pass
 
     def _max_view_elems(self, H: int, W: int) -> int:
-        """Largest (pixels x row stride) of any activation view of ONE image at this size: the kernels keep element offsets in
-        32 bits, so a batch is split when B times this reaches 2^31 (C2f concat buffers are larger than the first
-        conv's output, which the round-1 estimate used)."""
-        key = (H, W)
-        hit = self._elems.get(key)
+        """Plan.max_view_elems of ONE image at this size: a batch is split when B times this reaches 2^31 (forward)."""
+        hit = self._elems.get((H, W))
         if hit is None:
-            p1 = Plan(self.cfg, 1, H, W, **self._fuse_kw())
-            hit = 1
-            for o in p1.ops:
-                for k in ("src0", "src1", "dst", "res"):
-                    t = o.get(k)
-                    if t is not None and t.buf < L.BSY_EXT_BASE:
-                        hs, ws = (t.H // 2, t.W // 2) if t.up else (t.H, t.W)
-                        hit = max(hit, hs * ws * t.ld)
-            self._elems[key] = hit
+            hit = self._elems[(H, W)] = Plan(self.cfg, 1, H, W, **self._fuse_kw()).max_view_elems()
         return hit
 
     def _ext(self, im, y, raws, proto=None):

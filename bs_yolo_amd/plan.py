@@ -16,6 +16,7 @@ stock tables in graphs.py), so a reference model drops in without translation.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from collections import OrderedDict
@@ -95,39 +96,37 @@ class WRec:
     b_off: int = -1
 
 
-def stem_supported(c0: int, c1: int, H: int, W: int) -> bool:
-    """Shapes csrc/stem_fused.hip accepts (mirror of stem_fused_supported / bsy_stem_fused_supported)."""
-    return (c0, c1) in ((32, 64), (16, 32)) and W % 4 == 0 and H >= 4 and W >= 4
+# Fusion switch -> the environment variable that decides it where the caller passes None.  Every switch defaults to on, and the
+# fp32-storage modes clear them all.  A new switch is one line here: Plan and YoloEngine take it as a keyword from this table.
+SWITCHES = {
+    "fuse_stem": "BSY_FUSE_STEM",        # layers 0 + 1 as one launch (csrc/stem_fused.hip); off: two launches
+    "fuse_bneck": "BSY_FUSE_BNECK",      # Bottleneck with the hidden map in LDS (csrc/bneck_fused.hip)
+    "fuse_head": "BSY_FUSE_HEAD",        # Detect's last convs decode in their epilogue; off: f32 logit maps + the decode launch
+    "fuse_dwpw": "BSY_FUSE_DWPW",        # DWConv 3x3 + Conv 1x1 of the class branch as one launch (csrc/dwpw_fused.hip)
+    "merge_c3k": "BSY_MERGE_C3K",        # C3k's cv1 and cv2 as one conv of twice the width
+    "fuse_msca": "BSY_FUSE_MSCA",        # MSCAAttention's nine depthwise convs and four means as one launch
+    "fuse_tail": "BSY_FUSE_TAIL",        # a whole C3k2 block as one launch (csrc/c3k2_fused.hip)
+    "fuse_pmsfa": "BSY_FUSE_PMSFA",      # PMSFA's depthwise 5x5 -> depthwise 7x7 -> 1x1 + shortcut as one launch (round 4, csrc/pmsfa_fused.hip)
+    "fuse_attn_pe": "BSY_FUSE_ATTN_PE",  # Attention.pe (depthwise 3x3 on v + the attention output) in the attention kernel's epilogue
+}
+
+@functools.lru_cache(maxsize=256)
+def kernel_takes(kernel: str, *shape: int) -> bool:
+    """Whether a fused kernel runs a shape: the library's own answer, bsy_<kernel>_supported(*shape) of include/bsyolo.h (the planner
+    keeps no list of its own).  Remembered: every new input shape builds a plan, and each asks the same few questions."""
+    return getattr(L.lib, f"bsy_{kernel}_supported")(*shape) == 1
 
 
-def msca_spatial_supported(H: int, W: int) -> bool:
-    """Maps whose (H x W x 8 channel) slabs fit LDS (mirror of csrc/bsyolo_ops.hip msca_spatial_supported)."""
-    return H > 0 and W > 0 and H * W <= 1890
-
-
-def attention_supported(kd: int, hd: int) -> bool:
-    """Head shapes csrc/attention.hip is instantiated for (mirror of attention_supported there)."""
-    return 0 < kd <= 64 and kd % 16 == 0 and 0 < hd <= 128 and hd % 32 == 0
-
-
-def pmsfa_tail_supported(c: int) -> bool:
-    """Widths csrc/pmsfa_fused.hip is instantiated for (mirror of pmsfa_tail_supported there)."""
-    return c in (32, 64)
-
-
-def dwpw_supported(c: int, cout: int) -> bool:
-    """Widths dwpw_fused_kernel accepts (mirror of bsy_dwpw_fused_supported)."""
-    return c > 0 and c % 32 == 0 and c <= 256 and cout % 8 == 0
-
-
-def c3k2_supported(cin: int, c: int, c2: int) -> bool:
-    """Widths csrc/c3k2_fused.hip is instantiated for (mirror of bsy_c3k2_fused_supported)."""
-    return (cin, c, c2) == (64, 32, 128)
-
-
-def bneck_supported(c: int, ch: int) -> bool:
-    """Widths csrc/bneck_fused.hip accepts (mirror of bsy_bottleneck_fused_supported)."""
-    return (c, ch) in ((32, 16), (64, 32))
+# Every field an op dict may carry besides kind / name / lane: what c_ops() serialises, then what only the host reads (the weight
+# record keys, and `cout` / `mfma_flops` for the autotuner's signature and the benchmark's per-family sums).  Plan._emit refuses
+# anything else: c_ops() reads with defaults, so a misspelt key would serialise as zero.
+OP_FIELDS = frozenset((
+    "H", "W", "OH", "OW", "src0", "src1", "dst", "res", "ksize", "stride", "pad", "act", "out_f32", "dst_scale", "dst_dy", "dst_dx", "mid_c",
+    "heads", "key_dim", "head_dim", "scale", "nl", "nc", "nm", "ne", "A", "box", "cls", "msk", "lvl_h", "lvl_w", "lvl_stride", "in_dtype",
+    "out_dtype", "level", "join", "ksplit",
+    "wkey", "wkey2", "wkeys", "cout", "mfma_flops"))
+# kinds that may run on a side lane (csrc/engine.hip bsy_plan_run forks and joins around them)
+LANE_KINDS = (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP_C3K2)
 
 
 class Plan:
@@ -143,11 +142,11 @@ class Plan:
         assert 0 <= level < L.BSY_MAX_LEVELS
         return cls.EXT_RAW0 + level if level < 3 else cls.EXT_RAW3 + level - 3
 
-    def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16,
-                 fuse_stem: Optional[bool] = None, fuse_bneck: Optional[bool] = None, fuse_head: Optional[bool] = None,
-                 fuse_dwpw: Optional[bool] = None, merge_c3k: Optional[bool] = None, fuse_msca: Optional[bool] = None,
-                 fuse_tail: Optional[bool] = None, precision: str = "fp16", lanes: Optional[bool] = None, latency: bool = False,
-                 fuse_pmsfa: Optional[bool] = None, repconv: str = "refconv", fuse_attn_pe: Optional[bool] = None):
+    def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16, precision: str = "fp16",
+                 lanes: Optional[bool] = None, latency: bool = False, repconv: str = "refconv", **switches: Optional[bool]):
+        """switches: the keys of SWITCHES; None (or absent) = what the switch's environment variable says, on where it is unset."""
+        if not set(switches) <= set(SWITCHES):
+            raise TypeError(f"Plan() got an unexpected keyword argument {sorted(set(switches) - set(SWITCHES))[0]!r}")
         self.cfg, self.B, self.H, self.W = cfg, B, H, W
         # What RepBottleneck.cv1 (YOLOv9's RepCSP, block.py:3634-3641) is in the model at hand: "refconv", the fork's own RepConv
         # (block.py:793-816: one bare 3x3 conv whose kernel is weight + convmap(weight); no BN, no bias, no activation) -- what every
@@ -164,22 +163,12 @@ class Plan:
         # fp32x: the same plan; its dense convs multiply on the fp16 matrix pipe with split-f16 operands (csrc/conv32x_mfma.hip)
         self.f32_mode = precision in ("fp32", "fp32x")
         self.split_f16 = precision == "fp32x"
-        if self.f32_mode:
-            fuse_stem = fuse_bneck = fuse_head = fuse_dwpw = merge_c3k = fuse_msca = fuse_tail = fuse_pmsfa = fuse_attn_pe = False
         self.in_dtype, self.out_dtype = in_dtype, out_dtype
-        self.fuse_stem = (os.environ.get("BSY_FUSE_STEM", "1") != "0") if fuse_stem is None else bool(fuse_stem)
-        self.fuse_bneck = (os.environ.get("BSY_FUSE_BNECK", "1") != "0") if fuse_bneck is None else bool(fuse_bneck)
-        self.fuse_head = (os.environ.get("BSY_FUSE_HEAD", "1") != "0") if fuse_head is None else bool(fuse_head)
-        # box-branch tail (cv2.x.1 + cv2.x.2 + DFL in one launch): part of the head fusion, BSY_FUSE_BOXTAIL=0 switches it off alone
+        for name, env in SWITCHES.items():
+            arg = switches.get(name)
+            setattr(self, name, not self.f32_mode and ((os.environ.get(env, "1") != "0") if arg is None else bool(arg)))
+        # box-branch tail (cv2.x.1 + cv2.x.2 + DFL in one launch): part of the head fusion; the variable below switches it off alone
         self.fuse_boxtail = self.fuse_head and os.environ.get("BSY_FUSE_BOXTAIL", "1") != "0"
-        self.fuse_dwpw = (os.environ.get("BSY_FUSE_DWPW", "1") != "0") if fuse_dwpw is None else bool(fuse_dwpw)
-        self.merge_c3k = (os.environ.get("BSY_MERGE_C3K", "1") != "0") if merge_c3k is None else bool(merge_c3k)
-        self.fuse_msca = (os.environ.get("BSY_FUSE_MSCA", "1") != "0") if fuse_msca is None else bool(fuse_msca)
-        self.fuse_tail = (os.environ.get("BSY_FUSE_TAIL", "1") != "0") if fuse_tail is None else bool(fuse_tail)
-        # PMSFA's depthwise 5x5 -> depthwise 7x7 -> 1x1 + shortcut as one launch (round 4, csrc/pmsfa_fused.hip)
-        self.fuse_pmsfa = (os.environ.get("BSY_FUSE_PMSFA", "1") != "0") if fuse_pmsfa is None else bool(fuse_pmsfa)
-        # Attention.pe (depthwise 3x3 on v + the attention output) in the attention kernel's epilogue (csrc/attention.hip)
-        self.fuse_attn_pe = (os.environ.get("BSY_FUSE_ATTN_PE", "1") != "0") if fuse_attn_pe is None else bool(fuse_attn_pe)
         self.buf_bytes: List[int] = []
         self.ops: List[dict] = []
         self.wrecs: "OrderedDict[str, WRec]" = OrderedDict()
@@ -197,9 +186,7 @@ class Plan:
         env = os.environ.get("BSY_LANES")
         if env == "0" or (env is None and not lanes and (lanes is not None or B * H * W < 12 * 640 * 640)):
             for o in self.ops:
-                if "lane" in o:
-                    o["lane"] = 0
-        assert all(o.get("lane", 0) == 0 or o["kind"] in (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP_C3K2) for o in self.ops)
+                o["lane"] = 0
 
     # ---- split-K (latency mode) ------------------------------------------------------------------------------------
     @staticmethod
@@ -256,6 +243,28 @@ class Plan:
             self.wrecs[key] = WRec(**kw)
         return key
 
+    def _emit(self, kind: int, name: str, flops: int = 0, /, **o) -> dict:
+        """The one place an op enters the list: `o` are its fields (OP_FIELDS), `flops` its share of the plan's 2 x MAC count.  H, W
+        default to the source's logical size (the destination's where an op has no source), OH, OW to the destination's (H, W where
+        it has none); the op runs on the lane that is current.  mfma_flops -- what of `flops` runs on the matrix pipe -- stays in the
+        op only where there is any: the benchmark tells the conv family by it.  (Positional-only parameters: a call with fifteen
+        keywords is then no dearer than the dict literal it replaces, which keeps plan construction -- on the first forward of every
+        new input shape -- where it was.)"""
+        assert o.keys() <= OP_FIELDS, f"{name}: unknown op field(s) {sorted(set(o) - OP_FIELDS)}"
+        assert not self._lane or kind in LANE_KINDS, f"{name}: an op of kind {kind} on a side lane"
+        if "H" not in o:
+            t = o["src0"] if o.get("src0") is not None else o["dst"]
+            o["H"], o["W"] = t.H, t.W
+        if "OH" not in o:
+            t = o.get("dst")
+            o["OH"], o["OW"] = (t.H, t.W) if t is not None else (o["H"], o["W"])
+        if "mfma_flops" in o and not o["mfma_flops"]:
+            del o["mfma_flops"]
+        o["kind"], o["name"], o["lane"] = kind, name, self._lane
+        self.flops += flops
+        self.ops.append(o)
+        return o
+
     def conv(self, name: str, src: Union[T, Sequence[T]], cout: int, k: int = 1, s: int = 1, act: bool = True,
              dst: Optional[T] = None, res: Optional[T] = None, plain: bool = False, out_f32: bool = False,
              perm: Optional[List[int]] = None, name2: Optional[str] = None, wkind: Optional[str] = None,
@@ -299,32 +308,27 @@ class Plan:
             wc, wi, wk = wshape or (cout, cin, k)  # wshape: the module's own weight shape where the op runs a re-laid-out copy
             key = self._wrec(name, name=name, kind=wkind or ("plain" if plain else "conv"), cout=wc, cin=wi, k=wk, perm=perm,
                              real_cout=real[0], real_cin=real[1], rows=rows, cols=cols)
-        self.ops.append(dict(kind=L.OP_CONV, H=H, W=W, OH=OH, OW=OW, src0=srcs[0],
-                             src1=srcs[1] if len(srcs) > 1 else None, dst=dst, res=res, ksize=k, stride=s, pad=p,
-                             act=int(act), out_f32=int(out_f32), wkey=key, dst_scale=1, name=name, lane=self._lane, cout=cout,
-                             mfma_flops=2 * self.B * OH * OW * cout * cin * k * k))
-        self.flops += 2 * self.B * OH * OW * cout * cin * k * k
+        fl = 2 * self.B * OH * OW * cout * cin * k * k
+        self._emit(L.OP_CONV, name, fl, src0=srcs[0], src1=srcs[1] if len(srcs) > 1 else None, dst=dst, res=res, ksize=k, stride=s, pad=p,
+                   act=int(act), out_f32=int(out_f32), wkey=key, dst_scale=1, cout=cout, mfma_flops=fl)
         return dst
 
     def conv_first(self, name: str, cout: int, k: int, s: int, p: Optional[int] = None) -> T:
         p = k // 2 if p is None else p
+        img = T(L.BSY_EXT_BASE + self.EXT_IMG, 0, 0, 3, self.H, self.W)
         if (k, s, p) == (6, 2, 2) and not self.f32_mode:
             # YOLOv5u's stem (cfg/models/v5/yolov5.yaml:16): space-to-depth of the image (one elementwise launch) + an ordinary
             # 3x3 stride-1 conv over its 12 (+4 zero) channels with the weights re-laid-out to match (weights.py "first_s2d")
             assert self.H % 2 == 0 and self.W % 2 == 0
             sd = self.alloc(16, self.H // 2, self.W // 2)
-            self.ops.append(dict(kind=L.OP_S2D, H=self.H, W=self.W, OH=self.H // 2, OW=self.W // 2,
-                                 src0=T(L.BSY_EXT_BASE + self.EXT_IMG, 0, 0, 3, self.H, self.W), dst=sd, in_dtype=self.in_dtype,
-                                 name=name + ".s2d"))
+            self._emit(L.OP_S2D, name + ".s2d", src0=img, dst=sd, in_dtype=self.in_dtype)
             return self.conv(name, sd, cout, 3, 1, wkind="first_s2d", wshape=(cout, 3, 6))
         OH, OW = (self.H + 2 * p - k) // s + 1, (self.W + 2 * p - k) // s + 1
         dst = self.alloc(cout, OH, OW)
         key = self._wrec(name, name=name, kind="first", cout=cout, cin=3, k=k)
-        self.ops.append(dict(kind=L.OP_CONV_FIRST, H=self.H, W=self.W, OH=OH, OW=OW,
-                             src0=T(L.BSY_EXT_BASE + self.EXT_IMG, 0, 0, 3, self.H, self.W), dst=dst, ksize=k, stride=s,
-                             pad=p, act=1, wkey=key, in_dtype=self.in_dtype, name=name,
-                             mfma_flops=2 * self.B * OH * OW * cout * 3 * k * k))
-        self.flops += 2 * self.B * OH * OW * cout * 3 * k * k
+        fl = 2 * self.B * OH * OW * cout * 3 * k * k
+        self._emit(L.OP_CONV_FIRST, name, fl, src0=img, dst=dst, ksize=k, stride=s, pad=p, act=1, wkey=key, in_dtype=self.in_dtype,
+                   mfma_flops=fl)
         return dst
 
     def dwconv(self, name: str, src: T, act: bool, dst: Optional[T] = None, res: Optional[T] = None, real_c: int = 0) -> T:
@@ -332,9 +336,8 @@ class Plan:
         if dst is None:
             dst = self.alloc(src.C, src.H, src.W)
         key = self._wrec(name, name=name, kind="dw", cout=src.C, cin=1, k=3, real_cout=real_c)
-        self.ops.append(dict(kind=L.OP_DWCONV, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, dst=dst, res=res,
-                             ksize=3, stride=1, pad=1, act=int(act), wkey=key, name=name, lane=self._lane))
-        self.flops += 2 * self.B * src.H * src.W * src.C * 9
+        self._emit(L.OP_DWCONV, name, 2 * self.B * src.H * src.W * src.C * 9,
+                   src0=src, dst=dst, res=res, ksize=3, stride=1, pad=1, act=int(act), wkey=key)
         return dst
 
     def dwconv_g(self, name: str, src: T, kh: int, kw: int, s: int, act_c: int, dst: Optional[T] = None, kind: str = "dwg",
@@ -347,31 +350,29 @@ class Plan:
             dst = self.alloc(src.C, OH, OW)
         assert dst.C == src.C and dst.H == OH and dst.W == OW
         key = self._wrec(name, name=name, kind=kind, cout=src.C, cin=1, k=kh, kw=kw, post=post, rows=rows, real_cout=real_c)
-        self.ops.append(dict(kind=L.OP_DWCONV_G, H=src.H, W=src.W, OH=OH, OW=OW, src0=src, dst=dst, ksize=kh, pad=kw, stride=s,
-                             act=int(act_c), wkey=key, heads=src.C, key_dim=0, name=name, lane=self._lane,
-                             mid_c=src.C // 2 if kind == "dwg_ext" else 0))  # first channel of the identity-kernel half
-        self.flops += 2 * self.B * OH * OW * src.C * kh * kw
+        self._emit(L.OP_DWCONV_G, name, 2 * self.B * OH * OW * src.C * kh * kw,
+                   src0=src, dst=dst, ksize=kh, pad=kw, stride=s, act=int(act_c), wkey=key, heads=src.C, key_dim=0,
+                   mid_c=src.C // 2 if kind == "dwg_ext" else 0)  # first channel of the identity-kernel half
         return dst
 
     def dwpw(self, name: str, src: T, cout: int, real: Tuple[int, int] = (0, 0)) -> T:
         """nn.Sequential(DWConv(c, c, 3), Conv(c, cout, 1)) (head.py:49-57): one fused launch where dwpw_fused.hip's
         dwpw_fused_kernel takes the widths, else the two ordinary launches.  real = the modules' own (cout, cin) where `cout` / `src`
         are padded to a multiple of 8."""
-        if not (self.fuse_dwpw and dwpw_supported(src.C, cout) and not src.up):
+        if not (self.fuse_dwpw and kernel_takes("dwpw_fused", src.C, cout) and not src.up):
             t = self.dwconv(name + ".0", src, act=True, real_c=real[1])
             return self.conv(name + ".1", t, cout, 1, 1, real=real)
         kd = self._wrec(name + ".0", name=name + ".0", kind="dw", cout=src.C, cin=1, k=3, real_cout=real[1])
         kp = self._wrec(name + ".1", name=name + ".1", kind="conv", cout=cout, cin=src.C, k=1, perm=None, real_cout=real[0], real_cin=real[1])
         dst = self.alloc(cout, src.H, src.W)
-        self.ops.append(dict(kind=L.OP_DWPW, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, dst=dst, ksize=3, stride=1, pad=1,
-                             act=1, wkey=kd, wkey2=kp, name=name, lane=self._lane,
-                             mfma_flops=2 * self.B * src.H * src.W * src.C * cout))  # the dense 1x1 part (the depthwise is VALU work)
-        self.flops += 2 * self.B * src.H * src.W * src.C * (9 + cout)
+        px = 2 * self.B * src.H * src.W * src.C
+        self._emit(L.OP_DWPW, name, px * (9 + cout), src0=src, dst=dst, ksize=3, stride=1, pad=1, act=1, wkey=kd, wkey2=kp,
+                   mfma_flops=px * cout)  # the dense 1x1 part (the depthwise is VALU work)
         return dst
 
     def copy(self, name: str, src: T, dst: T):
         assert dst.C == src.C and dst.H == src.H and dst.W == src.W and not dst.up
-        self.ops.append(dict(kind=L.OP_COPY, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, dst=dst, name=name, lane=self._lane))
+        self._emit(L.OP_COPY, name, src0=src, dst=dst)
 
     # ---- module expansions -----------------------------------------------------------------------------------
     def bottleneck(self, name: str, x: T, dst: T, shortcut: bool, k=(3, 3), e=0.5, rep: bool = False):
@@ -381,14 +382,12 @@ class Plan:
         c_ = int(dst.real * e)
         cv1 = dict(act=self.repconv == "repvgg", wkind=self.repconv) if rep else {}
         if (not rep and self.fuse_bneck and tuple(k) == (3, 3) and shortcut and x.C == dst.C and not x.up and not x.f32 and x.cmap is None and dst.cmap is None
-                and bneck_supported(x.C, c_)):
+                and kernel_takes("bottleneck_fused", x.C, c_)):
             # one launch, hidden map kept in LDS (csrc/bneck_fused.hip)
             k1 = self._wrec(name + ".cv1", name=name + ".cv1", kind="conv", cout=c_, cin=x.C, k=3, perm=None)
             k2 = self._wrec(name + ".cv2", name=name + ".cv2", kind="conv", cout=dst.C, cin=c_, k=3, perm=None)
-            self.ops.append(dict(kind=L.OP_BNECK, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=x, dst=dst, ksize=3, stride=1,
-                                 pad=1, act=1, wkey=k1, wkey2=k2, mid_c=c_, name=name, lane=self._lane,
-                                 mfma_flops=2 * self.B * x.H * x.W * 9 * 2 * c_ * x.C))
-            self.flops += 2 * self.B * x.H * x.W * 9 * 2 * c_ * x.C
+            fl = 2 * self.B * x.H * x.W * 9 * 2 * c_ * x.C
+            self._emit(L.OP_BNECK, name, fl, src0=x, dst=dst, ksize=3, stride=1, pad=1, act=1, wkey=k1, wkey2=k2, mid_c=c_, mfma_flops=fl)
             return
         res = x if (shortcut and x.C == dst.C) else None
         if c_ % 8 and not self.f32_mode:
@@ -438,16 +437,14 @@ class Plan:
         xs = [x] if isinstance(x, T) else list(x)
         c = int(c2 * e)
         if (self.fuse_tail and inner == "bottleneck" and n == 1 and shortcut and len(xs) == 1 and not xs[0].up and not xs[0].f32
-                and c3k2_supported(xs[0].C, c, c2)):
+                and kernel_takes("c3k2_fused", xs[0].C, c, c2)):
             # the whole block in one launch (csrc/c3k2_fused.hip): x in, out out, the [y0 | y1 | y2] concat never reaches HBM
             names = [name + ".cv1", name + ".m.0.cv1", name + ".m.0.cv2", name + ".cv2"]
             shapes = [(2 * c, xs[0].C, 1), (c // 2, c, 3), (c, c // 2, 3), (c2, 3 * c, 1)]
             keys = [self._wrec(nm, name=nm, kind="conv", cout=co, cin=ci, k=k, perm=None) for nm, (co, ci, k) in zip(names, shapes)]
             dst = self.alloc(c2, xs[0].H, xs[0].W)
             fl = 2 * self.B * xs[0].H * xs[0].W * sum(co * ci * k * k for co, ci, k in shapes)
-            self.ops.append(dict(kind=L.OP_C3K2, H=xs[0].H, W=xs[0].W, OH=xs[0].H, OW=xs[0].W, src0=xs[0], dst=dst, ksize=3, stride=1, pad=1,
-                                 act=1, wkeys=keys, mid_c=c, name=name, lane=self._lane, mfma_flops=fl))
-            self.flops += fl
+            self._emit(L.OP_C3K2, name, fl, src0=xs[0], dst=dst, ksize=3, stride=1, pad=1, act=1, wkeys=keys, mid_c=c, mfma_flops=fl)
             return dst
         # fp16 path, chunk width not a multiple of 8 (c = 12 / 20 ...; tasks.py:1016 scales c2 by any width multiple): every chunk of the
         # concat is carried on the next multiple of 8 as a zero-padded piece (T.cmap) -- cv1 writes zero rows there, cv2 reads zero columns
@@ -502,16 +499,16 @@ class Plan:
         if c % 16:
             return self._pmsfa_padded(name, x, dst)
         P = self.conv(name + ".conv1", x, c, 3, 1)
-        if self.fuse_pmsfa and pmsfa_tail_supported(c) and not x.up:
+        if self.fuse_pmsfa and kernel_takes("pmsfa_tail", c) and not x.up:
             # everything after conv1 in one launch: the map is read once and written once (csrc/pmsfa_fused.hip); the weight records are
             # the unfused plan's, in its order (blob layout, synth_state_dict's random draws)
             k2 = self._wrec(name + ".conv2", name=name + ".conv2", kind="dwg", cout=c // 2, cin=1, k=5, kw=5, post=None, rows=None, real_cout=0)
             k3 = self._wrec(name + ".conv3", name=name + ".conv3", kind="dwg_ext", cout=c // 2, cin=1, k=7, kw=7, post=None, rows=None, real_cout=0)
             k4 = self._wrec(name + ".conv4", name=name + ".conv4", kind="conv", cout=c, cin=c, k=1, perm=None)
-            self.ops.append(dict(kind=L.OP_PMSFA_TAIL, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=P, res=x, dst=dst, ksize=1, stride=1, pad=0, act=1,
-                                 wkeys=[k2, k3, k4], heads=c // 2, key_dim=c // 2, name=name + ".tail", lane=self._lane,
-                                 mfma_flops=2 * self.B * x.H * x.W * c * c))
-            self.flops += 2 * self.B * x.H * x.W * (c // 2 * 25 + c // 2 * 49 + c * c)  # what the three launches count
+            px = 2 * self.B * x.H * x.W
+            self._emit(L.OP_PMSFA_TAIL, name + ".tail", px * (c // 2 * 25 + c // 2 * 49 + c * c),  # what the three launches count
+                       src0=P, res=x, dst=dst, ksize=1, stride=1, pad=0, act=1, wkeys=[k2, k3, k4], heads=c // 2, key_dim=c // 2,
+                       mfma_flops=px * c * c)  # the 1x1
             return
         Q = self.dwconv_g(name + ".conv2", P.slice(0, c // 2), 5, 5, 1, c // 2)
         # S overwrites p1 (dead once conv2 has read it): conv4 then reads ONE contiguous source [S | p2] = P -- at c = 32 two 16-channel
@@ -559,7 +556,7 @@ class Plan:
         C, H, W = x.C, x.H, x.W
         strips = ((5, "conv0"), (7, "conv1"), (11, "conv2"), (21, "conv3"))
         branches, logits = [], []
-        if self.fuse_msca and msca_spatial_supported(H, W):
+        if self.fuse_msca and kernel_takes("msca_spatial", H, W):
             # one launch for the nine depthwise convs and the four global means (csrc/bsyolo_ops.hip msca_spatial_kernel)
             keys = [self._wrec(name + ".conv0", name=name + ".conv0", kind="dwg_plain", cout=C, cin=1, k=5, kw=5)]
             for i, (k, base) in enumerate(strips):
@@ -570,9 +567,8 @@ class Plan:
                 self._wrec(se, name=se, kind="plain", cout=C, cin=C, k=1, perm=None)  # synth_state_dict's random draws)
             branches = [self.alloc(C, H, W) for _ in strips]
             gaps = [self.alloc(C, 1, 1) for _ in strips]
-            self.ops.append(dict(kind=L.OP_MSCA_SPATIAL, H=H, W=W, OH=H, OW=W, src0=x, box=branches[:3], res=branches[3],
-                                 cls=gaps[:3], msk=[gaps[3]], wkeys=keys, name=name + ".spatial", lane=self._lane))
-            self.flops += 2 * self.B * H * W * C * (25 + 2 * sum(k for k, _ in strips))
+            self._emit(L.OP_MSCA_SPATIAL, name + ".spatial", 2 * self.B * H * W * C * (25 + 2 * sum(k for k, _ in strips)),
+                       src0=x, box=branches[:3], res=branches[3], cls=gaps[:3], msk=[gaps[3]], wkeys=keys)
             for i, g in enumerate(gaps):
                 logits.append(self.conv(f"{name}.SE{i + 1}.conv.0", g, C, 1, 1, act=False, plain=True, out_f32=True))
         else:
@@ -582,14 +578,13 @@ class Plan:
                 a = self.dwconv_g(f"{name}.{base}_2", a, k, 1, 1, 0, kind="dwg_plain", post=(name + ".dilconv") if i < 3 else None)
                 branches.append(a)
                 g = self.alloc(C, 1, 1)
-                self.ops.append(dict(kind=L.OP_GAP, H=H, W=W, OH=1, OW=1, src0=a, dst=g, name=f"{name}.gap{i}", lane=self._lane))
+                self._emit(L.OP_GAP, f"{name}.gap{i}", src0=a, dst=g)
                 logits.append(self.conv(f"{name}.SE{i + 1}.conv.0", g, C, 1, 1, act=False, plain=True, out_f32=True))
         mix = self.alloc(C, H, W)
-        self.ops.append(dict(kind=L.OP_MSCA_MIX, H=H, W=W, OH=H, OW=W, dst=mix, box=branches[:3], res=branches[3], cls=logits[:3],
-                             msk=[logits[3]], name=name + ".mix", lane=self._lane))
+        self._emit(L.OP_MSCA_MIX, name + ".mix", dst=mix, box=branches[:3], res=branches[3], cls=logits[:3], msk=[logits[3]])
         t = self.conv(name + ".conv4", mix, C, 1, 1, act=False, plain=True)
         out = self.alloc(C, H, W)
-        self.ops.append(dict(kind=L.OP_MUL, H=H, W=W, OH=H, OW=W, src0=t, src1=x, dst=out, name=name + ".mul", lane=self._lane))
+        self._emit(L.OP_MUL, name + ".mul", src0=t, src1=x, dst=out)
         return out
 
     def ela(self, name: str, x: T) -> T:
@@ -603,8 +598,7 @@ class Plan:
         self.buf_bytes.append(self.B * (2 * (x.H + x.W) + 2) * x.C * 4)
         scratch = T(len(self.buf_bytes) - 1, x.C, 0, x.C, 1, 1, False, True)
         dst = self.alloc(x.C, x.H, x.W)
-        self.ops.append(dict(kind=L.OP_ELA, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=x, dst=dst, res=scratch, ksize=k, wkey=key,
-                             name=name, lane=self._lane))
+        self._emit(L.OP_ELA, name, src0=x, dst=dst, res=scratch, ksize=k, wkey=key)
         return dst
 
     def sppf(self, name: str, x: T, c2: int, c_: Optional[int] = None, last: str = "cv2") -> T:
@@ -613,7 +607,7 @@ class Plan:
         c_ = x.C // 2 if c_ is None else c_
         cat = self.alloc(4 * c_, x.H, x.W)
         self.conv(name + ".cv1", x, c_, 1, 1, dst=cat.slice(0, c_))
-        self.ops.append(dict(kind=L.OP_SPPF_POOL, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=cat.slice(0, c_), name=name + ".m"))
+        self._emit(L.OP_SPPF_POOL, name + ".m", src0=cat.slice(0, c_))
         return self.conv(name + "." + last, cat, c2, 1, 1)
 
     # ---- YOLOv9 (GELAN) blocks --------------------------------------------------------------------------------------
@@ -628,7 +622,7 @@ class Plan:
             raise NotImplementedError(f"{name}: {src.C} channels at offset {src.coff} are not multiples of {v}")
         OH, OW = (src.H // 2, src.W // 2) if mode else (src.H, src.W)
         dst = self.alloc(src.C, OH, OW)
-        self.ops.append(dict(kind=L.OP_POOL_DOWN, H=src.H, W=src.W, OH=OH, OW=OW, src0=src, dst=dst, level=mode, name=name, lane=self._lane))
+        self._emit(L.OP_POOL_DOWN, name, src0=src, dst=dst, level=mode)
         return dst
 
     def aconv(self, name: str, x: T, c2: int) -> T:
@@ -686,7 +680,7 @@ class Plan:
         nh = c // 64
         hd = c // nh
         kd = int(hd * 0.5)
-        if not self.f32_mode and not attention_supported(kd, hd):
+        if not self.f32_mode and not kernel_takes("attention", kd, hd):
             # e.g. a width multiple of 0.3125: heads of 40 / 80 channels; the fp32-storage modes run any head shape
             raise NotImplementedError(f"{name}: attention heads of key_dim {kd} / head_dim {hd} are not on the fp16 path (16..64 in steps of 16 / 32..128 in steps of 32)")
         ab = self.alloc(2 * c, x.H, x.W)
@@ -703,16 +697,14 @@ class Plan:
             qkv = self.conv(pn + ".attn.qkv", b, nh * per, 1, 1, act=False, perm=perm)
             att = self.alloc(c, x.H, x.W)
             N = x.H * x.W
-            self.flops += 2 * self.B * nh * N * N * (kd + hd)
+            attn = dict(src0=qkv, dst=att, heads=nh, key_dim=kd, head_dim=hd, scale=float(kd ** -0.5))
+            fl = 2 * self.B * nh * N * N * (kd + hd)
             if self.fuse_attn_pe:  # v@attn^T + pe(v) in one launch: the same weight record and the same bits as the two below
                 key = self._wrec(pn + ".attn.pe", name=pn + ".attn.pe", kind="dw", cout=c, cin=1, k=3, real_cout=0)
-                self.ops.append(dict(kind=L.OP_ATTN, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=qkv, dst=att, heads=nh, key_dim=kd,
-                                     head_dim=hd, scale=float(kd ** -0.5), act=1, wkey=key, name=pn + ".attn+pe", lane=self._lane))
-                self.flops += 2 * self.B * N * c * 9
+                self._emit(L.OP_ATTN, pn + ".attn+pe", fl + 2 * self.B * N * c * 9, act=1, wkey=key, **attn)
                 xo = att
             else:
-                self.ops.append(dict(kind=L.OP_ATTN, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=qkv, dst=att, heads=nh, key_dim=kd,
-                                     head_dim=hd, scale=float(kd ** -0.5), name=pn + ".attn"))
+                self._emit(L.OP_ATTN, pn + ".attn", fl, **attn)
                 xo = self.dwconv(pn + ".attn.pe", qkv.slice(2 * nh * kd, c), act=False, res=att)  # v@attn^T + pe(v)
             self.conv(pn + ".attn.proj", xo, c, 1, 1, act=False, dst=b, res=b)                # b = b + proj(.)
             f = self.conv(pn + ".ffn.0", b, 2 * c, 1, 1)
@@ -728,30 +720,31 @@ class Plan:
                 key = f"{name}.upsample@{dy}{dx}"
                 if key not in self.wrecs:
                     self.wrecs[key] = WRec(name=name + ".upsample", kind="deconv", cout=c_, cin=c_, k=1, tap=(dy, dx))
-                self.ops.append(dict(kind=L.OP_CONV, H=x.H, W=x.W, OH=x.H, OW=x.W, src0=t, src1=None,
-                                     dst=T(up.buf, up.ld, 0, c_, x.H, x.W, False, up.f32), res=None, ksize=1, stride=1, pad=0, act=0,
-                                     out_f32=0, wkey=key, dst_scale=2, dst_dy=dy, dst_dx=dx, name=key,
-                                     mfma_flops=2 * self.B * x.H * x.W * c_ * c_))
-                self.flops += 2 * self.B * x.H * x.W * c_ * c_
+                fl = 2 * self.B * x.H * x.W * c_ * c_
+                self._emit(L.OP_CONV, key, fl, src0=t, src1=None, dst=T(up.buf, up.ld, 0, c_, x.H, x.W, False, up.f32), res=None, ksize=1,
+                           stride=1, pad=0, act=0, out_f32=0, wkey=key, dst_scale=2, dst_dy=dy, dst_dx=dx, mfma_flops=fl)
         t = self.conv(name + ".cv2", up, c_, 3, 1)
         p = self.conv(name + ".cv3", t, nm, 1, 1)
-        self.ops.append(dict(kind=L.OP_NHWC2NCHW, H=p.H, W=p.W, OH=0, OW=0, src0=p,
-                             dst=T(L.BSY_EXT_BASE + self.EXT_PROTO, 0, 0, nm, 0, 0), out_dtype=self.out_dtype,
-                             name=name + ".nchw"))
+        self._emit(L.OP_NHWC2NCHW, name + ".nchw", src0=p, dst=T(L.BSY_EXT_BASE + self.EXT_PROTO, 0, 0, nm, 0, 0), OH=0, OW=0,
+                   out_dtype=self.out_dtype)
         self.meta.update(proto_hw=(p.H, p.W))
         return p
+
+    def _decoding_conv(self, name: str, src: T, k: int, *, cout: int, mode: int, level: int, a0: int, A: int, nc: int, stride: float,
+                       flops: int, **fields):
+        """A conv op with the Detect decoder in its epilogue (out_f32 = mode 2: class branch / 3: box branch): it writes level `level`'s
+        rows of the prediction tensor (first anchor a0 of A, stride `stride`) and that level's raw map."""
+        y = T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc, 0, 0)
+        raw = T(L.BSY_EXT_BASE + self.ext_raw(level), 0, 0, 64 + nc, 0, 0)
+        self._emit(L.OP_CONV, name, flops, src0=src, src1=None, dst=y, res=None, OH=src.H, OW=src.W, ksize=k, stride=1, pad=k // 2,
+                   out_f32=mode, dst_scale=1, cout=cout, nl=cout, nc=nc, nm=0, A=A, box=[raw], cls=[], msk=[], level=level,
+                   lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype, mfma_flops=flops, **fields)
 
     def _head_conv(self, name: str, src: T, cout: int, mode: int, level: int, a0: int, A: int, nc: int, stride: float, real_cin: int = 0):
         """Last 1x1 conv of a Detect branch with the decoder fused into its epilogue (out_f32 = mode 2 / 3)."""
         key = self._wrec(name, name=name, kind="plain", cout=cout, cin=src.C, k=1, perm=None, real_cin=real_cin)
-        y = T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc, 0, 0)
-        raw = T(L.BSY_EXT_BASE + self.ext_raw(level), 0, 0, 64 + nc, 0, 0)
-        self.ops.append(dict(kind=L.OP_CONV, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, src1=None, dst=y, res=None,
-                             ksize=1, stride=1, pad=0, act=0, out_f32=mode, wkey=key, dst_scale=1, name=name, cout=cout,
-                             lane=self._lane, nl=cout, nc=nc, nm=0, A=A, box=[raw], cls=[], msk=[], level=level,
-                             lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype,
-                             mfma_flops=2 * self.B * src.H * src.W * cout * src.C))
-        self.flops += 2 * self.B * src.H * src.W * cout * src.C
+        self._decoding_conv(name, src, 1, cout=cout, mode=mode, level=level, a0=a0, A=A, nc=nc, stride=stride,
+                            flops=2 * self.B * src.H * src.W * cout * src.C, act=0, wkey=key)
 
     def _box_tail(self, name: str, i: int, src: T, level: int, a0: int, A: int, nc: int, stride: float):
         """cv2.i.1 (3x3, 64 -> 64, SiLU) + cv2.i.2 (1x1, 64 -> 64 box logits) + DFL / dist2bbox (head.py:49-57, :141-146) as ONE
@@ -760,14 +753,8 @@ class Plan:
         n1, n2 = f"{name}.cv2.{i}.1", f"{name}.cv2.{i}.2"
         k1 = self._wrec(n1, name=n1, kind="conv", cout=64, cin=src.C, k=3, perm=None)
         k2 = self._wrec(n2, name=n2, kind="plain", cout=64, cin=64, k=1, perm=None)
-        y = T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc, 0, 0)
-        raw = T(L.BSY_EXT_BASE + self.ext_raw(level), 0, 0, 64 + nc, 0, 0)
-        fl = 2 * self.B * src.H * src.W * 64 * (9 * src.C + 64)
-        self.ops.append(dict(kind=L.OP_CONV, H=src.H, W=src.W, OH=src.H, OW=src.W, src0=src, src1=None, dst=y, res=None,
-                             ksize=3, stride=1, pad=1, act=1, out_f32=3, wkey=k1, wkey2=k2, mid_c=64, dst_scale=1, name=n1 + "+2",
-                             cout=64, lane=self._lane, nl=64, nc=nc, nm=0, A=A, box=[raw], cls=[], msk=[], level=level,
-                             lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype, mfma_flops=fl))
-        self.flops += fl
+        self._decoding_conv(n1 + "+2", src, 3, cout=64, mode=3, level=level, a0=a0, A=A, nc=nc, stride=stride,
+                            flops=2 * self.B * src.H * src.W * 64 * (9 * src.C + 64), act=1, wkey=k1, wkey2=k2, mid_c=64)
 
     def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0):
         """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels)."""
@@ -815,22 +802,16 @@ class Plan:
                 self._head_conv(f"{name}.cv3.{i}.2", t, nc, 2, i, a0[i], A, nc, strides[i], real_cin=r3)
             else:
                 clss.append(self.conv(f"{name}.cv3.{i}.2", t, nc, 1, 1, act=False, plain=True, out_f32=True, real=(0, r3)))
-            if nm:
+            if nm or ne:
+                # Segment.cv4 (head.py:175-197) / OBB.cv4 (:208-209): Conv(x, c4, 3) -> Conv(c4, c4, 3) -> Conv2d(c4, nm or ne, 1), on lanes
+                # of their own.  OBB's angle logits land in an f32 map 8 channels wide (zero weights and bias past `ne`): the conv kernels
+                # write cout in 8-channel pieces and the decoder reads 16-byte rows; it passes them in the msk slots with nm = 0
                 self._lane = 2 * len(xs) + i
-                c4 = max(ch[0] // 4, nm)
+                c4 = max(ch[0] // 4, nm or ne)
+                wout, real = (nm, 0) if nm else (make_divisible(ne, 8), ne)
                 t = self.conv(f"{name}.cv4.{i}.0", x, c4, 3, 1)
                 t = self.conv(f"{name}.cv4.{i}.1", t, c4, 3, 1)
-                msks.append(self.conv(f"{name}.cv4.{i}.2", t, nm, 1, 1, act=False, plain=True, out_f32=True))
-            if ne:
-                # OBB.cv4 (head.py:208-209): Conv(x, c4, 3) -> Conv(c4, c4, 3) -> Conv2d(c4, ne, 1), on lanes of their own as Segment's.
-                # The angle logits land in an f32 map 8 channels wide (zero weights and bias past `ne`): the conv kernels write cout
-                # in 8-channel pieces and the decoder reads 16-byte rows; it passes them in the msk slots with nm = 0
-                self._lane = 2 * len(xs) + i
-                c4 = max(ch[0] // 4, ne)
-                t = self.conv(f"{name}.cv4.{i}.0", x, c4, 3, 1)
-                t = self.conv(f"{name}.cv4.{i}.1", t, c4, 3, 1)
-                msks.append(self.conv(f"{name}.cv4.{i}.2", t, make_divisible(ne, 8), 1, 1, act=False, plain=True, out_f32=True,
-                                      real=(ne, 0)))
+                msks.append(self.conv(f"{name}.cv4.{i}.2", t, wout, 1, 1, act=False, plain=True, out_f32=True, real=(real, 0)))
         self._lane = 0
         self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
         if fused:
@@ -838,18 +819,12 @@ class Plan:
         # a Detect head that takes the decode launch on the fp16 path does so because fuse_head is off: the launch then sums the DFL in
         # the fused epilogue's order (act = 1), so the switch returns the fused plan's bits at three levels as it does at four.  Segment,
         # OBB and the fp32-storage modes have no fused form and keep the order their outputs have always had
-        self.ops.append(dict(kind=L.OP_DECODE, join=1, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=nm, ne=ne, A=A, box=boxes,
-                             act=int(not self.f32_mode and nm == 0 and ne == 0),
-                             cls=clss, msk=msks, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs], lvl_stride=strides,
-                             dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne, 0, 0), out_dtype=self.out_dtype,
-                             name=name + ".decode"))
+        lvl = dict(H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, A=A, box=boxes, cls=clss, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs],
+                   lvl_stride=strides, out_dtype=self.out_dtype)
+        self._emit(L.OP_DECODE, name + ".decode", join=1, nm=nm, ne=ne, msk=msks, act=int(not self.f32_mode and nm == 0 and ne == 0),
+                   dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne, 0, 0), **lvl)
         for i in range(len(xs)):
-            self.ops.append(dict(kind=L.OP_RAW_NCHW, H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, nm=0, A=A,
-                                 box=boxes, cls=clss, msk=[], lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs],
-                                 lvl_stride=strides, level=i,
-                                 dst=T(L.BSY_EXT_BASE + self.ext_raw(i), 0, 0, 64 + nc, 0, 0),
-                                 out_dtype=self.out_dtype, name=f"{name}.raw{i}"))
-        self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
+            self._emit(L.OP_RAW_NCHW, f"{name}.raw{i}", nm=0, msk=[], level=i, dst=T(L.BSY_EXT_BASE + self.ext_raw(i), 0, 0, 64 + nc, 0, 0), **lvl)
 
     # ---- graph walk (nn/tasks.py:138-165 + :940-1105) -----------------------------------------------------------
     def _build(self):
@@ -872,15 +847,15 @@ class Plan:
         for i, (f, n, m, args) in enumerate(layers):
             name = f"model.{i}"
             args = [nc if a == "nc" else a for a in args]
+            arg = lambda j, default: args[j] if len(args) > j else default  # noqa: E731
             n = max(round(n * depth), 1) if n > 1 else n
             if f != -1:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
             if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv"):
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m == "Conv":
-                    k = args[1] if len(args) > 1 else 1
-                    s = args[2] if len(args) > 2 else 1
-                    pad = args[3] if len(args) > 3 and args[3] is not None else k // 2
+                    k, s = arg(1, 1), arg(2, 1)
+                    pad = k // 2 if arg(3, None) is None else args[3]
                     if i == 0:
                         if (k, s, pad) not in ((3, 2, 1), (6, 2, 2)):
                             raise NotImplementedError(f"image conv k={k} s={s} p={pad}: 3x3 s2 p1 or 6x6 s2 p2 only")
@@ -891,40 +866,35 @@ class Plan:
                             raise NotImplementedError(f"Conv with padding {pad} != k // 2 is not accelerated")
                         y = self.conv(name, x, c2, k, s)
                 elif m == "C3":  # block.py:3320-3334; parse_model inserts the repeat count (tasks.py:1038)
-                    xs = x if isinstance(x, list) else x
-                    shortcut = bool(args[1]) if len(args) > 1 else True
-                    x0 = xs[0] if isinstance(xs, list) else xs
+                    x0 = x[0] if isinstance(x, list) else x
                     y = self.alloc(c2, x0.H, x0.W)
-                    self.c3k(name, xs, y, n, shortcut, k=(1, 3))
+                    self.c3k(name, x, y, n, bool(arg(1, True)), k=(1, 3))
                 elif m == "DWConv":  # conv.py:224-229: Conv(c1, c2, k, s, g=gcd(c1, c2))
                     assert isinstance(x, T)
-                    k = args[1] if len(args) > 1 else 1
-                    s = args[2] if len(args) > 2 else 1
+                    k, s = arg(1, 1), arg(2, 1)
                     if c2 != x.C:
                         raise NotImplementedError(f"DWConv {x.C} -> {c2}: only the depthwise case c1 == c2 is accelerated")
                     y = self.dwconv_g(name, x, k, k, s, x.C)
                 elif m == "C3k2":
                     legacy = False
-                    c3k = bool(args[1]) if len(args) > 1 else False
-                    e = args[2] if len(args) > 2 else 0.5
+                    c3k, e = bool(arg(1, False)), arg(2, 0.5)
                     if scale and scale in "mlx":
                         c3k = True
                     y = self.c2f(name, x, c2, n, True, e, "c3k" if c3k else "bottleneck")
                 elif m == "C3k2_gai":  # tasks.py:1038: repeat count inserted, no m/l/x override, `legacy` untouched
-                    c3k = bool(args[1]) if len(args) > 1 else False
-                    e = args[2] if len(args) > 2 else 0.5
+                    c3k, e = bool(arg(1, False)), arg(2, 0.5)
                     y = self.c2f(name, x, c2, n, True, e, "c3k_gai" if c3k else "pmsfa")
                 elif m == "SCDown":
                     assert isinstance(x, T)
                     y = self.scdown(name, x, c2, args[1], args[2])
                 elif m == "C2f":
-                    shortcut = bool(args[1]) if len(args) > 1 else False
+                    shortcut = bool(arg(1, False))
                     y = self.c2f(name, x, c2, n, shortcut, 0.5, "c2f")
                 elif m == "C2":  # the necks of yolov8-p6.yaml / yolov8-seg-p6.yaml
-                    shortcut = bool(args[1]) if len(args) > 1 else True
+                    shortcut = bool(arg(1, True))
                     y = self.c2(name, x, c2, n, shortcut)
                 elif m == "SPPF":
-                    assert isinstance(x, T) and (len(args) < 2 or args[1] == 5)
+                    assert isinstance(x, T) and arg(1, 5) == 5
                     y = self.sppf(name, x, c2)
                 else:
                     assert isinstance(x, T)
@@ -935,11 +905,11 @@ class Plan:
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m in ("RepNCSPELAN4", "ELAN1"):
                     rep = m == "RepNCSPELAN4"
-                    y = self.elan(name, x, c2, args[1], args[2], (args[3] if len(args) > 3 else 1) if rep else 0, rep)
+                    y = self.elan(name, x, c2, args[1], args[2], arg(3, 1) if rep else 0, rep)
                 else:
                     assert isinstance(x, T)
                     if m == "SPPELAN":
-                        if len(args) > 2 and args[2] != 5:
+                        if arg(2, 5) != 5:
                             raise NotImplementedError(f"{name}: SPPELAN with k = {args[2]} (the pool kernel is built for 5)")
                         if args[1] % 8 and not self.f32_mode:
                             raise NotImplementedError(f"{name}: SPPELAN with a hidden width of {args[1]} channels is not on the fp16 path (multiples of 8)")
@@ -983,7 +953,7 @@ class Plan:
                     self.proto(name + ".proto", xs[0], npr, nm)
                     self.detect(name, xs, args[0], legacy, nm=nm)
                 elif m == "OBB":  # head.py:200-227, args [nc, ne] (+ the channel list parse_model appends, tasks.py:1075)
-                    ne = args[1] if len(args) > 1 and not isinstance(args[1], (list, tuple)) else 1
+                    ne = 1 if isinstance(arg(1, 1), (list, tuple)) else arg(1, 1)
                     if ne != 1:
                         raise NotImplementedError(f"OBB with ne = {ne}: dist2rbox (utils/tal.py:404-423) decodes one angle")
                     self.detect(name, xs, args[0], legacy, ne=ne)
@@ -1011,7 +981,7 @@ class Plan:
         if (b["src0"] is not mid or b.get("src1") is not None or b.get("res") is not None or b["ksize"] != 3
                 or b["stride"] != 2 or b["out_f32"] or not b["act"] or a["ksize"] != 3 or a["stride"] != 2):
             return
-        if not stem_supported(mid.C, b["dst"].C, self.H, self.W):
+        if not kernel_takes("stem_fused", mid.C, b["dst"].C, self.H, self.W):
             return
         for o in self.ops[2:]:  # layer 0 must have no other reader
             for key in ("src0", "src1", "res"):
@@ -1019,10 +989,9 @@ class Plan:
                 if t is not None and t.buf == mid.buf:
                     return
         self.buf_bytes[mid.buf] = 16  # never written
-        self.ops[0:2] = [dict(kind=L.OP_STEM, H=self.H, W=self.W, OH=b["OH"], OW=b["OW"], src0=a["src0"], dst=b["dst"],
-                              ksize=3, stride=2, pad=1, act=1, wkey=a["wkey"], wkey2=b["wkey"], mid_c=mid.C,
-                              in_dtype=self.in_dtype, name=a["name"] + "+" + b["name"].split(".")[-1], lane=0,
-                              mfma_flops=a["mfma_flops"] + b["mfma_flops"])]
+        self._emit(L.OP_STEM, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], ksize=3, stride=2, pad=1, act=1,
+                   wkey=a["wkey"], wkey2=b["wkey"], mid_c=mid.C, in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"] + b["mfma_flops"])
+        self.ops[0:2] = [self.ops.pop()]  # (the two layers' flops are counted already)
         self.layer_out[0] = None
 
     # ---- workspace layout -----------------------------------------------------------------------------------------
@@ -1042,6 +1011,13 @@ class Plan:
                     out.append(t.buf)
         return out
 
+    def max_view_elems(self) -> int:
+        """Largest (pixels x row stride) of ONE image over the workspace views the ops name as source, destination or residual: the
+        kernels keep element offsets in 32 bits, so the engine splits a batch when B times this (of the one-image plan) reaches 2^31.
+        A C2f concat buffer is larger than the first conv's output."""
+        views = [o.get(k) for o in self.ops for k in self._VIEW_KEYS]
+        return max([1] + [(t.H // 2) * (t.W // 2) * t.ld if t.up else t.H * t.W * t.ld for t in views if t is not None and t.buf < L.BSY_EXT_BASE])
+
     def buffer_lifetimes(self) -> List[Optional[Tuple[int, int]]]:
         """Per buffer: (first, last) index of the ops that touch it, or None for a buffer no op uses.  Ops on side lanes run
         concurrently with everything between their fork and the next join (csrc/engine.hip bsy_plan_run), so every buffer a
@@ -1056,7 +1032,7 @@ class Plan:
                     life[b][1] = i
         i = 0
         while i < n:
-            if self.ops[i].get("lane", 0) > 0:
+            if self.ops[i]["lane"] > 0:
                 start = i
                 end = n - 1  # the tail join of bsy_plan_run
                 for j in range(i + 1, n):
@@ -1064,7 +1040,7 @@ class Plan:
                         end = j
                         break
                 for j in range(start, end + 1):
-                    if self.ops[j].get("lane", 0) > 0:
+                    if self.ops[j]["lane"] > 0:
                         for b in self.op_buffers(self.ops[j]):
                             life[b][0] = min(life[b][0], start)
                             life[b][1] = max(life[b][1], end)
@@ -1115,10 +1091,16 @@ class Plan:
 
     # ---- serialisation ------------------------------------------------------------------------------------------
     def c_ops(self):
+        def v(t):
+            return L.View(*(t.view() if t is not None else L.NO_VIEW))
+
+        def offsets(key):
+            w = self.wrecs[key]
+            assert w.w_off >= 0, "pack weights before serialising"
+            return w.w_off, w.b_off
+
         arr = (L.Op * len(self.ops))()
         for o, d in zip(arr, self.ops):
-            def v(t):
-                return L.View(*(t.view() if t is not None else L.NO_VIEW))
             o.kind = d["kind"]
             o.B, o.H, o.W, o.OH, o.OW = self.B, d["H"], d["W"], d["OH"], d["OW"]
             o.src0, o.src1 = v(d.get("src0")), v(d.get("src1"))
@@ -1129,21 +1111,16 @@ class Plan:
             o.act, o.out_f32 = d.get("act", 0), d.get("out_f32", 0)
             o.dst_scale, o.dst_dy, o.dst_dx = d.get("dst_scale", 1), d.get("dst_dy", 0), d.get("dst_dx", 0)
             if "wkey" in d:
-                w = self.wrecs[d["wkey"]]
-                assert w.w_off >= 0, "pack weights before serialising"
-                o.w_off, o.b_off = w.w_off, w.b_off
+                o.w_off, o.b_off = offsets(d["wkey"])
             if "wkey2" in d:
-                w = self.wrecs[d["wkey2"]]
-                assert w.w_off >= 0, "pack weights before serialising"
-                o.w2_off, o.b2_off = w.w_off, w.b_off
+                o.w2_off, o.b2_off = offsets(d["wkey2"])
             o.mid_c = d.get("mid_c", 0)
             for j, k in enumerate(d.get("wkeys", [])):
-                w = self.wrecs[k]
-                assert w.w_off >= 0, "pack weights before serialising"
-                o.aux_off[2 * j], o.aux_off[2 * j + 1] = w.w_off, w.b_off
-            if d["kind"] == L.OP_ELA:
+                o.aux_off[2 * j], o.aux_off[2 * j + 1] = offsets(k)
+            if d["kind"] == L.OP_ELA:  # the three sigmoids are known once the weights are packed (WRec.coef).  They stay in the plan's
+                # own op: a side effect of serialising that nothing reads today (the device gets them through `o` below)
                 cf = self.wrecs[d["wkey"]].coef
-                d = dict(d, scale=cf[0], lvl_stride=[cf[1], cf[2]])
+                d["scale"], d["lvl_stride"] = cf[0], [cf[1], cf[2]]
             o.heads, o.key_dim, o.head_dim, o.scale = d.get("heads", 0), d.get("key_dim", 0), d.get("head_dim", 0), \
                 d.get("scale", 0.0)
             o.nl, o.nc, o.nm, o.A = d.get("nl", 0), d.get("nc", 0), d.get("nm", 0), d.get("A", 0)
@@ -1156,7 +1133,7 @@ class Plan:
                 o.lvl_w[j] = d["lvl_w"][j] if j < len(d.get("lvl_w", [])) else 0
                 o.lvl_stride[j] = d["lvl_stride"][j] if j < len(d.get("lvl_stride", [])) else 0.0
             o.in_dtype, o.out_dtype, o.level = d.get("in_dtype", 0), d.get("out_dtype", 0), d.get("level", 0)  # POOL_DOWN: level = mode
-            o.lane, o.join, o.tuned_cfg = d.get("lane", 0), d.get("join", 0), 0
+            o.lane, o.join, o.tuned_cfg = d["lane"], d.get("join", 0), 0
             o.prec = (2 if self.split_f16 else 1) if self.f32_mode else 0
             o.ksplit = d.get("ksplit", 0)
         return arr

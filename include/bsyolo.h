@@ -93,7 +93,7 @@ enum bsy_op_kind {
     BSY_OP_PMSFA_TAIL = 20, /* PMSFA after its conv1, as one launch (block.py:3046-3054; round 4, csrc/pmsfa_fused.hip): src0 = P = conv1's output
                             * [p1 | p2] (C channels), res = the module's input x, dst = conv4(cat(conv3(q1), q2, p2)) + x with
                             * [q1 | q2] = conv2(p1).  aux_off = (weights, bias) byte offsets of conv2 (f32 [25][heads]), conv3 (f32 [49][key_dim])
-                            * and conv4 (packed 1x1); heads / key_dim = row lengths of the two depthwise weight tensors.  C in {32, 64, 128};
+                            * and conv4 (packed 1x1); heads / key_dim = row lengths of the two depthwise weight tensors.  C in {32, 64};
                             * the same bits as the three launches it replaces                                              */
     /* 21: retired (the chained-1x1 launch of round 4, removed); not reused */
     BSY_OP_POOL_DOWN = 22, /* pooling front end of YOLOv9's AConv / ADown (block.py:3692-3723; csrc/pool_down.hip): src0 (H x W, even) -> dst,
@@ -316,6 +316,11 @@ int bsy_ela(const void* x, int ldx, int B, int H, int W, int C, int k, const flo
 int bsy_dwpw_fused(const void* x, int ldx, int B, int H, int W, int C, const float* dww, const float* dwb, const void* w,
                    const float* b, void* y, int ldy, int C2, int act, bsy_stream stream);
 int bsy_dwpw_fused_supported(int C, int C2);
+/* 1 when the fp16 path runs this shape: ATTN's head shape (as bsy_attention), PMSFA_TAIL's width, MSCA_SPATIAL's map.  The host-side
+ * planner (bs_yolo_amd/plan.py) asks these and the *_fused_supported entry points above; it keeps no list of its own. */
+int bsy_attention_supported(int key_dim, int head_dim);
+int bsy_pmsfa_tail_supported(int C);
+int bsy_msca_spatial_supported(int H, int W);
 
 /* DWConv (conv.py:224-229) 3x3 s1: w f32 [9][C], b f32 [C]. */
 int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* b, void* y, int ldy,

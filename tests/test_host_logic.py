@@ -594,6 +594,107 @@ def test_plugin_reads_a_live_reference_model():
     assert len(c1) == len(c2)
 
 
+# ---- plan snapshots: what the planner hands to the device, byte for byte (tools/plan_snapshot.py) ------------------------------
+def _plan_snapshot():
+    sys.path.insert(0, str(ROOT / "tools"))
+    import plan_snapshot
+    return plan_snapshot
+
+
+@pytest.fixture
+def snap(monkeypatch):
+    """tools/plan_snapshot.py, with everything a Plan reads from the environment unset."""
+    S = _plan_snapshot()
+    for k in S.PLAN_ENV:
+        monkeypatch.delenv(k, raising=False)
+    return S
+
+
+def test_plans_are_the_recorded_ones(snap):
+    """Op array, buffer table, weight records (their blob offsets, the blob's length) and both arena layouts of every case of tools/plan_snapshot.py equal the
+    committed digests (tests/golden/plan_snapshots.json): a host-side change of the planner that is meant to leave the device's work
+    alone leaves these alone.  python tools/plan_snapshot.py --dump DIR at two commits shows what moved."""
+    want = json.loads(snap.FIXTURE.read_text())
+    cases = snap.cases()
+    assert sorted(want) == sorted(cid for cid, _, _ in cases) and len(cases) >= 117 + 16
+    got = {cid: snap.snapshot(build, pack)[0] for cid, build, pack in cases}
+    assert not {cid: (got[cid], want[cid]) for cid in want if got[cid] != want[cid]}
+
+
+def test_plan_switches_read_their_environment_variable(snap, monkeypatch):
+    """BSY_FUSE_X=0 (BSY_MERGE_C3K=0) builds the plan of keyword X=False, on graphs where every switch changes something; BSY_LANES
+    forces the head lanes off / on at a size where they are on by default; an unknown switch is a TypeError."""
+    from bs_yolo_amd.plan import SWITCHES
+    assert snap.SWITCH_ENV == SWITCHES  # (the tool keeps a copy of the table so that it also runs on a tree without one)
+    digest = lambda build: snap.snapshot(build, False)[0]["digest"]  # noqa: E731
+    graphs = [(stock_cfg("yolo11", "s"), 2, 64, 96), (stock_cfg("yolo11", "m", 80, "segment"), 2, 64, 96), (stock_cfg("bsyolo11", "s"), 2, 64, 96)]
+    for name, env in snap.SWITCH_ENV.items():
+        moved = 0
+        for g in graphs:
+            on, off = digest(lambda: Plan(*g)), digest(lambda: Plan(*g, **{name: False}))
+            moved += on != off
+            monkeypatch.setenv(env, "0")
+            assert digest(lambda: Plan(*g)) == off, (name, env)
+            assert digest(lambda: Plan(*g, **{name: True})) == on, (name, env)  # the argument wins over the variable
+            monkeypatch.delenv(env)
+        assert moved, f"{name} changes none of the graphs"
+    big = (stock_cfg("yolo11", "s"), 16, 640, 640)
+    lanes = lambda p: sum(1 for o in p.ops if o.get("lane", 0) > 0)  # noqa: E731
+    assert lanes(Plan(*big)) == 14 and lanes(Plan(*big, lanes=False)) == 0
+    assert sum(1 for o in Plan(stock_cfg("yolo11", "s"), 8, 640, 640, latency=True).ops if o.get("ksplit")) == 2
+    for value, kw in (("0", False), ("1", True)):
+        want = digest(lambda: Plan(*big, lanes=kw))
+        monkeypatch.setenv("BSY_LANES", value)
+        assert digest(lambda: Plan(*big)) == want
+        monkeypatch.delenv("BSY_LANES")
+    with pytest.raises(TypeError, match="fuse_stemm"):
+        Plan(*graphs[0], fuse_stemm=False)
+
+
+def test_emitter_refuses_unknown_fields():
+    """c_ops() reads every field with a default, so a misspelt key would serialise as zero: Plan._emit asserts on it instead; it fills
+    the lane and the map sizes itself, and lets only the kinds the engine forks for onto a side lane."""
+    p = Plan(stock_cfg("yolo11", "n"), 1, 64, 64)
+    with pytest.raises(AssertionError, match="strid"):
+        p._emit(L.OP_COPY, "x", src0=p.ops[1]["dst"], dst=p.ops[1]["dst"], strid=2)
+    n, fl = len(p.ops), p.flops
+    with pytest.raises(AssertionError, match="flops"):  # positional: a keyword of that name would be taken for a field
+        p._emit(L.OP_COPY, "x", src0=p.ops[1]["dst"], dst=p.ops[1]["dst"], flops=7)
+    o = p._emit(L.OP_COPY, "x", 7, src0=p.ops[1]["src0"], dst=p.ops[1]["dst"], mfma_flops=0)
+    assert p.ops[n] is o and len(p.ops) == n + 1 and p.flops == fl + 7 and o["lane"] == 0 and "mfma_flops" not in o
+    assert (o["H"], o["W"], o["OH"], o["OW"]) == (p.ops[1]["H"], p.ops[1]["W"], p.ops[1]["OH"], p.ops[1]["OW"])
+    assert all("lane" in o for o in p.ops)
+    p._lane = 1
+    with pytest.raises(AssertionError, match="side lane"):
+        p._emit(L.OP_COPY, "y", src0=p.ops[1]["dst"], dst=p.ops[1]["dst"])
+
+
+def test_max_view_elems_counts_source_destination_and_residual_views():
+    """Plan.max_view_elems (the engine's batch-split threshold): the largest one-image view among src0 / src1 / dst / res, an upsampled
+    source at its stored size; the per-level lists (box / cls / msk, the split-K slabs among them) are not counted."""
+    for cfg, hw in ((stock_cfg("yolo11", "s"), (640, 640)), (stock_cfg("yolov8", "l", 80, "segment"), (96, 64)), (stock_cfg("bsyolo11", "s"), (64, 96))):
+        p = Plan(cfg, 1, *hw)
+        want = 1
+        for o in p.ops:
+            for k in ("src0", "src1", "dst", "res"):
+                t = o.get(k)
+                if t is not None and t.buf < L.BSY_EXT_BASE:
+                    hs, ws = (t.H // 2, t.W // 2) if t.up else (t.H, t.W)
+                    want = max(want, hs * ws * t.ld)
+        assert p.max_view_elems() == want > 1
+
+
+def test_library_says_which_shapes_the_fused_kernels_take():
+    """The planner asks the library (bsy_*_supported), it keeps no list of its own: the three predicates it asks besides the *_fused ones,
+    at the edges the kernels define."""
+    for (kd, hd), ok in {(16, 32): 1, (32, 64): 1, (64, 128): 1, (40, 80): 0, (80, 160): 0, (0, 32): 0, (32, 48): 0}.items():
+        assert L.lib.bsy_attention_supported(kd, hd) == ok, (kd, hd)
+    for c, ok in {32: 1, 64: 1, 48: 0, 128: 0}.items():
+        assert L.lib.bsy_pmsfa_tail_supported(c) == ok, c
+    for (h, w), ok in {(42, 45): 1, (31, 61): 0, (0, 45): 0, (0, 1): 0}.items():  # 1890 px fit LDS, 1891 do not
+        assert L.lib.bsy_msca_spatial_supported(h, w) == ok, (h, w)
+
+
 # ---- build / ISA guards (need hipcc's binutils only, no GPU) ----------------------------------------------------------------
 def test_isa_has_no_packed_f32():
     """The concurrency-hazard mitigation of DESIGN.md section 7, enforced on the SHIPPED code objects: no kernel of
