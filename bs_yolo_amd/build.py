@@ -40,6 +40,8 @@ SOURCES = {
     "nms.hip": ["-ffp-contract=off"],
     "obb.hip": ["-ffp-contract=off"],
     "topk.hip": [],
+    "classify.hip": ["-fno-vectorize"],  # without it the loop vectoriser puts packed f32 arithmetic into classify_tail_kernel<half, streamed>,
+    # which tests/test_host_logic.py::test_isa_has_no_packed_f32 refuses in any kernel of the library (observed: that test failed)
     "letterbox.hip": ["-ffp-contract=off"],
     "masks.hip": ["-ffp-contract=off"],
     "val_match.hip": ["-ffp-contract=off"],

@@ -334,6 +334,10 @@ int val_match_from_iou(const float* iou, const float* det, int row, const int32_
 int launch_nhwc2nchw(const half_t* src, int ld, int B, int C, int hw, void* out, int out_dtype, hipStream_t s);
 int launch_raw_nchw(const float* box, int ldb, const float* cls, int ldc, int B, int h, int w, int nc, void* out,
                     int out_dtype, hipStream_t s);
+// classify.hip: Classify's tail (head.py:300-304) -- row softmax of the f32 logit map, the logits in out_dtype and the k most
+// probable classes, one launch; arguments as bsy_classify_tail's, checked here (the engine's op and the entry point share the bounds)
+int launch_classify_tail(const float* logits, int ld, int B, int nc, void* y, void* x, int out_dtype, int k, int32_t* topk_idx,
+                         float* topk_val, hipStream_t s);
 
 // WHY these exist (round 1): the natural form `fmaf((float)h[j], w[j], a[j])` compiles to
 // v_cvt_f32_f16 (SDWA WORD_1 for the odd elements) feeding SLP-packed v_pk_fma_f32 -- and that sequence returned wrong

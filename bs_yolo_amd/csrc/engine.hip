@@ -258,6 +258,20 @@ struct Resolver {
     float* f(const bsy_view& v) { char* b = base(v); return b ? (float*)b + v.coff : nullptr; }
 };
 
+// Classify's tail (csrc/classify.hip): the logit map is f32 in every precision mode, so both op switches come here.  x and the
+// top-k rows are optional outputs: an unbound slot leaves them out (the rows only together).
+int run_classify_tail(const bsy_op& op, Resolver& R, hipStream_t s) {
+    auto bound = [&](const bsy_view& v) { return v.buf >= BSY_EXT_BASE && v.buf - BSY_EXT_BASE < R.n_ext && R.ext[v.buf - BSY_EXT_BASE]; };
+    const float* logits = R.f(op.src0);
+    void* y = R.base(op.dst);
+    void* x = bound(op.res) ? R.base(op.res) : nullptr;
+    const bool rows = op.ksize > 0 && bound(op.box[0]) && bound(op.cls[0]);
+    int32_t* idx = rows ? (int32_t*)R.base(op.box[0]) : nullptr;
+    float* val = rows ? (float*)R.base(op.cls[0]) : nullptr;
+    if (!R.ok) return BSY_ERR_ARG;
+    return launch_classify_tail(logits, op.src0.ld, op.B, op.nc, y, x, op.out_dtype, rows ? op.ksize : 0, idx, val, s);
+}
+
 // fp32 correctness mode (bsy_op.prec == 1): same op records, f32 views, kernels of ref32.hip.  DECODE and RAW_NCHW consume f32
 // logit maps in both modes and fall through to the common path.
 
@@ -378,6 +392,8 @@ int run_op_f32(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, 
             if (!R.ok) return BSY_ERR_ARG;
             return launch_ela32(a, src, dst, s);
         }
+        case BSY_OP_CLASSIFY_TAIL:
+            return run_classify_tail(op, R, s);
         case BSY_OP_DECODE:
         case BSY_OP_RAW_NCHW:
             handled = false;
@@ -641,6 +657,8 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             if (!R.ok) return BSY_ERR_ARG;
             return launch_nhwc2nchw(src, op.src0.ld, op.B, op.src0.C, op.H * op.W, out, op.out_dtype, s);
         }
+        case BSY_OP_CLASSIFY_TAIL:
+            return run_classify_tail(op, R, s);
         default:
             BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown op kind %d", op.kind);
     }

@@ -1,8 +1,8 @@
-// Building blocks shared by the postprocess units nms.hip, obb.hip, sahi.hip and topk.hip (val_ap.hip and engine.hip take the two
+// Building blocks shared by the postprocess units nms.hip, obb.hip, sahi.hip, topk.hip and classify.hip (val_ap.hip and engine.hip take the two
 // size helpers only).  Everything here is inline: a __global__ lives in exactly one unit (the key sort: nms.hip) and is reached
 // from the others through the host launchers declared at the end.
 //   host:   pow2_at_least, align256, Carver (workspace layout, measured and carved by the same calls), dispatch_dtype
-//   device: block_bitonic_desc, greedy_resolve_256, kept_rank / block_kept_rank, first_max_class, score_key / decode_score_key
+//   device: block_bitonic_desc, greedy_resolve_256, kept_rank / block_kept_rank, first_max_class, score_key / decode_score_key, ord_key
 // What is NOT shared, on purpose: the overlap tests (iou_gt, nmm_matched, has_match64) round differently because each mirrors
 // its own reference; they stay with their units.
 #pragma once
@@ -181,6 +181,15 @@ __device__ __forceinline__ int first_max_class(const T* cp, int A, int nc, float
 
 // fp32 score bits << 32 | ~candidate index: ONE descending sort gives "score descending, ties by ascending index".
 __device__ __forceinline__ u64 score_key(float score, unsigned idx) { return ((u64)__float_as_uint(score) << 32) | (u64)(~idx); }
+
+// float -> unsigned with the same order (NaN above +inf, as torch's topk ranks it; -0 == +0).  Used for ranking only: the rows
+// carry the scores as stored
+__device__ __forceinline__ unsigned ord_key(float f) {
+    unsigned u = __float_as_uint(f);
+    if (f != f) u = 0x7fc00000u;
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 
 // The inverse.  The index is anchor * nc + class with multi_label, else the anchor, whose class is looked up again;
 // pb = the image's prediction (4 + nc + .. rows of A).

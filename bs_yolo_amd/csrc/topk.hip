@@ -20,15 +20,6 @@
 #define TOPK_MAX_AN (1LL << 30)  // bound on A * nc
 #define TOPK_U 8  // keys a thread loads before it uses the first: the passes are bound by L2 latency, not bandwidth
 
-// float -> unsigned with the same order (NaN above +inf, as torch's topk ranks it; -0 == +0).  Used for ranking only: the rows
-// carry the scores as stored
-__device__ __forceinline__ unsigned ord_key(float f) {
-    unsigned u = __float_as_uint(f);
-    if (f != f) u = 0x7fc00000u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 struct TopkK {
     const void* pred;  // (B, 4 + nc, A)
     int B, nc, A, K;

@@ -4,6 +4,11 @@
 (nn/autobackend.py:524: ``self.model(im, augment=, visualize=, embed=)`` -> ``(y, x_list)``, head.py:74), with
 ``im`` a contiguous BCHW fp16/fp32 tensor on the engine's device.  PyTorch is only used for device memory and
 the current stream; all compute goes through libbsyolo_hip.so.
+
+An engine built from a classification graph (a `Classify` head) returns what Classify.forward returns in eval (head.py:304): ``(y, x)``,
+the softmax and the logits, (B, nc) each in the input's dtype.  The top-min(nc, 5) classes of the same launch -- what the reference's
+predictor and validator take with an argsort -- are kept as ``engine.last_topk = (idx int32, val f32)``, (B, k) device rows of the
+LAST forward (in graph mode they belong to the ring slot of that forward, like y).
 """
 from __future__ import annotations
 
@@ -112,6 +117,8 @@ class YoloEngine:
         self.nl = len(self.meta["levels"])  # detection levels: 3, or 4 on the P2 / P6 graphs
         self.max_stride = int(max(self.meta["strides"]))  # inputs are multiples of it: 32, 64 on a P6 graph
         self.names = {i: f"{i}" for i in range(self.nc)}
+        self.task = self.meta.get("task", "detect")  # "classify": forward returns (y, x), see the module docstring
+        self.last_topk: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
 
     def load_weights(self, state_dict: Mapping[str, torch.Tensor], bn_eps: float = BN_EPS) -> None:
         """Replace the engine's weights in place (same graph, new values: an EMA update, a fine-tuned checkpoint).  Plans, tuning and
@@ -252,6 +259,13 @@ class YoloEngine:
         if B > 1 and B * big >= (1 << 31) - (1 << 24):
             n_chunks = -(-B * big // ((1 << 31) - (1 << 24)))
             step = -(-B // n_chunks)
+            if self.task == "classify":
+                outs, tops = [], []
+                for i in range(0, B, step):
+                    outs.append(self.forward(im[i:i + step], want_raw))
+                    tops.append(self.last_topk)
+                self.last_topk = (torch.cat([t[0] for t in tops]), torch.cat([t[1] for t in tops]))
+                return torch.cat([o[0] for o in outs]), (torch.cat([o[1] for o in outs]) if want_raw else None)
             outs = [self.forward(im[i:i + step], want_raw) for i in range(0, B, step)]
             y = torch.cat([o[0] for o in outs])
             nl = self.nl
@@ -268,6 +282,8 @@ class YoloEngine:
     def _forward_one(self, im, want_raw, B, H, W):
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
         m = plan.meta
+        if self.task == "classify":
+            return self._forward_classify(plan, h, im, want_raw, B, H, W)
 
         def outputs():
             y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
@@ -280,15 +296,44 @@ class YoloEngine:
                 proto = torch.empty((B, m["nm"], ph, pw), dtype=im.dtype, device=self.device)
             return y, raws, proto
 
-        if self.graph:  # outputs from this shape's ring: the captured graphs hold their addresses
-            ring = self._rings.setdefault(((B, H, W, im.dtype, im.dtype), bool(want_raw)), {"i": 0, "slots": []})
-            if len(ring["slots"]) < self.graph_ring:
-                ring["slots"].append(outputs())
-            y, raws, proto = ring["slots"][ring["i"] % len(ring["slots"])]
-            ring["i"] += 1
-        else:
-            y, raws, proto = outputs()
+        y, raws, proto = self._output_set(outputs, im, want_raw)
         ext, n = self._ext(im, y, raws, proto)
+        self._run(plan, h, ext, n, im, B, H, W)
+        if m["nm"]:  # Segment.forward (head.py:197): (cat(y, mc), (raw, mc, proto)); y already carries the mc rows
+            return y, (raws, y[:, 4 + m["nc"]:], proto)
+        if m["ne"]:  # OBB.forward (head.py:223): (cat(y, angle), (raw, angle)); y already carries the angle row
+            return y, (raws, y[:, 4 + m["nc"]:])
+        return y, raws
+
+    def _output_set(self, make, im, want_raw):
+        """The output tensors of one forward: fresh ones (make()), or in graph mode the next set of this shape's ring -- the captured
+        graphs hold their addresses."""
+        if not self.graph:
+            return make()
+        B, _, H, W = im.shape
+        ring = self._rings.setdefault(((B, H, W, im.dtype, im.dtype), bool(want_raw)), {"i": 0, "slots": []})
+        if len(ring["slots"]) < self.graph_ring:
+            ring["slots"].append(make())
+        ring["i"] += 1
+        return ring["slots"][(ring["i"] - 1) % len(ring["slots"])]
+
+    def _forward_classify(self, plan, h, im, want_raw, B, H, W):
+        """Slots (Plan.EXT_*): 0 image, 1 y, 2 x, 3 / 4 the top-k index / value rows.  want_raw=False leaves x unbound (None returned)."""
+        nc, k = plan.meta["nc"], plan.meta["topk"]
+
+        def outputs():
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
+            return (new((B, nc), im.dtype), new((B, nc), im.dtype) if want_raw else None, new((B, k), torch.int32), new((B, k), torch.float32))
+
+        y, x, idx, val = self._output_set(outputs, im, want_raw)
+        ptrs = [im.data_ptr(), y.data_ptr(), x.data_ptr() if x is not None else None, idx.data_ptr(), val.data_ptr()]
+        self._run(plan, h, (C.c_void_p * len(ptrs))(*ptrs), len(ptrs), im, B, H, W)
+        self.last_topk = (idx, val)
+        return y, x
+
+    def _run(self, plan, h, ext, n, im, B, H, W):
+        """One forward of `plan` on the current stream with the external slots `ext`: ordered behind the previous forward, autotuned
+        on the first call of a shape, replayed as a graph in graph mode."""
         cur_stream = torch.cuda.current_stream(self.device)
         stream = cur_stream.cuda_stream
         if self._last_done is not None and self._last_stream != stream:
@@ -327,11 +372,6 @@ class YoloEngine:
             self._last_done = torch.cuda.Event()
         self._last_done.record(cur_stream)
         self._last_stream = stream
-        if m["nm"]:  # Segment.forward (head.py:197): (cat(y, mc), (raw, mc, proto)); y already carries the mc rows
-            return y, (raws, y[:, 4 + m["nc"]:], proto)
-        if m["ne"]:  # OBB.forward (head.py:223): (cat(y, angle), (raw, angle)); y already carries the angle row
-            return y, (raws, y[:, 4 + m["nc"]:])
-        return y, raws
 
     def tuning(self, B, H, W, dtype=torch.float16):
         plan, h = self.plan_for(B, H, W, dtype, dtype)
@@ -357,9 +397,10 @@ class YoloEngine:
     def forward_augment(self, im: torch.Tensor):
         """DetectionModel._predict_augment (nn/tasks.py:354-370) -> (y, None): three forwards at the scaled sizes, the scaled inputs
         made by bsy_scale_img, the passes clipped / descaled / concatenated by ONE bsy_tta_merge on the current stream.  A Segment
-        graph (and an OBB one) returns its single-scale forward, as the reference reverts for every class but DetectionModel (:356-358)."""
+        graph (an OBB one, a classification one) returns its single-scale forward, as the reference reverts for every class but
+        DetectionModel (:356-358)."""
         with self._lock:
-            if self.meta["nm"] or self.meta["ne"]:
+            if self.meta["nm"] or self.meta["ne"] or self.task == "classify":
                 return self.forward(im)
             if im.device != self.device:
                 raise ValueError(f"input on {im.device}, engine on {self.device}")
@@ -405,8 +446,13 @@ class YoloEngine:
         B, _, H, W = im.shape
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
         m = plan.meta
-        y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
-        ext, n = self._ext(im, y, [None] * len(m["levels"]))
+        if self.task == "classify":
+            y, x = (torch.empty((B, m["nc"]), dtype=im.dtype, device=self.device) for _ in range(2))
+            idx, val = (torch.empty((B, m["topk"]), dtype=dt, device=self.device) for dt in (torch.int32, torch.float32))
+            ext, n = (C.c_void_p * 5)(im.data_ptr(), y.data_ptr(), x.data_ptr(), idx.data_ptr(), val.data_ptr()), 5
+        else:
+            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
+            ext, n = self._ext(im, y, [None] * len(m["levels"]))
         ms = (C.c_float * len(plan.ops))()
         L.check(L.lib.bsy_plan_profile(h, ext, n, L.stream_ptr(self.device), ms))
         return [(o["name"], o["kind"], float(t)) for o, t in zip(plan.ops, ms)], plan

@@ -4,7 +4,8 @@ The reference ships these graphs as cfg/models/11/yolo11-seg.yaml:15-47 (stock Y
 cfg/models/v8/yolov8-seg.yaml:15-46, cfg/models/v5/yolov5.yaml:14-50, cfg/models/11/yolo11.yaml:15-52 (the modified BS-YOLO
 graph, family "bsyolo11") and the four-level variants cfg/models/v8/yolov8-p2.yaml, v8/yolov8-p6.yaml (+ yolov8-seg-p6.yaml) and
 v5/yolov5-p6.yaml (families "yolov8-p2", "yolov8-p6", "yolov5-p6"), and the YOLOv9 (GELAN) graphs cfg/models/v9/yolov9{t,s,m,c}.yaml and
-yolov9c-seg.yaml (family "yolov9": literal widths per size, no scales table).  They are
+yolov9c-seg.yaml (family "yolov9": literal widths per size, no scales table), and the classification graphs
+cfg/models/11/yolo11-cls.yaml:8-30 and v8/yolov8-cls.yaml:8-29 (task "classify" of the families "yolo11" and "yolov8").  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -191,13 +192,44 @@ def _yolov9(size: str) -> dict:
     }
 
 
+# Classification graphs: backbones and scales tables of their own, one Classify layer as the head.  cfg/models/11/yolo11-cls.yaml:8-30:
+# the detect backbone without SPPF, and C2PSA reaches max_channels at m / l / x (512, where detect's table says the same)
+_YOLO11_CLS = {
+    "scales": {"n": [0.50, 0.25, 1024], "s": [0.50, 0.50, 1024], "m": [0.50, 1.00, 512], "l": [1.00, 1.00, 512],
+               "x": [1.00, 1.50, 512]},
+    "backbone": [
+        [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "Conv", [128, 3, 2]], [-1, 2, "C3k2", [256, False, 0.25]],
+        [-1, 1, "Conv", [256, 3, 2]], [-1, 2, "C3k2", [512, False, 0.25]], [-1, 1, "Conv", [512, 3, 2]],
+        [-1, 2, "C3k2", [512, True]], [-1, 1, "Conv", [1024, 3, 2]], [-1, 2, "C3k2", [1024, True]],
+        [-1, 2, "C2PSA", [1024]],
+    ],
+}
+
+# cfg/models/v8/yolov8-cls.yaml:8-29: no SPPF, and every scale's max_channels is 1024 (detect's m / l / x: 768 / 512 / 512)
+_YOLOV8_CLS = {
+    "scales": {"n": [0.33, 0.25, 1024], "s": [0.33, 0.50, 1024], "m": [0.67, 0.75, 1024], "l": [1.00, 1.00, 1024],
+               "x": [1.00, 1.25, 1024]},
+    "backbone": [
+        [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "Conv", [128, 3, 2]], [-1, 3, "C2f", [128, True]],
+        [-1, 1, "Conv", [256, 3, 2]], [-1, 6, "C2f", [256, True]], [-1, 1, "Conv", [512, 3, 2]],
+        [-1, 6, "C2f", [512, True]], [-1, 1, "Conv", [1024, 3, 2]], [-1, 3, "C2f", [1024, True]],
+    ],
+}
+
+_CLS_FAMILIES = {"yolo11": _YOLO11_CLS, "yolov8": _YOLOV8_CLS}
 _FAMILIES = {"yolo11": _YOLO11, "yolov8": _YOLOV8, "bsyolo11": _BSYOLO11, "yolov5": _YOLOV5,
              "yolov8-p2": _YOLOV8_P2, "yolov8-p6": _YOLOV8_P6, "yolov5-p6": _YOLOV5_P6}
 
 
 def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str = "detect") -> dict:
     """e.g. stock_cfg("yolo11", "s") == what the reference builds for 'yolo11s.yaml' upstream; stock_cfg("yolov9", "c", task="segment")
-    == 'yolov9c-seg.yaml' (family "yolov9": scale is one of t / s / m / c, segment exists for c only; the dict has no `scales`)."""
+    == 'yolov9c-seg.yaml' (family "yolov9": scale is one of t / s / m / c, segment exists for c only; the dict has no `scales`);
+    stock_cfg("yolo11", "n", 1000, "classify") == 'yolo11n-cls.yaml' (families "yolo11" and "yolov8" only)."""
+    if task == "classify":
+        if family not in _CLS_FAMILIES:
+            raise ValueError(f"{family}: no classification graph (yolo11, yolov8)")
+        fam = copy.deepcopy(_CLS_FAMILIES[family])
+        return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"], "head": [[-1, 1, "Classify", ["nc"]]]}
     if family == "yolov9":
         if scale not in _V9_SIZES or task not in ("detect", "segment") or (task == "segment" and scale != "c"):
             raise ValueError(f"yolov9: scale {scale!r} / task {task!r} (detect: t, s, m, c; segment: c)")

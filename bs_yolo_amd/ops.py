@@ -349,3 +349,22 @@ def end2end_topk(pred: torch.Tensor, max_det: int = 300, out: Optional[torch.Ten
     L.check(L.lib.bsy_end2end_topk(_p(pred), L.dtype_code(pred.dtype), B, nc, A, int(max_det), _p(out), _p(workspace),
                                    workspace.numel() * workspace.element_size(), _stream(pred)))
     return out
+
+
+def classify_tail(logits: torch.Tensor, nc: int, k: int = 0, out_dtype: torch.dtype = torch.float32):
+    """Classify's tail (nn/modules/head.py:300-304) in one launch (bsy_classify_tail): logits (B, ld) fp32 on the device, ld a multiple
+    of 4 and >= nc, rows 16-byte aligned -> (y, x, idx, val): y = softmax(logits[:, :nc]) and x = logits[:, :nc], (B, nc) each in
+    out_dtype; idx (int32) / val (fp32), (B, k): the k most probable classes by the STORED y, descending, ties to the lower class
+    (a stable descending sort of y) -- None, None with k = 0.  Columns past nc are never read.  No host synchronisation."""
+    if not logits.is_cuda:
+        raise RuntimeError("bs_yolo_amd.ops.classify_tail needs a GPU tensor (no CPU fallback)")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous (B, ld) fp32 tensor")
+    B, ld = logits.shape
+    y = torch.empty((B, nc), dtype=out_dtype, device=logits.device)
+    x = torch.empty((B, nc), dtype=out_dtype, device=logits.device)
+    idx = torch.empty((B, k), dtype=torch.int32, device=logits.device) if k else None
+    val = torch.empty((B, k), dtype=torch.float32, device=logits.device) if k else None
+    L.check(L.lib.bsy_classify_tail(_p(logits), ld, B, int(nc), _p(y), _p(x), L.dtype_code(out_dtype), int(k),
+                                    _p(idx) if k else None, _p(val) if k else None, _stream(logits)))
+    return y, x, idx, val

@@ -135,6 +135,7 @@ class Plan:
     EXT_IMG, EXT_Y, EXT_RAW0 = 0, 1, 2  # external slots: image, prediction, raw level maps (2,3,4), proto (5)
     EXT_PROTO = 5
     EXT_RAW3 = 6  # the fourth level's raw map (P2 / P6 heads): behind the proto slot, so that slots 0-5 stay what they were
+    EXT_LOGITS, EXT_TOPK_IDX, EXT_TOPK_VAL = 2, 3, 4  # a classify plan's slots behind image and y: x (the logits), the top-k rows
 
     @classmethod
     def ext_raw(cls, level: int) -> int:
@@ -826,6 +827,26 @@ class Plan:
         for i in range(len(xs)):
             self._emit(L.OP_RAW_NCHW, f"{name}.raw{i}", nm=0, msk=[], level=i, dst=T(L.BSY_EXT_BASE + self.ext_raw(i), 0, 0, 64 + nc, 0, 0), **lvl)
 
+    def classify(self, name: str, x: T, nc: int):
+        """head.py:282-304 Classify in eval: (y, x) = (softmax(x), x), x = linear(pool(conv(x)).flatten(1)); Dropout(p = 0) is the
+        identity.  conv is an ordinary 1x1 Conv (BN folded, SiLU); the global mean is OP_GAP; linear is a plain 1x1 conv on the
+        (B, 1, 1, 1280) map writing f32 logits (a class count that is no multiple of 8 on the next one, zero weights and bias in the
+        padding, as the OBB angle branch does); OP_CLASSIFY_TAIL turns the logits into y, x and the top-k rows (csrc/classify.hip)."""
+        assert not x.up
+        t = self.conv(name + ".conv", x, 1280, 1, 1)
+        g = self.alloc(1280, 1, 1)
+        self._emit(L.OP_GAP, name + ".pool", src0=t, dst=g)
+        ncp = make_divisible(nc, 8)
+        lg = self.conv(name + ".linear", g, ncp, 1, 1, act=False, plain=True, out_f32=True, real=(nc if ncp != nc else 0, 0))
+        k = min(nc, 5)  # what the predictor and the validator rank (classify/predict.py:51-60, val.py:56-60)
+        ext = lambda slot, c: T(L.BSY_EXT_BASE + slot, 0, 0, c, 0, 0)  # noqa: E731
+        self._emit(L.OP_CLASSIFY_TAIL, name + ".tail", src0=lg, dst=ext(self.EXT_Y, nc), res=ext(self.EXT_LOGITS, nc), nc=nc, ksize=k,
+                   box=[ext(self.EXT_TOPK_IDX, k)], cls=[ext(self.EXT_TOPK_VAL, k)], out_dtype=self.out_dtype, OH=0, OW=0)
+        # strides: the engine's size multiple (the backbone halves the map five times); ClassificationModel.stride itself is 1
+        # (tasks.py:457).  No anchors, levels or raw maps: the engine's readers of A / levels / no see an empty head
+        self.meta.update(task="classify", nc=nc, nm=0, ne=0, A=0, no=0, strides=[32.0], levels=[], topk=k)
+        self.pooled = g  # the (B, 1, 1, 1280) mean, for tests that read it back (YoloEngine.read_view)
+
     # ---- graph walk (nn/tasks.py:138-165 + :940-1105) -----------------------------------------------------------
     def _build(self):
         d = self.cfg
@@ -959,6 +980,16 @@ class Plan:
                     self.detect(name, xs, args[0], legacy, ne=ne)
                 else:
                     self.detect(name, xs, args[0], legacy)
+                y, cout = None, 0
+            elif m == "Classify":  # head.py:282-304, args [nc, k, s, p, g] (tasks.py:1016-1023 puts c1 in front)
+                if not isinstance(x, T):
+                    raise NotImplementedError(f"{name}: Classify fed by {len(x)} tensors (its torch.cat, head.py:298) is not accelerated")
+                if i != len(layers) - 1:
+                    raise NotImplementedError(f"{name}: Classify is accelerated as the last layer only")
+                if (arg(1, 1), arg(2, 1), arg(3, None), arg(4, 1)) != (1, 1, None, 1):
+                    raise NotImplementedError(f"{name}: Classify with k, s, p, g = {args[1:5]} (the default 1x1 conv is accelerated)")
+                # tasks.py:1019-1020: an output width that is not the class count is scaled like any other
+                self.classify(name, x, args[0] if args[0] == nc else make_divisible(min(args[0], max_ch) * width, 8))
                 y, cout = None, 0
             else:
                 raise NotImplementedError(f"module {m} is not on the accelerated path")

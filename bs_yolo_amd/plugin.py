@@ -7,7 +7,9 @@ Three hooks, each using an extension point the reference already has (see INTEGR
                            (nn/autobackend.py:136-147, call at :524) reaches the engine.  The graph comes from
                            ``model.yaml`` (the dict parse_model consumed, nn/tasks.py:313-321) and the weights from
                            ``model.state_dict()``.  ``augment=True`` on a ``DetectionModel`` runs the engine's test-time
-                           augmentation (tasks.py:354-370; ``tta="reference"`` opts out).  Anything else the engine does not cover
+                           augmentation (tasks.py:354-370; ``tta="reference"`` opts out).  A ``ClassificationModel``
+                           (tasks.py:439-490, a ``Classify`` head) returns ``(y, x)`` as Classify.forward does in eval (head.py:304).
+                           Anything else the engine does not cover
                            (training mode, visualize / embed / profile (tasks.py:137-164), augment on other model classes, CPU
                            tensors, unsupported modules) goes to the original forward.
   install(model)           per-module hook (the fallback level for graphs `accelerate` does not cover: a custom block, an
@@ -26,7 +28,8 @@ Three hooks, each using an extension point the reference already has (see INTEGR
   install_masks(ops_module) same for ``ultralytics.utils.ops.process_mask`` (models/yolo/segment/predict.py:53).
   install_val_metrics(v)   rebinds ``_process_batch`` on a Detection / Segmentation / OBB validator instance
                            (models/yolo/detect/val.py:209-228, segment/val.py:173-217, obb/val.py:53-80): true-positive matching
-                           on box IoU, mask IoU or probiou on the device.
+                           on box IoU, mask IoU or probiou on the device.  On a ClassificationValidator it rebinds ``update_metrics``
+                           (classify/val.py:56-60): the top-5 rows come from the forward's own launch, not from an argsort.
   install_preprocess(p)    rebinds ``BasePredictor.preprocess`` (engine/predictor.py:116-134) on a predictor instance so
                            lists of HWC BGR uint8 images are letterboxed on the device.
 """
@@ -43,7 +46,7 @@ from .engine import YoloEngine
 from .plan import Plan
 from .weights import BN_EPS, repconv_form
 
-SUPPORTED_HEADS = ("Detect", "Segment", "OBB")
+SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify")
 
 
 def _on_device(t) -> bool:
@@ -124,6 +127,13 @@ def max_stride(cfg: dict) -> int:
     return gs
 
 
+def _head_exports(model) -> bool:
+    """Whether the last layer of a reference model (BaseModel.model, an nn.Sequential) has its `export` flag set."""
+    seq = getattr(model, "model", None)
+    kids = list(seq.children()) if isinstance(seq, torch.nn.Module) else []
+    return bool(kids and getattr(kids[-1], "export", False))
+
+
 FP32_MODES = {"engine_fp32x": "fp32x", "engine_fp32": "fp32", "engine": "fp16", "reference": None}
 
 
@@ -156,6 +166,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     cfg = cfg_of(model)
     support, gs = _graph_facts(cfg)  # gs: a P6 graph takes multiples of 64; anything else goes to the reference forward, as non-multiples of 32 do
     orig_forward = model.forward
+    classify = cfg["head"][-1][2] == "Classify"
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
              "tta_calls": 0, "support": support, "failed": set(), "repconv": None}
     fp32_mode = fp32_inputs or os.environ.get("BSY_FP32_INPUTS", "engine_fp32x")
@@ -201,6 +212,9 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
                 state["fallbacks"] += 1
                 return orig_forward(x, *args, **kwargs)
             visualize = embed = profile = False
+        if classify and _head_exports(self):  # Classify.export (head.py:285, :304): y alone, the exporter's business
+            state["fallbacks"] += 1
+            return orig_forward(x, *args, **kwargs)
         if (self.training or visualize or embed or profile or args or not isinstance(x, torch.Tensor)
                 or not _on_device(x) or x.dim() != 4 or x.dtype not in (torch.float16, torch.float32)
                 or x.shape[1] != 3 or x.shape[2] % gs or x.shape[3] % gs or x.shape[0] == 0):
@@ -233,6 +247,11 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
         state["fp32_calls" if want32 else "engine_calls"] += 1
         if augment:
             state["tta_calls"] += 1
+        eng = state["engine32" if want32 else "engine"]
+        if eng.task == "classify":
+            # the top-k index rows of the same launch travel with y: ClassificationValidator.postprocess hands preds[0] on as it is
+            # (classify/val.py:96-98), and install_val_metrics' update_metrics takes them instead of an argsort
+            y._bsy_topk = eng.last_topk[0]
         return y, raws
 
     model.forward = types.MethodType(forward, model)
@@ -666,12 +685,17 @@ def install_masks(ops_module):
 
 
 def install_val_metrics(validator):
-    """validator = a DetectionValidator, SegmentationValidator or OBBValidator instance: its per-image `_process_batch`
+    """validator = a ClassificationValidator: see _install_classify_metrics.  Else
+    validator = a DetectionValidator, SegmentationValidator or OBBValidator instance: its per-image `_process_batch`
     (models/yolo/detect/val.py:209-228, segment/val.py:173-217, obb/val.py:53-80: an IoU matrix + match_predictions, numpy on the
     host in the reference) goes to the device kernels for CUDA detections.  The rebound method takes the segment validator's full
     signature and dispatches on the CALL, not on the class: masks=True -> mask IoU; 5-column labels (xywhr) -> probiou; everything
     else -> box IoU.  CPU tensors and more than 1024 detections go to the original method with the arguments they came with."""
     from . import val as _val
+    if type(validator).__name__ == "ClassificationValidator":
+        return _install_classify_metrics(validator)
+    if not hasattr(validator, "_process_batch"):
+        raise TypeError(f"install_val_metrics: {type(validator).__name__} is neither a ClassificationValidator nor a validator with _process_batch")
     orig = validator._process_batch
 
     def _process_batch(self, detections, gt_bboxes, gt_cls, pred_masks=None, gt_masks=None, overlap=False, masks=False):
@@ -686,6 +710,27 @@ def install_val_metrics(validator):
         return _val.process_batch(detections, gt_bboxes, gt_cls, self.iouv)
 
     validator._process_batch = types.MethodType(_process_batch, validator)
+    return validator
+
+
+def _install_classify_metrics(validator):
+    """validator = a ClassificationValidator instance (it has no `_process_batch`): `update_metrics(preds, batch)`
+    (models/yolo/classify/val.py:56-60) appends preds.argsort(1, descending=True)[:, :min(nc, 5)] as int32 on the CPU.  For the y of an
+    accelerated ClassificationModel -- a device tensor that carries the top-min(nc, 5) index rows bsy_classify_tail wrote in the same
+    launch (accelerate's forward attaches them) -- those rows are appended instead: the same classes wherever the stored
+    probabilities differ, the lower class first where they are equal (argsort leaves that order unspecified).  Any other `preds` (a CPU
+    tensor, a device tensor of another model) goes to the original method.  The targets are handled as the reference does."""
+    orig = validator.update_metrics
+
+    def update_metrics(self, preds, batch):
+        rows = getattr(preds, "_bsy_topk", None)
+        n5 = min(len(self.names), 5)
+        if not (isinstance(preds, torch.Tensor) and _on_device(preds)) or rows is None or tuple(rows.shape) != (preds.shape[0], n5):
+            return orig(preds, batch)
+        self.pred.append(rows.type(torch.int32).cpu())
+        self.targets.append(batch["cls"].type(torch.int32).cpu())
+
+    validator.update_metrics = types.MethodType(update_metrics, validator)
     return validator
 
 

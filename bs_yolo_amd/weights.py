@@ -114,6 +114,8 @@ def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f3
         return torch.cat([wsp.reshape(-1), wch.reshape(-1), gw, gb]).contiguous().numpy().tobytes(), b""
     if r.kind in ("plain", "dwg_plain"):
         w, b = _f32(sd[r.name + ".weight"]), _f32(sd[r.name + ".bias"])
+        if w.dim() == 2:  # nn.Linear (Classify.linear, head.py:294): a 1x1 conv on the (B, 1, 1, cin) map
+            w = w[:, :, None, None]
     elif r.kind == "deconv":
         # nn.ConvTranspose2d(c, c, 2, 2, 0) (block.py:91): out[2i+dy, 2j+dx] = W[:, :, dy, dx]^T x[i, j] + b, i.e. one
         # 1x1 conv per output phase; weight layout (cin, cout, 2, 2)

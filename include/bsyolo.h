@@ -100,7 +100,11 @@ enum bsy_op_kind {
                             * f16 views (f32 in the fp32-storage modes).  `level` carries the MODE (the field is otherwise RAW_NCHW's):
                             * 0: dst (H x W) = avg_pool2d(src0, 2, 1) in rows / columns 0 .. H-2 / W-2, its last row and column ZERO;
                             * 1: dst (H/2 x W/2) = max_pool2d(avg_pool2d(src0, 2, 1), 3, 2, 1)                             */
-    BSY_OP_ELA = 15        /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
+    BSY_OP_CLASSIFY_TAIL = 23, /* Classify's tail (head.py:300-304; csrc/classify.hip, bsy_classify_tail): src0 = the f32 logit map (B, 1, 1, ld)
+                            * the linear conv wrote (every precision mode), nc = classes, dst = y = softmax (external slot, (B, nc)), res = x = the
+                            * logits (external slot, optional), ksize = k, box[0] / cls[0] = the top-k index (int32) / value (f32) rows
+                            * (external slots, (B, k); optional: skipped together when either is unbound), out_dtype = dtype of y and x */
+    BSY_OP_ELA = 15       /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
                             * res = f32 scratch buffer of (2 (H + W) + 2) * C floats per image                          */
@@ -148,7 +152,7 @@ typedef struct bsy_op {
     int64_t aux_off[18];    /* MSCA_SPATIAL: (weights, bias) byte offsets of its nine depthwise convs */
     int32_t prec;           /* 0: the fp16-storage product path.  1: fp32 correctness mode -- every workspace view is NHWC f32,
                              * dense conv weights are f32 [k*k*Cin][Cout], arithmetic is fp32 (csrc/ref32.hip); kinds CONV_FIRST,
-                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ELA, POOL_DOWN.
+                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ELA, POOL_DOWN, CLASSIFY_TAIL.
                              * 2: fp32x mode -- storage and every non-conv kernel as in mode 1; dense convs (CONV) multiply on the
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
@@ -428,6 +432,25 @@ int bsy_obb_scale(float* det, const int32_t* counts, int B, int max_det, int row
 size_t bsy_end2end_topk_workspace_bytes(int B, int A, int nc, int max_det);
 int bsy_end2end_topk(const void* pred, int pred_dtype, int B, int nc, int A, int max_det, float* out, void* workspace,
                      size_t workspace_bytes, bsy_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Classify's tail (nn/modules/head.py:300-304) and the ranking ClassificationPredictor / ClassificationValidator take of it
+ * (models/yolo/classify/predict.py:51-60, val.py:56-60: preds.argsort(1, descending=True)[:, :5]), whole batch in ONE launch, one
+ * workgroup per image, no host sync, no allocation, no float atomics (csrc/classify.hip): safe inside a captured graph.
+ *   logits    : (B, ld) f32, 16-byte aligned, ld a multiple of 4 and >= nc; columns nc .. ld are never read into a result.
+ *   y         : (B, nc) out_dtype (BSY_F16 / BSY_F32), contiguous: softmax(logits[:, :nc]) in fp32 with the row maximum
+ *               subtracted (a row of equal logits gives 1 / nc; +-80 does not overflow), rounded once to out_dtype.
+ *   x         : (B, nc) out_dtype, contiguous: the logits in out_dtype.  May be NULL.
+ *   topk_*    : (B, k) each: the k largest STORED probabilities of each row (y as rounded to out_dtype), descending, as class
+ *               index (int32) and value (f32).  Both NULL with k = 0.
+ *   Ties      : to the lower class index -- a stable descending sort of y.  NaN ranks above +inf, as in bsy_end2end_topk.
+ *   Bounds    : 1 <= nc <= 65536, 0 <= k <= min(nc, 16), 1 <= B <= 65535, pointers non-null and aligned to their element (logits
+ *               to 16 bytes); anything else is BSY_ERR_ARG before any launch.
+ * A row of up to 32768 classes stays in LDS (rows past 64 KiB set the kernel's dynamic-LDS attribute on the current device); a longer one
+ * is streamed from memory three times.  The same arithmetic either way.
+ * --------------------------------------------------------------------------------------------------------- */
+int bsy_classify_tail(const float* logits, int ld, int B, int nc, void* y, void* x, int out_dtype, int k, int32_t* topk_idx,
+                      float* topk_val, bsy_stream stream);
 
 /* scale_boxes + clip_boxes (utils/ops.py:92-127, :319-337) applied to all rows of `out` in place:
  * per image b: gain[b], pad_x[b], pad_y[b] (HOST-computed with Python round()), orig shape (h0[b], w0[b]). */
