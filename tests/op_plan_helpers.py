@@ -1,9 +1,10 @@
-"""Shared pieces of the one-op plan tests (test_glue_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every
+"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every
 tensor bound as an external slot, poisoned views and a weight-blob builder.  Not a test module."""
 import ctypes as C
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 DEV = "cuda:0"
 NAN = float("nan")
@@ -86,6 +87,89 @@ def weights_blob(arrays):
         offs.append(len(blob))
         blob += np.ascontiguousarray(a).tobytes()
     return blob, offs
+
+
+_NAN_PAD = np.full(128, np.nan, np.float32).tobytes()  # 512 bytes; an f32 NaN read as two f16 is (0, NaN)
+
+
+def poisoned_blob(arrays):
+    """weights_blob with NaN instead of zeros between the records: every record is followed by 256 to 511 bytes of NaN, so a read
+    past a record's end -- or in front of the next one -- reaches the output.  -> (bytes, [offset of each])."""
+    blob, offs = b"", []
+    for a in arrays:
+        offs.append(len(blob))
+        blob += np.ascontiguousarray(a).tobytes()
+        blob += _NAN_PAD[:4 * ((-len(blob) % 256) // 4 + 64)]
+        assert len(blob) % 256 == 0, "records are whole 4-byte words"
+    return blob, offs
+
+
+def nhwc(x):
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+def nchw(x):
+    return x.permute(0, 3, 1, 2).contiguous()
+
+
+def dw_ref(x, w9, bias, act, res, kh=3, kw=3, stride=1, act_c=None):
+    """fp64 depthwise conv of x (B, H, W, C); w9 (kh * kw, C) tap-major as the kernels read it; SiLU on the first act_c channels."""
+    Cc = x.shape[-1]
+    w = w9.double().t().reshape(Cc, 1, kh, kw)
+    y = F.conv2d(nchw(x.double()), w, bias.double(), stride, (kh // 2, kw // 2), 1, Cc)
+    n = Cc if act_c is None else act_c
+    if act and n:
+        y = torch.cat((F.silu(y[:, :n]), y[:, n:]), 1)
+    y = nhwc(y)
+    return y + res.double() if res is not None else y
+
+
+def dwg_record(wk, bias, wld, koff):
+    """A DWCONV_G weight record whose rows are longer than the launch: wk (taps, C) in columns [koff, koff + C) of a NaN (taps, wld)
+    matrix, bias (C,) behind koff NaNs.  -> (matrix, bias vector) as float32 arrays for a blob."""
+    taps, Cc = wk.shape
+    assert koff + Cc <= wld
+    w, b = torch.full((taps, wld), NAN), torch.full((koff + Cc,), NAN)
+    w[:, koff:koff + Cc], b[koff:] = wk, bias
+    return w.numpy(), b.numpy()
+
+
+def dwg_op(prec, B, H, W, kh, kw, stride, src, dst, w_off, b_off, wld, koff, act_c, mid_c=0):
+    """A DWCONV_G op, fields as run_op reads them: ksize = kh, pad = kw, heads = weight row length, key_dim = channel offset into the
+    rows and the bias, act = leading SiLU channels, mid_c = first channel of an identity-kernel half (0 = none)."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_DWCONV_G, prec, B, H, W)
+    op.OH, op.OW = (H + 2 * (kh // 2) - kh) // stride + 1, (W + 2 * (kw // 2) - kw) // stride + 1
+    op.ksize, op.pad, op.stride, op.heads, op.key_dim, op.act, op.mid_c = kh, kw, stride, wld, koff, int(act_c), int(mid_c)
+    op.src0, op.dst, op.w_off, op.b_off = src, dst, w_off, b_off
+    return op
+
+
+def conv1x1_op(B, H, W, src, dst, w_off, b_off, act=True, res=None):
+    """A fp16 1x1 CONV op (weights packed by ops.pack_conv_weight) as Plan.conv emits it: one source, SiLU, an optional shortcut."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_CONV, 0, B, H, W)
+    op.ksize, op.stride, op.pad, op.act, op.dst_scale = 1, 1, 0, int(act), 1
+    op.src0, op.dst, op.w_off, op.b_off = src, dst, w_off, b_off
+    if res is not None:
+        op.res = res
+    return op
+
+
+def packed_1x1(w, b):
+    """Dense (cout, cin) f16-valued weights + f32 bias -> the packed [CoutPad][Kpad] f16 matrix and [CoutPad] f32 bias, as host arrays."""
+    from bs_yolo_amd import ops as O
+    wp, bp = O.pack_conv_weight(w[:, :, None, None], b, "cpu")
+    return wp.numpy(), bp.numpy()
+
+
+def assert_outside_views_intact(t, before, views):
+    """Everything of the device tensor `t` outside the channel ranges `views` = [(coff, C), ...] has the bits of `before` (its host
+    copy from before the run)."""
+    keep = torch.ones(t.shape[-1], dtype=torch.bool)
+    for coff, C_ in views:
+        keep[coff:coff + C_] = False
+    assert torch.equal(bits(t)[..., keep], bits(before)[..., keep]), "a store left the destination view"
 
 
 def ulp(v, mant, floor_exp):

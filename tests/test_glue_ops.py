@@ -16,8 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from op_plan_helpers import (DEV, NAN, POISON16, POISON32, assert_poison_intact, bits, new_op, poisoned, run_op, ulp16, ulp32,
-                             view, weights_blob)
+from op_plan_helpers import (DEV, NAN, POISON16, POISON32, assert_poison_intact, bits, dw_ref as _dw_ref, nchw, new_op, nhwc,
+                             poisoned, run_op, ulp16, ulp32, view, weights_blob)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,14 +42,6 @@ def _randn(g, *shape, prec=0, scale=1.0):
 
 def _gen(*key):
     return torch.Generator().manual_seed(sum((i + 1) * 7919 * int(k) for i, k in enumerate(key)) % (2 ** 31))
-
-
-def nhwc(x):
-    return x.permute(0, 2, 3, 1).contiguous()
-
-
-def nchw(x):
-    return x.permute(0, 3, 1, 2).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -361,18 +353,6 @@ def _dw_run(prec, x, w9, bias, act, res, cs, lds):
     run_op(op, ext, blob)
     assert_poison_intact(dst, cd, Cc, _poison(prec))
     return dst[..., cd:cd + Cc].cpu()
-
-
-def _dw_ref(x, w9, bias, act, res, kh=3, kw=3, stride=1, act_c=None):
-    """fp64 depthwise conv of x (B, H, W, C); w9 (kh * kw, C) tap-major as the kernels read it; SiLU on the first act_c channels."""
-    Cc = x.shape[-1]
-    w = w9.double().t().reshape(Cc, 1, kh, kw)
-    y = F.conv2d(nchw(x.double()), w, bias.double(), stride, (kh // 2, kw // 2), 1, Cc)
-    n = Cc if act_c is None else act_c
-    if act and n:
-        y = torch.cat((F.silu(y[:, :n]), y[:, n:]), 1)
-    y = nhwc(y)
-    return y + res.double() if res is not None else y
 
 
 DW_SHAPES = [(1, 1), (1, 9), (7, 1), (8, 2), (9, 7), (17, 3)]
