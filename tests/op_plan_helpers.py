@@ -1,4 +1,4 @@
-"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every
+"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every
 tensor bound as an external slot, poisoned views and a weight-blob builder.  Not a test module."""
 import ctypes as C
 
@@ -161,6 +161,52 @@ def packed_1x1(w, b):
     from bs_yolo_amd import ops as O
     wp, bp = O.pack_conv_weight(w[:, :, None, None], b, "cpu")
     return wp.numpy(), bp.numpy()
+
+
+def conv32_record(w, b, prec):
+    """One dense conv's record for the fp32-storage modes, laid out as weights.pack_record does for f32 / split: the f32
+    [k*k*cin][cout] matrix of w (cout, cin, k, k) and, for prec == 2, the hi / lo f16 planes of weights.split_f16_planes at the
+    256-byte offsets run_op_f32 computes behind it.  The gaps between the three parts hold f32 NaN (read as f16: 0, NaN); the planes'
+    own padding up to Kpad stays zero, the kernels multiply it.  -> (weight record as a uint8 array, bias as a float32 array)."""
+    from bs_yolo_amd import weights as Wt
+    cout, cin, k, _ = w.shape
+    K = k * k * cin
+    rec = w.float().permute(2, 3, 1, 0).reshape(K, cout).contiguous().numpy().tobytes()
+    if prec == 2:
+        hi, lo = Wt.split_f16_planes(w.float().permute(0, 2, 3, 1).reshape(cout, K))
+        assert hi.shape == (cout, (K + 31) // 32 * 32)
+        for plane in (hi, lo):
+            rec += _NAN_PAD[:-len(rec) % 256] + plane.numpy().tobytes()
+            assert len(rec) % 4 == 0
+    return np.frombuffer(rec, np.uint8), b.float().contiguous().numpy()
+
+
+def conv32_op(prec, B, H, W, ksize, stride, pad, src0, dst, w_off, b_off, src1=None, up0=0, up1=0, res=None, act=0, dst_scale=1, dst_dy=0,
+              dst_dx=0, in_dtype=None, first=False):
+    """A CONV (first: CONV_FIRST, src0 = the BCHW image of `in_dtype`) op of the fp32-storage modes, fields as run_op_f32 reads them.
+    H, W: the conv's input map (a source read through nearest x2 holds H / 2 x W / 2); the destination holds OH * dst_scale rows."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_CONV_FIRST if first else L.OP_CONV, prec, B, H, W)
+    op.OH, op.OW = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    op.ksize, op.stride, op.pad, op.act = ksize, stride, pad, int(act)
+    op.src0, op.dst, op.up0, op.up1 = src0, dst, up0, up1
+    if src1 is not None:
+        op.src1 = src1
+    if res is not None:
+        op.res = res
+    op.dst_scale, op.dst_dy, op.dst_dx = dst_scale, dst_dy, dst_dx
+    op.in_dtype = L.BSY_F32 if in_dtype is None else in_dtype
+    op.w_off, op.b_off = w_off, b_off
+    return op
+
+
+def attn32_op(prec, B, H, W, src, dst, heads, key_dim, head_dim, scale):
+    """An ATTN op of the fp32-storage modes: src = the [q | k | v] map (heads * (2 key_dim + head_dim) channels), N = H * W."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_ATTN, prec, B, H, W)
+    op.src0, op.dst = src, dst
+    op.heads, op.key_dim, op.head_dim, op.scale = heads, key_dim, head_dim, float(scale)
+    return op
 
 
 def assert_outside_views_intact(t, before, views):
