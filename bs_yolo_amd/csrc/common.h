@@ -325,6 +325,9 @@ struct DecodeArgs {
     int ne;  // OBB angle channels (0 / 1): msk[l] then holds the angle logits and nm is 0
     int halves;  // 1: the DFL sums run in the fused head epilogue's order at every level count (a Detect plan whose decode launch stands
                  // in for the fused head, bsy_op.act); 0: that order for heads of four levels only, bin order up to three
+    int nk, kdim;  // Pose keypoint channels (nkpt * kdim; 0: none) and channels per keypoint (2 / 3): msk[l] then holds the level's keypoint
+                   // logits (nm = ne = 0); y gets nk decoded rows behind the scores (Pose.kpts_decode, kpt_decode.h)
+    void* kraw;    // nk: (B, nk, A) tensor of y's dtype for the undecoded logits, or null
 };
 int launch_decode(const DecodeArgs& a, hipStream_t s);
 // val_match.hip: the validator's matching rule on an IoU matrix (B, Lmax, max_det) made elsewhere (val_masks.hip); arguments as

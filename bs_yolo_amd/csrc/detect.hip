@@ -4,12 +4,16 @@
 // make_anchors / dist2bbox (utils/tal.py:371-395) and, for Segment, the mask-coefficient concat (head.py:190-197).
 // The reference runs ~10 elementwise/softmax launches over (B,144,A); here one kernel reads the fp32 logits written by
 // the last 1x1 convs once (coalesced, through LDS), does the four 16-bin softmax expectations per anchor and writes
-// every output channel coalesced along the anchor axis.  HBM-bound: (64+nc+nm)*4 B in, (4+nc+nm)*sizeof(T) out per
+// every output channel coalesced along the anchor axis.  A Pose head's keypoint rows (head.py:242-279) come out of the same launch
+// (mode DEC_KPT below).  HBM-bound: (64+nc+nm)*4 B in, (4+nc+nm)*sizeof(T) out per
 // anchor.  All arithmetic fp32.
 //
 // raw_nchw_kernel rebuilds the `x` list Detect.forward returns next to y (head.py:69-74: cat(cv2(x), cv3(x)) per
 // level, BCHW); only launched when the caller asks for it.
+#include <algorithm>
+
 #include "common.h"
+#include "kpt_decode.h"
 
 struct DecodeK {
     const float* box[BSY_MAX_LEVELS];
@@ -20,6 +24,8 @@ struct DecodeK {
     float stride[BSY_MAX_LEVELS];
     int nl, B, nc, nm, A;
     int ne;  // ROT: angle channels (1), read through the msk slots
+    int nk, kdim;  // KPT: keypoint channels (nkpt * kdim) read through the msk slots, kdim = 2 (x, y) or 3 (x, y, visibility)
+    void* kraw;    // KPT: (B, nk, A) tensor of y's dtype for the undecoded keypoint logits, or null
 };
 
 // One workgroup = 64 consecutive anchors of one (image, level).  Their logits are contiguous in HBM
@@ -35,9 +41,17 @@ struct DecodeK {
 // their outputs have always had (HALVES = false is the kernel as it was) -- in the stand-alone entry point, in Segment / OBB plans
 // and in the fp32-storage modes, which have no fused form; a Detect plan of the fp16 path whose decode launch stands in for the
 // fused head (fuse_head off) asks for HALVES at any level count (DecodeArgs.halves), so that switch, too, returns the fused bits.
+// Mode DEC_KPT (Pose head, head.py:242-250): the msk slots carry the keypoint logits of cv4.  Rows 0 .. 4 + nc of y are the plain
+// instance's, computed by the same statements; the keypoint rows follow in a second phase, because the logits of 64 anchors (up to
+// 64 x 192 floats) do not fit into 64 KiB of LDS beside the box tile: once the boxes and scores are written, the whole LDS block is
+// reused for the [64][nk | 1] keypoint tile (an odd row stride: conflict-free columns).  Wave `part` decodes keypoints part, part + 4,
+// ...: every store is 64 consecutive anchors of one row.  The logit is rounded to T FIRST and decoded with kpt_decode.h's overload
+// for T, so y[:, 4 + nc:] is bsy_kpts_decode of the raw tensor bit for bit; the raw tensor (optional) gets the rounded logits.
 #define DEC_TA 64
-template <typename T, bool ROT, bool HALVES>
+enum { DEC_PLAIN = 0, DEC_ROT = 1, DEC_KPT = 2 };
+template <typename T, int MODE, bool HALVES>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restrict__ y) {
+    constexpr bool ROT = MODE == DEC_ROT, KPT = MODE == DEC_KPT;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
@@ -52,7 +66,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
     const int la0 = t * DEC_TA;
     const int na = min(DEC_TA, hw - la0);
     if (na <= 0) return;
-    const int nx = ROT ? p.ne : p.nm;      // rows read through the msk slots
+    const int nx = ROT ? p.ne : KPT ? 0 : p.nm;  // rows staged beside the class logits (KPT: the keypoints come in a second phase)
     const int nch = p.nc + nx;
     const int cst = nch + 1;               // padded row stride of the class/mask tile
     float* sbox = dsm;                     // [64][65]
@@ -122,41 +136,81 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
         sd[a * 4 + part] = num / den;
     }
     __syncthreads();
-    if (a >= na) return;
+    if (!KPT && a >= na) return;
     const int la = la0 + a;
-    T* yp = y + (size_t)b * (4 + nch) * p.A + p.a0[l] + la;
-    if (ROT) {
-        if (part == 0) {
+    T* yp = y + (size_t)b * (4 + nch + (KPT ? p.nk : 0)) * p.A + p.a0[l] + la;
+    if (!KPT || a < na) {  // (KPT: the threads past the tile's end still stage the keypoint tile below)
+        if (ROT) {
+            if (part == 0) {
+                const float ax = (float)(la % p.w[l]) + 0.5f, ay = (float)(la / p.w[l]) + 0.5f;
+                const float lt0 = sd[a * 4 + 0], lt1 = sd[a * 4 + 1], rb0 = sd[a * 4 + 2], rb1 = sd[a * 4 + 3];
+                const float th = (sigmoid_f(scls[a * cst + p.nc]) - 0.25f) * 3.14159265358979323846f;
+                const float c = cosf(th), s = sinf(th);
+                const float xf = (rb0 - lt0) / 2.0f, yf = (rb1 - lt1) / 2.0f;
+                const float st = p.stride[l];
+                yp[0] = (T)((xf * c - yf * s + ax) * st);
+                yp[(size_t)p.A] = (T)((xf * s + yf * c + ay) * st);
+                yp[(size_t)2 * p.A] = (T)((lt0 + rb0) * st);
+                yp[(size_t)3 * p.A] = (T)((lt1 + rb1) * st);
+                yp[(size_t)(4 + p.nc) * p.A] = (T)th;
+            }
+        } else if (part == 0) {
             const float ax = (float)(la % p.w[l]) + 0.5f, ay = (float)(la / p.w[l]) + 0.5f;
-            const float lt0 = sd[a * 4 + 0], lt1 = sd[a * 4 + 1], rb0 = sd[a * 4 + 2], rb1 = sd[a * 4 + 3];
-            const float th = (sigmoid_f(scls[a * cst + p.nc]) - 0.25f) * 3.14159265358979323846f;
-            const float c = cosf(th), s = sinf(th);
-            const float xf = (rb0 - lt0) / 2.0f, yf = (rb1 - lt1) / 2.0f;
+            const float x1 = ax - sd[a * 4 + 0], y1 = ay - sd[a * 4 + 1], x2 = ax + sd[a * 4 + 2], y2 = ay + sd[a * 4 + 3];
             const float st = p.stride[l];
-            yp[0] = (T)((xf * c - yf * s + ax) * st);
-            yp[(size_t)p.A] = (T)((xf * s + yf * c + ay) * st);
-            yp[(size_t)2 * p.A] = (T)((lt0 + rb0) * st);
-            yp[(size_t)3 * p.A] = (T)((lt1 + rb1) * st);
-            yp[(size_t)(4 + p.nc) * p.A] = (T)th;
+            yp[0] = (T)(((x1 + x2) * 0.5f) * st);
+            yp[(size_t)p.A] = (T)(((y1 + y2) * 0.5f) * st);
+            yp[(size_t)2 * p.A] = (T)((x2 - x1) * st);
+            yp[(size_t)3 * p.A] = (T)((y2 - y1) * st);
         }
-    } else if (part == 0) {
-        const float ax = (float)(la % p.w[l]) + 0.5f, ay = (float)(la / p.w[l]) + 0.5f;
-        const float x1 = ax - sd[a * 4 + 0], y1 = ay - sd[a * 4 + 1], x2 = ax + sd[a * 4 + 2], y2 = ay + sd[a * 4 + 3];
-        const float st = p.stride[l];
-        yp[0] = (T)(((x1 + x2) * 0.5f) * st);
-        yp[(size_t)p.A] = (T)(((y1 + y2) * 0.5f) * st);
-        yp[(size_t)2 * p.A] = (T)((x2 - x1) * st);
-        yp[(size_t)3 * p.A] = (T)((y2 - y1) * st);
+        const float* cr = scls + a * cst;
+        for (int c = part; c < p.nc; c += 4) yp[(size_t)(4 + c) * p.A] = (T)sigmoid_f(cr[c]);
+        for (int c = part; c < p.nm; c += 4) yp[(size_t)(4 + p.nc + c) * p.A] = (T)cr[p.nc + c];
     }
-    const float* cr = scls + a * cst;
-    for (int c = part; c < p.nc; c += 4) yp[(size_t)(4 + c) * p.A] = (T)sigmoid_f(cr[c]);
-    for (int c = part; c < p.nm; c += 4) yp[(size_t)(4 + p.nc + c) * p.A] = (T)cr[p.nc + c];
+    if (KPT) {
+        __syncthreads();  // boxes and scores are out: the LDS block is free
+        const int nk = p.nk, kst = nk | 1;
+        const float* kp = p.msk[l] + pix0 * p.ldm[l];
+        const int nqk = (nk + 3) >> 2;  // ldm is a multiple of 4 >= nk
+        for (int i = tid; i < na * nqk; i += 256) {
+            const int r = i / nqk, q = i - r * nqk;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(kp + (size_t)r * p.ldm[l] + 4 * q);
+            float* d = dsm + r * kst + 4 * q;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < nk) d[e] = v[e];
+        }
+        __syncthreads();
+        if (a >= na) return;
+        const float ax = (float)(la % p.w[l]), ay = (float)(la / p.w[l]);  // the cell; kpt_xy adds the anchor's half
+        const float st = p.stride[l];
+        const float* kr = dsm + a * kst;
+        T* yk = yp + (size_t)(4 + p.nc) * p.A;
+        T* rw = p.kraw ? static_cast<T*>(p.kraw) + (size_t)b * nk * p.A + p.a0[l] + la : nullptr;
+        const int nkpt = nk / p.kdim;
+        for (int k = part; k < nkpt; k += 4) {
+            const int c = k * p.kdim;
+            const T vx = (T)kr[c], vy = (T)kr[c + 1];
+            yk[(size_t)c * p.A] = kpt_xy(vx, ax, st);
+            yk[(size_t)(c + 1) * p.A] = kpt_xy(vy, ay, st);
+            if (rw) { rw[(size_t)c * p.A] = vx; rw[(size_t)(c + 1) * p.A] = vy; }
+            if (p.kdim == 3) {
+                const T vv = (T)kr[c + 2];
+                yk[(size_t)(c + 2) * p.A] = kpt_vis(vv);
+                if (rw) rw[(size_t)(c + 2) * p.A] = vv;
+            }
+        }
+    }
 }
 
 int launch_decode(const DecodeArgs& a, hipStream_t s) {
     if (a.nl < 1 || a.nl > BSY_MAX_LEVELS || a.nc < 1 || a.B < 1) BSY_FAIL(BSY_ERR_ARG, "decode: bad sizes");
     if (a.ne < 0 || a.ne > 1 || (a.ne && a.nm)) BSY_FAIL(BSY_ERR_ARG, "decode: ne = %d with nm = %d (one angle, no mask coefficients)", a.ne, a.nm);
-    const int nx = a.nm + a.ne;  // rows read through the msk slots
+    if (a.nk < 0 || (a.nk && (a.nm || a.ne)))
+        BSY_FAIL(BSY_ERR_ARG, "decode: nk = %d with nm = %d, ne = %d (keypoints, mask coefficients and the angle exclude each other)", a.nk, a.nm, a.ne);
+    if (a.nk && ((a.kdim != 2 && a.kdim != 3) || a.nk % a.kdim || a.nk / a.kdim > 64))
+        BSY_FAIL(BSY_ERR_ARG, "decode: nk = %d, kdim = %d (kdim 2 or 3, 1 to 64 keypoints of kdim channels)", a.nk, a.kdim);
+    const int nx = a.nm + a.ne + a.nk;  // rows read through the msk slots
     DecodeK k;
     int A = 0;
     for (int l = 0; l < BSY_MAX_LEVELS; ++l) {
@@ -173,6 +227,7 @@ int launch_decode(const DecodeArgs& a, hipStream_t s) {
     }
     if (a.A && a.A != A) BSY_FAIL(BSY_ERR_ARG, "decode: anchor count mismatch (%d vs %d)", a.A, A);
     k.nl = a.nl; k.B = a.B; k.nc = a.nc; k.nm = a.nm; k.A = A; k.ne = a.ne;
+    k.nk = a.nk; k.kdim = a.kdim; k.kraw = a.nk ? a.kraw : nullptr;
     int tiles = 0;
     for (int l = 0; l < a.nl; ++l) {
         tiles += (a.h[l] * a.w[l] + DEC_TA - 1) / DEC_TA;
@@ -181,21 +236,30 @@ int launch_decode(const DecodeArgs& a, hipStream_t s) {
             BSY_FAIL(BSY_ERR_ARG, "decode: level %d class/mask rows must be 16-byte aligned multiples of 4 floats", l);
     }
     dim3 grid(tiles, a.B);
-    const size_t lds = (size_t)DEC_TA * (65 + (a.nc + nx + 1) + 4) * sizeof(float);
+    // KPT: the keypoint tile [64][nk | 1] reuses the block in a second phase (decode_kernel), the first holds box and class logits only
+    const size_t lds = std::max<size_t>((size_t)DEC_TA * (65 + (a.nc + nx - a.nk + 1) + 4), (size_t)DEC_TA * (a.nk | 1)) * sizeof(float);
     if (lds > 64 * 1024) BSY_FAIL(BSY_ERR_ARG, "decode: nc + nm = %d too large", a.nc + nx);
     const bool halves = a.nl > 3 || a.halves;  // (an OBB head has at most three levels: plan.py)
-    if (a.y_dtype == BSY_F16 && a.ne)
-        hipLaunchKernelGGL((decode_kernel<half_t, true, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+    if (a.y_dtype == BSY_F16 && a.nk && halves)
+        hipLaunchKernelGGL((decode_kernel<half_t, DEC_KPT, true>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+    else if (a.y_dtype == BSY_F32 && a.nk && halves)
+        hipLaunchKernelGGL((decode_kernel<float, DEC_KPT, true>), grid, dim3(256), lds, s, k, (float*)a.y);
+    else if (a.y_dtype == BSY_F16 && a.nk)
+        hipLaunchKernelGGL((decode_kernel<half_t, DEC_KPT, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+    else if (a.y_dtype == BSY_F32 && a.nk)
+        hipLaunchKernelGGL((decode_kernel<float, DEC_KPT, false>), grid, dim3(256), lds, s, k, (float*)a.y);
+    else if (a.y_dtype == BSY_F16 && a.ne)
+        hipLaunchKernelGGL((decode_kernel<half_t, DEC_ROT, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32 && a.ne)
-        hipLaunchKernelGGL((decode_kernel<float, true, false>), grid, dim3(256), lds, s, k, (float*)a.y);
+        hipLaunchKernelGGL((decode_kernel<float, DEC_ROT, false>), grid, dim3(256), lds, s, k, (float*)a.y);
     else if (a.y_dtype == BSY_F16 && halves)
-        hipLaunchKernelGGL((decode_kernel<half_t, false, true>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+        hipLaunchKernelGGL((decode_kernel<half_t, DEC_PLAIN, true>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32 && halves)
-        hipLaunchKernelGGL((decode_kernel<float, false, true>), grid, dim3(256), lds, s, k, (float*)a.y);
+        hipLaunchKernelGGL((decode_kernel<float, DEC_PLAIN, true>), grid, dim3(256), lds, s, k, (float*)a.y);
     else if (a.y_dtype == BSY_F16)
-        hipLaunchKernelGGL((decode_kernel<half_t, false, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
+        hipLaunchKernelGGL((decode_kernel<half_t, DEC_PLAIN, false>), grid, dim3(256), lds, s, k, (half_t*)a.y);
     else if (a.y_dtype == BSY_F32)
-        hipLaunchKernelGGL((decode_kernel<float, false, false>), grid, dim3(256), lds, s, k, (float*)a.y);
+        hipLaunchKernelGGL((decode_kernel<float, DEC_PLAIN, false>), grid, dim3(256), lds, s, k, (float*)a.y);
     else
         BSY_FAIL(BSY_ERR_ARG, "decode: y dtype %d unsupported", a.y_dtype);
     HIP_TRY(hipGetLastError());

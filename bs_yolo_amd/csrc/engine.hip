@@ -626,13 +626,17 @@ int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, Conv
             memset(&a, 0, sizeof(a));
             a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A; a.ne = op.ne;
             a.halves = op.act && !op.nm && !op.ne;  // DECODE: act = the fused head epilogue's DFL order (include/bsyolo.h)
-            const bool extra = op.nm || op.ne;  // mask coefficients (Segment) or angle logits (OBB) in the msk slots
+            a.nk = op.nk; a.kdim = op.kdim;
+            const bool extra = op.nm || op.ne || op.nk;  // mask coefficients (Segment), angle (OBB) or keypoint (Pose) logits in the msk slots
             for (int l = 0; l < op.nl && l < BSY_MAX_LEVELS; ++l) {
                 a.box[l] = R.f(op.box[l]); a.cls[l] = R.f(op.cls[l]); a.msk[l] = extra ? R.f(op.msk[l]) : nullptr;
                 a.ldb[l] = op.box[l].ld; a.ldc[l] = op.cls[l].ld; a.ldm[l] = extra ? op.msk[l].ld : 0;
                 a.h[l] = op.lvl_h[l]; a.w[l] = op.lvl_w[l]; a.stride[l] = op.lvl_stride[l];
             }
             a.y = R.base(op.dst); a.y_dtype = op.out_dtype;
+            // Pose: res = the raw keypoint tensor, an optional output (an unbound external slot leaves it out)
+            if (op.nk && op.res.buf >= BSY_EXT_BASE && op.res.buf - BSY_EXT_BASE < R.n_ext && R.ext[op.res.buf - BSY_EXT_BASE])
+                a.kraw = R.base(op.res);
             if (!R.ok) return BSY_ERR_ARG;
             return launch_decode(a, s);
         }

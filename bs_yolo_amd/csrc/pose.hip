@@ -5,6 +5,7 @@
 // Compiled with -ffp-contract=off: both must round like the fp32 / fp16 torch ops they replace.
 #include "common.h"
 #include "postproc.h"
+#include "kpt_decode.h"
 
 constexpr int KPT_MAX = 64;     // keypoints per instance the entry points take
 constexpr int KD_THREADS = 256; // anchors per workgroup of the decode
@@ -19,19 +20,7 @@ struct KptDecodeK {
     int nl, nkpt, ndim, A;
 };
 
-// The reference's expression per dtype.  fp32: (v * 2 + (ax - 0.5)) * stride, every operation rounded once.  fp16: torch rounds to
-// fp16 after every operation, and the anchors and strides are fp16 tensors themselves (make_anchors takes the feature maps' dtype);
-// a sum or product of two fp16 values rounded to fp32 and then to fp16 is the correctly rounded fp16 result, so the fp32 pipe
-// with a conversion after each step returns those bits.
-__device__ __forceinline__ float kpt_xy(float v, float a, float stride) { return (v * 2.0f + (a + 0.5f - 0.5f)) * stride; }
-__device__ __forceinline__ half_t kpt_xy(half_t v, float a, float stride) {
-    const half_t a16 = (half_t)((float)(half_t)(a + 0.5f) - 0.5f);
-    const half_t t = (half_t)((float)v * 2.0f);
-    const half_t s = (half_t)((float)t + (float)a16);
-    return (half_t)((float)s * (float)(half_t)stride);
-}
-__device__ __forceinline__ float kpt_vis(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ half_t kpt_vis(half_t v) { return (half_t)(1.0f / (1.0f + expf(-(float)v))); }
+// The per-element arithmetic (kpt_xy / kpt_vis, both overloads) is kpt_decode.h, which detect.hip's keypoint mode shares.
 
 // Thread = anchor, workgroup = KD_THREADS consecutive anchors of one (image, group of KD_GROUP keypoints): every load and store is
 // coalesced along A.  HBM-bound: nk * sizeof(T) read and written per anchor; no LDS, no transposes.

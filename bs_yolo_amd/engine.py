@@ -9,6 +9,10 @@ An engine built from a classification graph (a `Classify` head) returns what Cla
 the softmax and the logits, (B, nc) each in the input's dtype.  The top-min(nc, 5) classes of the same launch -- what the reference's
 predictor and validator take with an argsort -- are kept as ``engine.last_topk = (idx int32, val f32)``, (B, k) device rows of the
 LAST forward (in graph mode they belong to the ring slot of that forward, like y).
+
+An engine built from a pose graph (a `Pose` head) returns what Pose.forward returns in eval (head.py:250): ``(y, (x_list, kpt))`` with
+y (B, 4 + nc + nk, A) -- the decoded keypoint rows behind the scores -- and kpt (B, nk, A) the raw keypoint logits;
+``want_raw=False`` gives ``(y, ([None] * nl, None))``.
 """
 from __future__ import annotations
 
@@ -237,7 +241,8 @@ class YoloEngine:
         return hit
 
     def _ext(self, im, y, raws, proto=None):
-        # slot order of Plan: image, y, raw maps of levels 0-2, proto, then the fourth level's raw map (Plan.EXT_RAW3)
+        # slot order of Plan: image, y, raw maps of levels 0-2, proto (a pose plan: the raw keypoint logits, Plan.EXT_KPT), then the
+        # fourth level's raw map (Plan.EXT_RAW3)
         raws = [r.data_ptr() if r is not None else None for r in raws]
         ptrs = [im.data_ptr(), y.data_ptr()] + raws[:3] + [proto.data_ptr() if proto is not None else None] + raws[3:]
         return (C.c_void_p * len(ptrs))(*ptrs), len(ptrs)
@@ -275,6 +280,9 @@ class YoloEngine:
             if self.meta["ne"]:
                 raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
                 return y, (raws, y[:, 4 + self.meta["nc"]:])
+            if self.meta.get("nk", 0):
+                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
+                return y, (raws, torch.cat([o[1][1] for o in outs]) if want_raw else None)
             return y, ([torch.cat([o[1][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl)
         with self._lock:  # plan table, arena and launch order are shared state
             return self._forward_one(im, want_raw, B, H, W)
@@ -286,7 +294,7 @@ class YoloEngine:
             return self._forward_classify(plan, h, im, want_raw, B, H, W)
 
         def outputs():
-            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
+            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"] + m.get("nk", 0), m["A"]), dtype=im.dtype, device=self.device)
             raws: List[Optional[torch.Tensor]] = [None] * len(m["levels"])
             if want_raw:
                 raws = [torch.empty((B, m["no"], lh, lw), dtype=im.dtype, device=self.device) for lh, lw in m["levels"]]
@@ -294,6 +302,8 @@ class YoloEngine:
             if m["nm"]:
                 ph, pw = m["proto_hw"]
                 proto = torch.empty((B, m["nm"], ph, pw), dtype=im.dtype, device=self.device)
+            elif m.get("nk", 0) and want_raw:  # the raw keypoint logits travel in the proto slot (Plan.EXT_KPT)
+                proto = torch.empty((B, m.get("nk", 0), m["A"]), dtype=im.dtype, device=self.device)
             return y, raws, proto
 
         y, raws, proto = self._output_set(outputs, im, want_raw)
@@ -303,6 +313,8 @@ class YoloEngine:
             return y, (raws, y[:, 4 + m["nc"]:], proto)
         if m["ne"]:  # OBB.forward (head.py:223): (cat(y, angle), (raw, angle)); y already carries the angle row
             return y, (raws, y[:, 4 + m["nc"]:])
+        if m.get("nk", 0):  # Pose.forward (head.py:250): (cat(y, pred_kpt), (raw, kpt)); y already carries the decoded keypoint rows
+            return y, (raws, proto)
         return y, raws
 
     def _output_set(self, make, im, want_raw):
@@ -397,10 +409,10 @@ class YoloEngine:
     def forward_augment(self, im: torch.Tensor):
         """DetectionModel._predict_augment (nn/tasks.py:354-370) -> (y, None): three forwards at the scaled sizes, the scaled inputs
         made by bsy_scale_img, the passes clipped / descaled / concatenated by ONE bsy_tta_merge on the current stream.  A Segment
-        graph (an OBB one, a classification one) returns its single-scale forward, as the reference reverts for every class but
+        graph (an OBB one, a pose one, a classification one) returns its single-scale forward, as the reference reverts for every class but
         DetectionModel (:356-358)."""
         with self._lock:
-            if self.meta["nm"] or self.meta["ne"] or self.task == "classify":
+            if self.meta["nm"] or self.meta["ne"] or self.meta.get("nk", 0) or self.task == "classify":
                 return self.forward(im)
             if im.device != self.device:
                 raise ValueError(f"input on {im.device}, engine on {self.device}")
@@ -451,7 +463,7 @@ class YoloEngine:
             idx, val = (torch.empty((B, m["topk"]), dtype=dt, device=self.device) for dt in (torch.int32, torch.float32))
             ext, n = (C.c_void_p * 5)(im.data_ptr(), y.data_ptr(), x.data_ptr(), idx.data_ptr(), val.data_ptr()), 5
         else:
-            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"], m["A"]), dtype=im.dtype, device=self.device)
+            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"] + m.get("nk", 0), m["A"]), dtype=im.dtype, device=self.device)
             ext, n = self._ext(im, y, [None] * len(m["levels"]))
         ms = (C.c_float * len(plan.ops))()
         L.check(L.lib.bsy_plan_profile(h, ext, n, L.stream_ptr(self.device), ms))

@@ -5,7 +5,9 @@ cfg/models/v8/yolov8-seg.yaml:15-46, cfg/models/v5/yolov5.yaml:14-50, cfg/models
 graph, family "bsyolo11") and the four-level variants cfg/models/v8/yolov8-p2.yaml, v8/yolov8-p6.yaml (+ yolov8-seg-p6.yaml) and
 v5/yolov5-p6.yaml (families "yolov8-p2", "yolov8-p6", "yolov5-p6"), and the YOLOv9 (GELAN) graphs cfg/models/v9/yolov9{t,s,m,c}.yaml and
 yolov9c-seg.yaml (family "yolov9": literal widths per size, no scales table), and the classification graphs
-cfg/models/11/yolo11-cls.yaml:8-30 and v8/yolov8-cls.yaml:8-29 (task "classify" of the families "yolo11" and "yolov8").  They are
+cfg/models/11/yolo11-cls.yaml:8-30 and v8/yolov8-cls.yaml:8-29 (task "classify" of the families "yolo11" and "yolov8"), and the pose
+graphs cfg/models/11/yolo11-pose.yaml, v8/yolov8-pose.yaml and v8/yolov8-pose-p6.yaml: the detect graphs of "yolo11", "yolov8" and
+"yolov8-p6" under a Pose head, with a top-level `kpt_shape` (task "pose").  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -217,19 +219,27 @@ _YOLOV8_CLS = {
 }
 
 _CLS_FAMILIES = {"yolo11": _YOLO11_CLS, "yolov8": _YOLOV8_CLS}
+_POSE_FAMILIES = ("yolo11", "yolov8", "yolov8-p6")  # the families the reference ships a -pose yaml for
 _FAMILIES = {"yolo11": _YOLO11, "yolov8": _YOLOV8, "bsyolo11": _BSYOLO11, "yolov5": _YOLOV5,
              "yolov8-p2": _YOLOV8_P2, "yolov8-p6": _YOLOV8_P6, "yolov5-p6": _YOLOV5_P6}
 
 
-def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str = "detect") -> dict:
+def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str = "detect", kpt_shape=None) -> dict:
     """e.g. stock_cfg("yolo11", "s") == what the reference builds for 'yolo11s.yaml' upstream; stock_cfg("yolov9", "c", task="segment")
     == 'yolov9c-seg.yaml' (family "yolov9": scale is one of t / s / m / c, segment exists for c only; the dict has no `scales`);
-    stock_cfg("yolo11", "n", 1000, "classify") == 'yolo11n-cls.yaml' (families "yolo11" and "yolov8" only)."""
+    stock_cfg("yolo11", "n", 1000, "classify") == 'yolo11n-cls.yaml' (families "yolo11" and "yolov8" only);
+    stock_cfg("yolo11", "n", 1, "pose", kpt_shape=(17, 3)) == 'yolo11n-pose.yaml' (families "yolo11", "yolov8" and "yolov8-p6" only;
+    `kpt_shape` = (keypoints, 2 or 3 channels each) is read by this task alone, becomes the dict's top-level `kpt_shape` and has to be
+    given: the four-argument call stock_cfg(family, scale, nc, "pose") raises ValueError for every family, as it always has)."""
     if task == "classify":
         if family not in _CLS_FAMILIES:
             raise ValueError(f"{family}: no classification graph (yolo11, yolov8)")
         fam = copy.deepcopy(_CLS_FAMILIES[family])
         return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"], "head": [[-1, 1, "Classify", ["nc"]]]}
+    if task == "pose" and family not in _POSE_FAMILIES:
+        raise ValueError(f"{family}: no pose graph ({', '.join(_POSE_FAMILIES)})")
+    if task == "pose" and kpt_shape is None:
+        raise ValueError("pose: kpt_shape=(keypoints, channels of each) is needed (the reference's yamls say (17, 3))")
     if family == "yolov9":
         if scale not in _V9_SIZES or task not in ("detect", "segment") or (task == "segment" and scale != "c"):
             raise ValueError(f"yolov9: scale {scale!r} / task {task!r} (detect: t, s, m, c; segment: c)")
@@ -244,6 +254,10 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
         head.append([fam["detect_from"], 1, "Segment", ["nc", 32, 256]])
     elif task == "obb":  # cfg/models/11/yolo11-obb.yaml:47, v8/yolov8-obb.yaml:46
         head.append([fam["detect_from"], 1, "OBB", ["nc", 1]])
+    elif task == "pose":  # cfg/models/11/yolo11-pose.yaml:48, v8/yolov8-pose.yaml:47, v8/yolov8-pose-p6.yaml:57
+        head.append([fam["detect_from"], 1, "Pose", ["nc", "kpt_shape"]])
+        return {"nc": nc, "kpt_shape": [int(v) for v in kpt_shape], "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"],
+                "head": head}
     else:
         raise ValueError(task)
     return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"], "head": head}

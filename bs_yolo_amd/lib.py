@@ -56,14 +56,14 @@ class Op(C.Structure):
         ("box", View * BSY_MAX_LEVELS), ("cls", View * BSY_MAX_LEVELS),
         ("lvl_h", C.c_int32 * BSY_MAX_LEVELS), ("lvl_w", C.c_int32 * BSY_MAX_LEVELS),
         ("lvl_stride", C.c_float * BSY_MAX_LEVELS),
-        ("reserved2", C.c_int32),
+        ("nk", C.c_int32),  # DECODE: keypoint channels (Pose); the word that was reserved2
         ("in_dtype", C.c_int32), ("out_dtype", C.c_int32),
         ("level", C.c_int32),
         ("lane", C.c_int32), ("tuned_cfg", C.c_int32), ("join", C.c_int32),
         ("mid_c", C.c_int32),
         ("w2_off", C.c_int64), ("b2_off", C.c_int64),
         ("aux_off", C.c_int64 * 18),
-        ("prec", C.c_int32), ("ne", C.c_int32), ("ksplit", C.c_int32), ("reserved1", C.c_int32),
+        ("prec", C.c_int32), ("ne", C.c_int32), ("ksplit", C.c_int32), ("kdim", C.c_int32),  # kdim: channels per keypoint
         ("msk", View * BSY_MAX_LEVELS),  # behind the fields that keep their offsets (include/bsyolo.h)
     ]
 

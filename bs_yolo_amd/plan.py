@@ -123,7 +123,7 @@ def kernel_takes(kernel: str, *shape: int) -> bool:
 OP_FIELDS = frozenset((
     "H", "W", "OH", "OW", "src0", "src1", "dst", "res", "ksize", "stride", "pad", "act", "out_f32", "dst_scale", "dst_dy", "dst_dx", "mid_c",
     "heads", "key_dim", "head_dim", "scale", "nl", "nc", "nm", "ne", "A", "box", "cls", "msk", "lvl_h", "lvl_w", "lvl_stride", "in_dtype",
-    "out_dtype", "level", "join", "ksplit",
+    "out_dtype", "level", "join", "ksplit", "nk", "kdim",
     "wkey", "wkey2", "wkeys", "cout", "mfma_flops"))
 # kinds that may run on a side lane (csrc/engine.hip bsy_plan_run forks and joins around them)
 LANE_KINDS = (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP_C3K2)
@@ -132,8 +132,9 @@ LANE_KINDS = (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP
 class Plan:
     """Flat op list + workspace buffer table for one (B, H, W)."""
 
-    EXT_IMG, EXT_Y, EXT_RAW0 = 0, 1, 2  # external slots: image, prediction, raw level maps (2,3,4), proto (5)
+    EXT_IMG, EXT_Y, EXT_RAW0 = 0, 1, 2  # external slots: image, prediction, raw level maps (2,3,4), proto / raw keypoints (5)
     EXT_PROTO = 5
+    EXT_KPT = 5  # a pose plan's raw keypoint logits (B, nk, A): the proto slot under another name (a pose plan has no proto)
     EXT_RAW3 = 6  # the fourth level's raw map (P2 / P6 heads): behind the proto slot, so that slots 0-5 stay what they were
     EXT_LOGITS, EXT_TOPK_IDX, EXT_TOPK_VAL = 2, 3, 4  # a classify plan's slots behind image and y: x (the logits), the top-k rows
 
@@ -757,8 +758,9 @@ class Plan:
         self._decoding_conv(n1 + "+2", src, 3, cout=64, mode=3, level=level, a0=a0, A=A, nc=nc, stride=stride,
                             flops=2 * self.B * src.H * src.W * 64 * (9 * src.C + 64), act=1, wkey=k1, wkey2=k2, mid_c=64)
 
-    def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0):
-        """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels)."""
+    def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0, nk: int = 0, kdim: int = 0):
+        """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels, Pose :230-279 with nk = nkpt * kdim keypoint
+        channels)."""
         if not 1 <= len(xs) <= L.BSY_MAX_LEVELS:
             raise NotImplementedError(f"{name}: a head on {len(xs)} levels (1 to {L.BSY_MAX_LEVELS} are accelerated)")
         if ne and len(xs) > 3:
@@ -773,7 +775,8 @@ class Plan:
         # conv_epilogue_head) -- no f32 logit maps, no decode launch, no raw-map transposes.  An OBB head's box decode needs the
         # angle of its cv4 branch (tal.py:404-423 dist2rbox), so OBB always takes the decode launch
         # Four levels (P2 / P6 graphs) fuse the same way: every fused op carries its own level, first anchor and stride
-        fused = self.fuse_head and nm == 0 and ne == 0
+        # A Pose head takes the decode launch too: it decodes the keypoint rows there (csrc/detect.hip, mode DEC_KPT)
+        fused = self.fuse_head and nm == 0 and ne == 0 and nk == 0
         # every (level, branch) chain is independent until the decoder: give each its own lane so the engine runs them
         # concurrently (the 40x40 / 20x20 chains are far too small to fill 256 CUs on their own)
         for i, x in enumerate(xs):
@@ -813,6 +816,18 @@ class Plan:
                 t = self.conv(f"{name}.cv4.{i}.0", x, c4, 3, 1)
                 t = self.conv(f"{name}.cv4.{i}.1", t, c4, 3, 1)
                 msks.append(self.conv(f"{name}.cv4.{i}.2", t, wout, 1, 1, act=False, plain=True, out_f32=True, real=(real, 0)))
+            elif nk:
+                # Pose.cv4 (head.py:239-240), the same shape of branch on the same lanes.  c4 = max(ch0 // 4, nk) is 51 for every stock
+                # n / s model: like the class branch's c3, the branch then runs on the next multiple of 8 with zero weights and biases
+                # in the padding.  The keypoint logits land in an f32 map make_divisible(nk, 8) wide, as OBB's angle does
+                self._lane = 2 * len(xs) + i
+                c4 = max(ch[0] // 4, nk)
+                c4p, wout = make_divisible(c4, 8), make_divisible(nk, 8)
+                r4 = c4 if c4p != c4 else 0
+                t = self.conv(f"{name}.cv4.{i}.0", x, c4p, 3, 1, real=(r4, 0))
+                t = self.conv(f"{name}.cv4.{i}.1", t, c4p, 3, 1, real=(r4, r4))
+                msks.append(self.conv(f"{name}.cv4.{i}.2", t, wout, 1, 1, act=False, plain=True, out_f32=True,
+                                      real=(nk if wout != nk else 0, r4)))
         self._lane = 0
         self.meta.update(A=A, nc=nc, nm=nm, ne=ne, no=64 + nc, strides=strides, levels=[(t.H, t.W) for t in xs])
         if fused:
@@ -822,8 +837,11 @@ class Plan:
         # OBB and the fp32-storage modes have no fused form and keep the order their outputs have always had
         lvl = dict(H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, A=A, box=boxes, cls=clss, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs],
                    lvl_stride=strides, out_dtype=self.out_dtype)
-        self._emit(L.OP_DECODE, name + ".decode", join=1, nm=nm, ne=ne, msk=msks, act=int(not self.f32_mode and nm == 0 and ne == 0),
-                   dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne, 0, 0), **lvl)
+        # Pose: res = the raw keypoint logits' slot (optional output), written by the same launch
+        kraw = T(L.BSY_EXT_BASE + self.EXT_KPT, 0, 0, nk, 0, 0) if nk else None
+        self._emit(L.OP_DECODE, name + ".decode", join=1, nm=nm, ne=ne, nk=nk, kdim=kdim, msk=msks, res=kraw,
+                   act=int(not self.f32_mode and nm == 0 and ne == 0 and nk == 0),
+                   dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne + nk, 0, 0), **lvl)
         for i in range(len(xs)):
             self._emit(L.OP_RAW_NCHW, f"{name}.raw{i}", nm=0, msk=[], level=i, dst=T(L.BSY_EXT_BASE + self.ext_raw(i), 0, 0, 64 + nc, 0, 0), **lvl)
 
@@ -965,7 +983,7 @@ class Plan:
                 assert all(isinstance(t, T) for t in x)
                 y = list(x)
                 cout = sum(t.C for t in x)
-            elif m in ("Detect", "Segment", "OBB"):
+            elif m in ("Detect", "Segment", "OBB", "Pose"):
                 xs = x if isinstance(x, list) else [x]
                 assert all(isinstance(t, T) for t in xs)
                 if m == "Segment":  # head.py:175-197; npr scaled like parse_model does (tasks.py:1082-1083)
@@ -978,6 +996,20 @@ class Plan:
                     if ne != 1:
                         raise NotImplementedError(f"OBB with ne = {ne}: dist2rbox (utils/tal.py:404-423) decodes one angle")
                     self.detect(name, xs, args[0], legacy, ne=ne)
+                elif m == "Pose":  # head.py:230-279, args [nc, kpt_shape] (+ the channel list parse_model appends).  Every pose yaml of the
+                    # reference names the model's top-level kpt_shape (tasks.py:981-985 evaluates the string; PoseModel.yaml holds the key,
+                    # with a dataset's override applied, tasks.py:429-431), and that form is the accelerated one: a head line that spells
+                    # the pair out stays on the reference, as every Pose line did before the plan had a pose form
+                    if arg(1, None) != "kpt_shape":
+                        raise NotImplementedError(f"{name}: Pose with the argument {arg(1, None)!r} (the yaml's form, the name 'kpt_shape', is accelerated)")
+                    ks = d.get("kpt_shape")
+                    if not isinstance(ks, (list, tuple)) or len(ks) != 2:
+                        raise NotImplementedError(f"{name}: the Pose head names kpt_shape, the model description has {ks!r} (a pair: keypoints, channels of each)")
+                    nkpt, ndim = int(ks[0]), int(ks[1])
+                    if ndim not in (2, 3) or not 1 <= nkpt <= 64:  # the limits of csrc/pose.hip and of the decode launch
+                        raise NotImplementedError(f"{name}: Pose with kpt_shape ({nkpt}, {ndim}): 1 to 64 keypoints of 2 or 3 channels are accelerated")
+                    self.detect(name, xs, args[0], legacy, nk=nkpt * ndim, kdim=ndim)
+                    self.meta.update(task="pose", nk=nkpt * ndim, kpt_shape=(nkpt, ndim))  # (only a pose plan's meta has these keys)
                 else:
                     self.detect(name, xs, args[0], legacy)
                 y, cout = None, 0
@@ -1156,6 +1188,7 @@ class Plan:
                 d.get("scale", 0.0)
             o.nl, o.nc, o.nm, o.A = d.get("nl", 0), d.get("nc", 0), d.get("nm", 0), d.get("A", 0)
             o.ne = d.get("ne", 0)
+            o.nk, o.kdim = d.get("nk", 0), d.get("kdim", 0)
             for j in range(L.BSY_MAX_LEVELS):
                 o.box[j] = v(d["box"][j] if j < len(d.get("box", [])) else None)
                 o.cls[j] = v(d["cls"][j] if j < len(d.get("cls", [])) else None)

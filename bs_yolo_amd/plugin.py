@@ -9,6 +9,8 @@ Three hooks, each using an extension point the reference already has (see INTEGR
                            ``model.state_dict()``.  ``augment=True`` on a ``DetectionModel`` runs the engine's test-time
                            augmentation (tasks.py:354-370; ``tta="reference"`` opts out).  A ``ClassificationModel``
                            (tasks.py:439-490, a ``Classify`` head) returns ``(y, x)`` as Classify.forward does in eval (head.py:304).
+                           A ``PoseModel`` (a ``Pose`` head) returns ``(y, (x_list, kpt))`` as Pose.forward does (head.py:250); with
+                           the head's ``export`` flag set it keeps its own forward (kpts_decode's export branch, head.py:255-272).
                            Anything else the engine does not cover
                            (training mode, visualize / embed / profile (tasks.py:137-164), augment on other model classes, CPU
                            tensors, unsupported modules) goes to the original forward.
@@ -48,7 +50,7 @@ from .engine import YoloEngine
 from .plan import Plan
 from .weights import BN_EPS, repconv_form
 
-SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify")
+SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify", "Pose")
 
 
 def _on_device(t) -> bool:
@@ -169,6 +171,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     support, gs = _graph_facts(cfg)  # gs: a P6 graph takes multiples of 64; anything else goes to the reference forward, as non-multiples of 32 do
     orig_forward = model.forward
     classify = cfg["head"][-1][2] == "Classify"
+    pose = cfg["head"][-1][2] == "Pose"
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
              "tta_calls": 0, "support": support, "failed": set(), "repconv": None}
     fp32_mode = fp32_inputs or os.environ.get("BSY_FP32_INPUTS", "engine_fp32x")
@@ -214,7 +217,9 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
                 state["fallbacks"] += 1
                 return orig_forward(x, *args, **kwargs)
             visualize = embed = profile = False
-        if classify and _head_exports(self):  # Classify.export (head.py:285, :304): y alone, the exporter's business
+        # Classify.export (head.py:285, :304): y alone, the exporter's business; Pose.export (head.py:250, :255-272): y alone, and
+        # kpts_decode's export branch is other arithmetic
+        if (classify or pose) and _head_exports(self):
             state["fallbacks"] += 1
             return orig_forward(x, *args, **kwargs)
         if (self.training or visualize or embed or profile or args or not isinstance(x, torch.Tensor)

@@ -63,7 +63,8 @@ enum bsy_op_kind {
     BSY_OP_SPPF_POOL = 3,  /* three chained MaxPool2d(5,1,2) -> channel slices of the SPPF concat buffer      */
     BSY_OP_ATTN = 4,       /* softmax(q^T k * scale) v, per (image, head); MFMA flash-style.  act = 1 (fp16 path): + pe(v) in
                             * the same launch, w_off / b_off = pe's depthwise f32 [9][C] / [C] (the bits of ATTN then DWCONV) */
-    BSY_OP_DECODE = 5,     /* Detect._inference: DFL + dist2bbox + sigmoid -> (B, 4+nc+nm, A); DFL summation order: `act`      */
+    BSY_OP_DECODE = 5,     /* Detect._inference: DFL + dist2bbox + sigmoid -> (B, 4+nc+nm, A); DFL summation order: `act`;
+                            * OBB: + the angle row (ne); Pose: + nk decoded keypoint rows (nk, kdim)                            */
     BSY_OP_RAW_NCHW = 6,   /* raw per-level head maps NHWC f32 -> BCHW (the `x` list Detect.forward returns)  */
     BSY_OP_NHWC2NCHW = 7,  /* NHWC f16 view -> BCHW tensor (Segment protos, block.py:80-97 output)            */
     BSY_OP_STEM = 8,       /* layers 0 + 1 fused: image -> Conv 3x3 s2 (3 -> mid_c) -> Conv 3x3 s2 (mid_c -> dst.C);
@@ -140,7 +141,10 @@ typedef struct bsy_op {
     bsy_view box[BSY_MAX_LEVELS], cls[BSY_MAX_LEVELS];
     int32_t lvl_h[BSY_MAX_LEVELS], lvl_w[BSY_MAX_LEVELS];
     float lvl_stride[BSY_MAX_LEVELS];
-    int32_t reserved2;
+    int32_t nk;             /* DECODE: keypoint channels of a Pose head (head.py:230-279), nkpt * kdim with 1 <= nkpt <= 64; 0 = none.  With nk
+                             * (and nm = ne = 0) msk[l] is the level's f32 keypoint-logit map; y gets nk rows behind the scores, bit for
+                             * bit bsy_kpts_decode of the logits rounded to y's dtype, and `res` (an external slot, optional: skipped
+                             * when unbound) the rounded logits themselves as (B, nk, A).  (The word was reserved2: offsets unchanged) */
     int32_t in_dtype, out_dtype; /* CONV_FIRST input dtype; DECODE/RAW output dtype */
     int32_t level;          /* RAW_NCHW: which level; output = external slot in dst.buf.  POOL_DOWN: the mode (0 / 1) */
     int32_t lane;           /* 0 = caller's stream; k > 0 = plan-owned side stream k (independent op chains, e.g. the
@@ -164,7 +168,7 @@ typedef struct bsy_op {
                              * (slices x B x OH x OW x round_up(Cout, 32) floats) and summed IN SLICE ORDER by a second launch that applies
                              * activation and shortcut: deterministic, independent of the batch and of the tile configuration.  The host
                              * chooses the factors from the layer's SHAPE only (bs_yolo_amd/plan.py split_factors), never from the batch. */
-    int32_t reserved1;
+    int32_t kdim;           /* DECODE with nk: channels per keypoint, 2 (x, y) or 3 (x, y, visibility).  (The word was reserved1) */
     bsy_view msk[BSY_MAX_LEVELS]; /* DECODE: per-level mask-coefficient (Segment) or angle-logit (OBB) maps; see box[] above */
 } bsy_op;
 
