@@ -1,5 +1,5 @@
-"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every
-tensor bound as an external slot, poisoned views and a weight-blob builder.  Not a test module."""
+"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py, test_fp16_conv_ops.py): a single bsy_op run through bsy_plan_create /
+bsy_plan_run with every tensor bound as an external slot, poisoned views and a weight-blob builder.  Not a test module."""
 import ctypes as C
 
 import numpy as np
@@ -231,3 +231,78 @@ def ulp16(v):
 
 def ulp32(v):
     return ulp(v, 23, -149)
+
+
+# ---- the fp16 CONV op (tests/test_fp16_conv_ops.py) ----
+def conv16_op(B, H, W, ksize, stride, pad, src0, dst, w_off, b_off, src1=None, up0=0, up1=0, res=None, act=0, out_f32=0, dst_scale=1,
+              dst_dy=0, dst_dx=0, nsl_c=0, nsl_t=0, slab=None):
+    """A fp16 CONV op, fields as run_op's BSY_OP_CONV case reads them (csrc/engine.hip).  H, W: the conv's input map (a source read
+    through nearest x2 holds H / 2 x W / 2); the destination holds OH * dst_scale rows.  Split-K: ksplit = nsl_c | nsl_t << 8 and
+    box[0] = `slab`, the view of the f32 slab buffer."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_CONV, 0, B, H, W)
+    op.OH, op.OW = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    op.ksize, op.stride, op.pad, op.act, op.out_f32 = ksize, stride, pad, int(act), int(out_f32)
+    op.src0, op.dst, op.up0, op.up1 = src0, dst, up0, up1
+    if src1 is not None:
+        op.src1 = src1
+    if res is not None:
+        op.res = res
+    op.dst_scale, op.dst_dy, op.dst_dx = dst_scale, dst_dy, dst_dx
+    if nsl_c * nsl_t > 1:
+        op.ksplit = nsl_c | nsl_t << 8
+        op.box[0] = slab
+    op.w_off, op.b_off = w_off, b_off
+    return op
+
+
+PHASES = ((0, 0), (0, 1), (1, 0), (1, 1))
+
+
+def conv16_blob(w, b, deconv=False, phases=PHASES):
+    """The packed records of one fp16 conv (k = 1 or 3) in a poisoned blob: ops.pack_conv_weight's [CoutPad][Kpad] f16 matrix and
+    [CoutPad] f32 bias, NaN between the records.  deconv: w is a ConvTranspose2d(cin, cout, 2, 2) weight (cin, cout, 2, 2) and every
+    phase (dy, dx) of `phases` gets a 1x1 record of its own, W[:, :, dy, dx]^T, as plan.py's WRec kind "deconv" and
+    weights.pack_record cut it.  -> (bytes, [(w_off, b_off, dy, dx), ...])."""
+    from bs_yolo_amd import ops as O
+    assert w.shape[-1] in ((2,) if deconv else (1, 3))
+    parts = [(dy, dx, w[:, :, dy, dx].t().contiguous()[:, :, None, None]) for dy, dx in phases] if deconv else [(0, 0, w)]
+    arrays = []
+    for _, _, wk in parts:
+        wp, bp = O.pack_conv_weight(wk, b, "cpu")
+        arrays += [wp.numpy(), bp.numpy()]
+    blob, offs = poisoned_blob(arrays)
+    return blob, [(offs[2 * i], offs[2 * i + 1], dy, dx) for i, (dy, dx, _) in enumerate(parts)]
+
+
+def run_conv_cfgs(ops, ext_tensors, blob, cfgs, refused, reset, collect):
+    """ONE plan of `ops` (all CONV) kept alive over a list of kernel configuration ids.  For every id: reset() (re-poison the
+    destination), bsy_plan_set_tuning with the id on every op, bsy_plan_check_tuning -- which must answer 1 on every op for an id of
+    `cfgs` and 0 for an id of `refused`: a preset that is not valid is ignored at launch, and the case would test the heuristic
+    configuration under another name -- then, for an id of `cfgs`, run on the current stream, synchronise and keep collect()'s value.
+    -> {id: collect()}.  The plan and the engine are destroyed whatever happens."""
+    from bs_yolo_amd import lib as L
+    blob = bytes(blob) + b"\0" * max(0, 256 - len(blob))
+    n, out = len(ops), {}
+    eng, plan = C.c_void_p(), C.c_void_p()
+    L.check(L.lib.bsy_engine_create(0, C.byref(eng)))
+    try:
+        L.check(L.lib.bsy_engine_load_weights(eng, (C.c_char * len(blob)).from_buffer_copy(blob), len(blob)))
+        L.check(L.lib.bsy_plan_create(eng, (L.Op * n)(*ops), n, None, 0, C.byref(plan)))
+        n_ext = len(ext_tensors)
+        ext = (C.c_void_p * max(n_ext, 1))(*[None if t is None else t.data_ptr() for t in ext_tensors])
+        for cfg, want in [(c, 1) for c in cfgs] + [(c, 0) for c in refused]:
+            reset()
+            L.check(L.lib.bsy_plan_set_tuning(plan, (C.c_int32 * n)(*[cfg] * n), n))
+            valid = (C.c_int32 * n)()
+            L.check(L.lib.bsy_plan_check_tuning(plan, ext, n_ext, valid, n))
+            assert list(valid) == [want] * n, "configuration 0x%02x: bsy_plan_check_tuning says %s, the case expects %d" % (cfg, list(valid), want)
+            if want:
+                L.check(L.lib.bsy_plan_run(plan, ext, n_ext, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                torch.cuda.synchronize()
+                out[cfg] = collect()
+    finally:
+        if plan:
+            L.lib.bsy_plan_destroy(plan)
+        L.lib.bsy_engine_destroy(eng)
+    return out
