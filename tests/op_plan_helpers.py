@@ -1,4 +1,4 @@
-"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py, test_fp16_conv_ops.py): a single bsy_op run through bsy_plan_create /
+"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py, test_fp16_conv_ops.py, test_fp16_head_ops.py): a single bsy_op run through bsy_plan_create /
 bsy_plan_run with every tensor bound as an external slot, poisoned views and a weight-blob builder.  Not a test module."""
 import ctypes as C
 
@@ -280,7 +280,8 @@ def run_conv_cfgs(ops, ext_tensors, blob, cfgs, refused, reset, collect):
     destination), bsy_plan_set_tuning with the id on every op, bsy_plan_check_tuning -- which must answer 1 on every op for an id of
     `cfgs` and 0 for an id of `refused`: a preset that is not valid is ignored at launch, and the case would test the heuristic
     configuration under another name -- then, for an id of `cfgs`, run on the current stream, synchronise and keep collect()'s value.
-    -> {id: collect()}.  The plan and the engine are destroyed whatever happens."""
+    An entry of `cfgs` may be a tuple with one id per op instead (ops of different kernel families in one plan).
+    -> {entry: collect()}.  The plan and the engine are destroyed whatever happens."""
     from bs_yolo_amd import lib as L
     blob = bytes(blob) + b"\0" * max(0, 256 - len(blob))
     n, out = len(ops), {}
@@ -293,10 +294,13 @@ def run_conv_cfgs(ops, ext_tensors, blob, cfgs, refused, reset, collect):
         ext = (C.c_void_p * max(n_ext, 1))(*[None if t is None else t.data_ptr() for t in ext_tensors])
         for cfg, want in [(c, 1) for c in cfgs] + [(c, 0) for c in refused]:
             reset()
-            L.check(L.lib.bsy_plan_set_tuning(plan, (C.c_int32 * n)(*[cfg] * n), n))
+            per_op = list(cfg) if isinstance(cfg, tuple) else [cfg] * n
+            assert len(per_op) == n
+            L.check(L.lib.bsy_plan_set_tuning(plan, (C.c_int32 * n)(*per_op), n))
             valid = (C.c_int32 * n)()
             L.check(L.lib.bsy_plan_check_tuning(plan, ext, n_ext, valid, n))
-            assert list(valid) == [want] * n, "configuration 0x%02x: bsy_plan_check_tuning says %s, the case expects %d" % (cfg, list(valid), want)
+            assert list(valid) == [want] * n, "configuration %s: bsy_plan_check_tuning says %s, the case expects %d" % (
+                "/".join("0x%02x" % c for c in dict.fromkeys(per_op)), list(valid), want)
             if want:
                 L.check(L.lib.bsy_plan_run(plan, ext, n_ext, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
                 torch.cuda.synchronize()
@@ -306,3 +310,32 @@ def run_conv_cfgs(ops, ext_tensors, blob, cfgs, refused, reset, collect):
             L.lib.bsy_plan_destroy(plan)
         L.lib.bsy_engine_destroy(eng)
     return out
+
+
+# ---- the fused Detect head ops (tests/test_fp16_head_ops.py) ----
+def conv16_records(convs):
+    """The packed records of several fp16 convs [(w, b), ...] in ONE poisoned blob, every matrix and every bias vector a record of its
+    own with NaN behind it.  -> (bytes, [(w_off, b_off), ...])."""
+    from bs_yolo_amd import ops as O
+    arrays = []
+    for w, b in convs:
+        wp, bp = O.pack_conv_weight(w, b, "cpu")
+        arrays += [wp.numpy(), bp.numpy()]
+    blob, offs = poisoned_blob(arrays)
+    return blob, [(offs[2 * i], offs[2 * i + 1]) for i in range(len(convs))]
+
+
+def head16_op(B, H, W, ksize, src0, y, w_off, b_off, mode, cout, A, a0, stride, out_dtype, raw=None, act=0, tail=None, res=None):
+    """A fp16 CONV op with the Detect decoder in its epilogue, fields as Plan._decoding_conv emits them and run_op's BSY_OP_CONV case
+    reads them: out_f32 = `mode` (2: class scores, 3: DFL boxes), dst = `y`, the (B, y.C, A) prediction tensor of `out_dtype` whose
+    anchors [a0, a0 + H * W) belong to this level, nl = the conv's couts, lvl_stride[0] = the level's stride, box[0] = `raw`, the level's
+    (B, raw.C, H, W) raw map of the same dtype (None: no raw map).  tail = (w2_off, b2_off): the box-branch tail -- this op is the 3x3
+    conv (64 couts, `act`) and the record named is the branch's 64 -> 64 1x1 conv."""
+    op = conv16_op(B, H, W, ksize, 1, ksize // 2, src0, y, w_off, b_off, res=res, act=act, out_f32=mode)
+    op.nl, op.A, op.out_dtype = cout, A, out_dtype
+    op.lvl_h[0], op.lvl_h[1], op.lvl_w[0], op.lvl_stride[0] = H, a0, W, float(stride)
+    if raw is not None:
+        op.box[0] = raw
+    if tail is not None:
+        op.mid_c, op.w2_off, op.b2_off = 64, tail[0], tail[1]
+    return op
