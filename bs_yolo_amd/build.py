@@ -55,6 +55,8 @@ SOURCES = {
     "conv32x_mfma.hip": ["-fno-vectorize"],  # fp32x mode: split-f16 operands on the fp16 matrix pipe
     "attention32x.hip": ["-fno-vectorize"],
     "engine.hip": [],
+    "plan_ops.hip": [],
+    "ops_api.hip": [],
 }
 
 

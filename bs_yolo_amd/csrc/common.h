@@ -30,42 +30,44 @@ void bsy_set_error(const char* fmt, ...);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// ---- resolved (pointer-level) launch arguments; filled by the engine or by the stand-alone C entry points ----
+// ---- resolved (pointer-level) launch arguments; filled by the builders of op_args.h (the engine's op records) or by the stand-alone C
+// entry points (ops_api.hip).  Every field starts zeroed: a field a filler does not mention is off, whichever filler it is. ----
 struct ConvArgs {
-    const half_t* src0;  // incl. channel offset
-    const half_t* src1;  // second concat operand or nullptr
-    int ld0, ld1;        // channels per pixel row of each source buffer
-    int C0, C1;          // channels taken from each source (Cin = C0 + C1), multiples of 8
-    int up0, up1;        // nearest-x2 read
-    int B, H, W, OH, OW; // logical input / output extents
-    int ksize, stride, pad;
-    const half_t* wgt;   // [CoutPad][Kpad]
-    const float* bias;   // [CoutPad]
-    void* dst;           // incl. channel offset; f16 or f32
-    int ldd, Cout, out_f32;
-    const half_t* res;   // incl. channel offset or nullptr
-    int ldr;
-    int act;
-    int dst_scale, dst_dy, dst_dx;
-    int cfg;  // kernel configuration id (tile << 4 | variant) chosen by the autotuner; < 0 = heuristic
+    const half_t* src0 = nullptr;  // incl. channel offset
+    const half_t* src1 = nullptr;  // second concat operand or nullptr
+    int ld0 = 0, ld1 = 0;          // channels per pixel row of each source buffer
+    int C0 = 0, C1 = 0;            // channels taken from each source (Cin = C0 + C1), multiples of 8
+    int up0 = 0, up1 = 0;          // nearest-x2 read
+    int B = 0, H = 0, W = 0, OH = 0, OW = 0;  // logical input / output extents
+    int ksize = 0, stride = 0, pad = 0;
+    const half_t* wgt = nullptr;   // [CoutPad][Kpad]
+    const float* bias = nullptr;   // [CoutPad]
+    void* dst = nullptr;           // incl. channel offset; f16 or f32
+    int ldd = 0, Cout = 0, out_f32 = 0;
+    const half_t* res = nullptr;   // incl. channel offset or nullptr
+    int ldr = 0;
+    int act = 0;
+    int dst_scale = 0, dst_dy = 0, dst_dx = 0;
+    int cfg = 0;  // kernel configuration id (tile << 4 | variant) chosen by the autotuner; < 0 = heuristic
     // Fused Detect decoder (epi != 0: the conv is the last layer of a head branch and writes the decoded prediction tensor
     // y (B, nrows, A) directly instead of a logit map; `dst` is then unused):
     //   epi 2: class scores  y[n, 4 + c, a0 + pix] = sigmoid(logit)                 (head.py:147)
     //   epi 3: boxes         y[n, 0..3, a0 + pix]  = dist2bbox(DFL(logits)) * stride (head.py:141-146, block.py:58-77)
     // raw (optional, may be null): the level's raw map (B, rawC, OH, OW) that Detect.forward also returns (head.py:74),
     // box logits at channels 0..63, class logits at 64...
-    int epi;
-    void* y;
-    int y_f32, A, a0, nrows;
-    float lvl_stride;
-    void* raw;
-    int raw_f32, rawC;
+    int epi = 0;
+    void* y = nullptr;
+    int y_f32 = 0, A = 0, a0 = 0, nrows = 0;
+    float lvl_stride = 0.f;
+    void* raw = nullptr;
+    int raw_f32 = 0, rawC = 0;
     // Box-branch tail (3x3 conv + the branch's last 1x1 conv + DFL decode in one launch; conv_patch.hip conv3x3_patch_kernel<.., TAIL>):
     // this op is the 3x3 conv (Cout = 64, its map never reaches HBM), tail_wgt / tail_bias the packed 64 -> 64 1x1 conv, epi = 3 and
     // the decoder fields above describe what the tail writes.  nullptr: no tail.
-    const half_t* tail_wgt;
-    const float* tail_bias;
+    const half_t* tail_wgt = nullptr;
+    const float* tail_bias = nullptr;
     // Split-K (latency mode): nsl_c channel slices x nsl_t tap slices of the layer's K walk, computed by separate workgroups of one launch
     // into f32 slabs of split_ws (nsl_c * nsl_t * B * OH * OW * round_up(Cout, 32) floats) and summed in slice order by a second
     // launch.  0 / 1 x 0 / 1: off.  Implicit-GEMM kernel only (conv_cfg_valid).
@@ -79,127 +81,129 @@ bool conv_cfg_valid(const ConvArgs& a, int cfg);
 int conv_korder(const ConvArgs& a);  // the layer's K walk (0 packed order, 1 / 2 chunk-major with 32- / 64-channel chunks): a function of its shape
 
 struct ConvFirstArgs {
-    const void* img;
-    int img_dtype;
-    int B, H, W, OH, OW, ksize, stride, pad;
-    const void* w;   // packed f16 [CoutPad][32], k = (kh, kw, c)  (same layout as every other conv)
-    const float* b;  // [CoutPad]
-    half_t* dst;
-    int ldd, Cout, act;
+    const void* img = nullptr;
+    int img_dtype = 0;
+    int B = 0, H = 0, W = 0, OH = 0, OW = 0, ksize = 0, stride = 0, pad = 0;
+    const void* w = nullptr;   // packed f16 [CoutPad][32], k = (kh, kw, c)  (same layout as every other conv)
+    const float* b = nullptr;  // [CoutPad]
+    half_t* dst = nullptr;
+    int ldd = 0, Cout = 0, act = 0;
 };
 int launch_conv_first(const ConvFirstArgs& a, hipStream_t s);
 
 // Fused stem (stem_fused.hip): image -> Conv 3x3 s2 (3 -> C0) -> Conv 3x3 s2 (C0 -> C1), layer 0 kept on chip.
 struct StemArgs {
-    const void* img;
-    int img_dtype;
-    int B, H, W, OH, OW;    // image extent; OH/OW = layer-1 output extent
-    const void* w0;         // layer 0: packed f16 [CoutPad][32]
-    const float* b0;
-    const void* w1;         // layer 1: packed f16 [CoutPad][Kpad1], k = (kh, kw, c)
-    const float* b1;
-    int C0, C1, Kpad1;
-    half_t* dst;
-    int ldd, act;
+    const void* img = nullptr;
+    int img_dtype = 0;
+    int B = 0, H = 0, W = 0, OH = 0, OW = 0;  // image extent; OH/OW = layer-1 output extent
+    const void* w0 = nullptr;  // layer 0: packed f16 [CoutPad][32]
+    const float* b0 = nullptr;
+    const void* w1 = nullptr;  // layer 1: packed f16 [CoutPad][Kpad1], k = (kh, kw, c)
+    const float* b1 = nullptr;
+    int C0 = 0, C1 = 0, Kpad1 = 0;
+    half_t* dst = nullptr;
+    int ldd = 0, act = 0;
 };
 bool stem_fused_supported(int C0, int C1, int H, int W);
 int launch_stem_fused(const StemArgs& a, hipStream_t s);
 
 // Fused Bottleneck (bneck_fused.hip): y = x + conv3x3(conv3x3(x)), hidden map kept on chip.
 struct BneckArgs {
-    const half_t* src;  // (B,H,W,lds) view of C channels
-    int lds;
-    int B, H, W, C, CH;
-    const void *w1, *w2;   // packed f16 [CoutPad][Kpad1] (C -> CH) and [CoutPad][Kpad2] (CH -> C)
-    const float *b1, *b2;
-    int Kpad1, Kpad2;
-    half_t* dst;
-    int ldd, act;
+    const half_t* src = nullptr;  // (B,H,W,lds) view of C channels
+    int lds = 0;
+    int B = 0, H = 0, W = 0, C = 0, CH = 0;
+    const void *w1 = nullptr, *w2 = nullptr;  // packed f16 [CoutPad][Kpad1] (C -> CH) and [CoutPad][Kpad2] (CH -> C)
+    const float *b1 = nullptr, *b2 = nullptr;
+    int Kpad1 = 0, Kpad2 = 0;
+    half_t* dst = nullptr;
+    int ldd = 0, act = 0;
 };
 bool bneck_fused_supported(int C, int CH);
 int launch_bneck_fused(const BneckArgs& a, hipStream_t s);
 
 // Fused C3k2 block (c3k2_fused.hip): out = cv2(cat(y0, y1, y1 + m.cv2(m.cv1(y1)))), [y0 | y1] = cv1(x); nothing but x and out in HBM.
 struct C3k2Args {
-    const half_t* src;  // (B,H,W,lds) view of Cin channels
-    int lds;
-    int B, H, W, Cin, C, C2;           // C = hidden width c of the block (cv1 -> 2c), bottleneck hidden c/2, output C2
-    const void *w1, *wa, *wb, *w4;     // packed f16 [CoutPad][Kpad]: cv1 (Cin -> 2c), m.cv1 (c -> c/2, 3x3), m.cv2 (c/2 -> c, 3x3), cv2 (3c -> C2)
-    const float *b1, *ba, *bb, *b4;
-    half_t* dst;
-    int ldd;
+    const half_t* src = nullptr;  // (B,H,W,lds) view of Cin channels
+    int lds = 0;
+    int B = 0, H = 0, W = 0, Cin = 0, C = 0, C2 = 0;  // C = hidden width c of the block (cv1 -> 2c), bottleneck hidden c/2, output C2
+    // packed f16 [CoutPad][Kpad]: cv1 (Cin -> 2c), m.cv1 (c -> c/2, 3x3), m.cv2 (c/2 -> c, 3x3), cv2 (3c -> C2)
+    const void *w1 = nullptr, *wa = nullptr, *wb = nullptr, *w4 = nullptr;
+    const float *b1 = nullptr, *ba = nullptr, *bb = nullptr, *b4 = nullptr;
+    half_t* dst = nullptr;
+    int ldd = 0;
 };
 bool c3k2_fused_supported(int Cin, int C, int C2);
 int launch_c3k2_fused(const C3k2Args& a, hipStream_t s);
 
 // ---- BS-YOLO-only modules (bsyolo_ops.hip) ----------------------------------------------------------------------------
 struct DwGenArgs {       // depthwise kh x kw, stride 1 / 2, "same" padding, + bias (+SiLU)
-    const half_t* src;
-    int lds;
-    int B, H, W, C, OH, OW, kh, kw, stride;
-    const float* w;      // [kh*kw][wld] (already offset to this launch's first channel)
-    int wld;
-    const float* b;
-    half_t* dst;
-    int ldd, act_c;      // SiLU on channels [0, act_c) of this launch, identity on the rest
+    const half_t* src = nullptr;
+    int lds = 0;
+    int B = 0, H = 0, W = 0, C = 0, OH = 0, OW = 0, kh = 0, kw = 0, stride = 0;
+    const float* w = nullptr;  // [kh*kw][wld] (already offset to this launch's first channel)
+    int wld = 0;
+    const float* b = nullptr;
+    half_t* dst = nullptr;
+    int ldd = 0, act_c = 0;    // SiLU on channels [0, act_c) of this launch, identity on the rest
     int ident_c0 = 0;    // > 0: channels [ident_c0, C) carry an identity kernel (centre tap 1, bias 0: PMSFA.conv3's pass-through half,
                          // weights.py "dwg_ext") -- the tiled kernels write x + 0 for them, which is what the full tap loop returns
 };
 int launch_dwconv_generic(const DwGenArgs& a, hipStream_t s);
 struct PmsfaArgs {       // PMSFA's tail in one launch (pmsfa_fused.hip): dst = conv4([conv3(conv2(p1)[:C/4]) | conv2(p1)[C/4:] | p2]) + x, P = [p1 | p2] = conv1(x)
-    const half_t* P;     // conv1's output, C channels
-    int ldp;
-    const half_t* x;     // the module's input (shortcut operand), C channels
-    int ldx;
-    half_t* dst;
-    int ldd;
-    int B, H, W, C;
-    const float* w2;     // conv2: depthwise 5x5 on C/2 channels, f32 [25][wld2]
-    const float* b2;
-    int wld2;
-    const float* w3;     // conv3: depthwise 7x7 on C/4 channels, f32 [49][wld3]
-    const float* b3;
-    int wld3;
-    const half_t* w4;    // conv4: packed 1x1 weights [cout][kpad4]
-    const float* b4;
-    int kpad4;
+    const half_t* P = nullptr;   // conv1's output, C channels
+    int ldp = 0;
+    const half_t* x = nullptr;   // the module's input (shortcut operand), C channels
+    int ldx = 0;
+    half_t* dst = nullptr;
+    int ldd = 0;
+    int B = 0, H = 0, W = 0, C = 0;
+    const float* w2 = nullptr;   // conv2: depthwise 5x5 on C/2 channels, f32 [25][wld2]
+    const float* b2 = nullptr;
+    int wld2 = 0;
+    const float* w3 = nullptr;   // conv3: depthwise 7x7 on C/4 channels, f32 [49][wld3]
+    const float* b3 = nullptr;
+    int wld3 = 0;
+    const half_t* w4 = nullptr;  // conv4: packed 1x1 weights [cout][kpad4]
+    const float* b4 = nullptr;
+    int kpad4 = 0;
 };
 bool pmsfa_tail_supported(int C);
 int launch_pmsfa_tail(const PmsfaArgs& a, hipStream_t s);
 int launch_copy_view(const half_t* src, int lds_, int up, int B, int H, int W, int C, half_t* dst, int ldd, hipStream_t s);
 int launch_gap(const half_t* src, int lds_, int B, int H, int W, int C, half_t* out, int ldo, hipStream_t s);
 struct MscaSpArgs {
-    const half_t* src;
-    int lds, B, H, W, C;
-    const float* w[9];  // conv0, conv0_1, conv0_2, conv1_1, conv1_2, conv2_1, conv2_2, conv3_1, conv3_2
-    const float* b[9];
-    half_t* br[4];
-    int ldb[4];
-    half_t* gap[4];
-    int ldg[4];
+    const half_t* src = nullptr;
+    int lds = 0, B = 0, H = 0, W = 0, C = 0;
+    const float* w[9] = {};  // conv0, conv0_1, conv0_2, conv1_1, conv1_2, conv2_1, conv2_2, conv3_1, conv3_2
+    const float* b[9] = {};
+    half_t* br[4] = {};
+    int ldb[4] = {};
+    half_t* gap[4] = {};
+    int ldg[4] = {};
 };
 bool msca_spatial_supported(int H, int W);
 int launch_msca_spatial(const MscaSpArgs& a, hipStream_t s);
 struct MixArgs {
-    const half_t* br[4];
-    int ldb[4];
-    const float* lg[4];  // branch logits (B, ldl) f32
-    int ldl[4];
-    int B, HW, C;
-    half_t* dst;
-    int ldd;
+    const half_t* br[4] = {};
+    int ldb[4] = {};
+    const float* lg[4] = {};  // branch logits (B, ldl) f32
+    int ldl[4] = {};
+    int B = 0, HW = 0, C = 0;
+    half_t* dst = nullptr;
+    int ldd = 0;
 };
 int launch_msca_mix(const MixArgs& a, hipStream_t s);
 int launch_mul(const half_t* a, int lda, const half_t* b, int ldb, long long npix, int C, half_t* dst, int ldd, hipStream_t s);
 struct ElaArgs {
-    const half_t* src;
-    int lds;
-    int B, H, W, C, k;
-    const float *wsp, *wch, *gnw, *gnb;  // spatial_conv [C][k], ch_att conv [C][k], GroupNorm weight / bias [C]
-    float ch_coef, sp_coef, res_coef;    // sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight)
-    float* scratch;                      // ela_scratch_floats(H, W, C) * B floats
-    half_t* dst;
-    int ldd;
+    const half_t* src = nullptr;
+    int lds = 0;
+    int B = 0, H = 0, W = 0, C = 0, k = 0;
+    // spatial_conv [C][k], ch_att conv [C][k], GroupNorm weight / bias [C]
+    const float *wsp = nullptr, *wch = nullptr, *gnw = nullptr, *gnb = nullptr;
+    float ch_coef = 0.f, sp_coef = 0.f, res_coef = 0.f;  // sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight)
+    float* scratch = nullptr;                            // ela_scratch_floats(H, W, C) * B floats
+    half_t* dst = nullptr;
+    int ldd = 0;
 };
 size_t ela_scratch_floats(int H, int W, int C);
 int launch_ela(const ElaArgs& a, hipStream_t s);
@@ -207,22 +211,22 @@ int launch_ela_gate(const ElaArgs& a, hipStream_t s);
 
 // ---- fp32 correctness mode (ref32.hip): plans with bsy_op.prec == 1; NHWC f32 views --------------------------------------------
 struct Conv32Args {
-    const void* src0;    // f32 view, or (first) the BCHW image in src_dtype
-    const void* src1;
-    int src_dtype, first;
-    int ld0, ld1, C0, C1, up0, up1;
-    int B, H, W, OH, OW, ks, stride, pad;
-    const float* w;      // f32 [k*k*Cin][Cout], k = (kh, kw, cin)
-    const float* bias;   // f32 [Cout]
-    float* dst;
-    int ldd, Cout;
-    const float* res;
-    int ldr, act, dst_scale, dst_dy, dst_dx;
+    const void* src0 = nullptr;  // f32 view, or (first) the BCHW image in src_dtype
+    const void* src1 = nullptr;
+    int src_dtype = 0, first = 0;
+    int ld0 = 0, ld1 = 0, C0 = 0, C1 = 0, up0 = 0, up1 = 0;
+    int B = 0, H = 0, W = 0, OH = 0, OW = 0, ks = 0, stride = 0, pad = 0;
+    const float* w = nullptr;     // f32 [k*k*Cin][Cout], k = (kh, kw, cin)
+    const float* bias = nullptr;  // f32 [Cout]
+    float* dst = nullptr;
+    int ldd = 0, Cout = 0;
+    const float* res = nullptr;
+    int ldr = 0, act = 0, dst_scale = 0, dst_dy = 0, dst_dx = 0;
     // fp32x mode (conv32x_mfma.hip): the same weights split into two f16 planes [Cout][wx_kpad], w = hi + lo, K padded to 32
     // with zeros; nullptr = the exact fp32 kernels only
-    const half_t* wx_hi;
-    const half_t* wx_lo;
-    int wx_kpad;
+    const half_t* wx_hi = nullptr;
+    const half_t* wx_lo = nullptr;
+    int wx_kpad = 0;
 };
 int launch_conv32(const Conv32Args& a, hipStream_t s);          // routes to the MFMA kernel where it applies, else the scalar one
 bool conv32x_mfma_supported(const Conv32Args& a);               // conv32x_mfma.hip: split-f16 operands, three f16 MFMAs per product
@@ -231,25 +235,25 @@ int launch_conv32_scalar(const Conv32Args& a, hipStream_t s);   // ref32.hip: on
 bool conv32_mfma_supported(const Conv32Args& a);                // conv32_mfma.hip: v_mfma_f32_32x32x2_f32, the same chain bit for bit
 int launch_conv32_mfma(const Conv32Args& a, hipStream_t s);
 struct Dw32Args {
-    const float* src;
-    int lds, B, H, W, C, OH, OW, kh, kw, stride;
-    const float* w;      // f32 [kh*kw][wld]
-    int wld;
-    const float* b;
-    float* dst;
-    int ldd, act_c;
-    const float* res;
-    int ldr;
+    const float* src = nullptr;
+    int lds = 0, B = 0, H = 0, W = 0, C = 0, OH = 0, OW = 0, kh = 0, kw = 0, stride = 0;
+    const float* w = nullptr;  // f32 [kh*kw][wld]
+    int wld = 0;
+    const float* b = nullptr;
+    float* dst = nullptr;
+    int ldd = 0, act_c = 0;
+    const float* res = nullptr;
+    int ldr = 0;
 };
 int launch_dw32(const Dw32Args& a, hipStream_t s);
 struct Mix32Args {
-    const float* br[4];
-    int ldb[4];
-    const float* lg[4];
-    int ldl[4];
-    int B, HW, C;
-    float* dst;
-    int ldd;
+    const float* br[4] = {};
+    int ldb[4] = {};
+    const float* lg[4] = {};
+    int ldl[4] = {};
+    int B = 0, HW = 0, C = 0;
+    float* dst = nullptr;
+    int ldd = 0;
 };
 int launch_mix32(const Mix32Args& a, hipStream_t s);
 int launch_sppf32(float* buf, int ld, int B, int H, int W, int C, hipStream_t s);
@@ -265,29 +269,29 @@ int launch_ela32(const ElaArgs& a, const float* src, float* dst, hipStream_t s);
 
 // Fused DWConv 3x3 (+SiLU) -> Conv 1x1 (+act) (dwpw_fused.hip: dwpw_fused_kernel)
 struct DwPwArgs {
-    const half_t* src;
-    int lds;
-    int B, H, W, C;
-    const float *dww, *dwb;  // depthwise f32 [9][C], [C]
-    const void* wgt;         // 1x1 packed f16 [CoutPad][Kpad]
-    const float* bias;
-    half_t* dst;
-    int ldd, Cout, act;
+    const half_t* src = nullptr;
+    int lds = 0;
+    int B = 0, H = 0, W = 0, C = 0;
+    const float *dww = nullptr, *dwb = nullptr;  // depthwise f32 [9][C], [C]
+    const void* wgt = nullptr;                   // 1x1 packed f16 [CoutPad][Kpad]
+    const float* bias = nullptr;
+    half_t* dst = nullptr;
+    int ldd = 0, Cout = 0, act = 0;
 };
 bool dwpw_fused_supported(int C, int Cout);
 int launch_dwpw_fused(const DwPwArgs& a, hipStream_t s);
 
 struct DwArgs {
-    const half_t* src;
-    int lds;
-    int B, H, W, C;
-    const float* w;  // [9][C]
-    const float* b;
-    half_t* dst;
-    int ldd;
-    int act;
-    const half_t* res;
-    int ldr;
+    const half_t* src = nullptr;
+    int lds = 0;
+    int B = 0, H = 0, W = 0, C = 0;
+    const float* w = nullptr;  // [9][C]
+    const float* b = nullptr;
+    half_t* dst = nullptr;
+    int ldd = 0;
+    int act = 0;
+    const half_t* res = nullptr;
+    int ldr = 0;
 };
 int launch_dwconv(const DwArgs& a, hipStream_t s);
 int launch_sppf_pool(half_t* buf, int ld, int B, int H, int W, int C, hipStream_t s);
@@ -297,12 +301,12 @@ int launch_pool_down(const void* src, int lds_, int soff, void* dst, int ldd, in
 int launch_s2d(const void* img, int img_dtype, int B, int H, int W, half_t* dst, int ldd, hipStream_t s);
 
 struct AttnArgs {
-    const half_t* qkv;
-    int ld;
-    int B, N, heads, key_dim, head_dim;
-    float scale;
-    half_t* out;
-    int ldo;
+    const half_t* qkv = nullptr;
+    int ld = 0;
+    int B = 0, N = 0, heads = 0, key_dim = 0, head_dim = 0;
+    float scale = 0.f;
+    half_t* out = nullptr;
+    int ldo = 0;
     // pe (block.py:4286 `+ self.pe(v)`) folded into the epilogue: depthwise 3x3 + bias on v over the H x W map (H * W = N), added to
     // the attention output as dwconv3x3_kernel<false, true> adds it.  pe_w f32 [9][heads * head_dim], pe_b f32 [heads * head_dim]; null: no pe
     int H = 0, W = 0;
@@ -313,21 +317,21 @@ int launch_attention(const AttnArgs& a, hipStream_t s, int impl = 0);  // impl 0
 bool attention_supported(int key_dim, int head_dim);
 
 struct DecodeArgs {
-    const float* box[BSY_MAX_LEVELS];
-    const float* cls[BSY_MAX_LEVELS];
-    const float* msk[BSY_MAX_LEVELS];
-    int ldb[BSY_MAX_LEVELS], ldc[BSY_MAX_LEVELS], ldm[BSY_MAX_LEVELS];
-    int h[BSY_MAX_LEVELS], w[BSY_MAX_LEVELS];
-    float stride[BSY_MAX_LEVELS];
-    int nl, B, nc, nm, A;
-    void* y;
-    int y_dtype;
-    int ne;  // OBB angle channels (0 / 1): msk[l] then holds the angle logits and nm is 0
-    int halves;  // 1: the DFL sums run in the fused head epilogue's order at every level count (a Detect plan whose decode launch stands
-                 // in for the fused head, bsy_op.act); 0: that order for heads of four levels only, bin order up to three
-    int nk, kdim;  // Pose keypoint channels (nkpt * kdim; 0: none) and channels per keypoint (2 / 3): msk[l] then holds the level's keypoint
-                   // logits (nm = ne = 0); y gets nk decoded rows behind the scores (Pose.kpts_decode, kpt_decode.h)
-    void* kraw;    // nk: (B, nk, A) tensor of y's dtype for the undecoded logits, or null
+    const float* box[BSY_MAX_LEVELS] = {};
+    const float* cls[BSY_MAX_LEVELS] = {};
+    const float* msk[BSY_MAX_LEVELS] = {};
+    int ldb[BSY_MAX_LEVELS] = {}, ldc[BSY_MAX_LEVELS] = {}, ldm[BSY_MAX_LEVELS] = {};
+    int h[BSY_MAX_LEVELS] = {}, w[BSY_MAX_LEVELS] = {};
+    float stride[BSY_MAX_LEVELS] = {};
+    int nl = 0, B = 0, nc = 0, nm = 0, A = 0;
+    void* y = nullptr;
+    int y_dtype = 0;
+    int ne = 0;  // OBB angle channels (0 / 1): msk[l] then holds the angle logits and nm is 0
+    int halves = 0;  // 1: the DFL sums run in the fused head epilogue's order at every level count (a Detect plan whose decode launch stands
+                     // in for the fused head, bsy_op.act); 0: that order for heads of four levels only, bin order up to three
+    int nk = 0, kdim = 0;  // Pose keypoint channels (nkpt * kdim; 0: none) and channels per keypoint (2 / 3): msk[l] then holds the level's keypoint
+                           // logits (nm = ne = 0); y gets nk decoded rows behind the scores (Pose.kpts_decode, kpt_decode.h)
+    void* kraw = nullptr;  // nk: (B, nk, A) tensor of y's dtype for the undecoded logits, or null
 };
 int launch_decode(const DecodeArgs& a, hipStream_t s);
 // val_match.hip: the validator's matching rule on an IoU matrix (B, Lmax, max_det) made elsewhere (val_masks.hip); arguments as

@@ -1,60 +1,15 @@
-// Engine / plan objects behind the C ABI (include/bsyolo.h) and the stand-alone operator entry points.
+// Engine / plan objects behind the C ABI (include/bsyolo.h): lifecycle, arena, guards, plan replay, graph capture, tuning, profile.
+// What an op record means is op_args.h, which launcher it goes to plan_ops.hip; the stand-alone operators are ops_api.hip.
 //
 // The host side (bs_yolo_amd/plan.py) flattens the model graph -- the work of BaseModel._predict_once
 // (nn/tasks.py:138-165) and of every module forward on the path -- into a list of bsy_op records that reference
 // workspace buffers by index.  A plan owns that workspace in HBM (one allocation, 256-byte aligned slices) and replays
 // the op list on the caller's stream; nothing here synchronises or allocates per call.
 #include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
-#include <vector>
 
-#include "common.h"
-#include "postproc.h"
-
-struct bsy_engine {
-    int device = 0;
-    void* weights = nullptr;
-    size_t weight_bytes = 0;
-    // ONE activation arena shared by every plan created with bsy_plan_create_arena (sized for the largest of them; a plan
-    // addresses it through host-assigned offsets).  Grows, never shrinks; plans resolve the base at run time.
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
-    unsigned arena_gen = 0;  // bumped whenever the arena moves: captured graphs hold its addresses
-    unsigned weights_gen = 0;  // bumped by every bsy_engine_load_weights: captured graphs hold addresses inside the weight blob too
-};
-
-struct bsy_plan {
-    bsy_engine* eng = nullptr;
-    std::vector<bsy_op> ops;
-    std::vector<size_t> buf_off;
-    std::vector<size_t> buf_size;
-    char* workspace = nullptr;     // plan-owned workspace (bsy_plan_create) ...
-    size_t workspace_bytes = 0;
-    bool use_arena = false;        // ... or the engine's shared arena (bsy_plan_create_arena): base = eng->arena
-    char* base() const { return use_arena ? eng->arena : workspace; }
-    std::vector<hipEvent_t> events;
-    // side streams ("lanes") for independent op chains + the events that fork / join them
-    std::vector<hipStream_t> lanes;      // index 0 unused (lane 0 = caller's stream)
-    std::vector<hipEvent_t> lane_done;   // per lane: recorded at its tail before a join
-    std::vector<hipEvent_t> lane_fork;   // per lane: recorded on the caller's stream where the lane forks (one event per lane:
-                                         // an event that still has a waiter pending is never re-recorded)
-    float last_event_overhead_ms = 0.f;  // bsy_plan_profile: median empty event interval of the last call
-    size_t guard = 0;                    // bytes of guard band behind every buffer (BSY_PLAN_GUARD)
-    // captured forwards (bsy_plan_graph_launch): one executable graph per set of external pointers, oldest first
-    struct Captured {
-        std::vector<void*> ext;
-        unsigned arena_gen, weights_gen;
-        hipGraphExec_t exec;
-    };
-    std::vector<Captured> graphs;
-    bool graph_unavailable = false;      // a capture failed once: this plan runs eagerly from then on
-    void drop_graphs() {
-        for (auto& g : graphs) (void)hipGraphExecDestroy(g.exec);
-        graphs.clear();
-    }
-};
+#include "engine.h"
 
 extern "C" int bsy_sizeof_op(void) { return (int)sizeof(bsy_op); }  // the host mirrors the record with ctypes: checked at load
 
@@ -99,8 +54,6 @@ extern "C" int bsy_engine_load_weights(bsy_engine* e, const void* host_blob, siz
     e->weight_bytes = bytes;
     return BSY_OK;
 }
-
-extern "C" void bsy_plan_destroy(bsy_plan* p);
 
 static int plan_make_lanes(bsy_plan* p) {
     int max_lane = 0;
@@ -237,440 +190,6 @@ extern "C" void bsy_plan_destroy(bsy_plan* p) {
     delete p;
 }
 
-namespace {
-struct Resolver {
-    const bsy_plan* p;
-    void* const* ext;
-    int n_ext;
-    bool ok = true;
-    // returns base pointer of the buffer (no channel offset) or nullptr when the view is absent
-    char* base(const bsy_view& v) {
-        if (v.buf < 0) return nullptr;
-        if (v.buf >= BSY_EXT_BASE) {
-            const int s = v.buf - BSY_EXT_BASE;
-            if (s >= n_ext || !ext[s]) { ok = false; bsy_set_error("plan_run: external slot %d not bound", s); return nullptr; }
-            return (char*)ext[s];
-        }
-        if ((size_t)v.buf >= p->buf_off.size()) { ok = false; bsy_set_error("plan_run: buffer %d out of range", v.buf); return nullptr; }
-        return p->base() + p->buf_off[v.buf];
-    }
-    half_t* h(const bsy_view& v) { char* b = base(v); return b ? (half_t*)b + v.coff : nullptr; }
-    float* f(const bsy_view& v) { char* b = base(v); return b ? (float*)b + v.coff : nullptr; }
-};
-
-// Classify's tail (csrc/classify.hip): the logit map is f32 in every precision mode, so both op switches come here.  x and the
-// top-k rows are optional outputs: an unbound slot leaves them out (the rows only together).
-int run_classify_tail(const bsy_op& op, Resolver& R, hipStream_t s) {
-    auto bound = [&](const bsy_view& v) { return v.buf >= BSY_EXT_BASE && v.buf - BSY_EXT_BASE < R.n_ext && R.ext[v.buf - BSY_EXT_BASE]; };
-    const float* logits = R.f(op.src0);
-    void* y = R.base(op.dst);
-    void* x = bound(op.res) ? R.base(op.res) : nullptr;
-    const bool rows = op.ksize > 0 && bound(op.box[0]) && bound(op.cls[0]);
-    int32_t* idx = rows ? (int32_t*)R.base(op.box[0]) : nullptr;
-    float* val = rows ? (float*)R.base(op.cls[0]) : nullptr;
-    if (!R.ok) return BSY_ERR_ARG;
-    return launch_classify_tail(logits, op.src0.ld, op.B, op.nc, y, x, op.out_dtype, rows ? op.ksize : 0, idx, val, s);
-}
-
-// fp32 correctness mode (bsy_op.prec == 1): same op records, f32 views, kernels of ref32.hip.  DECODE and RAW_NCHW consume f32
-// logit maps in both modes and fall through to the common path.
-
-int run_op_f32(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, bool& handled) {
-    const char* wb = (const char*)p->eng->weights;
-    handled = true;
-    switch (op.kind) {
-        case BSY_OP_CONV_FIRST:
-        case BSY_OP_CONV: {
-            Conv32Args a;
-            memset(&a, 0, sizeof(a));
-            a.first = op.kind == BSY_OP_CONV_FIRST;
-            a.src0 = a.first ? (const void*)R.base(op.src0) : (const void*)R.f(op.src0);
-            a.src_dtype = op.in_dtype;
-            a.src1 = R.f(op.src1);
-            a.ld0 = op.src0.ld; a.ld1 = op.src1.buf >= 0 ? op.src1.ld : 0;
-            a.C0 = op.src0.C; a.C1 = op.src1.buf >= 0 ? op.src1.C : 0;
-            a.up0 = op.up0; a.up1 = op.up1;
-            a.B = op.B; a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW; a.ks = op.ksize; a.stride = op.stride; a.pad = op.pad;
-            a.w = (const float*)(wb + op.w_off); a.bias = (const float*)(wb + op.b_off);
-            a.dst = R.f(op.dst); a.ldd = op.dst.ld; a.Cout = op.dst.C;
-            a.res = R.f(op.res); a.ldr = op.res.buf >= 0 ? op.res.ld : 0;
-            a.act = op.act; a.dst_scale = op.dst_scale > 0 ? op.dst_scale : 1; a.dst_dy = op.dst_dy; a.dst_dx = op.dst_dx;
-            if (op.out_f32 >= 2) BSY_FAIL(BSY_ERR_ARG, "fp32 mode: fused Detect decoder ops are not part of fp32 plans");
-            if (!R.ok) return BSY_ERR_ARG;
-            if (op.prec == 2) {  // fp32x: split-f16 planes behind the f32 matrix; shapes the kernel does not take stay exact
-                // byte offsets of the two f16 weight planes the record carries behind its f32 matrix (weights.py pack_record):
-                // [f32 K x Cout][pad to 256][hi: Cout x Kpad f16][pad to 256][lo: Cout x Kpad f16], Kpad = K rounded up to 32
-                const size_t K = (size_t)a.ks * a.ks * (a.C0 + a.C1), kpad = (K + 31) & ~(size_t)31;
-                const size_t hi_off = align256(K * a.Cout * 4), lo_off = hi_off + align256((size_t)a.Cout * kpad * 2);
-                a.wx_hi = (const half_t*)(wb + op.w_off + hi_off);
-                a.wx_lo = (const half_t*)(wb + op.w_off + lo_off);
-                a.wx_kpad = (int)kpad;
-                if (conv32x_mfma_supported(a)) return launch_conv32x_mfma(a, s);
-            }
-            return launch_conv32(a, s);
-        }
-        case BSY_OP_DWCONV:
-        case BSY_OP_DWCONV_G: {
-            Dw32Args a;
-            memset(&a, 0, sizeof(a));
-            const bool g = op.kind == BSY_OP_DWCONV_G;
-            a.src = R.f(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C; a.OH = op.OH; a.OW = op.OW;
-            a.kh = g ? op.ksize : 3; a.kw = g ? op.pad : 3; a.stride = g ? op.stride : 1;
-            a.wld = g ? op.heads : op.src0.C;
-            a.w = (const float*)(wb + op.w_off) + (g ? op.key_dim : 0); a.b = (const float*)(wb + op.b_off) + (g ? op.key_dim : 0);
-            a.dst = R.f(op.dst); a.ldd = op.dst.ld; a.act_c = g ? op.act : (op.act ? op.src0.C : 0);
-            a.res = g ? nullptr : R.f(op.res); a.ldr = (!g && op.res.buf >= 0) ? op.res.ld : 0;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_dw32(a, s);
-        }
-        case BSY_OP_SPPF_POOL: {
-            float* b = R.f(op.src0);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_sppf32(b, op.src0.ld, op.B, op.H, op.W, op.src0.C, s);
-        }
-        case BSY_OP_POOL_DOWN: {
-            const char* src = R.base(op.src0);
-            char* dst = R.base(op.dst);
-            if (!R.ok || op.src0.C != op.dst.C) return BSY_ERR_ARG;
-            return launch_pool_down(src, op.src0.ld, op.src0.coff, dst, op.dst.ld, op.dst.coff, op.B, op.H, op.W, op.src0.C, op.level, BSY_F32, s);
-        }
-        case BSY_OP_ATTN: {
-            const float* q = R.f(op.src0);
-            float* o = R.f(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            if (op.prec == 2 && attn32x_supported(op.src0.ld, op.dst.ld, op.key_dim, op.head_dim, q, o))  // fp32x: split-f16 products on the matrix pipe
-                return launch_attn32x(q, op.src0.ld, op.B, op.H * op.W, op.heads, op.key_dim, op.head_dim, op.scale, o, op.dst.ld, s);
-            return launch_attn32(q, op.src0.ld, op.B, op.H * op.W, op.heads, op.key_dim, op.head_dim, op.scale, o, op.dst.ld, s);
-        }
-        case BSY_OP_NHWC2NCHW: {
-            if (op.dst.buf >= BSY_EXT_BASE && (op.dst.buf - BSY_EXT_BASE >= R.n_ext || !R.ext[op.dst.buf - BSY_EXT_BASE])) return BSY_OK;
-            const float* src = R.f(op.src0);
-            void* out = R.base(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_nhwc2nchw32(src, op.src0.ld, op.B, op.src0.C, op.H * op.W, out, op.out_dtype, s);
-        }
-        case BSY_OP_COPY: {
-            const float* src = R.f(op.src0);
-            float* dst = R.f(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_copy32(src, op.src0.ld, op.up0, op.B, op.H, op.W, op.src0.C, dst, op.dst.ld, s);
-        }
-        case BSY_OP_GAP: {
-            const float* src = R.f(op.src0);
-            float* dst = R.f(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_gap32(src, op.src0.ld, op.B, op.H, op.W, op.src0.C, dst, op.dst.ld, s);
-        }
-        case BSY_OP_MSCA_MIX: {
-            Mix32Args a;
-            for (int i = 0; i < 4; ++i) {
-                const bsy_view& bv = i < 3 ? op.box[i] : op.res;
-                const bsy_view& lv = i < 3 ? op.cls[i] : op.msk[0];
-                a.br[i] = R.f(bv); a.ldb[i] = bv.ld; a.lg[i] = R.f(lv); a.ldl[i] = lv.ld;
-            }
-            a.B = op.B; a.HW = op.H * op.W; a.C = op.dst.C; a.dst = R.f(op.dst); a.ldd = op.dst.ld;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_mix32(a, s);
-        }
-        case BSY_OP_MUL: {
-            const float* x = R.f(op.src0);
-            const float* y = R.f(op.src1);
-            float* dst = R.f(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_mul32(x, op.src0.ld, y, op.src1.ld, (long long)op.B * op.H * op.W, op.dst.C, dst, op.dst.ld, s);
-        }
-        case BSY_OP_ELA: {
-            ElaArgs a;
-            memset(&a, 0, sizeof(a));
-            a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C; a.k = op.ksize;
-            const float* blob = (const float*)(wb + op.w_off);
-            a.wsp = blob; a.wch = blob + (size_t)a.C * a.k; a.gnw = a.wch + (size_t)a.C * a.k; a.gnb = a.gnw + a.C;
-            a.ch_coef = op.scale; a.sp_coef = op.lvl_stride[0]; a.res_coef = op.lvl_stride[1];
-            a.scratch = R.f(op.res); a.ldd = op.dst.ld;
-            const float* src = R.f(op.src0);
-            float* dst = R.f(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_ela32(a, src, dst, s);
-        }
-        case BSY_OP_CLASSIFY_TAIL:
-            return run_classify_tail(op, R, s);
-        case BSY_OP_DECODE:
-        case BSY_OP_RAW_NCHW:
-            handled = false;
-            return BSY_OK;
-        default:
-            BSY_FAIL(BSY_ERR_ARG, "fp32 mode: op kind %d has no fp32 implementation (fused kinds are fp16-only)", op.kind);
-    }
-}
-
-int run_op(const bsy_plan* p, const bsy_op& op, Resolver& R, hipStream_t s, ConvArgs* cargs = nullptr) {
-    const char* wb = (const char*)p->eng->weights;
-    if (op.prec == 1 || op.prec == 2) {
-        bool handled = false;
-        const int rc = run_op_f32(p, op, R, s, handled);
-        if (rc != BSY_OK || handled) return rc;
-    } else if (op.prec != 0) {
-        BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown precision mode %d", op.prec);
-    }
-    switch (op.kind) {
-        case BSY_OP_CONV_FIRST: {
-            ConvFirstArgs a;
-            a.img = R.base(op.src0); a.img_dtype = op.in_dtype;
-            a.B = op.B; a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW;
-            a.ksize = op.ksize; a.stride = op.stride; a.pad = op.pad;
-            a.w = (const void*)(wb + op.w_off); a.b = (const float*)(wb + op.b_off);
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.Cout = op.dst.C; a.act = op.act;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_conv_first(a, s);
-        }
-        case BSY_OP_STEM: {
-            StemArgs a;
-            a.img = R.base(op.src0); a.img_dtype = op.in_dtype;
-            a.B = op.B; a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW;
-            a.w0 = (const void*)(wb + op.w_off); a.b0 = (const float*)(wb + op.b_off);
-            a.w1 = (const void*)(wb + op.w2_off); a.b1 = (const float*)(wb + op.b2_off);
-            a.C0 = op.mid_c; a.C1 = op.dst.C;
-            int cp = 0;
-            bsy_conv_packed_dims(a.C1, a.C0, 3, &cp, &a.Kpad1);
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.act = op.act;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_stem_fused(a, s);
-        }
-        case BSY_OP_BNECK: {
-            BneckArgs a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W;
-            a.C = op.dst.C; a.CH = op.mid_c;
-            a.w1 = (const void*)(wb + op.w_off); a.b1 = (const float*)(wb + op.b_off);
-            a.w2 = (const void*)(wb + op.w2_off); a.b2 = (const float*)(wb + op.b2_off);
-            int cp = 0;
-            bsy_conv_packed_dims(a.CH, a.C, 3, &cp, &a.Kpad1);
-            bsy_conv_packed_dims(a.C, a.CH, 3, &cp, &a.Kpad2);
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.act = op.act;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_bneck_fused(a, s);
-        }
-        case BSY_OP_S2D: {
-            const void* img = R.base(op.src0);
-            half_t* dst = R.h(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_s2d(img, op.in_dtype, op.B, op.H, op.W, dst, op.dst.ld, s);
-        }
-        case BSY_OP_C3K2: {
-            C3k2Args a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W;
-            a.Cin = op.src0.C; a.C = op.mid_c; a.C2 = op.dst.C;
-            a.w1 = wb + op.aux_off[0]; a.b1 = (const float*)(wb + op.aux_off[1]);
-            a.wa = wb + op.aux_off[2]; a.ba = (const float*)(wb + op.aux_off[3]);
-            a.wb = wb + op.aux_off[4]; a.bb = (const float*)(wb + op.aux_off[5]);
-            a.w4 = wb + op.aux_off[6]; a.b4 = (const float*)(wb + op.aux_off[7]);
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_c3k2_fused(a, s);
-        }
-        case BSY_OP_DWPW: {
-            DwPwArgs a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C;
-            a.dww = (const float*)(wb + op.w_off); a.dwb = (const float*)(wb + op.b_off);
-            a.wgt = (const void*)(wb + op.w2_off); a.bias = (const float*)(wb + op.b2_off);
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.Cout = op.dst.C; a.act = op.act;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_dwpw_fused(a, s);
-        }
-        case BSY_OP_DWCONV_G: {
-            DwGenArgs a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C;
-            a.OH = op.OH; a.OW = op.OW; a.kh = op.ksize; a.kw = op.pad; a.stride = op.stride;
-            a.wld = op.heads; a.w = (const float*)(wb + op.w_off) + op.key_dim; a.b = (const float*)(wb + op.b_off) + op.key_dim;
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.act_c = op.act;  // act = number of leading channels with SiLU
-            a.ident_c0 = op.mid_c;  // first channel of an identity-kernel half (plan.py dwconv_g kind "dwg_ext"), 0 = none
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_dwconv_generic(a, s);
-        }
-        case BSY_OP_PMSFA_TAIL: {
-            PmsfaArgs a;
-            a.P = R.h(op.src0); a.ldp = op.src0.ld; a.x = R.h(op.res); a.ldx = op.res.ld; a.dst = R.h(op.dst); a.ldd = op.dst.ld;
-            a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.dst.C;
-            a.w2 = (const float*)(wb + op.aux_off[0]); a.b2 = (const float*)(wb + op.aux_off[1]); a.wld2 = op.heads;
-            a.w3 = (const float*)(wb + op.aux_off[2]); a.b3 = (const float*)(wb + op.aux_off[3]); a.wld3 = op.key_dim;
-            a.w4 = (const half_t*)(wb + op.aux_off[4]); a.b4 = (const float*)(wb + op.aux_off[5]);
-            int cp = 0;
-            bsy_conv_packed_dims(a.C, a.C, 1, &cp, &a.kpad4);
-            if (!R.ok || op.src0.C != a.C || op.res.C != a.C) return BSY_ERR_ARG;
-            return launch_pmsfa_tail(a, s);
-        }
-        case BSY_OP_COPY: {
-            const half_t* src = R.h(op.src0);
-            half_t* dst = R.h(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_copy_view(src, op.src0.ld, op.up0, op.B, op.H, op.W, op.src0.C, dst, op.dst.ld, s);
-        }
-        case BSY_OP_GAP: {
-            const half_t* src = R.h(op.src0);
-            half_t* dst = R.h(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_gap(src, op.src0.ld, op.B, op.H, op.W, op.src0.C, dst, op.dst.ld, s);
-        }
-        case BSY_OP_MSCA_SPATIAL: {
-            MscaSpArgs a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C;
-            for (int i = 0; i < 9; ++i) {
-                a.w[i] = (const float*)(wb + op.aux_off[2 * i]);
-                a.b[i] = (const float*)(wb + op.aux_off[2 * i + 1]);
-            }
-            for (int i = 0; i < 4; ++i) {
-                const bsy_view& bv = i < 3 ? op.box[i] : op.res;
-                const bsy_view& gv = i < 3 ? op.cls[i] : op.msk[0];
-                a.br[i] = R.h(bv); a.ldb[i] = bv.ld; a.gap[i] = R.h(gv); a.ldg[i] = gv.ld;
-            }
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_msca_spatial(a, s);
-        }
-        case BSY_OP_MSCA_MIX: {
-            MixArgs a;
-            for (int i = 0; i < 4; ++i) {
-                const bsy_view& bv = i < 3 ? op.box[i] : op.res;
-                const bsy_view& lv = i < 3 ? op.cls[i] : op.msk[0];
-                a.br[i] = R.h(bv); a.ldb[i] = bv.ld; a.lg[i] = R.f(lv); a.ldl[i] = lv.ld;
-            }
-            a.B = op.B; a.HW = op.H * op.W; a.C = op.dst.C; a.dst = R.h(op.dst); a.ldd = op.dst.ld;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_msca_mix(a, s);
-        }
-        case BSY_OP_MUL: {
-            const half_t* x = R.h(op.src0);
-            const half_t* y = R.h(op.src1);
-            half_t* dst = R.h(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_mul(x, op.src0.ld, y, op.src1.ld, (long long)op.B * op.H * op.W, op.dst.C, dst, op.dst.ld, s);
-        }
-        case BSY_OP_ELA: {
-            ElaArgs a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C; a.k = op.ksize;
-            const float* blob = (const float*)(wb + op.w_off);
-            a.wsp = blob; a.wch = blob + (size_t)a.C * a.k; a.gnw = a.wch + (size_t)a.C * a.k; a.gnb = a.gnw + a.C;
-            a.ch_coef = op.scale; a.sp_coef = op.lvl_stride[0]; a.res_coef = op.lvl_stride[1];
-            a.scratch = R.f(op.res); a.dst = R.h(op.dst); a.ldd = op.dst.ld;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_ela(a, s);
-        }
-        case BSY_OP_CONV: {
-            ConvArgs a;
-            a.src0 = R.h(op.src0); a.src1 = R.h(op.src1);
-            a.ld0 = op.src0.ld; a.ld1 = op.src1.buf >= 0 ? op.src1.ld : 0;
-            a.C0 = op.src0.C; a.C1 = op.src1.buf >= 0 ? op.src1.C : 0;
-            a.up0 = op.up0; a.up1 = op.up1;
-            a.B = op.B; a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW;
-            a.ksize = op.ksize; a.stride = op.stride; a.pad = op.pad;
-            a.wgt = (const half_t*)(wb + op.w_off); a.bias = (const float*)(wb + op.b_off);
-            a.dst = op.out_f32 ? (void*)R.f(op.dst) : (void*)R.h(op.dst);
-            a.ldd = op.dst.ld; a.Cout = op.dst.C; a.out_f32 = op.out_f32;
-            a.res = R.h(op.res); a.ldr = op.res.buf >= 0 ? op.res.ld : 0;
-            a.act = op.act; a.dst_scale = op.dst_scale; a.dst_dy = op.dst_dy; a.dst_dx = op.dst_dx;
-            a.epi = 0; a.y = nullptr; a.raw = nullptr; a.y_f32 = a.raw_f32 = a.A = a.a0 = a.nrows = a.rawC = 0; a.lvl_stride = 0.f;
-            a.tail_wgt = nullptr; a.tail_bias = nullptr;
-            if (op.out_f32 >= 2) {  // fused Detect decoder: dst = the prediction tensor y, box[0] = the level's raw map (optional)
-                a.epi = op.out_f32; a.out_f32 = 0; a.dst = nullptr; a.ldd = 8; a.Cout = op.nl;
-                a.y = R.base(op.dst); a.y_f32 = op.out_dtype == BSY_F32; a.A = op.A; a.a0 = op.lvl_h[1]; a.nrows = op.dst.C;
-                a.lvl_stride = op.lvl_stride[0];
-                const bsy_view& rv = op.box[0];
-                const bool bound = rv.buf >= BSY_EXT_BASE && rv.buf - BSY_EXT_BASE < R.n_ext && R.ext[rv.buf - BSY_EXT_BASE];
-                a.raw = bound ? R.base(rv) : nullptr; a.raw_f32 = a.y_f32; a.rawC = rv.C;
-                if (op.out_f32 == 3 && op.mid_c > 0) {  // box-branch tail: this op is the 3x3 conv, (w2, b2) the branch's last 1x1 conv
-                    a.Cout = op.mid_c;
-                    a.tail_wgt = (const half_t*)(wb + op.w2_off); a.tail_bias = (const float*)(wb + op.b2_off);
-                }
-            }
-            if (op.ksplit > 0 && op.out_f32 == 0) {  // split-K (latency-mode plans): ksplit = channel slices | tap slices << 8, box[0] = the f32 slab buffer
-                a.nsl_c = op.ksplit & 255; a.nsl_t = (op.ksplit >> 8) & 255;
-                a.split_ws = R.f(op.box[0]);
-            }
-            a.cfg = op.tuned_cfg - 1;  // 0 = not tuned -> heuristic
-            if (!R.ok) return BSY_ERR_ARG;
-            if (cargs) { *cargs = a; return BSY_OK; }
-            return launch_conv(a, s);
-        }
-        case BSY_OP_DWCONV: {
-            DwArgs a;
-            a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.src0.C;
-            a.w = (const float*)(wb + op.w_off); a.b = (const float*)(wb + op.b_off);
-            a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.act = op.act;
-            a.res = R.h(op.res); a.ldr = op.res.buf >= 0 ? op.res.ld : 0;
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_dwconv(a, s);
-        }
-        case BSY_OP_SPPF_POOL: {
-            half_t* b = R.h(op.src0);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_sppf_pool(b, op.src0.ld, op.B, op.H, op.W, op.src0.C, s);
-        }
-        case BSY_OP_POOL_DOWN: {
-            const char* src = R.base(op.src0);
-            char* dst = R.base(op.dst);
-            if (!R.ok || op.src0.C != op.dst.C) return BSY_ERR_ARG;
-            return launch_pool_down(src, op.src0.ld, op.src0.coff, dst, op.dst.ld, op.dst.coff, op.B, op.H, op.W, op.src0.C, op.level, BSY_F16, s);
-        }
-        case BSY_OP_ATTN: {
-            AttnArgs a;
-            a.qkv = R.h(op.src0); a.ld = op.src0.ld; a.B = op.B; a.N = op.H * op.W; a.heads = op.heads;
-            a.key_dim = op.key_dim; a.head_dim = op.head_dim; a.scale = op.scale;
-            a.out = R.h(op.dst); a.ldo = op.dst.ld;
-            if (op.act) {  // ATTN: act = pe folded into the epilogue, w_off / b_off = its depthwise weights (include/bsyolo.h)
-                a.H = op.H; a.W = op.W;
-                a.pe_w = (const float*)(wb + op.w_off); a.pe_b = (const float*)(wb + op.b_off);
-            }
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_attention(a, s);
-        }
-        case BSY_OP_DECODE: {
-            DecodeArgs a;
-            memset(&a, 0, sizeof(a));
-            a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A; a.ne = op.ne;
-            a.halves = op.act && !op.nm && !op.ne;  // DECODE: act = the fused head epilogue's DFL order (include/bsyolo.h)
-            a.nk = op.nk; a.kdim = op.kdim;
-            const bool extra = op.nm || op.ne || op.nk;  // mask coefficients (Segment), angle (OBB) or keypoint (Pose) logits in the msk slots
-            for (int l = 0; l < op.nl && l < BSY_MAX_LEVELS; ++l) {
-                a.box[l] = R.f(op.box[l]); a.cls[l] = R.f(op.cls[l]); a.msk[l] = extra ? R.f(op.msk[l]) : nullptr;
-                a.ldb[l] = op.box[l].ld; a.ldc[l] = op.cls[l].ld; a.ldm[l] = extra ? op.msk[l].ld : 0;
-                a.h[l] = op.lvl_h[l]; a.w[l] = op.lvl_w[l]; a.stride[l] = op.lvl_stride[l];
-            }
-            a.y = R.base(op.dst); a.y_dtype = op.out_dtype;
-            // Pose: res = the raw keypoint tensor, an optional output (an unbound external slot leaves it out)
-            if (op.nk && op.res.buf >= BSY_EXT_BASE && op.res.buf - BSY_EXT_BASE < R.n_ext && R.ext[op.res.buf - BSY_EXT_BASE])
-                a.kraw = R.base(op.res);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_decode(a, s);
-        }
-        case BSY_OP_RAW_NCHW: {
-            const int l = op.level;
-            if (l < 0 || l >= BSY_MAX_LEVELS) BSY_FAIL(BSY_ERR_ARG, "raw_nchw: level %d", l);
-            // optional output: silently skipped when the slot is not bound
-            if (op.dst.buf >= BSY_EXT_BASE && (op.dst.buf - BSY_EXT_BASE >= R.n_ext || !R.ext[op.dst.buf - BSY_EXT_BASE]))
-                return BSY_OK;
-            const float* box = R.f(op.box[l]);
-            const float* cls = R.f(op.cls[l]);
-            void* out = R.base(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_raw_nchw(box, op.box[l].ld, cls, op.cls[l].ld, op.B, op.lvl_h[l], op.lvl_w[l], op.nc, out,
-                                   op.out_dtype, s);
-        }
-        case BSY_OP_NHWC2NCHW: {
-            if (op.dst.buf >= BSY_EXT_BASE && (op.dst.buf - BSY_EXT_BASE >= R.n_ext || !R.ext[op.dst.buf - BSY_EXT_BASE]))
-                return BSY_OK;  // optional output
-            const half_t* src = R.h(op.src0);
-            void* out = R.base(op.dst);
-            if (!R.ok) return BSY_ERR_ARG;
-            return launch_nhwc2nchw(src, op.src0.ld, op.B, op.src0.C, op.H * op.W, out, op.out_dtype, s);
-        }
-        case BSY_OP_CLASSIFY_TAIL:
-            return run_classify_tail(op, R, s);
-        default:
-            BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown op kind %d", op.kind);
-    }
-}
-}  // namespace
-
-extern "C" void bsy_plan_destroy(bsy_plan* p);
-
 // Ops are listed in a valid serial order.  An op on lane k > 0 runs on the plan's side stream k, which is forked from
 // the caller's stream (event wait) the first time it is used after a join; an op flagged `join` first waits for every
 // active side stream.  Chains on different lanes must not depend on each other between a fork and the next join
@@ -678,7 +197,7 @@ extern "C" void bsy_plan_destroy(bsy_plan* p);
 extern "C" int bsy_plan_run(bsy_plan* p, void* const* ext, int n_ext, bsy_stream stream) {
     if (!p || (n_ext && !ext)) BSY_FAIL(BSY_ERR_ARG, "plan_run: bad argument");
     hipStream_t main = (hipStream_t)stream;
-    Resolver R{p, ext, n_ext};
+    Resolver R = p->resolver(ext, n_ext);
     unsigned active = 0;  // bit k: side stream k has work since the last join
     int rc = BSY_OK;
     for (size_t i = 0; i < p->ops.size() && rc == BSY_OK; ++i) {
@@ -710,7 +229,7 @@ extern "C" int bsy_plan_run(bsy_plan* p, void* const* ext, int n_ext, bsy_stream
                 active |= 1u << op.lane;
             }
         }
-        rc = run_op(p, op, R, s);
+        rc = run_op(op, R, p->weights(), s);
     }
     // never leave side streams un-joined (error paths included): the caller only synchronises its own stream.  After an
     // error the lanes are drained on the host as well, so that nothing of this forward can still be writing the workspace
@@ -784,14 +303,13 @@ extern "C" int bsy_plan_autotune(bsy_plan* p, void* const* ext, int n_ext, bsy_s
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
-    Resolver R{p, ext, n_ext};
+    Resolver R = p->resolver(ext, n_ext);
     int rc = BSY_OK;
     for (size_t i = 0; i < p->ops.size() && rc == BSY_OK; ++i) {
         bsy_op& op = p->ops[i];
-        if (op.kind != BSY_OP_CONV || op.tuned_cfg > 0 || op.prec != 0) { rc = run_op(p, op, R, s); continue; }  // preset (bsy_plan_set_tuning): kept
+        if (op.kind != BSY_OP_CONV || op.tuned_cfg > 0 || op.prec != 0) { rc = run_op(op, R, p->weights(), s); continue; }  // preset (bsy_plan_set_tuning): kept
         ConvArgs a;
-        rc = run_op(p, op, R, s, &a);
-        if (rc != BSY_OK) break;
+        if (!build_conv(a, op, R, p->weights())) { rc = BSY_ERR_ARG; break; }
         int cand[BSY_CONV_MAX_CFG];
         const int nc = conv_candidates(a, cand, BSY_CONV_MAX_CFG);
         // Candidates are timed ROUND-ROBIN (three rounds; per round one warm-up + a burst of five launches each) and ranked by
@@ -850,14 +368,13 @@ extern "C" int bsy_plan_set_tuning(bsy_plan* p, const int32_t* cfg, int n) {
 // would fall back to the heuristic configuration: a stale or foreign tune cache), -1 = not a conv op or not preset.  Launches nothing.
 extern "C" int bsy_plan_check_tuning(bsy_plan* p, void* const* ext, int n_ext, int32_t* valid, int n) {
     if (!p || !valid || (n_ext && !ext) || n != (int)p->ops.size()) BSY_FAIL(BSY_ERR_ARG, "plan_check_tuning: bad argument");
-    Resolver R{p, ext, n_ext};
+    Resolver R = p->resolver(ext, n_ext);
     for (int i = 0; i < n; ++i) {
         const bsy_op& op = p->ops[i];
         valid[i] = -1;
         if (op.kind != BSY_OP_CONV || op.tuned_cfg <= 0 || op.prec != 0) continue;
         ConvArgs a;
-        const int rc = run_op(p, op, R, nullptr, &a);  // arguments only: nothing is launched when `cargs` is given
-        if (rc != BSY_OK) return rc;
+        if (!build_conv(a, op, R, p->weights())) return BSY_ERR_ARG;
         valid[i] = conv_cfg_valid(a, op.tuned_cfg - 1) ? 1 : 0;
     }
     return BSY_OK;
@@ -881,10 +398,10 @@ extern "C" int bsy_plan_profile(bsy_plan* p, void* const* ext, int n_ext, bsy_st
         HIP_TRY(hipEventCreate(&ev));
         p->events.push_back(ev);
     }
-    Resolver R{p, ext, n_ext};
+    Resolver R = p->resolver(ext, n_ext);
     HIP_TRY(hipEventRecord(p->events[0], s));
     for (size_t i = 0; i < n; ++i) {
-        const int rc = run_op(p, p->ops[i], R, s);
+        const int rc = run_op(p->ops[i], R, p->weights(), s);
         if (rc != BSY_OK) return rc;
         HIP_TRY(hipEventRecord(p->events[i + 1], s));
     }
@@ -915,21 +432,20 @@ extern "C" int bsy_plan_autotune_in_place(bsy_plan* p, void* const* ext, int n_e
     p->drop_graphs();
     hipStream_t s = (hipStream_t)stream;
     const size_t n = p->ops.size();
-    Resolver R{p, ext, n_ext};
+    Resolver R = p->resolver(ext, n_ext);
     std::vector<std::vector<int>> cand(n);
     size_t K = 0;
     for (size_t i = 0; i < n; ++i) {  // one plain pass: the operands of every op exist, and the conv ops yield their arguments
         bsy_op& op = p->ops[i];
         if (op.kind == BSY_OP_CONV && op.tuned_cfg <= 0 && op.prec == 0) {
             ConvArgs a;
-            int rc = run_op(p, op, R, s, &a);
-            if (rc != BSY_OK) return rc;
+            if (!build_conv(a, op, R, p->weights())) return BSY_ERR_ARG;
             int list[BSY_CONV_MAX_CFG];
             const int nc = conv_candidates(a, list, BSY_CONV_MAX_CFG);
             cand[i].assign(list, list + (nc > 0 ? nc : 0));
             K = cand[i].size() > K ? cand[i].size() : K;
         }
-        const int rc = run_op(p, op, R, s);
+        const int rc = run_op(op, R, p->weights(), s);
         if (rc != BSY_OK) return rc;
     }
     if (K == 0) return BSY_OK;
@@ -959,234 +475,4 @@ extern "C" int bsy_plan_autotune_in_place(bsy_plan* p, void* const* ext, int n_e
     for (size_t i = 0; i < n; ++i)
         if (!cand[i].empty()) p->ops[i].tuned_cfg = best_c[i] + 1;
     return BSY_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Stand-alone operators
-// ---------------------------------------------------------------------------------------------------------------
-extern "C" int bsy_conv2d(const void* x, int ldx, int B, int H, int W, int C1, const void* w, const float* b, void* y,
-                          int ldy, int C2, int ksize, int stride, int act, const void* res, int ldr, int y_f32,
-                          bsy_stream stream) {
-    if (!x || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv2d: null pointer");
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = (const half_t*)x; a.ld0 = ldx; a.C0 = C1; a.B = B; a.H = H; a.W = W;
-    a.ksize = ksize; a.stride = stride; a.pad = ksize / 2;  // autopad (nn/modules/conv.py:29-35)
-    a.OH = (H + 2 * a.pad - ksize) / stride + 1; a.OW = (W + 2 * a.pad - ksize) / stride + 1;
-    a.wgt = (const half_t*)w; a.bias = b; a.dst = y; a.ldd = ldy; a.Cout = C2; a.out_f32 = y_f32;
-    a.res = (const half_t*)res; a.ldr = ldr; a.act = act; a.dst_scale = 1;
-    const char* forced = getenv("BSY_CONV_CFG");  // experiments: BSY_CONV_CFG=<tile<<4|variant>; an id that is not valid
-    a.cfg = forced ? atoi(forced) : -1;           // for this shape is an error (so A/B scripts see it), unset = heuristic
-    if (a.cfg >= 0 && !conv_cfg_valid(a, a.cfg)) BSY_FAIL(BSY_ERR_ARG, "conv: BSY_CONV_CFG=%d is not valid for this shape", a.cfg);
-    return launch_conv(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_conv2d_f32(const float* x, int ldx, int B, int H, int W, int C1, const float* w, const float* b, float* y, int ldy,
-                              int C2, int ksize, int stride, int act, const float* res, int ldr, int impl, bsy_stream stream) {
-    if (!x || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv2d_f32: null pointer");
-    if (B <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 <= 0 || ksize < 1 || !(ksize & 1) || (stride != 1 && stride != 2) || ldx < C1 || ldy < C2 ||
-        (res && ldr < C2) || impl < 0 || impl > 2)
-        BSY_FAIL(BSY_ERR_ARG, "conv2d_f32: bad shape");
-    Conv32Args a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src_dtype = BSY_F32; a.ld0 = ldx; a.C0 = C1; a.B = B; a.H = H; a.W = W;
-    a.ks = ksize; a.stride = stride; a.pad = ksize / 2;  // autopad (nn/modules/conv.py:29-35)
-    a.OH = (H + 2 * a.pad - ksize) / stride + 1; a.OW = (W + 2 * a.pad - ksize) / stride + 1;
-    a.w = w; a.bias = b; a.dst = y; a.ldd = ldy; a.Cout = C2; a.res = res; a.ldr = ldr; a.act = act; a.dst_scale = 1;
-    if (impl == 1) return launch_conv32_scalar(a, (hipStream_t)stream);
-    if (impl == 2) return launch_conv32_mfma(a, (hipStream_t)stream);
-    return launch_conv32(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_conv2d_f32x(const float* x, int ldx, int B, int H, int W, int C1, const void* w_hi, const void* w_lo, int k_pad,
-                               const float* b, float* y, int ldy, int C2, int ksize, int stride, int act, const float* res, int ldr,
-                               bsy_stream stream) {
-    if (!x || !w_hi || !w_lo || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv2d_f32x: null pointer");
-    if (B <= 0 || H <= 0 || W <= 0 || C1 <= 0 || C2 <= 0 || ksize < 1 || !(ksize & 1) || (stride != 1 && stride != 2) || ldx < C1 || ldy < C2 ||
-        (res && ldr < C2) || k_pad < ksize * ksize * C1 || (k_pad & 31))
-        BSY_FAIL(BSY_ERR_ARG, "conv2d_f32x: bad shape");
-    Conv32Args a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src_dtype = BSY_F32; a.ld0 = ldx; a.C0 = C1; a.B = B; a.H = H; a.W = W;
-    a.ks = ksize; a.stride = stride; a.pad = ksize / 2;
-    a.OH = (H + 2 * a.pad - ksize) / stride + 1; a.OW = (W + 2 * a.pad - ksize) / stride + 1;
-    a.w = (const float*)w_hi;  // only its alignment is looked at (conv32_mfma_supported); this entry point never runs the exact kernels
-    a.bias = b; a.dst = y; a.ldd = ldy; a.Cout = C2; a.res = res; a.ldr = ldr; a.act = act; a.dst_scale = 1;
-    a.wx_hi = (const half_t*)w_hi; a.wx_lo = (const half_t*)w_lo; a.wx_kpad = k_pad;
-    return launch_conv32x_mfma(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_conv_first_f32(const void* img, int img_dtype, int B, int H, int W, const float* w, const float* b, float* y, int ldy,
-                                 int C2, int ksize, int stride, int act, int impl, bsy_stream stream) {
-    if (!img || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv_first_f32: null pointer");
-    if (B <= 0 || H <= 0 || W <= 0 || C2 <= 0 || ksize < 1 || !(ksize & 1) || (stride != 1 && stride != 2) || ldy < C2 || impl < 0 || impl > 2 ||
-        (img_dtype != BSY_F16 && img_dtype != BSY_F32))
-        BSY_FAIL(BSY_ERR_ARG, "conv_first_f32: bad shape");
-    Conv32Args a;
-    memset(&a, 0, sizeof(a));
-    a.first = 1; a.src0 = img; a.src_dtype = img_dtype; a.C0 = 3; a.B = B; a.H = H; a.W = W;
-    a.ks = ksize; a.stride = stride; a.pad = ksize / 2;
-    a.OH = (H + 2 * a.pad - ksize) / stride + 1; a.OW = (W + 2 * a.pad - ksize) / stride + 1;
-    a.w = w; a.bias = b; a.dst = y; a.ldd = ldy; a.Cout = C2; a.act = act; a.dst_scale = 1;
-    if (impl == 1) return launch_conv32_scalar(a, (hipStream_t)stream);
-    if (impl == 2) return launch_conv32_mfma(a, (hipStream_t)stream);
-    return launch_conv32(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_attention_f32(const float* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale, float* out,
-                                 int ldo, int impl, bsy_stream stream) {
-    if (!qkv || !out || B <= 0 || N <= 0 || impl < 0 || impl > 3) BSY_FAIL(BSY_ERR_ARG, "attention_f32: bad argument");
-    if (impl == 3) return launch_attn32x(qkv, ld, B, N, heads, key_dim, head_dim, scale, out, ldo, (hipStream_t)stream);
-    return launch_attn32(qkv, ld, B, N, heads, key_dim, head_dim, scale, out, ldo, (hipStream_t)stream, impl);
-}
-
-extern "C" int bsy_conv_first(const void* img, int img_dtype, int B, int H, int W, const void* w, const float* b,
-                              void* y, int ldy, int C2, int ksize, int stride, int act, bsy_stream stream) {
-    if (!img || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv_first: null pointer");
-    ConvFirstArgs a;
-    a.img = img; a.img_dtype = img_dtype; a.B = B; a.H = H; a.W = W; a.ksize = ksize; a.stride = stride; a.pad = ksize / 2;
-    a.OH = (H + 2 * a.pad - ksize) / stride + 1; a.OW = (W + 2 * a.pad - ksize) / stride + 1;
-    a.w = w; a.b = b; a.dst = (half_t*)y; a.ldd = ldy; a.Cout = C2; a.act = act;
-    return launch_conv_first(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_stem_fused(const void* img, int img_dtype, int B, int H, int W, const void* w0, const float* b0, int C0,
-                              const void* w1, const float* b1, int C1, void* y, int ldy, int act, bsy_stream stream) {
-    if (!img || !w0 || !b0 || !w1 || !b1 || !y) BSY_FAIL(BSY_ERR_ARG, "stem: null pointer");
-    StemArgs a;
-    a.img = img; a.img_dtype = img_dtype; a.B = B; a.H = H; a.W = W;
-    const int OH0 = (H - 1) / 2 + 1, OW0 = (W - 1) / 2 + 1;
-    a.OH = (OH0 - 1) / 2 + 1; a.OW = (OW0 - 1) / 2 + 1;
-    a.w0 = w0; a.b0 = b0; a.w1 = w1; a.b1 = b1; a.C0 = C0; a.C1 = C1;
-    int cp = 0;
-    bsy_conv_packed_dims(C1, C0, 3, &cp, &a.Kpad1);
-    a.dst = (half_t*)y; a.ldd = ldy; a.act = act;
-    return launch_stem_fused(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_stem_fused_supported(int C0, int C1, int H, int W) { return stem_fused_supported(C0, C1, H, W) ? 1 : 0; }
-
-extern "C" int bsy_bottleneck_fused(const void* x, int ldx, int B, int H, int W, int C, int CH, const void* w1,
-                                    const float* b1, const void* w2, const float* b2, void* y, int ldy, int act,
-                                    bsy_stream stream) {
-    if (!x || !w1 || !b1 || !w2 || !b2 || !y) BSY_FAIL(BSY_ERR_ARG, "bottleneck: null pointer");
-    BneckArgs a;
-    a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.CH = CH;
-    a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
-    int cp = 0;
-    if (C <= 0 || CH <= 0) BSY_FAIL(BSY_ERR_ARG, "bottleneck: bad widths");
-    bsy_conv_packed_dims(CH, C, 3, &cp, &a.Kpad1);
-    bsy_conv_packed_dims(C, CH, 3, &cp, &a.Kpad2);
-    a.dst = (half_t*)y; a.ldd = ldy; a.act = act;
-    return launch_bneck_fused(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_bottleneck_fused_supported(int C, int CH) { return bneck_fused_supported(C, CH) ? 1 : 0; }
-
-extern "C" int bsy_c3k2_fused(const void* x, int ldx, int B, int H, int W, int Cin, int c, int C2, const void* w1, const float* b1,
-                              const void* wa, const float* ba, const void* wb, const float* bb, const void* w4, const float* b4,
-                              void* y, int ldy, bsy_stream stream) {
-    C3k2Args a;
-    a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.C = c; a.C2 = C2;
-    a.w1 = w1; a.b1 = b1; a.wa = wa; a.ba = ba; a.wb = wb; a.bb = bb; a.w4 = w4; a.b4 = b4;
-    a.dst = (half_t*)y; a.ldd = ldy;
-    return launch_c3k2_fused(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_c3k2_fused_supported(int Cin, int c, int C2) { return c3k2_fused_supported(Cin, c, C2) ? 1 : 0; }
-
-extern "C" int bsy_dwconv(const void* x, int ldx, int B, int H, int W, int C, int kh, int kw, int stride, const float* w,
-                          int wld, const float* b, void* y, int ldy, int act, bsy_stream stream) {
-    DwGenArgs a;
-    a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.kh = kh; a.kw = kw; a.stride = stride;
-    if (kh < 1 || kw < 1 || (stride != 1 && stride != 2)) BSY_FAIL(BSY_ERR_ARG, "dwconv: bad kernel / stride");
-    a.OH = (H + 2 * (kh / 2) - kh) / stride + 1; a.OW = (W + 2 * (kw / 2) - kw) / stride + 1;
-    a.w = w; a.wld = wld; a.b = b; a.dst = (half_t*)y; a.ldd = ldy; a.act_c = act ? C : 0;
-    return launch_dwconv_generic(a, (hipStream_t)stream);
-}
-
-extern "C" size_t bsy_ela_scratch_bytes(int B, int H, int W, int C) {
-    return (B > 0 && H > 0 && W > 0 && C > 0) ? ela_scratch_floats(H, W, C) * (size_t)B * sizeof(float) : 0;
-}
-
-extern "C" int bsy_ela(const void* x, int ldx, int B, int H, int W, int C, int k, const float* wsp, const float* wch,
-                       const float* gnw, const float* gnb, const float* coef, void* scratch, void* y, int ldy,
-                       bsy_stream stream) {
-    if (!coef) BSY_FAIL(BSY_ERR_ARG, "ela: null coefficient pointer");
-    ElaArgs a;
-    a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.k = k;
-    a.wsp = wsp; a.wch = wch; a.gnw = gnw; a.gnb = gnb; a.ch_coef = coef[0]; a.sp_coef = coef[1]; a.res_coef = coef[2];
-    a.scratch = (float*)scratch; a.dst = (half_t*)y; a.ldd = ldy;
-    return launch_ela(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_dwpw_fused(const void* x, int ldx, int B, int H, int W, int C, const float* dww, const float* dwb,
-                              const void* w, const float* b, void* y, int ldy, int C2, int act, bsy_stream stream) {
-    DwPwArgs a;
-    a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.dww = dww; a.dwb = dwb; a.wgt = w; a.bias = b;
-    a.dst = (half_t*)y; a.ldd = ldy; a.Cout = C2; a.act = act;
-    return launch_dwpw_fused(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_dwpw_fused_supported(int C, int C2) { return dwpw_fused_supported(C, C2) ? 1 : 0; }
-extern "C" int bsy_attention_supported(int key_dim, int head_dim) { return attention_supported(key_dim, head_dim) ? 1 : 0; }
-extern "C" int bsy_pmsfa_tail_supported(int C) { return pmsfa_tail_supported(C) ? 1 : 0; }
-extern "C" int bsy_msca_spatial_supported(int H, int W) { return msca_spatial_supported(H, W) ? 1 : 0; }
-
-extern "C" int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* b, void* y,
-                             int ldy, int act, const void* res, int ldr, bsy_stream stream) {
-    if (!x || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "dwconv3x3: null pointer");
-    DwArgs a;
-    a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.w = w; a.b = b;
-    a.dst = (half_t*)y; a.ldd = ldy; a.act = act; a.res = (const half_t*)res; a.ldr = ldr;
-    return launch_dwconv(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_sppf_pool(void* buf, int ld, int B, int H, int W, int C, bsy_stream stream) {
-    if (!buf) BSY_FAIL(BSY_ERR_ARG, "sppf_pool: null pointer");
-    return launch_sppf_pool((half_t*)buf, ld, B, H, W, C, (hipStream_t)stream);
-}
-
-extern "C" int bsy_pool_down(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
-                             bsy_stream stream) {
-    return launch_pool_down(x, ldx, xoff, y, ldy, yoff, B, H, W, C, mode, dtype, (hipStream_t)stream);
-}
-
-extern "C" int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale,
-                             void* out, int ldo, bsy_stream stream) {
-    if (!qkv || !out) BSY_FAIL(BSY_ERR_ARG, "attention: null pointer");
-    AttnArgs a;
-    a.qkv = (const half_t*)qkv; a.ld = ld; a.B = B; a.N = N; a.heads = heads; a.key_dim = key_dim; a.head_dim = head_dim;
-    a.scale = scale; a.out = (half_t*)out; a.ldo = ldo;
-    return launch_attention(a, (hipStream_t)stream);
-}
-
-extern "C" int bsy_attention_pe(const void* qkv, int ld, int B, int H, int W, int heads, int key_dim, int head_dim, float scale,
-                                const float* pe_w, const float* pe_b, void* out, int ldo, int impl, bsy_stream stream) {
-    if (!qkv || !out || (pe_w && !pe_b)) BSY_FAIL(BSY_ERR_ARG, "attention_pe: null pointer");
-    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffff) BSY_FAIL(BSY_ERR_ARG, "attention_pe: bad map size");
-    AttnArgs a;
-    a.qkv = (const half_t*)qkv; a.ld = ld; a.B = B; a.N = H * W; a.heads = heads; a.key_dim = key_dim; a.head_dim = head_dim;
-    a.scale = scale; a.out = (half_t*)out; a.ldo = ldo;
-    a.H = H; a.W = W; a.pe_w = pe_w; a.pe_b = pe_w ? pe_b : nullptr;
-    return launch_attention(a, (hipStream_t)stream, impl);
-}
-
-extern "C" int bsy_detect_decode(const float* const* box, const int* ldb, const float* const* cls, const int* ldc,
-                                 const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
-                                 const float* lvl_stride, int nl, int B, int nc, int nm, void* y, int y_dtype,
-                                 bsy_stream stream) {
-    if (!box || !ldb || !cls || !ldc || !lvl_h || !lvl_w || !lvl_stride || !y || nl < 1 || nl > BSY_MAX_LEVELS)
-        BSY_FAIL(BSY_ERR_ARG, "detect_decode: bad argument");
-    if (nm && (!msk || !ldm)) BSY_FAIL(BSY_ERR_ARG, "detect_decode: mask inputs missing");
-    DecodeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nl = nl; a.B = B; a.nc = nc; a.nm = nm; a.A = 0;
-    for (int l = 0; l < nl; ++l) {
-        a.box[l] = box[l]; a.cls[l] = cls[l]; a.msk[l] = nm ? msk[l] : nullptr;
-        a.ldb[l] = ldb[l]; a.ldc[l] = ldc[l]; a.ldm[l] = nm ? ldm[l] : 0;
-        a.h[l] = lvl_h[l]; a.w[l] = lvl_w[l]; a.stride[l] = lvl_stride[l];
-    }
-    a.y = y; a.y_dtype = y_dtype;
-    return launch_decode(a, (hipStream_t)stream);
 }

@@ -1,5 +1,5 @@
-// Building blocks shared by the postprocess units nms.hip, obb.hip, sahi.hip, topk.hip and classify.hip (val_ap.hip and engine.hip take the two
-// size helpers only).  Everything here is inline: a __global__ lives in exactly one unit (the key sort: nms.hip) and is reached
+// Building blocks shared by the postprocess units nms.hip, obb.hip, sahi.hip, topk.hip and classify.hip (val_ap.hip takes the
+// size helpers only; align256 itself is common.h's, for engine.hip and op_args.h).  Everything here is inline: a __global__ lives in exactly one unit (the key sort: nms.hip) and is reached
 // from the others through the host launchers declared at the end.
 //   host:   pow2_at_least, align256, Carver (workspace layout, measured and carved by the same calls), dispatch_dtype
 //   device: block_bitonic_desc, greedy_resolve_256, kept_rank / block_kept_rank, first_max_class, score_key / decode_score_key, ord_key
@@ -21,8 +21,6 @@ __host__ __device__ inline I pow2_at_least(I n) {
     while (p < n) p <<= 1;
     return p;
 }
-
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Bump allocator over a caller's workspace.  Each unit describes its layout ONCE, as a function that runs the same align() /
 // take() calls with the real base pointer (the pointers are used) or with nullptr (only `need` is used: the *_workspace_bytes

@@ -102,7 +102,7 @@ def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f3
     """-> (weight bytes, bias bytes) for one op.  f32: the fp32 correctness mode's layout for dense convs -- f32
     [k*k*cin][cout] (K order (kh, kw, cin) as in the fp16 layout, cout fastest), bias f32 [cout], no padding
     (csrc/ref32.hip); depthwise / ELA records are f32 in both modes.  split (fp32x mode, with f32): the f32 matrix is followed
-    by the two f16 planes of split_f16_planes, each part padded to 256 bytes (csrc/engine.hip run_op_f32 computes the same
+    by the two f16 planes of split_f16_planes, each part padded to 256 bytes (csrc/op_args.h build_conv32 computes the same
     offsets)."""
     if r.kind == "ela":
         # ELA (nn/Addmodules/ELA.py:36-72): [spatial_conv (C,k)][ch_att.2 (C,k)][gn.weight][gn.bias]; the three scalar mixing

@@ -236,7 +236,7 @@ def ulp32(v):
 # ---- the fp16 CONV op (tests/test_fp16_conv_ops.py) ----
 def conv16_op(B, H, W, ksize, stride, pad, src0, dst, w_off, b_off, src1=None, up0=0, up1=0, res=None, act=0, out_f32=0, dst_scale=1,
               dst_dy=0, dst_dx=0, nsl_c=0, nsl_t=0, slab=None):
-    """A fp16 CONV op, fields as run_op's BSY_OP_CONV case reads them (csrc/engine.hip).  H, W: the conv's input map (a source read
+    """A fp16 CONV op, fields as build_conv reads them (csrc/op_args.h).  H, W: the conv's input map (a source read
     through nearest x2 holds H / 2 x W / 2); the destination holds OH * dst_scale rows.  Split-K: ksplit = nsl_c | nsl_t << 8 and
     box[0] = `slab`, the view of the f32 slab buffer."""
     from bs_yolo_amd import lib as L
