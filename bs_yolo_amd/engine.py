@@ -247,12 +247,21 @@ class YoloEngine:
         ptrs = [im.data_ptr(), y.data_ptr()] + raws[:3] + [proto.data_ptr() if proto is not None else None] + raws[3:]
         return (C.c_void_p * len(ptrs))(*ptrs), len(ptrs)
 
+    @staticmethod
+    def _dense(im: torch.Tensor) -> torch.Tensor:
+        """`im` contiguous AND with its first element on a 16-byte boundary.  contiguous() keeps a contiguous view at an odd storage
+        offset as it is, and the fused stem (csrc/stem_fused.hip: 4-pixel vector loads) refuses such a pointer where the unfused plan
+        takes the element-wise load; such a view is copied, so every plan sees the same aligned image (one elementwise launch on the
+        current stream; in graph mode a copy at a new address is captured like any other new input)."""
+        im = im.contiguous()
+        return im.clone() if im.data_ptr() % 16 else im
+
     def forward(self, im: torch.Tensor, want_raw: bool = True):
         if im.device != self.device:
             raise ValueError(f"input on {im.device}, engine on {self.device}")
         if im.dtype not in (torch.float16, torch.float32):
             raise TypeError("input must be fp16 or fp32 (BCHW, 0..1)")
-        im = im.contiguous()
+        im = self._dense(im)
         B, Cc, H, W = im.shape
         if Cc != 3:
             raise ValueError("expected 3 input channels")
@@ -418,7 +427,7 @@ class YoloEngine:
                 raise ValueError(f"input on {im.device}, engine on {self.device}")
             if im.dtype not in (torch.float16, torch.float32) or im.dim() != 4 or im.shape[1] != 3:
                 raise TypeError("input must be a BCHW fp16 or fp32 image tensor")
-            im = im.contiguous()
+            im = self._dense(im)
             B, _, H, W = im.shape
             passes = self.tta_geometry(H, W)
             cur = torch.cuda.current_stream(self.device)
@@ -454,7 +463,7 @@ class YoloEngine:
 
     def profile(self, im: torch.Tensor):
         """Per-op device time (ms) of one forward, measured with HIP events on the current stream."""
-        im = im.contiguous()
+        im = self._dense(im)
         B, _, H, W = im.shape
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
         m = plan.meta

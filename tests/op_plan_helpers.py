@@ -1,6 +1,8 @@
-"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py, test_fp16_conv_ops.py, test_fp16_head_ops.py): a single bsy_op run through bsy_plan_create /
-bsy_plan_run with every tensor bound as an external slot, poisoned views and a weight-blob builder.  Not a test module."""
+"""Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py, test_fp16_conv_ops.py, test_fp16_head_ops.py,
+test_fp16_block_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every tensor bound as an external slot, poisoned
+views and a weight-blob builder.  Not a test module."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -37,13 +39,18 @@ def new_op(kind, prec, B, H, W):
 def run_op(op, ext_tensors, blob=b""):
     """One-op plan: engine + weights (`blob`, padded to 256 bytes: bsy_plan_create refuses an engine without weights), plan, run on
     the current stream, synchronise; plan and engine are destroyed whatever happens.  None in ext_tensors = a null slot."""
+    run_ops([op], ext_tensors, blob)
+
+
+def run_ops(ops, ext_tensors, blob=b""):
+    """run_op for a chain of ops in ONE plan, launched in their order on the current stream."""
     from bs_yolo_amd import lib as L
     blob = bytes(blob) + b"\0" * max(0, 256 - len(blob))
     eng, plan = C.c_void_p(), C.c_void_p()
     L.check(L.lib.bsy_engine_create(0, C.byref(eng)))
     try:
         L.check(L.lib.bsy_engine_load_weights(eng, (C.c_char * len(blob)).from_buffer_copy(blob), len(blob)))
-        L.check(L.lib.bsy_plan_create(eng, (L.Op * 1)(op), 1, None, 0, C.byref(plan)))
+        L.check(L.lib.bsy_plan_create(eng, (L.Op * len(ops))(*ops), len(ops), None, 0, C.byref(plan)))
         n = len(ext_tensors)
         ext = (C.c_void_p * max(n, 1))(*[None if t is None else t.data_ptr() for t in ext_tensors])
         L.check(L.lib.bsy_plan_run(plan, ext, n, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
@@ -338,4 +345,105 @@ def head16_op(B, H, W, ksize, src0, y, w_off, b_off, mode, cout, A, a0, stride, 
         op.box[0] = raw
     if tail is not None:
         op.mid_c, op.w2_off, op.b2_off = 64, tail[0], tail[1]
+    return op
+
+
+# ---- the derived bound of the fp16 conv ops (tests/test_fp16_conv_ops.py, tests/test_fp16_block_ops.py) ----
+U = 2.0 ** -24  # unit roundoff of f32
+
+
+def _u16(t):
+    return torch.from_numpy(ulp16(t.numpy()))
+
+
+def _bound(ly, c, two_roundings):
+    """Allowed |got - fp64| per output element -> (arithmetic part, rounding part):
+
+      arithmetic:  1.1 (K + nsl) 2^-24 S  +  8 * 2^-24 |a|  (SiLU)
+                   the order-independent bound of a length-K fp32 sum that starts at the bias, one more add per split-K slice
+                   (gamma_n <= 1.1 n u here), carried through SiLU, whose slope lies in (-0.1, 1.1); x / (1 + expf(-x)).
+      rounding:    half an f16 ulp of y (subnormal floor included; out_f32: 2^-24 |y|), plus half an f16 ulp of a where the form rounds
+                   before it adds the shortcut -- half(half(act(v)) + r): conv_epilogue_lds and the patch kernel; conv_epilogue and
+                   splitk_reduce_kernel add in f32 and round once."""
+    arith = 1.1 * (ly.K + ly.nsl) * U * c.S
+    if c.act:
+        arith = arith + 8 * U * c.a.abs()
+    rnd = U * c.ref.abs() if ly.out_f32 else 0.5 * _u16(c.ref)
+    if two_roundings and c.res is not None:
+        rnd = rnd + 0.5 * _u16(c.a)
+    return arith, rnd
+
+
+def _worst(got, ref, bound):
+    """worst |got - ref| / bound; inf when got is not finite (a NaN from outside a view or between the weight records reached it)."""
+    got = got.to(torch.float64)
+    if not bool(torch.isfinite(got).all()):
+        return math.inf
+    return float(((got - ref).abs() / bound).max())
+
+
+# ---- the image and fused block ops (tests/test_fp16_block_ops.py) ----
+def poisoned_image(x, dtype, mis=0):
+    """The BCHW image `x` as a whole tensor of `dtype` inside a larger NaN-filled device allocation: at least one image row (and 64
+    elements) of NaN in front of it and behind it, its first element `mis` elements past a 128-byte boundary.  A read outside the
+    image reaches the output as NaN.  -> (the allocation, the image: a view into it)."""
+    n, pad = x.numel(), (x.shape[-1] + 63) // 64 * 64 + 64
+    flat = torch.full((2 * pad + n + 8,), NAN, dtype=dtype)
+    flat[pad + mis:pad + mis + n] = x.to(dtype).reshape(-1)
+    flat = flat.to(DEV)
+    img = flat[pad + mis:pad + mis + n].view(x.shape)
+    assert img.is_contiguous() and img.data_ptr() % 128 == (mis * img.element_size()) % 128
+    return flat, img
+
+
+def image_view(slot):
+    """The image as Plan.conv_first names it: the whole BCHW tensor of an external slot (ld and coff 0, C 3)."""
+    return view(slot, 0, 0, 3)
+
+
+def conv_first16_op(B, H, W, dst, w_off, b_off, in_dtype, act=1, img=None, ksize=3, stride=2, pad=1):
+    """A fp16 CONV_FIRST op, fields as Plan.conv_first emits them and build_conv_first reads them: src0 = the image (slot 0 unless
+    `img`), H / W its size, dst the NHWC f16 view, (w_off, b_off) the record packed with a zero 4th input channel."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_CONV_FIRST, 0, B, H, W)
+    op.OH, op.OW = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    op.ksize, op.stride, op.pad, op.act, op.dst_scale, op.in_dtype = ksize, stride, pad, int(act), 1, in_dtype
+    op.src0, op.dst, op.w_off, op.b_off = image_view(0) if img is None else img, dst, w_off, b_off
+    return op
+
+
+def stem_op(B, H, W, dst, mid_c, rec0, rec1, in_dtype, act=1, img=None):
+    """A STEM op, fields as Plan._fuse_stem emits them and build_stem reads them: H / W = the image, OH / OW = the layer-1 map,
+    mid_c = C0, dst.C = C1, (w_off, b_off) = rec0 of layer 0, (w2_off, b2_off) = rec1 of layer 1."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_STEM, 0, B, H, W)
+    oh0, ow0 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    op.OH, op.OW = (oh0 - 1) // 2 + 1, (ow0 - 1) // 2 + 1
+    op.ksize, op.stride, op.pad, op.act, op.dst_scale, op.in_dtype, op.mid_c = 3, 2, 1, int(act), 1, in_dtype, mid_c
+    op.src0, op.dst = image_view(0) if img is None else img, dst
+    (op.w_off, op.b_off), (op.w2_off, op.b2_off) = rec0, rec1
+    return op
+
+
+def bneck_op(B, H, W, src, dst, mid_c, rec1, rec2, act=1):
+    """A BNECK op, fields as Plan.bottleneck emits them and build_bneck reads them: mid_c = the hidden width, rec1 / rec2 = the
+    (w, b) records of cv1 / cv2; the shortcut is the source view itself."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_BNECK, 0, B, H, W)
+    op.ksize, op.stride, op.pad, op.act, op.dst_scale, op.mid_c = 3, 1, 1, int(act), 1, mid_c
+    op.src0, op.dst = src, dst
+    (op.w_off, op.b_off), (op.w2_off, op.b2_off) = rec1, rec2
+    return op
+
+
+def c3k2_op(B, H, W, src, dst, mid_c, recs):
+    """A C3K2 op, fields as Plan.c2f emits them and build_c3k2 reads them: mid_c = c, aux_off[0..7] = the (w, b) records of cv1,
+    m.cv1, m.cv2, cv2."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_C3K2, 0, B, H, W)
+    op.ksize, op.stride, op.pad, op.act, op.dst_scale, op.mid_c = 3, 1, 1, 1, 1, mid_c
+    op.src0, op.dst = src, dst
+    assert len(recs) == 4
+    for j, (w_off, b_off) in enumerate(recs):
+        op.aux_off[2 * j], op.aux_off[2 * j + 1] = w_off, b_off
     return op

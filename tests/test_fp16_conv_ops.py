@@ -28,8 +28,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from op_plan_helpers import (NAN, PHASES, POISON16, POISON32, assert_poison_intact, bits, conv16_blob, conv16_op, nchw, nhwc, poisoned,
-                             run_conv_cfgs, run_op, ulp16, view)
+from op_plan_helpers import (NAN, PHASES, POISON16, POISON32, _bound, _u16, _worst, assert_poison_intact, bits, conv16_blob, conv16_op,  # noqa: F401
+                             nchw, nhwc, poisoned, run_conv_cfgs, run_op, view)
 
 gpu = pytest.mark.gpu
 
@@ -37,7 +37,6 @@ if torch.cuda.is_available():
     from bs_yolo_amd import lib as L  # noqa: F401  (fails loudly when the .so is missing)
 
 F32, F16, F64 = torch.float32, torch.float16, torch.float64
-U = 2.0 ** -24  # unit roundoff of f32
 
 
 def _gen(*key):
@@ -316,36 +315,6 @@ def _case(pl, kind):
         assert float(v.abs().max()) <= 2048 and float(y.abs().max()) <= 2048 and float(S.max()) < 2 ** 24
         y = y + 0.0  # no kernel returns -0 here: the chains start at a +0 or non-zero bias
     return SimpleNamespace(xs=c.xs, w=c.w, b=c.b, res=c.res, act=c.act, lin=lin, v=v, a=a, ref=y, S=S)
-
-
-def _u16(t):
-    return torch.from_numpy(ulp16(t.numpy()))
-
-
-def _bound(ly, c, two_roundings):
-    """Allowed |got - fp64| per output element -> (arithmetic part, rounding part):
-
-      arithmetic:  1.1 (K + nsl) 2^-24 S  +  8 * 2^-24 |a|  (SiLU)
-                   the order-independent bound of a length-K fp32 sum that starts at the bias, one more add per split-K slice
-                   (gamma_n <= 1.1 n u here), carried through SiLU, whose slope lies in (-0.1, 1.1); x / (1 + expf(-x)).
-      rounding:    half an f16 ulp of y (subnormal floor included; out_f32: 2^-24 |y|), plus half an f16 ulp of a where the form rounds
-                   before it adds the shortcut -- half(half(act(v)) + r): conv_epilogue_lds and the patch kernel; conv_epilogue and
-                   splitk_reduce_kernel add in f32 and round once."""
-    arith = 1.1 * (ly.K + ly.nsl) * U * c.S
-    if c.act:
-        arith = arith + 8 * U * c.a.abs()
-    rnd = U * c.ref.abs() if ly.out_f32 else 0.5 * _u16(c.ref)
-    if two_roundings and c.res is not None:
-        rnd = rnd + 0.5 * _u16(c.a)
-    return arith, rnd
-
-
-def _worst(got, ref, bound):
-    """worst |got - ref| / bound; inf when got is not finite (a NaN from outside a view or between the weight records reached it)."""
-    got = got.to(F64)
-    if not bool(torch.isfinite(got).all()):
-        return math.inf
-    return float(((got - ref).abs() / bound).max())
 
 
 # ------------------------------------------------------------------------------------------------------------

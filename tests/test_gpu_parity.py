@@ -486,8 +486,9 @@ def test_conv_first_matches_oracle(dtype):
 def test_stem_fused_matches_unfused_and_oracle(dtype, shape, c0, c1):
     """Layers 0 + 1 as one launch (csrc/stem_fused.hip): bit-identical to bsy_conv_first + bsy_conv2d, and equal to
     the fp32 reference of the two Conv.forward_fuse calls (conv.py:149-151) with the layer-0 map rounded to fp16.
-    Shapes cover ragged tiles (layer-1 maps 9 x 13, 17 x 9), heights that are not multiples of 4, and more tiles
-    than persistent workgroups (70 images)."""
+    Shapes cover ragged tiles (layer-1 maps 9 x 13, 17 x 9) and heights that are not multiples of 4.  The 70-image case is
+    70 x 2 x 2 = 280 tiles (make_tile_grid pads each side to two tiles), under the grid cap of 768 (f16) / 512 (f32): no workgroup
+    takes a second tile here; tests/test_fp16_block_ops.py has the persistent-walk cases."""
     g = torch.Generator().manual_seed(12)
     img = torch.rand(*shape, generator=g)
     w0 = h16(torch.randn(c0, 3, 3, 3, generator=g) * 0.3)
@@ -520,8 +521,10 @@ def test_stem_fused_rejects_unsupported():
 def test_bottleneck_fused_matches_unfused_and_oracle(shape, widths, monkeypatch):
     """Bottleneck (block.py:3405-3419, k = (3,3), shortcut) as one launch (csrc/bneck_fused.hip; 32/16: YOLO11s model.2,
     64/32: model.4 / model.16): bit-identical to two bsy_conv2d launches (the second with the residual) and equal to the fp32 reference with the hidden map rounded to fp16.  Input and output are
-    channel slices of one wider buffer, as inside C3k2's concat buffer; shapes cover ragged tiles, maps smaller than one tile
-    and more tiles than persistent workgroups."""
+    channel slices of one wider buffer, as inside C3k2's concat buffer; shapes cover ragged tiles and maps smaller than one tile.
+    The 300-image case exceeds the grid cap (768 / 256 workgroups) only through padded empty tiles (16 x 16 is 2 x 1 tiles, padded to
+    2 x 2): a workgroup's second tile inside a map is always the first tile of another image.  A walk that continues inside one
+    image runs in tests/test_fp16_block_ops.py."""
     B, H, W = shape
     c, ch = widths
     ld = 3 * c
@@ -561,7 +564,8 @@ def test_c3k2_fused_matches_unfused_and_oracle(shape):
     """The whole C3k2 block (c3k = False, one Bottleneck; block.py:3796-3804) as ONE launch (csrc/c3k2_fused.hip): bit-identical
     to the three-launch path it replaces (cv1 conv -> fused Bottleneck on the y1 slice of the concat buffer -> cv2 conv) and
     equal to the fp32 reference with every intermediate map rounded to fp16.  Shapes: ragged tiles, maps smaller than one
-    tile, more tiles than persistent workgroups; the input is a channel slice of a wider buffer."""
+    tile; the input is a channel slice of a wider buffer.  The 300-image case (8 x 16: 2 x 1 tiles, padded to 2 x 2) exceeds the
+    grid cap of 768 only through padded empty tiles; tests/test_fp16_block_ops.py has the walk that continues inside one image."""
     B, H, W = shape
     cin, c, c2 = 64, 32, 128
     g = torch.Generator().manual_seed(33)
