@@ -14,7 +14,7 @@
 //   * conv 1's weights live in registers as MFMA A fragments for the whole launch (72 VGPRs), conv 2's in LDS.
 // K order (tap-major, channels ascending, 16 per MFMA) and the epilogue arithmetic (f16(SiLU) then + residual in f32)
 // equal conv_gemm.hip's, so the result is bit-identical to the two-launch path.
-#include "common.h"
+#include "fused_tile.h"
 
 #define BN_TH 8
 #define BN_TW 16
@@ -64,10 +64,7 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
     half8 a1[KSA];
 #pragma unroll
     for (int ks = 0; ks < KSA; ++ks) a1[ks] = *reinterpret_cast<const half8*>(p.w1 + (size_t)lrow * p.Kpad1 + 16 * ks + 8 * lh);
-    for (int i = tid; i < C * (9 * CH / 8); i += 256) {
-        const int row = i / (9 * CH / 8), ch = i - row * (9 * CH / 8);
-        *reinterpret_cast<half8*>(sw2 + row * W2S + ch * 8) = *reinterpret_cast<const half8*>(p.w2 + (size_t)row * p.Kpad2 + ch * 8);
-    }
+    stage_rows<256, C, 9 * CH / 8, W2S>(sw2, p.w2, p.Kpad2, tid);
     const half_t* a2base = sw2 + lrow * W2S + 8 * lh;
 
     // tile-independent lane tables
@@ -84,14 +81,11 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
     const half_t* b2base = smid + (ty2 * BN_MC + tx2) * MS + 8 * lh;     // hidden entry of tap (0, 0), this lane half's chunk
     const half_t* rbase = sx + ((ty2 + 2) * BN_XC + tx2 + 2) * XS + 4 * lh;  // residual: the pixel's own input entry
 
-    auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const TileIdx t = tile_index(p.grid, tile);
-        n = t.n; oy0 = t.ty * BN_TH; ox0 = t.tx * BN_TW;
-    };
     half8 pre[NLOAD];
-    int nn = 0, noy0 = 0, nox0 = 0;
+    int nn = 0, noy0 = 0, nox0 = 0;  // the tile whose patch is in `pre`
     auto fetch = [&](int tile) {
-        tile_origin(tile, nn, noy0, nox0);
+        const TileOrigin o = tile_origin<BN_TH, BN_TW>(p.grid, tile);
+        nn = o.n; noy0 = o.oy0; nox0 = o.ox0;
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
             const int y = noy0 - 2 + (it_rc[i] & 255), x = nox0 - 2 + ((it_rc[i] >> 8) & 255);
@@ -123,25 +117,11 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
             const half_t* xb = sx + (r * BN_XC + c) * XS + 8 * lh;  // input entry of tap (0, 0), this lane half's chunk
             f32x16 acc;
             acc_bias(acc, sb1, lh);  // accumulators start at the bias (common.h acc_bias)
-#pragma unroll
-            for (int ks = 0; ks < KSA; ++ks) {
-                const int k0 = 16 * ks, tap = k0 / C, ch0 = (k0 % C) / 8;  // compile-time; lane half 1 = next chunk
-                const half8 bf = *reinterpret_cast<const half8*>(xb + ((tap / 3) * BN_XC + tap % 3) * XS + ch0 * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[ks], bf, acc, 0, 0, 0);
-            }
-            const unsigned keep = ((unsigned)(oy0 - 1 + r) < (unsigned)p.H && (unsigned)(ox0 - 1 + c) < (unsigned)p.W) ? 0xffffffffu : 0u;
+            mfma_taps3x3<C, BN_XC, XS, KSA>(acc, [&](int k0) { return a1[k0 / 16]; }, xb);
+            const unsigned keep = ((unsigned)(oy0 - 1 + r) < (unsigned)p.H && (unsigned)(ox0 - 1 + c) < (unsigned)p.W) ? 0xffffffffu : 0u;  // outside the map: conv 2's zero padding
             if (mm < BN_NM) {
 #pragma unroll
-                for (int g = 0; g < CH / 8; ++g) {
-                    union { half4 h; unsigned u[2]; } o;
-                    f32x4 t = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                    if (p.act) t = silu4_f(t);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o.h[q] = (half_t)t[q];
-                    o.u[0] &= keep;  // outside the map: conv 2's zero padding
-                    o.u[1] &= keep;
-                    *reinterpret_cast<half4*>(smid + mm * MS + 8 * g + 4 * lh) = o.h;
-                }
+                for (int g = 0; g < CH / 8; ++g) *reinterpret_cast<half4*>(smid + mm * MS + 8 * g + 4 * lh) = act_f16(acc_group(acc, g), p.act, keep);
             }
         }
         lds_barrier();  // hidden patch complete
@@ -150,35 +130,15 @@ __global__ __launch_bounds__(256, 3) void bneck_fused_kernel(const BneckK p) {
         {
             f32x16 acc;
             acc_bias(acc, sb2, lh);
-#pragma unroll
-            for (int ks = 0; ks < KSB; ++ks) {
-                const int k0 = 16 * ks, tap = k0 / CH, ch0 = (k0 % CH) / 8;
-                const half8 bf = *reinterpret_cast<const half8*>(b2base + ((tap / 3) * BN_MC + tap % 3) * MS + ch0 * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(a2base + 16 * ks), bf, acc, 0, 0, 0);
-            }
+            mfma_taps3x3<CH, BN_MC, MS, KSB>(acc, [&](int k0) { return *reinterpret_cast<const half8*>(a2base + k0); }, b2base);
             const int prow = wave * 32 + lrow;
 #pragma unroll
-            for (int g = 0; g < C / 8; ++g) {
-                const half4 rv = *reinterpret_cast<const half4*>(rbase + 8 * g);
-                half4 o;
-                f32x4 t = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                if (p.act) t = silu4_f(t);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = (half_t)((float)(half_t)t[q] + (float)rv[q]);
-                *reinterpret_cast<half4*>(sout + prow * LDO + 8 * g + 4 * lh) = o;
-            }
+            for (int g = 0; g < C / 8; ++g)
+                *reinterpret_cast<half4*>(sout + prow * LDO + 8 * g + 4 * lh) = act_res_f16(*reinterpret_cast<const half4*>(rbase + 8 * g), acc_group(acc, g), p.act);
         }
         lds_barrier();  // output tile complete
 
-        constexpr int CPRW = C / 8;
-#pragma unroll
-        for (int id = tid; id < BN_TH * BN_TW * CPRW; id += 256) {
-            const int prow = id / CPRW, cc = (id % CPRW) * 8;
-            const int oy = oy0 + prow / BN_TW, ox = ox0 + prow % BN_TW;
-            if (oy < p.H && ox < p.W)
-                *reinterpret_cast<half8*>(p.dst + ((size_t)(n * p.H + oy) * p.W + ox) * p.ldd + cc) =
-                    *reinterpret_cast<const half8*>(sout + prow * LDO + cc);
-        }
+        store_tile<BN_TH, BN_TW, C, LDO, 256>(p.dst, p.H, p.W, p.ldd, sout, n, oy0, ox0, tid);
     }
 }
 
@@ -217,14 +177,8 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
 
     if (tid < CH) sb1[tid] = p.b1[tid];
     if (tid < C) sb2[tid] = p.b2[tid];
-    for (int i = tid; i < CH * (9 * C / 8); i += 512) {
-        const int row = i / (9 * C / 8), ch = i - row * (9 * C / 8);
-        *reinterpret_cast<half8*>(sw1 + row * W1S + ch * 8) = *reinterpret_cast<const half8*>(p.w1 + (size_t)row * p.Kpad1 + ch * 8);
-    }
-    for (int i = tid; i < C * (9 * CH / 8); i += 512) {
-        const int row = i / (9 * CH / 8), ch = i - row * (9 * CH / 8);
-        *reinterpret_cast<half8*>(sw2 + row * W2S + ch * 8) = *reinterpret_cast<const half8*>(p.w2 + (size_t)row * p.Kpad2 + ch * 8);
-    }
+    stage_rows<512, CH, 9 * C / 8, W1S>(sw1, p.w1, p.Kpad1, tid);
+    stage_rows<512, C, 9 * CH / 8, W2S>(sw2, p.w2, p.Kpad2, tid);
 
     // tile-independent lane tables
     int it_off[NLOAD], it_r[NLOAD], it_c[NLOAD];
@@ -262,14 +216,11 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
     const half_t* rbase = sx + ((ty2 + 2) * BN_XC + tx2 + 2) * XS + 32 * ct + 4 * lh;  // shortcut: the pixel's own input entry
     half_t* obase = sout + (pt * 32 + lrow) * LDO + 32 * ct + 4 * lh;
 
-    auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const TileIdx t = tile_index(p.grid, tile);
-        n = t.n; oy0 = t.ty * BN_TH; ox0 = t.tx * BN_TW;
-    };
     half8 pre[NLOAD];
-    int nn = 0, noy0 = 0, nox0 = 0;
+    int nn = 0, noy0 = 0, nox0 = 0;  // the tile whose patch is in `pre`
     auto fetch = [&](int tile) {
-        tile_origin(tile, nn, noy0, nox0);
+        const TileOrigin o = tile_origin<BN_TH, BN_TW>(p.grid, tile);
+        nn = o.n; noy0 = o.oy0; nox0 = o.ox0;
         const half_t* tb = p.src + ((long long)(nn * p.H + noy0 - 2) * p.W + (nox0 - 2)) * p.lds;  // patch origin (a base only)
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
@@ -296,26 +247,12 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
         if (wave < BN_NMT) {
             f32x16 acc;
             acc_bias(acc, sb1, lh);
-#pragma unroll
-            for (int ks = 0; ks < KSA; ++ks) {
-                // the layer's K walk (conv_select.hip conv_korder: 3x3, Cin % 32 == 0 -> chunk-major, 32-channel chunks): chunk, tap, 16-wide half
-                const int chunk = ks / 18, tap = (ks % 18) >> 1, k0 = tap * C + 32 * chunk + 16 * (ks & 1), ch0 = (k0 % C) / 8;  // compile-time
-                const half8 bf = *reinterpret_cast<const half8*>(xb + ((tap / 3) * BN_XC + tap % 3) * XS + ch0 * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(a1base + k0), bf, acc, 0, 0, 0);
-            }
-            const unsigned keep = ((unsigned)(oy0 - 1 + r1) < (unsigned)p.H && (unsigned)(ox0 - 1 + c1) < (unsigned)p.W) ? 0xffffffffu : 0u;
+            // the layer's K walk (conv_select.hip conv_korder: 3x3, Cin % 32 == 0 -> chunk-major, 32-channel chunks)
+            mfma_taps3x3<C, BN_XC, XS, KSA, KOrder::Chunk32Major>(acc, [&](int k0) { return *reinterpret_cast<const half8*>(a1base + k0); }, xb);
+            const unsigned keep = ((unsigned)(oy0 - 1 + r1) < (unsigned)p.H && (unsigned)(ox0 - 1 + c1) < (unsigned)p.W) ? 0xffffffffu : 0u;  // outside the map: conv 2's zero padding
             if (mm1 < BN_NM) {
 #pragma unroll
-                for (int g = 0; g < CH / 8; ++g) {
-                    union { half4 h; unsigned u[2]; } o;
-                    f32x4 t = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                    if (p.act) t = silu4_f(t);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o.h[q] = (half_t)t[q];
-                    o.u[0] &= keep;  // outside the map: conv 2's zero padding
-                    o.u[1] &= keep;
-                    *reinterpret_cast<half4*>(smid + mm1 * MS + 8 * g + 4 * lh) = o.h;
-                }
+                for (int g = 0; g < CH / 8; ++g) *reinterpret_cast<half4*>(smid + mm1 * MS + 8 * g + 4 * lh) = act_f16(acc_group(acc, g), p.act, keep);
             }
         }
         lds_barrier();  // hidden patch complete
@@ -324,22 +261,9 @@ __global__ __launch_bounds__(512) void bneck_fused_wide_kernel(const BneckK p) {
         {
             f32x16 acc;
             acc_bias(acc, sb2 + 32 * ct, lh);
+            mfma_taps3x3<CH, BN_MC, MS, KSB>(acc, [&](int k0) { return *reinterpret_cast<const half8*>(a2base + k0); }, b2base);
 #pragma unroll
-            for (int ks = 0; ks < KSB; ++ks) {
-                const int k0 = 16 * ks, tap = k0 / CH, ch0 = (k0 % CH) / 8;
-                const half8 bf = *reinterpret_cast<const half8*>(b2base + ((tap / 3) * BN_MC + tap % 3) * MS + ch0 * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(a2base + 16 * ks), bf, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const half4 rv = *reinterpret_cast<const half4*>(rbase + 8 * g);
-                half4 o;
-                f32x4 t = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                if (p.act) t = silu4_f(t);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = (half_t)((float)(half_t)t[q] + (float)rv[q]);
-                *reinterpret_cast<half4*>(obase + 8 * g) = o;
-            }
+            for (int g = 0; g < 4; ++g) *reinterpret_cast<half4*>(obase + 8 * g) = act_res_f16(*reinterpret_cast<const half4*>(rbase + 8 * g), acc_group(acc, g), p.act);
         }
         lds_barrier();  // output tile complete
 #pragma unroll
@@ -354,8 +278,7 @@ bool bneck_fused_supported(int C, int CH) { return (C == 32 && CH == 16) || (C =
 int launch_bneck_fused(const BneckArgs& a, hipStream_t s) {
     if (!bneck_fused_supported(a.C, a.CH)) BSY_FAIL(BSY_ERR_ARG, "bottleneck: unsupported widths (C %d, hidden %d): need (32, 16) or (64, 32)", a.C, a.CH);
     if (a.B <= 0 || a.H <= 0 || a.W <= 0) BSY_FAIL(BSY_ERR_ARG, "bottleneck: bad extent");
-    if (((uintptr_t)a.src & 15) || ((uintptr_t)a.dst & 15) || (a.lds & 7) || (a.ldd & 7) || a.lds < a.C || a.ldd < a.C ||
-        ((uintptr_t)a.w1 & 15) || ((uintptr_t)a.w2 & 15) || ((uintptr_t)a.b1 & 15) || ((uintptr_t)a.b2 & 15) ||
+    if (!all_aligned16(a.src, a.dst, a.w1, a.w2, a.b1, a.b2) || (a.lds & 7) || (a.ldd & 7) || a.lds < a.C || a.ldd < a.C ||
         a.Kpad1 < 9 * a.C || a.Kpad2 < 9 * a.CH || (a.Kpad1 & 7) || (a.Kpad2 & 7))
         BSY_FAIL(BSY_ERR_ARG, "bottleneck: misaligned pointer / leading dimension");
     BneckK k;
@@ -364,12 +287,12 @@ int launch_bneck_fused(const BneckArgs& a, hipStream_t s) {
     const int rc = make_tile_grid(k.grid, a.B, a.H, a.W, BN_TH, BN_TW, "bottleneck");
     if (rc != BSY_OK) return rc;
     if (a.C == 64) {
-        const int grid = k.grid.ntiles < 256 ? k.grid.ntiles : 256;  // one 512-thread workgroup (143 KiB of LDS) per CU
+        const int grid = persistent_grid(k.grid.ntiles, 256);  // one 512-thread workgroup (143 KiB of LDS) per CU
         hipLaunchKernelGGL((bneck_fused_wide_kernel<64, 32>), dim3(grid), dim3(512), 0, s, k);
         HIP_TRY(hipGetLastError());
         return BSY_OK;
     }
-    const int grid = k.grid.ntiles < 768 ? k.grid.ntiles : 768;  // 3 workgroups per CU
+    const int grid = persistent_grid(k.grid.ntiles, 768);  // 3 workgroups per CU
     hipLaunchKernelGGL((bneck_fused_kernel<32, 16>), dim3(grid), dim3(256), 0, s, k);
     HIP_TRY(hipGetLastError());
     return BSY_OK;

@@ -18,7 +18,7 @@
 // cv2 as MFMA A fragments in registers).  K orders (channels
 // ascending for the 1x1 convs, tap-major for the 3x3 convs) and the epilogue arithmetic (f16(SiLU), shortcut added in f32)
 // equal conv_gemm.hip's / bneck_fused.hip's, so the block returns bit for bit what the three-launch path returns.
-#include "common.h"
+#include "fused_tile.h"
 
 #define CK_TH 4
 #define CK_TW 16
@@ -88,26 +88,13 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
     half8 w1y1[KS1], a4[3 * KSEG];
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) w1y1[ks] = *reinterpret_cast<const half8*>(p.w1 + (size_t)(C + lrow) * p.K1 + 16 * ks + 8 * lh);
-    for (int i = tid; i < C * (CIN / 8); i += 256) {
-        const int row = i / (CIN / 8), ch = i - row * (CIN / 8);
-        *reinterpret_cast<half8*>(sw0 + row * W0S + ch * 8) = *reinterpret_cast<const half8*>(p.w1 + (size_t)row * p.K1 + ch * 8);
-    }
+    stage_rows<256, C, CIN / 8, W0S>(sw0, p.w1, p.K1, tid);
 #pragma unroll
     for (int ks = 0; ks < 3 * KSEG; ++ks) a4[ks] = *reinterpret_cast<const half8*>(p.w4 + (size_t)(32 * wave + lrow) * p.K4 + 16 * ks + 8 * lh);
-    for (int i = tid; i < CH * (9 * C / 8); i += 256) {
-        const int row = i / (9 * C / 8), ch = i - row * (9 * C / 8);
-        *reinterpret_cast<half8*>(swa + row * WAS + ch * 8) = *reinterpret_cast<const half8*>(p.wa + (size_t)row * p.Ka + ch * 8);
-    }
-    for (int i = tid; i < C * (9 * CH / 8); i += 256) {
-        const int row = i / (9 * CH / 8), ch = i - row * (9 * CH / 8);
-        *reinterpret_cast<half8*>(swb + row * WBS + ch * 8) = *reinterpret_cast<const half8*>(p.wb + (size_t)row * p.Kb + ch * 8);
-    }
+    stage_rows<256, CH, 9 * C / 8, WAS>(swa, p.wa, p.Ka, tid);
+    stage_rows<256, C, 9 * CH / 8, WBS>(swb, p.wb, p.Kb, tid);
 
     // Tile-independent lane constants: nothing that depends only on the lane is recomputed per tile.
-    auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const TileIdx t = tile_index(p.grid, tile);
-        n = t.n; oy0 = t.ty * CK_TH; ox0 = t.tx * CK_TW;
-    };
     // S1 jobs of this wave (compile-time job list per wave, lane-constant entries): job A = y1 on patch pixel tile `wave`;
     // job B = y1 on pixel tile 4 (wave 0) or y0 on output pixel tile wave - 1 (waves 1, 2); wave 3 has no job B
     const int lty = lrow >> 4, ltx = lrow & 15;
@@ -117,9 +104,10 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
     const unsigned relA = (unsigned)((rA * p.W + cA) * p.lds + 8 * lh), relB = (unsigned)((rB * p.W + cB) * p.lds + 8 * lh);
     // x of the NEXT tile, already in cv1's B-fragment layout (lane = patch pixel, k-step ks = channels 16 ks + 8 lh ..): zeros outside the image
     half8 xa[KS1], xb[KS1];
-    int nn = 0, noy0 = 0, nox0 = 0;
+    int nn = 0, noy0 = 0, nox0 = 0;  // the tile whose x is in `xa` / `xb`
     auto fetch = [&](int tile) {
-        tile_origin(tile, nn, noy0, nox0);
+        const TileOrigin o = tile_origin<CK_TH, CK_TW>(p.grid, tile);
+        nn = o.n; noy0 = o.oy0; nox0 = o.ox0;
         // patch origin pixel (oy0 - 2, ox0 - 2): may lie outside the image -- only a base for pointer arithmetic
         const half_t* tb = p.src + ((long long)(nn * p.H + noy0 - 2) * p.W + (nox0 - 2)) * p.lds;
         const bool inA = (unsigned)(noy0 - 2 + rA) < (unsigned)p.H && (unsigned)(nox0 - 2 + cA) < (unsigned)p.W;
@@ -160,15 +148,7 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
             const unsigned keep = (is_y0 || ((unsigned)(oy0 - 2 + r) < (unsigned)p.H && (unsigned)(ox0 - 2 + c) < (unsigned)p.W)) ? 0xffffffffu : 0u;
             half_t* d = is_y0 ? sy0 + opix * YS : sy1 + e * YS;
 #pragma unroll
-            for (int g = 0; g < C / 8; ++g) {
-                union { half4 h; unsigned u[2]; } o;
-                const f32x4 tv = silu4_f(f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]});
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o.h[q] = (half_t)tv[q];
-                o.u[0] &= keep;
-                o.u[1] &= keep;
-                *reinterpret_cast<half4*>(d + 8 * g + 4 * lh) = o.h;
-            }
+            for (int g = 0; g < C / 8; ++g) *reinterpret_cast<half4*>(d + 8 * g + 4 * lh) = act_f16(acc_group(acc, g), 1, keep);
         };
         s1_job(false, w1y1, xa, eA, rA, cA, 0);
         if (wave == 0) s1_job(false, w1y1, xb, eB, rB, cB, 0);
@@ -192,24 +172,11 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
             const half_t* a1base = swa + ao;
             f32x16 acc;
             acc_bias(acc, sba, lh);  // (rows >= CH read into the next bias array: accumulator rows no epilogue uses)
-#pragma unroll
-            for (int ks = 0; ks < KSA; ++ks) {
-                const int k0 = 16 * ks, tap = k0 / C, ch0 = (k0 % C) / 8;  // compile-time
-                const half8 bf = *reinterpret_cast<const half8*>(yb + ((tap / 3) * CK_XC + tap % 3) * YS + ch0 * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(a1base + 16 * ks), bf, acc, 0, 0, 0);
-            }
-            const unsigned keep = ((unsigned)(oy0 - 1 + r) < (unsigned)p.H && (unsigned)(ox0 - 1 + c) < (unsigned)p.W) ? 0xffffffffu : 0u;
+            mfma_taps3x3<C, CK_XC, YS, KSA>(acc, [&](int k0) { return *reinterpret_cast<const half8*>(a1base + k0); }, yb);
+            const unsigned keep = ((unsigned)(oy0 - 1 + r) < (unsigned)p.H && (unsigned)(ox0 - 1 + c) < (unsigned)p.W) ? 0xffffffffu : 0u;  // outside the map: m.cv2's zero padding
             if (mm < CK_NM) {
 #pragma unroll
-                for (int g = 0; g < CH / 8; ++g) {
-                    union { half4 h; unsigned u[2]; } o;
-                    const f32x4 tv = silu4_f(f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]});
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o.h[q] = (half_t)tv[q];
-                    o.u[0] &= keep;  // outside the map: m.cv2's zero padding
-                    o.u[1] &= keep;
-                    *reinterpret_cast<half4*>(smid + mm * MS + 8 * g + 4 * lh) = o.h;
-                }
+                for (int g = 0; g < CH / 8; ++g) *reinterpret_cast<half4*>(smid + mm * MS + 8 * g + 4 * lh) = act_f16(acc_group(acc, g), 1, keep);
             }
         }
         lds_barrier();  // (C) hidden patch complete
@@ -221,21 +188,10 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
             const half_t* y1own = sy1 + ((ty2 + 2) * CK_XC + ltx + 2) * YS;        // the pixel's own y1 entry (the shortcut)
             f32x16 acc;
             acc_bias(acc, sbb, lh);
+            mfma_taps3x3<CH, CK_MC, MS, KSB>(acc, [&](int k0) { return *reinterpret_cast<const half8*>(a2base + k0); }, b2base);
 #pragma unroll
-            for (int ks = 0; ks < KSB; ++ks) {
-                const int k0 = 16 * ks, tap = k0 / CH, ch0 = (k0 % CH) / 8;
-                const half8 bf = *reinterpret_cast<const half8*>(b2base + ((tap / 3) * CK_MC + tap % 3) * MS + ch0 * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8*>(a2base + 16 * ks), bf, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int g = 0; g < C / 8; ++g) {
-                const half4 rv = *reinterpret_cast<const half4*>(y1own + 8 * g + 4 * lh);
-                half4 o;
-                const f32x4 tv = silu4_f(f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]});
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = (half_t)((float)(half_t)tv[q] + (float)rv[q]);
-                *reinterpret_cast<half4*>(sy2 + (32 * wave + lrow) * YS + 8 * g + 4 * lh) = o;
-            }
+            for (int g = 0; g < C / 8; ++g)
+                *reinterpret_cast<half4*>(sy2 + (32 * wave + lrow) * YS + 8 * g + 4 * lh) = act_res_f16(*reinterpret_cast<const half4*>(y1own + 8 * g + 4 * lh), acc_group(acc, g), 1);
         }
         lds_barrier();  // (D) y2 tile complete
 
@@ -258,14 +214,7 @@ __global__ __launch_bounds__(256, 3) void c3k2_fused_kernel(const C3k2K p) {
 #pragma unroll
             for (int q2 = 0; q2 < 2; ++q2)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int cc = 32 * wave + 8 * g + 4 * lh;
-                    half4 o;
-                    const f32x4 tv = silu4_f(f32x4{acc[q2][4 * g], acc[q2][4 * g + 1], acc[q2][4 * g + 2], acc[q2][4 * g + 3]});
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = (half_t)tv[q];
-                    *reinterpret_cast<half4*>(sout + (32 * q2 + lrow) * OS + cc) = o;
-                }
+                for (int g = 0; g < 4; ++g) *reinterpret_cast<half4*>(sout + (32 * q2 + lrow) * OS + (32 * wave + 8 * g + 4 * lh)) = act_f16(acc_group(acc[q2], g), 1);
         }
         lds_barrier();  // (E) output tile complete
 
@@ -299,7 +248,7 @@ int launch_c3k2_fused(const C3k2Args& a, hipStream_t s) {
     bsy_conv_packed_dims(a.C2, 3 * a.C, 1, &cp, &k.K4);
     const int rc = make_tile_grid(k.grid, a.B, a.H, a.W, CK_TH, CK_TW, "c3k2");
     if (rc != BSY_OK) return rc;
-    const int grid = k.grid.ntiles < 768 ? k.grid.ntiles : 768;  // three 256-thread workgroups (48 KiB of LDS each) per CU
+    const int grid = persistent_grid(k.grid.ntiles, 768);  // three 256-thread workgroups (48 KiB of LDS each) per CU
     hipLaunchKernelGGL((c3k2_fused_kernel<64, 32, 128>), dim3(grid), dim3(256), 0, s, k);
     HIP_TRY(hipGetLastError());
     return BSY_OK;

@@ -19,7 +19,7 @@
 // (bsyolo_ops.hip dwconv_tile_kernel), SiLU in f32 and one rounding to f16 per intermediate map, conv4's K walk in ascending
 // 16-channel MFMA steps from accumulators that start at the bias, activation rounded to f16 BEFORE the shortcut is added
 // (conv_kernels.h conv_epilogue_lds) -- the fused and the unfused plan return the same bits (tests/test_gpu_parity.py).
-#include "common.h"
+#include "fused_tile.h"
 
 namespace {
 
@@ -62,10 +62,7 @@ __global__ __launch_bounds__(256, 2) void pmsfa_tail_kernel(const PmsfaArgs a, i
         const int row = i / CQ, c = i - row * CQ;
         sW3[i] = row < 49 ? a.w3[(size_t)row * a.wld3 + c] : a.b3[c];
     }
-    for (int i = tid; i < C * (C / 8); i += 256) {
-        const int row = i / (C / 8), pc = i - row * (C / 8);
-        *reinterpret_cast<half8*>(sW4 + row * LDW + pc * 8) = *reinterpret_cast<const half8*>(a.w4 + (size_t)row * a.kpad4 + pc * 8);
-    }
+    stage_rows<256, C, C / 8, LDW>(sW4, a.w4, a.kpad4, tid);
 
     // ---- per thread, tile-independent: which pieces of the p1 patch / of p2 / of the output it moves -----------------------
     constexpr int NPATCH = (P1H * P1W * NP1 + 255) / 256;
@@ -266,13 +263,7 @@ __global__ __launch_bounds__(256, 2) void pmsfa_tail_kernel(const PmsfaArgs a, i
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 tv = silu4_f(f32x4{acc[ct][mt][4 * g], acc[ct][mt][4 * g + 1], acc[ct][mt][4 * g + 2], acc[ct][mt][4 * g + 3]});
-                    half4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (half_t)tv[e];
-                    *reinterpret_cast<half4*>(sO + prow * LDO + ct * 32 + 8 * g + 4 * lh) = o;
-                }
+                for (int g = 0; g < 4; ++g) *reinterpret_cast<half4*>(sO + prow * LDO + ct * 32 + 8 * g + 4 * lh) = act_f16(acc_group(acc[ct][mt], g), 1);
         }
         // rows [wave * RW, (wave + 1) * RW) were written by this wave only; a wave's LDS operations execute in order
 #pragma unroll
@@ -296,7 +287,7 @@ int launch_tail(const PmsfaArgs& a, hipStream_t s) {
     // persistent workgroups (the weights are staged once, the next tile's patch is fetched under the current tile's arithmetic): as many
     // as are resident at once -- two per CU at 71 / 76 KiB of LDS and <= 256 registers
     const int resident = 256 * 2;  // MI355X: 256 CUs
-    const unsigned grid = (unsigned)(ntiles < resident ? ntiles : resident);
+    const unsigned grid = (unsigned)persistent_grid((int)ntiles, resident);
     const unsigned spanP = (unsigned)((((long long)a.B * a.H * a.W - 1) * a.ldp + C / 2) * 2);  // p1 = the first half of every pixel of P
     hipLaunchKernelGGL((pmsfa_tail_kernel<C, TH, TW>), dim3(grid), dim3(256), 0, s, a, tiles_x, tiles_y, (int)ntiles, spanP);
     HIP_TRY(hipGetLastError());
@@ -314,8 +305,7 @@ int launch_pmsfa_tail(const PmsfaArgs& a, hipStream_t s) {
     if ((a.ldp & 7) || (a.ldx & 7) || (a.ldd & 7) || a.ldp < a.C || a.ldx < a.C || a.ldd < a.C || (a.wld2 & 3) || (a.wld3 & 3) || a.wld2 < a.C / 2 ||
         a.wld3 < a.C / 4 || (a.kpad4 & 7) || a.kpad4 < a.C)
         BSY_FAIL(BSY_ERR_ARG, "pmsfa_tail: strides must be multiples of 8 channels and cover the views");
-    if (((uintptr_t)a.P & 15) || ((uintptr_t)a.x & 15) || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.w2 & 15) || ((uintptr_t)a.b2 & 15) ||
-        ((uintptr_t)a.w3 & 15) || ((uintptr_t)a.b3 & 15) || ((uintptr_t)a.w4 & 15) || ((uintptr_t)a.b4 & 15))
+    if (!all_aligned16(a.P, a.x, a.dst, a.w2, a.b2, a.w3, a.b3, a.w4, a.b4))
         BSY_FAIL(BSY_ERR_ARG, "pmsfa_tail: pointers must be 16-byte aligned");
     if ((long long)a.B * a.H * a.W * a.ldp >= (1LL << 31)) BSY_FAIL(BSY_ERR_ARG, "pmsfa_tail: source view exceeds 2^31 elements (split the batch)");
     if (a.dst == a.x || a.dst == a.P) BSY_FAIL(BSY_ERR_ARG, "pmsfa_tail: the output must not alias an input (tiles read their neighbours' halo)");

@@ -16,7 +16,8 @@
 //     start computing the current one, so HBM latency hides under the MFMA / LDS work; stores go through an LDS tile
 //     as coalesced 16-byte pieces.
 // Accumulation order (K ascending in 16-wide MFMA steps, k = (kh, kw, c)) equals conv_first.hip's and conv_gemm.hip's,
-// so the result is bit-identical to the unfused pair (tests/test_gpu_parity.py::test_stem_fused_matches_unfused).
+// so the result is bit-identical to the unfused pair (tests/test_gpu_parity.py::test_stem_fused_matches_unfused_and_oracle).
+#include "fused_tile.h"
 #include "image_conv.h"
 
 #define ST_TH 4
@@ -91,14 +92,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 3) void stem_fused_kernel
     }
     const int e1base = (2 * (2 * mt1 + (lrow >> 4))) * ST_C0W + (lrow & 15);  // layer-1 lane pixel -> patch entry of tap (0, 0)
 
-    auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
-        const TileIdx t = tile_index(p.grid, tile);
-        n = t.n; oy0 = t.ty * ST_TH; ox0 = t.tx * ST_TW;
-    };
     ImgItem<T> pre[ST_NLOAD];
     int nn = 0, noy0 = 0, nox0 = 0;  // coordinates of the tile whose patch is in `pre`
     auto fetch = [&](int tile) {
-        tile_origin(tile, nn, noy0, nox0);
+        const TileOrigin o = tile_origin<ST_TH, ST_TW>(p.grid, tile);
+        nn = o.n; noy0 = o.oy0; nox0 = o.ox0;
         const int n = nn, oy0 = noy0, ox0 = nox0;
         const T* ip = img + (size_t)n * 3 * p.H * p.W;
 #pragma unroll
@@ -133,21 +131,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 3) void stem_fused_kernel
             for (int s = 0; s < IMGC_KSUB; ++s)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[s], img_frag<ST_ROWPX>(simg, win, s, lh), acc, 0, 0, 0);
             // bias + SiLU -> f16; positions outside the layer-0 map are layer 1's zero padding
-            // (an AND with an all-ones / all-zeros word: a select on `inside` makes the compiler branch around each SiLU)
             const unsigned keep = ((unsigned)(r00 + r) < (unsigned)p.OH0 && (unsigned)(c00 + c) < (unsigned)p.OW0) ? 0xffffffffu : 0u;
             const int e = r * ST_C0W + (c & 1) * ST_EV + (c >> 1);
             if (pp < ST_NE) {
 #pragma unroll
-                for (int g = 0; g < NCH; ++g) {  // couts 8g + 4lh .. +3  (C0 = 16: g < 2 only)
-                    union { half4 h; unsigned u[2]; } o;
-                    f32x4 t = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                    if (p.act) t = silu4_f(t);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o.h[q] = (half_t)t[q];
-                    o.u[0] &= keep;
-                    o.u[1] &= keep;
-                    *reinterpret_cast<half4*>(smid + (e * NCH + (g ^ ((e >> 2) & (NCH - 1)))) * 8 + 4 * lh) = o.h;
-                }
+                for (int g = 0; g < NCH; ++g)  // couts 8g + 4lh .. +3  (C0 = 16: g < 2 only)
+                    *reinterpret_cast<half4*>(smid + (e * NCH + (g ^ ((e >> 2) & (NCH - 1)))) * 8 + 4 * lh) = act_f16(acc_group(acc, g), p.act, keep);
             }
         }
         lds_barrier();  // layer-0 patch complete
@@ -172,27 +161,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 3) void stem_fused_kernel
             }
             const int prow = mt1 * 32 + lrow;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c = nh1 * 32 + 8 * g + 4 * lh;
-                half4 o;
-                f32x4 t = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                if (p.act) t = silu4_f(t);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = (half_t)t[q];
-                *reinterpret_cast<half4*>(sout + prow * LDO + c) = o;
-            }
+            for (int g = 0; g < 4; ++g) *reinterpret_cast<half4*>(sout + prow * LDO + (nh1 * 32 + 8 * g + 4 * lh)) = act_f16(acc_group(acc, g), p.act);
         }
         lds_barrier();  // output tile complete
 
-        constexpr int CPRW = C1 / 8;
-#pragma unroll
-        for (int id = tid; id < ST_TH * ST_TW * CPRW; id += 256) {
-            const int prow = id / CPRW, cc = (id % CPRW) * 8;
-            const int oy = oy0 + prow / ST_TW, ox = ox0 + prow % ST_TW;
-            if (oy < p.OH1 && ox < p.OW1)
-                *reinterpret_cast<half8*>(p.dst + ((size_t)(n * p.OH1 + oy) * p.OW1 + ox) * p.ldd + cc) =
-                    *reinterpret_cast<const half8*>(sout + prow * LDO + cc);
-        }
+        store_tile<ST_TH, ST_TW, C1, LDO, 256>(p.dst, p.OH1, p.OW1, p.ldd, sout, n, oy0, ox0, tid);
     }
 }
 
@@ -203,7 +176,7 @@ bool stem_fused_supported(int C0, int C1, int H, int W) {
 template <typename T>
 static int launch_t(const StemArgs& a, const StemK& k, hipStream_t s) {
     const int slots = sizeof(T) == 4 ? 512 : 768;      // 3 workgroups per CU (register-limited: a fourth needs <= 128 VGPRs and spills 61; f32 images: 2), tiles dealt round-robin
-    const int grid = k.grid.ntiles < slots ? k.grid.ntiles : slots;
+    const int grid = persistent_grid(k.grid.ntiles, slots);
     if (a.C0 == 32) hipLaunchKernelGGL((stem_fused_kernel<T, 32, 64>), dim3(grid), dim3(256), 0, s, k);
     else hipLaunchKernelGGL((stem_fused_kernel<T, 16, 32>), dim3(grid), dim3(256), 0, s, k);
     HIP_TRY(hipGetLastError());
@@ -217,8 +190,8 @@ int launch_stem_fused(const StemArgs& a, hipStream_t s) {
     const int OH1 = (OH0 - 1) / 2 + 1, OW1 = (OW0 - 1) / 2 + 1;
     if (a.OH != OH1 || a.OW != OW1) BSY_FAIL(BSY_ERR_ARG, "stem: output extent mismatch (%d x %d, expected %d x %d)", a.OH, a.OW, OH1, OW1);
     const int esz = a.img_dtype == BSY_F32 ? 4 : 2;
-    if (((uintptr_t)a.img & (4 * esz - 1)) || ((uintptr_t)a.dst & 15) || (a.ldd & 7) || ((uintptr_t)a.w0 & 15) ||
-        ((uintptr_t)a.w1 & 15) || ((uintptr_t)a.b0 & 15) || ((uintptr_t)a.b1 & 15) || (a.Kpad1 & 7) || a.Kpad1 < 9 * a.C0 || a.Kpad1 < 16 * ((9 * a.C0 + 15) / 16))
+    if (((uintptr_t)a.img & (4 * esz - 1)) || !all_aligned16(a.dst, a.w0, a.w1, a.b0, a.b1) || (a.ldd & 7) || (a.Kpad1 & 7) || a.Kpad1 < 9 * a.C0 ||
+        a.Kpad1 < 16 * ((9 * a.C0 + 15) / 16))
         BSY_FAIL(BSY_ERR_ARG, "stem: misaligned pointer / leading dimension");
     StemK k;
     k.img = a.img; k.w0 = (const half_t*)a.w0; k.b0 = a.b0; k.w1 = (const half_t*)a.w1; k.b1 = a.b1; k.dst = a.dst;
