@@ -31,6 +31,45 @@ from . import tta as T
 from .plan import SWITCHES, Plan
 from .weights import BN_EPS, adopt_offsets, pack_plan_weights, repconv_form
 
+_DTYPES = {"int32": torch.int32, "float32": torch.float32}  # Plan.outputs' dtypes besides "io", the forward's own
+
+
+def _outputs(plan: Plan, want_raw: bool, device, dtype) -> Dict[str, Optional[torch.Tensor]]:
+    """Fresh tensors for the plan's external outputs (Plan.outputs), by name; None for the ones only a want_raw caller has."""
+    return {o.name: torch.empty(o.shape, dtype=_DTYPES.get(o.dtype, dtype), device=device) if want_raw or not o.raw_only else None
+            for o in plan.outputs.values()}
+
+
+def _bind(plan: Plan, im: torch.Tensor, outs: Mapping[str, Optional[torch.Tensor]]):
+    """(void* array, length) of the plan's external slots: the image and every output `outs` holds; the others stay unbound (NULL), and
+    the launches skip their stores (include/bsyolo.h, bsy_plan_run)."""
+    ptrs = [None] * (1 + max(o.slot for o in plan.outputs.values()))
+    ptrs[Plan.EXT_IMG] = im.data_ptr()
+    for o in plan.outputs.values():
+        if outs.get(o.name) is not None:
+            ptrs[o.slot] = outs[o.name].data_ptr()
+    return (C.c_void_p * len(ptrs))(*ptrs), len(ptrs)
+
+
+def pack_outputs(meta: Mapping, outs: Mapping[str, Optional[torch.Tensor]]):
+    """What the model's forward returns in eval, from the outputs by name (y already carries the rows behind the scores)."""
+    y = outs["y"]
+    if meta.get("task") == "classify":  # Classify.forward (head.py:304): (softmax, logits)
+        return y, outs["x"]
+    raws = [outs[f"raw{l}"] for l in range(len(meta["levels"]))]
+    if meta["nm"]:  # Segment.forward (head.py:197): (cat(y, mc), (raw, mc, proto))
+        return y, (raws, y[:, 4 + meta["nc"]:], outs["proto"])
+    if meta["ne"]:  # OBB.forward (head.py:223): (cat(y, angle), (raw, angle))
+        return y, (raws, y[:, 4 + meta["nc"]:])
+    if meta.get("nk", 0):  # Pose.forward (head.py:250): (cat(y, pred_kpt), (raw, kpt))
+        return y, (raws, outs["kpt"])
+    return y, raws  # Detect.forward (head.py:74)
+
+
+def cat_outputs(chunks: List[Mapping[str, Optional[torch.Tensor]]]) -> Dict[str, Optional[torch.Tensor]]:
+    """The outputs of consecutive slices of a batch, joined along dim 0 (an output no chunk has stays None)."""
+    return {k: None if v is None else torch.cat([c[k] for c in chunks]) for k, v in chunks[0].items()}
+
 
 class YoloEngine:
     def __init__(self, cfg: dict, state_dict: Mapping[str, torch.Tensor], device: int = 0, bn_eps: float = BN_EPS,
@@ -240,13 +279,6 @@ class YoloEngine:
             hit = self._elems[(H, W)] = Plan(self.cfg, 1, H, W, **self._fuse_kw()).max_view_elems()
         return hit
 
-    def _ext(self, im, y, raws, proto=None):
-        # slot order of Plan: image, y, raw maps of levels 0-2, proto (a pose plan: the raw keypoint logits, Plan.EXT_KPT), then the
-        # fourth level's raw map (Plan.EXT_RAW3)
-        raws = [r.data_ptr() if r is not None else None for r in raws]
-        ptrs = [im.data_ptr(), y.data_ptr()] + raws[:3] + [proto.data_ptr() if proto is not None else None] + raws[3:]
-        return (C.c_void_p * len(ptrs))(*ptrs), len(ptrs)
-
     @staticmethod
     def _dense(im: torch.Tensor) -> torch.Tensor:
         """`im` contiguous AND with its first element on a 16-byte boundary.  contiguous() keeps a contiguous view at an odd storage
@@ -267,90 +299,38 @@ class YoloEngine:
             raise ValueError("expected 3 input channels")
         if H % self.max_stride or W % self.max_stride:  # (before any plan of this size is built: the graph walk asserts on such maps)
             raise ValueError(f"input {H}x{W} must be a multiple of the max stride {self.max_stride} (utils/checks.py:120-172)")
+        outs = self._forward_outs(im, want_raw)
+        if "topk_idx" in outs:  # a classify plan's rows (of the whole batch where it was split)
+            self.last_topk = (outs["topk_idx"], outs["topk_val"])
+        return pack_outputs(self.meta, outs)
+
+    def _forward_outs(self, im, want_raw):
+        """The outputs of one forward by name (Plan.outputs)."""
+        B, _, H, W = im.shape
         # the kernels keep element offsets in 32 bits: split batches whose largest activation would exceed 2^31
         # elements (e.g. 256 x 1280x1280) into equal chunks -- images are independent
         big = self._max_view_elems(H, W)
         if B > 1 and B * big >= (1 << 31) - (1 << 24):
             n_chunks = -(-B * big // ((1 << 31) - (1 << 24)))
             step = -(-B // n_chunks)
-            if self.task == "classify":
-                outs, tops = [], []
-                for i in range(0, B, step):
-                    outs.append(self.forward(im[i:i + step], want_raw))
-                    tops.append(self.last_topk)
-                self.last_topk = (torch.cat([t[0] for t in tops]), torch.cat([t[1] for t in tops]))
-                return torch.cat([o[0] for o in outs]), (torch.cat([o[1] for o in outs]) if want_raw else None)
-            outs = [self.forward(im[i:i + step], want_raw) for i in range(0, B, step)]
-            y = torch.cat([o[0] for o in outs])
-            nl = self.nl
-            if self.meta["nm"]:
-                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
-                return y, (raws, y[:, 4 + self.meta["nc"]:], torch.cat([o[1][2] for o in outs]))
-            if self.meta["ne"]:
-                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
-                return y, (raws, y[:, 4 + self.meta["nc"]:])
-            if self.meta.get("nk", 0):
-                raws = [torch.cat([o[1][0][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl
-                return y, (raws, torch.cat([o[1][1] for o in outs]) if want_raw else None)
-            return y, ([torch.cat([o[1][l] for o in outs]) for l in range(nl)] if want_raw else [None] * nl)
+            return cat_outputs([self._forward_outs(self._dense(im[i:i + step]), want_raw) for i in range(0, B, step)])
         with self._lock:  # plan table, arena and launch order are shared state
-            return self._forward_one(im, want_raw, B, H, W)
+            plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
+            outs = self._output_set(plan, im, want_raw)
+            self._run(plan, h, *_bind(plan, im, outs), im, B, H, W)
+            return outs
 
-    def _forward_one(self, im, want_raw, B, H, W):
-        plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
-        m = plan.meta
-        if self.task == "classify":
-            return self._forward_classify(plan, h, im, want_raw, B, H, W)
-
-        def outputs():
-            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"] + m.get("nk", 0), m["A"]), dtype=im.dtype, device=self.device)
-            raws: List[Optional[torch.Tensor]] = [None] * len(m["levels"])
-            if want_raw:
-                raws = [torch.empty((B, m["no"], lh, lw), dtype=im.dtype, device=self.device) for lh, lw in m["levels"]]
-            proto = None
-            if m["nm"]:
-                ph, pw = m["proto_hw"]
-                proto = torch.empty((B, m["nm"], ph, pw), dtype=im.dtype, device=self.device)
-            elif m.get("nk", 0) and want_raw:  # the raw keypoint logits travel in the proto slot (Plan.EXT_KPT)
-                proto = torch.empty((B, m.get("nk", 0), m["A"]), dtype=im.dtype, device=self.device)
-            return y, raws, proto
-
-        y, raws, proto = self._output_set(outputs, im, want_raw)
-        ext, n = self._ext(im, y, raws, proto)
-        self._run(plan, h, ext, n, im, B, H, W)
-        if m["nm"]:  # Segment.forward (head.py:197): (cat(y, mc), (raw, mc, proto)); y already carries the mc rows
-            return y, (raws, y[:, 4 + m["nc"]:], proto)
-        if m["ne"]:  # OBB.forward (head.py:223): (cat(y, angle), (raw, angle)); y already carries the angle row
-            return y, (raws, y[:, 4 + m["nc"]:])
-        if m.get("nk", 0):  # Pose.forward (head.py:250): (cat(y, pred_kpt), (raw, kpt)); y already carries the decoded keypoint rows
-            return y, (raws, proto)
-        return y, raws
-
-    def _output_set(self, make, im, want_raw):
-        """The output tensors of one forward: fresh ones (make()), or in graph mode the next set of this shape's ring -- the captured
+    def _output_set(self, plan, im, want_raw):
+        """The output tensors of one forward: fresh ones (_outputs), or in graph mode the next set of this shape's ring -- the captured
         graphs hold their addresses."""
         if not self.graph:
-            return make()
+            return _outputs(plan, want_raw, self.device, im.dtype)
         B, _, H, W = im.shape
         ring = self._rings.setdefault(((B, H, W, im.dtype, im.dtype), bool(want_raw)), {"i": 0, "slots": []})
         if len(ring["slots"]) < self.graph_ring:
-            ring["slots"].append(make())
+            ring["slots"].append(_outputs(plan, want_raw, self.device, im.dtype))
         ring["i"] += 1
         return ring["slots"][(ring["i"] - 1) % len(ring["slots"])]
-
-    def _forward_classify(self, plan, h, im, want_raw, B, H, W):
-        """Slots (Plan.EXT_*): 0 image, 1 y, 2 x, 3 / 4 the top-k index / value rows.  want_raw=False leaves x unbound (None returned)."""
-        nc, k = plan.meta["nc"], plan.meta["topk"]
-
-        def outputs():
-            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
-            return (new((B, nc), im.dtype), new((B, nc), im.dtype) if want_raw else None, new((B, k), torch.int32), new((B, k), torch.float32))
-
-        y, x, idx, val = self._output_set(outputs, im, want_raw)
-        ptrs = [im.data_ptr(), y.data_ptr(), x.data_ptr() if x is not None else None, idx.data_ptr(), val.data_ptr()]
-        self._run(plan, h, (C.c_void_p * len(ptrs))(*ptrs), len(ptrs), im, B, H, W)
-        self.last_topk = (idx, val)
-        return y, x
 
     def _run(self, plan, h, ext, n, im, B, H, W):
         """One forward of `plan` on the current stream with the external slots `ext`: ordered behind the previous forward, autotuned
@@ -466,14 +446,9 @@ class YoloEngine:
         im = self._dense(im)
         B, _, H, W = im.shape
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
-        m = plan.meta
-        if self.task == "classify":
-            y, x = (torch.empty((B, m["nc"]), dtype=im.dtype, device=self.device) for _ in range(2))
-            idx, val = (torch.empty((B, m["topk"]), dtype=dt, device=self.device) for dt in (torch.int32, torch.float32))
-            ext, n = (C.c_void_p * 5)(im.data_ptr(), y.data_ptr(), x.data_ptr(), idx.data_ptr(), val.data_ptr()), 5
-        else:
-            y = torch.empty((B, 4 + m["nc"] + m["nm"] + m["ne"] + m.get("nk", 0), m["A"]), dtype=im.dtype, device=self.device)
-            ext, n = self._ext(im, y, [None] * len(m["levels"]))
+        # bound: every output of a classify plan; of the others the image and y alone (no raw map, proto or keypoint store is timed)
+        outs = _outputs(plan, self.task == "classify", self.device, im.dtype)
+        ext, n = _bind(plan, im, outs if self.task == "classify" else {"y": outs["y"]})
         ms = (C.c_float * len(plan.ops))()
         L.check(L.lib.bsy_plan_profile(h, ext, n, L.stream_ptr(self.device), ms))
         return [(o["name"], o["kind"], float(t)) for o, t in zip(plan.ops, ms)], plan

@@ -19,7 +19,7 @@ from __future__ import annotations
 import functools
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -127,14 +127,14 @@ OP_FIELDS = frozenset((
     "wkey", "wkey2", "wkeys", "cout", "mfma_flops"))
 # kinds that may run on a side lane (csrc/engine.hip bsy_plan_run forks and joins around them)
 LANE_KINDS = (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP_C3K2)
+Output = namedtuple("Output", "name slot shape dtype raw_only")  # one external output of a plan (Plan._ext, Plan.outputs)
 
 
 class Plan:
     """Flat op list + workspace buffer table for one (B, H, W)."""
 
-    EXT_IMG, EXT_Y, EXT_RAW0 = 0, 1, 2  # external slots: image, prediction, raw level maps (2,3,4), proto / raw keypoints (5)
-    EXT_PROTO = 5
-    EXT_KPT = 5  # a pose plan's raw keypoint logits (B, nk, A): the proto slot under another name (a pose plan has no proto)
+    EXT_IMG, EXT_Y, EXT_RAW0 = 0, 1, 2  # external slots (the one numbering; a plan's own are in `outputs`): image, prediction, raw level maps (2, 3, 4)
+    EXT_PROTO = EXT_KPT = 5  # a segment plan's proto, or a pose plan's raw keypoint logits (B, nk, A): a plan has one or the other
     EXT_RAW3 = 6  # the fourth level's raw map (P2 / P6 heads): behind the proto slot, so that slots 0-5 stay what they were
     EXT_LOGITS, EXT_TOPK_IDX, EXT_TOPK_VAL = 2, 3, 4  # a classify plan's slots behind image and y: x (the logits), the top-k rows
 
@@ -143,6 +143,18 @@ class Plan:
         """External slot of level `level`'s raw map."""
         assert 0 <= level < L.BSY_MAX_LEVELS
         return cls.EXT_RAW0 + level if level < 3 else cls.EXT_RAW3 + level - 3
+
+    def _ext(self, name: str, slot: int, C: int, tail: Tuple[int, ...] = (), dtype: str = "io", raw_only: bool = False) -> T:
+        """The view of external slot `slot`, C channels wide.  Every slot but the image is an output and enters `outputs` by name: shape (B, C) + tail,
+        dtype ("io": the plan's out_dtype), raw_only (only a caller that wants the raw outputs has it); a name met again (y, at every fused level) says the same."""
+        if slot != self.EXT_IMG:
+            out = Output(name, slot, (self.B, C) + tuple(tail), dtype, raw_only)
+            assert self.outputs.get(name, out) == out, f"external output {out} after {self.outputs[name]}"
+            self.outputs[name] = out
+        return T(L.BSY_EXT_BASE + slot, 0, 0, C, *(tail if slot == self.EXT_IMG else (0, 0)))  # (the image's view alone carries its size)
+
+    def _raw(self, level: int, nc: int, x: T) -> T:  # the view of level `level`'s raw map (B, no, h, w), `x` being any map of that level
+        return self._ext(f"raw{level}", self.ext_raw(level), 64 + nc, (x.H, x.W), raw_only=True)
 
     def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16, precision: str = "fp16",
                  lanes: Optional[bool] = None, latency: bool = False, repconv: str = "refconv", **switches: Optional[bool]):
@@ -176,6 +188,7 @@ class Plan:
         self.wrecs: "OrderedDict[str, WRec]" = OrderedDict()
         self.flops = 0  # 2*MAC of every dense/depthwise conv + attention matmuls, whole batch
         self.meta: Dict = {}
+        self.outputs: Dict[str, Output] = {}
         self._lane = 0
         self._build()
         if self.latency:
@@ -317,7 +330,7 @@ class Plan:
 
     def conv_first(self, name: str, cout: int, k: int, s: int, p: Optional[int] = None) -> T:
         p = k // 2 if p is None else p
-        img = T(L.BSY_EXT_BASE + self.EXT_IMG, 0, 0, 3, self.H, self.W)
+        img = self._ext("im", self.EXT_IMG, 3, (self.H, self.W))
         if (k, s, p) == (6, 2, 2) and not self.f32_mode:
             # YOLOv5u's stem (cfg/models/v5/yolov5.yaml:16): space-to-depth of the image (one elementwise launch) + an ordinary
             # 3x3 stride-1 conv over its 12 (+4 zero) channels with the weights re-laid-out to match (weights.py "first_s2d")
@@ -727,8 +740,7 @@ class Plan:
                            stride=1, pad=0, act=0, out_f32=0, wkey=key, dst_scale=2, dst_dy=dy, dst_dx=dx, mfma_flops=fl)
         t = self.conv(name + ".cv2", up, c_, 3, 1)
         p = self.conv(name + ".cv3", t, nm, 1, 1)
-        self._emit(L.OP_NHWC2NCHW, name + ".nchw", src0=p, dst=T(L.BSY_EXT_BASE + self.EXT_PROTO, 0, 0, nm, 0, 0), OH=0, OW=0,
-                   out_dtype=self.out_dtype)
+        self._emit(L.OP_NHWC2NCHW, name + ".nchw", src0=p, dst=self._ext("proto", self.EXT_PROTO, nm, (p.H, p.W)), OH=0, OW=0, out_dtype=self.out_dtype)
         self.meta.update(proto_hw=(p.H, p.W))
         return p
 
@@ -736,10 +748,8 @@ class Plan:
                        flops: int, **fields):
         """A conv op with the Detect decoder in its epilogue (out_f32 = mode 2: class branch / 3: box branch): it writes level `level`'s
         rows of the prediction tensor (first anchor a0 of A, stride `stride`) and that level's raw map."""
-        y = T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc, 0, 0)
-        raw = T(L.BSY_EXT_BASE + self.ext_raw(level), 0, 0, 64 + nc, 0, 0)
-        self._emit(L.OP_CONV, name, flops, src0=src, src1=None, dst=y, res=None, OH=src.H, OW=src.W, ksize=k, stride=1, pad=k // 2,
-                   out_f32=mode, dst_scale=1, cout=cout, nl=cout, nc=nc, nm=0, A=A, box=[raw], cls=[], msk=[], level=level,
+        self._emit(L.OP_CONV, name, flops, src0=src, src1=None, dst=self._ext("y", self.EXT_Y, 4 + nc, (A,)), res=None, OH=src.H, OW=src.W, ksize=k,
+                   stride=1, pad=k // 2, out_f32=mode, dst_scale=1, cout=cout, nl=cout, nc=nc, nm=0, A=A, box=[self._raw(level, nc, src)], cls=[], msk=[], level=level,
                    lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype, mfma_flops=flops, **fields)
 
     def _head_conv(self, name: str, src: T, cout: int, mode: int, level: int, a0: int, A: int, nc: int, stride: float, real_cin: int = 0):
@@ -837,13 +847,11 @@ class Plan:
         # OBB and the fp32-storage modes have no fused form and keep the order their outputs have always had
         lvl = dict(H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, A=A, box=boxes, cls=clss, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs],
                    lvl_stride=strides, out_dtype=self.out_dtype)
-        # Pose: res = the raw keypoint logits' slot (optional output), written by the same launch
-        kraw = T(L.BSY_EXT_BASE + self.EXT_KPT, 0, 0, nk, 0, 0) if nk else None
+        kraw = self._ext("kpt", self.EXT_KPT, nk, (A,), raw_only=True) if nk else None
         self._emit(L.OP_DECODE, name + ".decode", join=1, nm=nm, ne=ne, nk=nk, kdim=kdim, msk=msks, res=kraw,
-                   act=int(not self.f32_mode and nm == 0 and ne == 0 and nk == 0),
-                   dst=T(L.BSY_EXT_BASE + self.EXT_Y, 0, 0, 4 + nc + nm + ne + nk, 0, 0), **lvl)
-        for i in range(len(xs)):
-            self._emit(L.OP_RAW_NCHW, f"{name}.raw{i}", nm=0, msk=[], level=i, dst=T(L.BSY_EXT_BASE + self.ext_raw(i), 0, 0, 64 + nc, 0, 0), **lvl)
+                   act=int(not self.f32_mode and nm == 0 and ne == 0 and nk == 0), dst=self._ext("y", self.EXT_Y, 4 + nc + nm + ne + nk, (A,)), **lvl)
+        for i, x in enumerate(xs):
+            self._emit(L.OP_RAW_NCHW, f"{name}.raw{i}", nm=0, msk=[], level=i, dst=self._raw(i, nc, x), **lvl)
 
     def classify(self, name: str, x: T, nc: int):
         """head.py:282-304 Classify in eval: (y, x) = (softmax(x), x), x = linear(pool(conv(x)).flatten(1)); Dropout(p = 0) is the
@@ -857,9 +865,9 @@ class Plan:
         ncp = make_divisible(nc, 8)
         lg = self.conv(name + ".linear", g, ncp, 1, 1, act=False, plain=True, out_f32=True, real=(nc if ncp != nc else 0, 0))
         k = min(nc, 5)  # what the predictor and the validator rank (classify/predict.py:51-60, val.py:56-60)
-        ext = lambda slot, c: T(L.BSY_EXT_BASE + slot, 0, 0, c, 0, 0)  # noqa: E731
-        self._emit(L.OP_CLASSIFY_TAIL, name + ".tail", src0=lg, dst=ext(self.EXT_Y, nc), res=ext(self.EXT_LOGITS, nc), nc=nc, ksize=k,
-                   box=[ext(self.EXT_TOPK_IDX, k)], cls=[ext(self.EXT_TOPK_VAL, k)], out_dtype=self.out_dtype, OH=0, OW=0)
+        idx, val = self._ext("topk_idx", self.EXT_TOPK_IDX, k, dtype="int32"), self._ext("topk_val", self.EXT_TOPK_VAL, k, dtype="float32")
+        self._emit(L.OP_CLASSIFY_TAIL, name + ".tail", src0=lg, dst=self._ext("y", self.EXT_Y, nc), res=self._ext("x", self.EXT_LOGITS, nc, raw_only=True),
+                   nc=nc, ksize=k, box=[idx], cls=[val], out_dtype=self.out_dtype, OH=0, OW=0)
         # strides: the engine's size multiple (the backbone halves the map five times); ClassificationModel.stride itself is 1
         # (tasks.py:457).  No anchors, levels or raw maps: the engine's readers of A / levels / no see an empty head
         self.meta.update(task="classify", nc=nc, nm=0, ne=0, A=0, no=0, strides=[32.0], levels=[], topk=k)
@@ -1063,16 +1071,8 @@ class Plan:
 
     def op_buffers(self, o: dict) -> List[int]:
         """Indices of the workspace buffers an op reads or writes (external slots excluded)."""
-        out = []
-        for k in self._VIEW_KEYS:
-            t = o.get(k)
-            if t is not None and t.buf < L.BSY_EXT_BASE:
-                out.append(t.buf)
-        for k in self._LIST_KEYS:
-            for t in o.get(k, []) or []:
-                if t is not None and t.buf < L.BSY_EXT_BASE:
-                    out.append(t.buf)
-        return out
+        views = [o.get(k) for k in self._VIEW_KEYS] + [t for k in self._LIST_KEYS for t in o.get(k) or []]
+        return [t.buf for t in views if t is not None and t.buf < L.BSY_EXT_BASE]
 
     def max_view_elems(self) -> int:
         """Largest (pixels x row stride) of ONE image over the workspace views the ops name as source, destination or residual: the

@@ -1015,6 +1015,54 @@ def test_engine_graph_mode_equals_eager(fam, scale, nc, task, shape, own_stream)
     graph.close()
 
 
+@pytest.mark.parametrize("task", ["detect", "segment", "obb", "pose", "classify"])
+def test_every_way_to_a_forward_returns_the_plain_bits(task, monkeypatch):
+    """One table of outputs behind every path (Plan.outputs; engine._outputs / _bind / cat_outputs / pack_outputs): for each task's
+    head, the chunked large-batch forward, graph mode over its ring of output sets and want_raw=False return the plain forward's
+    value -- the same nesting, None where there is no tensor, and the same bits in every tensor and in last_topk."""
+    from bs_yolo_amd.plan import Plan
+    from bs_yolo_amd.weights import synth_state_dict
+    cfg = stock_cfg("yolo11", "n", 3, task, **({"kpt_shape": (17, 3)} if task == "pose" else {}))
+    P = synth_state_dict(Plan(cfg, 1, 64, 64), 4)
+    x = torch.rand(3, 3, 64, 64, generator=torch.Generator().manual_seed(64)).half().to(DEV)
+
+    def same(a, b):
+        if isinstance(a, (list, tuple)):
+            return type(a) is type(b) and len(a) == len(b) and all(same(p, q) for p, q in zip(a, b))
+        return (a is None and b is None) if a is None or b is None else torch.equal(a, b)
+
+    keep = lambda v: type(v)(keep(t) for t in v) if isinstance(v, (list, tuple)) else None if v is None else v.clone()  # noqa: E731
+    eng = YoloEngine(cfg, P, autotune=False)
+    ref, top = keep(eng(x)), keep(eng.last_topk)
+    assert (top is None) == (task != "classify") and ref[0].shape[0] == 3
+    y, extra = eng(x, want_raw=False)
+    assert torch.equal(y, ref[0]) and same(eng.last_topk, top)
+    if task == "classify":
+        assert extra is None
+    else:
+        raws = extra if task == "detect" else extra[0]
+        assert raws == [None] * 3 and (task != "pose" or extra[1] is None)
+        assert task not in ("segment", "obb") or torch.equal(extra[1], ref[1][1])
+        assert task != "segment" or torch.equal(extra[2], ref[1][2])
+    monkeypatch.setattr(eng, "_max_view_elems", lambda H, W: (1 << 31) // 2)  # forces the chunked large-batch path
+    n_plans = len(eng._plans)
+    assert same(eng(x), ref) and same(eng.last_topk, top)
+    assert len(eng._plans) > n_plans  # (it ran as smaller batches)
+    eng.close()
+    graph = YoloEngine(cfg, P, autotune=False, graph=True, graph_ring=2)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(torch.cuda.Stream(device=DEV)):
+        outs = []
+        for _ in range(3):
+            out = graph(x)
+            outs.append((out, keep(out), keep(graph.last_topk)))
+    torch.cuda.synchronize()
+    assert graph.graph_stats == {"captures": 2, "replays": 1, "eager": 0}, graph.graph_stats
+    assert all(same(snap, ref) and same(t, top) for _, snap, t in outs)
+    assert outs[2][0][0].data_ptr() == outs[0][0][0].data_ptr() != outs[1][0][0].data_ptr()  # a ring of two output sets
+    graph.close()
+
+
 @pytest.mark.parametrize("scale,shape", [("s", (8, 640, 640)), ("n", (6, 320, 224))])
 def test_engine_latency_mode_split_k(scale, shape):
     """Latency mode (round 4): long-K conv layers with few tiles per image run split-K -- the slices of a layer's K
@@ -1852,7 +1900,8 @@ def test_engine_drops_presets_that_do_not_fit_the_shape(tmp_path, monkeypatch):
     plan, h = eng.plan_for(2, 96, 128, torch.float16, torch.float16)
     import ctypes as C
     from bs_yolo_amd import lib as L
-    ext, n = eng._ext(x, y, [None, None, None], None)
+    from bs_yolo_amd.engine import _bind
+    ext, n = _bind(plan, x, {"y": y})
     valid = (C.c_int32 * len(plan.ops))()
     L.check(L.lib.bsy_plan_check_tuning(h, ext, n, valid, len(plan.ops)))
     assert 0 not in list(valid) and 1 in list(valid)

@@ -684,6 +684,103 @@ def test_max_view_elems_counts_source_destination_and_residual_views():
         assert p.max_view_elems() == want > 1
 
 
+# ---- a plan's external outputs: Plan.outputs, and the engine's pure functions over it -------------------------------------------
+def _task_cfg(family, scale, task, nc=3):
+    return stock_cfg(family, scale, nc, task, **({"kpt_shape": (17, 3)} if task == "pose" else {}))
+
+
+OUTPUT_GRAPHS = [("yolo11", "n", t, (64, 64)) for t in ("detect", "segment", "obb", "pose", "classify")] + [
+    ("yolov8-p6", "n", "segment", (128, 192)), ("yolov9", "t", "detect", (64, 64)), ("bsyolo11", "n", "detect", (64, 64))]
+
+
+@pytest.mark.parametrize("family,scale,task,hw", OUTPUT_GRAPHS)
+def test_output_table_says_what_the_ops_write(family, scale, task, hw):
+    """Plan.outputs against the op list, which is what the device sees: the external slots the ops' views name are the image and the
+    table's slots, one name per slot; every view onto a slot is as wide as its entry's shape[1] (the raw maps a fused head conv writes
+    through box[0]: `no`); raw_only marks the raw maps, the raw keypoint logits and the logits, nothing else; and the entries are the
+    ones the engine's return forms are written for (slots pinned as numbers: they are the library's ABI)."""
+    B = 2
+    for kw in ({}, {"fuse_head": False}, {"precision": "fp32"}):
+        plan = Plan(_task_cfg(family, scale, task), B, *hw, **kw)
+        m, table = plan.meta, plan.outputs
+        by_slot = {}
+        for o in table.values():
+            by_slot.setdefault(o.slot, []).append(o)
+        assert all(len(v) == 1 for v in by_slot.values()), table
+        assert [n for n, o in table.items() if n != o.name] == []
+        seen = set()
+        for op in plan.ops:
+            views = [(k, op.get(k)) for k in ("src0", "src1", "dst", "res")] + [(k, t) for k in ("box", "cls", "msk") for t in op.get(k) or []]
+            for k, t in views:
+                if t is None or t.buf < L.BSY_EXT_BASE:
+                    continue
+                slot = t.buf - L.BSY_EXT_BASE
+                seen.add(slot)
+                if slot:
+                    assert t.C == by_slot[slot][0].shape[1], (op["name"], k, slot, t.C)
+                    if op["kind"] == L.OP_CONV and k == "box":
+                        assert op["out_f32"] >= 2 and t.C == m["no"] and by_slot[slot][0].name == f"raw{op['level']}"
+        assert seen == {0} | set(by_slot), (seen, table)
+        assert {o.name for o in table.values() if o.raw_only} == {n for n in table if n.startswith("raw") or n in ("kpt", "x")}
+        if task == "classify":
+            k = min(3, 5)
+            want = {"y": (1, (B, 3), "io"), "x": (2, (B, 3), "io"), "topk_idx": (3, (B, k), "int32"), "topk_val": (4, (B, k), "float32")}
+        else:
+            nl = len(m["levels"])
+            assert nl == (4 if family == "yolov8-p6" else 3) and m["no"] == 64 + 3
+            want = {"y": (1, (B, 4 + 3 + m["nm"] + m["ne"] + m.get("nk", 0), m["A"]), "io")}
+            want.update({f"raw{l}": ([2, 3, 4, 6][l], (B, m["no"]) + tuple(m["levels"][l]), "io") for l in range(nl)})
+            if task == "segment":
+                want["proto"] = (5, (B, 32) + tuple(m["proto_hw"]), "io")
+            if task == "pose":
+                want["kpt"] = (5, (B, 51, m["A"]), "io")
+        assert {n: (o.slot, o.shape, o.dtype) for n, o in table.items()} == want
+
+
+def _tree_equal(a, b):
+    """Same nesting, the same None positions, torch.equal tensors."""
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(_tree_equal(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is None and b is None
+    return a.dtype == b.dtype and torch.equal(a, b)
+
+
+@pytest.mark.parametrize("want_raw", [True, False])
+@pytest.mark.parametrize("task", ["detect", "segment", "obb", "pose", "classify"])
+def test_pack_and_cat_outputs(task, want_raw):
+    """engine.pack_outputs / cat_outputs, on CPU tensors shaped by a real plan's table at B = 5: the return value packed from the
+    concatenated chunks (2, 2, 1 images) is the one packed from the whole batch, in the form of the task's head (head.py:74, :197,
+    :223, :250, :304), and the rows behind the scores that Segment and OBB return are views of the returned y."""
+    from bs_yolo_amd.engine import cat_outputs, pack_outputs
+    plan = Plan(_task_cfg("yolo11", "n", task), 5, 64, 64)
+    g = torch.Generator().manual_seed(5)
+    dtypes = {"io": torch.float16, "int32": torch.int32, "float32": torch.float32}
+    whole = {n: None if o.raw_only and not want_raw else (torch.rand(o.shape, generator=g) * 100).to(dtypes[o.dtype]) for n, o in plan.outputs.items()}
+    chunks = [{n: None if t is None else t[a:b] for n, t in whole.items()} for a, b in ((0, 2), (2, 4), (4, 5))]
+    cat = cat_outputs(chunks)
+    assert list(cat) == list(whole) and all(_tree_equal(cat[n], whole[n]) for n in whole)
+    one, many = pack_outputs(plan.meta, whole), pack_outputs(plan.meta, cat)
+    assert _tree_equal(one, many)
+    nl, raws = 3, [whole.get(f"raw{l}") for l in range(3)]
+    assert raws == [None] * nl if not want_raw or task == "classify" else all(r is not None for r in raws)
+    for y, extra in (one, many):
+        assert y.shape[0] == 5
+        rows = y[:, 4 + 3:]
+        if task == "detect":
+            assert isinstance(extra, list) and len(extra) == nl
+        elif task == "segment":
+            assert len(extra) == 3 and len(extra[0]) == nl and extra[2].shape == (5, 32, 16, 16)
+        elif task == "obb":
+            assert len(extra) == 2 and len(extra[0]) == nl and extra[1].shape == (5, 1, y.shape[2])
+        elif task == "pose":
+            assert len(extra) == 2 and len(extra[0]) == nl and (extra[1].shape == (5, 51, y.shape[2]) if want_raw else extra[1] is None)
+        else:
+            assert y.shape == (5, 3) and (extra.shape == (5, 3) if want_raw else extra is None)
+        if task in ("segment", "obb"):
+            assert extra[1]._base is y and extra[1].data_ptr() == rows.data_ptr() and extra[1].shape == rows.shape and extra[1].stride() == rows.stride()
+
+
 def test_library_says_which_shapes_the_fused_kernels_take():
     """The planner asks the library (bsy_*_supported), it keeps no list of its own: the three predicates it asks besides the *_fused ones,
     at the edges the kernels define."""
