@@ -1,16 +1,19 @@
 """Tensor-level wrappers over the stand-alone C entry points (same kernels the engine launches).
 
 Used by the per-module hooks (plugin.py) and by the parity tests.  Activations are NHWC fp16 torch tensors
-(``x.permute(0, 2, 3, 1).contiguous()`` of the reference's BCHW tensors); every call runs on the current stream.
+(``x.permute(0, 2, 3, 1).contiguous()`` of the reference's BCHW tensors) or channel slices of wider ones (`_nhwc`); every call runs
+on the current stream.  Weights are given raw -- the module's fp32 (w, b), packed on every call -- or as the `Packed` pair a
+``pack_*`` function returned, so that a caller packs once and calls many times.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
 from . import lib as L
+from .weights import dense_f16, dense_f32, depthwise
 
 
 def _stream(t: torch.Tensor):
@@ -21,94 +24,114 @@ def _p(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def pack_conv_weight(w: torch.Tensor, b: Optional[torch.Tensor], device) -> tuple:
-    """(Cout, Cin, k, k) fp32 [+ bias] -> packed fp16 [CoutPad][Kpad] + fp32 [CoutPad] on `device`."""
-    cout, cin, k, _ = w.shape
-    cp, kp = C.c_int(), C.c_int()
-    L.check(L.lib.bsy_conv_packed_dims(cout, cin, k, C.byref(cp), C.byref(kp)))
-    w = w.detach().float().cpu()
-    if cin == 3:  # image conv: zero 4th input channel (csrc/image_conv.h)
-        w = torch.cat([w, torch.zeros(cout, 1, k, k)], 1)
-        cin = 4
-    K = k * k * cin
-    wp = torch.zeros(cp.value, kp.value, dtype=torch.float16)
-    wp[:cout, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).half()
-    bp = torch.zeros(cp.value, dtype=torch.float32)
-    if b is not None:
-        bp[:cout] = b.detach().float().cpu()
-    return wp.to(device), bp.to(device)
+def _nhwc(t: Optional[torch.Tensor]):
+    """(pointer, ld, B, H, W, C) of an NHWC tensor, or of a channel slice of a wider one: channels adjacent, pixels `ld` elements apart
+    in (b, h, w) order (stride(3) == 1, stride(2) == ld, stride(1) == W * ld, stride(0) == H * W * ld; a dimension of size 1 has no
+    stride to speak of).  None -> a null pointer with ld 0."""
+    if t is None:
+        return None, 0, 0, 0, 0, 0
+    B, H, W, c = t.shape
+    ld = t.stride(2) if W > 1 else t.stride(1) if H > 1 else t.stride(0) if B > 1 else c
+    assert all(n == 1 or s == e for n, s, e in zip(t.shape, t.stride(), (H * W * ld, W * ld, ld, 1))), (tuple(t.shape), t.stride())
+    return _p(t), ld, B, H, W, c
+
+
+class Packed(tuple):
+    """(w, b): a conv's weights in a device layout of weights.py, on the device.  `shape` is the raw weight's (Cout, Cin, kh, kw), so a
+    wrapper reads its widths off raw and packed weights alike."""
+    def __new__(cls, w, b, shape):
+        self = super().__new__(cls, (w, b))
+        self.shape = tuple(shape)
+        return self
+
+
+def pack_conv_weight(w: torch.Tensor, b: Optional[torch.Tensor], device) -> Packed:
+    """(Cout, Cin, k, k) fp32 [+ bias] -> packed fp16 [CoutPad][Kpad] + fp32 [CoutPad] on `device` (weights.dense_f16)."""
+    wp, bp = dense_f16(w, b)
+    return Packed(wp.to(device), bp.to(device), w.shape)
+
+
+def pack_conv_weight_f32(w: torch.Tensor, b: torch.Tensor, device, split: bool = False) -> Packed:
+    """(Cout, Cin, k, k) + bias -> ((f32 [K][Cout] matrix,) or, split, (matrix, hi, lo)) + f32 [Cout] on `device` (weights.dense_f32)."""
+    mats, bp = dense_f32(w, b, split)
+    return Packed(tuple(t.to(device) for t in mats), bp.to(device), w.shape)
+
+
+def pack_dw_weight(w: torch.Tensor, b: torch.Tensor, device) -> Packed:
+    """(C, 1, kh, kw) + bias -> f32 [kh*kw][C] + f32 [C] on `device` (weights.depthwise)."""
+    wp, bp = depthwise(w, b)
+    return Packed(wp.to(device), bp.to(device), w.shape)
+
+
+def _packed(pack, w, b, device, **kw) -> Packed:
+    return w if isinstance(w, Packed) else pack(w, b, device, **kw)
+
+
+def _out_hw(H: int, W: int, kh: int, kw: int, s: int):
+    return (H + 2 * (kh // 2) - kh) // s + 1, (W + 2 * (kw // 2) - kw) // s + 1
 
 
 def conv2d_nhwc(x: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor, cout: int, k: int, s: int = 1, act: bool = True,
                 res: Optional[torch.Tensor] = None, out_f32: bool = False, cin: Optional[int] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x (B,H,W,ld) fp16 (uses the first `cin` channels) -> (B,OH,OW,cout).  Conv.forward_fuse (conv.py:149-151)."""
-    assert x.dtype == torch.float16 and x.is_contiguous() and x.dim() == 4
-    B, H, W, ld = x.shape
-    cin = ld if cin is None else cin
-    p = k // 2
-    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    """x (B,H,W,C) fp16 view (uses the first `cin` channels), (wp, bp) = pack_conv_weight(...) -> (B,OH,OW,cout), into the view `out`
+    where one is given.  Conv.forward_fuse (conv.py:149-151)."""
+    assert x.dtype == torch.float16
+    px, ld, B, H, W, c = _nhwc(x)
+    cin = c if cin is None else cin
     if out is None:
         ldy = (cout + 3) // 4 * 4 if out_f32 else (cout + 7) // 8 * 8
-        out = torch.zeros((B, OH, OW, ldy), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
-    L.check(L.lib.bsy_conv2d(_p(x), ld, B, H, W, cin, _p(wp), _p(bp), _p(out), out.shape[-1], cout, k, s, int(act),
-                             _p(res), res.shape[-1] if res is not None else 0, int(out_f32), _stream(x)))
+        out = torch.zeros((B, *_out_hw(H, W, k, k, s), ldy), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
+    L.check(L.lib.bsy_conv2d(px, ld, B, H, W, cin, _p(wp), _p(bp), *_nhwc(out)[:2], cout, k, s, int(act), *_nhwc(res)[:2], int(out_f32),
+                             _stream(x)))
     return out
+
+
+def _conv2d_f32(x, w, b, k, s, cin, split):
+    """What both fp32-storage convs do before their call: the packed weights, the input view and a new zeroed output."""
+    assert x.dtype == torch.float32
+    px, ld, B, H, W, c = _nhwc(x)
+    cin = c if cin is None else cin
+    cout = w.shape[0]
+    assert tuple(w.shape) == (cout, cin, k, k)
+    mats, bk = _packed(pack_conv_weight_f32, w, b, x.device, split=split)
+    ldy = (cout + 3) // 4 * 4
+    out = torch.zeros((B, *_out_hw(H, W, k, k, s), ldy), dtype=torch.float32, device=x.device)
+    return mats, bk, (px, ld, B, H, W, cin), out, ldy, cout
 
 
 def conv2d_nhwc_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, k: int, s: int = 1, act: bool = True,
                     res: Optional[torch.Tensor] = None, cin: Optional[int] = None, impl: int = 0) -> torch.Tensor:
-    """fp32 engine mode's conv: x (B,H,W,ld) f32 (first `cin` channels), w (Cout,Cin,k,k) f32, b (Cout) -> (B,OH,OW,Cout) f32.
+    """fp32 engine mode's conv: x (B,H,W,C) f32 view (first `cin` channels), w (Cout,Cin,k,k) f32, b (Cout) -- or w =
+    pack_conv_weight_f32(w, b, device) -- -> (B,OH,OW,Cout) f32.
     impl 0 = the engine's routing, 1 = scalar kernel, 2 = fp32 MFMA kernel (bsy_conv2d_f32)."""
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
-    B, H, W, ld = x.shape
-    cin = ld if cin is None else cin
-    cout = w.shape[0]
-    assert tuple(w.shape) == (cout, cin, k, k)
-    wk = w.detach().float().permute(2, 3, 1, 0).reshape(k * k * cin, cout).contiguous().to(x.device)
-    bk = b.detach().float().contiguous().to(x.device)
-    p = k // 2
-    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    ldy = (cout + 3) // 4 * 4
-    out = torch.zeros((B, OH, OW, ldy), dtype=torch.float32, device=x.device)
-    L.check(L.lib.bsy_conv2d_f32(_p(x), ld, B, H, W, cin, _p(wk), _p(bk), _p(out), ldy, cout, k, s, int(act), _p(res),
-                                 res.shape[-1] if res is not None else 0, impl, _stream(x)))
+    mats, bk, xa, out, ldy, cout = _conv2d_f32(x, w, b, k, s, cin, False)
+    L.check(L.lib.bsy_conv2d_f32(*xa, _p(mats[0]), _p(bk), _p(out), ldy, cout, k, s, int(act), *_nhwc(res)[:2], impl, _stream(x)))
     return out
 
 
 def conv2d_nhwc_f32x(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, k: int, s: int = 1, act: bool = True,
                      res: Optional[torch.Tensor] = None, cin: Optional[int] = None) -> torch.Tensor:
     """fp32x engine mode's conv (bsy_conv2d_f32x): fp32 NHWC in / out, operands split into f16 pairs, three f16 MFMAs per product.
-    x (B,H,W,ld) f32 (first `cin` channels), w (Cout,Cin,k,k) f32, b (Cout) -> (B,OH,OW,Cout up 4) f32."""
-    from .weights import split_f16_planes
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
-    B, H, W, ld = x.shape
-    cin = ld if cin is None else cin
-    cout = w.shape[0]
-    assert tuple(w.shape) == (cout, cin, k, k)
-    hi, lo = split_f16_planes(w.detach().float().cpu().permute(0, 2, 3, 1).reshape(cout, k * k * cin))
-    hi, lo = hi.contiguous().to(x.device), lo.contiguous().to(x.device)
-    bk = b.detach().float().contiguous().to(x.device)
-    p = k // 2
-    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    ldy = (cout + 3) // 4 * 4
-    out = torch.zeros((B, OH, OW, ldy), dtype=torch.float32, device=x.device)
-    L.check(L.lib.bsy_conv2d_f32x(_p(x), ld, B, H, W, cin, _p(hi), _p(lo), hi.shape[1], _p(bk), _p(out), ldy, cout, k, s, int(act),
-                                  _p(res), res.shape[-1] if res is not None else 0, _stream(x)))
+    x (B,H,W,C) f32 view (first `cin` channels), w (Cout,Cin,k,k) f32, b (Cout) -- or w = pack_conv_weight_f32(w, b, device,
+    split=True) -- -> (B,OH,OW,Cout up 4) f32."""
+    (_, hi, lo), bk, xa, out, ldy, cout = _conv2d_f32(x, w, b, k, s, cin, True)
+    L.check(L.lib.bsy_conv2d_f32x(*xa, _p(hi), _p(lo), hi.shape[1], _p(bk), _p(out), ldy, cout, k, s, int(act), *_nhwc(res)[:2],
+                                  _stream(x)))
     return out
 
 
-def conv_first(img: torch.Tensor, w: torch.Tensor, b: torch.Tensor, k: int = 3, s: int = 2, act: bool = True):
-    """img BCHW fp16/fp32; w (Cout,3,3,3) fp32; -> NHWC fp16."""
+def conv_first(img: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, k: int = 3, s: int = 2, act: bool = True,
+               out: Optional[torch.Tensor] = None):
+    """img BCHW fp16/fp32; w (Cout,3,3,3) fp32, b (Cout) -- or w = pack_conv_weight(w, b, device); -> NHWC fp16."""
     assert img.is_contiguous() and img.shape[1] == 3
     B, _, H, W = img.shape
     cout = w.shape[0]
-    wp, bp = pack_conv_weight(w, b, img.device)
-    p = k // 2
-    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    out = torch.empty((B, OH, OW, cout), dtype=torch.float16, device=img.device)
-    L.check(L.lib.bsy_conv_first(_p(img), L.dtype_code(img.dtype), B, H, W, _p(wp), _p(bp), _p(out), cout, cout, k, s,
-                                 int(act), _stream(img)))
+    wp, bp = _packed(pack_conv_weight, w, b, img.device)
+    if out is None:
+        out = torch.empty((B, *_out_hw(H, W, k, k, s), cout), dtype=torch.float16, device=img.device)
+    L.check(L.lib.bsy_conv_first(_p(img), L.dtype_code(img.dtype), B, H, W, _p(wp), _p(bp), *_nhwc(out)[:2], cout, k, s, int(act),
+                                 _stream(img)))
     return out
 
 
@@ -118,8 +141,8 @@ def stem_fused(img: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w1: torch.
     assert img.is_contiguous() and img.shape[1] == 3
     B, _, H, W = img.shape
     c0, c1 = w0.shape[0], w1.shape[0]
-    w0p, b0p = pack_conv_weight(w0, b0, img.device)
-    w1p, b1p = pack_conv_weight(w1, b1, img.device)
+    w0p, b0p = _packed(pack_conv_weight, w0, b0, img.device)
+    w1p, b1p = _packed(pack_conv_weight, w1, b1, img.device)
     oh0, ow0 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((B, (oh0 - 1) // 2 + 1, (ow0 - 1) // 2 + 1, c1), dtype=torch.float16, device=img.device)
     L.check(L.lib.bsy_stem_fused(_p(img), L.dtype_code(img.dtype), B, H, W, _p(w0p), _p(b0p), c0, _p(w1p), _p(b1p), c1,
@@ -130,57 +153,55 @@ def stem_fused(img: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w1: torch.
 def bottleneck_fused(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x + cv2(cv1(x)) in one launch.  x, out: (B,H,W,C) fp16 NHWC, possibly channel slices of wider buffers
-    (stride(2) = leading dimension); w1 (CH,C,3,3), w2 (C,CH,3,3) fp32 (BN already folded)."""
-    B, H, W, c = x.shape
-    assert x.stride(3) == 1 and x.stride(1) == W * x.stride(2) and x.stride(0) == H * W * x.stride(2)
+    (stride(2) = leading dimension); w1 (CH,C,3,3), w2 (C,CH,3,3) fp32 (BN already folded) with their biases, or pack_conv_weight's
+    pairs in the place of w1 / w2."""
+    px, ld, B, H, W, c = _nhwc(x)
     ch = w1.shape[0]
-    w1p, b1p = pack_conv_weight(w1, b1, x.device)
-    w2p, b2p = pack_conv_weight(w2, b2, x.device)
+    w1p, b1p = _packed(pack_conv_weight, w1, b1, x.device)
+    w2p, b2p = _packed(pack_conv_weight, w2, b2, x.device)
     if out is None:
         out = torch.empty((B, H, W, c), dtype=torch.float16, device=x.device)
-    assert out.shape == x.shape and out.stride(3) == 1 and out.stride(1) == W * out.stride(2)
-    L.check(L.lib.bsy_bottleneck_fused(_p(x), x.stride(2), B, H, W, c, ch, _p(w1p), _p(b1p), _p(w2p), _p(b2p), _p(out),
-                                       out.stride(2), 1, _stream(x)))
+    assert out.shape == x.shape
+    L.check(L.lib.bsy_bottleneck_fused(px, ld, B, H, W, c, ch, _p(w1p), _p(b1p), _p(w2p), _p(b2p), *_nhwc(out)[:2], 1, _stream(x)))
     return out
 
 
 def c3k2_fused(x: torch.Tensor, w1, b1, wa, ba, wb, bb, w4, b4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Whole C3k2 block (c3k = False, one Bottleneck; block.py:3796-3804) in one launch: x (B,H,W,Cin) fp16 NHWC view ->
-    (B,H,W,C2).  w1 (2c,Cin,1,1), wa (c/2,c,3,3), wb (c,c/2,3,3), w4 (C2,3c,1,1) fp32 with BN folded, biases fp32."""
-    B, H, W, cin = x.shape
-    assert x.stride(3) == 1 and x.stride(1) == W * x.stride(2) and x.stride(0) == H * W * x.stride(2)
+    (B,H,W,C2).  w1 (2c,Cin,1,1), wa (c/2,c,3,3), wb (c,c/2,3,3), w4 (C2,3c,1,1) fp32 with BN folded, biases fp32; or
+    pack_conv_weight's pairs in the place of the weights."""
+    px, ld, B, H, W, cin = _nhwc(x)
     c, c2 = wb.shape[0], w4.shape[0]
-    packs = [pack_conv_weight(w, b, x.device) for w, b in ((w1, b1), (wa, ba), (wb, bb), (w4, b4))]
+    packs = [_packed(pack_conv_weight, w, b, x.device) for w, b in ((w1, b1), (wa, ba), (wb, bb), (w4, b4))]  # (alive until the launch)
     if out is None:
         out = torch.empty((B, H, W, c2), dtype=torch.float16, device=x.device)
-    assert out.shape == (B, H, W, c2) and out.stride(3) == 1 and out.stride(1) == W * out.stride(2)
-    L.check(L.lib.bsy_c3k2_fused(_p(x), x.stride(2), B, H, W, cin, c, c2, _p(packs[0][0]), _p(packs[0][1]), _p(packs[1][0]),
-                                 _p(packs[1][1]), _p(packs[2][0]), _p(packs[2][1]), _p(packs[3][0]), _p(packs[3][1]), _p(out),
-                                 out.stride(2), _stream(x)))
+    assert out.shape == (B, H, W, c2)
+    L.check(L.lib.bsy_c3k2_fused(px, ld, B, H, W, cin, c, c2, *[_p(t) for pk in packs for t in pk], *_nhwc(out)[:2], _stream(x)))
     return out
 
 
 def dwpw_fused(x: torch.Tensor, wd: torch.Tensor, bd: torch.Tensor, w: torch.Tensor, b: torch.Tensor, act: bool = True) -> torch.Tensor:
-    """DWConv 3x3 + SiLU -> Conv 1x1 (+act) in one launch.  x (B,H,W,C) fp16; wd (C,1,3,3), bd (C); w (C2,C,1,1), b (C2)."""
-    B, H, W, Cc = x.shape
+    """DWConv 3x3 + SiLU -> Conv 1x1 (+act) in one launch.  x (B,H,W,C) fp16 view; wd (C,1,3,3), bd (C) or pack_dw_weight's pair;
+    w (C2,C,1,1), b (C2) or pack_conv_weight's pair."""
+    px, ld, B, H, W, Cc = _nhwc(x)
     c2 = w.shape[0]
-    wdp = wd.detach().float().cpu().view(Cc, 9).t().contiguous().to(x.device)
-    bdp = bd.detach().float().contiguous().to(x.device)
-    wp, bp = pack_conv_weight(w, b, x.device)
+    wdp, bdp = _packed(pack_dw_weight, wd, bd, x.device)
+    wp, bp = _packed(pack_conv_weight, w, b, x.device)
     out = torch.empty((B, H, W, c2), dtype=torch.float16, device=x.device)
-    L.check(L.lib.bsy_dwpw_fused(_p(x), Cc, B, H, W, Cc, _p(wdp), _p(bdp), _p(wp), _p(bp), _p(out), c2, c2, int(act), _stream(x)))
+    L.check(L.lib.bsy_dwpw_fused(px, ld, B, H, W, Cc, _p(wdp), _p(bdp), _p(wp), _p(bp), _p(out), c2, c2, int(act), _stream(x)))
     return out
 
 
-def dwconv_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, stride: int = 1, act: bool = False) -> torch.Tensor:
-    """Depthwise kh x kw conv, padding k/2 (csrc/bsyolo_ops.hip).  x (B,H,W,C) fp16; w (C,1,kh,kw) fp32; b (C)."""
-    B, H, W, Cc = x.shape
+def dwconv_nhwc(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, stride: int = 1, act: bool = False,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise kh x kw conv, padding k/2 (csrc/bsyolo_ops.hip).  x (B,H,W,C) fp16 view; w (C,1,kh,kw) fp32, b (C) -- or w =
+    pack_dw_weight(w, b, device)."""
+    px, ld, B, H, W, Cc = _nhwc(x)
     kh, kw = int(w.shape[2]), int(w.shape[3])
-    wp = w.detach().float().cpu().view(Cc, kh * kw).t().contiguous().to(x.device)
-    bp = b.detach().float().contiguous().to(x.device)
-    OH, OW = (H + 2 * (kh // 2) - kh) // stride + 1, (W + 2 * (kw // 2) - kw) // stride + 1
-    out = torch.empty((B, OH, OW, Cc), dtype=torch.float16, device=x.device)
-    L.check(L.lib.bsy_dwconv(_p(x), Cc, B, H, W, Cc, kh, kw, stride, _p(wp), Cc, _p(bp), _p(out), Cc, int(act), _stream(x)))
+    wp, bp = _packed(pack_dw_weight, w, b, x.device)
+    if out is None:
+        out = torch.empty((B, *_out_hw(H, W, kh, kw, stride), Cc), dtype=torch.float16, device=x.device)
+    L.check(L.lib.bsy_dwconv(px, ld, B, H, W, Cc, kh, kw, stride, _p(wp), Cc, _p(bp), *_nhwc(out)[:2], int(act), _stream(x)))
     return out
 
 
@@ -199,25 +220,27 @@ def ela_nhwc(x: torch.Tensor, wsp: torch.Tensor, wch: torch.Tensor, gnw: torch.T
     return out
 
 
-def dwconv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, act: bool = True,
+def dwconv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, act: bool = True,
                    res: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x (B,H,W,C) fp16; w (C,1,3,3) fp32.  DWConv (conv.py:224-229)."""
-    B, H, W, Cc = x.shape
-    wp = w.detach().float().cpu().view(Cc, 9).t().contiguous().to(x.device)
-    bp = b.detach().float().contiguous().to(x.device)
-    out = torch.empty_like(x)
-    L.check(L.lib.bsy_dwconv3x3(_p(x), Cc, B, H, W, Cc, _p(wp), _p(bp), _p(out), Cc, int(act), _p(res),
-                                res.shape[-1] if res is not None else 0, _stream(x)))
+    """x (B,H,W,C) fp16 view, res likewise; w (C,1,3,3) fp32, b (C) -- or w = pack_dw_weight(w, b, device).  DWConv (conv.py:224-229)."""
+    px, ld, B, H, W, Cc = _nhwc(x)
+    wp, bp = _packed(pack_dw_weight, w, b, x.device)
+    out = torch.empty((B, H, W, Cc), dtype=x.dtype, device=x.device)
+    L.check(L.lib.bsy_dwconv3x3(px, ld, B, H, W, Cc, _p(wp), _p(bp), _p(out), Cc, int(act), *_nhwc(res)[:2], _stream(x)))
     return out
 
 
-def sppf_pool_nhwc(x1: torch.Tensor) -> torch.Tensor:
-    """x1 (B,H,W,C) -> (B,H,W,4C) = cat[x1, m(x1), m(m(x1)), m(m(m(x1)))], m = MaxPool2d(5,1,2) (block.py:3145-3149)."""
+def sppf_pool_nhwc(x1: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x1 (B,H,W,C) -> (B,H,W,4C) = cat[x1, m(x1), m(m(x1)), m(m(m(x1)))], m = MaxPool2d(5,1,2) (block.py:3145-3149).  `out`: the
+    (B,H,W,4C) concat buffer (a view) whose first C channels are x1 itself; the pools fill the rest in place."""
     B, H, W, Cc = x1.shape
-    buf = torch.zeros((B, H, W, 4 * Cc), dtype=torch.float16, device=x1.device)
-    buf[..., :Cc] = x1
-    L.check(L.lib.bsy_sppf_pool(_p(buf), 4 * Cc, B, H, W, Cc, _stream(x1)))
-    return buf
+    if out is None:
+        out = torch.zeros((B, H, W, 4 * Cc), dtype=torch.float16, device=x1.device)
+        out[..., :Cc] = x1
+    else:
+        assert out.shape == (B, H, W, 4 * Cc) and out.data_ptr() == x1.data_ptr()
+    L.check(L.lib.bsy_sppf_pool(*_nhwc(out)[:2], B, H, W, Cc, _stream(x1)))
+    return out
 
 
 def pool_down_nhwc(x: torch.Tensor, mode: int, C: Optional[int] = None, coff: int = 0, out: Optional[torch.Tensor] = None,
@@ -250,43 +273,41 @@ def attention_pe_nhwc(qkv: torch.Tensor, heads: int, key_dim: int, head_dim: int
                       out: Optional[torch.Tensor] = None, out_coff: int = 0) -> torch.Tensor:
     """qkv (B,H,W,heads*(2kd+hd)) fp16 in [q|k|v] order -> attention + pe(v) (B,H,W,heads*hd) in one launch (block.py:4279-4286).
     pe_w (heads*hd,1,3,3) / pe_b (heads*hd): Attention.pe's folded depthwise conv; None runs the attention alone.  impl 0 auto /
-    1 resident / 2 streaming kernel form.  `out` (B,H,W,ld >= out_coff + heads*hd): written at channel out_coff, the rest untouched."""
-    assert qkv.is_contiguous() and qkv.dim() == 4
-    B, H, W, ld = qkv.shape
+    1 resident / 2 streaming kernel form.  `out` (B,H,W,>= out_coff + heads*hd), a view: written at channel out_coff, the rest untouched.
+    pe_w may be pack_dw_weight's pair."""
+    assert qkv.dim() == 4
+    pq, ld, B, H, W, _ = _nhwc(qkv)
     Cc = heads * head_dim
     if out is None:
         out = torch.empty((B, H, W, Cc), dtype=torch.float16, device=qkv.device)
-    assert out.is_contiguous() and out.dtype == torch.float16 and out.shape[:3] == qkv.shape[:3]
-    wp = bp = None
-    if pe_w is not None:
-        wp = pe_w.detach().float().cpu().view(Cc, 9).t().contiguous().to(qkv.device)
-        bp = pe_b.detach().float().contiguous().to(qkv.device)
-    dst = out.view(-1)[out_coff:] if out_coff else out
-    L.check(L.lib.bsy_attention_pe(_p(qkv), ld, B, H, W, heads, key_dim, head_dim, float(scale), _p(wp), _p(bp), _p(dst),
-                                   out.shape[-1], int(impl), _stream(qkv)))
+    assert out.dtype == torch.float16 and out.shape[:3] == qkv.shape[:3] and out.shape[3] >= out_coff + Cc
+    wp, bp = _packed(pack_dw_weight, pe_w, pe_b, qkv.device) if pe_w is not None else (None, None)
+    L.check(L.lib.bsy_attention_pe(pq, ld, B, H, W, heads, key_dim, head_dim, float(scale), _p(wp), _p(bp), *_nhwc(out[..., out_coff:])[:2],
+                                   int(impl), _stream(qkv)))
     return out
 
 
 def detect_decode(box: Sequence[torch.Tensor], cls: Sequence[torch.Tensor], hw: Sequence[tuple],
                   strides: Sequence[float], nc: int, out_dtype=torch.float32,
                   msk: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
-    """box[l] (B*h*w, 64) f32, cls[l] (B*h*w, ldc) f32 -> (B, 4+nc+nm, A) (head.py:100-131)."""
+    """box[l], cls[l] [, msk[l]] f32: (B*h*w, 64 / >= nc / nm) matrices, or (B, h, w, .) maps -- also channel slices of one (B, h, w, no)
+    tensor per level, rows a multiple of 4 floats apart -> (B, 4+nc+nm, A) (head.py:100-131)."""
     nl = len(box)
-    B = box[0].shape[0] // (hw[0][0] * hw[0][1])
+    B = box[0].numel() // (box[0].shape[-1] * hw[0][0] * hw[0][1])
     nm = msk[0].shape[-1] if msk else 0
     A = sum(h * w for h, w in hw)
     y = torch.empty((B, 4 + nc + nm, A), dtype=out_dtype, device=box[0].device)
     vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-    bp = (vp * nl)(*[t.data_ptr() for t in box])
-    cp = (vp * nl)(*[t.data_ptr() for t in cls])
-    mp = (vp * nl)(*[t.data_ptr() for t in msk]) if msk else None
-    ldb = (i32 * nl)(*[t.shape[-1] for t in box])
-    ldc = (i32 * nl)(*[t.shape[-1] for t in cls])
-    ldm = (i32 * nl)(*[t.shape[-1] for t in msk]) if msk else None
+
+    def rows(ts):  # (pointers, leading dimensions) of one tensor per level
+        if not ts:
+            return None, None
+        return (vp * nl)(*[t.data_ptr() for t in ts]), (i32 * nl)(*[_nhwc(t)[1] if t.dim() == 4 else t.stride(0) for t in ts])
+
     hh = (i32 * nl)(*[h for h, _ in hw])
     ww = (i32 * nl)(*[w for _, w in hw])
     st = (f32 * nl)(*[float(s) for s in strides])
-    L.check(L.lib.bsy_detect_decode(bp, ldb, cp, ldc, mp, ldm, hh, ww, st, nl, B, nc, nm, _p(y), L.dtype_code(out_dtype),
+    L.check(L.lib.bsy_detect_decode(*rows(box), *rows(cls), *rows(msk), hh, ww, st, nl, B, nc, nm, _p(y), L.dtype_code(out_dtype),
                                     _stream(y)))
     return y
 

@@ -96,7 +96,15 @@ class WRec:
     b_off: int = -1
 
 
-# Fusion switch -> the environment variable that decides it where the caller passes None.  Every switch defaults to on, and the
+def qkv_perm(nh: int, kd: int, hd: int) -> List[int]:
+    """Attention.qkv's output rows are emitted per head as [q(kd) k(kd) v(hd)] by the reference (block.py:4274-4276); the kernels
+    want [q(all heads) | k(all heads) | v(all heads)], so that v is one channel slice and heads are contiguous: row i of that order
+    is the module's row qkv_perm(...)[i]."""
+    per = 2 * kd + hd
+    return [h * per + off + i for off, n in ((0, kd), (kd, kd), (2 * kd, hd)) for h in range(nh) for i in range(n)]
+
+
+# Fusion switch -> the environment variable that decides it where the caller passes None. Every switch defaults to on, and the
 # fp32-storage modes clear them all.  A new switch is one line here: Plan and YoloEngine take it as a keyword from this table.
 SWITCHES = {
     "fuse_stem": "BSY_FUSE_STEM",        # layers 0 + 1 as one launch (csrc/stem_fused.hip); off: two launches
@@ -701,12 +709,8 @@ class Plan:
         ab = self.alloc(2 * c, x.H, x.W)
         self.conv(name + ".cv1", x, 2 * c, 1, 1, dst=ab)
         b = ab.slice(c, c)
-        # qkv rows are emitted per head as [q(kd) k(kd) v(hd)] by the reference (block.py:4274-4276); reorder to
-        # [q(all heads) | k(all heads) | v(all heads)] so that v is one channel slice and heads are contiguous
         per = 2 * kd + hd
-        perm = [h * per + i for h in range(nh) for i in range(kd)] + \
-               [h * per + kd + i for h in range(nh) for i in range(kd)] + \
-               [h * per + 2 * kd + i for h in range(nh) for i in range(hd)]
+        perm = qkv_perm(nh, kd, hd)
         for i in range(n):
             pn = f"{name}.m.{i}"
             qkv = self.conv(pn + ".attn.qkv", b, nh * per, 1, 1, act=False, perm=perm)

@@ -46,8 +46,9 @@ import torch
 
 from . import lib as _L
 from . import nms as _nms
+from . import ops as _O
 from .engine import YoloEngine
-from .plan import Plan
+from .plan import Plan, qkv_perm
 from .weights import BN_EPS, repconv_form
 
 SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify", "Pose")
@@ -308,27 +309,9 @@ def _conv_spec(m):
 def _conv_forward(m, spec):
     """The replacement forward of one Conv / DWConv instance.  Falls back to the module's own forward for anything but a
     fp16 CUDA NCHW tensor in eval mode; re-packs its weights when they change (``Tensor._version`` / storage)."""
-    from .ops import _p, _stream, pack_conv_weight
-    from .weights import fold_conv_bn
-    import ctypes as C
     kind, k, s, act = spec
     orig = m.forward
-    st = {"ver": None, "dev": None, "w": None, "b": None, "calls": 0, "fallbacks": 0}
-
-    def pack(dev):
-        sd = {"m.conv." + n: t for n, t in m.conv.state_dict().items()}
-        bn = getattr(m, "bn", None)
-        if st["fold_bn"]:
-            sd.update({"m.bn." + n: t for n, t in bn.state_dict().items()})
-        elif "m.conv.bias" not in sd:
-            sd["m.conv.bias"] = torch.zeros(m.conv.out_channels)
-        w, b = fold_conv_bn(sd, "m", float(bn.eps) if isinstance(bn, torch.nn.BatchNorm2d) else BN_EPS)
-        if kind == "dw":
-            c = m.conv.out_channels
-            st["w"] = w.view(c, k * k).t().contiguous().to(dev)
-            st["b"] = b.contiguous().to(dev)
-        else:
-            st["w"], st["b"] = pack_conv_weight(w, b, dev)
+    st = {"ver": None, "dev": None, "w": None, "calls": 0, "fallbacks": 0}
 
     def fwd(self, x):
         if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float16 or x.dim() != 4 or self.training
@@ -337,30 +320,21 @@ def _conv_forward(m, spec):
             return orig(x)
         ver = _weights_version(self)
         if st["ver"] != ver or st["dev"] != x.device:
-            pack(x.device)
+            st["w"] = (_O.pack_dw_weight if kind == "dw" else _O.pack_conv_weight)(*_folded(self, orig), x.device)
             st["ver"], st["dev"] = ver, x.device
-        B, c1, H, W = x.shape
+        B, _, H, W = x.shape
         c2 = self.conv.out_channels
-        OH, OW = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
-        out = torch.empty((B, OH, OW, c2), dtype=torch.float16, device=x.device)
+        out = torch.empty((B, (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1, c2), dtype=torch.float16, device=x.device)
         with torch.cuda.device(x.device):
             if kind == "first":
-                xi = x.contiguous()
-                _L.check(_L.lib.bsy_conv_first(_p(xi), _L.dtype_code(xi.dtype), B, H, W, _p(st["w"]), _p(st["b"]), _p(out), c2, c2, k, s,
-                                               act, _stream(x)))
+                _O.conv_first(x.contiguous(), st["w"], None, k, s, act, out=out)
+            elif kind == "conv":
+                _O.conv2d_nhwc(_nhwc(x), *st["w"], c2, k, s, act, out=out)
             else:
-                xn = x.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)  # NHWC view, no copy when already channels_last
-                if kind == "conv":
-                    _L.check(_L.lib.bsy_conv2d(_p(xn), c1, B, H, W, c1, _p(st["w"]), _p(st["b"]), _p(out), c2, c2, k, s, act, None, 0, 0,
-                                               _stream(x)))
-                else:
-                    _L.check(_L.lib.bsy_dwconv(_p(xn), c1, B, H, W, c1, k, k, s, _p(st["w"]), c1, _p(st["b"]), _p(out), c2, act, _stream(x)))
+                _O.dwconv_nhwc(_nhwc(x), st["w"], None, s, act, out=out)
         st["calls"] += 1
         return out.permute(0, 3, 1, 2)  # NCHW tensor in channels_last memory format
 
-    # un-fused module (its forward = conv -> bn -> act): BatchNorm is folded at pack time; after BaseModel.fuse() (tasks.py:209-215:
-    # conv replaced by the fused conv, `bn` deleted, forward = forward_fuse) conv.bias already holds it
-    st["fold_bn"] = isinstance(getattr(m, "bn", None), torch.nn.BatchNorm2d) and getattr(orig, "__name__", "") != "forward_fuse"
     return fwd, st
 
 
@@ -372,12 +346,14 @@ def _silu_conv(m, k=None, s=1, groups=1) -> bool:
             and conv.stride == (s, s) and conv.padding == (conv.kernel_size[0] // 2,) * 2 and conv.dilation == (1, 1))
 
 
-def _folded(m):
-    """(weight, bias) fp32 of a reference Conv module, BatchNorm folded in when the module still has one (un-fused)."""
+def _folded(m, forward=None):
+    """(weight, bias) fp32 of a reference Conv module.  Un-fused (its forward = conv -> bn -> act) BatchNorm is folded in; after
+    BaseModel.fuse() (tasks.py:209-215: conv replaced by the fused conv, `bn` deleted, forward = forward_fuse) conv.bias already
+    holds it.  `forward`: the module's own forward where a hook has taken its place (captured at install time)."""
     from .weights import fold_conv_bn
     sd = {"m.conv." + n: t for n, t in m.conv.state_dict().items()}
     bn = getattr(m, "bn", None)
-    if isinstance(bn, torch.nn.BatchNorm2d) and getattr(m.forward, "__name__", "") != "forward_fuse":
+    if isinstance(bn, torch.nn.BatchNorm2d) and getattr(forward or m.forward, "__name__", "") != "forward_fuse":
         sd.update({"m.bn." + n: t for n, t in bn.state_dict().items()})
     elif "m.conv.bias" not in sd:
         sd["m.conv.bias"] = torch.zeros(m.conv.out_channels)
@@ -429,159 +405,113 @@ def _nhwc(x):
     return x.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
 
 
+def _fp16_map(self, x, cin) -> bool:
+    """What the block operators take: an fp16 NCHW device tensor of `cin` channels, in eval mode."""
+    return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and not self.training and x.shape[1] == cin
+
+
+def _pack_convs(dev, *convs):
+    return [_O.pack_conv_weight(*_folded(c), dev) for c in convs]
+
+
+def _sppf(self, x, pk, st):
+    xn = _nhwc(x)
+    B, H, W, _ = xn.shape
+    c_, c2 = self.cv1.conv.out_channels, self.cv2.conv.out_channels
+    cat = torch.empty((B, H, W, 4 * c_), dtype=torch.float16, device=x.device)
+    out = torch.empty((B, H, W, c2), dtype=torch.float16, device=x.device)
+    # cv1 writes channels [0, c_) of the concat buffer, the pools fill the rest in place, cv2 reads all of it
+    _O.conv2d_nhwc(xn, *pk[0], c_, 1, 1, True, out=cat[..., :c_])
+    _O.sppf_pool_nhwc(cat[..., :c_], out=cat)
+    return _O.conv2d_nhwc(cat, *pk[1], c2, 1, 1, True, out=out).permute(0, 3, 1, 2)
+
+
+def _pack_attention(self, dev):
+    perm = torch.tensor(qkv_perm(self.num_heads, self.key_dim, self.head_dim))
+    wq, bq = _folded(self.qkv)
+    return [_O.pack_conv_weight(wq[perm], bq[perm], dev), *_pack_convs(dev, self.proj), _O.pack_dw_weight(*_folded(self.pe), dev)]
+
+
+def _attention(self, x, pk, st):
+    xn = _nhwc(x)
+    B, H, W, c = xn.shape
+    nh, kd, hd = self.num_heads, self.key_dim, self.head_dim
+    ld = nh * (2 * kd + hd)
+    qkv = torch.empty((B, H, W, ld), dtype=torch.float16, device=x.device)
+    out = torch.empty((B, H, W, c), dtype=torch.float16, device=x.device)
+    _O.conv2d_nhwc(xn, *pk[0], ld, 1, 1, False, out=qkv)
+    att = _O.attention_nhwc(qkv.view(B, H * W, ld), nh, kd, hd, self.scale).view(B, H, W, c)
+    xo = _O.dwconv3x3_nhwc(qkv[..., 2 * nh * kd:], pk[2], act=False, res=att)  # v @ attn^T + pe(v): the depthwise conv reads the v slice
+    return _O.conv2d_nhwc(xo, *pk[1], c, 1, 1, False, out=out).permute(0, 3, 1, 2)
+
+
+def _detect_takes(self, x) -> bool:
+    """Detect._inference(x) with x = the per-level (B, 64 + nc, h, w) logit maps (head.py:100-131).  export / format / end2end variants
+    compute something else (head.py:66-67, 109-127: dist2bbox(xywh=not end2end), format-specific rescaling), checked at CALL time:
+    exporters flip these attributes on live modules."""
+    xs = list(x) if isinstance(x, (list, tuple)) else None
+    return not (xs is None or len(xs) != self.nl or self.training or getattr(self, "export", False) or getattr(self, "end2end", False)
+                or getattr(self, "format", None) is not None
+                or not all(torch.is_tensor(t) and t.is_cuda and t.dtype in (torch.float16, torch.float32) and t.dim() == 4
+                           and t.shape[1] == self.no and t.shape[0] == xs[0].shape[0] for t in xs))
+
+
+def _detect(self, x, pk, st):
+    maps = [t.permute(0, 2, 3, 1).float().contiguous() for t in x]  # (B, h, w, no) f32: what bsy_detect_decode reads
+    ld = self.no + (-self.no % 4)  # its rows are multiples of 4 floats: a one-class head (a stock pose model: no = 65) is padded
+    if ld != self.no:
+        maps = [torch.nn.functional.pad(t, (0, ld - self.no)) for t in maps]
+    hw, strides = [(int(t.shape[1]), int(t.shape[2])) for t in maps], [float(v) for v in self.stride]
+    y = _O.detect_decode([t[..., :64] for t in maps], [t[..., 64:] for t in maps], hw, strides, self.nc, x[0].dtype)
+    st["levels"] = (hw, strides, y.shape[2], y.shape[0])
+    # the reference's _inference caches anchors / strides per input shape as a side effect (head.py:105-107) and code outside
+    # the path may read them (exporters, Detect.decode_bboxes callers): keep `shape` as the reference does and drop the cached
+    # grids, so that the reference's own _inference -- on a fallback call -- rebuilds them for ITS shape instead of reusing ours
+    self.shape = None
+    return y
+
+
+# kind -> (takes(self, x): the call is the operator's, checked at call time; pack(self, dev) -> device weights, or None; body(self, x,
+# weights, st) -> what the module's own method returns)
+_BLOCKS = {
+    "sppf": (lambda self, x: _fp16_map(self, x, self.cv1.conv.in_channels), lambda self, dev: _pack_convs(dev, self.cv1, self.cv2), _sppf),
+    "attention": (lambda self, x: _fp16_map(self, x, self.num_heads * self.head_dim), _pack_attention, _attention),
+    "bottleneck": (lambda self, x: _fp16_map(self, x, self.cv1.conv.in_channels), lambda self, dev: _pack_convs(dev, self.cv1, self.cv2),
+                   lambda self, x, pk, st: _O.bottleneck_fused(_nhwc(x), pk[0], None, pk[1], None).permute(0, 3, 1, 2)),
+    "c3k2": (lambda self, x: _fp16_map(self, x, self.cv1.conv.in_channels),
+             lambda self, dev: _pack_convs(dev, self.cv1, self.m[0].cv1, self.m[0].cv2, self.cv2),
+             lambda self, x, pk, st: _O.c3k2_fused(_nhwc(x), pk[0], None, pk[1], None, pk[2], None, pk[3], None).permute(0, 3, 1, 2)),
+    "detect": (_detect_takes, None, _detect),
+    "pose": (_detect_takes, None, _detect),
+}
+
+
 def _block_forward(m, kind):
-    """The replacement `forward` (`_inference` for Detect and Pose) of one block instance.  fp16 CUDA tensors in eval mode; anything
-    else reaches the module's own method.  Weights are re-packed when they change (`_weights_version`)."""
-    from .ops import _p, _stream, pack_conv_weight
+    """The replacement `forward` (`_inference` for Detect and Pose) of one block instance: one skeleton, the kind (_BLOCKS) says which
+    calls it takes, how its weights pack and what it runs.  Anything it does not take reaches the module's own method.  Weights are
+    re-packed when they change (`_weights_version`) or move to another device, never per call."""
+    takes, pack, body = _BLOCKS[kind]
     attr = "_inference" if kind in ("detect", "pose") else "forward"
     orig = getattr(m, attr)
-    st = {"ver": None, "dev": None, "w": None, "calls": 0, "fallbacks": 0, "kind": kind, "attr": attr}
-    # detect / pose: what the last _inference call decoded -- ((h, w) per level, strides, A, B) -- or None when it fell back;
+    # levels (detect / pose): what the last _inference call decoded -- ((h, w) per level, strides, A, B) -- or None when it fell back;
     # Pose's kpts_decode hook, which runs later in the same forward (head.py:246-249), reads it
-    st["levels"] = None
+    st = {"ver": None, "dev": None, "w": None, "calls": 0, "fallbacks": 0, "kind": kind, "attr": attr, "levels": None}
 
-    def usable(self, x):
-        return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and not self.training
-
-    def ready(self, dev):
-        ver = _weights_version(self)
-        if st["ver"] != ver or st["dev"] != dev:
-            st["w"] = pack(self, dev)
-            st["ver"], st["dev"] = ver, dev
-        return st["w"]
-
-    if kind == "sppf":
-        def pack(self, dev):
-            return [pack_conv_weight(*_folded(c), dev) for c in (self.cv1, self.cv2)]
-
-        def fwd(self, x):
-            if not usable(self, x) or x.shape[1] != self.cv1.conv.in_channels:
-                st["fallbacks"] += 1
-                return orig(x)
-            (w1, b1), (w2, b2) = ready(self, x.device)
-            B, c1, H, W = x.shape
-            c_, c2 = self.cv1.conv.out_channels, self.cv2.conv.out_channels
-            xn = _nhwc(x)
-            cat = torch.empty((B, H, W, 4 * c_), dtype=torch.float16, device=x.device)
-            out = torch.empty((B, H, W, c2), dtype=torch.float16, device=x.device)
-            with torch.cuda.device(x.device):
-                s = _stream(x)  # cv1 writes channels [0, c_) of the concat buffer, the pools fill the rest in place, cv2 reads all of it
-                _L.check(_L.lib.bsy_conv2d(_p(xn), c1, B, H, W, c1, _p(w1), _p(b1), _p(cat), 4 * c_, c_, 1, 1, 1, None, 0, 0, s))
-                _L.check(_L.lib.bsy_sppf_pool(_p(cat), 4 * c_, B, H, W, c_, s))
-                _L.check(_L.lib.bsy_conv2d(_p(cat), 4 * c_, B, H, W, 4 * c_, _p(w2), _p(b2), _p(out), c2, c2, 1, 1, 1, None, 0, 0, s))
-            st["calls"] += 1
-            return out.permute(0, 3, 1, 2)
-    elif kind == "attention":
-        def pack(self, dev):
-            nh, kd, hd = self.num_heads, self.key_dim, self.head_dim
-            per = 2 * kd + hd  # the module emits [q k v] per head (block.py:4274-4276); the kernels want [q | k | v] by heads
-            perm = torch.tensor([h * per + i for h in range(nh) for i in range(kd)] + [h * per + kd + i for h in range(nh) for i in range(kd)]
-                                + [h * per + 2 * kd + i for h in range(nh) for i in range(hd)])
-            wq, bq = _folded(self.qkv)
-            wpe, bpe = _folded(self.pe)
-            c = nh * hd
-            return [pack_conv_weight(wq[perm], bq[perm], dev), pack_conv_weight(*_folded(self.proj), dev),
-                    (wpe.view(c, 9).t().contiguous().to(dev), bpe.contiguous().to(dev))]
-
-        def fwd(self, x):
-            if not usable(self, x) or x.shape[1] != self.num_heads * self.head_dim:
-                st["fallbacks"] += 1
-                return orig(x)
-            (wq, bq), (wp, bp), (wd, bd) = ready(self, x.device)
-            B, c, H, W = x.shape
-            nh, kd, hd = self.num_heads, self.key_dim, self.head_dim
-            ld = nh * (2 * kd + hd)
-            xn = _nhwc(x)
-            qkv = torch.empty((B, H, W, ld), dtype=torch.float16, device=x.device)
-            att = torch.empty((B, H, W, c), dtype=torch.float16, device=x.device)
-            xo = torch.empty_like(att)
-            out = torch.empty_like(att)
-            with torch.cuda.device(x.device):
-                s = _stream(x)
-                _L.check(_L.lib.bsy_conv2d(_p(xn), c, B, H, W, c, _p(wq), _p(bq), _p(qkv), ld, ld, 1, 1, 0, None, 0, 0, s))
-                _L.check(_L.lib.bsy_attention(_p(qkv), ld, B, H * W, nh, kd, hd, float(self.scale), _p(att), c, s))
-                v = qkv[..., 2 * nh * kd:]  # v @ attn^T + pe(v): the depthwise conv reads the v slice and adds the attention output
-                _L.check(_L.lib.bsy_dwconv3x3(_p(v), ld, B, H, W, c, _p(wd), _p(bd), _p(xo), c, 0, _p(att), c, s))
-                _L.check(_L.lib.bsy_conv2d(_p(xo), c, B, H, W, c, _p(wp), _p(bp), _p(out), c, c, 1, 1, 0, None, 0, 0, s))
-            st["calls"] += 1
-            return out.permute(0, 3, 1, 2)
-    elif kind == "bottleneck":
-        def pack(self, dev):
-            return [pack_conv_weight(*_folded(c), dev) for c in (self.cv1, self.cv2)]
-
-        def fwd(self, x):
-            if not usable(self, x) or x.shape[1] != self.cv1.conv.in_channels:
-                st["fallbacks"] += 1
-                return orig(x)
-            (w1, b1), (w2, b2) = ready(self, x.device)
-            B, c, H, W = x.shape
-            xn = _nhwc(x)
-            out = torch.empty((B, H, W, c), dtype=torch.float16, device=x.device)
-            with torch.cuda.device(x.device):
-                _L.check(_L.lib.bsy_bottleneck_fused(_p(xn), xn.stride(2), B, H, W, c, self.cv1.conv.out_channels, _p(w1), _p(b1), _p(w2), _p(b2),
-                                                     _p(out), c, 1, _stream(x)))
-            st["calls"] += 1
-            return out.permute(0, 3, 1, 2)
-    elif kind == "c3k2":
-        def pack(self, dev):
-            return [pack_conv_weight(*_folded(c), dev) for c in (self.cv1, self.m[0].cv1, self.m[0].cv2, self.cv2)]
-
-        def fwd(self, x):
-            if not usable(self, x) or x.shape[1] != self.cv1.conv.in_channels:
-                st["fallbacks"] += 1
-                return orig(x)
-            pk = ready(self, x.device)
-            B, cin, H, W = x.shape
-            c2 = self.cv2.conv.out_channels
-            xn = _nhwc(x)
-            out = torch.empty((B, H, W, c2), dtype=torch.float16, device=x.device)
-            with torch.cuda.device(x.device):
-                _L.check(_L.lib.bsy_c3k2_fused(_p(xn), xn.stride(2), B, H, W, cin, self.c, c2, _p(pk[0][0]), _p(pk[0][1]), _p(pk[1][0]), _p(pk[1][1]),
-                                               _p(pk[2][0]), _p(pk[2][1]), _p(pk[3][0]), _p(pk[3][1]), _p(out), c2, _stream(x)))
-            st["calls"] += 1
-            return out.permute(0, 3, 1, 2)
-    else:  # detect: Detect._inference(x) with x = the per-level (B, 64 + nc, h, w) logit maps (head.py:100-131)
-        import ctypes as C
-
-        def pack(self, dev):
-            return None
-
-        def fwd(self, x):
-            xs = list(x) if isinstance(x, (list, tuple)) else None
-            nm = 0
-            # export / format / end2end variants compute something else (head.py:66-67, 109-127: dist2bbox(xywh=not end2end), format-
-            # specific rescaling), checked at CALL time: exporters flip these attributes on live modules
-            if (xs is None or len(xs) != self.nl or self.training or getattr(self, "export", False) or getattr(self, "end2end", False)
-                    or getattr(self, "format", None) is not None
-                    or not all(torch.is_tensor(t) and t.is_cuda and t.dtype in (torch.float16, torch.float32) and t.dim() == 4
-                               and t.shape[1] == self.no and t.shape[0] == xs[0].shape[0] for t in xs)):
-                st["fallbacks"] += 1
-                st["levels"] = None
-                return orig(x)
-            B, nl, nc = xs[0].shape[0], self.nl, self.nc
-            dev, dt = xs[0].device, xs[0].dtype
-            maps = [t.permute(0, 2, 3, 1).float().contiguous() for t in xs]  # (B, h, w, no) f32: what bsy_detect_decode reads
-            ld = self.no + (-self.no % 4)  # its rows are multiples of 4 floats: a one-class head (a stock pose model: no = 65) is padded
-            if ld != self.no:
-                maps = [torch.nn.functional.pad(t, (0, ld - self.no)) for t in maps]
-            A = sum(t.shape[1] * t.shape[2] for t in maps)
-            y = torch.empty((B, 4 + nc, A), dtype=dt, device=dev)
-            vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-            box = (vp * nl)(*[t.data_ptr() for t in maps])
-            cls = (vp * nl)(*[t.data_ptr() + 64 * 4 for t in maps])
-            ldv = (i32 * nl)(*[ld] * nl)
-            hh = (i32 * nl)(*[t.shape[1] for t in maps])
-            ww = (i32 * nl)(*[t.shape[2] for t in maps])
-            sv = (f32 * nl)(*[float(v) for v in self.stride])
-            with torch.cuda.device(dev):
-                _L.check(_L.lib.bsy_detect_decode(box, ldv, cls, ldv, None, None, hh, ww, sv, nl, B, nc, nm, _p(y), _L.dtype_code(dt), _stream(y)))
-            st["calls"] += 1
-            st["levels"] = ([(int(t.shape[1]), int(t.shape[2])) for t in maps], [float(v) for v in self.stride], A, B)
-            # the reference's _inference caches anchors / strides per input shape as a side effect (head.py:105-107) and code outside
-            # the path may read them (exporters, Detect.decode_bboxes callers): keep `shape` as the reference does and drop the cached
-            # grids, so that the reference's own _inference -- on a fallback call -- rebuilds them for ITS shape instead of reusing ours
-            self.shape = None
-            return y
+    def fwd(self, x):
+        if not takes(self, x):
+            st["fallbacks"] += 1
+            st["levels"] = None
+            return orig(x)
+        dev = (x if torch.is_tensor(x) else x[0]).device
+        if pack is not None:
+            ver = _weights_version(self)
+            if st["ver"] != ver or st["dev"] != dev:
+                st["w"] = pack(self, dev)
+                st["ver"], st["dev"] = ver, dev
+        with torch.cuda.device(dev):
+            y = body(self, x, st["w"], st)
+        st["calls"] += 1
+        return y
     return fwd, st
 
 
@@ -591,7 +521,6 @@ def _pose_kpts_forward(m, st):
     and strides that hook recorded for the same forward.  Whenever that call itself fell back the reference's anchors are valid, and the
     original method runs; it also runs on `export` (checked at call time), for CPU tensors and for a map that is not the recorded
     (B, nk, A)."""
-    from .ops import kpts_decode
     orig = m.kpts_decode
 
     def fwd(self, bs, kpts):
@@ -602,7 +531,7 @@ def _pose_kpts_forward(m, st):
             st["kpt_fallbacks"] = st.get("kpt_fallbacks", 0) + 1
             return orig(bs, kpts)
         with torch.cuda.device(kpts.device):
-            y = kpts_decode(kpts.contiguous(), lv[0], lv[1], self.kpt_shape)
+            y = _O.kpts_decode(kpts.contiguous(), lv[0], lv[1], self.kpt_shape)
         st["kpt_calls"] = st.get("kpt_calls", 0) + 1
         return y
     return fwd

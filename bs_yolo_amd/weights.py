@@ -4,18 +4,23 @@
                      BaseModel.fuse, nn/tasks.py:209-215): W' = diag(g / sqrt(var + eps)) W,  b' = beta - g mu / sqrt(var + eps).
                      Accepts either an un-fused state_dict (conv.weight + bn.*) or an already fused one
                      (conv.weight + conv.bias), which is what a reference model holds after AutoBackend's fuse().
-  * pack layouts  -- conv   : fp16 [CoutPad128][Kpad32], K order (kh, kw, cin)  (conv_gemm.hip), bias fp32 [CoutPad128]
-                     first  : same as conv with cin = 3 (K = 27 -> 32)  (conv_first.hip)
-                     dw     : fp32 [9][C] (elementwise.hip)
+  * pack_record   -- three steps, each stated once: the record's SOURCE reads the module's fp32 (w, b) from the state dict (SOURCES:
+                     key names, the module's own shapes and synth_state_dict's draws side by side), op_channels re-lays them out
+                     to the op's channels, and a LAYOUT function writes the device form:
+                     dense_f16  : fp16 [CoutPad][Kpad], K order (kh, kw, cin), bias fp32 [CoutPad]  (conv_gemm.hip, conv_first.hip)
+                     dense_f32  : f32 [K][Cout] (+ the split-f16 planes of the fp32x mode), bias f32 [Cout]  (ref32.hip, conv32x_mfma.hip)
+                     depthwise  : f32 [kh*kw][C], bias f32 [C]  (elementwise.hip, bsyolo_ops.hip)
+                     The stand-alone operators (ops.py) and the per-module hooks (plugin.py) pack with the same three functions.
 """
 from __future__ import annotations
 
+import ctypes
 import re
-from typing import Dict, Mapping
+from typing import Dict, List, Mapping, Tuple
 
-import numpy as np
 import torch
 
+from . import lib as L
 from .plan import Plan, WRec
 
 BN_EPS = 1e-3  # utils/torch_utils.py:424
@@ -80,8 +85,40 @@ def repconv_form(sd: Mapping[str, torch.Tensor]) -> str:
     return "repvgg" if any(_REPVGG_KEY.search(k) for k in sd) else "refconv"
 
 
+# ---- layouts: an op's final fp32 (w, b) -> the tensors the kernels read (on the CPU; callers move or serialise them) ----
 def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a
+
+
+def _bytes(*parts: torch.Tensor) -> bytes:
+    """The tensors' bytes one after the other, each but the last padded to 256 bytes (a record's f32 matrix and its split planes:
+    csrc/op_args.h build_conv32 computes the same offsets)."""
+    raw = [t.numpy().tobytes() for t in parts]
+    return b"".join(x.ljust(_align(len(x)), b"\0") for x in raw[:-1]) + raw[-1]
+
+
+def packed_dims(cout: int, cin: int, k: int) -> Tuple[int, int]:
+    """(CoutPad, Kpad) of the fp16 dense layout, as the library says them (csrc/conv_select.hip bsy_conv_packed_dims)."""
+    cp, kp = ctypes.c_int(), ctypes.c_int()
+    L.check(L.lib.bsy_conv_packed_dims(cout, cin, k, ctypes.byref(cp), ctypes.byref(kp)))
+    return cp.value, kp.value
+
+
+def dense_f16(w, b=None):
+    """(Cout, Cin, k, k) [+ bias (Cout)] -> fp16 [CoutPad][Kpad], K order (kh, kw, cin), and bias f32 [CoutPad], zero in the padding
+    (csrc/conv_gemm.hip).  An image conv (Cin = 3) is packed with a zero 4th input channel, K = (kh, kw, c4) (csrc/image_conv.h)."""
+    w = _f32(w)
+    cout, cin, k, _ = w.shape
+    cp, kp = packed_dims(cout, cin, k)
+    if cin == 3:
+        w = torch.cat([w, torch.zeros(cout, 1, k, k)], 1)
+    K = k * k * w.shape[1]
+    wp = torch.zeros(cp, kp, dtype=torch.float16)
+    wp[:cout, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).to(torch.float16)
+    bp = torch.zeros(cp, dtype=torch.float32)
+    if b is not None:
+        bp[:cout] = _f32(b)
+    return wp, bp
 
 
 def split_f16_planes(w2d: torch.Tensor):
@@ -98,121 +135,186 @@ def split_f16_planes(w2d: torch.Tensor):
     return hi, lo
 
 
-def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f32: bool = False, split: bool = False):
-    """-> (weight bytes, bias bytes) for one op.  f32: the fp32 correctness mode's layout for dense convs -- f32
-    [k*k*cin][cout] (K order (kh, kw, cin) as in the fp16 layout, cout fastest), bias f32 [cout], no padding
-    (csrc/ref32.hip); depthwise / ELA records are f32 in both modes.  split (fp32x mode, with f32): the f32 matrix is followed
-    by the two f16 planes of split_f16_planes, each part padded to 256 bytes (csrc/op_args.h build_conv32 computes the same
-    offsets)."""
-    if r.kind == "ela":
-        # ELA (nn/Addmodules/ELA.py:36-72): [spatial_conv (C,k)][ch_att.2 (C,k)][gn.weight][gn.bias]; the three scalar mixing
-        # weights enter the op record as their sigmoids
-        c, k = r.cout, r.k
-        wsp, wch = _f32(sd[r.name + ".spatial_conv.weight"]).reshape(c, k), _f32(sd[r.name + ".ch_att.2.weight"]).reshape(c, k)
-        gw, gb = _f32(sd[r.name + ".gn.weight"]), _f32(sd[r.name + ".gn.bias"])
-        r.coef = tuple(float(torch.sigmoid(_f32(sd[r.name + "." + s]).view(-1)[0])) for s in ("ch_weight", "sp_weight", "res_weight"))
-        return torch.cat([wsp.reshape(-1), wch.reshape(-1), gw, gb]).contiguous().numpy().tobytes(), b""
-    if r.kind in ("plain", "dwg_plain"):
-        w, b = _f32(sd[r.name + ".weight"]), _f32(sd[r.name + ".bias"])
-        if w.dim() == 2:  # nn.Linear (Classify.linear, head.py:294): a 1x1 conv on the (B, 1, 1, cin) map
-            w = w[:, :, None, None]
-    elif r.kind == "deconv":
-        # nn.ConvTranspose2d(c, c, 2, 2, 0) (block.py:91): out[2i+dy, 2j+dx] = W[:, :, dy, dx]^T x[i, j] + b, i.e. one
-        # 1x1 conv per output phase; weight layout (cin, cout, 2, 2)
-        wt, b = _f32(sd[r.name + ".weight"]), _f32(sd[r.name + ".bias"])
-        dy, dx = r.tap
-        w = wt[:, :, dy, dx].t().contiguous().view(r.cout, r.cin, 1, 1)
-    elif r.kind == "conv2":  # two Conv modules on the same input, stacked along cout (plan.py conv(name2=...))
-        (w, b), (w2, b2) = fold_conv_bn(sd, r.name, eps), fold_conv_bn(sd, r.post, eps)
-        w, b = torch.cat([w, w2]), torch.cat([b, b2])
-    elif r.kind == "refconv":
-        w, b = fold_refconv(sd, r.name)
-    elif r.kind == "repvgg":
-        w, b = fold_repvgg(sd, r.name, eps)
-    else:
-        w, b = fold_conv_bn(sd, r.name, eps)
+def dense_f32(w, b, split: bool = False):
+    """(Cout, Cin, k, k) + bias -> ((matrix,) or (matrix, hi, lo), bias): the fp32 correctness mode's f32 [k*k*cin][cout] matrix (K order
+    (kh, kw, cin) as in the fp16 layout, cout fastest) and bias f32 [cout], no padding (csrc/ref32.hip); split (fp32x mode) adds the two
+    f16 planes of split_f16_planes, which a record carries behind the matrix (_bytes)."""
+    w = _f32(w)
+    cout = w.shape[0]
+    mats = (w.permute(2, 3, 1, 0).reshape(-1, cout).contiguous(),)
+    if split:
+        mats += split_f16_planes(w.permute(0, 2, 3, 1).reshape(cout, -1))
+    return mats, _f32(b).contiguous()
+
+
+def depthwise(w, b):
+    """(C, 1, kh, kw) + bias -> f32 [kh*kw][C] and bias f32 [C], in every precision (csrc/elementwise.hip, csrc/bsyolo_ops.hip)."""
+    w = _f32(w)
+    return w.reshape(w.shape[0], -1).t().contiguous(), _f32(b).contiguous()
+
+
+# ---- sources: where a record's (w, b) come from in the state dict.  Per source the parameters it reads -- (key, the module's own
+# shape, synth_state_dict's draw), in the order they are drawn -- and the reader (sd, r, eps) -> fp32 (w, b) of the module ----
+DW_KINDS = ("dw", "dwg", "dwg_plain", "dwg_ext")
+
+
+def _he(fan: int):  # He-normal
+    return lambda g, shape: torch.randn(*shape, generator=g) * (2.0 / fan) ** 0.5
+
+
+def _uni(scale: float, shift: float):
+    return lambda g, shape: torch.rand(*shape, generator=g) * scale + shift
+
+
+def _module_dims(r: WRec):
+    """The module's own (cout, cin, kh, kw): the record's, or real_cout / real_cin where the op runs wider than the module."""
+    co = r.real_cout or (r.cout // 2 if r.kind == "dwg_ext" else r.cout)
+    return co, 1 if r.kind in DW_KINDS else (r.real_cin or r.cin), r.k, r.kw or r.k
+
+
+def _conv_bn_params(prefix: str, co: int, ci: int, kh: int, kw: int):
+    """A reference Conv module (conv.py:133-151), un-fused: what fold_conv_bn reads.  Randomised BN statistics."""
+    return [(prefix + ".conv.weight", (co, ci, kh, kw), _he(ci * kh * kw)),
+            (prefix + ".bn.weight", (co,), _uni(0.6, 0.7)), (prefix + ".bn.bias", (co,), _uni(0.6, -0.3)),
+            (prefix + ".bn.running_mean", (co,), _uni(0.6, -0.3)), (prefix + ".bn.running_var", (co,), _uni(1.0, 0.5))]
+
+
+def _conv2(r):  # two Conv modules on the same input, half the width each, stacked along cout (plan.py conv(name2=...))
+    co, ci, kh, kw = _module_dims(r)
+    return _conv_bn_params(r.name, co // 2, ci, kh, kw) + _conv_bn_params(r.post, co // 2, ci, kh, kw)
+
+
+def _read_conv2(sd, r, eps):
+    (w, b), (w2, b2) = fold_conv_bn(sd, r.name, eps), fold_conv_bn(sd, r.post, eps)
+    return torch.cat([w, w2]), torch.cat([b, b2])
+
+
+def _bare(r):  # a bare nn.Conv2d / nn.Linear with bias; `post`: a depthwise 1x1 conv after it (MSCAAttention.dilconv, MSCA.py:31)
+    co, ci, kh, kw = _module_dims(r)
+    post = [(r.post + ".weight", (co, 1, 1, 1), _uni(1.0, 0.5)), (r.post + ".bias", (co,), _uni(0.4, -0.2))] if r.post else []
+    return [(r.name + ".weight", (co, ci, kh, kw), _he(ci * kh * kw)), (r.name + ".bias", (co,), _uni(0.4, -0.2))] + post
+
+
+def _read_bare(sd, r, eps):
+    w, b = _f32(sd[r.name + ".weight"]), _f32(sd[r.name + ".bias"])
+    if w.dim() == 2:  # nn.Linear (Classify.linear, head.py:294): a 1x1 conv on the (B, 1, 1, cin) map
+        w = w[:, :, None, None]
+    if r.post:  # y -> a*y + d, folded in
+        a, d = _f32(sd[r.post + ".weight"]).view(-1), _f32(sd[r.post + ".bias"])
+        w, b = w * a.view(-1, 1, 1, 1), a * b + d
+    return w, b
+
+
+def _deconv(r):  # nn.ConvTranspose2d(c, c, 2, 2, 0) (block.py:91), weight layout (cin, cout, 2, 2); one record per output phase
+    return [(r.name + ".weight", (r.cin, r.cout, 2, 2), _he(r.cin)), (r.name + ".bias", (r.cout,), _uni(0.4, -0.2))]
+
+
+def _read_deconv(sd, r, eps):
+    dy, dx = r.tap  # out[2i+dy, 2j+dx] = W[:, :, dy, dx]^T x[i, j] + b, i.e. one 1x1 conv per output phase
+    return _f32(sd[r.name + ".weight"])[:, :, dy, dx].permute(1, 0).reshape(r.cout, r.cin, 1, 1), _f32(sd[r.name + ".bias"])
+
+
+def _refconv(r):  # block.py:793-816: a buffer `weight` and the per-kernel 3x3 map over it
+    co, ci, kh, kw = _module_dims(r)
+    return [(r.name + ".weight", (co, ci, kh, kw), _he(ci * kh * kw)),
+            (r.name + ".convmap.weight", (co * ci, 1, 3, 3), lambda g, shape: torch.randn(*shape, generator=g) * (2.0 / 9) ** 0.5 * 0.25)]
+
+
+def _repvgg(r):  # conv.py:296-397, un-fused: a 3x3 and a 1x1 Conv + BN
+    co, ci, _, _ = _module_dims(r)
+    return _conv_bn_params(r.name + ".conv1", co, ci, 3, 3) + _conv_bn_params(r.name + ".conv2", co, ci, 1, 1)
+
+
+def _ela(r):  # ELA (nn/Addmodules/ELA.py:36-72): three scalar mixing weights, two Conv1d over k taps, one GroupNorm
+    c, k = r.cout, r.k
+    return ([(f"{r.name}.{s}", (1,), lambda g, shape: torch.randn(*shape, generator=g)) for s in ("ch_weight", "sp_weight", "res_weight")]
+            + [(r.name + ".spatial_conv.weight", (c, 1, k), _he(k)), (r.name + ".ch_att.2.weight", (c, 1, k), _he(k)),
+               (r.name + ".gn.weight", (c,), _uni(0.6, 0.7)), (r.name + ".gn.bias", (c,), _uni(0.6, -0.3))])
+
+
+def _read_ela(sd, r, eps):
+    """-> ([spatial_conv (C,k)][ch_att.2 (C,k)][gn.weight][gn.bias] as one vector, no bias); the three scalar mixing weights enter
+    the op record as their sigmoids (r.coef)."""
+    p = [_f32(sd[key]) for key, _, _ in _ela(r)]
+    r.coef = tuple(float(torch.sigmoid(t.view(-1)[0])) for t in p[:3])
+    return torch.cat([t.reshape(-1) for t in p[3:]]).contiguous(), None
+
+
+_CONV_BN = (lambda r: _conv_bn_params(r.name, *_module_dims(r)), lambda sd, r, eps: fold_conv_bn(sd, r.name, eps))
+_BARE = (_bare, _read_bare)
+SOURCES = {"conv": _CONV_BN, "first": _CONV_BN, "first_s2d": _CONV_BN, "dw": _CONV_BN, "dwg": _CONV_BN, "dwg_ext": _CONV_BN,
+           "conv2": (_conv2, _read_conv2), "plain": _BARE, "dwg_plain": _BARE, "deconv": (_deconv, _read_deconv),
+           "refconv": (_refconv, lambda sd, r, eps: fold_refconv(sd, r.name)),
+           "repvgg": (_repvgg, lambda sd, r, eps: fold_repvgg(sd, r.name, eps)), "ela": (_ela, _read_ela)}
+
+
+def record_keys(r: WRec) -> List[str]:
+    """The state-dict keys record `r` reads of an un-fused reference model."""
+    return [key for key, _, _ in SOURCES[r.kind][0](r)]
+
+
+# ---- channel step: the module's (w, b) -> the op's ----
+def _take(t: torch.Tensor, idx, dim: int = 0) -> torch.Tensor:
+    """t's slices idx[0], idx[1], ... along `dim`; zeros where idx[i] < 0."""
+    idx = torch.as_tensor(idx, dtype=torch.long)
+    assert int(idx.max()) < t.shape[dim], (tuple(t.shape), dim, int(idx.max()))
+    return t.index_select(dim, idx.clamp(min=0)).index_fill_(dim, torch.nonzero(idx < 0).view(-1), 0.0)
+
+
+def op_channels(r: WRec, w: torch.Tensor, b: torch.Tensor):
+    """The module's fp32 (w, b) -> the op's (r.cout, r.cin | 1, kh, kw) and (r.cout): which channels are re-laid out or zero."""
+    dw = r.kind in DW_KINDS
+    shape = (r.cout, 1 if dw else r.cin, r.k, r.kw or r.k)
     if r.rows is not None or r.cols is not None:
-        # the op's channels are a re-laid-out, zero-padded copy of the module's (plan.py _pmsfa_padded)
-        dw = w.shape[1] == 1 and r.kind in ("dw", "dwg", "dwg_plain", "dwg_ext")
+        # the op's channels are a re-laid-out, zero-padded copy of the module's (plan.py _pmsfa_padded, T.cmap)
         if r.rows is not None:
-            idx = torch.as_tensor(r.rows, dtype=torch.long)
-            assert int(idx.max()) < w.shape[0], (r.name, tuple(w.shape), int(idx.max()))
-            w2, b2 = torch.zeros(len(idx), *w.shape[1:]), torch.zeros(len(idx))
-            w2[idx >= 0], b2[idx >= 0] = w[idx[idx >= 0]], b[idx[idx >= 0]]
-            w, b = w2, b2
+            w, b = _take(w, r.rows), _take(b, r.rows)
         if r.cols is not None and not dw:
-            idx = torch.as_tensor(r.cols, dtype=torch.long)
-            assert int(idx.max()) < w.shape[1], (r.name, tuple(w.shape), int(idx.max()))
-            w2 = torch.zeros(w.shape[0], len(idx), *w.shape[2:])
-            w2[:, idx >= 0] = w[:, idx[idx >= 0]]
-            w = w2
+            w = _take(w, r.cols, 1)
     elif r.real_cout or r.real_cin:
         # the op runs wider than the module (plan.py detect(): widths padded to a multiple of 8): zero weights and biases in the padding
-        dw = w.shape[1] == 1 and r.kind in ("dw", "dwg", "dwg_plain", "dwg_ext")
-        co, ci = r.real_cout or r.cout, (1 if dw else (r.real_cin or r.cin))
+        co, ci = _module_dims(r)[:2]
         assert tuple(w.shape[:2]) == (co, ci), (r.name, tuple(w.shape), (co, ci))
-        w2 = torch.zeros(r.cout, 1 if dw else r.cin, *w.shape[2:])
-        w2[:co, :ci] = w
-        b2 = torch.zeros(r.cout)
-        b2[:co] = b
-        w, b = w2, b2
-    if r.kind == "first_s2d" and not f32:
+        w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, shape[1] - ci, 0, r.cout - co))
+        b = torch.nn.functional.pad(b, (0, r.cout - co))
+    if r.kind == "first_s2d":
         # 6x6 stride-2 pad-2 image conv (YOLOv5u's stem, cfg/models/v5/yolov5.yaml:16) = 3x3 stride-1 pad-1 conv over the
         # space-to-depth image [Y][X][(dy, dx, c)] (csrc/elementwise.hip s2d_kernel): input row 2 oy - 2 + kh with kh = 2 a + dy is
-        # s2d row oy - 1 + a, so w3[co][(dy, dx, c)][a][b] = w[co][c][2a + dy][2b + dx]; channels 12 .. 15 are zero padding
-        cout = r.cout
-        assert tuple(w.shape) == (cout, 3, 6, 6), (r.name, tuple(w.shape))
-        w3 = torch.zeros(cout, 16, 3, 3)
+        # s2d row oy - 1 + a, so w3[co][(dy, dx, c)][a][b] = w[co][c][2a + dy][2b + dx]; channels 12 .. 15 are zero padding.
+        # (Only fp16 plans hold such a record: plan.py conv_first.)
+        assert tuple(w.shape) == (r.cout, 3, 6, 6), (r.name, tuple(w.shape))
+        shape = (r.cout, 16, 3, 3)
+        w3 = torch.zeros(shape)
         for dy in (0, 1):
             for dx in (0, 1):
                 w3[:, (dy * 2 + dx) * 3:(dy * 2 + dx) * 3 + 3] = w[:, :, dy::2, dx::2]
         w = w3
-        r = WRec(name=r.name, kind="conv", cout=cout, cin=16, k=3)
-    if r.kind in ("conv", "conv2", "plain", "first", "first_s2d", "deconv", "refconv", "repvgg"):
-        cout, cin, k = r.cout, r.cin, r.k
-        assert tuple(w.shape) == (cout, cin, k, k), (r.name, tuple(w.shape), (cout, cin, k, k))
-        if r.perm is not None:
-            idx = torch.as_tensor(r.perm, dtype=torch.long)
-            w, b = w[idx], b[idx]
-        if f32:
-            wb = w.permute(2, 3, 1, 0).reshape(k * k * cin, cout).contiguous().numpy().tobytes()
-            if split:
-                hi, lo = split_f16_planes(w.permute(0, 2, 3, 1).reshape(cout, k * k * cin))
-                hb = hi.numpy().tobytes()
-                wb = wb + b"\0" * (_align(len(wb)) - len(wb)) + hb + b"\0" * (_align(len(hb)) - len(hb)) + lo.numpy().tobytes()
-            return wb, b.contiguous().numpy().tobytes()
-        if r.kind == "first":  # image conv: zero 4th input channel, k = (kh, kw, c4)  (csrc/image_conv.h)
-            w = torch.cat([w, torch.zeros(cout, 4 - cin, k, k)], 1)
-            cin = 4
-        K = k * k * cin
-        cp, kp = (cout + 127) // 128 * 128, (K + 31) // 32 * 32
-        wp = torch.zeros(cp, kp, dtype=torch.float16)
-        wp[:cout, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).to(torch.float16)
-        bp = torch.zeros(cp, dtype=torch.float32)
-        bp[:cout] = b
-        return wp.numpy().tobytes(), bp.numpy().tobytes()
-    if r.kind in ("dwg", "dwg_plain", "dwg_ext"):
-        # generic depthwise (csrc/bsyolo_ops.hip): f32 [kh*kw][C] + bias [C]
-        kh, kw = r.k, r.kw or r.k
-        if r.kind == "dwg_ext":
-            # PMSFA.conv3 (block.py:3042): a depthwise 7x7 over the first half of its input, extended with an identity
-            # kernel (centre tap 1, bias 0, no activation) so the second half passes through untouched
-            half = r.cout // 2
-            assert tuple(w.shape) == (half, 1, kh, kw), (r.name, tuple(w.shape))
-            ident = torch.zeros(r.cout - half, 1, kh, kw)
-            ident[:, 0, kh // 2, kw // 2] = 1.0
-            w, b = torch.cat([w, ident]), torch.cat([b, torch.zeros(r.cout - half)])
-        assert tuple(w.shape) == (r.cout, 1, kh, kw), (r.name, tuple(w.shape), (r.cout, kh, kw))
-        if r.post:  # a following depthwise 1x1 conv (MSCAAttention.dilconv, MSCA.py:31): y -> a*y + d, folded in
-            a, d = _f32(sd[r.post + ".weight"]).view(-1), _f32(sd[r.post + ".bias"])
-            w, b = w * a.view(-1, 1, 1, 1), a * b + d
-        wp = w.view(r.cout, kh * kw).t().contiguous()
-        return wp.numpy().tobytes(), b.contiguous().numpy().tobytes()
-    if r.kind == "dw":
-        assert tuple(w.shape) == (r.cout, 1, 3, 3), (r.name, tuple(w.shape))
-        wp = w.view(r.cout, 9).t().contiguous()
-        return wp.numpy().tobytes(), b.contiguous().numpy().tobytes()
-    raise ValueError(r.kind)
+    if r.kind == "dwg_ext":
+        # PMSFA.conv3 (block.py:3042): a depthwise 7x7 over the first half of its input, extended with an identity
+        # kernel (centre tap 1, bias 0, no activation) so the second half passes through untouched
+        half = r.cout // 2
+        assert tuple(w.shape) == (half,) + shape[1:], (r.name, tuple(w.shape))
+        ident = torch.zeros(r.cout - half, *shape[1:])
+        ident[:, 0, shape[2] // 2, shape[3] // 2] = 1.0
+        w, b = torch.cat([w, ident]), torch.cat([b, torch.zeros(r.cout - half)])
+    assert tuple(w.shape) == shape, (r.name, tuple(w.shape), shape)
+    if r.perm is not None:  # output-channel permutation (qkv)
+        w, b = _take(w, r.perm), _take(b, r.perm)
+    return w, b
+
+
+def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f32: bool = False, split: bool = False):
+    """-> (weight bytes, bias bytes) for one op: source -> channel step -> layout.  f32: dense convs in the fp32 correctness mode's
+    layout (dense_f32; split, the fp32x mode: followed by the two f16 planes); depthwise / ELA records are f32 in every mode."""
+    w, b = SOURCES[r.kind][1](sd, r, eps)
+    if r.kind == "ela":  # one flat f32 vector as it is read, no bias
+        return _bytes(w), b""
+    w, b = op_channels(r, w, b)
+    if r.kind not in DW_KINDS and f32:
+        mats, bp = dense_f32(w, b, split)
+        return _bytes(*mats), _bytes(bp)
+    wp, bp = depthwise(w, b) if r.kind in DW_KINDS else dense_f16(w, b)
+    return _bytes(wp), _bytes(bp)
 
 
 def pack_plan_weights(plan: Plan, sd: Mapping[str, torch.Tensor], eps: float = BN_EPS) -> bytes:
@@ -220,16 +322,9 @@ def pack_plan_weights(plan: Plan, sd: Mapping[str, torch.Tensor], eps: float = B
     chunks, off = [], 0
     for r in plan.wrecs.values():
         wb, bb = pack_record(sd, r, eps, f32=getattr(plan, "f32_mode", False), split=getattr(plan, "split_f16", False))
-        r.w_off = off
-        chunks.append(wb)
-        pad = _align(len(wb)) - len(wb)
-        chunks.append(b"\0" * pad)
-        off += len(wb) + pad
-        r.b_off = off
-        chunks.append(bb)
-        pad = _align(len(bb)) - len(bb)
-        chunks.append(b"\0" * pad)
-        off += len(bb) + pad
+        r.w_off, r.b_off = off, off + _align(len(wb))
+        chunks += [wb, b"\0" * (_align(len(wb)) - len(wb)), bb, b"\0" * (_align(len(bb)) - len(bb))]
+        off = r.b_off + _align(len(bb))
     return b"".join(chunks)
 
 
@@ -243,75 +338,20 @@ def adopt_offsets(plan: Plan, packed: Plan) -> None:
 
 def synth_state_dict(plan: Plan, seed: int = 0, cls_gain: float = 0.1, cls_bias: float = -4.21) -> Dict[str, torch.Tensor]:
     """Seeded random parameters for benchmarking without a checkpoint (no weights ship with the reference:
-    .MISSING_LARGE_BLOBS).  He-normal conv weights, randomised BN statistics.  The class head is damped (cls_gain) and
+    .MISSING_LARGE_BLOBS): every record's parameters (SOURCES) in the records' order, a module that several records read drawn
+    once.  He-normal conv weights, randomised BN statistics.  The class head is damped (cls_gain) and
     shifted (cls_bias) so that a realistic share of anchors passes conf 0.25: the defaults put 1.5 % of the anchors
     of YOLO11s @640 (seed 0) above 0.25 (SURVEY 8d asks for 1-2 %), i.e. ~126 NMS candidates per image."""
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
     for r in plan.wrecs.values():
-        if r.kind == "deconv":
-            if r.name + ".weight" not in sd:
-                sd[r.name + ".weight"] = torch.randn(r.cin, r.cout, 2, 2, generator=g) * (2.0 / r.cin) ** 0.5
-                sd[r.name + ".bias"] = torch.rand(r.cout, generator=g) * 0.4 - 0.2
-            continue
-        if r.kind == "ela":
-            for s_ in ("ch_weight", "sp_weight", "res_weight"):
-                sd[f"{r.name}.{s_}"] = torch.randn(1, generator=g)
-            sd[r.name + ".spatial_conv.weight"] = torch.randn(r.cout, 1, r.k, generator=g) * (2.0 / r.k) ** 0.5
-            sd[r.name + ".ch_att.2.weight"] = torch.randn(r.cout, 1, r.k, generator=g) * (2.0 / r.k) ** 0.5
-            sd[r.name + ".gn.weight"] = torch.rand(r.cout, generator=g) * 0.6 + 0.7
-            sd[r.name + ".gn.bias"] = torch.rand(r.cout, generator=g) * 0.6 - 0.3
-            continue
-        if r.kind == "dwg_plain":
-            kh, kw = r.k, r.kw or r.k
-            sd[r.name + ".weight"] = torch.randn(r.cout, 1, kh, kw, generator=g) * (2.0 / (kh * kw)) ** 0.5
-            sd[r.name + ".bias"] = torch.rand(r.cout, generator=g) * 0.4 - 0.2
-            if r.post and r.post + ".weight" not in sd:
-                sd[r.post + ".weight"] = torch.rand(r.cout, 1, 1, 1, generator=g) + 0.5
-                sd[r.post + ".bias"] = torch.rand(r.cout, generator=g) * 0.4 - 0.2
-            continue
-        if r.kind in ("dwg", "dwg_ext"):
-            kh, kw = r.k, r.kw or r.k
-            co = r.real_cout or (r.cout // 2 if r.kind == "dwg_ext" else r.cout)
-            sd[r.name + ".conv.weight"] = torch.randn(co, 1, kh, kw, generator=g) * (2.0 / (kh * kw)) ** 0.5
-            sd[r.name + ".bn.weight"] = torch.rand(co, generator=g) * 0.6 + 0.7
-            sd[r.name + ".bn.bias"] = torch.rand(co, generator=g) * 0.6 - 0.3
-            sd[r.name + ".bn.running_mean"] = torch.rand(co, generator=g) * 0.6 - 0.3
-            sd[r.name + ".bn.running_var"] = torch.rand(co, generator=g) + 0.5
-            continue
-        if r.kind == "plain":
-            rci = r.real_cin or r.cin
-            fan = rci * r.k * r.k
-            sd[r.name + ".weight"] = torch.randn(r.real_cout or r.cout, rci, r.k, r.k, generator=g) * (2.0 / fan) ** 0.5
-            if ".cv3." in r.name:
-                sd[r.name + ".weight"] *= cls_gain
-                sd[r.name + ".bias"] = torch.full((r.real_cout or r.cout,), float(cls_bias))
-            elif ".cv2." in r.name:
-                sd[r.name + ".bias"] = torch.rand(r.cout, generator=g) + 0.5
+        for key, shape, draw in SOURCES[r.kind][0](r):
+            if key in sd:
+                continue
+            if r.kind == "plain" and ".cv3." in r.name:  # Detect's class branch: damped weights, a constant bias (nothing drawn)
+                sd[key] = draw(g, shape) * cls_gain if key.endswith(".weight") else torch.full(shape, float(cls_bias))
+            elif r.kind == "plain" and ".cv2." in r.name and key.endswith(".bias"):  # the box branch
+                sd[key] = torch.rand(*shape, generator=g) + 0.5
             else:
-                sd[r.name + ".bias"] = torch.rand(r.real_cout or r.cout, generator=g) * 0.4 - 0.2
-            continue
-        cin = 1 if r.kind == "dw" else (r.real_cin or r.cin)
-        fan = cin * r.k * r.k
-        if r.kind == "refconv":  # block.py:793-816: a buffer `weight` and the per-kernel 3x3 map over it
-            co = r.real_cout or r.cout
-            sd[r.name + ".weight"] = torch.randn(co, cin, r.k, r.k, generator=g) * (2.0 / fan) ** 0.5
-            sd[r.name + ".convmap.weight"] = torch.randn(co * cin, 1, 3, 3, generator=g) * (2.0 / 9) ** 0.5 * 0.25
-            continue
-        if r.kind == "repvgg":  # conv.py:296-397, un-fused: a 3x3 and a 1x1 Conv + BN
-            co = r.real_cout or r.cout
-            for nm, kk in ((r.name + ".conv1", 3), (r.name + ".conv2", 1)):
-                sd[nm + ".conv.weight"] = torch.randn(co, cin, kk, kk, generator=g) * (2.0 / (cin * kk * kk)) ** 0.5
-                sd[nm + ".bn.weight"] = torch.rand(co, generator=g) * 0.6 + 0.7
-                sd[nm + ".bn.bias"] = torch.rand(co, generator=g) * 0.6 - 0.3
-                sd[nm + ".bn.running_mean"] = torch.rand(co, generator=g) * 0.6 - 0.3
-                sd[nm + ".bn.running_var"] = torch.rand(co, generator=g) + 0.5
-            continue
-        # kind "conv2": two modules of half the width each, drawn in the order the unmerged plan draws them
-        for nm, co in (((r.name, (r.real_cout or r.cout) // 2), (r.post, (r.real_cout or r.cout) // 2)) if r.kind == "conv2" else ((r.name, r.real_cout or r.cout),)):
-            sd[nm + ".conv.weight"] = torch.randn(co, cin, r.k, r.k, generator=g) * (2.0 / fan) ** 0.5
-            sd[nm + ".bn.weight"] = torch.rand(co, generator=g) * 0.6 + 0.7
-            sd[nm + ".bn.bias"] = torch.rand(co, generator=g) * 0.6 - 0.3
-            sd[nm + ".bn.running_mean"] = torch.rand(co, generator=g) * 0.6 - 0.3
-            sd[nm + ".bn.running_var"] = torch.rand(co, generator=g) + 0.5
+                sd[key] = draw(g, shape)
     return sd

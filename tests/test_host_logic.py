@@ -17,7 +17,7 @@ from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.letterbox import LetterBox
 from bs_yolo_amd.parallel import shard_bounds
 from bs_yolo_amd.plan import Plan
-from bs_yolo_amd.weights import fold_conv_bn, pack_plan_weights, pack_record, synth_state_dict
+from bs_yolo_amd.weights import fold_conv_bn, pack_plan_weights, pack_record, record_keys, synth_state_dict
 from oracle import yolo_ref as R
 
 
@@ -263,19 +263,7 @@ def test_plan_consumes_exactly_the_reference_parameters():
         p = Plan(stock_cfg(fam, scale), 2, 96, 64)
         m = R.Model(fam, scale, 80, "detect")
         want = {n for n, _ in m.param_specs() if not n.endswith("dfl.conv.weight")}
-        used = set()
-        for r in p.wrecs.values():
-            if r.kind in ("plain", "dwg_plain"):
-                used |= {r.name + ".weight", r.name + ".bias"}
-                if r.post:
-                    used |= {r.post + ".weight", r.post + ".bias"}
-            elif r.kind == "ela":
-                used |= {f"{r.name}.{s}" for s in ("ch_weight", "sp_weight", "res_weight", "ch_att.2.weight",
-                                                   "spatial_conv.weight", "gn.weight", "gn.bias")}
-            else:
-                for nm in ((r.name, r.post) if r.kind == "conv2" else (r.name,)):
-                    used |= {nm + ".conv.weight"} | {f"{nm}.bn.{s}" for s in ("weight", "bias", "running_mean", "running_var")}
-        assert used == want
+        assert {k for r in p.wrecs.values() for k in record_keys(r)} == want
         # every view stays inside its buffer and respects the kernels' alignment rules
         for o in p.ops:
             for key in ("src0", "src1", "dst", "res"):
@@ -302,14 +290,7 @@ def test_c2f_chunks_that_are_not_multiples_of_8_are_zero_padded_pieces(fam, widt
         p = Plan(cfg, 2, 96, 64)
         m = R.Model(fam, "t", 80, "detect")
         want = {n for n, _ in m.param_specs() if not n.endswith("dfl.conv.weight")}
-        used = set()
-        for r in p.wrecs.values():
-            if r.kind == "plain":
-                used |= {r.name + ".weight", r.name + ".bias"}
-            else:
-                for nm in ((r.name, r.post) if r.kind == "conv2" else (r.name,)):
-                    used |= {nm + ".conv.weight"} | {f"{nm}.bn.{s}" for s in ("weight", "bias", "running_mean", "running_var")}
-        assert used == want
+        assert {k for r in p.wrecs.values() for k in record_keys(r)} == want
         sd = synth_state_dict(p, 3)
         for n_, shape in m.param_specs():  # the synthetic parameters have the MODULE's shapes, not the padded ops'
             if n_ in sd:
@@ -393,13 +374,7 @@ def test_segment_plan_matches_reference_work():
     assert p.meta["proto_hw"] == (160, 160) and p.meta["nm"] == 32 and p.meta["A"] == 8400
     m = R.Model("yolov8", "l", 80, "segment")
     want = {n for n, _ in m.param_specs() if not n.endswith("dfl.conv.weight")}
-    used = set()
-    for r in p.wrecs.values():
-        if r.kind in ("plain", "deconv"):
-            used |= {r.name + ".weight", r.name + ".bias"}
-        else:
-            used |= {r.name + ".conv.weight"} | {f"{r.name}.bn.{s}" for s in ("weight", "bias", "running_mean", "running_var")}
-    assert used == want
+    assert {k for r in p.wrecs.values() for k in record_keys(r)} == want
 
 
 def test_fold_matches_reference_known_answer():
@@ -456,6 +431,106 @@ def test_pack_blob_offsets_are_aligned_and_disjoint():
         assert r.w_off % 256 == 0 and r.b_off % 256 == 0 and 0 <= r.w_off < r.b_off < len(blob)
         spans.append((r.w_off, r.b_off))
     assert spans == sorted(spans)
+
+
+# ---- the device layouts and the channel step of weights.py, element by element against expectations written here -------------------
+def test_dense_f16_layout_element_by_element():
+    """fp16 [CoutPad][Kpad] with K order (kh, kw, cin) and zero padding; an image conv gets a zero 4th input channel; the padded dims
+    are the library's (bsy_conv_packed_dims)."""
+    import ctypes as C
+    from bs_yolo_amd.weights import dense_f16
+    cout, cin, k = 5, 8, 3
+    w = torch.arange(cout * cin * k * k, dtype=torch.float32).view(cout, cin, k, k)  # integers below 2048: exact in fp16
+    b = torch.arange(cout, dtype=torch.float32) + 0.5
+    wp, bp = dense_f16(w, b)
+    assert wp.dtype == torch.float16 and tuple(wp.shape) == (128, 96) and bp.dtype == torch.float32 and tuple(bp.shape) == (128,)
+    for co in range(cout):
+        for kh in range(k):
+            for kw in range(k):
+                for ci in range(cin):
+                    assert float(wp[co, (kh * 3 + kw) * cin + ci]) == float(w[co, ci, kh, kw])
+    assert torch.all(wp[cout:] == 0) and torch.all(wp[:, k * k * cin:] == 0)
+    assert torch.equal(bp[:cout], b) and torch.all(bp[cout:] == 0)
+    w3 = 1 + torch.arange(cout * 3 * k * k, dtype=torch.float32).view(cout, 3, k, k)  # the image case: cin 3 -> 4
+    wp, bp = dense_f16(w3)
+    assert tuple(wp.shape) == (128, 64) and torch.all(bp == 0)
+    for co in range(cout):
+        for tap in range(k * k):
+            for ci in range(4):
+                assert float(wp[co, tap * 4 + ci]) == (float(w3[co, ci, tap // 3, tap % 3]) if ci < 3 else 0.0)
+    assert torch.all(wp[cout:] == 0) and torch.all(wp[:, k * k * 4:] == 0)
+    cp, kp = C.c_int(), C.c_int()
+    for c2 in (5, 128, 129):
+        for c1 in (3, 8, 40):
+            for kk in (1, 3):
+                assert L.lib.bsy_conv_packed_dims(c2, c1, kk, C.byref(cp), C.byref(kp)) == 0
+                wp, bp = dense_f16(torch.zeros(c2, c1, kk, kk))
+                assert tuple(wp.shape) == (cp.value, kp.value) and tuple(bp.shape) == (cp.value,), (c2, c1, kk)
+
+
+def test_dense_f32_and_split_layout_element_by_element():
+    """f32 [K][Cout], K order (kh, kw, cin), bias as it is; the fp32x mode's f16 planes hi + lo give w back to 2^-22 relative -- hi
+    keeps 11 bits, lo 11 more of the exact remainder, and with |w| >= 2^-3 lo stays clear of the f16 subnormals' absolute 2^-25 --
+    and sit in the record where csrc/op_args.h build_conv32 looks for them: each part padded to 256 bytes."""
+    from bs_yolo_amd.plan import WRec
+    from bs_yolo_amd.weights import dense_f32
+    g = torch.Generator().manual_seed(5)
+    cout, cin, k = 5, 8, 3
+    K = k * k * cin
+    w = (0.125 + 3.875 * torch.rand(cout, cin, k, k, generator=g)) * (1 - 2 * torch.randint(0, 2, (cout, cin, k, k), generator=g))
+    b = torch.randn(cout, generator=g)
+    (m,), bb = dense_f32(w, b)
+    assert m.dtype == torch.float32 and tuple(m.shape) == (K, cout) and torch.equal(bb, b)
+    for co in range(cout):
+        for kh in range(k):
+            for kw in range(k):
+                for ci in range(cin):
+                    assert float(m[(kh * 3 + kw) * cin + ci, co]) == float(w[co, ci, kh, kw])
+    (m2, hi, lo), _ = dense_f32(w, b, split=True)
+    assert torch.equal(m2, m) and hi.dtype == lo.dtype == torch.float16 and tuple(hi.shape) == tuple(lo.shape) == (cout, 96)
+    assert torch.all(hi[:, K:] == 0) and torch.all(lo[:, K:] == 0)
+    for co in range(cout):
+        for kk in range(K):
+            want = float(w[co, kk % cin, kk // cin // 3, kk // cin % 3])
+            assert abs(float(hi[co, kk]) + float(lo[co, kk]) - want) <= 2.0 ** -22 * abs(want)
+    wb, bias = pack_record({"c.weight": w, "c.bias": b}, WRec("c", "plain", cout, cin, k), f32=True, split=True)
+    align256 = lambda n: (n + 255) // 256 * 256  # noqa: E731
+    hi_off = align256(K * cout * 4)  # op_args.h: hi_off = align256(K * Cout * 4), lo_off = hi_off + align256(Cout * kpad * 2)
+    lo_off = hi_off + align256(cout * 96 * 2)
+    assert (hi_off, lo_off, len(wb)) == (1536, 2560, 2560 + cout * 96 * 2)
+    assert wb[:K * cout * 4] == m.numpy().tobytes() and wb[hi_off:hi_off + cout * 96 * 2] == hi.numpy().tobytes()
+    assert wb[lo_off:] == lo.numpy().tobytes() and bias == b.numpy().tobytes()
+
+
+def test_depthwise_layout_element_by_element():
+    """f32 [kh*kw][C], taps in (kh, kw) order, channels adjacent: a 3x3 and a 1x5 strip."""
+    from bs_yolo_amd.weights import depthwise
+    g = torch.Generator().manual_seed(6)
+    for kh, kw in ((3, 3), (1, 5)):
+        w, b = torch.randn(8, 1, kh, kw, generator=g), torch.randn(8, generator=g)
+        wp, bp = depthwise(w, b)
+        assert wp.dtype == torch.float32 and tuple(wp.shape) == (kh * kw, 8) and wp.is_contiguous() and torch.equal(bp, b)
+        for c in range(8):
+            for i in range(kh):
+                for j in range(kw):
+                    assert float(wp[i * kw + j, c]) == float(w[c, 0, i, j])
+
+
+def test_channel_step_puts_zero_rows_columns_and_biases_where_the_maps_say():
+    from bs_yolo_amd.plan import WRec
+    from bs_yolo_amd.weights import op_channels
+    g = torch.Generator().manual_seed(7)
+    w, b = torch.randn(3, 5, 3, 3, generator=g), torch.randn(3, generator=g)
+    rows, cols = [2, -1, 0, 1], [-1, 4, 0, 1, 2, 3]
+    w2, b2 = op_channels(WRec("c", "conv", 4, 6, 3, rows=rows, cols=cols), w, b)
+    assert tuple(w2.shape) == (4, 6, 3, 3) and tuple(b2.shape) == (4,)
+    for i, ri in enumerate(rows):
+        assert float(b2[i]) == (float(b[ri]) if ri >= 0 else 0.0)
+        for j, cj in enumerate(cols):
+            assert torch.equal(w2[i, j], w[ri, cj] if ri >= 0 and cj >= 0 else torch.zeros(3, 3)), (i, j)
+    w2, b2 = op_channels(WRec("c", "conv", 8, 8, 3, real_cout=3, real_cin=5), w, b)
+    assert tuple(w2.shape) == (8, 8, 3, 3) and torch.equal(w2[:3, :5], w) and torch.equal(b2[:3], b)
+    assert torch.all(w2[3:] == 0) and torch.all(w2[:, 5:] == 0) and torch.all(b2[3:] == 0)
 
 
 def test_letterbox_geometry_matches_reference_golden():

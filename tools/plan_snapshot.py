@@ -2,7 +2,8 @@
 the regression fixture of host-side refactors of bs_yolo_amd/plan.py (tests/test_host_logic.py, tests/golden/plan_snapshots.json).
 
     python tools/plan_snapshot.py                   print "<case> <ops> <digest>" per case and compare with the fixture
-    python tools/plan_snapshot.py --dump DIR        also write every case's plain-text form to DIR/<case>.txt (diff two commits' DIRs)
+    python tools/plan_snapshot.py --dump DIR        also write every case's plain-text form to DIR/<case>.txt (diff two commits' DIRs);
+                                                    there every case packs, in its precision's layout: see "host:" below
     python tools/plan_snapshot.py --write           rewrite the fixture -- ONLY at a commit whose plans are known to be right
 
 A snapshot is the sha256 of the text that --dump writes: the serialised op array (after packing synthetic weights, or with running
@@ -10,7 +11,9 @@ record offsets where a case is not packed), buffer sizes, flops, meta, layer out
 (name, mfma_flops, cout, weight keys), both arena layouts and the autotuner's conv signatures.  Lines that begin with "host:" are
 written but not hashed: the packed blob's sha256 and ELA's exact coefficients come out of torch's CPU kernels (randn, sigmoid), whose
 last bits differ from one CPU to the next, so they compare between two commits on ONE machine only; the digest holds the blob's
-length, every record's offsets and the coefficients to four decimals.  Needs no GPU."""
+length, every record's offsets and the coefficients to four decimals.  A case whose digest is taken with running offsets gets its
+packed blob's length, sha256 and coefficients as "host:" lines in a dump (packed from a second plan, so the hashed text stays as it is):
+two commits' dumps then compare the weight bytes of every case, fp32 and fp32x layouts included.  Needs no GPU."""
 import dataclasses
 import hashlib
 import json
@@ -88,18 +91,25 @@ def _t(t):
     return f"({t.buf},{t.ld},{t.coff},{t.C},{t.H},{t.W},{int(t.up)},{int(t.f32)},{t.cmap})"
 
 
-def snapshot_text(plan, pack):
-    """The plain-text form of one plan (see the module docstring)."""
+def _packed(plan):
+    """Packs synthetic weights into `plan` -> (blob length, the "host:" lines of the blob's sha256 and ELA's exact coefficients)."""
+    blob = pack_plan_weights(plan, synth_state_dict(plan))
+    return len(blob), [f"host: blob {hashlib.sha256(blob).hexdigest()}"] + [f"host: coef {k} {r.coef}" for k, r in plan.wrecs.items() if r.kind == "ela"]
+
+
+def snapshot_text(plan, pack, host_plan=None):
+    """The plain-text form of one plan (see the module docstring).  host_plan: a second plan of an unpacked case, packed for its
+    "host:" lines."""
     lines = []
     if pack:
-        blob = pack_plan_weights(plan, synth_state_dict(plan))
-        lines.append(f"blob {len(blob)} bytes")
-        lines.append(f"host: blob {hashlib.sha256(blob).hexdigest()}")
-        for k, r in plan.wrecs.items():
-            if r.kind == "ela":
-                lines.append(f"host: coef {k} {r.coef}")
-                r.coef = tuple(round(c, 4) for c in r.coef)
+        n, host = _packed(plan)
+        lines += [f"blob {n} bytes"] + host
+        for r in plan.wrecs.values():
+            r.coef = tuple(round(c, 4) for c in r.coef)
     else:
+        if host_plan is not None:
+            n, host = _packed(host_plan)
+            lines += [f"host: blob {n} bytes"] + host
         for i, r in enumerate(plan.wrecs.values()):
             r.w_off, r.b_off = 512 * i, 512 * i + 256
     raw = bytes(plan.c_ops())
@@ -117,9 +127,9 @@ def snapshot_text(plan, pack):
     return "\n".join(lines) + "\n"
 
 
-def snapshot(build, pack):
+def snapshot(build, pack, host=False):
     plan = build()
-    text = snapshot_text(plan, pack)
+    text = snapshot_text(plan, pack, build() if host and not pack else None)
     hashed = "".join(ln for ln in text.splitlines(True) if not ln.startswith("host:"))
     return {"digest": hashlib.sha256(hashed.encode()).hexdigest(), "ops": len(plan.ops)}, text
 
@@ -132,7 +142,7 @@ def main(argv):
     have = json.loads(FIXTURE.read_text()) if FIXTURE.exists() else {}
     got, bad = {}, []
     for cid, build, pack in cases():
-        got[cid], text = snapshot(build, pack)
+        got[cid], text = snapshot(build, pack, host=dump is not None)
         if dump:
             (dump / (cid.replace("/", "__") + ".txt")).write_text(text)
         if have and have.get(cid) != got[cid]:
