@@ -33,6 +33,7 @@ SOURCES = {
     "c3k2_fused.hip": [],
     "bsyolo_ops.hip": [],
     "pmsfa_fused.hip": [],
+    "ghost_fused.hip": [],
     "elementwise.hip": [],
     "pool_down.hip": ["-ffp-contract=off"],  # the average must round like ATen's: ordered fp32 sum, one product, one rounding
     "attention.hip": [],

@@ -7,6 +7,7 @@
 //   gap_kernel            : per (image, channel) mean over H x W                  (MSCA.py:69-72, ELA.py:50)
 //   msca_mix_kernel       : softmax_i(sigmoid(l_i)) weighted sum of the four branch maps   (MSCA.py:74-82)
 //   mul_kernel            : elementwise product of two maps                        (MSCA.py:86 `attn * u`)
+//   add_kernel            : elementwise sum of two maps                            (block.py:3402 GhostBottleneck's shortcut)
 //   ela_stats / ela_gate / ela_apply : ELA (nn/Addmodules/ELA.py:77-101)
 // All NHWC f16 channel-slice views (8-channel = 16-byte pieces); reductions and gates in f32.  These layers are a few
 // percent of the BS-YOLO forward; the kernels are written for clarity and coalescing, not tuned.
@@ -684,6 +685,30 @@ int launch_mul(const half_t* a, int lda, const half_t* b, int ldb, long long npi
         BSY_FAIL(BSY_ERR_ARG, "mul: bad layout");
     const long long total = npix * (C / 8);
     hipLaunchKernelGGL(mul_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, lda, b, ldb, npix, C, dst, ldd);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}
+
+// dst = a + b (GhostBottleneck's shortcut where the GhostConv runs as separate launches): the sum in f32, rounded once.  dst may be a's view
+// (no __restrict__): a thread reads its 16-byte pieces before it writes the one at the same place, and no other thread touches it.
+__global__ __launch_bounds__(256) void add_kernel(const half_t* a, int lda, const half_t* b, int ldb, long long npix, int C, half_t* dst, int ldd) {
+    const int C8 = C >> 3;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npix * C8) return;
+    const int c = (int)(idx % C8) * 8;
+    const long long pix = idx / C8;
+    const half8 x = *reinterpret_cast<const half8*>(a + (size_t)pix * lda + c), y = *reinterpret_cast<const half8*>(b + (size_t)pix * ldb + c);
+    half8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)x[j] + (float)y[j]);
+    *reinterpret_cast<half8*>(dst + (size_t)pix * ldd + c) = o;
+}
+
+int launch_add(const half_t* a, int lda, const half_t* b, int ldb, long long npix, int C, half_t* dst, int ldd, hipStream_t s) {
+    if (!a || !b || !dst || (C & 7) || C <= 0 || (lda & 7) || (ldb & 7) || (ldd & 7) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)dst) & 15) || npix <= 0)
+        BSY_FAIL(BSY_ERR_ARG, "add: bad layout");
+    const long long total = npix * (C / 8);
+    hipLaunchKernelGGL(add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, lda, b, ldb, npix, C, dst, ldd);
     HIP_TRY(hipGetLastError());
     return BSY_OK;
 }

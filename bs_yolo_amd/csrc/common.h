@@ -135,6 +135,24 @@ struct C3k2Args {
 bool c3k2_fused_supported(int Cin, int C, int C2);
 int launch_c3k2_fused(const C3k2Args& a, hipStream_t s);
 
+// GhostConv with a 1x1 stride-1 cv1 (ghost_fused.hip): dst = [y | z] (+ res), y = act(cv1 x), z = act(cv2 y), cv2 depthwise 5x5; y only on chip
+// between the two convs.
+struct GhostArgs {
+    const half_t* src = nullptr;  // (B,H,W,lds) view of Cin channels
+    int lds = 0;
+    int B = 0, H = 0, W = 0, Cin = 0, CH = 0;  // CH = hidden width: cv1 Cin -> CH, cv2 depthwise on CH, dst / res 2 CH channels
+    const half_t* w1 = nullptr;  // cv1: packed f16 [CoutPad][Kpad]
+    const float* b1 = nullptr;
+    const float* w2 = nullptr;   // cv2: f32 [25][CH]
+    const float* b2 = nullptr;   // f32 [CH]
+    half_t* dst = nullptr;
+    int ldd = 0, act = 0;
+    const half_t* res = nullptr;  // shortcut operand (2 CH channels) or nullptr; may be dst's view
+    int ldr = 0;
+};
+bool ghost_fused_supported(int Cin, int CH);
+int launch_ghost_fused(const GhostArgs& a, hipStream_t s);
+
 // ---- BS-YOLO-only modules (bsyolo_ops.hip) ----------------------------------------------------------------------------
 struct DwGenArgs {       // depthwise kh x kw, stride 1 / 2, "same" padding, + bias (+SiLU)
     const half_t* src = nullptr;
@@ -194,6 +212,7 @@ struct MixArgs {
 };
 int launch_msca_mix(const MixArgs& a, hipStream_t s);
 int launch_mul(const half_t* a, int lda, const half_t* b, int ldb, long long npix, int C, half_t* dst, int ldd, hipStream_t s);
+int launch_add(const half_t* a, int lda, const half_t* b, int ldb, long long npix, int C, half_t* dst, int ldd, hipStream_t s);  // dst may be a
 struct ElaArgs {
     const half_t* src = nullptr;
     int lds = 0;
@@ -265,6 +284,7 @@ int launch_nhwc2nchw32(const float* src, int ld, int B, int C, int hw, void* out
 int launch_copy32(const float* src, int lds_, int up, int B, int H, int W, int C, float* dst, int ldd, hipStream_t s);
 int launch_gap32(const float* src, int lds_, int B, int H, int W, int C, float* out, int ldo, hipStream_t s);
 int launch_mul32(const float* x, int ldx, const float* y, int ldy, long long npix, int C, float* dst, int ldd, hipStream_t s);
+int launch_add32(const float* x, int ldx, const float* y, int ldy, long long npix, int C, float* dst, int ldd, hipStream_t s);  // dst may be x
 int launch_ela32(const ElaArgs& a, const float* src, float* dst, hipStream_t s);  // a.src / a.dst unused
 
 // Fused DWConv 3x3 (+SiLU) -> Conv 1x1 (+act) (dwpw_fused.hip: dwpw_fused_kernel)

@@ -23,6 +23,15 @@ __device__ __forceinline__ void stage_rows(half_t* dst, const half_t* src, int k
     }
 }
 
+// The same where the shape is known at launch only (ghost_fused.hip: one instantiation per accumulator count serves every width).
+template <int NT>
+__device__ __forceinline__ void stage_rows(half_t* dst, const half_t* src, int kpad, int tid, int rows, int chunks, int pitch) {
+    for (int i = tid; i < rows * chunks; i += NT) {
+        const int row = i / chunks, ch = i - row * chunks;
+        *reinterpret_cast<half8*>(dst + row * pitch + ch * 8) = *reinterpret_cast<const half8*>(src + (size_t)row * kpad + ch * 8);
+    }
+}
+
 // ---- epilogues --------------------------------------------------------------------------------------------------------------------
 // Group g of an accumulator tile: couts 8g + 4lh .. + 3 of this lane's pixel
 __device__ __forceinline__ f32x4 acc_group(const f32x16& acc, int g) {

@@ -70,7 +70,7 @@ inline void dwg_fields(Args& a, const bsy_op& op, const char* wb) {
     a.w = (const float*)(wb + op.w_off) + op.key_dim; a.b = (const float*)(wb + op.b_off) + op.key_dim;
     a.act_c = op.act;
 }
-// Ops whose launchers take scalars (SPPF_POOL, COPY, GAP, fp32 ATTN, MUL): only their views are resolved, the first n of src0 (the
+// Ops whose launchers take scalars (SPPF_POOL, COPY, GAP, fp32 ATTN, MUL, ADD): only their views are resolved, the first n of src0 (the
 // buffer SPPF_POOL works in), dst, src1.  T = the storage type.
 template <typename T>
 struct Views {
@@ -244,6 +244,21 @@ inline bool build_dwpw(DwPwArgs& a, const bsy_op& op, Resolver& R, const char* w
     a.dww = (const float*)(wb + op.w_off); a.dwb = (const float*)(wb + op.b_off);
     a.wgt = (const void*)(wb + op.w2_off); a.bias = (const float*)(wb + op.b2_off);
     a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.Cout = op.dst.C; a.act = op.act;
+    return R.ok;
+}
+// GHOST: mid_c = the hidden width CH (dst and res are [y | z], 2 CH channels); (w, b) = cv1 packed 1x1, (w2, b2) = cv2 depthwise f32 [25][CH];
+// ksize / stride / pad describe cv2 and are fixed
+inline bool build_ghost(GhostArgs& a, const bsy_op& op, Resolver& R, const char* wb) {
+    a.src = R.h(op.src0); a.lds = op.src0.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.src0.C; a.CH = op.mid_c;
+    a.w1 = (const half_t*)(wb + op.w_off); a.b1 = (const float*)(wb + op.b_off);
+    a.w2 = (const float*)(wb + op.w2_off); a.b2 = (const float*)(wb + op.b2_off);
+    a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.act = op.act;
+    a.res = R.h(op.res); a.ldr = op.res.buf >= 0 ? op.res.ld : 0;
+    if (R.ok && (op.dst.C != 2 * op.mid_c || (op.res.buf >= 0 && op.res.C != op.dst.C) || op.ksize != 5 || op.stride != 1 || op.pad != 2 || op.up0 ||
+                 op.OH != op.H || op.OW != op.W)) {
+        R.ok = false;
+        bsy_set_error("ghost: dst (%d) and res must have 2 x mid_c (%d) channels, cv2 is 5x5 stride 1 pad 2 on the source's extent", op.dst.C, op.mid_c);
+    }
     return R.ok;
 }
 inline bool build_dwconv_g(DwGenArgs& a, const bsy_op& op, Resolver& R, const char* wb) {

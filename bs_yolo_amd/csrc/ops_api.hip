@@ -172,6 +172,7 @@ extern "C" int bsy_dwpw_fused_supported(int C, int C2) { return dwpw_fused_suppo
 extern "C" int bsy_attention_supported(int key_dim, int head_dim) { return attention_supported(key_dim, head_dim) ? 1 : 0; }
 extern "C" int bsy_pmsfa_tail_supported(int C) { return pmsfa_tail_supported(C) ? 1 : 0; }
 extern "C" int bsy_msca_spatial_supported(int H, int W) { return msca_spatial_supported(H, W) ? 1 : 0; }
+extern "C" int bsy_ghost_fused_supported(int Cin, int CH) { return ghost_fused_supported(Cin, CH) ? 1 : 0; }
 
 extern "C" int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* b, void* y,
                              int ldy, int act, const void* res, int ldr, bsy_stream stream) {

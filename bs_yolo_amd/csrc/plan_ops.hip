@@ -54,6 +54,9 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
         case BSY_OP_MUL:
             if (!build_views(v32, op, R, 3)) return BSY_ERR_ARG;
             return launch_mul32(v32.src0, op.src0.ld, v32.src1, op.src1.ld, (long long)op.B * op.H * op.W, op.dst.C, v32.dst, op.dst.ld, s);
+        case BSY_OP_ADD:
+            if (!build_views(v32, op, R, 3)) return BSY_ERR_ARG;
+            return launch_add32(v32.src0, op.src0.ld, v32.src1, op.src1.ld, (long long)op.B * op.H * op.W, op.dst.C, v32.dst, op.dst.ld, s);
         case BSY_OP_ELA: {
             ElaArgs a;
             const float* src;
@@ -77,6 +80,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
         case BSY_OP_DWPW: return run(build_dwpw, launch_dwpw_fused, op, R, wb, s);
         case BSY_OP_DWCONV_G: return run(build_dwconv_g, launch_dwconv_generic, op, R, wb, s);
         case BSY_OP_PMSFA_TAIL: return run(build_pmsfa_tail, launch_pmsfa_tail, op, R, wb, s);
+        case BSY_OP_GHOST: return run(build_ghost, launch_ghost_fused, op, R, wb, s);
         case BSY_OP_MSCA_SPATIAL: return run(build_msca_spatial, launch_msca_spatial, op, R, wb, s);
         case BSY_OP_MSCA_MIX: return run(build_mix<half_t, MixArgs>, launch_msca_mix, op, R, wb, s);
         case BSY_OP_ELA: return run(build_ela, launch_ela, op, R, wb, s);
@@ -100,6 +104,9 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
         case BSY_OP_MUL:
             if (!build_views(v, op, R, 3)) return BSY_ERR_ARG;
             return launch_mul(v.src0, op.src0.ld, v.src1, op.src1.ld, (long long)op.B * op.H * op.W, op.dst.C, v.dst, op.dst.ld, s);
+        case BSY_OP_ADD:
+            if (!build_views(v, op, R, 3)) return BSY_ERR_ARG;
+            return launch_add(v.src0, op.src0.ld, v.src1, op.src1.ld, (long long)op.B * op.H * op.W, op.dst.C, v.dst, op.dst.ld, s);
         case BSY_OP_SPPF_POOL:
             return build_views(v, op, R, 1) ? launch_sppf_pool(v.src0, op.src0.ld, op.B, op.H, op.W, op.src0.C, s) : BSY_ERR_ARG;
         case BSY_OP_POOL_DOWN: {  // f16 views, f32 in the fp32-storage modes

@@ -445,6 +445,15 @@ __global__ __launch_bounds__(256) void mul32_kernel(const float* x, int ldx, con
     dst[(size_t)pix * ldd + c] = x[(size_t)pix * ldx + c] * y[(size_t)pix * ldy + c];
 }
 
+// dst = x + y (GhostBottleneck's shortcut, block.py:3400-3402); dst may be x: every element is read before it is written, by one thread
+__global__ __launch_bounds__(256) void add32_kernel(const float* x, int ldx, const float* y, int ldy, long long npix, int C, float* dst, int ldd) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= npix * C) return;
+    const int c = (int)(idx % C);
+    const long long pix = idx / C;
+    dst[(size_t)pix * ldd + c] = x[(size_t)pix * ldx + c] + y[(size_t)pix * ldy + c];
+}
+
 // ELA row / column means into the scratch layout of bsyolo_ops.hip (the gate kernel there is f32 already and is reused)
 __global__ __launch_bounds__(256) void ela_stats32_kernel(const float* src, int lds_, int H, int W, int C, float* scratch, size_t per_img) {
     const int n = blockIdx.y, dir = blockIdx.z;
@@ -582,6 +591,13 @@ int launch_mix32(const Mix32Args& a, hipStream_t s) {
 int launch_mul32(const float* x, int ldx, const float* y, int ldy, long long npix, int C, float* dst, int ldd, hipStream_t s) {
     if (!x || !y || !dst) BSY_FAIL(BSY_ERR_ARG, "mul32: null pointer");
     hipLaunchKernelGGL(mul32_kernel, dim3(nblk(npix * C)), dim3(256), 0, s, x, ldx, y, ldy, npix, C, dst, ldd);
+    HIP_TRY(hipGetLastError());
+    return BSY_OK;
+}
+
+int launch_add32(const float* x, int ldx, const float* y, int ldy, long long npix, int C, float* dst, int ldd, hipStream_t s) {
+    if (!x || !y || !dst || npix <= 0 || C <= 0) BSY_FAIL(BSY_ERR_ARG, "add32: bad argument");
+    hipLaunchKernelGGL(add32_kernel, dim3(nblk(npix * C)), dim3(256), 0, s, x, ldx, y, ldy, npix, C, dst, ldd);
     HIP_TRY(hipGetLastError());
     return BSY_OK;
 }

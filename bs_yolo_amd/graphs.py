@@ -7,7 +7,9 @@ v5/yolov5-p6.yaml (families "yolov8-p2", "yolov8-p6", "yolov5-p6"), and the YOLO
 yolov9c-seg.yaml (family "yolov9": literal widths per size, no scales table), and the classification graphs
 cfg/models/11/yolo11-cls.yaml:8-30 and v8/yolov8-cls.yaml:8-29 (task "classify" of the families "yolo11" and "yolov8"), and the pose
 graphs cfg/models/11/yolo11-pose.yaml, v8/yolov8-pose.yaml and v8/yolov8-pose-p6.yaml: the detect graphs of "yolo11", "yolov8" and
-"yolov8-p6" under a Pose head, with a top-level `kpt_shape` (task "pose").  They are
+"yolov8-p6" under a Pose head, with a top-level `kpt_shape` (task "pose"), and the ghost graphs cfg/models/v8/yolov8-ghost.yaml,
+yolov8-ghost-p2.yaml and yolov8-ghost-p6.yaml (families "yolov8-ghost", "yolov8-ghost-p2", "yolov8-ghost-p6": GhostConv downsamplers and
+C3Ghost blocks on the YOLOv8 layouts, detect only).  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -152,6 +154,59 @@ _YOLOV5_P6 = {
     "detect_from": [23, 26, 29, 32],
 }
 
+# YOLOv8-ghost, cfg/models/v8/yolov8-ghost.yaml:15-47: the YOLOv8 layout with a GhostConv for every stride-2 Conv behind the stem and a C3Ghost
+# for every C2f; the scales table is YOLOv8's
+_YOLOV8_GHOST = {
+    "scales": _YOLOV8["scales"],
+    "backbone": [
+        [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "GhostConv", [128, 3, 2]], [-1, 3, "C3Ghost", [128, True]],
+        [-1, 1, "GhostConv", [256, 3, 2]], [-1, 6, "C3Ghost", [256, True]], [-1, 1, "GhostConv", [512, 3, 2]],
+        [-1, 6, "C3Ghost", [512, True]], [-1, 1, "GhostConv", [1024, 3, 2]], [-1, 3, "C3Ghost", [1024, True]],
+        [-1, 1, "SPPF", [1024, 5]],
+    ],
+    "head": [
+        _UP, _cat(6), [-1, 3, "C3Ghost", [512]],
+        _UP, _cat(4), [-1, 3, "C3Ghost", [256]],
+        [-1, 1, "GhostConv", [256, 3, 2]], _cat(12), [-1, 3, "C3Ghost", [512]],
+        [-1, 1, "GhostConv", [512, 3, 2]], _cat(9), [-1, 3, "C3Ghost", [1024]],
+    ],
+    "detect_from": [15, 18, 21],
+}
+
+# cfg/models/v8/yolov8-ghost-p2.yaml:14-54: the same backbone, the neck one step further up to stride 4, Detect on (P2, P3, P4, P5)
+_YOLOV8_GHOST_P2 = {
+    "scales": _YOLOV8["scales"],
+    "backbone": _YOLOV8_GHOST["backbone"],
+    "head": [
+        _UP, _cat(6), [-1, 3, "C3Ghost", [512]],
+        _UP, _cat(4), [-1, 3, "C3Ghost", [256]],
+        _UP, _cat(2), [-1, 3, "C3Ghost", [128]],
+        [-1, 1, "GhostConv", [128, 3, 2]], _cat(15), [-1, 3, "C3Ghost", [256]],
+        [-1, 1, "GhostConv", [256, 3, 2]], _cat(12), [-1, 3, "C3Ghost", [512]],
+        [-1, 1, "GhostConv", [512, 3, 2]], _cat(9), [-1, 3, "C3Ghost", [1024]],
+    ],
+    "detect_from": [18, 21, 24, 27],
+}
+
+# cfg/models/v8/yolov8-ghost-p6.yaml:14-56: a 768-channel stride-32 stage and a stride-64 stage before SPPF, the head on (P3, P4, P5, P6)
+_YOLOV8_GHOST_P6 = {
+    "scales": _YOLOV8["scales"],
+    "backbone": [
+        [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "GhostConv", [128, 3, 2]], [-1, 3, "C3Ghost", [128, True]],
+        [-1, 1, "GhostConv", [256, 3, 2]], [-1, 6, "C3Ghost", [256, True]], [-1, 1, "GhostConv", [512, 3, 2]],
+        [-1, 6, "C3Ghost", [512, True]], [-1, 1, "GhostConv", [768, 3, 2]], [-1, 3, "C3Ghost", [768, True]],
+        [-1, 1, "GhostConv", [1024, 3, 2]], [-1, 3, "C3Ghost", [1024, True]], [-1, 1, "SPPF", [1024, 5]],
+    ],
+    "head": [
+        _UP, _cat(8), [-1, 3, "C3Ghost", [768]],
+        _UP, _cat(6), [-1, 3, "C3Ghost", [512]],
+        _UP, _cat(4), [-1, 3, "C3Ghost", [256]],
+        [-1, 1, "GhostConv", [256, 3, 2]], _cat(17), [-1, 3, "C3Ghost", [512]],
+        [-1, 1, "GhostConv", [512, 3, 2]], _cat(14), [-1, 3, "C3Ghost", [768]],
+        [-1, 1, "GhostConv", [768, 3, 2]], _cat(11), [-1, 3, "C3Ghost", [1024]],
+    ],
+    "detect_from": [20, 23, 26, 29],
+}
 
 
 # YOLOv9 (GELAN), cfg/models/v9/yolov9{t,s,m,c}.yaml:7-41: one layout for all four sizes -- stem, four ELAN stages with a
@@ -221,7 +276,8 @@ _YOLOV8_CLS = {
 _CLS_FAMILIES = {"yolo11": _YOLO11_CLS, "yolov8": _YOLOV8_CLS}
 _POSE_FAMILIES = ("yolo11", "yolov8", "yolov8-p6")  # the families the reference ships a -pose yaml for
 _FAMILIES = {"yolo11": _YOLO11, "yolov8": _YOLOV8, "bsyolo11": _BSYOLO11, "yolov5": _YOLOV5,
-             "yolov8-p2": _YOLOV8_P2, "yolov8-p6": _YOLOV8_P6, "yolov5-p6": _YOLOV5_P6}
+             "yolov8-p2": _YOLOV8_P2, "yolov8-p6": _YOLOV8_P6, "yolov5-p6": _YOLOV5_P6,
+             "yolov8-ghost": _YOLOV8_GHOST, "yolov8-ghost-p2": _YOLOV8_GHOST_P2, "yolov8-ghost-p6": _YOLOV8_GHOST_P6}
 
 
 def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str = "detect", kpt_shape=None) -> dict:

@@ -191,6 +191,9 @@ class Plan:
             setattr(self, name, not self.f32_mode and ((os.environ.get(env, "1") != "0") if arg is None else bool(arg)))
         # box-branch tail (cv2.x.1 + cv2.x.2 + DFL in one launch): part of the head fusion; the variable below switches it off alone
         self.fuse_boxtail = self.fuse_head and os.environ.get("BSY_FUSE_BOXTAIL", "1") != "0"
+        # GhostConv (1x1 cv1 + depthwise 5x5 cv2 + the GhostBottleneck shortcut) as one launch (csrc/ghost_fused.hip).  Not in SWITCHES: every
+        # entry of that table changes one of the graphs the switch test builds, and none of those holds a GhostConv
+        self.fuse_ghost = not self.f32_mode and os.environ.get("BSY_FUSE_GHOST", "1") != "0"
         self.buf_bytes: List[int] = []
         self.ops: List[dict] = []
         self.wrecs: "OrderedDict[str, WRec]" = OrderedDict()
@@ -428,10 +431,63 @@ class Plan:
         t = self.conv(name + ".cv1", x, c_, k[0], 1, **cv1)
         self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res)
 
-    def c3k(self, name: str, x, dst: T, n: int, shortcut: bool, k=(3, 3), rep: bool = False):
+    def ghostconv(self, name: str, src: Union[T, Sequence[T]], c2: int, k: int = 1, s: int = 1, act: bool = True, dst: Optional[T] = None,
+                  res: Optional[T] = None) -> T:
+        """conv.py:280-293 GhostConv: cat(y, cv2(y)) with y = cv1(x), cv1 = Conv(c1, c2 // 2, k, s, act), cv2 = Conv(c2 // 2, c2 // 2, 5, 1,
+        g = c2 // 2, act), depthwise.  res: a shortcut operand added to the concat (GhostBottleneck).  One OP_GHOST where cv1 is 1x1
+        stride 1 on one plain source and the kernel takes the widths; else cv1 and cv2 as CONV and DWCONV_G into the halves of one
+        buffer, which with a shortcut is a scratch buffer that OP_ADD adds `res` to.  fp16 path, c2 // 2 not a multiple of 8: both halves
+        are carried on the next multiple of 8 as zero-padded pieces (T.cmap), as c2f / c3k carry their chunks."""
+        srcs = [src] if isinstance(src, T) else list(src)
+        if c2 % 2:
+            raise NotImplementedError(f"{name}: GhostConv with {c2} output channels does not split into two halves")
+        if k not in (1, 3) or s not in (1, 2):
+            raise NotImplementedError(f"{name}: GhostConv with k={k} s={s} (cv1 is accelerated for k 1 / 3, stride 1 / 2)")
+        hr = c2 // 2  # the module's hidden width
+        pad = bool(hr % 8) and not self.f32_mode
+        CH = make_divisible(hr, 8) if pad else hr
+        p = k // 2
+        OH, OW = (srcs[0].H + 2 * p - k) // s + 1, (srcs[0].W + 2 * p - k) // s + 1
+        new = lambda: self.alloc(2 * CH, OH, OW).padded([(CH, hr)] * 2) if pad else self.alloc(2 * CH, OH, OW)  # noqa: E731
+        if dst is None:
+            dst = new()
+        assert dst.C == 2 * CH and dst.H == OH and dst.W == OW and (res is None or res.C == dst.C)
+        fuse = (self.fuse_ghost and k == 1 and s == 1 and len(srcs) == 1 and not srcs[0].up and not srcs[0].C % 8 and not srcs[0].coff % 8
+                and kernel_takes("ghost_fused", srcs[0].C, CH))
+        pair = dst if res is None or fuse else new()
+        first = len(self.ops)
+        y = self.conv(name + ".cv1", srcs[0] if len(srcs) == 1 else srcs, CH, k, s, act=act, dst=pair.slice(0, CH))
+        self.dwconv_g(name + ".cv2", y, 5, 5, 1, CH if act else 0, dst=pair.slice(CH, CH),
+                      rows=[i if i < hr else -1 for i in range(CH)] if pad else None, real_c=hr if pad else 0)
+        if fuse:
+            # the two launches just listed become one: their weight records (the unfused plan's, in its order) and their flops stay
+            cv1, cv2 = self.ops[first:]
+            del self.ops[first:]
+            self._emit(L.OP_GHOST, name, src0=srcs[0], dst=dst, res=res, ksize=5, stride=1, pad=2, act=int(act), mid_c=CH, wkey=cv1["wkey"],
+                       wkey2=cv2["wkey"], mfma_flops=cv1["mfma_flops"])  # the dense 1x1 part (the depthwise is VALU work)
+        elif res is not None:
+            self._emit(L.OP_ADD, name + ".add", src0=pair, src1=res, dst=dst)
+        return dst
+
+    def ghost_bottleneck(self, name: str, x: T, dst: T, s: int = 1):
+        """block.py:3384-3402 with s = 1 (the only form the reference's yamls reach): x + GhostConv(c2 // 2, c2, 1, 1, act=False)(GhostConv(c1,
+        c2 // 2, 1, 1)(x)); nn.Sequential names the two `conv.0` and `conv.2`.  The first GhostConv's hidden width is c2 // 4 (zero-padded
+        pieces where that is 4, 12, 20 ...), the second's c2 // 2."""
+        if s != 1:
+            raise NotImplementedError(f"{name}: GhostBottleneck with s = {s} (its depthwise stride-2 form is in no shipped graph) is not accelerated")
+        c2 = dst.real
+        if x.real != c2 or c2 % 4:
+            raise NotImplementedError(f"{name}: GhostBottleneck {x.real} -> {c2} (the identity shortcut needs equal widths, the halves a multiple of 4)")
+        c_ = c2 // 2
+        if c_ % 8 and not self.f32_mode:
+            raise NotImplementedError(f"{name}: GhostBottleneck with a hidden width of {c_} channels is not on the fp16 path (multiples of 8)")
+        t = self.ghostconv(name + ".conv.0", x, c_, 1, 1, True)
+        self.ghostconv(name + ".conv.2", t, c2, 1, 1, False, dst=dst, res=x)
+
+    def c3k(self, name: str, x, dst: T, n: int, shortcut: bool, k=(3, 3), rep: bool = False, ghost: bool = False):
         """block.py:3320-3334 + :3807-3815: cv3(cat(m(cv1 x), cv2 x)), m = n x Bottleneck(c_, c_, k=(3,3), e=1); C3 itself
         (YOLOv5u) is the same with k = ((1,1), (3,3)) and may read a two-operand Concat.  rep: RepCSP (:3644-3651), the same block
-        over RepBottlenecks."""
+        over RepBottlenecks.  ghost: C3Ghost (:3374-3381), the same block over GhostBottleneck(c_, c_)."""
         cr = int(dst.real * 0.5)  # the module's hidden width
         x0 = x if isinstance(x, T) else x[0]
         # fp16 path, hidden width not a multiple of 8 (a C3k of 12 / 20 / 24 channels ...): both halves of the concat are zero-padded pieces
@@ -451,7 +507,10 @@ class Plan:
             self.conv(name + ".cv2", x, c_, 1, 1, dst=cat.slice(c_, c_))
         for i in range(n):
             out = cat.slice(0, c_) if i == n - 1 else new()
-            self.bottleneck(f"{name}.m.{i}", cur, out, shortcut, k, 1.0, rep=rep)
+            if ghost:
+                self.ghost_bottleneck(f"{name}.m.{i}", cur, out)
+            else:
+                self.bottleneck(f"{name}.m.{i}", cur, out, shortcut, k, 1.0, rep=rep)
             cur = out
         self.conv(name + ".cv3", cat, dst.C, 1, 1, dst=dst)
 
@@ -902,7 +961,7 @@ class Plan:
             n = max(round(n * depth), 1) if n > 1 else n
             if f != -1:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
-            if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv"):
+            if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv", "GhostConv", "C3Ghost", "GhostBottleneck"):
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m == "Conv":
                     k, s = arg(1, 1), arg(2, 1)
@@ -920,6 +979,20 @@ class Plan:
                     x0 = x[0] if isinstance(x, list) else x
                     y = self.alloc(c2, x0.H, x0.W)
                     self.c3k(name, x, y, n, bool(arg(1, True)), k=(1, 3))
+                elif m == "C3Ghost":  # block.py:3374-3381; the repeat count is inserted as for C3 (tasks.py:1033)
+                    x0 = x[0] if isinstance(x, list) else x
+                    y = self.alloc(c2, x0.H, x0.W)
+                    self.c3k(name, x, y, n, True, ghost=True)
+                elif m == "GhostConv":  # conv.py:280-293, args [c2, k, s, g, act]; the yamls' stride-2 3x3 downsamplers
+                    if x is None or arg(3, 1) != 1:
+                        raise NotImplementedError(f"{name}: GhostConv on the image or with g = {arg(3, 1)} is not accelerated")
+                    if (c2 // 2) % 8 and not self.f32_mode:
+                        raise NotImplementedError(f"{name}: a top-level GhostConv with halves of {c2 // 2} channels is not on the fp16 path (multiples of 8)")
+                    y = self.ghostconv(name, x, c2, arg(1, 1), arg(2, 1), bool(arg(4, True)))
+                elif m == "GhostBottleneck":  # block.py:3384-3402, args [c2, k, s]
+                    assert isinstance(x, T)
+                    y = self.alloc(c2, x.H, x.W)
+                    self.ghost_bottleneck(name, x, y, arg(2, 1))
                 elif m == "DWConv":  # conv.py:224-229: Conv(c1, c2, k, s, g=gcd(c1, c2))
                     assert isinstance(x, T)
                     k, s = arg(1, 1), arg(2, 1)

@@ -105,6 +105,14 @@ enum bsy_op_kind {
                             * the linear conv wrote (every precision mode), nc = classes, dst = y = softmax (external slot, (B, nc)), res = x = the
                             * logits (external slot, optional), ksize = k, box[0] / cls[0] = the top-k index (int32) / value (f32) rows
                             * (external slots, (B, k); optional: skipped together when either is unbound), out_dtype = dtype of y and x */
+    BSY_OP_GHOST = 24,     /* GhostConv (conv.py:280-293) with a 1x1 stride-1 cv1, as one launch (csrc/ghost_fused.hip; fp16 path only): src0 = x
+                            * (Cin channels) -> dst = [y | z] (2 mid_c channels), y = cv1(x), z = cv2(y) (depthwise 5x5 on mid_c channels);
+                            * act (0 / 1) applies to both convs; res (optional, 2 mid_c channels) = a shortcut added after the activation
+                            * (GhostBottleneck, block.py:3400-3402).  w_off / b_off = cv1 (packed 1x1), w2_off / b2_off = cv2 (f32 [25][mid_c] /
+                            * [mid_c]); ksize = 5, stride = 1, pad = 2 describe the depthwise conv.  Widths: bsy_ghost_fused_supported(Cin,
+                            * mid_c).  The same bits as the launches it replaces: CONV 1x1, DWCONV_G 5x5 and, with res, ADD                   */
+    BSY_OP_ADD = 25,       /* dst = src0 + src1 elementwise (both storage types; f16: the sum is taken in f32 and rounded once); dst may be
+                            * src0's view                                                                                                  */
     BSY_OP_ELA = 15       /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
@@ -156,7 +164,7 @@ typedef struct bsy_op {
     int64_t aux_off[18];    /* MSCA_SPATIAL: (weights, bias) byte offsets of its nine depthwise convs */
     int32_t prec;           /* 0: the fp16-storage product path.  1: fp32 correctness mode -- every workspace view is NHWC f32,
                              * dense conv weights are f32 [k*k*Cin][Cout], arithmetic is fp32 (csrc/ref32.hip); kinds CONV_FIRST,
-                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ELA, POOL_DOWN, CLASSIFY_TAIL.
+                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL.
                              * 2: fp32x mode -- storage and every non-conv kernel as in mode 1; dense convs (CONV) multiply on the
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
@@ -329,6 +337,9 @@ int bsy_dwpw_fused_supported(int C, int C2);
 int bsy_attention_supported(int key_dim, int head_dim);
 int bsy_pmsfa_tail_supported(int C);
 int bsy_msca_spatial_supported(int H, int W);
+/* 1 when BSY_OP_GHOST runs a GhostConv of Cin input channels and CH hidden channels (its output has 2 CH): both multiples of 8, Cin up
+ * to 512 and CH up to 256.  Anything else: the planner emits CONV 1x1 + DWCONV_G 5x5 (+ ADD), and the op itself is an error. */
+int bsy_ghost_fused_supported(int Cin, int CH);
 
 /* DWConv (conv.py:224-229) 3x3 s1: w f32 [9][C], b f32 [C]. */
 int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* b, void* y, int ldy,
