@@ -61,6 +61,7 @@ struct ConvArgs {
     void* y = nullptr;
     int y_f32 = 0, A = 0, a0 = 0, nrows = 0;
     float lvl_stride = 0.f;
+    int xyxy = 0;  // epi 3: rows 0..3 are (x1, y1, x2, y2) * stride -- dist2bbox(xywh=False), an end2end head (head.py:148) -- instead of xywh
     void* raw = nullptr;
     int raw_f32 = 0, rawC = 0;
     // Box-branch tail (3x3 conv + the branch's last 1x1 conv + DFL decode in one launch; conv_patch.hip conv3x3_patch_kernel<.., TAIL>):
@@ -352,6 +353,7 @@ struct DecodeArgs {
     int nk = 0, kdim = 0;  // Pose keypoint channels (nkpt * kdim; 0: none) and channels per keypoint (2 / 3): msk[l] then holds the level's keypoint
                            // logits (nm = ne = 0); y gets nk decoded rows behind the scores (Pose.kpts_decode, kpt_decode.h)
     void* kraw = nullptr;  // nk: (B, nk, A) tensor of y's dtype for the undecoded logits, or null
+    int xyxy = 0;  // 1: rows 0..3 are (x1, y1, x2, y2) * stride, the box form of an end2end head (dist2bbox(xywh=False), head.py:148); nm = ne = nk = 0
 };
 int launch_decode(const DecodeArgs& a, hipStream_t s);
 // val_match.hip: the validator's matching rule on an IoU matrix (B, Lmax, max_det) made elsewhere (val_masks.hip); arguments as

@@ -34,6 +34,7 @@ struct ConvK {
     int tiles_x, tiles_y, B;  // patch kernel: 8 x 16 output tiles per image
     int epi, y_f32, A, a0, nrows, raw_f32, rawC;  // fused Detect decoder (ConvArgs::epi)
     float lvl_stride;
+    int xyxy;  // box rows as corners (ConvArgs::xyxy)
     void* y;
     void* raw;
     const half_t* tail_wgt;  // box-branch tail (ConvArgs::tail_wgt): packed [128][64] 1x1 weights, f32 bias
@@ -193,7 +194,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[NT][
 //   epi 2 (class logits): sigmoid, rows 4 + c.
 //   epi 3 (box logits, 4 sides x 16 DFL bins = 64 couts in one wave: WAVES_N == 1, NT == 2): a side's 16 bins sit in
 //          8 registers of this lane and 8 of lane ^ 32 -> softmax expectation with three cross-lane exchanges, then
-//          dist2bbox (xywh) * stride, rows 0..3.
+//          dist2bbox (xywh; xyxy where ConvK::xyxy is set) * stride, rows 0..3.
 // The raw logits go to the level's raw map (B, 64 + nc, h, w) when the caller bound one.
 template <typename T>
 __device__ __forceinline__ void head_store(void* base, size_t idx, float v) { reinterpret_cast<T*>(base)[idx] = (T)v; }
@@ -239,8 +240,9 @@ __device__ __forceinline__ void dfl_decode_store(const ConvK& p, const f32x16& l
         const int ay_i = pix / p.OW, ax_i = pix - ay_i * p.OW;
         const float ax = (float)ax_i + 0.5f, ay = (float)ay_i + 0.5f;
         const float x1 = ax - dist[0], y1 = ay - dist[1], x2 = ax + dist[2], y2 = ay + dist[3];
-        const float o[4] = {((x1 + x2) * 0.5f) * p.lvl_stride, ((y1 + y2) * 0.5f) * p.lvl_stride,
-                            (x2 - x1) * p.lvl_stride, (y2 - y1) * p.lvl_stride};
+        // xyxy (an end2end head): (anchor - lt) * stride, (anchor + rb) * stride, as tal.py:385-395 with xywh=False then head.py:129
+        const float o[4] = {(p.xyxy ? x1 : (x1 + x2) * 0.5f) * p.lvl_stride, (p.xyxy ? y1 : (y1 + y2) * 0.5f) * p.lvl_stride,
+                            (p.xyxy ? x2 : x2 - x1) * p.lvl_stride, (p.xyxy ? y2 : y2 - y1) * p.lvl_stride};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const size_t yi = ybase + (size_t)r * p.A;

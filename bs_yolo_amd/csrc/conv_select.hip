@@ -227,6 +227,7 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
     k.wgt = a.wgt; k.bias = a.bias; k.dst = a.dst; k.ldd = a.ldd; k.Cout = a.Cout; k.out_f32 = a.out_f32;
     k.res = a.res; k.ldr = a.ldr; k.act = a.act; k.B = a.B; k.tiles_x = k.tiles_y = 0;
     k.epi = a.epi; k.y = a.y; k.y_f32 = a.y_f32; k.A = a.A; k.a0 = a.a0; k.nrows = a.nrows; k.lvl_stride = a.lvl_stride;
+    k.xyxy = a.epi == 3 && a.xyxy;
     k.raw = a.raw; k.raw_f32 = a.raw_f32; k.rawC = a.rawC;
     k.tail_wgt = a.tail_wgt; k.tail_bias = a.tail_bias;
     if (a.tail_wgt && !a.epi) BSY_FAIL(BSY_ERR_ARG, "conv: a box-branch tail needs the decoder arguments (epi 3)");

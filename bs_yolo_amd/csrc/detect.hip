@@ -26,6 +26,7 @@ struct DecodeK {
     int ne;  // ROT: angle channels (1), read through the msk slots
     int nk, kdim;  // KPT: keypoint channels (nkpt * kdim) read through the msk slots, kdim = 2 (x, y) or 3 (x, y, visibility)
     void* kraw;    // KPT: (B, nk, A) tensor of y's dtype for the undecoded keypoint logits, or null
+    int xyxy;      // PLAIN: rows 0..3 as corners (x1, y1, x2, y2) * stride (DecodeArgs::xyxy)
 };
 
 // One workgroup = 64 consecutive anchors of one (image, level).  Their logits are contiguous in HBM
@@ -158,10 +159,11 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p, T* __restr
             const float ax = (float)(la % p.w[l]) + 0.5f, ay = (float)(la / p.w[l]) + 0.5f;
             const float x1 = ax - sd[a * 4 + 0], y1 = ay - sd[a * 4 + 1], x2 = ax + sd[a * 4 + 2], y2 = ay + sd[a * 4 + 3];
             const float st = p.stride[l];
-            yp[0] = (T)(((x1 + x2) * 0.5f) * st);
-            yp[(size_t)p.A] = (T)(((y1 + y2) * 0.5f) * st);
-            yp[(size_t)2 * p.A] = (T)((x2 - x1) * st);
-            yp[(size_t)3 * p.A] = (T)((y2 - y1) * st);
+            // xyxy (an end2end head): (anchor - lt) * stride, (anchor + rb) * stride, as tal.py:385-395 with xywh=False then head.py:129
+            yp[0] = (T)((p.xyxy ? x1 : (x1 + x2) * 0.5f) * st);
+            yp[(size_t)p.A] = (T)((p.xyxy ? y1 : (y1 + y2) * 0.5f) * st);
+            yp[(size_t)2 * p.A] = (T)((p.xyxy ? x2 : x2 - x1) * st);
+            yp[(size_t)3 * p.A] = (T)((p.xyxy ? y2 : y2 - y1) * st);
         }
         const float* cr = scls + a * cst;
         for (int c = part; c < p.nc; c += 4) yp[(size_t)(4 + c) * p.A] = (T)sigmoid_f(cr[c]);
@@ -210,8 +212,10 @@ int launch_decode(const DecodeArgs& a, hipStream_t s) {
         BSY_FAIL(BSY_ERR_ARG, "decode: nk = %d with nm = %d, ne = %d (keypoints, mask coefficients and the angle exclude each other)", a.nk, a.nm, a.ne);
     if (a.nk && ((a.kdim != 2 && a.kdim != 3) || a.nk % a.kdim || a.nk / a.kdim > 64))
         BSY_FAIL(BSY_ERR_ARG, "decode: nk = %d, kdim = %d (kdim 2 or 3, 1 to 64 keypoints of kdim channels)", a.nk, a.kdim);
+    if (a.xyxy && (a.nm || a.ne || a.nk)) BSY_FAIL(BSY_ERR_ARG, "decode: xyxy boxes with nm = %d, ne = %d, nk = %d (a plain Detect head only)", a.nm, a.ne, a.nk);
     const int nx = a.nm + a.ne + a.nk;  // rows read through the msk slots
     DecodeK k;
+    k.xyxy = a.xyxy ? 1 : 0;
     int A = 0;
     for (int l = 0; l < BSY_MAX_LEVELS; ++l) {
         const bool on = l < a.nl;

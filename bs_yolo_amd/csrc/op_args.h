@@ -131,11 +131,29 @@ inline bool build_classify_tail(ClassifyArgs& a, const bsy_op& op, Resolver& R) 
     }
     return R.ok;
 }
-// DECODE (f32 logit maps in every precision mode).  act = the fused head epilogue's DFL order; the msk slots hold mask coefficients
+// E2E_TOPK (csrc/topk.hip, every precision mode): src0 = the pre-top-k tensor (B, 4 + nc, A) of out_dtype, dst = the rows (B, min(ksize, A), 6)
+// f32, res = the scratch of bsy_end2end_topk_workspace_bytes(B, A, nc, ksize) bytes (the planner sizes the buffer with the same call)
+struct TopkArgs {
+    const void* pred = nullptr;
+    float* rows = nullptr;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+};
+inline bool build_e2e_topk(TopkArgs& a, const bsy_op& op, Resolver& R) {
+    a.pred = R.base(op.src0); a.rows = (float*)R.base(op.dst); a.ws = R.base(op.res);
+    a.ws_bytes = bsy_end2end_topk_workspace_bytes(op.B, op.A, op.nc, op.ksize);
+    if (R.ok && (!a.pred || !a.rows || !a.ws || !a.ws_bytes || op.src0.C != 4 + op.nc)) {
+        R.ok = false;
+        bsy_set_error("e2e_topk: src0 (%d rows, nc = %d), dst and the res scratch are all needed; B = %d, A = %d, max_det = %d", op.src0.C, op.nc, op.B, op.A, op.ksize);
+    }
+    return R.ok;
+}
+// DECODE (f32 logit maps in every precision mode).  act bit 0 = the fused head epilogue's DFL order, bit 1 = xyxy boxes; the msk slots hold mask coefficients
 // (Segment), angle (OBB) or keypoint (Pose) logits; Pose: res = the raw keypoint tensor, an optional output
 inline bool build_decode(DecodeArgs& a, const bsy_op& op, Resolver& R, const char*) {
     a.nl = op.nl; a.B = op.B; a.nc = op.nc; a.nm = op.nm; a.A = op.A; a.ne = op.ne;
-    a.halves = op.act && !op.nm && !op.ne;
+    a.halves = (op.act & 1) && !op.nm && !op.ne;
+    a.xyxy = (op.act >> 1) & 1;
     a.nk = op.nk; a.kdim = op.kdim;
     const bool extra = op.nm || op.ne || op.nk;
     for (int l = 0; l < op.nl && l < BSY_MAX_LEVELS; ++l) {
@@ -312,11 +330,12 @@ inline bool build_conv(ConvArgs& a, const bsy_op& op, Resolver& R, const char* w
     a.res = R.h(op.res); a.ldr = op.res.buf >= 0 ? op.res.ld : 0;
     a.act = op.act; a.dst_scale = op.dst_scale; a.dst_dy = op.dst_dy; a.dst_dx = op.dst_dx;
     if (op.out_f32 >= 2) {  // fused Detect decoder: dst = the prediction tensor y, box[0] = the level's raw map (optional)
-        a.epi = op.out_f32; a.out_f32 = 0; a.dst = nullptr; a.ldd = 8; a.Cout = op.nl;
+        a.epi = op.out_f32 == 4 ? 3 : op.out_f32; a.xyxy = op.out_f32 == 4;  // mode 4: the box branch (3) storing corners
+        a.out_f32 = 0; a.dst = nullptr; a.ldd = 8; a.Cout = op.nl;
         a.y = R.base(op.dst); a.y_f32 = op.out_dtype == BSY_F32; a.A = op.A; a.a0 = op.lvl_h[1]; a.nrows = op.dst.C;
         a.lvl_stride = op.lvl_stride[0];
         a.raw = R.optional(op.box[0]); a.raw_f32 = a.y_f32; a.rawC = op.box[0].C;
-        if (op.out_f32 == 3 && op.mid_c > 0) {  // box-branch tail: this op is the 3x3 conv, (w2, b2) the branch's last 1x1 conv
+        if (a.epi == 3 && op.mid_c > 0) {  // box-branch tail: this op is the 3x3 conv, (w2, b2) the branch's last 1x1 conv
             a.Cout = op.mid_c;
             a.tail_wgt = (const half_t*)(wb + op.w2_off); a.tail_bias = (const float*)(wb + op.b2_off);
         }

@@ -217,10 +217,19 @@ extern "C" int bsy_detect_decode(const float* const* box, const int* ldb, const 
                                  const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
                                  const float* lvl_stride, int nl, int B, int nc, int nm, void* y, int y_dtype,
                                  bsy_stream stream) {
+    return bsy_detect_decode_fmt(box, ldb, cls, ldc, msk, ldm, lvl_h, lvl_w, lvl_stride, nl, B, nc, nm, 0, y, y_dtype, stream);
+}
+
+extern "C" int bsy_detect_decode_fmt(const float* const* box, const int* ldb, const float* const* cls, const int* ldc,
+                                     const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
+                                     const float* lvl_stride, int nl, int B, int nc, int nm, int xyxy, void* y, int y_dtype,
+                                     bsy_stream stream) {
     if (!box || !ldb || !cls || !ldc || !lvl_h || !lvl_w || !lvl_stride || !y || nl < 1 || nl > BSY_MAX_LEVELS)
         BSY_FAIL(BSY_ERR_ARG, "detect_decode: bad argument");
     if (nm && (!msk || !ldm)) BSY_FAIL(BSY_ERR_ARG, "detect_decode: mask inputs missing");
+    if (xyxy != 0 && xyxy != 1) BSY_FAIL(BSY_ERR_ARG, "detect_decode: xyxy = %d (0 or 1)", xyxy);
     DecodeArgs a;
+    a.xyxy = xyxy;
     a.nl = nl; a.B = B; a.nc = nc; a.nm = nm;
     for (int l = 0; l < nl; ++l) {
         a.box[l] = box[l]; a.cls[l] = cls[l]; a.msk[l] = nm ? msk[l] : nullptr;

@@ -16,8 +16,8 @@ int run(bool (*build)(Args&, const bsy_op&, Resolver&, const char*), int (*launc
 int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
     if (op.prec < 0 || op.prec > 2) BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown precision mode %d", op.prec);
     // fp32 correctness mode (bsy_op.prec == 1, and 2 = fp32x) first: same op records, f32 views, kernels of ref32.hip.  DECODE, RAW_NCHW
-    // and CLASSIFY_TAIL consume f32 logit maps in every mode, POOL_DOWN takes the storage type as an argument: they break out of this
-    // switch into the common one.
+    // and CLASSIFY_TAIL consume f32 logit maps in every mode, POOL_DOWN takes the storage type as an argument, E2E_TOPK reads a tensor of
+    // out_dtype: they break out of this switch into the common one.
     Views<float> v32;
     if (op.prec) switch (op.kind) {
         case BSY_OP_CONV_FIRST:
@@ -67,6 +67,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
         case BSY_OP_CLASSIFY_TAIL:
         case BSY_OP_DECODE:
         case BSY_OP_RAW_NCHW:
+        case BSY_OP_E2E_TOPK:
             break;
         default:
             BSY_FAIL(BSY_ERR_ARG, "fp32 mode: op kind %d has no fp32 implementation (fused kinds are fp16-only)", op.kind);
@@ -132,6 +133,11 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
             ClassifyArgs a;
             if (!build_classify_tail(a, op, R)) return BSY_ERR_ARG;
             return launch_classify_tail(a.logits, op.src0.ld, op.B, op.nc, a.y, a.x, op.out_dtype, a.k, a.idx, a.val, s);
+        }
+        case BSY_OP_E2E_TOPK: {  // the two launches of bsy_end2end_topk on `s`: nothing but kernel launches, so it is captured like any op
+            TopkArgs a;
+            if (!build_e2e_topk(a, op, R)) return BSY_ERR_ARG;
+            return bsy_end2end_topk(a.pred, op.out_dtype, op.B, op.nc, op.A, op.ksize, a.rows, a.ws, a.ws_bytes, (bsy_stream)s);
         }
         default:
             BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown op kind %d", op.kind);

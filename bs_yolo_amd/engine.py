@@ -13,6 +13,12 @@ LAST forward (in graph mode they belong to the ring slot of that forward, like y
 An engine built from a pose graph (a `Pose` head) returns what Pose.forward returns in eval (head.py:250): ``(y, (x_list, kpt))`` with
 y (B, 4 + nc + nk, A) -- the decoded keypoint rows behind the scores -- and kpt (B, nk, A) the raw keypoint logits;
 ``want_raw=False`` gives ``(y, ([None] * nl, None))``.
+
+An engine built from a YOLOv10 graph (a `v10Detect` head) returns what v10Detect.forward_end2end returns in eval (head.py:96-98):
+``(rows, {"one2many": [...], "one2one": [...]})`` with rows (B, min(max_det, A), 6) fp32 -- [x1, y1, x2, y2, score, class], the top-k of
+the one2one head (BSY_OP_E2E_TOPK) -- and the raw maps of both head copies, BCHW in the input's dtype.  ``want_raw=False`` gives
+``(rows, {"one2many": [None] * nl, "one2one": [None] * nl})`` from a plan of its own that never runs the one2many branches.  The
+pre-top-k tensor (B, 4 + nc, A) of the last ``want_raw=True`` forward is kept as ``engine.last_e2e_pre`` (as last_topk is).
 """
 from __future__ import annotations
 
@@ -53,6 +59,9 @@ def _bind(plan: Plan, im: torch.Tensor, outs: Mapping[str, Optional[torch.Tensor
 
 def pack_outputs(meta: Mapping, outs: Mapping[str, Optional[torch.Tensor]]):
     """What the model's forward returns in eval, from the outputs by name (y already carries the rows behind the scores)."""
+    if meta.get("end2end"):  # v10Detect.forward_end2end (head.py:98): (rows, {"one2many": x, "one2one": one2one})
+        nl = range(len(meta["levels"]))
+        return outs["rows"], {"one2many": [outs.get(f"o2m{l}") for l in nl], "one2one": [outs[f"o2o{l}"] for l in nl]}
     y = outs["y"]
     if meta.get("task") == "classify":  # Classify.forward (head.py:304): (softmax, logits)
         return y, outs["x"]
@@ -74,9 +83,10 @@ def cat_outputs(chunks: List[Mapping[str, Optional[torch.Tensor]]]) -> Dict[str,
 class YoloEngine:
     def __init__(self, cfg: dict, state_dict: Mapping[str, torch.Tensor], device: int = 0, bn_eps: float = BN_EPS,
                  autotune: Optional[bool] = None, max_plans: Optional[int] = None, precision: str = "fp16", graph: Optional[bool] = None,
-                 graph_ring: int = 3, latency: Optional[bool] = None, repconv: Optional[str] = None, **switches: Optional[bool]):
+                 graph_ring: int = 3, latency: Optional[bool] = None, repconv: Optional[str] = None, max_det: int = 300,
+                 **switches: Optional[bool]):
         """switches: the fusion switches of plan.SWITCHES (fuse_stem=False, ...), handed to every plan; None or absent = the switch's
-        environment variable, on where that is unset."""
+        environment variable, on where that is unset.  max_det: the rows a v10Detect head's top-k keeps (1 .. 4096; other heads ignore it)."""
         if not set(switches) <= set(SWITCHES):
             raise TypeError(f"YoloEngine() got an unexpected keyword argument {sorted(set(switches) - set(SWITCHES))[0]!r}")
         if not torch.cuda.is_available():
@@ -148,8 +158,10 @@ class YoloEngine:
         self.switches = dict(switches)
         # YOLOv9 graphs: which RepConv the RepBottlenecks hold (Plan's `repconv`); None reads it off the state dict's keys
         self.repconv = repconv or repconv_form(state_dict)
-        # pack once with a throw-away plan (op list structure does not depend on the input size)
-        self._packed = Plan(cfg, 1, 64, 64, **self._fuse_kw())
+        self.max_det = int(max_det)
+        # pack once with a throw-away plan (op list structure does not depend on the input size).  one2many: a v10Detect head's plan with
+        # both head copies, so that the blob holds every weight and the rows-only plans adopt their share of its offsets
+        self._packed = Plan(cfg, 1, 64, 64, one2many=True, **self._fuse_kw())
         blob = pack_plan_weights(self._packed, state_dict, bn_eps)
         self.weight_bytes = len(blob)
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
@@ -162,6 +174,8 @@ class YoloEngine:
         self.names = {i: f"{i}" for i in range(self.nc)}
         self.task = self.meta.get("task", "detect")  # "classify": forward returns (y, x), see the module docstring
         self.last_topk: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self.end2end = bool(self.meta.get("end2end"))  # a v10Detect head: forward returns (rows, {...}), see the module docstring
+        self.last_e2e_pre: Optional[torch.Tensor] = None
 
     def load_weights(self, state_dict: Mapping[str, torch.Tensor], bn_eps: float = BN_EPS) -> None:
         """Replace the engine's weights in place (same graph, new values: an EMA update, a fine-tuned checkpoint).  Plans, tuning and
@@ -177,11 +191,14 @@ class YoloEngine:
             L.check(L.lib.bsy_engine_load_weights(self._h, buf, len(blob)))
 
     def _fuse_kw(self):
-        return dict(self.switches, precision=self.precision, lanes=True if self.graph else None, latency=self.latency, repconv=self.repconv)
+        return dict(self.switches, precision=self.precision, lanes=True if self.graph else None, latency=self.latency, repconv=self.repconv,
+                    max_det=self.max_det)
 
     # -- plans --------------------------------------------------------------------------------------------------
-    def plan_for(self, B: int, H: int, W: int, in_dtype: torch.dtype, out_dtype: torch.dtype):
-        key = (B, H, W, in_dtype, out_dtype)
+    def plan_for(self, B: int, H: int, W: int, in_dtype: torch.dtype, out_dtype: torch.dtype, one2many: bool = False):
+        """one2many: an end2end engine's plan with the one2many branches, built when a want_raw caller first needs it (others: ignored)."""
+        one2many = bool(one2many) and self.end2end
+        key = (B, H, W, in_dtype, out_dtype) + ((True,) if one2many else ())
         hit = self._plans.get(key)
         if hit is not None:
             self._plans.move_to_end(key)
@@ -189,7 +206,7 @@ class YoloEngine:
         gs = self.max_stride
         if H % gs or W % gs:
             raise ValueError(f"input {H}x{W} must be a multiple of the max stride {gs} (utils/checks.py:120-172)")
-        plan = Plan(self.cfg, B, H, W, L.dtype_code(in_dtype), L.dtype_code(out_dtype), **self._fuse_kw())
+        plan = Plan(self.cfg, B, H, W, L.dtype_code(in_dtype), L.dtype_code(out_dtype), one2many=one2many, **self._fuse_kw())
         adopt_offsets(plan, self._packed)
         ops = plan.c_ops()
         sizes = (C.c_int64 * len(plan.buf_bytes))(*plan.buf_bytes)
@@ -216,6 +233,7 @@ class YoloEngine:
             L.lib.bsy_plan_destroy(old)
             for rk in [k for k in self._rings if k[0] == old_key]:
                 del self._rings[rk]
+        plan.key = key
         self._plans[key] = (plan, h)
         return plan, h
 
@@ -302,6 +320,8 @@ class YoloEngine:
         outs = self._forward_outs(im, want_raw)
         if "topk_idx" in outs:  # a classify plan's rows (of the whole batch where it was split)
             self.last_topk = (outs["topk_idx"], outs["topk_val"])
+        if self.end2end and want_raw:  # what the rows were selected from (of the whole batch where it was split)
+            self.last_e2e_pre = outs["pre"]
         return pack_outputs(self.meta, outs)
 
     def _forward_outs(self, im, want_raw):
@@ -315,7 +335,7 @@ class YoloEngine:
             step = -(-B // n_chunks)
             return cat_outputs([self._forward_outs(self._dense(im[i:i + step]), want_raw) for i in range(0, B, step)])
         with self._lock:  # plan table, arena and launch order are shared state
-            plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
+            plan, h = self.plan_for(B, H, W, im.dtype, im.dtype, one2many=want_raw)
             outs = self._output_set(plan, im, want_raw)
             self._run(plan, h, *_bind(plan, im, outs), im, B, H, W)
             return outs
@@ -326,7 +346,7 @@ class YoloEngine:
         if not self.graph:
             return _outputs(plan, want_raw, self.device, im.dtype)
         B, _, H, W = im.shape
-        ring = self._rings.setdefault(((B, H, W, im.dtype, im.dtype), bool(want_raw)), {"i": 0, "slots": []})
+        ring = self._rings.setdefault((plan.key, bool(want_raw)), {"i": 0, "slots": []})
         if len(ring["slots"]) < self.graph_ring:
             ring["slots"].append(_outputs(plan, want_raw, self.device, im.dtype))
         ring["i"] += 1
@@ -339,9 +359,9 @@ class YoloEngine:
         stream = cur_stream.cuda_stream
         if self._last_done is not None and self._last_stream != stream:
             cur_stream.wait_event(self._last_done)  # the arena is still owned by a forward on another stream
-        if self.autotune and (B, H, W, im.dtype) not in self._tuned:
+        if self.autotune and plan.key not in self._tuned:
             # first call for this shape: pick the fastest kernel configuration per conv op (runs the plan once)
-            self._tuned.add((B, H, W, im.dtype))
+            self._tuned.add(plan.key)
             self._autotune(plan, h, ext, n, stream)
         if self.graph:
             how = C.c_int(-1)
@@ -400,6 +420,8 @@ class YoloEngine:
         made by bsy_scale_img, the passes clipped / descaled / concatenated by ONE bsy_tta_merge on the current stream.  A Segment
         graph (an OBB one, a pose one, a classification one) returns its single-scale forward, as the reference reverts for every class but
         DetectionModel (:356-358)."""
+        if self.end2end:  # tasks.py:356: the reference does not augment an end2end model; its rows are no input of the merge
+            raise NotImplementedError("test-time augmentation of an end2end (v10Detect) model is not accelerated (tasks.py:356)")
         with self._lock:
             if self.meta["nm"] or self.meta["ne"] or self.meta.get("nk", 0) or self.task == "classify":
                 return self.forward(im)
@@ -446,9 +468,10 @@ class YoloEngine:
         im = self._dense(im)
         B, _, H, W = im.shape
         plan, h = self.plan_for(B, H, W, im.dtype, im.dtype)
-        # bound: every output of a classify plan; of the others the image and y alone (no raw map, proto or keypoint store is timed)
+        # bound: every output of a classify plan; of the others the image and what every caller gets -- y, or an end2end plan's pre-top-k
+        # tensor and rows -- alone (no raw map, proto or keypoint store is timed)
         outs = _outputs(plan, self.task == "classify", self.device, im.dtype)
-        ext, n = _bind(plan, im, outs if self.task == "classify" else {"y": outs["y"]})
+        ext, n = _bind(plan, im, outs if self.task == "classify" else {o.name: outs[o.name] for o in plan.outputs.values() if not o.raw_only})
         ms = (C.c_float * len(plan.ops))()
         L.check(L.lib.bsy_plan_profile(h, ext, n, L.stream_ptr(self.device), ms))
         return [(o["name"], o["kind"], float(t)) for o, t in zip(plan.ops, ms)], plan

@@ -9,7 +9,8 @@ cfg/models/11/yolo11-cls.yaml:8-30 and v8/yolov8-cls.yaml:8-29 (task "classify" 
 graphs cfg/models/11/yolo11-pose.yaml, v8/yolov8-pose.yaml and v8/yolov8-pose-p6.yaml: the detect graphs of "yolo11", "yolov8" and
 "yolov8-p6" under a Pose head, with a top-level `kpt_shape` (task "pose"), and the ghost graphs cfg/models/v8/yolov8-ghost.yaml,
 yolov8-ghost-p2.yaml and yolov8-ghost-p6.yaml (families "yolov8-ghost", "yolov8-ghost-p2", "yolov8-ghost-p6": GhostConv downsamplers and
-C3Ghost blocks on the YOLOv8 layouts, detect only).  They are
+C3Ghost blocks on the YOLOv8 layouts, detect only), and the YOLOv10 graphs cfg/models/v10/yolov10{n,s,m,b,l,x}.yaml (family
+"yolov10": one layout, a literal table per size of where C2fCIB stands and whether it holds the 7x7 RepVGGDW; a v10Detect head).  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -249,6 +250,45 @@ def _yolov9(size: str) -> dict:
     }
 
 
+# YOLOv10, cfg/models/v10/yolov10{n,s,m,b,l,x}.yaml:6-41: the YOLOv8 layout with SCDown for the stride-2 convs of P4 / P5 (and of the neck's
+# last step), PSA behind SPPF and the NMS-free v10Detect head.  Every size is its own file with a one-entry `scales` table; they differ in
+# which of layers 6, 8, 13, 19, 22 are C2fCIB instead of C2f and in C2fCIB's `lk` argument (RepVGGDW 7x7; n and s only).
+_V10_SIZES = {
+    "n": dict(scale=[0.33, 0.25, 1024], cib=(22,), lk=True),
+    "s": dict(scale=[0.33, 0.50, 1024], cib=(8, 22), lk=True),
+    "m": dict(scale=[0.67, 0.75, 768], cib=(8, 19, 22), lk=False),
+    "b": dict(scale=[0.67, 1.00, 512], cib=(8, 13, 19, 22), lk=False),
+    "l": dict(scale=[1.00, 1.00, 512], cib=(8, 13, 19, 22), lk=False),
+    "x": dict(scale=[1.00, 1.25, 512], cib=(6, 8, 13, 19, 22), lk=False),
+}
+
+
+def _yolov10(size: str) -> dict:
+    z = _V10_SIZES[size]
+
+    def blk(i, n, c2, backbone):
+        if i in z["cib"]:
+            return [-1, n, "C2fCIB", [c2, True, True] if z["lk"] else [c2, True]]
+        return [-1, n, "C2f", [c2, True] if backbone else [c2]]
+
+    return {
+        "scales": {size: list(z["scale"])},
+        "backbone": [
+            [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "Conv", [128, 3, 2]], blk(2, 3, 128, True),
+            [-1, 1, "Conv", [256, 3, 2]], blk(4, 6, 256, True), [-1, 1, "SCDown", [512, 3, 2]],
+            blk(6, 6, 512, True), [-1, 1, "SCDown", [1024, 3, 2]], blk(8, 3, 1024, True),
+            [-1, 1, "SPPF", [1024, 5]], [-1, 1, "PSA", [1024]],
+        ],
+        "head": [
+            _UP, _cat(6), blk(13, 3, 512, False),
+            _UP, _cat(4), blk(16, 3, 256, False),
+            [-1, 1, "Conv", [256, 3, 2]], _cat(13), blk(19, 3, 512, False),
+            [-1, 1, "SCDown", [512, 3, 2]], _cat(10), blk(22, 3, 1024, False),
+        ],
+        "detect_from": [16, 19, 22],
+    }
+
+
 # Classification graphs: backbones and scales tables of their own, one Classify layer as the head.  cfg/models/11/yolo11-cls.yaml:8-30:
 # the detect backbone without SPPF, and C2PSA reaches max_channels at m / l / x (512, where detect's table says the same)
 _YOLO11_CLS = {
@@ -286,7 +326,8 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
     stock_cfg("yolo11", "n", 1000, "classify") == 'yolo11n-cls.yaml' (families "yolo11" and "yolov8" only);
     stock_cfg("yolo11", "n", 1, "pose", kpt_shape=(17, 3)) == 'yolo11n-pose.yaml' (families "yolo11", "yolov8" and "yolov8-p6" only;
     `kpt_shape` = (keypoints, 2 or 3 channels each) is read by this task alone, becomes the dict's top-level `kpt_shape` and has to be
-    given: the four-argument call stock_cfg(family, scale, nc, "pose") raises ValueError for every family, as it always has)."""
+    given: the four-argument call stock_cfg(family, scale, nc, "pose") raises ValueError for every family, as it always has);
+    stock_cfg("yolov10", "s") == 'yolov10s.yaml' (scales n, s, m, b, l, x; detect only)."""
     if task == "classify":
         if family not in _CLS_FAMILIES:
             raise ValueError(f"{family}: no classification graph (yolo11, yolov8)")
@@ -302,6 +343,12 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
         fam = copy.deepcopy(_yolov9(scale))
         head = fam["head"] + [[fam["detect_from"], 1, "Detect", ["nc"]] if task == "detect" else [fam["detect_from"], 1, "Segment", ["nc", 32, 256]]]
         return {"nc": nc, "backbone": fam["backbone"], "head": head}
+    if family == "yolov10":  # detect only, under the v10Detect head; `scales` holds the one entry its yaml has
+        if scale not in _V10_SIZES or task != "detect":
+            raise ValueError(f"yolov10: scale {scale!r} / task {task!r} (detect: n, s, m, b, l, x)")
+        fam = copy.deepcopy(_yolov10(scale))
+        return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"],
+                "head": fam["head"] + [[fam["detect_from"], 1, "v10Detect", ["nc"]]]}
     fam = copy.deepcopy(_FAMILIES[family])
     head = list(fam["head"])
     if task == "detect":

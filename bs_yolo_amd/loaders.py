@@ -366,6 +366,8 @@ def predict_stream(engine, loader: LoadImagesPinned, conf: float = 0.25, iou: fl
     for every loader batch -> (batch, det (B, max_det, 6) fp32 with boxes scaled back to each original image
     (scale_boxes, ops.py:92-127), counts (B,) int32), all device-resident; the next batch decodes and uploads meanwhile."""
     from .nms import nms_batched, scale_boxes_batched
+    if getattr(engine, "end2end", False):  # (B, K, 6) rows, not a (B, 4 + nc, A) prediction: the loop below runs NMS on the latter
+        raise NotImplementedError("predict_stream on an end2end (v10Detect) engine is not implemented: its forward returns top-k rows")
     for batch in loader:
         y = engine(batch.im, want_raw=False)[0]
         det, counts = nms_batched(y, conf, iou, classes=classes, agnostic=agnostic, max_det=max_det)

@@ -289,9 +289,10 @@ def attention_pe_nhwc(qkv: torch.Tensor, heads: int, key_dim: int, head_dim: int
 
 def detect_decode(box: Sequence[torch.Tensor], cls: Sequence[torch.Tensor], hw: Sequence[tuple],
                   strides: Sequence[float], nc: int, out_dtype=torch.float32,
-                  msk: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+                  msk: Optional[Sequence[torch.Tensor]] = None, xyxy: bool = False) -> torch.Tensor:
     """box[l], cls[l] [, msk[l]] f32: (B*h*w, 64 / >= nc / nm) matrices, or (B, h, w, .) maps -- also channel slices of one (B, h, w, no)
-    tensor per level, rows a multiple of 4 floats apart -> (B, 4+nc+nm, A) (head.py:100-131)."""
+    tensor per level, rows a multiple of 4 floats apart -> (B, 4+nc+nm, A) (head.py:100-131).  xyxy: the boxes as corners, the form an
+    end2end head decodes (head.py:148; bsy_detect_decode_fmt); False is bsy_detect_decode as it always was."""
     nl = len(box)
     B = box[0].numel() // (box[0].shape[-1] * hw[0][0] * hw[0][1])
     nm = msk[0].shape[-1] if msk else 0
@@ -307,6 +308,10 @@ def detect_decode(box: Sequence[torch.Tensor], cls: Sequence[torch.Tensor], hw: 
     hh = (i32 * nl)(*[h for h, _ in hw])
     ww = (i32 * nl)(*[w for _, w in hw])
     st = (f32 * nl)(*[float(s) for s in strides])
+    if xyxy:
+        L.check(L.lib.bsy_detect_decode_fmt(*rows(box), *rows(cls), *rows(msk), hh, ww, st, nl, B, nc, nm, 1, _p(y), L.dtype_code(out_dtype),
+                                            _stream(y)))
+        return y
     L.check(L.lib.bsy_detect_decode(*rows(box), *rows(cls), *rows(msk), hh, ww, st, nl, B, nc, nm, _p(y), L.dtype_code(out_dtype),
                                     _stream(y)))
     return y

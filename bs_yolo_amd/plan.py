@@ -145,6 +145,9 @@ class Plan:
     EXT_PROTO = EXT_KPT = 5  # a segment plan's proto, or a pose plan's raw keypoint logits (B, nk, A): a plan has one or the other
     EXT_RAW3 = 6  # the fourth level's raw map (P2 / P6 heads): behind the proto slot, so that slots 0-5 stay what they were
     EXT_LOGITS, EXT_TOPK_IDX, EXT_TOPK_VAL = 2, 3, 4  # a classify plan's slots behind image and y: x (the logits), the top-k rows
+    # An end2end (v10Detect) plan: the pre-top-k tensor `pre` takes y's slot and the one2one raw maps `o2o{l}` the raw slots; behind
+    # every slot an earlier plan uses come the top-k rows and the one2many raw maps `o2m{l}` (levels 0 .. 3 at 8 .. 11)
+    EXT_ROWS, EXT_O2M0 = 7, 8
 
     @classmethod
     def ext_raw(cls, level: int) -> int:
@@ -162,11 +165,19 @@ class Plan:
         return T(L.BSY_EXT_BASE + slot, 0, 0, C, *(tail if slot == self.EXT_IMG else (0, 0)))  # (the image's view alone carries its size)
 
     def _raw(self, level: int, nc: int, x: T) -> T:  # the view of level `level`'s raw map (B, no, h, w), `x` being any map of that level
-        return self._ext(f"raw{level}", self.ext_raw(level), 64 + nc, (x.H, x.W), raw_only=True)
+        if self._e2e == "o2m":
+            return self._ext(f"o2m{level}", self.EXT_O2M0 + level, 64 + nc, (x.H, x.W), raw_only=True)
+        return self._ext(f"o2o{level}" if self._e2e else f"raw{level}", self.ext_raw(level), 64 + nc, (x.H, x.W), raw_only=True)
+
+    def _y(self, rows: int, A: int) -> T:  # the prediction tensor (B, rows, A): `y`, or an end2end head's pre-top-k tensor `pre`
+        return self._ext("pre" if self._e2e else "y", self.EXT_Y, rows, (A,))
 
     def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16, precision: str = "fp16",
-                 lanes: Optional[bool] = None, latency: bool = False, repconv: str = "refconv", **switches: Optional[bool]):
-        """switches: the keys of SWITCHES; None (or absent) = what the switch's environment variable says, on where it is unset."""
+                 lanes: Optional[bool] = None, latency: bool = False, repconv: str = "refconv", max_det: int = 300, one2many: bool = False,
+                 **switches: Optional[bool]):
+        """switches: the keys of SWITCHES; None (or absent) = what the switch's environment variable says, on where it is unset.
+        max_det, one2many: read by a v10Detect head alone -- the rows its top-k keeps, and whether the one2many branches (cv2 / cv3, raw
+        maps only, which a caller who wants the rows alone must not pay for) are part of the plan."""
         if not set(switches) <= set(SWITCHES):
             raise TypeError(f"Plan() got an unexpected keyword argument {sorted(set(switches) - set(SWITCHES))[0]!r}")
         self.cfg, self.B, self.H, self.W = cfg, B, H, W
@@ -177,6 +188,10 @@ class Plan:
         if repconv not in ("refconv", "repvgg"):
             raise ValueError(f"repconv must be 'refconv' or 'repvgg', not {repconv!r}")
         self.repconv = repconv
+        if not 1 <= int(max_det) <= 4096:
+            raise ValueError(f"max_det must be 1 .. 4096 (the top-k sorts its winners in LDS), not {max_det!r}")
+        self.max_det, self.one2many = int(max_det), bool(one2many)
+        self._e2e = ""  # which head copy of a v10Detect is being emitted: "" (not an end2end head), "o2o", "o2m"
         # latency mode (round 4; fp16 path): long-K conv layers with few tiles per image run split-K (split_factors below)
         self.latency = bool(latency) and precision == "fp16"
         if precision not in ("fp16", "fp32", "fp32x"):
@@ -381,15 +396,16 @@ class Plan:
                    mid_c=src.C // 2 if kind == "dwg_ext" else 0)  # first channel of the identity-kernel half
         return dst
 
-    def dwpw(self, name: str, src: T, cout: int, real: Tuple[int, int] = (0, 0)) -> T:
+    def dwpw(self, name: str, src: T, cout: int, real: Tuple[int, int] = (0, 0), parts: Tuple[str, str] = ("0", "1")) -> T:
         """nn.Sequential(DWConv(c, c, 3), Conv(c, cout, 1)) (head.py:49-57): one fused launch where dwpw_fused.hip's
         dwpw_fused_kernel takes the widths, else the two ordinary launches.  real = the modules' own (cout, cin) where `cout` / `src`
-        are padded to a multiple of 8."""
-        if not (self.fuse_dwpw and kernel_takes("dwpw_fused", src.C, cout) and not src.up):
-            t = self.dwconv(name + ".0", src, act=True, real_c=real[1])
-            return self.conv(name + ".1", t, cout, 1, 1, real=real)
-        kd = self._wrec(name + ".0", name=name + ".0", kind="dw", cout=src.C, cin=1, k=3, real_cout=real[1])
-        kp = self._wrec(name + ".1", name=name + ".1", kind="conv", cout=cout, cin=src.C, k=1, perm=None, real_cout=real[0], real_cin=real[1])
+        are padded to a multiple of 8.  parts: the two modules' names under `name` (CIB's second pair is "2", "3")."""
+        nd, npw = f"{name}.{parts[0]}", f"{name}.{parts[1]}"
+        if not (self.fuse_dwpw and kernel_takes("dwpw_fused", src.C, cout) and not src.up and src.cmap is None):
+            t = self.dwconv(nd, src, act=True, real_c=real[1])
+            return self.conv(npw, t, cout, 1, 1, real=real)
+        kd = self._wrec(nd, name=nd, kind="dw", cout=src.C, cin=1, k=3, real_cout=real[1])
+        kp = self._wrec(npw, name=npw, kind="conv", cout=cout, cin=src.C, k=1, perm=None, real_cout=real[0], real_cin=real[1])
         dst = self.alloc(cout, src.H, src.W)
         px = 2 * self.B * src.H * src.W * src.C
         self._emit(L.OP_DWPW, name, px * (9 + cout), src0=src, dst=dst, ksize=3, stride=1, pad=1, act=1, wkey=kd, wkey2=kp,
@@ -430,6 +446,31 @@ class Plan:
             return
         t = self.conv(name + ".cv1", x, c_, k[0], 1, **cv1)
         self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res)
+
+    def cib(self, name: str, x: T, dst: T, shortcut: bool, lk: bool):
+        """block.py:4176-4212 CIB(c, c, shortcut, e = 1.0, lk), the block of C2fCIB: x + cv1(x), cv1 a Sequential of five Convs, SiLU after each --
+        0: depthwise 3x3 (c); 1: 1x1 (c -> 2c); 2: depthwise 3x3 (2c), or with lk RepVGGDW (2c): a depthwise 7x7 once folded (weights.py
+        kind "repvggdw"); 3: 1x1 (2c -> c); 4: depthwise 3x3 (c).  Lowered as dwpw(0 + 1), dwpw(2 + 3) -- with lk DWCONV_G 7x7, then CONV --
+        and DWCONV(4) with x as its shortcut, written into the C2f piece.  A piece carried on the next multiple of 8 (T.cmap: c = 12,
+        20 ...; 2c is a multiple of 8 whenever c2 is) takes the two-launch forms, with zero weights and biases in its padding."""
+        c = dst.real
+        assert x.real == c and x.C == dst.C and not x.up
+        n = name + ".cv1"
+        if x.cmap is not None or dst.cmap is not None:
+            piece = lambda: self.alloc(x.C, x.H, x.W).padded([(x.C, c)])  # noqa: E731
+            t = self.dwconv(n + ".0", x, act=True, dst=piece(), real_c=c)
+            t = self.conv(n + ".1", t, 2 * c, 1, 1)
+        else:
+            t = self.dwpw(n, x, 2 * c)
+        if lk:
+            t = self.dwconv_g(n + ".2", t, 7, 7, 1, 2 * c, kind="repvggdw")
+            t = self.conv(n + ".3", t, dst.C, 1, 1, dst=piece() if dst.cmap is not None or x.cmap is not None else None)
+        elif x.cmap is not None or dst.cmap is not None:
+            t = self.dwconv(n + ".2", t, act=True)
+            t = self.conv(n + ".3", t, dst.C, 1, 1, dst=piece())
+        else:
+            t = self.dwpw(n, t, dst.C, parts=("2", "3"))
+        self.dwconv(n + ".4", t, act=True, dst=dst, res=x if shortcut else None, real_c=c if t.cmap is not None else 0)
 
     def ghostconv(self, name: str, src: Union[T, Sequence[T]], c2: int, k: int = 1, s: int = 1, act: bool = True, dst: Optional[T] = None,
                   res: Optional[T] = None) -> T:
@@ -514,8 +555,8 @@ class Plan:
             cur = out
         self.conv(name + ".cv3", cat, dst.C, 1, 1, dst=dst)
 
-    def c2f(self, name: str, x, c2: int, n: int, shortcut: bool, e: float, inner: str) -> T:
-        """block.py:3295-3317 (C2f) / :3796-3804 (C3k2).  inner: 'c2f' | 'bottleneck' | 'c3k'."""
+    def c2f(self, name: str, x, c2: int, n: int, shortcut: bool, e: float, inner: str, lk: bool = False) -> T:
+        """block.py:3295-3317 (C2f) / :3796-3804 (C3k2) / :4215-4232 (C2fCIB).  inner: 'c2f' | 'bottleneck' | 'c3k' | 'cib' (with `lk`: CIB's RepVGGDW)."""
         xs = [x] if isinstance(x, T) else list(x)
         c = int(c2 * e)
         if (self.fuse_tail and inner == "bottleneck" and n == 1 and shortcut and len(xs) == 1 and not xs[0].up and not xs[0].f32
@@ -531,7 +572,7 @@ class Plan:
         # fp16 path, chunk width not a multiple of 8 (c = 12 / 20 ...; tasks.py:1016 scales c2 by any width multiple): every chunk of the
         # concat is carried on the next multiple of 8 as a zero-padded piece (T.cmap) -- cv1 writes zero rows there, cv2 reads zero columns
         cr = c
-        if cr % 8 and not self.f32_mode and inner in ("bottleneck", "c2f", "c3k"):
+        if cr % 8 and not self.f32_mode and inner in ("bottleneck", "c2f", "c3k", "cib"):
             c = make_divisible(cr, 8)
         cat = self.alloc((2 + n) * c, xs[0].H, xs[0].W)
         if c != cr:
@@ -545,6 +586,8 @@ class Plan:
                 self.c3k_gai(f"{name}.m.{i}", src, dst, 2)
             elif inner == "c3k":
                 self.c3k(f"{name}.m.{i}", src, dst, 2, shortcut)
+            elif inner == "cib":
+                self.cib(f"{name}.m.{i}", src, dst, shortcut, lk)
             elif inner == "c2f":
                 self.bottleneck(f"{name}.m.{i}", src, dst, shortcut, (3, 3), 1.0)
             else:
@@ -755,8 +798,10 @@ class Plan:
             src = dst
         return self.conv(name + ".cv4", cat, c2, 1, 1)
 
-    def c2psa(self, name: str, x: T, c2: int, n: int) -> T:
-        """block.py:4429-4468 with PSABlock :4348-4383 and Attention :4235-4288."""
+    def c2psa(self, name: str, x: T, c2: int, n: int = 1, psa: bool = False) -> T:
+        """block.py:4429-4468 with PSABlock :4348-4383 and Attention :4235-4288.  psa: the PSA module (:4386-4426, YOLOv10) -- the same
+        dataflow with exactly one block and no repeat argument, whose `attn`, `ffn.0` and `ffn.1` stand directly under the layer."""
+        assert n == 1 or not psa
         assert x.C == c2
         c = int(c2 * 0.5)
         nh = c // 64
@@ -771,7 +816,7 @@ class Plan:
         per = 2 * kd + hd
         perm = qkv_perm(nh, kd, hd)
         for i in range(n):
-            pn = f"{name}.m.{i}"
+            pn = name if psa else f"{name}.m.{i}"
             qkv = self.conv(pn + ".attn.qkv", b, nh * per, 1, 1, act=False, perm=perm)
             att = self.alloc(c, x.H, x.W)
             N = x.H * x.W
@@ -811,7 +856,9 @@ class Plan:
                        flops: int, **fields):
         """A conv op with the Detect decoder in its epilogue (out_f32 = mode 2: class branch / 3: box branch): it writes level `level`'s
         rows of the prediction tensor (first anchor a0 of A, stride `stride`) and that level's raw map."""
-        self._emit(L.OP_CONV, name, flops, src0=src, src1=None, dst=self._ext("y", self.EXT_Y, 4 + nc, (A,)), res=None, OH=src.H, OW=src.W, ksize=k,
+        if mode == 3 and self._e2e:
+            mode = 4  # an end2end head's boxes are corners (head.py:148): the box epilogue's xyxy form
+        self._emit(L.OP_CONV, name, flops, src0=src, src1=None, dst=self._y(4 + nc, A), res=None, OH=src.H, OW=src.W, ksize=k,
                    stride=1, pad=k // 2, out_f32=mode, dst_scale=1, cout=cout, nl=cout, nc=nc, nm=0, A=A, box=[self._raw(level, nc, src)], cls=[], msk=[], level=level,
                    lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype, mfma_flops=flops, **fields)
 
@@ -821,19 +868,52 @@ class Plan:
         self._decoding_conv(name, src, 1, cout=cout, mode=mode, level=level, a0=a0, A=A, nc=nc, stride=stride,
                             flops=2 * self.B * src.H * src.W * cout * src.C, act=0, wkey=key)
 
-    def _box_tail(self, name: str, i: int, src: T, level: int, a0: int, A: int, nc: int, stride: float):
+    def _box_tail(self, name: str, i: int, src: T, level: int, a0: int, A: int, nc: int, stride: float, cv2: str = "cv2"):
         """cv2.i.1 (3x3, 64 -> 64, SiLU) + cv2.i.2 (1x1, 64 -> 64 box logits) + DFL / dist2bbox (head.py:49-57, :141-146) as ONE
         conv op: the patch kernel's TAIL form (conv_patch.hip) multiplies its activated fp16 tile with the 1x1 weights straight from
         LDS and decodes the accumulators -- bit for bit what the two launches produce, without the 64-channel map's round trip."""
-        n1, n2 = f"{name}.cv2.{i}.1", f"{name}.cv2.{i}.2"
+        n1, n2 = f"{name}.{cv2}.{i}.1", f"{name}.{cv2}.{i}.2"
         k1 = self._wrec(n1, name=n1, kind="conv", cout=64, cin=src.C, k=3, perm=None)
         k2 = self._wrec(n2, name=n2, kind="plain", cout=64, cin=64, k=1, perm=None)
         self._decoding_conv(n1 + "+2", src, 3, cout=64, mode=3, level=level, a0=a0, A=A, nc=nc, stride=stride,
                             flops=2 * self.B * src.H * src.W * 64 * (9 * src.C + 64), act=1, wkey=k1, wkey2=k2, mid_c=64)
 
-    def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0, nk: int = 0, kdim: int = 0):
+    def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0, nk: int = 0, kdim: int = 0,
+               end2end: bool = False):
         """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels, Pose :230-279 with nk = nkpt * kdim keypoint
-        channels)."""
+        channels).  end2end: v10Detect (:592-625, forward_end2end :76-98) -- the one2one copy of the branches (one2one_cv2 / one2one_cv3)
+        decodes corner boxes into the pre-top-k tensor `pre` and writes the one2one raw maps `o2o{l}`, BSY_OP_E2E_TOPK turns `pre` into the
+        rows (B, min(max_det, A), 6); the one2many copy (cv2 / cv3: raw maps `o2m{l}` only, nothing decoded) is emitted in a plan built
+        with one2many=True alone, always through f32 logit maps and the raw-map transposes (the fused epilogues write a prediction tensor)."""
+        if end2end:
+            assert not (nm or ne or nk or legacy)
+            start = len(self.ops)
+            self._e2e = "o2o"
+            self._detect(name, xs, nc, False, 0, 0, 0, 0, "one2one_")
+            if self.one2many:
+                self._e2e = "o2m"
+                self._detect(name, xs, nc, False, 0, 0, 0, 0, "")
+            self._e2e = "o2o"
+            # every branch chain of both copies first, each on its lane; then what runs on lane 0 behind a join: the decode launch (a
+            # plan without the fused head), the top-k, and last the raw-map transposes, which nothing waits for
+            head = self.ops[start:]
+            self.ops[start:] = ([o for o in head if o["kind"] not in (L.OP_DECODE, L.OP_RAW_NCHW)] + [o for o in head if o["kind"] == L.OP_DECODE])
+            A, K = self.meta["A"], min(self.max_det, self.meta["A"])
+            self.buf_bytes.append(int(L.lib.bsy_end2end_topk_workspace_bytes(self.B, A, nc, self.max_det)))
+            scratch = T(len(self.buf_bytes) - 1, 0, 0, 0, 1, 1, False, True)
+            self._emit(L.OP_E2E_TOPK, name + ".topk", join=1, src0=self._y(4 + nc, A), res=scratch, nc=nc, A=A, ksize=self.max_det, H=self.H,
+                       W=self.W, OH=0, OW=0, dst=self._ext("rows", self.EXT_ROWS, K, (6,), dtype="float32"), out_dtype=self.out_dtype)
+            self.ops += [o for o in head if o["kind"] == L.OP_RAW_NCHW]
+            self._e2e = ""
+            self.meta.update(end2end=True, max_det=self.max_det, K=K, one2many=self.one2many)
+            return
+        self._detect(name, xs, nc, legacy, nm, ne, nk, kdim, "")
+
+    def _detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int, ne: int, nk: int, kdim: int, pfx: str):
+        """One copy of the head's branches: `pfx` in front of cv2 / cv3 ("one2one_" for v10Detect's one2one copy)."""
+        cv2, cv3 = f"{name}.{pfx}cv2", f"{name}.{pfx}cv3"
+        o2m = self._e2e == "o2m"
+        lane0 = 2 * len(xs) if o2m else 0  # (an end2end head has no cv4 branches: their lanes carry the one2many copy)
         if not 1 <= len(xs) <= L.BSY_MAX_LEVELS:
             raise NotImplementedError(f"{name}: a head on {len(xs)} levels (1 to {L.BSY_MAX_LEVELS} are accelerated)")
         if ne and len(xs) > 3:
@@ -849,36 +929,36 @@ class Plan:
         # angle of its cv4 branch (tal.py:404-423 dist2rbox), so OBB always takes the decode launch
         # Four levels (P2 / P6 graphs) fuse the same way: every fused op carries its own level, first anchor and stride
         # A Pose head takes the decode launch too: it decodes the keypoint rows there (csrc/detect.hip, mode DEC_KPT)
-        fused = self.fuse_head and nm == 0 and ne == 0 and nk == 0
+        fused = self.fuse_head and nm == 0 and ne == 0 and nk == 0 and not o2m
         # every (level, branch) chain is independent until the decoder: give each its own lane so the engine runs them
         # concurrently (the 40x40 / 20x20 chains are far too small to fill 256 CUs on their own)
         for i, x in enumerate(xs):
             assert not x.up
-            self._lane = 2 * i
-            t = self.conv(f"{name}.cv2.{i}.0", x, c2, 3, 1)
+            self._lane = lane0 + 2 * i
+            t = self.conv(f"{cv2}.{i}.0", x, c2, 3, 1)
             if fused and self.fuse_boxtail and c2 == 64:
-                self._box_tail(name, i, t, i, a0[i], A, nc, strides[i])
+                self._box_tail(name, i, t, i, a0[i], A, nc, strides[i], pfx + "cv2")
             else:
-                t = self.conv(f"{name}.cv2.{i}.1", t, c2, 3, 1)
+                t = self.conv(f"{cv2}.{i}.1", t, c2, 3, 1)
                 if fused:
-                    self._head_conv(f"{name}.cv2.{i}.2", t, 64, 3, i, a0[i], A, nc, strides[i])
+                    self._head_conv(f"{cv2}.{i}.2", t, 64, 3, i, a0[i], A, nc, strides[i])
                 else:
-                    boxes.append(self.conv(f"{name}.cv2.{i}.2", t, 64, 1, 1, act=False, plain=True, out_f32=True))
-            self._lane = 2 * i + 1
+                    boxes.append(self.conv(f"{cv2}.{i}.2", t, 64, 1, 1, act=False, plain=True, out_f32=True))
+            self._lane = lane0 + 2 * i + 1
             # c3 = max(ch0, min(nc, 100)) (head.py:39) need not be a multiple of 8 (YOLO11n with 65 .. 100 or more classes: 100): the
             # branch then runs c3p channels wide with zero weights / biases in the padding -- SiLU(0) = 0 all the way, same results
             c3p = make_divisible(c3, 8)
             r3 = c3 if c3p != c3 else 0
             if legacy:
-                t = self.conv(f"{name}.cv3.{i}.0", x, c3p, 3, 1, real=(r3, 0))
-                t = self.conv(f"{name}.cv3.{i}.1", t, c3p, 3, 1, real=(r3, r3))
+                t = self.conv(f"{cv3}.{i}.0", x, c3p, 3, 1, real=(r3, 0))
+                t = self.conv(f"{cv3}.{i}.1", t, c3p, 3, 1, real=(r3, r3))
             else:
-                t = self.dwpw(f"{name}.cv3.{i}.0", x, c3p, real=(r3, 0))
-                t = self.dwpw(f"{name}.cv3.{i}.1", t, c3p, real=(r3, r3))
+                t = self.dwpw(f"{cv3}.{i}.0", x, c3p, real=(r3, 0))
+                t = self.dwpw(f"{cv3}.{i}.1", t, c3p, real=(r3, r3))
             if fused:
-                self._head_conv(f"{name}.cv3.{i}.2", t, nc, 2, i, a0[i], A, nc, strides[i], real_cin=r3)
+                self._head_conv(f"{cv3}.{i}.2", t, nc, 2, i, a0[i], A, nc, strides[i], real_cin=r3)
             else:
-                clss.append(self.conv(f"{name}.cv3.{i}.2", t, nc, 1, 1, act=False, plain=True, out_f32=True, real=(0, r3)))
+                clss.append(self.conv(f"{cv3}.{i}.2", t, nc, 1, 1, act=False, plain=True, out_f32=True, real=(0, r3)))
             if nm or ne:
                 # Segment.cv4 (head.py:175-197) / OBB.cv4 (:208-209): Conv(x, c4, 3) -> Conv(c4, c4, 3) -> Conv2d(c4, nm or ne, 1), on lanes
                 # of their own.  OBB's angle logits land in an f32 map 8 channels wide (zero weights and bias past `ne`): the conv kernels
@@ -911,10 +991,12 @@ class Plan:
         lvl = dict(H=self.H, W=self.W, OH=0, OW=0, nl=len(xs), nc=nc, A=A, box=boxes, cls=clss, lvl_h=[t.H for t in xs], lvl_w=[t.W for t in xs],
                    lvl_stride=strides, out_dtype=self.out_dtype)
         kraw = self._ext("kpt", self.EXT_KPT, nk, (A,), raw_only=True) if nk else None
-        self._emit(L.OP_DECODE, name + ".decode", join=1, nm=nm, ne=ne, nk=nk, kdim=kdim, msk=msks, res=kraw,
-                   act=int(not self.f32_mode and nm == 0 and ne == 0 and nk == 0), dst=self._ext("y", self.EXT_Y, 4 + nc + nm + ne + nk, (A,)), **lvl)
+        if not o2m:  # (act: bit 0 = the fused epilogue's DFL order, bit 1 = corner boxes, an end2end head's)
+            self._emit(L.OP_DECODE, name + ".decode", join=1, nm=nm, ne=ne, nk=nk, kdim=kdim, msk=msks, res=kraw,
+                       act=int(not self.f32_mode and nm == 0 and ne == 0 and nk == 0) | (2 if self._e2e else 0),
+                       dst=self._y(4 + nc + nm + ne + nk, A), **lvl)
         for i, x in enumerate(xs):
-            self._emit(L.OP_RAW_NCHW, f"{name}.raw{i}", nm=0, msk=[], level=i, dst=self._raw(i, nc, x), **lvl)
+            self._emit(L.OP_RAW_NCHW, f"{name}.{self._e2e or 'raw'}{i}", nm=0, msk=[], level=i, dst=self._raw(i, nc, x), **lvl)
 
     def classify(self, name: str, x: T, nc: int):
         """head.py:282-304 Classify in eval: (y, x) = (softmax(x), x), x = linear(pool(conv(x)).flatten(1)); Dropout(p = 0) is the
@@ -961,7 +1043,8 @@ class Plan:
             n = max(round(n * depth), 1) if n > 1 else n
             if f != -1:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
-            if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv", "GhostConv", "C3Ghost", "GhostBottleneck"):
+            if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv", "GhostConv", "C3Ghost", "GhostBottleneck",
+                     "C2fCIB", "PSA"):
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m == "Conv":
                     k, s = arg(1, 1), arg(2, 1)
@@ -1014,6 +1097,11 @@ class Plan:
                 elif m == "C2f":
                     shortcut = bool(arg(1, False))
                     y = self.c2f(name, x, c2, n, shortcut, 0.5, "c2f")
+                elif m == "C2fCIB":  # block.py:4215-4232, args [c2, shortcut, lk]; the repeat count is inserted as for C2f (tasks.py:1037-1043)
+                    y = self.c2f(name, x, c2, n, bool(arg(1, False)), 0.5, "cib", lk=bool(arg(2, False)))
+                elif m == "PSA":  # block.py:4386-4426, args [c2]: no repeat count (tasks.py:1010), one block
+                    assert isinstance(x, T)
+                    y = self.c2psa(name, x, c2, 1, psa=True)
                 elif m == "C2":  # the necks of yolov8-p6.yaml / yolov8-seg-p6.yaml
                     shortcut = bool(arg(1, True))
                     y = self.c2(name, x, c2, n, shortcut)
@@ -1068,7 +1156,7 @@ class Plan:
                 assert all(isinstance(t, T) for t in x)
                 y = list(x)
                 cout = sum(t.C for t in x)
-            elif m in ("Detect", "Segment", "OBB", "Pose"):
+            elif m in ("Detect", "Segment", "OBB", "Pose", "v10Detect"):
                 xs = x if isinstance(x, list) else [x]
                 assert all(isinstance(t, T) for t in xs)
                 if m == "Segment":  # head.py:175-197; npr scaled like parse_model does (tasks.py:1082-1083)
@@ -1095,6 +1183,10 @@ class Plan:
                         raise NotImplementedError(f"{name}: Pose with kpt_shape ({nkpt}, {ndim}): 1 to 64 keypoints of 2 or 3 channels are accelerated")
                     self.detect(name, xs, args[0], legacy, nk=nkpt * ndim, kdim=ndim)
                     self.meta.update(task="pose", nk=nkpt * ndim, kpt_shape=(nkpt, ndim))  # (only a pose plan's meta has these keys)
+                elif m == "v10Detect":  # head.py:592-625: Detect with end2end = True and the light class branch whatever the graph holds
+                    if i != len(layers) - 1:
+                        raise NotImplementedError(f"{name}: v10Detect is accelerated as the last layer only")
+                    self.detect(name, xs, args[0], False, end2end=True)
                 else:
                     self.detect(name, xs, args[0], legacy)
                 y, cout = None, 0

@@ -51,7 +51,7 @@ from .engine import YoloEngine
 from .plan import Plan, qkv_perm
 from .weights import BN_EPS, repconv_form
 
-SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify", "Pose")
+SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify", "Pose", "v10Detect")
 
 
 def _on_device(t) -> bool:
@@ -132,18 +132,23 @@ def max_stride(cfg: dict) -> int:
     return gs
 
 
-def _head_exports(model) -> bool:
-    """Whether the last layer of a reference model (BaseModel.model, an nn.Sequential) has its `export` flag set."""
+def _head_attr(model, attr: str, default):
+    """`attr` of the last layer of a reference model (BaseModel.model, an nn.Sequential), `default` where there is none."""
     seq = getattr(model, "model", None)
     kids = list(seq.children()) if isinstance(seq, torch.nn.Module) else []
-    return bool(kids and getattr(kids[-1], "export", False))
+    return getattr(kids[-1], attr, default) if kids else default
+
+
+def _head_exports(model) -> bool:
+    """Whether the last layer of a reference model has its `export` flag set."""
+    return bool(_head_attr(model, "export", False))
 
 
 FP32_MODES = {"engine_fp32x": "fp32x", "engine_fp32": "fp32", "engine": "fp16", "reference": None}
 
 
 def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_inputs: Optional[str] = None,
-               tta: Optional[str] = None):
+               tta: Optional[str] = None, e2e_raw: bool = True):
     """Install the engine behind ``model.forward``.  Returns the same model object.
 
     fp32_inputs: what an fp32 image tensor gets (the reference's ``predict()`` default is ``half=False``,
@@ -166,13 +171,20 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
 
     tta: what ``augment=True`` (test-time augmentation, nn/tasks.py:354-370) gets on a ``DetectionModel``: ``"engine"`` (default)
     the engine's three scaled passes + HIP glue (YoloEngine.forward_augment), in whichever precision the call runs;
-    ``"reference"`` the original forward.  ``BSY_TTA`` overrides the default; ``state["tta_calls"]`` counts engine TTA calls."""
+    ``"reference"`` the original forward.  ``BSY_TTA`` overrides the default; ``state["tta_calls"]`` counts engine TTA calls.
+
+    A YOLOv10 model (a ``v10Detect`` head) returns the engine's pair ``(rows, {"one2many": [...], "one2one": [...]})``, the reference's
+    own return value in eval (head.py:96-98); ``max_det`` is read from the head (``model.model[-1].max_det``) when the engine is built.
+    e2e_raw: True (default) keeps the raw maps of both head copies in that dict -- the validator's loss reads them during training --;
+    False runs the rows-only plan, without the one2many branches, and the dict holds ``None`` for every level.  ``augment=True`` (the
+    reference does not augment an end2end model, tasks.py:356) and a head with ``export`` set keep their own forward."""
     import os
     cfg = cfg_of(model)
     support, gs = _graph_facts(cfg)  # gs: a P6 graph takes multiples of 64; anything else goes to the reference forward, as non-multiples of 32 do
     orig_forward = model.forward
     classify = cfg["head"][-1][2] == "Classify"
     pose = cfg["head"][-1][2] == "Pose"
+    e2e = cfg["head"][-1][2] == "v10Detect"
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
              "tta_calls": 0, "support": support, "failed": set(), "repconv": None}
     fp32_mode = fp32_inputs or os.environ.get("BSY_FP32_INPUTS", "engine_fp32x")
@@ -184,7 +196,8 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
         raise ValueError(f"tta must be 'engine' or 'reference', not {tta_mode!r}")
 
     def _engine_for(dev: torch.device, precision: str = "fp16") -> YoloEngine:
-        key = (dev.index or 0, _weights_version(model))
+        max_det = int(_head_attr(model, "max_det", 300)) if e2e else 300  # v10Detect.max_det (head.py:601), read at every build
+        key = (dev.index or 0, _weights_version(model), max_det)
         if state["key"] != key:
             for k in ("engine", "engine32"):
                 if state[k] is not None:
@@ -202,7 +215,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
             # so a rebuild after a weight reload or a fuse() sees the form the model holds now
             state["repconv"] = repconv_form(sd)
             state[slot] = YoloEngine(cfg, sd, device=dev.index or 0, bn_eps=model_bn_eps(model), precision=precision,
-                                     repconv=state["repconv"])
+                                     repconv=state["repconv"], max_det=max_det)
         return state[slot]
 
     def forward(self, x, *args, **kwargs):
@@ -214,13 +227,14 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
         # end2end), and then visualize / embed / profile are ignored as predict() does (tasks.py:134-136); anything else keeps its
         # own forward (which reverts to single-scale or augments in torch)
         if augment:
-            if tta_mode != "engine" or type(self).__name__ != "DetectionModel" or getattr(self, "end2end", False):
+            if tta_mode != "engine" or type(self).__name__ != "DetectionModel" or getattr(self, "end2end", False) or e2e:
                 state["fallbacks"] += 1
                 return orig_forward(x, *args, **kwargs)
             visualize = embed = profile = False
         # Classify.export (head.py:285, :304): y alone, the exporter's business; Pose.export (head.py:250, :255-272): y alone, and
         # kpts_decode's export branch is other arithmetic
-        if (classify or pose) and _head_exports(self):
+        # v10Detect.export (head.py:98): the rows alone
+        if (classify or pose or e2e) and _head_exports(self):
             state["fallbacks"] += 1
             return orig_forward(x, *args, **kwargs)
         if (self.training or visualize or embed or profile or args or not isinstance(x, torch.Tensor)
@@ -244,7 +258,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
                 "(the fp16 product path, ~3x faster again, |dscore| up to 6e-3), reference (the original forward); predict(half=True) "
                 "runs the fp16 path.", precision, fp32_mode)
         try:
-            y, raws = _engine_for(x.device, precision)(x, augment=bool(augment))
+            y, raws = _engine_for(x.device, precision)(x, augment=bool(augment), want_raw=bool(e2e_raw) or not e2e)
         except (_L.BsyError, NotImplementedError, AssertionError) as e:  # a shape / graph the engine rejects: the reference runs it
             if verbose:
                 print(f"bs_yolo_amd: falling back to the reference forward ({e})")

@@ -140,6 +140,8 @@ def get_sliced_prediction(image, detection_model, slice_height: int = 640, slice
     each slice to the ultralytics predictor); None = feed the slices natively when their size is a multiple of the model's largest stride
     (`detection_model.max_stride`: 64 for a P6 graph; 32 where the model does not say), else imgsz 640.
     Slices larger than the image shrink to it (get_slice_bboxes)."""
+    if getattr(detection_model, "end2end", False):  # (B, K, 6) rows, not a (B, 4 + nc, A) prediction: nothing here runs NMS on them
+        raise NotImplementedError("sliced prediction on an end2end (v10Detect) engine is not implemented: its forward returns top-k rows")
     dev = detection_model.device if hasattr(detection_model, "device") else torch.device("cuda:0")
     img = _as_device_image(image, dev)
     H, W = int(img.shape[0]), int(img.shape[1])

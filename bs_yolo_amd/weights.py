@@ -73,6 +73,19 @@ def fold_repvgg(sd: Mapping[str, torch.Tensor], prefix: str, eps: float = BN_EPS
     return w3 + torch.nn.functional.pad(w1, [1, 1, 1, 1]), b3 + b1
 
 
+def fold_repvggdw(sd: Mapping[str, torch.Tensor], prefix: str, eps: float = BN_EPS):
+    """(weight (C, 1, 7, 7), bias) fp32 of RepVGGDW (block.py:3818-3877; CIB's third stage with lk=True): SiLU(conv(x) + conv1(x)), a depthwise
+    7x7 and a depthwise 3x3 Conv with BatchNorm each, folded as its fuse() does (:3853-3877) -- each branch folded with its BN, the 3x3
+    kernel zero-padded to 7x7, kernels and biases added.  A model that went through fuse() holds the result as conv.weight / conv.bias
+    (`conv1` is gone) and is taken as it is; the keys tell the two forms apart, as for fold_repvgg."""
+    if prefix + ".conv1.conv.weight" not in sd:
+        return _f32(sd[prefix + ".conv.weight"]), _f32(sd[prefix + ".conv.bias"])
+    w7, b7 = fold_conv_bn(sd, prefix + ".conv", eps)
+    w3, b3 = fold_conv_bn(sd, prefix + ".conv1", eps)
+    assert w7.shape[-1] == 7 and w3.shape[-1] == 3 and w7.shape[1] == w3.shape[1] == 1, (prefix, tuple(w7.shape), tuple(w3.shape))
+    return w7 + torch.nn.functional.pad(w3, [2, 2, 2, 2]), b7 + b3
+
+
 _REPVGG_KEY = re.compile(r"\.cv[23]\.0\.m\.\d+\.cv1\.(conv1\.conv|conv)\.weight$")
 
 
@@ -155,7 +168,7 @@ def depthwise(w, b):
 
 # ---- sources: where a record's (w, b) come from in the state dict.  Per source the parameters it reads -- (key, the module's own
 # shape, synth_state_dict's draw), in the order they are drawn -- and the reader (sd, r, eps) -> fp32 (w, b) of the module ----
-DW_KINDS = ("dw", "dwg", "dwg_plain", "dwg_ext")
+DW_KINDS = ("dw", "dwg", "dwg_plain", "dwg_ext", "repvggdw")
 
 
 def _he(fan: int):  # He-normal
@@ -225,6 +238,11 @@ def _repvgg(r):  # conv.py:296-397, un-fused: a 3x3 and a 1x1 Conv + BN
     return _conv_bn_params(r.name + ".conv1", co, ci, 3, 3) + _conv_bn_params(r.name + ".conv2", co, ci, 1, 1)
 
 
+def _repvggdw(r):  # block.py:3818-3877, un-fused: a depthwise 7x7 and a depthwise 3x3 Conv + BN
+    co = _module_dims(r)[0]
+    return _conv_bn_params(r.name + ".conv", co, 1, 7, 7) + _conv_bn_params(r.name + ".conv1", co, 1, 3, 3)
+
+
 def _ela(r):  # ELA (nn/Addmodules/ELA.py:36-72): three scalar mixing weights, two Conv1d over k taps, one GroupNorm
     c, k = r.cout, r.k
     return ([(f"{r.name}.{s}", (1,), lambda g, shape: torch.randn(*shape, generator=g)) for s in ("ch_weight", "sp_weight", "res_weight")]
@@ -245,7 +263,8 @@ _BARE = (_bare, _read_bare)
 SOURCES = {"conv": _CONV_BN, "first": _CONV_BN, "first_s2d": _CONV_BN, "dw": _CONV_BN, "dwg": _CONV_BN, "dwg_ext": _CONV_BN,
            "conv2": (_conv2, _read_conv2), "plain": _BARE, "dwg_plain": _BARE, "deconv": (_deconv, _read_deconv),
            "refconv": (_refconv, lambda sd, r, eps: fold_refconv(sd, r.name)),
-           "repvgg": (_repvgg, lambda sd, r, eps: fold_repvgg(sd, r.name, eps)), "ela": (_ela, _read_ela)}
+           "repvgg": (_repvgg, lambda sd, r, eps: fold_repvgg(sd, r.name, eps)),
+           "repvggdw": (_repvggdw, lambda sd, r, eps: fold_repvggdw(sd, r.name, eps)), "ela": (_ela, _read_ela)}
 
 
 def record_keys(r: WRec) -> List[str]:
@@ -348,9 +367,9 @@ def synth_state_dict(plan: Plan, seed: int = 0, cls_gain: float = 0.1, cls_bias:
         for key, shape, draw in SOURCES[r.kind][0](r):
             if key in sd:
                 continue
-            if r.kind == "plain" and ".cv3." in r.name:  # Detect's class branch: damped weights, a constant bias (nothing drawn)
+            if r.kind == "plain" and "cv3." in r.name:  # Detect's class branch (v10Detect's one2one_cv3 too): damped weights, a constant bias (nothing drawn)
                 sd[key] = draw(g, shape) * cls_gain if key.endswith(".weight") else torch.full(shape, float(cls_bias))
-            elif r.kind == "plain" and ".cv2." in r.name and key.endswith(".bias"):  # the box branch
+            elif r.kind == "plain" and "cv2." in r.name and key.endswith(".bias"):  # the box branch
                 sd[key] = torch.rand(*shape, generator=g) + 0.5
             else:
                 sd[key] = draw(g, shape)

@@ -113,7 +113,11 @@ enum bsy_op_kind {
                             * mid_c).  The same bits as the launches it replaces: CONV 1x1, DWCONV_G 5x5 and, with res, ADD                   */
     BSY_OP_ADD = 25,       /* dst = src0 + src1 elementwise (both storage types; f16: the sum is taken in f32 and rounded once); dst may be
                             * src0's view                                                                                                  */
-    BSY_OP_ELA = 15       /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
+    BSY_OP_E2E_TOPK = 26,  /* v10Detect.postprocess (head.py:151-172) as a plan op: the two launches of bsy_end2end_topk (csrc/topk.hip), every
+                            * precision mode.  src0 = the pre-top-k tensor (B, 4 + nc, A) of out_dtype (an external slot or a buffer), nc, A,
+                            * ksize = max_det (1 .. 4096), dst = the rows (B, min(max_det, A), 6) f32, res = scratch of
+                            * bsy_end2end_topk_workspace_bytes(B, A, nc, max_det) bytes.  The bits of bsy_end2end_topk on the same tensor          */
+    BSY_OP_ELA = 15      /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
                             * res = f32 scratch buffer of (2 (H + W) + 2) * C floats per image                          */
@@ -129,14 +133,17 @@ typedef struct bsy_op {
     bsy_view res;           /* residual added AFTER the activation (Bottleneck / PSABlock shortcut); buf<0 if none */
     int32_t ksize, stride, pad;
     int32_t act;            /* 0 identity, 1 SiLU.  DECODE (nm = ne = 0): 1 = the DFL sums run in the fused head epilogue's order whatever the
-                             * level count, so that a Detect plan with the decode launch returns the bits of the plan with the fused head */
+                             * level count, so that a Detect plan with the decode launch returns the bits of the plan with the fused head;
+                             * DECODE, bit 1 (value 2, nm = ne = nk = 0): rows 0..3 are the corners (x1, y1, x2, y2) * stride -- dist2bbox with
+                             * xywh=False, the box form of an end2end head (head.py:148) -- instead of (cx, cy, w, h) * stride */
     int32_t out_f32;        /* output mode.  0: dst f16.  1: dst f32 (final head convs feeding BSY_OP_DECODE).
                              * 2 / 3: fused Detect decoder -- the conv is the last layer of a class (2) / box (3) branch
                              * of level `level` and writes rows of the prediction tensor directly: dst = y view
                              * (external slot, C = 4 + nc), nl = the conv's output channels (64 / nc), box[0] = that
                              * level's raw map (external slot, optional),
                              * A = anchors of all levels, lvl_h[1] = first anchor of this level, lvl_stride[0] = stride,
-                             * out_dtype = dtype of y and of the raw map */
+                             * out_dtype = dtype of y and of the raw map.
+                             * 4: mode 3 storing the corners (x1, y1, x2, y2) * stride instead of (cx, cy, w, h) * stride (an end2end head) */
     int32_t dst_scale, dst_dy, dst_dx; /* ConvTranspose2d(2,2,s2) as 4 scattered 1x1 convs: out pixel (s*oh+dy, s*ow+dx); scale 1 = plain */
     int64_t w_off, b_off;   /* byte offsets into the engine's weight blob (packed f16 weights / f32 bias) */
     int32_t heads, key_dim, head_dim; /* ATTN */
@@ -384,6 +391,12 @@ int bsy_attention_pe(const void* qkv, int ld, int B, int H, int W, int heads, in
 int bsy_detect_decode(const float* const* box, const int* ldb, const float* const* cls, const int* ldc,
                       const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
                       const float* lvl_stride, int nl, int B, int nc, int nm, void* y, int y_dtype, bsy_stream stream);
+/* bsy_detect_decode with the box form as an argument.  xyxy = 0: rows 0..3 = (cx, cy, w, h) * stride, bsy_detect_decode bit for bit.
+ * xyxy = 1 (nm = 0): rows 0..3 = (x1, y1, x2, y2) * stride = (anchor - lt) * stride, (anchor + rb) * stride in f32, rounded once to
+ * y_dtype -- dist2bbox with xywh=False, what an end2end head decodes (head.py:148) and bsy_end2end_topk reads. */
+int bsy_detect_decode_fmt(const float* const* box, const int* ldb, const float* const* cls, const int* ldc,
+                          const float* const* msk, const int* ldm, const int* lvl_h, const int* lvl_w,
+                          const float* lvl_stride, int nl, int B, int nc, int nm, int xyxy, void* y, int y_dtype, bsy_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * non_max_suppression (utils/ops.py:167-316) incl. xywh2xyxy (:416-433) and the greedy IoU suppression the
