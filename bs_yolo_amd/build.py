@@ -36,6 +36,7 @@ SOURCES = {
     "ghost_fused.hip": [],
     "elementwise.hip": [],
     "pool_down.hip": ["-ffp-contract=off"],  # the average must round like ATen's: ordered fp32 sum, one product, one rounding
+    "maxpool.hip": [],
     "attention.hip": [],
     "detect.hip": [],
     "nms.hip": ["-ffp-contract=off"],

@@ -89,8 +89,10 @@ struct ConvFirstArgs {
     const float* b = nullptr;  // [CoutPad]
     half_t* dst = nullptr;
     int ldd = 0, Cout = 0, act = 0;
+    int pool = 0;  // 1 (stride 1 only): MaxPool2d(2, 2, 0) in the epilogue; OH x OW stays the conv's extent, dst is (OH / 2) x (OW / 2)
 };
 int launch_conv_first(const ConvFirstArgs& a, hipStream_t s);
+bool first_pool_supported(int Cout, int H, int W);
 
 // Fused stem (stem_fused.hip): image -> Conv 3x3 s2 (3 -> C0) -> Conv 3x3 s2 (C0 -> C1), layer 0 kept on chip.
 struct StemArgs {
@@ -319,6 +321,9 @@ int launch_sppf_pool(half_t* buf, int ld, int B, int H, int W, int C, hipStream_
 // pool_down.hip: src / dst = first element of the buffers, soff / doff = first channel of the views; dtype BSY_F16 / BSY_F32
 int launch_pool_down(const void* src, int lds_, int soff, void* dst, int ldd, int doff, int B, int H, int W, int C, int mode, int dtype,
                      hipStream_t s);
+// maxpool.hip: the same calling convention; mode 0 = MaxPool2d(2, 2, 0), 1 = ZeroPad2d((0, 1, 0, 1)) + MaxPool2d(2, 1, 0)
+int launch_maxpool(const void* src, int lds_, int soff, void* dst, int ldd, int doff, int B, int H, int W, int C, int mode, int dtype,
+                   hipStream_t s);
 int launch_s2d(const void* img, int img_dtype, int B, int H, int W, half_t* dst, int ldd, hipStream_t s);
 
 struct AttnArgs {

@@ -1,6 +1,6 @@
 // What a bsy_op record MEANS: one builder per op kind and storage type turns a record (include/bsyolo.h) into the launch arguments of
 // its kernel family (common.h).  This is the one place where the record's overloaded fields are read -- `heads` as a weight row length,
-// `pad` as a kernel width, `lvl_h[1]` as a first anchor, `act` as a DFL order, `level` as a pooling mode -- for plan_ops.hip (the two
+// `pad` as a kernel width, `lvl_h[1]` as a first anchor, `act` as a DFL order, `level` as a pooling mode (POOL_DOWN, MAXPOOL) -- for plan_ops.hip (the two
 // dispatch switches) and for the tuners of engine.hip, which need a conv's arguments without a launch.  A builder takes the record, the
 // resolver and the base of the weight blob, and returns false on refusal with the error text set.  Nothing here launches, allocates or
 // needs a device or a plan object: tools/op_args_check.cpp drives the builders over a host vector.
@@ -89,6 +89,17 @@ inline bool build_views(Views<T>& v, const bsy_op& op, Resolver& R, int n) {
 inline bool build_pool_down(const char*& src, char*& dst, const bsy_op& op, Resolver& R) {
     src = R.base(op.src0); dst = R.base(op.dst);
     if (R.ok && op.src0.C != op.dst.C) { R.ok = false; bsy_set_error("pool_down: %d channels in, %d out", op.src0.C, op.dst.C); }
+    return R.ok;
+}
+// MAXPOOL (both storage types): POOL_DOWN's calling convention; `level` = the mode, (H, W) the source's extent, (OH, OW) the destination's
+inline bool build_maxpool(const char*& src, char*& dst, const bsy_op& op, Resolver& R) {
+    src = R.base(op.src0); dst = R.base(op.dst);
+    const int oh = op.level ? op.H : op.H / 2, ow = op.level ? op.W : op.W / 2;
+    if (R.ok && (op.src0.C != op.dst.C || op.OH != oh || op.OW != ow)) {
+        R.ok = false;
+        bsy_set_error("maxpool: %d channels in, %d out; mode %d on %d x %d gives %d x %d, the record says %d x %d", op.src0.C, op.dst.C, op.level, op.H,
+                      op.W, oh, ow, op.OH, op.OW);
+    }
     return R.ok;
 }
 // NHWC2NCHW: dst = the whole BCHW tensor, an optional output -- `skip`: its slot is unbound, nothing is resolved or launched
@@ -219,6 +230,16 @@ inline bool build_conv_first(ConvFirstArgs& a, const bsy_op& op, Resolver& R, co
     a.ksize = op.ksize; a.stride = op.stride; a.pad = op.pad;
     a.w = (const void*)(wb + op.w_off); a.b = (const float*)(wb + op.b_off);
     a.dst = R.h(op.dst); a.ldd = op.dst.ld; a.Cout = op.dst.C; a.act = op.act;
+    return R.ok;
+}
+// FIRST_POOL: CONV_FIRST's record with ksize / stride / pad = the conv's (3, 1, 1) and (OH, OW) = the POOLED extent the destination has
+inline bool build_first_pool(ConvFirstArgs& a, const bsy_op& op, Resolver& R, const char* wb) {
+    if (!build_conv_first(a, op, R, wb)) return false;
+    a.pool = 1; a.OH = op.H; a.OW = op.W;
+    if (op.stride != 1 || op.OH != op.H / 2 || op.OW != op.W / 2 || (op.H & 1) || (op.W & 1)) {
+        R.ok = false;
+        bsy_set_error("first_pool: a stride-1 conv on an even image, pooled to half its extent (got s=%d, %d x %d -> %d x %d)", op.stride, op.H, op.W, op.OH, op.OW);
+    }
     return R.ok;
 }
 inline bool build_stem(StemArgs& a, const bsy_op& op, Resolver& R, const char* wb) {

@@ -104,6 +104,7 @@ extern "C" int bsy_stem_fused(const void* img, int img_dtype, int B, int H, int 
     return launch_stem_fused(a, (hipStream_t)stream);
 }
 
+extern "C" int bsy_first_pool_supported(int C2, int H, int W) { return first_pool_supported(C2, H, W) ? 1 : 0; }
 extern "C" int bsy_stem_fused_supported(int C0, int C1, int H, int W) { return stem_fused_supported(C0, C1, H, W) ? 1 : 0; }
 
 extern "C" int bsy_bottleneck_fused(const void* x, int ldx, int B, int H, int W, int C, int CH, const void* w1,
@@ -191,6 +192,11 @@ extern "C" int bsy_sppf_pool(void* buf, int ld, int B, int H, int W, int C, bsy_
 extern "C" int bsy_pool_down(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
                              bsy_stream stream) {
     return launch_pool_down(x, ldx, xoff, y, ldy, yoff, B, H, W, C, mode, dtype, (hipStream_t)stream);
+}
+
+extern "C" int bsy_maxpool2d(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
+                             bsy_stream stream) {
+    return launch_maxpool(x, ldx, xoff, y, ldy, yoff, B, H, W, C, mode, dtype, (hipStream_t)stream);
 }
 
 extern "C" int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale,

@@ -16,7 +16,7 @@ int run(bool (*build)(Args&, const bsy_op&, Resolver&, const char*), int (*launc
 int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
     if (op.prec < 0 || op.prec > 2) BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown precision mode %d", op.prec);
     // fp32 correctness mode (bsy_op.prec == 1, and 2 = fp32x) first: same op records, f32 views, kernels of ref32.hip.  DECODE, RAW_NCHW
-    // and CLASSIFY_TAIL consume f32 logit maps in every mode, POOL_DOWN takes the storage type as an argument, E2E_TOPK reads a tensor of
+    // and CLASSIFY_TAIL consume f32 logit maps in every mode, POOL_DOWN and MAXPOOL take the storage type as an argument, E2E_TOPK reads a tensor of
     // out_dtype: they break out of this switch into the common one.
     Views<float> v32;
     if (op.prec) switch (op.kind) {
@@ -64,6 +64,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
             return build_ela32(a, src, dst, op, R, wb) ? launch_ela32(a, src, dst, s) : BSY_ERR_ARG;
         }
         case BSY_OP_POOL_DOWN:
+        case BSY_OP_MAXPOOL:
         case BSY_OP_CLASSIFY_TAIL:
         case BSY_OP_DECODE:
         case BSY_OP_RAW_NCHW:
@@ -75,6 +76,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
     Views<half_t> v;
     switch (op.kind) {
         case BSY_OP_CONV_FIRST: return run(build_conv_first, launch_conv_first, op, R, wb, s);
+        case BSY_OP_FIRST_POOL: return run(build_first_pool, launch_conv_first, op, R, wb, s);
         case BSY_OP_STEM: return run(build_stem, launch_stem_fused, op, R, wb, s);
         case BSY_OP_BNECK: return run(build_bneck, launch_bneck_fused, op, R, wb, s);
         case BSY_OP_C3K2: return run(build_c3k2, launch_c3k2_fused, op, R, wb, s);
@@ -116,6 +118,13 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
             if (!build_pool_down(src, dst, op, R)) return BSY_ERR_ARG;
             return launch_pool_down(src, op.src0.ld, op.src0.coff, dst, op.dst.ld, op.dst.coff, op.B, op.H, op.W, op.src0.C, op.level,
                                     op.prec ? BSY_F32 : BSY_F16, s);
+        }
+        case BSY_OP_MAXPOOL: {  // f16 views, f32 in the fp32-storage modes
+            const char* src;
+            char* dst;
+            if (!build_maxpool(src, dst, op, R)) return BSY_ERR_ARG;
+            return launch_maxpool(src, op.src0.ld, op.src0.coff, dst, op.dst.ld, op.dst.coff, op.B, op.H, op.W, op.src0.C, op.level,
+                                  op.prec ? BSY_F32 : BSY_F16, s);
         }
         case BSY_OP_RAW_NCHW: {
             RawNchwArgs a;

@@ -10,7 +10,9 @@ graphs cfg/models/11/yolo11-pose.yaml, v8/yolov8-pose.yaml and v8/yolov8-pose-p6
 "yolov8-p6" under a Pose head, with a top-level `kpt_shape` (task "pose"), and the ghost graphs cfg/models/v8/yolov8-ghost.yaml,
 yolov8-ghost-p2.yaml and yolov8-ghost-p6.yaml (families "yolov8-ghost", "yolov8-ghost-p2", "yolov8-ghost-p6": GhostConv downsamplers and
 C3Ghost blocks on the YOLOv8 layouts, detect only), and the YOLOv10 graphs cfg/models/v10/yolov10{n,s,m,b,l,x}.yaml (family
-"yolov10": one layout, a literal table per size of where C2fCIB stands and whether it holds the 7x7 RepVGGDW; a v10Detect head).  They are
+"yolov10": one layout, a literal table per size of where C2fCIB stands and whether it holds the 7x7 RepVGGDW; a v10Detect head), and the
+YOLOv3 graphs cfg/models/v3/yolov3.yaml, yolov3-spp.yaml and yolov3-tiny.yaml (families "yolov3", "yolov3-spp", "yolov3-tiny": one size
+each, `depth_multiple` / `width_multiple` of 1.0 instead of a scales table; detect only).  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -289,6 +291,47 @@ def _yolov10(size: str) -> dict:
     }
 
 
+# YOLOv3, cfg/models/v3/yolov3.yaml:10-46: darknet-53 -- a stride-1 image conv, then top-level Bottlenecks (chains of up to 8, parse_model's
+# nn.Sequential) between stride-2 convs -- and a head of Bottlenecks without shortcut, the first of each upper level reading the Concat
+# of an upsampled map directly (a 3x3 conv over it).  yolov3-spp.yaml differs in layer 12 alone: SPP instead of a 1x1 Conv.
+def _yolov3(spp: bool) -> dict:
+    return {
+        "backbone": [
+            [-1, 1, "Conv", [32, 3, 1]], [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "Bottleneck", [64]],
+            [-1, 1, "Conv", [128, 3, 2]], [-1, 2, "Bottleneck", [128]], [-1, 1, "Conv", [256, 3, 2]],
+            [-1, 8, "Bottleneck", [256]], [-1, 1, "Conv", [512, 3, 2]], [-1, 8, "Bottleneck", [512]],
+            [-1, 1, "Conv", [1024, 3, 2]], [-1, 4, "Bottleneck", [1024]],
+        ],
+        "head": [
+            [-1, 1, "Bottleneck", [1024, False]], [-1, 1, "SPP", [512, [5, 9, 13]]] if spp else [-1, 1, "Conv", [512, 1, 1]],
+            [-1, 1, "Conv", [1024, 3, 1]], [-1, 1, "Conv", [512, 1, 1]], [-1, 1, "Conv", [1024, 3, 1]],
+            [-2, 1, "Conv", [256, 1, 1]], _UP, _cat(8),
+            [-1, 1, "Bottleneck", [512, False]], [-1, 1, "Bottleneck", [512, False]], [-1, 1, "Conv", [256, 1, 1]], [-1, 1, "Conv", [512, 3, 1]],
+            [-2, 1, "Conv", [128, 1, 1]], _UP, _cat(6),
+            [-1, 1, "Bottleneck", [256, False]], [-1, 2, "Bottleneck", [256, False]],
+        ],
+        "detect_from": [27, 22, 15],
+    }
+
+
+# cfg/models/v3/yolov3-tiny.yaml:10-37: conv / max-pool pairs down to stride 32, a zero pad + stride-1 pool that keeps the 1/32 map's size, and
+# a two-level head (P4, P5) whose upper level is one 3x3 conv over the Concat of an upsampled map
+_YOLOV3_TINY = {
+    "backbone": [
+        [-1, 1, "Conv", [16, 3, 1]], [-1, 1, "nn.MaxPool2d", [2, 2, 0]], [-1, 1, "Conv", [32, 3, 1]], [-1, 1, "nn.MaxPool2d", [2, 2, 0]],
+        [-1, 1, "Conv", [64, 3, 1]], [-1, 1, "nn.MaxPool2d", [2, 2, 0]], [-1, 1, "Conv", [128, 3, 1]], [-1, 1, "nn.MaxPool2d", [2, 2, 0]],
+        [-1, 1, "Conv", [256, 3, 1]], [-1, 1, "nn.MaxPool2d", [2, 2, 0]], [-1, 1, "Conv", [512, 3, 1]],
+        [-1, 1, "nn.ZeroPad2d", [[0, 1, 0, 1]]], [-1, 1, "nn.MaxPool2d", [2, 1, 0]],
+    ],
+    "head": [
+        [-1, 1, "Conv", [1024, 3, 1]], [-1, 1, "Conv", [256, 1, 1]], [-1, 1, "Conv", [512, 3, 1]],
+        [-2, 1, "Conv", [128, 1, 1]], _UP, _cat(8), [-1, 1, "Conv", [256, 3, 1]],
+    ],
+    "detect_from": [19, 15],
+}
+_V3_FAMILIES = {"yolov3": lambda: _yolov3(False), "yolov3-spp": lambda: _yolov3(True), "yolov3-tiny": lambda: _YOLOV3_TINY}
+
+
 # Classification graphs: backbones and scales tables of their own, one Classify layer as the head.  cfg/models/11/yolo11-cls.yaml:8-30:
 # the detect backbone without SPPF, and C2PSA reaches max_channels at m / l / x (512, where detect's table says the same)
 _YOLO11_CLS = {
@@ -327,7 +370,15 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
     stock_cfg("yolo11", "n", 1, "pose", kpt_shape=(17, 3)) == 'yolo11n-pose.yaml' (families "yolo11", "yolov8" and "yolov8-p6" only;
     `kpt_shape` = (keypoints, 2 or 3 channels each) is read by this task alone, becomes the dict's top-level `kpt_shape` and has to be
     given: the four-argument call stock_cfg(family, scale, nc, "pose") raises ValueError for every family, as it always has);
-    stock_cfg("yolov10", "s") == 'yolov10s.yaml' (scales n, s, m, b, l, x; detect only)."""
+    stock_cfg("yolov10", "s") == 'yolov10s.yaml' (scales n, s, m, b, l, x; detect only);
+    stock_cfg("yolov3-tiny", None) == 'yolov3-tiny.yaml' (families "yolov3", "yolov3-spp", "yolov3-tiny": one size each, so `scale` must be
+    None or ""; detect only; the dict carries depth_multiple = width_multiple = 1.0 and no `scales`)."""
+    if family in _V3_FAMILIES:
+        if scale not in (None, "") or task != "detect":
+            raise ValueError(f"{family}: scale {scale!r} / task {task!r} (one size, scale None; detect only)")
+        fam = copy.deepcopy(_V3_FAMILIES[family]())
+        return {"nc": nc, "depth_multiple": 1.0, "width_multiple": 1.0, "backbone": fam["backbone"],
+                "head": fam["head"] + [[fam["detect_from"], 1, "Detect", ["nc"]]]}
     if task == "classify":
         if family not in _CLS_FAMILIES:
             raise ValueError(f"{family}: no classification graph (yolo11, yolov8)")

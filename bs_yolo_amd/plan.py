@@ -138,6 +138,12 @@ LANE_KINDS = (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP
 Output = namedtuple("Output", "name slot shape dtype raw_only")  # one external output of a plan (Plan._ext, Plan.outputs)
 
 
+@dataclass
+class _ZeroPadded:
+    """What an accepted nn.ZeroPad2d [[0, 1, 0, 1]] layer hands to the nn.MaxPool2d [2, 1, 0] behind it: its input, unpadded."""
+    src: T
+
+
 class Plan:
     """Flat op list + workspace buffer table for one (B, H, W)."""
 
@@ -209,6 +215,10 @@ class Plan:
         # GhostConv (1x1 cv1 + depthwise 5x5 cv2 + the GhostBottleneck shortcut) as one launch (csrc/ghost_fused.hip).  Not in SWITCHES: every
         # entry of that table changes one of the graphs the switch test builds, and none of those holds a GhostConv
         self.fuse_ghost = not self.f32_mode and os.environ.get("BSY_FUSE_GHOST", "1") != "0"
+        # yolov3-tiny's stride-1 image conv and the MaxPool2d(2, 2, 0) behind it as one launch (BSY_OP_FIRST_POOL, csrc/conv_first.hip).  Not in
+        # SWITCHES for the same reason: no graph of the switch test starts with that pair
+        self.fuse_first_pool = not self.f32_mode and os.environ.get("BSY_FUSE_FIRST_POOL", "1") != "0"
+        self._up_real: Dict[Tuple[int, int, int], T] = {}  # upsampled views a 3x3 conv has had materialised (conv below)
         self.buf_bytes: List[int] = []
         self.ops: List[dict] = []
         self.wrecs: "OrderedDict[str, WRec]" = OrderedDict()
@@ -317,6 +327,11 @@ class Plan:
         assert 1 <= len(srcs) <= 2, "at most two concat operands per conv"
         H, W = srcs[0].H, srcs[0].W
         assert all(t.H == H and t.W == W and (t.f32 == self.f32_mode) for t in srcs)
+        if k != 1 and any(t.up for t in srcs):
+            # the conv kernels gather nearest x2 for 1x1 convs alone (csrc/conv_select.hip): a 3x3 conv over a Concat whose operand is a
+            # virtual Upsample (yolov3-tiny's layer 19, cv1 of YOLOv3's head Bottlenecks) reads that operand from a map of its own,
+            # written once by OP_COPY through up0, in every precision
+            srcs = [self._materialise(f"{name}.up{j}", t) if t.up else t for j, t in enumerate(srcs)]
         cin = sum(t.C for t in srcs)
         if not self.f32_mode and any(t.C % 8 or t.coff % 8 for t in srcs):
             # csrc/conv_gemm.hip reads its sources in 16-byte (8-channel) pieces; a block whose hidden width is 12 or 20 channels
@@ -415,6 +430,45 @@ class Plan:
     def copy(self, name: str, src: T, dst: T):
         assert dst.C == src.C and dst.H == src.H and dst.W == src.W and not dst.up
         self._emit(L.OP_COPY, name, src0=src, dst=dst)
+
+    def _materialise(self, name: str, src: T) -> T:
+        """The full-size map of a virtual nearest x2 Upsample view, written by one OP_COPY the first time a consumer needs it."""
+        key = (src.buf, src.coff, src.C)
+        if key not in self._up_real:
+            real = self.alloc(src.C, src.H, src.W)
+            real.cmap = src.cmap
+            self.copy(name, src, real)
+            self._up_real[key] = real
+        return self._up_real[key]
+
+    def maxpool(self, name: str, src: T, mode: int) -> T:
+        """csrc/maxpool.hip.  mode 0: nn.MaxPool2d(2, 2, 0) on an even map; mode 1: nn.ZeroPad2d((0, 1, 0, 1)) + nn.MaxPool2d(2, 1, 0), the
+        padded taps counting as 0.0."""
+        if src.up or src.cmap is not None:
+            raise NotImplementedError(f"{name}: a max pool over an upsampled or zero-padded view is not accelerated")
+        if mode == 0 and (src.H % 2 or src.W % 2 or src.H < 2 or src.W < 2):
+            raise NotImplementedError(f"{name}: MaxPool2d(2, 2, 0) on an odd {src.H} x {src.W} map is not accelerated")
+        v = 4 if self.f32_mode else 8
+        if src.C % v or src.coff % v:
+            raise NotImplementedError(f"{name}: {src.C} channels at offset {src.coff} are not multiples of {v}")
+        dst = self.alloc(src.C, *((src.H, src.W) if mode else (src.H // 2, src.W // 2)))
+        self._emit(L.OP_MAXPOOL, name, src0=src, dst=dst, level=mode, ksize=2, stride=1 if mode else 2, pad=0)
+        return dst
+
+    def top_bottleneck(self, name: str, x: Union[T, List[T]], c2: int, shortcut: bool, k=(3, 3), e: float = 0.5) -> T:
+        """A Bottleneck as a top-level layer (YOLOv3's darknet-53 and its head; block.py:3405-3419).  A two-operand Concat goes to cv1 as two
+        sources; the identity shortcut exists where c1 == c2 (:3413), which a Concat input of the shipped graphs never has."""
+        if isinstance(x, T):
+            dst = self.alloc(c2, x.H, x.W)
+            self.bottleneck(name, x, dst, shortcut, k, e)
+            return dst
+        c_ = int(c2 * e)
+        if shortcut and sum(t.C for t in x) == c2:
+            raise NotImplementedError(f"{name}: a Bottleneck with a shortcut over a Concat is not accelerated")
+        if c_ % 8 and not self.f32_mode:
+            raise NotImplementedError(f"{name}: a Bottleneck with a hidden width of {c_} channels over a Concat is not on the fp16 path (multiples of 8)")
+        t = self.conv(name + ".cv1", x, c_, k[0], 1)
+        return self.conv(name + ".cv2", t, c2, k[1], 1)
 
     # ---- module expansions -----------------------------------------------------------------------------------
     def bottleneck(self, name: str, x: T, dst: T, shortcut: bool, k=(3, 3), e=0.5, rep: bool = False):
@@ -1043,18 +1097,20 @@ class Plan:
             n = max(round(n * depth), 1) if n > 1 else n
             if f != -1:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
+            if isinstance(x, _ZeroPadded) and m != "nn.MaxPool2d":
+                raise NotImplementedError(f"model.{i - 1}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] (model.{i} is {m})")
             if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv", "GhostConv", "C3Ghost", "GhostBottleneck",
-                     "C2fCIB", "PSA"):
+                     "C2fCIB", "PSA", "Bottleneck", "SPP"):
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m == "Conv":
                     k, s = arg(1, 1), arg(2, 1)
                     pad = k // 2 if arg(3, None) is None else args[3]
                     if i == 0:
-                        if (k, s, pad) not in ((3, 2, 1), (6, 2, 2)):
-                            raise NotImplementedError(f"image conv k={k} s={s} p={pad}: 3x3 s2 p1 or 6x6 s2 p2 only")
+                        if (k, s, pad) not in ((3, 2, 1), (3, 1, 1), (6, 2, 2)):
+                            raise NotImplementedError(f"image conv k={k} s={s} p={pad}: 3x3 s2 p1, 3x3 s1 p1 or 6x6 s2 p2 only")
                         y = self.conv_first(name, c2, k, s, pad)
                     else:
-                        assert isinstance(x, T)
+                        assert isinstance(x, T) or all(isinstance(t, T) for t in x)  # (a list: a two-operand Concat, yolov3-tiny's layer 19)
                         if pad != k // 2:
                             raise NotImplementedError(f"Conv with padding {pad} != k // 2 is not accelerated")
                         y = self.conv(name, x, c2, k, s)
@@ -1108,6 +1164,21 @@ class Plan:
                 elif m == "SPPF":
                     assert isinstance(x, T) and arg(1, 5) == 5
                     y = self.sppf(name, x, c2)
+                elif m == "SPP":  # block.py:3088-3111, args [c2, k]: cv2(cat(x', m5 x', m9 x', m13 x')), x' = cv1(x).  Stride-1 max pools
+                    # compose -- m5 . m5 = m9, m5 . m5 . m5 = m13, bit for bit -- so k = (5, 9, 13) is SPPF's dataflow under the same names
+                    if not isinstance(x, T) or list(arg(1, (5, 9, 13))) != [5, 9, 13]:
+                        raise NotImplementedError(f"{name}: SPP with k = {arg(1, None)} (k = [5, 9, 13] on one input is accelerated)")
+                    if (x.C // 2) % 8 and not self.f32_mode:
+                        raise NotImplementedError(f"{name}: SPP with a hidden width of {x.C // 2} channels is not on the fp16 path (multiples of 8)")
+                    y = self.sppf(name, x, c2)
+                elif m == "Bottleneck":  # block.py:3405-3419, args [c2, shortcut, g, k, e]; n > 1: parse_model's nn.Sequential (tasks.py:1094)
+                    if arg(2, 1) != 1:
+                        raise NotImplementedError(f"{name}: Bottleneck with g = {args[2]} is not accelerated")
+                    if n > 1 and (not isinstance(x, T) or x.C != c2):
+                        raise NotImplementedError(f"{name}: {n} chained Bottlenecks need an input of their own width ({c2} channels)")
+                    y = x
+                    for j in range(n):
+                        y = self.top_bottleneck(name if n == 1 else f"{name}.{j}", y, c2, bool(arg(1, True)), tuple(arg(3, (3, 3))), arg(4, 0.5))
                 else:
                     assert isinstance(x, T)
                     y = self.c2psa(name, x, c2, n)
@@ -1137,6 +1208,29 @@ class Plan:
                 assert isinstance(x, T)
                 y = self.ela(name, x)
                 cout = x.C
+            elif m == "nn.ZeroPad2d":
+                # accepted in one place: [[0, 1, 0, 1]] in front of nn.MaxPool2d [2, 1, 0] that reads it alone (yolov3-tiny's layers 11 + 12);
+                # the pair is one MAXPOOL of mode 1, emitted at the pool
+                nxt = layers[i + 1] if i + 1 < len(layers) else None
+                if not isinstance(x, T) or [list(a) if isinstance(a, (list, tuple)) else a for a in args] != [[0, 1, 0, 1]]:
+                    raise NotImplementedError(f"{name}: nn.ZeroPad2d {args} (only [[0, 1, 0, 1]] on one input is accelerated)")
+                if nxt is None or nxt[0] != -1 or nxt[2] != "nn.MaxPool2d" or list(nxt[3]) != [2, 1, 0]:
+                    raise NotImplementedError(f"{name}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] reading it alone")
+                for j, (fj, _, _, _) in enumerate(layers):
+                    if j != i + 1 and any((v if v >= 0 else j + v) == i for v in ([fj] if isinstance(fj, int) else fj)):
+                        raise NotImplementedError(f"{name}: the output of nn.ZeroPad2d is read by model.{j} as well: the padded map is never stored")
+                y = _ZeroPadded(x)
+                cout = x.C
+            elif m == "nn.MaxPool2d":
+                k, s, p = arg(0, None), arg(1, None), arg(2, 0)
+                if isinstance(x, _ZeroPadded):
+                    assert (k, s, p) == (2, 1, 0)
+                    y = self.maxpool(name, x.src, 1)
+                elif isinstance(x, T) and (k, s, p) == (2, 2, 0) and len(args) <= 3:
+                    y = self.maxpool(name, x, 0)
+                else:
+                    raise NotImplementedError(f"{name}: nn.MaxPool2d {args} (only [2, 2, 0], and [2, 1, 0] behind nn.ZeroPad2d [[0, 1, 0, 1]], are accelerated)")
+                cout = y.C
             elif m == "nn.Upsample":
                 assert isinstance(x, T) and not x.up and args[1] == 2 and args[2] == "nearest"
                 y = T(x.buf, x.ld, x.coff, x.C, x.H * 2, x.W * 2, True, x.f32)
@@ -1205,9 +1299,32 @@ class Plan:
             outs.append(y)
             chans.append(cout)
             x = y
-        self.layer_out = outs
+        self.layer_out = [None if isinstance(t, _ZeroPadded) else t for t in outs]
         self.meta.update(scale=scale, n_layers=len(layers), legacy=legacy)
         self._fuse_stem()
+        self._fuse_first_pool()
+
+    def _fuse_first_pool(self):
+        """Peephole: layer 0 (image conv 3x3 s1 p1) + layer 1 (MaxPool2d(2, 2, 0) fed by layer 0 alone) -> one OP_FIRST_POOL launch
+        (csrc/conv_first.hip); layer 0's map is then never materialised (layer_out[0] = None), as in _fuse_stem."""
+        if not self.fuse_first_pool or len(self.ops) < 2:
+            return
+        a, b = self.ops[0], self.ops[1]
+        if a["kind"] != L.OP_CONV_FIRST or b["kind"] != L.OP_MAXPOOL or (a["ksize"], a["stride"], a["pad"]) != (3, 1, 1) or b["level"] != 0:
+            return
+        mid = a["dst"]
+        if b["src0"] is not mid or not kernel_takes("first_pool", mid.C, self.H, self.W):
+            return
+        for o in self.ops[2:]:  # layer 0 must have no other reader
+            for key in ("src0", "src1", "res"):
+                t = o.get(key)
+                if t is not None and t.buf == mid.buf:
+                    return
+        self.buf_bytes[mid.buf] = 16  # never written
+        self._emit(L.OP_FIRST_POOL, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], H=self.H, W=self.W, ksize=3, stride=1,
+                   pad=1, act=1, wkey=a["wkey"], in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"])
+        self.ops[0:2] = [self.ops.pop()]  # (layer 0's flops are counted already)
+        self.layer_out[0] = None
 
     def _fuse_stem(self):
         """Peephole: layer 0 (image conv) + layer 1 (3x3 s2 conv fed by layer 0 alone) -> one OP_STEM launch

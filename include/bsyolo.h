@@ -57,7 +57,7 @@ typedef struct bsy_view {
 } bsy_view;
 
 enum bsy_op_kind {
-    BSY_OP_CONV_FIRST = 0, /* image (BCHW f16/f32, C=3) -> conv kxk s2 + bias + act -> NHWC f16            */
+    BSY_OP_CONV_FIRST = 0, /* image (BCHW f16/f32, C=3) -> conv 3x3 s2 or s1, pad 1, + bias + act -> NHWC f16 */
     BSY_OP_CONV = 1,       /* implicit-GEMM conv k in {1,3}, s in {1,2}, MFMA f16, fused bias/SiLU/residual   */
     BSY_OP_DWCONV = 2,     /* depthwise 3x3 s1 + bias (+SiLU) (+residual)                                     */
     BSY_OP_SPPF_POOL = 3,  /* three chained MaxPool2d(5,1,2) -> channel slices of the SPPF concat buffer      */
@@ -117,6 +117,12 @@ enum bsy_op_kind {
                             * precision mode.  src0 = the pre-top-k tensor (B, 4 + nc, A) of out_dtype (an external slot or a buffer), nc, A,
                             * ksize = max_det (1 .. 4096), dst = the rows (B, min(max_det, A), 6) f32, res = scratch of
                             * bsy_end2end_topk_workspace_bytes(B, A, nc, max_det) bytes.  The bits of bsy_end2end_topk on the same tensor          */
+    BSY_OP_MAXPOOL = 27,   /* the 2x2 max pools of YOLOv3-tiny (csrc/maxpool.hip, bsy_maxpool2d): src0 (H x W) -> dst (OH x OW), f16 views (f32 in
+                            * the fp32-storage modes).  `level` carries the MODE, as for POOL_DOWN: 0: MaxPool2d(2, 2, 0), H and W even, dst
+                            * H/2 x W/2; 1: ZeroPad2d((0, 1, 0, 1)) + MaxPool2d(2, 1, 0), dst H x W, taps past the border count as 0.0          */
+    BSY_OP_FIRST_POOL = 28, /* image conv 3x3 stride 1 pad 1 + bias + act, then MaxPool2d(2, 2, 0), as one launch (csrc/conv_first.hip; fp16 path
+                            * only): CONV_FIRST's record with stride = 1 and (OH, OW) = (H / 2, W / 2), the extent of dst; H, W even
+                            * (bsy_first_pool_supported).  The conv's map is never stored; the bits of CONV_FIRST -> MAXPOOL mode 0           */
     BSY_OP_ELA = 15      /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
@@ -161,7 +167,7 @@ typedef struct bsy_op {
                              * bit bsy_kpts_decode of the logits rounded to y's dtype, and `res` (an external slot, optional: skipped
                              * when unbound) the rounded logits themselves as (B, nk, A).  (The word was reserved2: offsets unchanged) */
     int32_t in_dtype, out_dtype; /* CONV_FIRST input dtype; DECODE/RAW output dtype */
-    int32_t level;          /* RAW_NCHW: which level; output = external slot in dst.buf.  POOL_DOWN: the mode (0 / 1) */
+    int32_t level;          /* RAW_NCHW: which level; output = external slot in dst.buf.  POOL_DOWN, MAXPOOL: the mode (0 / 1) */
     int32_t lane;           /* 0 = caller's stream; k > 0 = plan-owned side stream k (independent op chains, e.g. the
                              * per-level Detect branches, run concurrently; forked from lane 0 at first use) */
     int32_t tuned_cfg;      /* conv: 1 + configuration id recorded by bsy_plan_autotune (0 = heuristic) */
@@ -171,7 +177,7 @@ typedef struct bsy_op {
     int64_t aux_off[18];    /* MSCA_SPATIAL: (weights, bias) byte offsets of its nine depthwise convs */
     int32_t prec;           /* 0: the fp16-storage product path.  1: fp32 correctness mode -- every workspace view is NHWC f32,
                              * dense conv weights are f32 [k*k*Cin][Cout], arithmetic is fp32 (csrc/ref32.hip); kinds CONV_FIRST,
-                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL.
+                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL, MAXPOOL.
                              * 2: fp32x mode -- storage and every non-conv kernel as in mode 1; dense convs (CONV) multiply on the
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
@@ -292,7 +298,7 @@ int bsy_attention_f32(const float* qkv, int ld, int B, int N, int heads, int key
  * C1 == 3 (the image conv) packs a zero 4th input channel: K = k*k*4. */
 int bsy_conv_packed_dims(int C2, int C1, int ksize, int* cout_pad, int* k_pad);
 
-/* First conv (3x3, stride 2) from a BCHW image (f16 or f32): w packed like bsy_conv2d's with a zero 4th input
+/* First conv (3x3, pad 1, stride 2 or 1) from a BCHW image (f16 or f32): w packed like bsy_conv2d's with a zero 4th input
  * channel ([CoutPad][64] f16, k = (kh, kw, c4)), b f32 [CoutPad] -> NHWC f16. */
 int bsy_conv_first(const void* img, int img_dtype, int B, int H, int W, const void* w, const float* b, void* y,
                    int ldy, int C2, int ksize, int stride, int act, bsy_stream stream);
@@ -365,6 +371,17 @@ int bsy_sppf_pool(void* buf, int ld, int B, int H, int W, int C, bsy_stream stre
  * H, W even and >= 2; C, ldx, ldy, xoff, yoff multiples of 8 (f16) / 4 (f32); anything else is BSY_ERR_ARG. */
 int bsy_pool_down(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
                   bsy_stream stream);
+
+/* The 2x2 max pools of YOLOv3-tiny (cfg/models/v3/yolov3-tiny.yaml; csrc/maxpool.hip), NHWC views as for bsy_pool_down.
+ * mode 0: y (B,H/2,W/2) = max_pool2d(x, 2, 2, 0); H, W even.
+ * mode 1: y (B,H,W) = max_pool2d(pad(x, (0, 1, 0, 1)), 2, 1, 0): a tap past the last row or column counts as 0.0 (ZeroPad2d pads the
+ *         data; it is not the pool's -inf padding), so an all-negative window on that border returns 0.
+ * A NaN wins and stays, as in ATen: F.max_pool2d's bits in both dtypes.  C, ldx, ldy, xoff, yoff multiples of 8 (f16) / 4 (f32);
+ * anything else is BSY_ERR_ARG. */
+int bsy_maxpool2d(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int B, int H, int W, int C, int mode, int dtype,
+                  bsy_stream stream);
+/* 1: BSY_OP_FIRST_POOL takes an image conv of C2 output channels on an H x W image (C2 a multiple of 8 up to 128; H, W even). */
+int bsy_first_pool_supported(int C2, int H, int W);
 
 /* Attention core (block.py:4267-4286): qkv NHWC f16 with channel order [q(all heads) | k(all heads) | v(all heads)],
  * out[pixel][head*head_dim + d] = sum_j softmax_j(q_i . k_j * scale) v_j[d].  key_dim in {16, 32, 48, 64}, head_dim in {32, 64, 96, 128}

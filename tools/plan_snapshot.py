@@ -32,7 +32,7 @@ FIXTURE = ROOT / "tests" / "golden" / "plan_snapshots.json"
 SWITCH_ENV = {"fuse_stem": "BSY_FUSE_STEM", "fuse_bneck": "BSY_FUSE_BNECK", "fuse_head": "BSY_FUSE_HEAD", "fuse_dwpw": "BSY_FUSE_DWPW",
               "merge_c3k": "BSY_MERGE_C3K", "fuse_msca": "BSY_FUSE_MSCA", "fuse_tail": "BSY_FUSE_TAIL", "fuse_pmsfa": "BSY_FUSE_PMSFA",
               "fuse_attn_pe": "BSY_FUSE_ATTN_PE"}
-PLAN_ENV = tuple(SWITCH_ENV.values()) + ("BSY_FUSE_BOXTAIL", "BSY_FUSE_GHOST", "BSY_LANES")  # what a Plan reads from the environment
+PLAN_ENV = tuple(SWITCH_ENV.values()) + ("BSY_FUSE_BOXTAIL", "BSY_FUSE_GHOST", "BSY_LANES", "BSY_FUSE_FIRST_POOL")  # what a Plan reads from the environment
 ALL_OFF = {k: False for k in SWITCH_ENV}
 OPTIONS = {"default": {}, "unfused": ALL_OFF, "latency_lanes": dict(latency=True, lanes=True)}
 # (family, scale, task, (B, H, W))
