@@ -548,6 +548,24 @@ __device__ __forceinline__ f32x4 silu4_f(f32x4 x) {
     for (int i = 0; i < 4; ++i) r[i] = silu_f(x[i]);
     return r;
 }
+// ReLU (activation id 2 of include/bsyolo.h), the one form every precision mode uses: a compare and a select, exact.  NaN fails the
+// compare and passes through, as torch.relu returns it (fmaxf would answer 0); the sign of a zero result is not specified.
+__device__ __forceinline__ float relu_f(float x) { return x < 0.0f ? 0.0f : x; }
+__device__ __forceinline__ f32x4 relu4_f(f32x4 x) {
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = relu_f(x[i]);
+    return r;
+}
+// The activation of a CONV_FIRST / FIRST_POOL / STEM / CONV op on the fp16 path: act = 0 identity, 1 SiLU, 2 ReLU.  Every fp16 conv
+// kernel exists twice: <name>, whose epilogue is `if (act) silu` as it always was -- instruction for instruction the kernel it was
+// before id 2 existed (tools/isa_diff.py) --, and <name>_relu, the same body instantiated with RELU = true, whose epilogue is
+// relu_f / relu4_f whatever `act` says.  The launchers pick by `act == 2`.  Every form that chose inside ONE kernel cost the SiLU path
+// occupancy, scratch or 0.2 - 5 % of the YOLO11s step: docs/experiments.md, "ReLU as activation id 2".
+// The fp32-storage kernels (conv32x_mfma.hip, conv32_mfma.hip, ref32.hip) pass their own SiLU (silu_rcp, silu32: no asm, so the choice
+// compiles to selects there).
+template <class SiLU>
+__device__ __forceinline__ float act32(float t, int act, SiLU silu) { return act == 2 ? relu_f(t) : act ? silu(t) : t; }
 // SiLU of the exact fp32 mode (ref32.hip, conv32_mfma.hip): the scalar and the MFMA kernels return the same bits only while both
 // evaluate this the same way, so every user is built with -ffp-contract=off -fno-vectorize (build.py).
 __device__ __forceinline__ float silu32(float x) { return x / (1.0f + expf(-x)); }

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void conv32_mfma_kernel(const
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu32(t) : t;
+                    v[e] = act32(t, a.act, silu32);
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);

@@ -64,7 +64,7 @@ __device__ __forceinline__ void epilogue_block(f32x16 (&acc)[NT][PB], const int 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float t = acc[an][b][4 * q + e];
-                v[e] = a.act ? silu_rcp(t) : t;
+                v[e] = act32(t, a.act, silu_rcp);
             }
             *reinterpret_cast<f32x4*>(wl + lj * RS + an * 32 + 8 * q + 4 * lh) = v;
         }
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void conv32x_mfma_kernel(const Conv32Args a
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu_rcp(t) : t;
+                    v[e] = act32(t, a.act, silu_rcp);
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(512, 2) void conv32x_big_kernel(const Conv32Args a,
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu_rcp(t) : t;
+                    v[e] = act32(t, a.act, silu_rcp);
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(256, 2) void conv32x_patch_kernel(const Conv32Args 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float tt = acc[an][b][4 * q + e];
-                    v[e] = a.act ? silu_rcp(tt) : tt;
+                    v[e] = act32(tt, a.act, silu_rcp);
                 }
                 if (a.res) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);

@@ -76,7 +76,7 @@ __device__ __forceinline__ void dma16_buf(bsy_rsrc_t r, unsigned voff, unsigned 
 __device__ __forceinline__ void dma16_buf(bsy_rsrc_t, unsigned, unsigned, half_t*) {}
 #endif
 
-template <int MT, int NT>
+template <int MT, int NT, bool RELU = false>
 __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[NT][MT], int m0, int n0, int wm, int wn,
                                               int lrow, int lh) {
     const int ohw = p.OH * p.OW;
@@ -110,7 +110,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[NT][
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             float t = acc[a][b][4 * g + e];  // (the accumulators started at the bias)
-                            v[e] = p.act ? silu_f(t) : t;
+                            v[e] = RELU ? relu_f(t) : (p.act ? silu_f(t) : t);
                         }
                         if (p.res && mvalid) {
                             const half4 rv = *reinterpret_cast<const half4*>(p.res + dpix * p.ldr + c);
@@ -144,7 +144,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[NT][
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float t = acc[a][b][4 * g + e];
-                    if (p.act) t = silu_f(t);
+                    if constexpr (RELU) t = relu_f(t);
+                    else if (p.act) t = silu_f(t);
                     v[e] = t;
                 }
                 const bool full = c + 3 < p.Cout;
@@ -344,7 +345,7 @@ __device__ __forceinline__ void conv_epilogue_cls_lds(const ConvK& p, f32x16 (&a
 // the whole kernel (3x).  Instead: bias + SiLU in registers -> fp16 tile [TM][TN] in LDS (the DMA ring is free after
 // the K loop) -> every thread moves 16-byte pieces with consecutive lanes on consecutive channels of one pixel row,
 // adding the residual (also read coalesced) on the way.
-template <int TM, int TN, int MT, int NT, int NTHR>
+template <int TM, int TN, int MT, int NT, int NTHR, bool RELU = false>
 __device__ __forceinline__ void conv_epilogue_lds(const ConvK& p, f32x16 (&acc)[NT][MT], half_t* stile, int m0, int n0,
                                                   int wm, int wn, int lrow, int lh, int tid) {
     constexpr int LDT = TN + 8;  // padded tile row (halves)
@@ -359,7 +360,8 @@ __device__ __forceinline__ void conv_epilogue_lds(const ConvK& p, f32x16 (&acc)[
                 const int c = cl + 8 * g + 4 * lh;
                 half4 o;
                 f32x4 t = f32x4{acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]};
-                if (p.act) t = silu4_f(t);
+                if constexpr (RELU) t = relu4_f(t);
+                else if (p.act) t = silu4_f(t);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = (half_t)t[e];
                 *reinterpret_cast<half4*>(stile + prow * LDT + c) = o;

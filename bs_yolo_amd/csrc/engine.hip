@@ -71,9 +71,30 @@ static int plan_make_lanes(bsy_plan* p) {
     return BSY_OK;
 }
 
+// bsy_op.act per kind (include/bsyolo.h): an activation id 0 / 1 / 2 (identity, SiLU, ReLU) for the four kinds whose kernels take one; a
+// field of its own meaning for DWCONV_G (a channel count), DECODE (bits) and ATTN (the pe flag); a 0 / 1 SiLU switch for every other
+// kind, whose kernels test it for truth -- an id above 1 there would run SiLU and say nothing, so it is refused here, by name.
+static int plan_check_acts(const bsy_op* ops, int n_ops, const char* who) {
+    static const char* const names[] = {"CONV_FIRST", "CONV", "DWCONV", "SPPF_POOL", "ATTN", "DECODE", "RAW_NCHW", "NHWC2NCHW", "STEM", "BNECK",
+                                        "DWCONV_G", "COPY", "GAP", "MSCA_MIX", "MUL", "ELA", "DWPW", "MSCA_SPATIAL", "C3K2", "S2D", "PMSFA_TAIL",
+                                        "CHAIN", "POOL_DOWN", "CLASSIFY_TAIL", "GHOST", "ADD", "E2E_TOPK", "MAXPOOL", "FIRST_POOL"};
+    static_assert(sizeof(names) / sizeof(names[0]) == BSY_OP_KIND_COUNT && BSY_OP_FIRST_POOL == BSY_OP_KIND_COUNT - 1 && BSY_OP_ELA == 15 &&
+                  BSY_OP_DWPW == 16 && BSY_OP_GHOST == 24, "names[] is indexed by bsy_op_kind: a new kind adds its name here, in the enum's order");
+    for (int i = 0; i < n_ops; ++i) {
+        const int kind = ops[i].kind, act = ops[i].act;
+        if (kind == BSY_OP_DWCONV_G || kind == BSY_OP_DECODE || kind == BSY_OP_ATTN) continue;
+        const bool ids = kind == BSY_OP_CONV_FIRST || kind == BSY_OP_FIRST_POOL || kind == BSY_OP_STEM || kind == BSY_OP_CONV;
+        if (act < 0 || act > (ids ? 2 : 1))
+            BSY_FAIL(BSY_ERR_ARG, "%s: op %d (%s) has act = %d: %s", who, i, kind >= 0 && kind < (int)(sizeof(names) / sizeof(names[0])) ? names[kind] : "?",
+                     act, ids ? "0 identity, 1 SiLU, 2 ReLU" : "this kind takes 0 or 1 (SiLU); ReLU (2) exists in CONV_FIRST, FIRST_POOL, STEM and CONV");
+    }
+    return BSY_OK;
+}
+
 extern "C" int bsy_plan_create(bsy_engine* e, const bsy_op* ops, int n_ops, const int64_t* buf_bytes, int n_bufs,
                                bsy_plan** out) {
     if (!e || !ops || n_ops <= 0 || !out || n_bufs < 0 || (n_bufs && !buf_bytes)) BSY_FAIL(BSY_ERR_ARG, "plan_create: bad argument");
+    if (const int rc = plan_check_acts(ops, n_ops, "plan_create")) return rc;
     if (!e->weights) BSY_FAIL(BSY_ERR_STATE, "plan_create: load weights first");
     HIP_TRY(hipSetDevice(e->device));
     bsy_plan* p = new bsy_plan();
@@ -124,6 +145,7 @@ extern "C" int bsy_plan_create_arena(bsy_engine* e, const bsy_op* ops, int n_ops
                                      int n_bufs, int64_t arena_bytes, bsy_plan** out) {
     if (!e || !ops || n_ops <= 0 || !out || n_bufs < 0 || (n_bufs && (!buf_bytes || !buf_off)) || arena_bytes < 0)
         BSY_FAIL(BSY_ERR_ARG, "plan_create_arena: bad argument");
+    if (const int rc = plan_check_acts(ops, n_ops, "plan_create_arena")) return rc;
     if (!e->weights) BSY_FAIL(BSY_ERR_STATE, "plan_create_arena: load weights first");
     for (int i = 0; i < n_bufs; ++i)
         if (buf_bytes[i] < 0 || buf_off[i] < 0 || (buf_off[i] & 255) || buf_off[i] + buf_bytes[i] > arena_bytes)

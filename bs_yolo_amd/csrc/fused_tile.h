@@ -38,12 +38,15 @@ __device__ __forceinline__ f32x4 acc_group(const f32x16& acc, int g) {
     return f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
 }
 
-// Activation (SiLU if act), rounded to f16: the four values a lane stores to an LDS tile as one 8-byte piece.  The epilogues
+// Activation, rounded to f16: the four values a lane stores to an LDS tile as one 8-byte piece.  RELU = false: SiLU if act, the form
+// every fused block kernel had; RELU = true (stem_fused_kernel_relu alone): ReLU, whatever act says.  The epilogues
 // return the piece and the caller stores it (`*reinterpret_cast<half4*>(dst) = act_f16(..)`): the address is then evaluated after
 // the arithmetic, as in the loops these replace -- with `dst` as an argument the register allocation of every caller moved.
+template <bool RELU = false>
 __device__ __forceinline__ half4 act_f16(f32x4 t, int act) {
     half4 o;
-    if (act) t = silu4_f(t);
+    if constexpr (RELU) t = relu4_f(t);
+    else if (act) t = silu4_f(t);
 #pragma unroll
     for (int q = 0; q < 4; ++q) o[q] = (half_t)t[q];
     return o;
@@ -51,9 +54,11 @@ __device__ __forceinline__ half4 act_f16(f32x4 t, int act) {
 // The same for a pixel of an intermediate patch that may lie outside the map, where the next conv's zero padding belongs:
 // keep = all ones inside, 0 outside.  An AND with the word, not a select on `inside`: the select makes the compiler branch
 // around each SiLU.
+template <bool RELU = false>
 __device__ __forceinline__ half4 act_f16(f32x4 t, int act, unsigned keep) {
     union { half4 h; unsigned u[2]; } o;
-    if (act) t = silu4_f(t);
+    if constexpr (RELU) t = relu4_f(t);
+    else if (act) t = silu4_f(t);
 #pragma unroll
     for (int q = 0; q < 4; ++q) o.h[q] = (half_t)t[q];
     o.u[0] &= keep;

@@ -10,6 +10,7 @@ static int same_out(int n, int k, int stride) { return (n + 2 * (k / 2) - k) / s
 extern "C" int bsy_conv2d(const void* x, int ldx, int B, int H, int W, int C1, const void* w, const float* b, void* y,
                           int ldy, int C2, int ksize, int stride, int act, const void* res, int ldr, int y_f32,
                           bsy_stream stream) {
+    if (act < 0 || act > 2) BSY_FAIL(BSY_ERR_ARG, "conv2d: act = %d (0 identity, 1 SiLU, 2 ReLU)", act);
     if (!x || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv2d: null pointer");
     ConvArgs a;
     a.src0 = (const half_t*)x; a.ld0 = ldx; a.C0 = C1; a.B = B; a.H = H; a.W = W;
@@ -46,6 +47,7 @@ static int launch_conv32_impl(const Conv32Args& a, int impl, bsy_stream stream) 
 
 extern "C" int bsy_conv2d_f32(const float* x, int ldx, int B, int H, int W, int C1, const float* w, const float* b, float* y, int ldy,
                               int C2, int ksize, int stride, int act, const float* res, int ldr, int impl, bsy_stream stream) {
+    if (act < 0 || act > 2) BSY_FAIL(BSY_ERR_ARG, "conv2d_f32: act = %d (0 identity, 1 SiLU, 2 ReLU)", act);
     if (!x || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv2d_f32: null pointer");
     if (!conv32_shape_ok(B, H, W, C1, C2, ksize, stride, ldx, ldy, res, ldr) || impl < 0 || impl > 2)
         BSY_FAIL(BSY_ERR_ARG, "conv2d_f32: bad shape");
@@ -55,6 +57,7 @@ extern "C" int bsy_conv2d_f32(const float* x, int ldx, int B, int H, int W, int 
 extern "C" int bsy_conv2d_f32x(const float* x, int ldx, int B, int H, int W, int C1, const void* w_hi, const void* w_lo, int k_pad,
                                const float* b, float* y, int ldy, int C2, int ksize, int stride, int act, const float* res, int ldr,
                                bsy_stream stream) {
+    if (act < 0 || act > 2) BSY_FAIL(BSY_ERR_ARG, "conv2d_f32x: act = %d (0 identity, 1 SiLU, 2 ReLU)", act);
     if (!x || !w_hi || !w_lo || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv2d_f32x: null pointer");
     if (!conv32_shape_ok(B, H, W, C1, C2, ksize, stride, ldx, ldy, res, ldr) || k_pad < ksize * ksize * C1 || (k_pad & 31))
         BSY_FAIL(BSY_ERR_ARG, "conv2d_f32x: bad shape");
@@ -66,6 +69,7 @@ extern "C" int bsy_conv2d_f32x(const float* x, int ldx, int B, int H, int W, int
 
 extern "C" int bsy_conv_first_f32(const void* img, int img_dtype, int B, int H, int W, const float* w, const float* b, float* y, int ldy,
                                  int C2, int ksize, int stride, int act, int impl, bsy_stream stream) {
+    if (act < 0 || act > 2) BSY_FAIL(BSY_ERR_ARG, "conv_first_f32: act = %d (0 identity, 1 SiLU, 2 ReLU)", act);
     if (!img || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv_first_f32: null pointer");
     if (!conv32_shape_ok(B, H, W, 3, C2, ksize, stride, 3, ldy, nullptr, 0) || impl < 0 || impl > 2 || (img_dtype != BSY_F16 && img_dtype != BSY_F32))
         BSY_FAIL(BSY_ERR_ARG, "conv_first_f32: bad shape");
@@ -83,6 +87,7 @@ extern "C" int bsy_attention_f32(const float* qkv, int ld, int B, int N, int hea
 
 extern "C" int bsy_conv_first(const void* img, int img_dtype, int B, int H, int W, const void* w, const float* b,
                               void* y, int ldy, int C2, int ksize, int stride, int act, bsy_stream stream) {
+    if (act < 0 || act > 2) BSY_FAIL(BSY_ERR_ARG, "conv_first: act = %d (0 identity, 1 SiLU, 2 ReLU)", act);
     if (!img || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "conv_first: null pointer");
     ConvFirstArgs a;
     a.img = img; a.img_dtype = img_dtype; a.B = B; a.H = H; a.W = W; a.ksize = ksize; a.stride = stride; a.pad = ksize / 2;
@@ -93,6 +98,7 @@ extern "C" int bsy_conv_first(const void* img, int img_dtype, int B, int H, int 
 
 extern "C" int bsy_stem_fused(const void* img, int img_dtype, int B, int H, int W, const void* w0, const float* b0, int C0,
                               const void* w1, const float* b1, int C1, void* y, int ldy, int act, bsy_stream stream) {
+    if (act < 0 || act > 2) BSY_FAIL(BSY_ERR_ARG, "stem: act = %d (0 identity, 1 SiLU, 2 ReLU)", act);
     if (!img || !w0 || !b0 || !w1 || !b1 || !y) BSY_FAIL(BSY_ERR_ARG, "stem: null pointer");
     StemArgs a;
     a.img = img; a.img_dtype = img_dtype; a.B = B; a.H = H; a.W = W;
@@ -110,6 +116,7 @@ extern "C" int bsy_stem_fused_supported(int C0, int C1, int H, int W) { return s
 extern "C" int bsy_bottleneck_fused(const void* x, int ldx, int B, int H, int W, int C, int CH, const void* w1,
                                     const float* b1, const void* w2, const float* b2, void* y, int ldy, int act,
                                     bsy_stream stream) {
+    if (act < 0 || act > 1) BSY_FAIL(BSY_ERR_ARG, "bottleneck: act = %d (this kernel takes 0 or 1, SiLU; ReLU exists in the conv, image-conv and stem calls)", act);
     if (!x || !w1 || !b1 || !w2 || !b2 || !y) BSY_FAIL(BSY_ERR_ARG, "bottleneck: null pointer");
     if (C <= 0 || CH <= 0) BSY_FAIL(BSY_ERR_ARG, "bottleneck: bad widths");
     BneckArgs a;
@@ -138,6 +145,7 @@ extern "C" int bsy_c3k2_fused_supported(int Cin, int c, int C2) { return c3k2_fu
 
 extern "C" int bsy_dwconv(const void* x, int ldx, int B, int H, int W, int C, int kh, int kw, int stride, const float* w,
                           int wld, const float* b, void* y, int ldy, int act, bsy_stream stream) {
+    if (act < 0 || act > 1) BSY_FAIL(BSY_ERR_ARG, "dwconv: act = %d (this kernel takes 0 or 1, SiLU; ReLU exists in the conv, image-conv and stem calls)", act);
     if (kh < 1 || kw < 1 || (stride != 1 && stride != 2)) BSY_FAIL(BSY_ERR_ARG, "dwconv: bad kernel / stride");
     DwGenArgs a;
     a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.kh = kh; a.kw = kw; a.stride = stride;
@@ -163,6 +171,7 @@ extern "C" int bsy_ela(const void* x, int ldx, int B, int H, int W, int C, int k
 
 extern "C" int bsy_dwpw_fused(const void* x, int ldx, int B, int H, int W, int C, const float* dww, const float* dwb,
                               const void* w, const float* b, void* y, int ldy, int C2, int act, bsy_stream stream) {
+    if (act < 0 || act > 1) BSY_FAIL(BSY_ERR_ARG, "dwpw_fused: act = %d (this kernel takes 0 or 1, SiLU; ReLU exists in the conv, image-conv and stem calls)", act);
     DwPwArgs a;
     a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.dww = dww; a.dwb = dwb; a.wgt = w; a.bias = b;
     a.dst = (half_t*)y; a.ldd = ldy; a.Cout = C2; a.act = act;
@@ -177,6 +186,7 @@ extern "C" int bsy_ghost_fused_supported(int Cin, int CH) { return ghost_fused_s
 
 extern "C" int bsy_dwconv3x3(const void* x, int ldx, int B, int H, int W, int C, const float* w, const float* b, void* y,
                              int ldy, int act, const void* res, int ldr, bsy_stream stream) {
+    if (act < 0 || act > 1) BSY_FAIL(BSY_ERR_ARG, "dwconv3x3: act = %d (this kernel takes 0 or 1, SiLU; ReLU exists in the conv, image-conv and stem calls)", act);
     if (!x || !w || !b || !y) BSY_FAIL(BSY_ERR_ARG, "dwconv3x3: null pointer");
     DwArgs a;
     a.src = (const half_t*)x; a.lds = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.w = w; a.b = b;

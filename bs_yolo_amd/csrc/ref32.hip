@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void conv32_kernel(const Conv32Args a) {
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
         if (!ok[j]) continue;
-        float v = a.act ? silu32(acc[j]) : acc[j];
+        float v = act32(acc[j], a.act, silu32);
         const size_t pix = (size_t)(n[j] * a.OH + oh[j]) * a.OW + ow[j];
         if (a.res) v += a.res[pix * a.ldr + o];  // shortcut: after the activation (Bottleneck / PSABlock)
         size_t dp = pix;

@@ -80,13 +80,45 @@ def cat_outputs(chunks: List[Mapping[str, Optional[torch.Tensor]]]) -> Dict[str,
     return {k: None if v is None else torch.cat([c[k] for c in chunks]) for k, v in chunks[0].items()}
 
 
+def sppf_form(model, cfg: dict) -> str:
+    """Plan's `sppf_act` of a live reference model.  Read under a ReLU graph (`activation: nn.ReLU()`) alone -- every other graph
+    answers "silu", which the plan ignores there.  Under ReLU every SPPF layer of the yaml is looked at: "relu" where cv1 and cv2 hold
+    nn.ReLU, "silu" where both hold nn.SiLU; layers that cannot be reached, another activation class, or convs that disagree (with each
+    other or between two SPPF layers) raise NotImplementedError: one plan parameter cannot describe that model."""
+    if cfg.get("activation") != "nn.ReLU()":
+        return "silu"
+    forms = set()
+    for i, layer in enumerate(list(cfg.get("backbone", [])) + list(cfg.get("head", []))):
+        if layer[2] != "SPPF":
+            continue
+        try:
+            acts = [model.model[i].cv1.act, model.model[i].cv2.act]
+        except (AttributeError, IndexError, TypeError, KeyError) as e:
+            raise NotImplementedError(f"model.{i}: cannot read SPPF's activations off the model ({type(e).__name__}: {e}); pass sppf_act") from e
+        for name, act in zip(("cv1", "cv2"), acts):
+            if not isinstance(act, (torch.nn.ReLU, torch.nn.SiLU)):
+                raise NotImplementedError(f"model.{i}.{name}: SPPF's activation is {act}: nn.SiLU and nn.ReLU are accelerated")
+            forms.add("relu" if isinstance(act, torch.nn.ReLU) else "silu")
+    if len(forms) > 1:
+        raise NotImplementedError("the model's SPPF convs disagree on their activation (nn.SiLU in some, nn.ReLU in others): not accelerated")
+    return forms.pop() if forms else "silu"
+
+
 class YoloEngine:
     def __init__(self, cfg: dict, state_dict: Mapping[str, torch.Tensor], device: int = 0, bn_eps: float = BN_EPS,
                  autotune: Optional[bool] = None, max_plans: Optional[int] = None, precision: str = "fp16", graph: Optional[bool] = None,
                  graph_ring: int = 3, latency: Optional[bool] = None, repconv: Optional[str] = None, max_det: int = 300,
-                 **switches: Optional[bool]):
+                 sppf_act: Optional[str] = None, **switches: Optional[bool]):
         """switches: the fusion switches of plan.SWITCHES (fuse_stem=False, ...), handed to every plan; None or absent = the switch's
-        environment variable, on where that is unset.  max_det: the rows a v10Detect head's top-k keeps (1 .. 4096; other heads ignore it)."""
+        environment variable, on where that is unset.  max_det: the rows a v10Detect head's top-k keeps (1 .. 4096; other heads ignore it).
+        state_dict: a mapping, or the reference model itself (its state_dict() is taken).  sppf_act: Plan's parameter of that name, what
+        SPPF's two convs apply in a graph under `activation: nn.ReLU()` (YOLOv6) -- "silu" in a model this fork built from the yaml, "relu"
+        in an upstream-pickled one.  None reads it off the model (sppf_form below) where `state_dict` is one; a bare state dict does not
+        say which form it came from, so None then means "silu": pass "relu" for an upstream checkpoint's state dict."""
+        if isinstance(state_dict, torch.nn.Module):
+            sppf_act = sppf_act or sppf_form(state_dict, cfg)
+            state_dict = {k: v.detach().float().cpu() for k, v in state_dict.state_dict().items()}
+        self.sppf_act = sppf_act or "silu"
         if not set(switches) <= set(SWITCHES):
             raise TypeError(f"YoloEngine() got an unexpected keyword argument {sorted(set(switches) - set(SWITCHES))[0]!r}")
         if not torch.cuda.is_available():
@@ -192,7 +224,7 @@ class YoloEngine:
 
     def _fuse_kw(self):
         return dict(self.switches, precision=self.precision, lanes=True if self.graph else None, latency=self.latency, repconv=self.repconv,
-                    max_det=self.max_det)
+                    max_det=self.max_det, sppf_act=self.sppf_act)
 
     # -- plans --------------------------------------------------------------------------------------------------
     def plan_for(self, B: int, H: int, W: int, in_dtype: torch.dtype, out_dtype: torch.dtype, one2many: bool = False):

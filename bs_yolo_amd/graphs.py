@@ -332,6 +332,27 @@ _YOLOV3_TINY = {
 _V3_FAMILIES = {"yolov3": lambda: _yolov3(False), "yolov3-spp": lambda: _yolov3(True), "yolov3-tiny": lambda: _YOLOV3_TINY}
 
 
+# YOLOv6-3.0, cfg/models/v6/yolov6.yaml:5-53: 3x3 / 1x1 Convs only -- stride-2 convs with chains of equal-width 3x3 Convs behind them
+# (repeats 6 / 12 / 18 / 6 in the backbone, 9 in every neck stage; parse_model's nn.Sequential) --, one SPPF, two nn.ConvTranspose2d
+# upsamplers and a legacy Detect; `activation: nn.ReLU()` at the top (plan.py Plan.sppf_act on what that means for SPPF)
+_YOLOV6 = {
+    "scales": {"n": [0.33, 0.25, 1024], "s": [0.33, 0.50, 1024], "m": [0.67, 0.75, 768], "l": [1.00, 1.00, 512], "x": [1.00, 1.25, 512]},
+    "backbone": [
+        [-1, 1, "Conv", [64, 3, 2]], [-1, 1, "Conv", [128, 3, 2]], [-1, 6, "Conv", [128, 3, 1]],
+        [-1, 1, "Conv", [256, 3, 2]], [-1, 12, "Conv", [256, 3, 1]], [-1, 1, "Conv", [512, 3, 2]],
+        [-1, 18, "Conv", [512, 3, 1]], [-1, 1, "Conv", [1024, 3, 2]], [-1, 6, "Conv", [1024, 3, 1]],
+        [-1, 1, "SPPF", [1024, 5]],
+    ],
+    "head": [
+        [-1, 1, "Conv", [256, 1, 1]], [-1, 1, "nn.ConvTranspose2d", [256, 2, 2, 0]], _cat(6), [-1, 1, "Conv", [256, 3, 1]], [-1, 9, "Conv", [256, 3, 1]],
+        [-1, 1, "Conv", [128, 1, 1]], [-1, 1, "nn.ConvTranspose2d", [128, 2, 2, 0]], _cat(4), [-1, 1, "Conv", [128, 3, 1]], [-1, 9, "Conv", [128, 3, 1]],
+        [-1, 1, "Conv", [128, 3, 2]], _cat(15), [-1, 1, "Conv", [256, 3, 1]], [-1, 9, "Conv", [256, 3, 1]],
+        [-1, 1, "Conv", [256, 3, 2]], _cat(10), [-1, 1, "Conv", [512, 3, 1]], [-1, 9, "Conv", [512, 3, 1]],
+    ],
+    "detect_from": [19, 23, 27],
+}
+
+
 # Classification graphs: backbones and scales tables of their own, one Classify layer as the head.  cfg/models/11/yolo11-cls.yaml:8-30:
 # the detect backbone without SPPF, and C2PSA reaches max_channels at m / l / x (512, where detect's table says the same)
 _YOLO11_CLS = {
@@ -400,6 +421,12 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
         fam = copy.deepcopy(_yolov10(scale))
         return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"],
                 "head": fam["head"] + [[fam["detect_from"], 1, "v10Detect", ["nc"]]]}
+    if family == "yolov6":  # detect only; the one stock graph with an `activation` key
+        if scale not in _YOLOV6["scales"] or task != "detect":
+            raise ValueError(f"yolov6: scale {scale!r} / task {task!r} (detect: n, s, m, l, x)")
+        fam = copy.deepcopy(_YOLOV6)
+        return {"nc": nc, "activation": "nn.ReLU()", "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"],
+                "head": fam["head"] + [[fam["detect_from"], 1, "Detect", ["nc"]]]}
     fam = copy.deepcopy(_FAMILIES[family])
     head = list(fam["head"])
     if task == "detect":

@@ -18,6 +18,7 @@ LIB_PATH = Path(os.environ["BSY_LIB"]) if os.environ.get("BSY_LIB") else PKG / "
 BSY_F16, BSY_F32, BSY_U8 = 0, 1, 2
 BSY_EXT_BASE = 0x100000
 BSY_MAX_LEVELS = 4  # include/bsyolo.h: length of bsy_op's per-level arrays
+ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2  # bsy_op.act of CONV_FIRST / FIRST_POOL / STEM / CONV
 (OP_CONV_FIRST, OP_CONV, OP_DWCONV, OP_SPPF_POOL, OP_ATTN, OP_DECODE, OP_RAW_NCHW, OP_NHWC2NCHW, OP_STEM, OP_BNECK, OP_DWCONV_G, OP_COPY, OP_GAP, OP_MSCA_MIX, OP_MUL, OP_ELA, OP_DWPW, OP_MSCA_SPATIAL, OP_C3K2, OP_S2D, OP_PMSFA_TAIL, OP_CHAIN, OP_POOL_DOWN, OP_CLASSIFY_TAIL, OP_GHOST, OP_ADD, OP_E2E_TOPK, OP_MAXPOOL, OP_FIRST_POOL) = range(29)
 # OP_CHAIN (21): retired kind, kept in the unpacking only because bench.py still names it; plans never contain it
 

@@ -180,7 +180,7 @@ class Plan:
 
     def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16, precision: str = "fp16",
                  lanes: Optional[bool] = None, latency: bool = False, repconv: str = "refconv", max_det: int = 300, one2many: bool = False,
-                 **switches: Optional[bool]):
+                 sppf_act: str = "silu", **switches: Optional[bool]):
         """switches: the keys of SWITCHES; None (or absent) = what the switch's environment variable says, on where it is unset.
         max_det, one2many: read by a v10Detect head alone -- the rows its top-k keeps, and whether the one2many branches (cv2 / cv3, raw
         maps only, which a caller who wants the rows alone must not pay for) are part of the plan."""
@@ -194,6 +194,19 @@ class Plan:
         if repconv not in ("refconv", "repvgg"):
             raise ValueError(f"repconv must be 'refconv' or 'repvgg', not {repconv!r}")
         self.repconv = repconv
+        # What SPPF's cv1 / cv2 apply in a graph whose yaml says `activation: nn.ReLU()` (YOLOv6); read nowhere else.  "silu" is what every
+        # yaml-built model of this fork holds: nn/modules/block.py:13 does `from ..Addmodules import *`, which shadows `Conv` for every
+        # class of block.py, and parse_model sets `default_act` on nn.modules.conv.Conv alone (tasks.py:956-957) -- the top-level Convs
+        # and the Detect head turn ReLU, SPPF's two Convs stay SiLU.  Upstream has no such shadowing: a model pickled there unpickles
+        # with ReLU in SPPF too, which is "relu".  plugin.accelerate and YoloEngine read the form from the live module.
+        if sppf_act not in ("silu", "relu"):
+            raise ValueError(f"sppf_act must be 'silu' or 'relu', not {sppf_act!r}")
+        self.sppf_act = sppf_act
+        # the graph's default activation as an id of include/bsyolo.h (1 SiLU, 2 ReLU): what `act=True` means to conv() below
+        activation = cfg.get("activation")
+        if activation not in (None, "", "nn.SiLU()", "nn.ReLU()"):
+            raise NotImplementedError(f"activation {activation!r} (tasks.py:956-957) is not accelerated: nn.SiLU() and nn.ReLU() are")
+        self.act_id = L.ACT_RELU if activation == "nn.ReLU()" else L.ACT_SILU
         if not 1 <= int(max_det) <= 4096:
             raise ValueError(f"max_det must be 1 .. 4096 (the top-k sorts its winners in LDS), not {max_det!r}")
         self.max_det, self.one2many = int(max_det), bool(one2many)
@@ -316,13 +329,15 @@ class Plan:
         self.ops.append(o)
         return o
 
-    def conv(self, name: str, src: Union[T, Sequence[T]], cout: int, k: int = 1, s: int = 1, act: bool = True,
+    def conv(self, name: str, src: Union[T, Sequence[T]], cout: int, k: int = 1, s: int = 1, act: Union[bool, int] = True,
              dst: Optional[T] = None, res: Optional[T] = None, plain: bool = False, out_f32: bool = False,
              perm: Optional[List[int]] = None, name2: Optional[str] = None, wkind: Optional[str] = None,
              wshape: Optional[Tuple[int, int, int]] = None, real: Tuple[int, int] = (0, 0),
              rows: Optional[List[int]] = None, cols: Optional[List[int]] = None) -> T:
         """name2: a second Conv module of the same input and kernel whose output channels follow this one's (weights.py
-        kind "conv2": the two folded weight matrices stacked along cout) -- one launch for both, cout = the total."""
+        kind "conv2": the two folded weight matrices stacked along cout) -- one launch for both, cout = the total.
+        act: True = the graph's default activation (self.act_id: SiLU, or ReLU under `activation: nn.ReLU()`), False = none, or an
+        activation id of include/bsyolo.h itself (SPPF's convs under ReLU name theirs)."""
         srcs = [src] if isinstance(src, T) else list(src)
         assert 1 <= len(srcs) <= 2, "at most two concat operands per conv"
         H, W = srcs[0].H, srcs[0].W
@@ -366,7 +381,7 @@ class Plan:
                              real_cout=real[0], real_cin=real[1], rows=rows, cols=cols)
         fl = 2 * self.B * OH * OW * cout * cin * k * k
         self._emit(L.OP_CONV, name, fl, src0=srcs[0], src1=srcs[1] if len(srcs) > 1 else None, dst=dst, res=res, ksize=k, stride=s, pad=p,
-                   act=int(act), out_f32=int(out_f32), wkey=key, dst_scale=1, cout=cout, mfma_flops=fl)
+                   act=self.act_id if act is True else int(act), out_f32=int(out_f32), wkey=key, dst_scale=1, cout=cout, mfma_flops=fl)
         return dst
 
     def conv_first(self, name: str, cout: int, k: int, s: int, p: Optional[int] = None) -> T:
@@ -383,7 +398,7 @@ class Plan:
         dst = self.alloc(cout, OH, OW)
         key = self._wrec(name, name=name, kind="first", cout=cout, cin=3, k=k)
         fl = 2 * self.B * OH * OW * cout * 3 * k * k
-        self._emit(L.OP_CONV_FIRST, name, fl, src0=img, dst=dst, ksize=k, stride=s, pad=p, act=1, wkey=key, in_dtype=self.in_dtype,
+        self._emit(L.OP_CONV_FIRST, name, fl, src0=img, dst=dst, ksize=k, stride=s, pad=p, act=self.act_id, wkey=key, in_dtype=self.in_dtype,
                    mfma_flops=fl)
         return dst
 
@@ -784,10 +799,12 @@ class Plan:
         """block.py:3114-3149.  SPPELAN (:3726-3743) is the same dataflow with the hidden width c_ from the yaml and the last conv
         named cv5."""
         c_ = x.C // 2 if c_ is None else c_
+        # under a ReLU graph the two convs follow sppf_act (__init__), not the graph's default
+        act = (L.ACT_RELU if self.sppf_act == "relu" else L.ACT_SILU) if self.act_id == L.ACT_RELU else True
         cat = self.alloc(4 * c_, x.H, x.W)
-        self.conv(name + ".cv1", x, c_, 1, 1, dst=cat.slice(0, c_))
+        self.conv(name + ".cv1", x, c_, 1, 1, act=act, dst=cat.slice(0, c_))
         self._emit(L.OP_SPPF_POOL, name + ".m", src0=cat.slice(0, c_))
-        return self.conv(name + "." + last, cat, c2, 1, 1)
+        return self.conv(name + "." + last, cat, c2, 1, 1, act=act)
 
     # ---- YOLOv9 (GELAN) blocks --------------------------------------------------------------------------------------
     def pool_down(self, name: str, src: T, mode: int) -> T:
@@ -888,18 +905,28 @@ class Plan:
             self.conv(pn + ".ffn.1", f, c, 1, 1, act=False, dst=b, res=b)                     # b = b + ffn(b)
         return self.conv(name + ".cv2", ab, c2, 1, 1)
 
+    def deconv(self, name: str, x: T, cout: int) -> T:
+        """nn.ConvTranspose2d(c1, cout, 2, 2, 0) with bias, no activation (Proto.upsample, block.py:91; YOLOv6's top-level upsamplers):
+        out[2i + dy, 2j + dx] = W[:, :, dy, dx]^T x[i, j] + b, so four 1x1 CONV ops, one per output phase (dy, dx), each writing its pixels
+        of the double-size map through dst_scale = 2.  One weight record per phase (weights.py kind "deconv"), all read `name`.weight / .bias."""
+        assert not x.up
+        if not self.f32_mode and (x.C % 8 or x.coff % 8):
+            raise NotImplementedError(f"{name}: source channels / offset {(x.C, x.coff)} are not multiples of 8 (fp16 path)")
+        up = self.alloc(cout, 2 * x.H, 2 * x.W)
+        for dy in (0, 1):
+            for dx in (0, 1):
+                key = f"{name}@{dy}{dx}"
+                if key not in self.wrecs:
+                    self.wrecs[key] = WRec(name=name, kind="deconv", cout=cout, cin=x.C, k=1, tap=(dy, dx))
+                fl = 2 * self.B * x.H * x.W * cout * x.C
+                self._emit(L.OP_CONV, key, fl, src0=x, src1=None, dst=T(up.buf, up.ld, 0, cout, x.H, x.W, False, up.f32), res=None, ksize=1,
+                           stride=1, pad=0, act=0, out_f32=0, wkey=key, dst_scale=2, dst_dy=dy, dst_dx=dx, mfma_flops=fl)
+        return up
+
     def proto(self, name: str, x: T, c_: int, nm: int) -> T:
         """block.py:80-97 Proto: cv3(cv2(ConvTranspose2d(c_, c_, 2, 2)(cv1(x)))) -> (B, nm, 2H, 2W)."""
         t = self.conv(name + ".cv1", x, c_, 3, 1)
-        up = self.alloc(c_, 2 * x.H, 2 * x.W)
-        for dy in (0, 1):
-            for dx in (0, 1):
-                key = f"{name}.upsample@{dy}{dx}"
-                if key not in self.wrecs:
-                    self.wrecs[key] = WRec(name=name + ".upsample", kind="deconv", cout=c_, cin=c_, k=1, tap=(dy, dx))
-                fl = 2 * self.B * x.H * x.W * c_ * c_
-                self._emit(L.OP_CONV, key, fl, src0=t, src1=None, dst=T(up.buf, up.ld, 0, c_, x.H, x.W, False, up.f32), res=None, ksize=1,
-                           stride=1, pad=0, act=0, out_f32=0, wkey=key, dst_scale=2, dst_dy=dy, dst_dx=dx, mfma_flops=fl)
+        up = self.deconv(name + ".upsample", t, c_)
         t = self.conv(name + ".cv2", up, c_, 3, 1)
         p = self.conv(name + ".cv3", t, nm, 1, 1)
         self._emit(L.OP_NHWC2NCHW, name + ".nchw", src0=p, dst=self._ext("proto", self.EXT_PROTO, nm, (p.H, p.W)), OH=0, OW=0, out_dtype=self.out_dtype)
@@ -930,7 +957,7 @@ class Plan:
         k1 = self._wrec(n1, name=n1, kind="conv", cout=64, cin=src.C, k=3, perm=None)
         k2 = self._wrec(n2, name=n2, kind="plain", cout=64, cin=64, k=1, perm=None)
         self._decoding_conv(n1 + "+2", src, 3, cout=64, mode=3, level=level, a0=a0, A=A, nc=nc, stride=stride,
-                            flops=2 * self.B * src.H * src.W * 64 * (9 * src.C + 64), act=1, wkey=k1, wkey2=k2, mid_c=64)
+                            flops=2 * self.B * src.H * src.W * 64 * (9 * src.C + 64), act=self.act_id, wkey=k1, wkey2=k2, mid_c=64)
 
     def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0, nk: int = 0, kdim: int = 0,
                end2end: bool = False):
@@ -1073,6 +1100,11 @@ class Plan:
         self.pooled = g  # the (B, 1, 1, 1280) mean, for tests that read it back (YoloEngine.read_view)
 
     # ---- graph walk (nn/tasks.py:138-165 + :940-1105) -----------------------------------------------------------
+    # A graph under `activation: nn.ReLU()`: the modules it may hold, and the op kinds they may lower to -- the four whose `act` is an
+    # activation id, and the glue (copies, pools, the decode launch and the raw-map transposes), which applies none
+    RELU_MODULES = ("Conv", "SPPF", "nn.ConvTranspose2d", "nn.Upsample", "nn.MaxPool2d", "nn.ZeroPad2d", "Concat", "Detect")
+    RELU_KINDS = (L.OP_CONV_FIRST, L.OP_FIRST_POOL, L.OP_STEM, L.OP_CONV, L.OP_COPY, L.OP_S2D, L.OP_SPPF_POOL, L.OP_MAXPOOL, L.OP_DECODE, L.OP_RAW_NCHW)
+
     def _build(self):
         d = self.cfg
         scales = d.get("scales")
@@ -1083,8 +1115,7 @@ class Plan:
                 scale = next(iter(scales))
             depth, width, max_ch = scales[scale]
         nc = d["nc"]
-        if d.get("activation"):
-            raise NotImplementedError("custom activation (tasks.py:956-957) is not accelerated")
+        relu = self.act_id == L.ACT_RELU
         legacy = True
         outs: List = []   # per layer: T, or list[T] for a lazy Concat
         chans: List[int] = []
@@ -1099,13 +1130,31 @@ class Plan:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
             if isinstance(x, _ZeroPadded) and m != "nn.MaxPool2d":
                 raise NotImplementedError(f"model.{i - 1}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] (model.{i} is {m})")
+            if relu and m not in self.RELU_MODULES:
+                # ReLU exists in the kernels of CONV_FIRST / FIRST_POOL / STEM / CONV alone; every block module lowers to other kinds as
+                # well (and, in this fork, would keep SiLU anyway: block.py:13 shadows Conv there).  No silent SiLU where the reference
+                # may hold ReLU, or the reverse: the graph stays on the reference
+                raise NotImplementedError(f"{name}: {m} under activation nn.ReLU() is not accelerated (ReLU graphs: {', '.join(self.RELU_MODULES)})")
+            first_op = len(self.ops)
             if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv", "GhostConv", "C3Ghost", "GhostBottleneck",
                      "C2fCIB", "PSA", "Bottleneck", "SPP"):
                 c2 = make_divisible(min(args[0], max_ch) * width, 8)
                 if m == "Conv":
                     k, s = arg(1, 1), arg(2, 1)
                     pad = k // 2 if arg(3, None) is None else args[3]
-                    if i == 0:
+                    if n > 1:
+                        # parse_model's nn.Sequential of n Convs (tasks.py:1094), every one built Conv(c1, c2, k, s): model.i.0 .. model.i.{n-1}
+                        # (YOLOv6's equal-width 3x3 chains).  From the second on a link reads c2 channels, so the chain exists where c1 == c2
+                        if i == 0:
+                            raise NotImplementedError(f"{name}: an image conv repeated {n} times is not accelerated")
+                        if not isinstance(x, T) or x.C != c2:
+                            raise NotImplementedError(f"{name}: {n} chained Convs need an input of their own width ({c2} channels)")
+                        if pad != k // 2:
+                            raise NotImplementedError(f"Conv with padding {pad} != k // 2 is not accelerated")
+                        y = x
+                        for j in range(n):
+                            y = self.conv(f"{name}.{j}", y, c2, k, s)
+                    elif i == 0:
                         if (k, s, pad) not in ((3, 2, 1), (3, 1, 1), (6, 2, 2)):
                             raise NotImplementedError(f"image conv k={k} s={s} p={pad}: 3x3 s2 p1, 3x3 s1 p1 or 6x6 s2 p2 only")
                         y = self.conv_first(name, c2, k, s, pad)
@@ -1231,6 +1280,17 @@ class Plan:
                 else:
                     raise NotImplementedError(f"{name}: nn.MaxPool2d {args} (only [2, 2, 0], and [2, 1, 0] behind nn.ZeroPad2d [[0, 1, 0, 1]], are accelerated)")
                 cout = y.C
+            elif m == "nn.ConvTranspose2d":
+                # args [c2, k, s, p, output_padding, groups, bias, dilation]; the class is in parse_model's base-module set (tasks.py:1006),
+                # so c2 is width-scaled like a Conv's and c1 put in front.  The 2x2 stride-2 upsampler is the accelerated form
+                if not isinstance(x, T) or x.up:
+                    raise NotImplementedError(f"{name}: nn.ConvTranspose2d on a Concat or an upsampled view is not accelerated")
+                if (arg(1, 1), arg(2, 1), arg(3, 0), arg(4, 0), arg(5, 1), arg(6, True), arg(7, 1)) != (2, 2, 0, 0, 1, True, 1) or len(args) > 8 or n != 1:
+                    raise NotImplementedError(f"{name}: nn.ConvTranspose2d {args} (kernel 2, stride 2, padding 0, no output padding, one group, "
+                                              "with bias, once, is accelerated)")
+                c2 = make_divisible(min(args[0], max_ch) * width, 8)
+                y = self.deconv(name, x, c2)
+                cout = c2
             elif m == "nn.Upsample":
                 assert isinstance(x, T) and not x.up and args[1] == 2 and args[2] == "nearest"
                 y = T(x.buf, x.ld, x.coff, x.C, x.H * 2, x.W * 2, True, x.f32)
@@ -1296,6 +1356,10 @@ class Plan:
                 y, cout = None, 0
             else:
                 raise NotImplementedError(f"module {m} is not on the accelerated path")
+            if relu:  # what RELU_MODULES promises, checked on the ops themselves
+                for o in self.ops[first_op:]:
+                    if o["kind"] not in self.RELU_KINDS:
+                        raise NotImplementedError(f"{name}: {m} lowers to op {o['name']} of kind {o['kind']}, which has no ReLU (activation nn.ReLU())")
             outs.append(y)
             chans.append(cout)
             x = y
@@ -1322,7 +1386,7 @@ class Plan:
                     return
         self.buf_bytes[mid.buf] = 16  # never written
         self._emit(L.OP_FIRST_POOL, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], H=self.H, W=self.W, ksize=3, stride=1,
-                   pad=1, act=1, wkey=a["wkey"], in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"])
+                   pad=1, act=a["act"], wkey=a["wkey"], in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"])
         self.ops[0:2] = [self.ops.pop()]  # (layer 0's flops are counted already)
         self.layer_out[0] = None
 
@@ -1336,7 +1400,7 @@ class Plan:
             return
         mid = a["dst"]
         if (b["src0"] is not mid or b.get("src1") is not None or b.get("res") is not None or b["ksize"] != 3
-                or b["stride"] != 2 or b["out_f32"] or not b["act"] or a["ksize"] != 3 or a["stride"] != 2):
+                or b["stride"] != 2 or b["out_f32"] or not b["act"] or b["act"] != a["act"] or a["ksize"] != 3 or a["stride"] != 2):
             return
         if not kernel_takes("stem_fused", mid.C, b["dst"].C, self.H, self.W):
             return
@@ -1346,7 +1410,7 @@ class Plan:
                 if t is not None and t.buf == mid.buf:
                     return
         self.buf_bytes[mid.buf] = 16  # never written
-        self._emit(L.OP_STEM, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], ksize=3, stride=2, pad=1, act=1,
+        self._emit(L.OP_STEM, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], ksize=3, stride=2, pad=1, act=a["act"],
                    wkey=a["wkey"], wkey2=b["wkey"], mid_c=mid.C, in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"] + b["mfma_flops"])
         self.ops[0:2] = [self.ops.pop()]  # (the two layers' flops are counted already)
         self.layer_out[0] = None

@@ -47,7 +47,7 @@ import torch
 from . import lib as _L
 from . import nms as _nms
 from . import ops as _O
-from .engine import YoloEngine
+from .engine import YoloEngine, sppf_form
 from .plan import Plan, qkv_perm
 from .weights import BN_EPS, repconv_form
 
@@ -144,6 +144,37 @@ def _head_exports(model) -> bool:
     return bool(_head_attr(model, "export", False))
 
 
+_ACT_IDS = ((torch.nn.ReLU, _L.ACT_RELU), (torch.nn.SiLU, _L.ACT_SILU), (torch.nn.Identity, _L.ACT_NONE))
+
+
+def _check_acts(model, cfg: dict, sppf_act: str, support: dict) -> None:
+    """Every conv the plan runs with an activation id (CONV_FIRST / FIRST_POOL / STEM / CONV ops over a Conv module's record) against the
+    live module's `act`: nn.ReLU <-> 2, nn.SiLU <-> 1, nn.Identity <-> 0.  A mismatch -- a module whose activation was swapped after the
+    yaml built it -- raises NotImplementedError: the engine would compute another function than the model.  Modules the plan's names
+    do not resolve to, and (outside ReLU graphs) activations of other classes, are left as they always were.
+    Cost and reach: this builds one whole Plan at 64 x 64 (host-side flattening, a few milliseconds) at accelerate() and again at every
+    engine rebuild, only to walk its op names; and it walks ONE precision's plan -- fp16 where the graph has one, else fp32 -- so a
+    module is checked under the name that precision's fusions give it (the stem and the fused head exist in fp16 alone).  Every Conv
+    module appears in both precisions' plans with the same activation, so one walk covers them."""
+    relu = cfg.get("activation") == "nn.ReLU()"
+    plan = Plan(cfg, 1, 64, 64, precision="fp16" if support.get("fp16") else "fp32", sppf_act=sppf_act)
+    for o in plan.ops:
+        if o["kind"] not in (_L.OP_CONV_FIRST, _L.OP_FIRST_POOL, _L.OP_STEM, _L.OP_CONV):
+            continue
+        for key in ("wkey", "wkey2") if o["kind"] in (_L.OP_STEM, _L.OP_CONV) else ("wkey",):
+            r = plan.wrecs.get(o.get(key))
+            if r is None or r.kind not in ("conv", "first", "first_s2d") or (key == "wkey2" and o["kind"] == _L.OP_CONV):
+                continue
+            try:
+                act = model.get_submodule(r.name).act
+            except AttributeError:
+                continue
+            ids = [i for cls, i in _ACT_IDS if isinstance(act, cls)]
+            if (ids and ids[0] != o["act"]) or (relu and not ids):
+                raise NotImplementedError(f"{r.name}: the module's activation is {act}, the plan runs act = {o['act']} there "
+                                          "(0 identity, 1 SiLU, 2 ReLU): the model does not compute what its yaml describes")
+
+
 FP32_MODES = {"engine_fp32x": "fp32x", "engine_fp32": "fp32", "engine": "fp16", "reference": None}
 
 
@@ -186,7 +217,8 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     pose = cfg["head"][-1][2] == "Pose"
     e2e = cfg["head"][-1][2] == "v10Detect"
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
-             "tta_calls": 0, "support": support, "failed": set(), "repconv": None}
+             "tta_calls": 0, "support": support, "failed": set(), "repconv": None, "sppf_act": sppf_form(model, cfg)}
+    _check_acts(model, cfg, state["sppf_act"], support)  # raises before anything is rebound: the model keeps its forward
     fp32_mode = fp32_inputs or os.environ.get("BSY_FP32_INPUTS", "engine_fp32x")
     if fp32_mode not in FP32_MODES:
         raise ValueError(f"fp32_inputs must be one of {sorted(FP32_MODES)}, not {fp32_mode!r}")
@@ -214,8 +246,13 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
             # YOLOv9: the fork's own RepConv or upstream's (an upstream-pickled checkpoint), told apart by the keys -- at every build,
             # so a rebuild after a weight reload or a fuse() sees the form the model holds now
             state["repconv"] = repconv_form(sd)
+            # YOLOv6: SPPF's activation, read off the live module like the RepConv form (Plan.sppf_act)
+            state["sppf_act"] = sppf_form(model, cfg)
+            # ... and the modules' activations against the plan's ids again: one swapped since accelerate() (the weights' fingerprint
+            # does not see it, so this holds from the next rebuild on) sends the call to the reference forward, which computes it
+            _check_acts(model, cfg, state["sppf_act"], support)
             state[slot] = YoloEngine(cfg, sd, device=dev.index or 0, bn_eps=model_bn_eps(model), precision=precision,
-                                     repconv=state["repconv"], max_det=max_det)
+                                     repconv=state["repconv"], max_det=max_det, sppf_act=state["sppf_act"])
         return state[slot]
 
     def forward(self, x, *args, **kwargs):

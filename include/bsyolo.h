@@ -58,7 +58,7 @@ typedef struct bsy_view {
 
 enum bsy_op_kind {
     BSY_OP_CONV_FIRST = 0, /* image (BCHW f16/f32, C=3) -> conv 3x3 s2 or s1, pad 1, + bias + act -> NHWC f16 */
-    BSY_OP_CONV = 1,       /* implicit-GEMM conv k in {1,3}, s in {1,2}, MFMA f16, fused bias/SiLU/residual   */
+    BSY_OP_CONV = 1,       /* implicit-GEMM conv k in {1,3}, s in {1,2}, MFMA f16, fused bias/act/residual    */
     BSY_OP_DWCONV = 2,     /* depthwise 3x3 s1 + bias (+SiLU) (+residual)                                     */
     BSY_OP_SPPF_POOL = 3,  /* three chained MaxPool2d(5,1,2) -> channel slices of the SPPF concat buffer      */
     BSY_OP_ATTN = 4,       /* softmax(q^T k * scale) v, per (image, head); MFMA flash-style.  act = 1 (fp16 path): + pe(v) in
@@ -128,6 +128,9 @@ enum bsy_op_kind {
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
                             * res = f32 scratch buffer of (2 (H + W) + 2) * C floats per image                          */
 };
+/* One more than the largest kind above (21 is retired).  A new kind raises this, and the library's table of kind names (csrc/engine.hip,
+ * the text of its error messages) is held to it by a static_assert. */
+#define BSY_OP_KIND_COUNT 29
 
 typedef struct bsy_op {
     int32_t kind;
@@ -138,7 +141,11 @@ typedef struct bsy_op {
     bsy_view dst;           /* dst.C = Cout */
     bsy_view res;           /* residual added AFTER the activation (Bottleneck / PSABlock shortcut); buf<0 if none */
     int32_t ksize, stride, pad;
-    int32_t act;            /* 0 identity, 1 SiLU.  DECODE (nm = ne = 0): 1 = the DFL sums run in the fused head epilogue's order whatever the
+    int32_t act;            /* CONV_FIRST, FIRST_POOL, STEM (both convs), CONV: the activation id -- 0 identity, 1 SiLU, 2 ReLU (t < 0 ? 0 : t: NaN
+                             * passes through, the sign of a zero result is not specified).  Results under 0 and 1 are what they were before id 2
+                             * existed, bit for bit.  Every other kind that applies an activation takes 0 or 1 (SiLU) only: bsy_plan_create refuses
+                             * a larger value there with BSY_ERR_ARG, naming the op.  DWCONV_G, ATTN and DECODE give the field a meaning of their
+                             * own (see the kinds).  DECODE (nm = ne = 0): 1 = the DFL sums run in the fused head epilogue's order whatever the
                              * level count, so that a Detect plan with the decode launch returns the bits of the plan with the fused head;
                              * DECODE, bit 1 (value 2, nm = ne = nk = 0): rows 0..3 are the corners (x1, y1, x2, y2) * stride -- dist2bbox with
                              * xywh=False, the box form of an end2end head (head.py:148) -- instead of (cx, cy, w, h) * stride */
@@ -265,7 +272,9 @@ int bsy_plan_profile(bsy_plan* p, void* const* ext, int n_ext, bsy_stream stream
 
 /* Conv.forward_fuse (nn/modules/conv.py:149-151): y = act(conv2d(x, w) + b) [+ res], NHWC f16 in/out.
  * x: (B,H,W,ldx) view of C1 channels; w: packed [CoutPad][Kpad] f16 (bsy_pack_conv_weight layout);
- * b: f32 [CoutPad]; y: (B,OH,OW,ldy); res same geometry as y or NULL. */
+ * b: f32 [CoutPad]; y: (B,OH,OW,ldy); res same geometry as y or NULL.
+ * act, here and in bsy_conv2d_f32 / bsy_conv2d_f32x / bsy_conv_first_f32 / bsy_conv_first / bsy_stem_fused: bsy_op.act's activation id,
+ * 0 identity, 1 SiLU, 2 ReLU. */
 int bsy_conv2d(const void* x, int ldx, int B, int H, int W, int C1, const void* w, const float* b, void* y, int ldy,
                int C2, int ksize, int stride, int act, const void* res, int ldr, int y_f32, bsy_stream stream);
 /* The same module in fp32 (the engine's fp32 mode: callers of predict() with the reference's default half=False,
