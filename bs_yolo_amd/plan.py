@@ -125,14 +125,16 @@ def kernel_takes(kernel: str, *shape: int) -> bool:
     return getattr(L.lib, f"bsy_{kernel}_supported")(*shape) == 1
 
 
-# Every field an op dict may carry besides kind / name / lane: what c_ops() serialises, then what only the host reads (the weight
-# record keys, and `cout` / `mfma_flops` for the autotuner's signature and the benchmark's per-family sums).  Plan._emit refuses
-# anything else: c_ops() reads with defaults, so a misspelt key would serialise as zero.
-OP_FIELDS = frozenset((
-    "H", "W", "OH", "OW", "src0", "src1", "dst", "res", "ksize", "stride", "pad", "act", "out_f32", "dst_scale", "dst_dy", "dst_dx", "mid_c",
-    "heads", "key_dim", "head_dim", "scale", "nl", "nc", "nm", "ne", "A", "box", "cls", "msk", "lvl_h", "lvl_w", "lvl_stride", "in_dtype",
-    "out_dtype", "level", "join", "ksplit", "nk", "kdim",
-    "wkey", "wkey2", "wkeys", "cout", "mfma_flops"))
+# Every field an op dict may carry besides kind / name / lane.  The scalars that c_ops() copies into the bsy_op member of the same name,
+# with what an op that lacks them serialises (a new scalar field is one entry here); the members c_ops() fills by hand -- sizes, views,
+# per-level view lists and numbers; and what only the host reads (the weight record keys, and `cout` / `mfma_flops` for the autotuner's
+# signature and the benchmark's per-family sums).  Plan._emit refuses anything else: a misspelt key would serialise as its default.
+SCALAR_FIELDS = (("ksize", 0), ("stride", 0), ("pad", 0), ("act", 0), ("out_f32", 0), ("dst_scale", 1), ("dst_dy", 0), ("dst_dx", 0),
+                 ("mid_c", 0), ("heads", 0), ("key_dim", 0), ("head_dim", 0), ("scale", 0.0), ("nl", 0), ("nc", 0), ("nm", 0), ("ne", 0),
+                 ("A", 0), ("nk", 0), ("kdim", 0), ("in_dtype", 0), ("out_dtype", 0), ("level", 0), ("join", 0), ("ksplit", 0))
+VIEW_FIELDS, LIST_FIELDS, LEVEL_FIELDS = ("src0", "src1", "dst", "res"), ("box", "cls", "msk"), (("lvl_h", 0), ("lvl_w", 0), ("lvl_stride", 0.0))
+OP_FIELDS = frozenset(("H", "W", "OH", "OW") + VIEW_FIELDS + LIST_FIELDS + tuple(f for f, _ in LEVEL_FIELDS + SCALAR_FIELDS)
+                      + ("wkey", "wkey2", "wkeys", "cout", "mfma_flops"))
 # kinds that may run on a side lane (csrc/engine.hip bsy_plan_run forks and joins around them)
 LANE_KINDS = (L.OP_CONV, L.OP_DWCONV, L.OP_BNECK, L.OP_DWCONV_G, L.OP_DWPW, L.OP_C3K2)
 Output = namedtuple("Output", "name slot shape dtype raw_only")  # one external output of a plan (Plan._ext, Plan.outputs)
@@ -142,6 +144,21 @@ Output = namedtuple("Output", "name slot shape dtype raw_only")  # one external 
 class _ZeroPadded:
     """What an accepted nn.ZeroPad2d [[0, 1, 0, 1]] layer hands to the nn.MaxPool2d [2, 1, 0] behind it: its input, unpadded."""
     src: T
+
+    def gate(self, i: int, m: str):
+        if m != "nn.MaxPool2d":
+            raise NotImplementedError(f"model.{i - 1}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] (model.{i} is {m})")
+
+
+class _Layer:
+    """What the graph walk hands to a layer's lowering (Plan.LOWERINGS): the layer's index, its name "model.i", its module, its input x
+    (`f` resolved: a T, a list of T behind a Concat, a _ZeroPadded, or None for the image), its arguments with "nc" resolved, its repeat
+    count depth-scaled, args[0] width-scaled where the table says the module's is (else None), and whether it is the graph's last.
+    ONE record per walk, refilled for every layer (a fresh one each was 5 % of plan construction): a lowering reads it and keeps none."""
+    __slots__ = ("i", "name", "m", "x", "args", "n", "c2", "last")
+
+    def arg(self, j: int, default):
+        return self.args[j] if len(self.args) > j else default
 
 
 class Plan:
@@ -300,6 +317,24 @@ class Plan:
         ld = make_divisible(C, 4) if f32 else make_divisible(C, 8)
         self.buf_bytes.append(self.B * H * W * ld * (4 if f32 else 2))
         return T(len(self.buf_bytes) - 1, ld, 0, C, H, W, False, f32)
+
+    def alloc_like(self, x: Union[T, List[T]], C: int) -> T:  # a fresh C-wide map of the size of x, or of a Concat's first operand
+        x0 = x[0] if isinstance(x, list) else x
+        return self.alloc(C, x0.H, x0.W)
+
+    def stored(self, w: int) -> int:  # the width a piece of w channels is carried on: the fp16 path reads 8-channel pieces
+        return w if self.f32_mode else w + -w % 8
+
+    def pieces(self, widths: List[int], H: int, W: int) -> Tuple[T, int]:
+        """One map of consecutive pieces of `widths` channels, each carried on its stored() width, zero-padded at its end (T.padded: zero weights
+        and bias where it is written, zero weight columns where it is read; no piece needs it: a plain map) -> (map, the first piece's stored width)."""
+        w8 = widths if self.f32_mode else [w + -w % 8 for w in widths]  # (stored(), in place: every block of every plan comes through here)
+        t = self.alloc(sum(w8), H, W)
+        return (t if w8 == widths else t.padded(list(zip(w8, widths)))), w8[0]
+
+    def _fp16_mult8(self, width: int, refusal: str):  # a width the fp16 path cannot carry, where no padded form exists
+        if width % 8 and not self.f32_mode:
+            raise NotImplementedError(refusal)
 
     # ---- op emitters -----------------------------------------------------------------------------------------
     def _wrec(self, key: str, **kw) -> str:
@@ -474,14 +509,13 @@ class Plan:
         """A Bottleneck as a top-level layer (YOLOv3's darknet-53 and its head; block.py:3405-3419).  A two-operand Concat goes to cv1 as two
         sources; the identity shortcut exists where c1 == c2 (:3413), which a Concat input of the shipped graphs never has."""
         if isinstance(x, T):
-            dst = self.alloc(c2, x.H, x.W)
+            dst = self.alloc_like(x, c2)
             self.bottleneck(name, x, dst, shortcut, k, e)
             return dst
         c_ = int(c2 * e)
         if shortcut and sum(t.C for t in x) == c2:
             raise NotImplementedError(f"{name}: a Bottleneck with a shortcut over a Concat is not accelerated")
-        if c_ % 8 and not self.f32_mode:
-            raise NotImplementedError(f"{name}: a Bottleneck with a hidden width of {c_} channels over a Concat is not on the fp16 path (multiples of 8)")
+        self._fp16_mult8(c_, f"{name}: a Bottleneck with a hidden width of {c_} channels over a Concat is not on the fp16 path (multiples of 8)")
         t = self.conv(name + ".cv1", x, c_, k[0], 1)
         return self.conv(name + ".cv2", t, c2, k[1], 1)
 
@@ -505,11 +539,12 @@ class Plan:
             # hidden width 4 / 12 / 20 (a C3k2 of 16 / 48 / 80 channels with e = 0.25 x 0.5, e.g. YOLO11 at width 0.125 / 0.375): the
             # hidden map is carried on the next multiple of 8 with zero weights and bias in the padding (weights.py real_cout /
             # real_cin, as Detect's class branch does for nc-dependent widths) -- SiLU(0) = 0 there, the real channels are unchanged
-            c8 = make_divisible(c_, 8)
             if x.cmap is not None or dst.cmap is not None:  # inside a block whose chunks are padded pieces themselves (c2f below)
-                t = self.conv(name + ".cv1", x, c8, k[0], 1, dst=self.alloc(c8, x.H, x.W).padded([(c8, c_)]), **cv1)
+                t, c8 = self.pieces([c_], x.H, x.W)
+                t = self.conv(name + ".cv1", x, c8, k[0], 1, dst=t, **cv1)
                 self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res)
                 return
+            c8 = self.stored(c_)
             t = self.conv(name + ".cv1", x, c8, k[0], 1, real=(c_, 0), **cv1)
             self.conv(name + ".cv2", t, dst.C, k[1], 1, dst=dst, res=res, real=(0, c_))
             return
@@ -524,19 +559,15 @@ class Plan:
         20 ...; 2c is a multiple of 8 whenever c2 is) takes the two-launch forms, with zero weights and biases in its padding."""
         c = dst.real
         assert x.real == c and x.C == dst.C and not x.up
-        n = name + ".cv1"
-        if x.cmap is not None or dst.cmap is not None:
-            piece = lambda: self.alloc(x.C, x.H, x.W).padded([(x.C, c)])  # noqa: E731
-            t = self.dwconv(n + ".0", x, act=True, dst=piece(), real_c=c)
+        n, padded = name + ".cv1", x.cmap is not None or dst.cmap is not None
+        if padded:
+            t = self.dwconv(n + ".0", x, act=True, dst=self.pieces([c], x.H, x.W)[0], real_c=c)
             t = self.conv(n + ".1", t, 2 * c, 1, 1)
         else:
             t = self.dwpw(n, x, 2 * c)
-        if lk:
-            t = self.dwconv_g(n + ".2", t, 7, 7, 1, 2 * c, kind="repvggdw")
-            t = self.conv(n + ".3", t, dst.C, 1, 1, dst=piece() if dst.cmap is not None or x.cmap is not None else None)
-        elif x.cmap is not None or dst.cmap is not None:
-            t = self.dwconv(n + ".2", t, act=True)
-            t = self.conv(n + ".3", t, dst.C, 1, 1, dst=piece())
+        if lk or padded:
+            t = self.dwconv_g(n + ".2", t, 7, 7, 1, 2 * c, kind="repvggdw") if lk else self.dwconv(n + ".2", t, act=True)
+            t = self.conv(n + ".3", t, dst.C, 1, 1, dst=self.pieces([c], x.H, x.W)[0] if padded else None)
         else:
             t = self.dwpw(n, t, dst.C, parts=("2", "3"))
         self.dwconv(n + ".4", t, act=True, dst=dst, res=x if shortcut else None, real_c=c if t.cmap is not None else 0)
@@ -554,17 +585,16 @@ class Plan:
         if k not in (1, 3) or s not in (1, 2):
             raise NotImplementedError(f"{name}: GhostConv with k={k} s={s} (cv1 is accelerated for k 1 / 3, stride 1 / 2)")
         hr = c2 // 2  # the module's hidden width
-        pad = bool(hr % 8) and not self.f32_mode
-        CH = make_divisible(hr, 8) if pad else hr
+        CH = self.stored(hr)
+        pad = CH != hr
         p = k // 2
         OH, OW = (srcs[0].H + 2 * p - k) // s + 1, (srcs[0].W + 2 * p - k) // s + 1
-        new = lambda: self.alloc(2 * CH, OH, OW).padded([(CH, hr)] * 2) if pad else self.alloc(2 * CH, OH, OW)  # noqa: E731
         if dst is None:
-            dst = new()
+            dst = self.pieces([hr, hr], OH, OW)[0]
         assert dst.C == 2 * CH and dst.H == OH and dst.W == OW and (res is None or res.C == dst.C)
         fuse = (self.fuse_ghost and k == 1 and s == 1 and len(srcs) == 1 and not srcs[0].up and not srcs[0].C % 8 and not srcs[0].coff % 8
                 and kernel_takes("ghost_fused", srcs[0].C, CH))
-        pair = dst if res is None or fuse else new()
+        pair = dst if res is None or fuse else self.pieces([hr, hr], OH, OW)[0]
         first = len(self.ops)
         y = self.conv(name + ".cv1", srcs[0] if len(srcs) == 1 else srcs, CH, k, s, act=act, dst=pair.slice(0, CH))
         self.dwconv_g(name + ".cv2", y, 5, 5, 1, CH if act else 0, dst=pair.slice(CH, CH),
@@ -589,8 +619,7 @@ class Plan:
         if x.real != c2 or c2 % 4:
             raise NotImplementedError(f"{name}: GhostBottleneck {x.real} -> {c2} (the identity shortcut needs equal widths, the halves a multiple of 4)")
         c_ = c2 // 2
-        if c_ % 8 and not self.f32_mode:
-            raise NotImplementedError(f"{name}: GhostBottleneck with a hidden width of {c_} channels is not on the fp16 path (multiples of 8)")
+        self._fp16_mult8(c_, f"{name}: GhostBottleneck with a hidden width of {c_} channels is not on the fp16 path (multiples of 8)")
         t = self.ghostconv(name + ".conv.0", x, c_, 1, 1, True)
         self.ghostconv(name + ".conv.2", t, c2, 1, 1, False, dst=dst, res=x)
 
@@ -601,22 +630,17 @@ class Plan:
         cr = int(dst.real * 0.5)  # the module's hidden width
         x0 = x if isinstance(x, T) else x[0]
         # fp16 path, hidden width not a multiple of 8 (a C3k of 12 / 20 / 24 channels ...): both halves of the concat are zero-padded pieces
-        pad = bool(cr % 8) and not self.f32_mode
-        c_ = make_divisible(cr, 8) if pad else cr
-        new = (lambda: self.alloc(c_, x0.H, x0.W).padded([(c_, cr)])) if pad else (lambda: self.alloc(c_, x0.H, x0.W))
-        cat = self.alloc(2 * c_, x0.H, x0.W)
-        if pad:
-            cat = cat.padded([(c_, cr), (c_, cr)])
+        cat, c_ = self.pieces([cr, cr], x0.H, x0.W)
         if self.merge_c3k and n >= 2:
             # cv1 and cv2 read the same x: ONE launch writes [cv1 x | cv2 x] into the concat buffer (twice the cout per
             # pixel tile, one launch less); the last bottleneck then overwrites the cv1 half, which only the first one reads
             self.conv(name + ".cv1", x, 2 * c_, 1, 1, dst=cat, name2=name + ".cv2")
             cur = cat.slice(0, c_)
         else:
-            cur = self.conv(name + ".cv1", x, c_, 1, 1, dst=new())
+            cur = self.conv(name + ".cv1", x, c_, 1, 1, dst=self.pieces([cr], x0.H, x0.W)[0])
             self.conv(name + ".cv2", x, c_, 1, 1, dst=cat.slice(c_, c_))
         for i in range(n):
-            out = cat.slice(0, c_) if i == n - 1 else new()
+            out = cat.slice(0, c_) if i == n - 1 else self.pieces([cr], x0.H, x0.W)[0]
             if ghost:
                 self.ghost_bottleneck(f"{name}.m.{i}", cur, out)
             else:
@@ -634,18 +658,14 @@ class Plan:
             names = [name + ".cv1", name + ".m.0.cv1", name + ".m.0.cv2", name + ".cv2"]
             shapes = [(2 * c, xs[0].C, 1), (c // 2, c, 3), (c, c // 2, 3), (c2, 3 * c, 1)]
             keys = [self._wrec(nm, name=nm, kind="conv", cout=co, cin=ci, k=k, perm=None) for nm, (co, ci, k) in zip(names, shapes)]
-            dst = self.alloc(c2, xs[0].H, xs[0].W)
+            dst = self.alloc_like(xs, c2)
             fl = 2 * self.B * xs[0].H * xs[0].W * sum(co * ci * k * k for co, ci, k in shapes)
             self._emit(L.OP_C3K2, name, fl, src0=xs[0], dst=dst, ksize=3, stride=1, pad=1, act=1, wkeys=keys, mid_c=c, mfma_flops=fl)
             return dst
         # fp16 path, chunk width not a multiple of 8 (c = 12 / 20 ...; tasks.py:1016 scales c2 by any width multiple): every chunk of the
         # concat is carried on the next multiple of 8 as a zero-padded piece (T.cmap) -- cv1 writes zero rows there, cv2 reads zero columns
-        cr = c
-        if cr % 8 and not self.f32_mode and inner in ("bottleneck", "c2f", "c3k", "cib"):
-            c = make_divisible(cr, 8)
-        cat = self.alloc((2 + n) * c, xs[0].H, xs[0].W)
-        if c != cr:
-            cat = cat.padded([(c, cr)] * (2 + n))
+        padded = inner in ("bottleneck", "c2f", "c3k", "cib")  # (PMSFA refuses such a width itself)
+        cat, c = self.pieces([c] * (2 + n), xs[0].H, xs[0].W) if padded else (self.alloc_like(xs, (2 + n) * c), c)
         self.conv(name + ".cv1", xs, 2 * c, 1, 1, dst=cat.slice(0, 2 * c))
         for i in range(n):
             src, dst = cat.slice((1 + i) * c, c), cat.slice((2 + i) * c, c)
@@ -668,13 +688,12 @@ class Plan:
         the two halves as a virtual concat (a two-source conv): m's output in a buffer of its own, b where cv1 left it."""
         xs = [x] if isinstance(x, T) else list(x)
         c = int(c2 * 0.5)
-        if c % 8 and not self.f32_mode:
-            raise NotImplementedError(f"{name}: C2 with a hidden width of {c} channels is not on the fp16 path (multiples of 8)")
-        ab = self.alloc(2 * c, xs[0].H, xs[0].W)
+        self._fp16_mult8(c, f"{name}: C2 with a hidden width of {c} channels is not on the fp16 path (multiples of 8)")
+        ab = self.alloc_like(xs, 2 * c)
         self.conv(name + ".cv1", xs, 2 * c, 1, 1, dst=ab)
         cur = ab.slice(0, c)
         for i in range(n):
-            out = self.alloc(c, xs[0].H, xs[0].W)
+            out = self.alloc_like(xs, c)
             self.bottleneck(f"{name}.m.{i}", cur, out, shortcut, (3, 3), 1.0)
             cur = out
         return self.conv(name + ".cv2", [cur, ab.slice(c, c)], c2, 1, 1)
@@ -848,20 +867,17 @@ class Plan:
             raise NotImplementedError(f"{name}: cv1's {c3} channels do not chunk into two halves")
         # fp16 path, a chunk or branch width that is no multiple of 8 (yolov9m's P4 stage: 360 -> 180 + 180, branches of 180): every piece
         # of the concat is carried on the next multiple of 8 with zero weights and bias in the padding, as c2f / c3k do (T.cmap)
-        pad = not self.f32_mode and bool(h % 8 or c4 % 8)
-        h8, c8 = (make_divisible(h, 8), make_divisible(c4, 8)) if pad else (h, c4)
         H, W = xs[0].H, xs[0].W
-        cat = self.alloc(2 * h8 + 2 * c8, H, W)
-        if pad:
-            cat = cat.padded([(h8, h), (h8, h), (c8, c4), (c8, c4)])
+        cat, h8 = self.pieces([h, h, c4, c4], H, W)
+        c8 = self.stored(c4)
         self.conv(name + ".cv1", xs, 2 * h8, 1, 1, dst=cat.slice(0, 2 * h8))
         src = cat.slice(h8, h8)
         for j, cv in enumerate(("cv2", "cv3")):
             dst = cat.slice(2 * h8 + j * c8, c8)
             if rep:
-                t = self.alloc(c8, H, W)
-                if pad:
-                    t = t.padded([(c8, c4)])
+                t = self.pieces([c4], H, W)[0]
+                if cat.cmap is not None and t.cmap is None:  # (padded chunks beside a branch width that needs none: the branch's
+                    t = t.padded([(c8, c4)])                  # map still says which channels are real, and its weight records with it)
                 self.c3k(f"{name}.{cv}.0", src, t, n, True, (3, 3), rep=True)
                 self.conv(f"{name}.{cv}.1", t, c8, 3, 1, dst=dst)
             else:
@@ -1106,329 +1122,319 @@ class Plan:
     RELU_KINDS = (L.OP_CONV_FIRST, L.OP_FIRST_POOL, L.OP_STEM, L.OP_CONV, L.OP_COPY, L.OP_S2D, L.OP_SPPF_POOL, L.OP_MAXPOOL, L.OP_DECODE, L.OP_RAW_NCHW)
 
     def _build(self):
+        """The bookkeeping every layer shares; what a module lowers to is its entry of LOWERINGS below."""
         d = self.cfg
-        scales = d.get("scales")
-        depth, width, max_ch = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
-        scale = d.get("scale")
-        if scales:
-            if not scale:
-                scale = next(iter(scales))
-            depth, width, max_ch = scales[scale]
-        nc = d["nc"]
-        relu = self.act_id == L.ACT_RELU
-        legacy = True
+        depth, self.width, self.max_ch, self.scale = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf"), d.get("scale")
+        if d.get("scales"):
+            if not self.scale:
+                self.scale = next(iter(d["scales"]))
+            depth, self.width, self.max_ch = d["scales"][self.scale]
+        nc, relu = d["nc"], self.act_id == L.ACT_RELU
+        self.legacy = True  # Detect's class branch is the heavy one (head.py:44-56) until a C3k2 says otherwise (tasks.py:1048)
+        self.layers = layers = list(d["backbone"]) + list(d["head"])
         outs: List = []   # per layer: T, or list[T] for a lazy Concat
-        chans: List[int] = []
-        x = None
-        layers = list(d["backbone"]) + list(d["head"])
+        x, ly, last, lowerings = None, _Layer(), len(layers) - 1, self.LOWERINGS
         for i, (f, n, m, args) in enumerate(layers):
             name = f"model.{i}"
             args = [nc if a == "nc" else a for a in args]
-            arg = lambda j, default: args[j] if len(args) > j else default  # noqa: E731
-            n = max(round(n * depth), 1) if n > 1 else n
             if f != -1:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
-            if isinstance(x, _ZeroPadded) and m != "nn.MaxPool2d":
-                raise NotImplementedError(f"model.{i - 1}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] (model.{i} is {m})")
+            if isinstance(x, _ZeroPadded):
+                x.gate(i, m)
             if relu and m not in self.RELU_MODULES:
                 # ReLU exists in the kernels of CONV_FIRST / FIRST_POOL / STEM / CONV alone; every block module lowers to other kinds as
                 # well (and, in this fork, would keep SiLU anyway: block.py:13 shadows Conv there).  No silent SiLU where the reference
                 # may hold ReLU, or the reverse: the graph stays on the reference
                 raise NotImplementedError(f"{name}: {m} under activation nn.ReLU() is not accelerated (ReLU graphs: {', '.join(self.RELU_MODULES)})")
-            first_op = len(self.ops)
-            if m in ("Conv", "C3k2", "C2f", "C2", "SPPF", "C2PSA", "C3k2_gai", "SCDown", "C3", "DWConv", "GhostConv", "C3Ghost", "GhostBottleneck",
-                     "C2fCIB", "PSA", "Bottleneck", "SPP"):
-                c2 = make_divisible(min(args[0], max_ch) * width, 8)
-                if m == "Conv":
-                    k, s = arg(1, 1), arg(2, 1)
-                    pad = k // 2 if arg(3, None) is None else args[3]
-                    if n > 1:
-                        # parse_model's nn.Sequential of n Convs (tasks.py:1094), every one built Conv(c1, c2, k, s): model.i.0 .. model.i.{n-1}
-                        # (YOLOv6's equal-width 3x3 chains).  From the second on a link reads c2 channels, so the chain exists where c1 == c2
-                        if i == 0:
-                            raise NotImplementedError(f"{name}: an image conv repeated {n} times is not accelerated")
-                        if not isinstance(x, T) or x.C != c2:
-                            raise NotImplementedError(f"{name}: {n} chained Convs need an input of their own width ({c2} channels)")
-                        if pad != k // 2:
-                            raise NotImplementedError(f"Conv with padding {pad} != k // 2 is not accelerated")
-                        y = x
-                        for j in range(n):
-                            y = self.conv(f"{name}.{j}", y, c2, k, s)
-                    elif i == 0:
-                        if (k, s, pad) not in ((3, 2, 1), (3, 1, 1), (6, 2, 2)):
-                            raise NotImplementedError(f"image conv k={k} s={s} p={pad}: 3x3 s2 p1, 3x3 s1 p1 or 6x6 s2 p2 only")
-                        y = self.conv_first(name, c2, k, s, pad)
-                    else:
-                        assert isinstance(x, T) or all(isinstance(t, T) for t in x)  # (a list: a two-operand Concat, yolov3-tiny's layer 19)
-                        if pad != k // 2:
-                            raise NotImplementedError(f"Conv with padding {pad} != k // 2 is not accelerated")
-                        y = self.conv(name, x, c2, k, s)
-                elif m == "C3":  # block.py:3320-3334; parse_model inserts the repeat count (tasks.py:1038)
-                    x0 = x[0] if isinstance(x, list) else x
-                    y = self.alloc(c2, x0.H, x0.W)
-                    self.c3k(name, x, y, n, bool(arg(1, True)), k=(1, 3))
-                elif m == "C3Ghost":  # block.py:3374-3381; the repeat count is inserted as for C3 (tasks.py:1033)
-                    x0 = x[0] if isinstance(x, list) else x
-                    y = self.alloc(c2, x0.H, x0.W)
-                    self.c3k(name, x, y, n, True, ghost=True)
-                elif m == "GhostConv":  # conv.py:280-293, args [c2, k, s, g, act]; the yamls' stride-2 3x3 downsamplers
-                    if x is None or arg(3, 1) != 1:
-                        raise NotImplementedError(f"{name}: GhostConv on the image or with g = {arg(3, 1)} is not accelerated")
-                    if (c2 // 2) % 8 and not self.f32_mode:
-                        raise NotImplementedError(f"{name}: a top-level GhostConv with halves of {c2 // 2} channels is not on the fp16 path (multiples of 8)")
-                    y = self.ghostconv(name, x, c2, arg(1, 1), arg(2, 1), bool(arg(4, True)))
-                elif m == "GhostBottleneck":  # block.py:3384-3402, args [c2, k, s]
-                    assert isinstance(x, T)
-                    y = self.alloc(c2, x.H, x.W)
-                    self.ghost_bottleneck(name, x, y, arg(2, 1))
-                elif m == "DWConv":  # conv.py:224-229: Conv(c1, c2, k, s, g=gcd(c1, c2))
-                    assert isinstance(x, T)
-                    k, s = arg(1, 1), arg(2, 1)
-                    if c2 != x.C:
-                        raise NotImplementedError(f"DWConv {x.C} -> {c2}: only the depthwise case c1 == c2 is accelerated")
-                    y = self.dwconv_g(name, x, k, k, s, x.C)
-                elif m == "C3k2":
-                    legacy = False
-                    c3k, e = bool(arg(1, False)), arg(2, 0.5)
-                    if scale and scale in "mlx":
-                        c3k = True
-                    y = self.c2f(name, x, c2, n, True, e, "c3k" if c3k else "bottleneck")
-                elif m == "C3k2_gai":  # tasks.py:1038: repeat count inserted, no m/l/x override, `legacy` untouched
-                    c3k, e = bool(arg(1, False)), arg(2, 0.5)
-                    y = self.c2f(name, x, c2, n, True, e, "c3k_gai" if c3k else "pmsfa")
-                elif m == "SCDown":
-                    assert isinstance(x, T)
-                    y = self.scdown(name, x, c2, args[1], args[2])
-                elif m == "C2f":
-                    shortcut = bool(arg(1, False))
-                    y = self.c2f(name, x, c2, n, shortcut, 0.5, "c2f")
-                elif m == "C2fCIB":  # block.py:4215-4232, args [c2, shortcut, lk]; the repeat count is inserted as for C2f (tasks.py:1037-1043)
-                    y = self.c2f(name, x, c2, n, bool(arg(1, False)), 0.5, "cib", lk=bool(arg(2, False)))
-                elif m == "PSA":  # block.py:4386-4426, args [c2]: no repeat count (tasks.py:1010), one block
-                    assert isinstance(x, T)
-                    y = self.c2psa(name, x, c2, 1, psa=True)
-                elif m == "C2":  # the necks of yolov8-p6.yaml / yolov8-seg-p6.yaml
-                    shortcut = bool(arg(1, True))
-                    y = self.c2(name, x, c2, n, shortcut)
-                elif m == "SPPF":
-                    assert isinstance(x, T) and arg(1, 5) == 5
-                    y = self.sppf(name, x, c2)
-                elif m == "SPP":  # block.py:3088-3111, args [c2, k]: cv2(cat(x', m5 x', m9 x', m13 x')), x' = cv1(x).  Stride-1 max pools
-                    # compose -- m5 . m5 = m9, m5 . m5 . m5 = m13, bit for bit -- so k = (5, 9, 13) is SPPF's dataflow under the same names
-                    if not isinstance(x, T) or list(arg(1, (5, 9, 13))) != [5, 9, 13]:
-                        raise NotImplementedError(f"{name}: SPP with k = {arg(1, None)} (k = [5, 9, 13] on one input is accelerated)")
-                    if (x.C // 2) % 8 and not self.f32_mode:
-                        raise NotImplementedError(f"{name}: SPP with a hidden width of {x.C // 2} channels is not on the fp16 path (multiples of 8)")
-                    y = self.sppf(name, x, c2)
-                elif m == "Bottleneck":  # block.py:3405-3419, args [c2, shortcut, g, k, e]; n > 1: parse_model's nn.Sequential (tasks.py:1094)
-                    if arg(2, 1) != 1:
-                        raise NotImplementedError(f"{name}: Bottleneck with g = {args[2]} is not accelerated")
-                    if n > 1 and (not isinstance(x, T) or x.C != c2):
-                        raise NotImplementedError(f"{name}: {n} chained Bottlenecks need an input of their own width ({c2} channels)")
-                    y = x
-                    for j in range(n):
-                        y = self.top_bottleneck(name if n == 1 else f"{name}.{j}", y, c2, bool(arg(1, True)), tuple(arg(3, (3, 3))), arg(4, 0.5))
-                else:
-                    assert isinstance(x, T)
-                    y = self.c2psa(name, x, c2, n)
-                cout = c2
-            elif m in ("RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN"):
-                # tasks.py:995-1023: c2 scaled like a Conv's, the other arguments literal, no repeat count inserted (n stays 1)
-                c2 = make_divisible(min(args[0], max_ch) * width, 8)
-                if m in ("RepNCSPELAN4", "ELAN1"):
-                    rep = m == "RepNCSPELAN4"
-                    y = self.elan(name, x, c2, args[1], args[2], arg(3, 1) if rep else 0, rep)
-                else:
-                    assert isinstance(x, T)
-                    if m == "SPPELAN":
-                        if arg(2, 5) != 5:
-                            raise NotImplementedError(f"{name}: SPPELAN with k = {args[2]} (the pool kernel is built for 5)")
-                        if args[1] % 8 and not self.f32_mode:
-                            raise NotImplementedError(f"{name}: SPPELAN with a hidden width of {args[1]} channels is not on the fp16 path (multiples of 8)")
-                        y = self.sppf(name, x, c2, args[1], "cv5")
-                    else:
-                        y = self.aconv(name, x, c2) if m == "AConv" else self.adown(name, x, c2)
-                cout = c2
-            elif m == "MSCAAttention":  # tasks.py:1052-1054
-                assert isinstance(x, T)
-                y = self.msca(name, x)
-                cout = x.C
-            elif m == "ELA":  # tasks.py:1066-1070: built on the input's channels
-                assert isinstance(x, T)
-                y = self.ela(name, x)
-                cout = x.C
-            elif m == "nn.ZeroPad2d":
-                # accepted in one place: [[0, 1, 0, 1]] in front of nn.MaxPool2d [2, 1, 0] that reads it alone (yolov3-tiny's layers 11 + 12);
-                # the pair is one MAXPOOL of mode 1, emitted at the pool
-                nxt = layers[i + 1] if i + 1 < len(layers) else None
-                if not isinstance(x, T) or [list(a) if isinstance(a, (list, tuple)) else a for a in args] != [[0, 1, 0, 1]]:
-                    raise NotImplementedError(f"{name}: nn.ZeroPad2d {args} (only [[0, 1, 0, 1]] on one input is accelerated)")
-                if nxt is None or nxt[0] != -1 or nxt[2] != "nn.MaxPool2d" or list(nxt[3]) != [2, 1, 0]:
-                    raise NotImplementedError(f"{name}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] reading it alone")
-                for j, (fj, _, _, _) in enumerate(layers):
-                    if j != i + 1 and any((v if v >= 0 else j + v) == i for v in ([fj] if isinstance(fj, int) else fj)):
-                        raise NotImplementedError(f"{name}: the output of nn.ZeroPad2d is read by model.{j} as well: the padded map is never stored")
-                y = _ZeroPadded(x)
-                cout = x.C
-            elif m == "nn.MaxPool2d":
-                k, s, p = arg(0, None), arg(1, None), arg(2, 0)
-                if isinstance(x, _ZeroPadded):
-                    assert (k, s, p) == (2, 1, 0)
-                    y = self.maxpool(name, x.src, 1)
-                elif isinstance(x, T) and (k, s, p) == (2, 2, 0) and len(args) <= 3:
-                    y = self.maxpool(name, x, 0)
-                else:
-                    raise NotImplementedError(f"{name}: nn.MaxPool2d {args} (only [2, 2, 0], and [2, 1, 0] behind nn.ZeroPad2d [[0, 1, 0, 1]], are accelerated)")
-                cout = y.C
-            elif m == "nn.ConvTranspose2d":
-                # args [c2, k, s, p, output_padding, groups, bias, dilation]; the class is in parse_model's base-module set (tasks.py:1006),
-                # so c2 is width-scaled like a Conv's and c1 put in front.  The 2x2 stride-2 upsampler is the accelerated form
-                if not isinstance(x, T) or x.up:
-                    raise NotImplementedError(f"{name}: nn.ConvTranspose2d on a Concat or an upsampled view is not accelerated")
-                if (arg(1, 1), arg(2, 1), arg(3, 0), arg(4, 0), arg(5, 1), arg(6, True), arg(7, 1)) != (2, 2, 0, 0, 1, True, 1) or len(args) > 8 or n != 1:
-                    raise NotImplementedError(f"{name}: nn.ConvTranspose2d {args} (kernel 2, stride 2, padding 0, no output padding, one group, "
-                                              "with bias, once, is accelerated)")
-                c2 = make_divisible(min(args[0], max_ch) * width, 8)
-                y = self.deconv(name, x, c2)
-                cout = c2
-            elif m == "nn.Upsample":
-                assert isinstance(x, T) and not x.up and args[1] == 2 and args[2] == "nearest"
-                y = T(x.buf, x.ld, x.coff, x.C, x.H * 2, x.W * 2, True, x.f32)
-                cout = x.C
-            elif m == "Concat":
-                assert isinstance(x, list) and len(x) == 2, "only two-operand Concat feeding a conv is accelerated"
-                # an operand that is itself a (lazy) Concat -- BS-YOLO's layer 21 reads layer 13 -- is materialised once
-                for j, t in enumerate(x):
-                    if isinstance(t, list):
-                        assert all(isinstance(u, T) for u in t)
-                        real = self.alloc(sum(u.C for u in t), t[0].H, t[0].W)
-                        c0 = 0
-                        for u in t:
-                            self.copy(f"{name}.cat{j}", u, real.slice(c0, u.C))
-                            c0 += u.C
-                        x[j] = real
-                assert all(isinstance(t, T) for t in x)
-                y = list(x)
-                cout = sum(t.C for t in x)
-            elif m in ("Detect", "Segment", "OBB", "Pose", "v10Detect"):
-                xs = x if isinstance(x, list) else [x]
-                assert all(isinstance(t, T) for t in xs)
-                if m == "Segment":  # head.py:175-197; npr scaled like parse_model does (tasks.py:1082-1083)
-                    nm = args[1]
-                    npr = make_divisible(min(args[2], max_ch) * width, 8)
-                    self.proto(name + ".proto", xs[0], npr, nm)
-                    self.detect(name, xs, args[0], legacy, nm=nm)
-                elif m == "OBB":  # head.py:200-227, args [nc, ne] (+ the channel list parse_model appends, tasks.py:1075)
-                    ne = 1 if isinstance(arg(1, 1), (list, tuple)) else arg(1, 1)
-                    if ne != 1:
-                        raise NotImplementedError(f"OBB with ne = {ne}: dist2rbox (utils/tal.py:404-423) decodes one angle")
-                    self.detect(name, xs, args[0], legacy, ne=ne)
-                elif m == "Pose":  # head.py:230-279, args [nc, kpt_shape] (+ the channel list parse_model appends).  Every pose yaml of the
-                    # reference names the model's top-level kpt_shape (tasks.py:981-985 evaluates the string; PoseModel.yaml holds the key,
-                    # with a dataset's override applied, tasks.py:429-431), and that form is the accelerated one: a head line that spells
-                    # the pair out stays on the reference, as every Pose line did before the plan had a pose form
-                    if arg(1, None) != "kpt_shape":
-                        raise NotImplementedError(f"{name}: Pose with the argument {arg(1, None)!r} (the yaml's form, the name 'kpt_shape', is accelerated)")
-                    ks = d.get("kpt_shape")
-                    if not isinstance(ks, (list, tuple)) or len(ks) != 2:
-                        raise NotImplementedError(f"{name}: the Pose head names kpt_shape, the model description has {ks!r} (a pair: keypoints, channels of each)")
-                    nkpt, ndim = int(ks[0]), int(ks[1])
-                    if ndim not in (2, 3) or not 1 <= nkpt <= 64:  # the limits of csrc/pose.hip and of the decode launch
-                        raise NotImplementedError(f"{name}: Pose with kpt_shape ({nkpt}, {ndim}): 1 to 64 keypoints of 2 or 3 channels are accelerated")
-                    self.detect(name, xs, args[0], legacy, nk=nkpt * ndim, kdim=ndim)
-                    self.meta.update(task="pose", nk=nkpt * ndim, kpt_shape=(nkpt, ndim))  # (only a pose plan's meta has these keys)
-                elif m == "v10Detect":  # head.py:592-625: Detect with end2end = True and the light class branch whatever the graph holds
-                    if i != len(layers) - 1:
-                        raise NotImplementedError(f"{name}: v10Detect is accelerated as the last layer only")
-                    self.detect(name, xs, args[0], False, end2end=True)
-                else:
-                    self.detect(name, xs, args[0], legacy)
-                y, cout = None, 0
-            elif m == "Classify":  # head.py:282-304, args [nc, k, s, p, g] (tasks.py:1016-1023 puts c1 in front)
-                if not isinstance(x, T):
-                    raise NotImplementedError(f"{name}: Classify fed by {len(x)} tensors (its torch.cat, head.py:298) is not accelerated")
-                if i != len(layers) - 1:
-                    raise NotImplementedError(f"{name}: Classify is accelerated as the last layer only")
-                if (arg(1, 1), arg(2, 1), arg(3, None), arg(4, 1)) != (1, 1, None, 1):
-                    raise NotImplementedError(f"{name}: Classify with k, s, p, g = {args[1:5]} (the default 1x1 conv is accelerated)")
-                # tasks.py:1019-1020: an output width that is not the class count is scaled like any other
-                self.classify(name, x, args[0] if args[0] == nc else make_divisible(min(args[0], max_ch) * width, 8))
-                y, cout = None, 0
-            else:
+            lower, scaled = lowerings.get(m, (None, False))
+            if lower is None:
                 raise NotImplementedError(f"module {m} is not on the accelerated path")
+            first_op = len(self.ops)
+            ly.i, ly.name, ly.m, ly.x, ly.args, ly.n, ly.last = i, name, m, x, args, max(round(n * depth), 1) if n > 1 else n, i == last
+            ly.c2 = self._scaled(args[0]) if scaled else None
+            x = lower(self, ly)
             if relu:  # what RELU_MODULES promises, checked on the ops themselves
                 for o in self.ops[first_op:]:
                     if o["kind"] not in self.RELU_KINDS:
                         raise NotImplementedError(f"{name}: {m} lowers to op {o['name']} of kind {o['kind']}, which has no ReLU (activation nn.ReLU())")
-            outs.append(y)
-            chans.append(cout)
-            x = y
+            outs.append(x)
         self.layer_out = [None if isinstance(t, _ZeroPadded) else t for t in outs]
-        self.meta.update(scale=scale, n_layers=len(layers), legacy=legacy)
+        self.meta.update(scale=self.scale, n_layers=len(layers), legacy=self.legacy)
         self._fuse_stem()
         self._fuse_first_pool()
 
-    def _fuse_first_pool(self):
-        """Peephole: layer 0 (image conv 3x3 s1 p1) + layer 1 (MaxPool2d(2, 2, 0) fed by layer 0 alone) -> one OP_FIRST_POOL launch
-        (csrc/conv_first.hip); layer 0's map is then never materialised (layer_out[0] = None), as in _fuse_stem."""
-        if not self.fuse_first_pool or len(self.ops) < 2:
-            return
-        a, b = self.ops[0], self.ops[1]
-        if a["kind"] != L.OP_CONV_FIRST or b["kind"] != L.OP_MAXPOOL or (a["ksize"], a["stride"], a["pad"]) != (3, 1, 1) or b["level"] != 0:
-            return
-        mid = a["dst"]
-        if b["src0"] is not mid or not kernel_takes("first_pool", mid.C, self.H, self.W):
-            return
-        for o in self.ops[2:]:  # layer 0 must have no other reader
-            for key in ("src0", "src1", "res"):
-                t = o.get(key)
-                if t is not None and t.buf == mid.buf:
-                    return
-        self.buf_bytes[mid.buf] = 16  # never written
-        self._emit(L.OP_FIRST_POOL, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], H=self.H, W=self.W, ksize=3, stride=1,
-                   pad=1, act=a["act"], wkey=a["wkey"], in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"])
-        self.ops[0:2] = [self.ops.pop()]  # (layer 0's flops are counted already)
-        self.layer_out[0] = None
+    def _scaled(self, c: int) -> int:  # parse_model's width scaling of a channel count (tasks.py:1016)
+        return make_divisible(min(c, self.max_ch) * self.width, 8)
 
-    def _fuse_stem(self):
-        """Peephole: layer 0 (image conv) + layer 1 (3x3 s2 conv fed by layer 0 alone) -> one OP_STEM launch
-        (csrc/stem_fused.hip); layer 0's map is then never materialised (layer_out[0] = None)."""
-        if not self.fuse_stem or len(self.ops) < 2:
+    # ---- lowerings (LOWERINGS below): ly is the layer's _Layer, the result the layer's output -- a T, a list of T (a lazy Concat), a
+    # _ZeroPadded, or None (a head).  A module's arguments are [c2, ...] as the yaml has them; ly.c2 is the first one width-scaled
+    def _m_conv(self, ly: _Layer):
+        name, x, n, c2, k, s = ly.name, ly.x, ly.n, ly.c2, ly.arg(1, 1), ly.arg(2, 1)
+        pad = k // 2 if ly.arg(3, None) is None else ly.args[3]
+        if ly.i == 0:
+            if n > 1:
+                raise NotImplementedError(f"{name}: an image conv repeated {n} times is not accelerated")
+            if (k, s, pad) not in ((3, 2, 1), (3, 1, 1), (6, 2, 2)):
+                raise NotImplementedError(f"image conv k={k} s={s} p={pad}: 3x3 s2 p1, 3x3 s1 p1 or 6x6 s2 p2 only")
+            return self.conv_first(name, c2, k, s, pad)
+        # n > 1: parse_model's nn.Sequential of n Convs (tasks.py:1094), every one built Conv(c1, c2, k, s): model.i.0 .. model.i.{n-1}
+        # (YOLOv6's equal-width 3x3 chains).  From the second on a link reads c2 channels, so the chain exists where c1 == c2
+        if n > 1 and (not isinstance(x, T) or x.C != c2):
+            raise NotImplementedError(f"{name}: {n} chained Convs need an input of their own width ({c2} channels)")
+        assert n > 1 or isinstance(x, T) or all(isinstance(t, T) for t in x)  # (a list: a two-operand Concat, yolov3-tiny's layer 19)
+        if pad != k // 2:
+            raise NotImplementedError(f"Conv with padding {pad} != k // 2 is not accelerated")
+        if n > 1:
+            for j in range(n):
+                x = self.conv(f"{name}.{j}", x, c2, k, s)
+            return x
+        return self.conv(name, x, c2, k, s)
+
+    def _m_c3(self, ly: _Layer):  # C3 (block.py:3320-3334), C3Ghost (:3374-3381); parse_model inserts the repeat count (tasks.py:1033, :1038)
+        y, ghost = self.alloc_like(ly.x, ly.c2), ly.m == "C3Ghost"
+        self.c3k(ly.name, ly.x, y, ly.n, ghost or bool(ly.arg(1, True)), k=(3, 3) if ghost else (1, 3), ghost=ghost)
+        return y
+
+    def _m_ghostconv(self, ly: _Layer):  # conv.py:280-293, args [c2, k, s, g, act]; the yamls' stride-2 3x3 downsamplers
+        if ly.x is None or ly.arg(3, 1) != 1:
+            raise NotImplementedError(f"{ly.name}: GhostConv on the image or with g = {ly.arg(3, 1)} is not accelerated")
+        self._fp16_mult8(ly.c2 // 2, f"{ly.name}: a top-level GhostConv with halves of {ly.c2 // 2} channels is not on the fp16 path (multiples of 8)")
+        return self.ghostconv(ly.name, ly.x, ly.c2, ly.arg(1, 1), ly.arg(2, 1), bool(ly.arg(4, True)))
+
+    def _m_ghost_bottleneck(self, ly: _Layer):  # block.py:3384-3402, args [c2, k, s]
+        assert isinstance(ly.x, T)
+        y = self.alloc_like(ly.x, ly.c2)
+        self.ghost_bottleneck(ly.name, ly.x, y, ly.arg(2, 1))
+        return y
+
+    def _m_dwconv(self, ly: _Layer):  # conv.py:224-229: Conv(c1, c2, k, s, g=gcd(c1, c2))
+        x, k, s = ly.x, ly.arg(1, 1), ly.arg(2, 1)
+        assert isinstance(x, T)
+        if ly.c2 != x.C:
+            raise NotImplementedError(f"DWConv {x.C} -> {ly.c2}: only the depthwise case c1 == c2 is accelerated")
+        return self.dwconv_g(ly.name, x, k, k, s, x.C)
+
+    def _m_c3k2(self, ly: _Layer):  # C3k2, and C3k2_gai (tasks.py:1038: the repeat count inserted, no m/l/x override, `legacy` untouched)
+        c3k, gai = bool(ly.arg(1, False)), ly.m == "C3k2_gai"
+        if not gai:
+            self.legacy = False
+            c3k = bool(self.scale and self.scale in "mlx") or c3k  # (tasks.py:1046-1049)
+        return self.c2f(ly.name, ly.x, ly.c2, ly.n, True, ly.arg(2, 0.5), ("c3k_gai" if c3k else "pmsfa") if gai else ("c3k" if c3k else "bottleneck"))
+
+    def _m_c2f(self, ly: _Layer):  # C2f [c2, shortcut]; C2fCIB (block.py:4215-4232) [c2, shortcut, lk]; repeat count inserted (tasks.py:1037-1043)
+        cib = ly.m == "C2fCIB"
+        return self.c2f(ly.name, ly.x, ly.c2, ly.n, bool(ly.arg(1, False)), 0.5, "cib" if cib else "c2f", lk=cib and bool(ly.arg(2, False)))
+
+    def _m_c2(self, ly: _Layer):  # the necks of yolov8-p6.yaml / yolov8-seg-p6.yaml
+        return self.c2(ly.name, ly.x, ly.c2, ly.n, bool(ly.arg(1, True)))
+
+    def _m_scdown(self, ly: _Layer):
+        assert isinstance(ly.x, T)
+        return self.scdown(ly.name, ly.x, ly.c2, ly.args[1], ly.args[2])
+
+    def _m_c2psa(self, ly: _Layer):  # C2PSA; PSA (block.py:4386-4426), args [c2]: no repeat count (tasks.py:1010), one block
+        assert isinstance(ly.x, T)
+        return self.c2psa(ly.name, ly.x, ly.c2, 1 if ly.m == "PSA" else ly.n, psa=ly.m == "PSA")
+
+    def _m_spp(self, ly: _Layer):
+        """SPPF; SPP (block.py:3088-3111, args [c2, k]): cv2(cat(x', m5 x', m9 x', m13 x')), x' = cv1(x) -- stride-1 max pools compose, m5 . m5
+        = m9, m5 . m5 . m5 = m13, bit for bit, so k = (5, 9, 13) is SPPF's dataflow under the same names; SPPELAN (args [c2, c3, k])."""
+        m, name, x = ly.m, ly.name, ly.x
+        if m == "SPPF":
+            assert isinstance(x, T) and ly.arg(1, 5) == 5
+        elif m == "SPP":
+            if not isinstance(x, T) or list(ly.arg(1, (5, 9, 13))) != [5, 9, 13]:
+                raise NotImplementedError(f"{name}: SPP with k = {ly.arg(1, None)} (k = [5, 9, 13] on one input is accelerated)")
+            self._fp16_mult8(x.C // 2, f"{name}: SPP with a hidden width of {x.C // 2} channels is not on the fp16 path (multiples of 8)")
+        else:
+            assert isinstance(x, T)
+            if ly.arg(2, 5) != 5:
+                raise NotImplementedError(f"{name}: SPPELAN with k = {ly.args[2]} (the pool kernel is built for 5)")
+            self._fp16_mult8(ly.args[1], f"{name}: SPPELAN with a hidden width of {ly.args[1]} channels is not on the fp16 path (multiples of 8)")
+            return self.sppf(name, x, ly.c2, ly.args[1], "cv5")
+        return self.sppf(name, x, ly.c2)
+
+    def _m_bottleneck(self, ly: _Layer):  # block.py:3405-3419, args [c2, shortcut, g, k, e]; n > 1: parse_model's nn.Sequential (tasks.py:1094)
+        name, x, n, c2 = ly.name, ly.x, ly.n, ly.c2
+        if ly.arg(2, 1) != 1:
+            raise NotImplementedError(f"{name}: Bottleneck with g = {ly.args[2]} is not accelerated")
+        if n > 1 and (not isinstance(x, T) or x.C != c2):
+            raise NotImplementedError(f"{name}: {n} chained Bottlenecks need an input of their own width ({c2} channels)")
+        for j in range(n):
+            x = self.top_bottleneck(name if n == 1 else f"{name}.{j}", x, c2, bool(ly.arg(1, True)), tuple(ly.arg(3, (3, 3))), ly.arg(4, 0.5))
+        return x
+
+    def _m_elan(self, ly: _Layer):  # YOLOv9's modules (tasks.py:995-1023): the arguments behind c2 literal, no repeat count inserted (n stays 1)
+        rep = ly.m == "RepNCSPELAN4"  # (else ELAN1)
+        return self.elan(ly.name, ly.x, ly.c2, ly.args[1], ly.args[2], ly.arg(3, 1) if rep else 0, rep)
+
+    def _m_down(self, ly: _Layer):
+        assert isinstance(ly.x, T)
+        return self.aconv(ly.name, ly.x, ly.c2) if ly.m == "AConv" else self.adown(ly.name, ly.x, ly.c2)
+
+    def _m_attention(self, ly: _Layer):  # MSCAAttention (tasks.py:1052-1054), ELA (:1066-1070): built on the input's channels
+        assert isinstance(ly.x, T)
+        return self.msca(ly.name, ly.x) if ly.m == "MSCAAttention" else self.ela(ly.name, ly.x)
+
+    def _m_zeropad(self, ly: _Layer):
+        """Accepted in one place: [[0, 1, 0, 1]] in front of nn.MaxPool2d [2, 1, 0] that reads it alone (yolov3-tiny's layers 11 + 12);
+        the pair is one MAXPOOL of mode 1, emitted at the pool."""
+        i, name, nxt = ly.i, ly.name, None if ly.last else self.layers[ly.i + 1]
+        if not isinstance(ly.x, T) or [list(a) if isinstance(a, (list, tuple)) else a for a in ly.args] != [[0, 1, 0, 1]]:
+            raise NotImplementedError(f"{name}: nn.ZeroPad2d {ly.args} (only [[0, 1, 0, 1]] on one input is accelerated)")
+        if nxt is None or nxt[0] != -1 or nxt[2] != "nn.MaxPool2d" or list(nxt[3]) != [2, 1, 0]:
+            raise NotImplementedError(f"{name}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] reading it alone")
+        for j, (fj, _, _, _) in enumerate(self.layers):
+            if j != i + 1 and any((v if v >= 0 else j + v) == i for v in ([fj] if isinstance(fj, int) else fj)):
+                raise NotImplementedError(f"{name}: the output of nn.ZeroPad2d is read by model.{j} as well: the padded map is never stored")
+        return _ZeroPadded(ly.x)
+
+    def _m_maxpool(self, ly: _Layer):
+        x, ksp = ly.x, (ly.arg(0, None), ly.arg(1, None), ly.arg(2, 0))
+        if isinstance(x, _ZeroPadded):
+            assert ksp == (2, 1, 0)
+            return self.maxpool(ly.name, x.src, 1)
+        if isinstance(x, T) and ksp == (2, 2, 0) and len(ly.args) <= 3:
+            return self.maxpool(ly.name, x, 0)
+        raise NotImplementedError(f"{ly.name}: nn.MaxPool2d {ly.args} (only [2, 2, 0], and [2, 1, 0] behind nn.ZeroPad2d [[0, 1, 0, 1]], are accelerated)")
+
+    def _m_deconv(self, ly: _Layer):
+        """args [c2, k, s, p, output_padding, groups, bias, dilation]; the class is in parse_model's base-module set (tasks.py:1006), so c2 is
+        width-scaled like a Conv's and c1 put in front -- here behind the refusals, which read no c2.  The 2x2 stride-2 upsampler is accelerated."""
+        name, x, arg = ly.name, ly.x, ly.arg
+        if not isinstance(x, T) or x.up:
+            raise NotImplementedError(f"{name}: nn.ConvTranspose2d on a Concat or an upsampled view is not accelerated")
+        if (arg(1, 1), arg(2, 1), arg(3, 0), arg(4, 0), arg(5, 1), arg(6, True), arg(7, 1)) != (2, 2, 0, 0, 1, True, 1) or len(ly.args) > 8 or ly.n != 1:
+            raise NotImplementedError(f"{name}: nn.ConvTranspose2d {ly.args} (kernel 2, stride 2, padding 0, no output padding, one group, "
+                                      "with bias, once, is accelerated)")
+        return self.deconv(name, x, self._scaled(ly.args[0]))
+
+    def _m_upsample(self, ly: _Layer):
+        x = ly.x
+        assert isinstance(x, T) and not x.up and ly.args[1] == 2 and ly.args[2] == "nearest"
+        return T(x.buf, x.ld, x.coff, x.C, x.H * 2, x.W * 2, True, x.f32)
+
+    def _m_concat(self, ly: _Layer):
+        x = ly.x
+        assert isinstance(x, list) and len(x) == 2, "only two-operand Concat feeding a conv is accelerated"
+        for j, t in enumerate(x):  # an operand that is itself a (lazy) Concat -- BS-YOLO's layer 21 reads layer 13 -- is materialised once
+            if isinstance(t, list):
+                assert all(isinstance(u, T) for u in t)
+                real = self.alloc_like(t, sum(u.C for u in t))
+                c0 = 0
+                for u in t:
+                    self.copy(f"{ly.name}.cat{j}", u, real.slice(c0, u.C))
+                    c0 += u.C
+                x[j] = real
+        assert all(isinstance(t, T) for t in x)
+        return list(x)
+
+    def _m_head(self, ly: _Layer):  # Detect, Segment, OBB, Pose, v10Detect: args [nc, ...] (+ the channel list parse_model appends, tasks.py:1075)
+        m, name, args, arg = ly.m, ly.name, ly.args, ly.arg
+        xs = ly.x if isinstance(ly.x, list) else [ly.x]
+        assert all(isinstance(t, T) for t in xs)
+        if m == "Segment":  # head.py:175-197, args [nc, nm, npr]; npr scaled like parse_model does (tasks.py:1082-1083)
+            self.proto(name + ".proto", xs[0], self._scaled(args[2]), args[1])
+            self.detect(name, xs, args[0], self.legacy, nm=args[1])
+        elif m == "OBB":  # head.py:200-227, args [nc, ne]
+            ne = 1 if isinstance(arg(1, 1), (list, tuple)) else arg(1, 1)
+            if ne != 1:
+                raise NotImplementedError(f"OBB with ne = {ne}: dist2rbox (utils/tal.py:404-423) decodes one angle")
+            self.detect(name, xs, args[0], self.legacy, ne=ne)
+        elif m == "Pose":
+            # head.py:230-279, args [nc, kpt_shape].  Every pose yaml of the reference names the model's top-level kpt_shape
+            # (tasks.py:981-985 evaluates the string; PoseModel.yaml holds the key, with a dataset's override applied, tasks.py:429-431),
+            # and that form is the accelerated one: a head line that spells the pair out stays on the reference
+            if arg(1, None) != "kpt_shape":
+                raise NotImplementedError(f"{name}: Pose with the argument {arg(1, None)!r} (the yaml's form, the name 'kpt_shape', is accelerated)")
+            ks = self.cfg.get("kpt_shape")
+            if not isinstance(ks, (list, tuple)) or len(ks) != 2:
+                raise NotImplementedError(f"{name}: the Pose head names kpt_shape, the model description has {ks!r} (a pair: keypoints, channels of each)")
+            nkpt, ndim = int(ks[0]), int(ks[1])
+            if ndim not in (2, 3) or not 1 <= nkpt <= 64:  # the limits of csrc/pose.hip and of the decode launch
+                raise NotImplementedError(f"{name}: Pose with kpt_shape ({nkpt}, {ndim}): 1 to 64 keypoints of 2 or 3 channels are accelerated")
+            self.detect(name, xs, args[0], self.legacy, nk=nkpt * ndim, kdim=ndim)
+            self.meta.update(task="pose", nk=nkpt * ndim, kpt_shape=(nkpt, ndim))  # (only a pose plan's meta has these keys)
+        elif m == "v10Detect":  # head.py:592-625: Detect with end2end = True and the light class branch whatever the graph holds
+            if not ly.last:
+                raise NotImplementedError(f"{name}: v10Detect is accelerated as the last layer only")
+            self.detect(name, xs, args[0], False, end2end=True)
+        else:
+            self.detect(name, xs, args[0], self.legacy)
+
+    def _m_classify(self, ly: _Layer):  # head.py:282-304, args [nc, k, s, p, g] (tasks.py:1016-1023 puts c1 in front)
+        name, x, args, arg = ly.name, ly.x, ly.args, ly.arg
+        if not isinstance(x, T):
+            raise NotImplementedError(f"{name}: Classify fed by {len(x)} tensors (its torch.cat, head.py:298) is not accelerated")
+        if not ly.last:
+            raise NotImplementedError(f"{name}: Classify is accelerated as the last layer only")
+        if (arg(1, 1), arg(2, 1), arg(3, None), arg(4, 1)) != (1, 1, None, 1):
+            raise NotImplementedError(f"{name}: Classify with k, s, p, g = {args[1:5]} (the default 1x1 conv is accelerated)")
+        # tasks.py:1019-1020: an output width that is not the class count is scaled like any other
+        self.classify(name, x, args[0] if args[0] == self.cfg["nc"] else self._scaled(args[0]))
+
+    # Module name -> (its lowering, whether args[0] is a channel count that parse_model width-scales: the lowering's ly.c2).  A new
+    # module is one entry here and its lowering above; a module that is not here is not on the accelerated path
+    LOWERINGS = {
+        "Conv": (_m_conv, True), "DWConv": (_m_dwconv, True), "GhostConv": (_m_ghostconv, True), "GhostBottleneck": (_m_ghost_bottleneck, True),
+        "C3": (_m_c3, True), "C3Ghost": (_m_c3, True), "C3k2": (_m_c3k2, True), "C3k2_gai": (_m_c3k2, True), "C2f": (_m_c2f, True),
+        "C2fCIB": (_m_c2f, True), "C2": (_m_c2, True), "SCDown": (_m_scdown, True), "C2PSA": (_m_c2psa, True), "PSA": (_m_c2psa, True),
+        "SPPF": (_m_spp, True), "SPP": (_m_spp, True), "SPPELAN": (_m_spp, True), "Bottleneck": (_m_bottleneck, True),
+        "RepNCSPELAN4": (_m_elan, True), "ELAN1": (_m_elan, True), "AConv": (_m_down, True), "ADown": (_m_down, True),
+        "MSCAAttention": (_m_attention, False), "ELA": (_m_attention, False), "nn.Upsample": (_m_upsample, False), "Concat": (_m_concat, False),
+        "nn.ZeroPad2d": (_m_zeropad, False), "nn.MaxPool2d": (_m_maxpool, False), "nn.ConvTranspose2d": (_m_deconv, False),  # (scales c2 itself)
+        "Detect": (_m_head, False), "Segment": (_m_head, False), "OBB": (_m_head, False), "Pose": (_m_head, False), "v10Detect": (_m_head, False),
+        "Classify": (_m_classify, False),
+    }
+
+    def _fuse_layer0(self, on: bool, kind: int, match):
+        """Layer 0 (the image conv) and the one op of layer 1, fed by layer 0 alone, as one launch of `kind`: match(a, b) returns the fused
+        op's own fields where the pair is that peephole's (else None).  Layer 0's map is then never materialised (layer_out[0] = None)."""
+        if not on or len(self.ops) < 2 or self.ops[0]["kind"] != L.OP_CONV_FIRST:
             return
         a, b = self.ops[0], self.ops[1]
-        if a["kind"] != L.OP_CONV_FIRST or b["kind"] != L.OP_CONV:
-            return
         mid = a["dst"]
-        if (b["src0"] is not mid or b.get("src1") is not None or b.get("res") is not None or b["ksize"] != 3
-                or b["stride"] != 2 or b["out_f32"] or not b["act"] or b["act"] != a["act"] or a["ksize"] != 3 or a["stride"] != 2):
-            return
-        if not kernel_takes("stem_fused", mid.C, b["dst"].C, self.H, self.W):
+        fields = match(a, b) if b.get("src0") is mid else None
+        if fields is None:
             return
         for o in self.ops[2:]:  # layer 0 must have no other reader
-            for key in ("src0", "src1", "res"):
-                t = o.get(key)
+            for t in (o.get("src0"), o.get("src1"), o.get("res")):
                 if t is not None and t.buf == mid.buf:
                     return
         self.buf_bytes[mid.buf] = 16  # never written
-        self._emit(L.OP_STEM, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], ksize=3, stride=2, pad=1, act=a["act"],
-                   wkey=a["wkey"], wkey2=b["wkey"], mid_c=mid.C, in_dtype=self.in_dtype, mfma_flops=a["mfma_flops"] + b["mfma_flops"])
+        self._emit(kind, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], act=a["act"], wkey=a["wkey"],
+                   in_dtype=self.in_dtype, **fields)
         self.ops[0:2] = [self.ops.pop()]  # (the two layers' flops are counted already)
         self.layer_out[0] = None
 
-    # ---- workspace layout -----------------------------------------------------------------------------------------
-    _VIEW_KEYS = ("src0", "src1", "dst", "res")
-    _LIST_KEYS = ("box", "cls", "msk")
+    def _fuse_first_pool(self):
+        """Peephole: layer 0 (image conv 3x3 s1 p1) + layer 1 (MaxPool2d(2, 2, 0)) -> one OP_FIRST_POOL launch (csrc/conv_first.hip)."""
+        def match(a, b):
+            if (b["kind"] == L.OP_MAXPOOL and (a["ksize"], a["stride"], a["pad"]) == (3, 1, 1) and b["level"] == 0
+                    and kernel_takes("first_pool", a["dst"].C, self.H, self.W)):
+                return dict(H=self.H, W=self.W, ksize=3, stride=1, pad=1, mfma_flops=a["mfma_flops"])
+        self._fuse_layer0(self.fuse_first_pool, L.OP_FIRST_POOL, match)
 
+    def _fuse_stem(self):
+        """Peephole: layer 0 (image conv 3x3 s2) + layer 1 (3x3 s2 conv, the same activation) -> one OP_STEM launch (csrc/stem_fused.hip)."""
+        def match(a, b):
+            if (b["kind"] == L.OP_CONV and b.get("src1") is None and b.get("res") is None and b["ksize"] == 3 and b["stride"] == 2
+                    and not b["out_f32"] and b["act"] and b["act"] == a["act"] and a["ksize"] == 3 and a["stride"] == 2
+                    and kernel_takes("stem_fused", a["dst"].C, b["dst"].C, self.H, self.W)):
+                return dict(ksize=3, stride=2, pad=1, wkey2=b["wkey"], mid_c=a["dst"].C, mfma_flops=a["mfma_flops"] + b["mfma_flops"])
+        self._fuse_layer0(self.fuse_stem, L.OP_STEM, match)
+
+    # ---- workspace layout -----------------------------------------------------------------------------------------
     def op_buffers(self, o: dict) -> List[int]:
         """Indices of the workspace buffers an op reads or writes (external slots excluded)."""
-        views = [o.get(k) for k in self._VIEW_KEYS] + [t for k in self._LIST_KEYS for t in o.get(k) or []]
+        views = [o.get(k) for k in VIEW_FIELDS] + [t for k in LIST_FIELDS for t in o.get(k) or []]
         return [t.buf for t in views if t is not None and t.buf < L.BSY_EXT_BASE]
 
     def max_view_elems(self) -> int:
         """Largest (pixels x row stride) of ONE image over the workspace views the ops name as source, destination or residual: the
         kernels keep element offsets in 32 bits, so the engine splits a batch when B times this (of the one-image plan) reaches 2^31.
         A C2f concat buffer is larger than the first conv's output."""
-        views = [o.get(k) for o in self.ops for k in self._VIEW_KEYS]
+        views = [o.get(k) for o in self.ops for k in VIEW_FIELDS]
         return max([1] + [(t.H // 2) * (t.W // 2) * t.ld if t.up else t.H * t.W * t.ld for t in views if t is not None and t.buf < L.BSY_EXT_BASE])
 
     def buffer_lifetimes(self) -> List[Optional[Tuple[int, int]]]:
@@ -1514,40 +1520,31 @@ class Plan:
 
         arr = (L.Op * len(self.ops))()
         for o, d in zip(arr, self.ops):
-            o.kind = d["kind"]
-            o.B, o.H, o.W, o.OH, o.OW = self.B, d["H"], d["W"], d["OH"], d["OW"]
-            o.src0, o.src1 = v(d.get("src0")), v(d.get("src1"))
-            o.up0 = int(bool(d.get("src0") and d["src0"].up))
-            o.up1 = int(bool(d.get("src1") and d["src1"].up))
-            o.dst, o.res = v(d.get("dst")), v(d.get("res"))
-            o.ksize, o.stride, o.pad = d.get("ksize", 0), d.get("stride", 0), d.get("pad", 0)
-            o.act, o.out_f32 = d.get("act", 0), d.get("out_f32", 0)
-            o.dst_scale, o.dst_dy, o.dst_dx = d.get("dst_scale", 1), d.get("dst_dy", 0), d.get("dst_dx", 0)
-            if "wkey" in d:
-                o.w_off, o.b_off = offsets(d["wkey"])
-            if "wkey2" in d:
-                o.w2_off, o.b2_off = offsets(d["wkey2"])
-            o.mid_c = d.get("mid_c", 0)
-            for j, k in enumerate(d.get("wkeys", [])):
-                o.aux_off[2 * j], o.aux_off[2 * j + 1] = offsets(k)
             if d["kind"] == L.OP_ELA:  # the three sigmoids are known once the weights are packed (WRec.coef).  They stay in the plan's
                 # own op: a side effect of serialising that nothing reads today (the device gets them through `o` below)
                 cf = self.wrecs[d["wkey"]].coef
                 d["scale"], d["lvl_stride"] = cf[0], [cf[1], cf[2]]
-            o.heads, o.key_dim, o.head_dim, o.scale = d.get("heads", 0), d.get("key_dim", 0), d.get("head_dim", 0), \
-                d.get("scale", 0.0)
-            o.nl, o.nc, o.nm, o.A = d.get("nl", 0), d.get("nc", 0), d.get("nm", 0), d.get("A", 0)
-            o.ne = d.get("ne", 0)
-            o.nk, o.kdim = d.get("nk", 0), d.get("kdim", 0)
-            for j in range(L.BSY_MAX_LEVELS):
-                o.box[j] = v(d["box"][j] if j < len(d.get("box", [])) else None)
-                o.cls[j] = v(d["cls"][j] if j < len(d.get("cls", [])) else None)
-                o.msk[j] = v(d["msk"][j] if j < len(d.get("msk", [])) else None)
-                o.lvl_h[j] = d["lvl_h"][j] if j < len(d.get("lvl_h", [])) else 0
-                o.lvl_w[j] = d["lvl_w"][j] if j < len(d.get("lvl_w", [])) else 0
-                o.lvl_stride[j] = d["lvl_stride"][j] if j < len(d.get("lvl_stride", [])) else 0.0
-            o.in_dtype, o.out_dtype, o.level = d.get("in_dtype", 0), d.get("out_dtype", 0), d.get("level", 0)  # POOL_DOWN: level = mode
-            o.lane, o.join, o.tuned_cfg = d["lane"], d.get("join", 0), 0
+            o.kind, o.lane, o.tuned_cfg = d["kind"], d["lane"], 0
+            o.B, o.H, o.W, o.OH, o.OW = self.B, d["H"], d["W"], d["OH"], d["OW"]
             o.prec = (2 if self.split_f16 else 1) if self.f32_mode else 0
-            o.ksplit = d.get("ksplit", 0)
+            for f, default in SCALAR_FIELDS:  # (level: the mode of MAXPOOL / POOL_DOWN as well)
+                setattr(o, f, d.get(f, default))
+            for f in VIEW_FIELDS:
+                setattr(o, f, v(d.get(f)))
+            o.up0 = int(bool(d.get("src0") and d["src0"].up))
+            o.up1 = int(bool(d.get("src1") and d["src1"].up))
+            for f in LIST_FIELDS:
+                views, member = d.get(f, ()), getattr(o, f)
+                for j in range(L.BSY_MAX_LEVELS):
+                    member[j] = v(views[j] if j < len(views) else None)
+            for f, default in LEVEL_FIELDS:
+                values, member = d.get(f, ()), getattr(o, f)
+                for j in range(L.BSY_MAX_LEVELS):
+                    member[j] = values[j] if j < len(values) else default
+            if "wkey" in d:
+                o.w_off, o.b_off = offsets(d["wkey"])
+            if "wkey2" in d:
+                o.w2_off, o.b2_off = offsets(d["wkey2"])
+            for j, k in enumerate(d.get("wkeys", [])):
+                o.aux_off[2 * j], o.aux_off[2 * j + 1] = offsets(k)
         return arr

@@ -367,6 +367,75 @@ def test_plan_rejects_unsupported_graphs():
         Plan(cfg, 1, 64, 64)
 
 
+def _edited(family, size, edits=None, nc=80, task="detect", append=None, **top):
+    """A stock graph with the layers `edits` names ({index over backbone + head: layer}) replaced, `append` put behind the last one and
+    the top-level keys `top` set (None: removed)."""
+    cfg = stock_cfg(family, size, nc, task, kpt_shape=(17, 3) if task == "pose" else None)
+    nb = len(cfg["backbone"])
+    layers = list(cfg["backbone"]) + list(cfg["head"]) + ([append] if append else [])
+    for i, layer in (edits or {}).items():
+        layers[i] = layer
+    cfg["backbone"], cfg["head"] = layers[:nb], layers[nb:]
+    for k, v in top.items():
+        cfg.pop(k) if v is None else cfg.update({k: v})
+    return cfg
+
+
+_T11 = dict(scale="t", scales={"t": [0.5, 0.1875, 1024]})  # YOLO11 at a width multiple of 0.1875: layer 1 is 24 channels wide
+# (id, () -> graph, Plan keywords): one row per `raise NotImplementedError` of the graph walk
+PLAN_REFUSALS = [
+    ("zeropad-not-before-pool", lambda: _edited("yolov3-tiny", None, {12: [-1, 1, "Conv", [512, 3, 1]]}), {}),
+    ("zeropad-arguments", lambda: _edited("yolov3-tiny", None, {11: [-1, 1, "nn.ZeroPad2d", [[1, 1, 1, 1]]]}), {}),
+    ("zeropad-second-reader", lambda: _edited("yolov3-tiny", None, {14: [11, 1, "Conv", [256, 1, 1]]}), {}),
+    ("relu-module", lambda: _edited("yolov6", "n", {13: [-1, 1, "C2f", [256]]}), {}),
+    ("conv-image-repeated", lambda: _edited("yolov6", "n", {0: [-1, 6, "Conv", [64, 3, 2]]}), {}),
+    ("conv-chain-width", lambda: _edited("yolov6", "n", {2: [-1, 6, "Conv", [256, 3, 1]]}), {}),
+    ("conv-chain-padding", lambda: _edited("yolov6", "n", {2: [-1, 6, "Conv", [128, 3, 1, 0]]}), {}),
+    ("conv-image-ksp", lambda: _edited("yolo11", "n", {0: [-1, 1, "Conv", [64, 5, 2]]}), {}),
+    ("conv-padding", lambda: _edited("yolo11", "n", {1: [-1, 1, "Conv", [128, 3, 2, 0]]}), {}),
+    ("ghostconv-image", lambda: _edited("yolov8-ghost", "n", {0: [-1, 1, "GhostConv", [64, 3, 2]]}), {}),
+    ("ghostconv-groups", lambda: _edited("yolov8-ghost", "n", {1: [-1, 1, "GhostConv", [128, 3, 2, 2]]}), {}),
+    ("ghostconv-halves-12", lambda: _edited("yolov8-ghost", "n", {1: [-1, 1, "GhostConv", [96, 3, 2]]}), {}),
+    ("dwconv-widths", lambda: _edited("yolo11", "n", {1: [-1, 1, "DWConv", [128, 3, 2]]}), {}),
+    ("spp-k", lambda: _edited("yolov3-spp", None, {12: [-1, 1, "SPP", [512, [5, 9]]]}), {}),
+    ("spp-hidden-width", lambda: _edited("yolo11", "n", {2: [-1, 1, "SPP", [256, [5, 9, 13]]]}, **_T11), {}),
+    ("bottleneck-groups", lambda: _edited("yolov3", None, {2: [-1, 1, "Bottleneck", [64, True, 2]]}), {}),
+    ("bottleneck-chain-width", lambda: _edited("yolov3", None, {4: [-1, 2, "Bottleneck", [256]]}), {}),
+    ("sppelan-k", lambda: _edited("yolov9", "c", {9: [-1, 1, "SPPELAN", [512, 256, 3]]}), {}),
+    ("sppelan-hidden-width", lambda: _edited("yolov9", "c", {9: [-1, 1, "SPPELAN", [512, 100]]}), {}),
+    ("maxpool-arguments", lambda: _edited("yolov3-tiny", None, {1: [-1, 1, "nn.MaxPool2d", [3, 2, 1]]}), {}),
+    ("deconv-on-concat", lambda: _edited("yolov6", "n", {13: [-1, 1, "nn.ConvTranspose2d", [256, 2, 2, 0]]}), {}),
+    ("deconv-arguments", lambda: _edited("yolov6", "n", {11: [-1, 1, "nn.ConvTranspose2d", [256, 3, 2, 0]]}), {}),
+    ("obb-ne", lambda: _edited("yolo11", "n", {23: [[16, 19, 22], 1, "OBB", ["nc", 2]]}, task="obb"), {}),
+    ("pose-spelled-out", lambda: _edited("yolo11", "n", {23: [[16, 19, 22], 1, "Pose", ["nc", [17, 3]]]}, 1, "pose"), {}),
+    ("pose-no-kpt-shape", lambda: _edited("yolo11", "n", None, 1, "pose", kpt_shape=None), {}),
+    ("pose-kpt-shape-range", lambda: _edited("yolo11", "n", None, 1, "pose", kpt_shape=[17, 4]), {}),
+    ("v10detect-not-last", lambda: _edited("yolov10", "n", append=[-1, 1, "Conv", [64, 1, 1]]), {}),
+    ("classify-list", lambda: _edited("yolo11", "n", {10: [[-1, 8], 1, "Classify", ["nc"]]}, 1000, "classify"), {}),
+    ("classify-not-last", lambda: _edited("yolo11", "n", None, 1000, "classify", append=[-1, 1, "Conv", [64, 1, 1]]), {}),
+    ("classify-arguments", lambda: _edited("yolo11", "n", {10: [-1, 1, "Classify", ["nc", 3]]}, 1000, "classify"), {}),
+    ("unknown-module", lambda: _edited("yolo11", "n", {2: [-1, 2, "C3k2_LRSA", [256, False, 0.25]]}), {}),
+]
+
+
+@pytest.mark.parametrize("cid,graph,kw", PLAN_REFUSALS, ids=[r[0] for r in PLAN_REFUSALS])
+def test_graph_walk_refusals_are_the_recorded_ones(cid, graph, kw, snap):
+    """Every `raise NotImplementedError` of Plan._build, reached through a stock graph with one layer (or one top-level key) edited:
+    the exception's exact type and its whole message equal what tests/golden/plan_refusals.json recorded before the walk was
+    split into per-module lowerings (the plan snapshots see only graphs that build).  Two sites have no row, because no graph reaches them:
+      * "nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] (model.i is ...)", the gate at the top of the walk: the
+        ZeroPad2d layer itself has by then refused every graph whose next layer is not that pool reading it alone, and every graph in
+        which another layer names it in `f`, so the layer that receives its output is always the pool;
+      * "... lowers to op ... which has no ReLU", the post-check on RELU_KINDS: of RELU_MODULES only Detect can emit another kind
+        (DWCONV / DWPW of the light class branch), and it does so only where a C3k2 has cleared `legacy` -- C3k2 is not in
+        RELU_MODULES, so a ReLU graph is refused at that layer first."""
+    want = json.loads((GOLDEN / "plan_refusals.json").read_text())
+    assert sorted(want) == sorted(r[0] for r in PLAN_REFUSALS)
+    with pytest.raises(NotImplementedError) as e:
+        Plan(graph(), 1, 64, 64, **kw)
+    assert {"type": type(e.value).__name__, "message": str(e.value)} == want[cid]
+
+
 def test_segment_plan_matches_reference_work():
     """YOLOv8l-seg @640 (BASELINE config 4): 210.4 GFLOP/image, protos at (160, 160)."""
     p = Plan(stock_cfg("yolov8", "l", 80, "segment"), 1, 640, 640)
@@ -691,7 +760,7 @@ def test_plans_are_the_recorded_ones(snap):
     alone leaves these alone.  python tools/plan_snapshot.py --dump DIR at two commits shows what moved."""
     want = json.loads(snap.FIXTURE.read_text())
     cases = snap.cases()
-    assert sorted(want) == sorted(cid for cid, _, _ in cases) and len(cases) >= 117 + 16
+    assert sorted(want) == sorted(cid for cid, _, _ in cases) and len(cases) >= 117 + 16 + 135 + 3
     got = {cid: snap.snapshot(build, pack)[0] for cid, build, pack in cases}
     assert not {cid: (got[cid], want[cid]) for cid in want if got[cid] != want[cid]}
 

@@ -40,6 +40,25 @@ MATRIX = [("yolo11", "n", "detect"), ("yolo11", "s", "detect"), ("yolo11", "m", 
           ("bsyolo11", "s", "detect"), ("yolov5", "s", "detect"), ("yolov8-p2", "s", "detect"), ("yolov9", "t", "detect"),
           ("yolov9", "m", "detect"), ("yolov9", "c", "segment")]
 MATRIX = [g + ((2, 64, 96),) for g in MATRIX] + [("yolov8-p6", "s", "detect", (2, 128, 192)), ("yolov5-p6", "s", "detect", (2, 128, 192))]
+# The families behind YOLOv9 and the pose / classify plans: (case name, () -> graph, (B, H, W), Plan keywords in every option)
+_S, _L = (2, 64, 96), (2, 128, 192)
+MATRIX2 = [
+    ("yolo11-n-pose", lambda: stock_cfg("yolo11", "n", 1, "pose", kpt_shape=(17, 3)), _S, {}),
+    ("yolov8-p6-s-pose", lambda: stock_cfg("yolov8-p6", "s", 1, "pose", kpt_shape=(17, 3)), _L, {}),
+    ("yolo11-n-classify", lambda: stock_cfg("yolo11", "n", 1000, "classify"), _S, {}),
+    ("yolov8-s-classify", lambda: stock_cfg("yolov8", "s", 10, "classify"), _S, {}),
+    ("yolov10-n-detect", lambda: stock_cfg("yolov10", "n"), _S, {}),
+    ("yolov10-b-detect", lambda: stock_cfg("yolov10", "b"), _S, {}),
+    ("yolov10-s-one2many-k50", lambda: stock_cfg("yolov10", "s"), _S, dict(one2many=True, max_det=50)),
+    ("yolov8-ghost-s-detect", lambda: stock_cfg("yolov8-ghost", "s"), _S, {}),
+    ("yolov8-ghost-p2-n-detect", lambda: stock_cfg("yolov8-ghost-p2", "n"), _S, {}),  # its C3Ghost: ghostconv on padded pieces
+    ("yolov8-ghost-p6-s-detect", lambda: stock_cfg("yolov8-ghost-p6", "s"), _L, {}),
+    ("yolov3-detect", lambda: stock_cfg("yolov3", None), _S, {}),
+    ("yolov3-spp-detect", lambda: stock_cfg("yolov3-spp", None), _S, {}),
+    ("yolov3-tiny-detect", lambda: stock_cfg("yolov3-tiny", None), _S, {}),
+    ("yolov6-n-detect", lambda: stock_cfg("yolov6", "n"), _S, {}),
+    ("yolov6-m-sppf-relu", lambda: stock_cfg("yolov6", "m"), _S, dict(sppf_act="relu")),
+]
 
 
 def clear_env():
@@ -47,8 +66,8 @@ def clear_env():
         os.environ.pop(k, None)
 
 
-def _width(family, width):
-    return dict(stock_cfg(family, "n"), scale="t", scales={"t": [0.5, width, 1024]})
+def _width(family, width, scale="n"):
+    return dict(stock_cfg(family, scale), scale="t", scales={"t": [0.5, width, 1024]})
 
 
 def cases():
@@ -61,7 +80,13 @@ def cases():
                 out.append((f"{fam}-{scale}-{task}/{prec}/{oname}",
                             lambda fam=fam, scale=scale, task=task, shape=shape, prec=prec, kw=kw: Plan(stock_cfg(fam, scale, 80, task), *shape, precision=prec, **kw),
                             oname == "default" and prec == "fp16"))
-    s11 = lambda: stock_cfg("yolo11", "s")  # noqa: E731
+    for cname, graph, shape, fixed in MATRIX2:
+        for prec in ("fp16", "fp32", "fp32x"):
+            for oname, kw in OPTIONS.items():
+                out.append((f"{cname}/{prec}/{oname}",
+                            lambda graph=graph, shape=shape, prec=prec, kw=dict(fixed, **kw): Plan(graph(), *shape, precision=prec, **kw),
+                            oname == "default" and prec == "fp16"))
+    s11 =lambda: stock_cfg("yolo11", "s")  # noqa: E731
     out += [
         ("extra/yolov8-p6-s-segment", lambda: Plan(stock_cfg("yolov8-p6", "s", 80, "segment"), 2, 128, 192), True),
         ("extra/yolo11-x", lambda: Plan(stock_cfg("yolo11", "x"), 2, 64, 64), True),
@@ -79,6 +104,10 @@ def cases():
         ("width/bsyolo11-0.375", lambda: Plan(_width("bsyolo11", 0.375), 2, 96, 64), True),
         ("width/bsyolo11-0.1875-fp32", lambda: Plan(_width("bsyolo11", 0.1875), 2, 96, 64, precision="fp32"), True),
         ("width/yolo11-0.3125-fp32", lambda: Plan(_width("yolo11", 0.3125), 2, 96, 64, precision="fp32"), True),
+        # CIB on padded pieces, without and (the b graph) with lk
+        ("width/yolov10-n-0.1875", lambda: Plan(_width("yolov10", 0.1875), 2, 96, 64), True),
+        ("width/yolov10-n-0.375", lambda: Plan(_width("yolov10", 0.375), 2, 96, 64), True),
+        ("width/yolov10-b-0.375", lambda: Plan(_width("yolov10", 0.375, "b"), 2, 96, 64), True),
     ]
     return out
 
