@@ -326,6 +326,22 @@ int launch_maxpool(const void* src, int lds_, int soff, void* dst, int ldd, int 
                    hipStream_t s);
 int launch_s2d(const void* img, int img_dtype, int B, int H, int W, half_t* dst, int ldd, hipStream_t s);
 
+// maxsig.hip: MaxSigmoidAttnBlock's gate (block.py:3483-3515), dst = proj * scale[m] * sigmoid(max_n <embed, G[n]>_head m + bias[m]).  Views of
+// `dtype` (BSY_F16 / BSY_F32) over B * HW pixels; arguments as bsy_maxsig_attn's, checked in the launcher (the engine's op and the entry
+// point share the checks)
+struct MaxSigArgs {
+    const void* embed = nullptr;
+    const void* proj = nullptr;
+    void* dst = nullptr;
+    int lde = 0, ldp = 0, ldd = 0;
+    int B = 0, HW = 0, heads = 0, hc = 0, nc = 0;
+    const void* G = nullptr;          // [rows][heads * hc] of dtype; f16: rows = nc rounded up to 32, the padding rows copies of row 0
+    const float* bias_scale = nullptr;  // [bias (heads) | scale (heads)]
+    int dtype = 0;
+};
+inline bool maxsig_supported(int hc) { return hc >= 16 && hc <= 128 && hc % 16 == 0; }  // the fp16 kernel's head widths: 1 .. 8 k-steps of 16
+int launch_maxsig(const MaxSigArgs& a, hipStream_t s);
+
 struct AttnArgs {
     const half_t* qkv = nullptr;
     int ld = 0;

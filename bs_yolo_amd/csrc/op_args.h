@@ -102,6 +102,37 @@ inline bool build_maxpool(const char*& src, char*& dst, const bsy_op& op, Resolv
     }
     return R.ok;
 }
+// MAXSIG (both storage types): src0 = the embedding, src1 = the projection, dst = its gated copy (may be src1's view); heads x head_dim
+// channels each, nc guide rows at w_off, [bias | scale] at b_off.  What needs no pointer is checked here, so that bsy_plan_create can ask
+// with an unbound resolver (maxsig_record_ok); the launcher checks the rest
+inline bool maxsig_record_ok(const bsy_op& op) {
+    const int C = op.heads * op.head_dim;
+    if (op.src0.buf < 0 || op.src1.buf < 0 || op.dst.buf < 0) { bsy_set_error("maxsig: null pointer (src0, src1 and dst are all needed)"); return false; }
+    if (op.nc < 1) { bsy_set_error("maxsig: nc = %d (at least one guide row)", op.nc); return false; }
+    if (op.heads < 1 || op.head_dim < 1 || op.src0.C != C || op.src1.C != C || op.dst.C != C) {
+        bsy_set_error("maxsig: %d heads of %d channels on views of %d / %d / %d channels", op.heads, op.head_dim, op.src0.C, op.src1.C, op.dst.C);
+        return false;
+    }
+    if (!op.prec && !maxsig_supported(op.head_dim)) {
+        bsy_set_error("maxsig: heads of hc = %d channels are not on the fp16 path (16 to 128 in steps of 16)", op.head_dim);
+        return false;
+    }
+    if (op.src0.buf == op.dst.buf && op.src0.coff < op.dst.coff + C && op.dst.coff < op.src0.coff + C) {
+        bsy_set_error("maxsig: the destination overlaps the embedding view (src0)");
+        return false;
+    }
+    return true;
+}
+inline bool build_maxsig(MaxSigArgs& a, const bsy_op& op, Resolver& R, const char* wb) {
+    if (!maxsig_record_ok(op)) { R.ok = false; return false; }
+    a.dtype = op.prec ? BSY_F32 : BSY_F16;
+    if (op.prec) { a.embed = R.f(op.src0); a.proj = R.f(op.src1); a.dst = R.f(op.dst); }
+    else { a.embed = R.h(op.src0); a.proj = R.h(op.src1); a.dst = R.h(op.dst); }
+    a.lde = op.src0.ld; a.ldp = op.src1.ld; a.ldd = op.dst.ld;
+    a.B = op.B; a.HW = op.H * op.W; a.heads = op.heads; a.hc = op.head_dim; a.nc = op.nc;
+    a.G = wb + op.w_off; a.bias_scale = (const float*)(wb + op.b_off);
+    return R.ok;
+}
 // NHWC2NCHW: dst = the whole BCHW tensor, an optional output -- `skip`: its slot is unbound, nothing is resolved or launched
 template <typename T>
 inline bool build_nhwc2nchw(const T*& src, void*& out, bool& skip, const bsy_op& op, Resolver& R) {

@@ -209,6 +209,17 @@ extern "C" int bsy_maxpool2d(const void* x, int ldx, int xoff, void* y, int ldy,
     return launch_maxpool(x, ldx, xoff, y, ldy, yoff, B, H, W, C, mode, dtype, (hipStream_t)stream);
 }
 
+extern "C" int bsy_maxsig_attn(const void* embed, int lde, const void* proj, int ldp, void* out, int ldo, int B, int H, int W, int heads, int hc,
+                               const void* G, int nc, const float* bias_scale, int dtype, bsy_stream stream) {
+    if (H < 1 || W < 1 || (long long)H * W > 0x7fffffff) BSY_FAIL(BSY_ERR_ARG, "maxsig: bad map size %d x %d", H, W);
+    MaxSigArgs a;
+    a.embed = embed; a.lde = lde; a.proj = proj; a.ldp = ldp; a.dst = out; a.ldd = ldo; a.B = B; a.HW = H * W; a.heads = heads; a.hc = hc;
+    a.G = G; a.nc = nc; a.bias_scale = bias_scale; a.dtype = dtype;
+    return launch_maxsig(a, (hipStream_t)stream);
+}
+
+extern "C" int bsy_maxsig_supported(int hc) { return maxsig_supported(hc) ? 1 : 0; }
+
 extern "C" int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale,
                              void* out, int ldo, bsy_stream stream) {
     if (!qkv || !out) BSY_FAIL(BSY_ERR_ARG, "attention: null pointer");

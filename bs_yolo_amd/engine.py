@@ -19,6 +19,10 @@ An engine built from a YOLOv10 graph (a `v10Detect` head) returns what v10Detect
 the one2one head (BSY_OP_E2E_TOPK) -- and the raw maps of both head copies, BCHW in the input's dtype.  ``want_raw=False`` gives
 ``(rows, {"one2many": [None] * nl, "one2one": [None] * nl})`` from a plan of its own that never runs the one2many branches.  The
 pre-top-k tensor (B, 4 + nc, A) of the last ``want_raw=True`` forward is kept as ``engine.last_e2e_pre`` (as last_topk is).
+
+An engine built from a YOLO-World v2 graph (C2fAttn blocks, a `WorldDetect` head) returns what WorldDetect.forward returns in eval: ``(y,
+x_list)`` with y (B, 4 + nc, A) and raw maps of 64 + nc channels, nc the ROWS of the text features it was built with (``txt_feats=``, the
+model's ``txt_feats``, or the state dict's reserved key "txt_feats"); the text is constant per engine and folded into its weights.
 """
 from __future__ import annotations
 
@@ -35,7 +39,7 @@ from . import lib as L
 from . import ops as O
 from . import tta as T
 from .plan import SWITCHES, Plan
-from .weights import BN_EPS, adopt_offsets, pack_plan_weights, repconv_form
+from .weights import BN_EPS, TXT_KEY, adopt_offsets, pack_plan_weights, repconv_form
 
 _DTYPES = {"int32": torch.int32, "float32": torch.float32}  # Plan.outputs' dtypes besides "io", the forward's own
 
@@ -108,16 +112,26 @@ class YoloEngine:
     def __init__(self, cfg: dict, state_dict: Mapping[str, torch.Tensor], device: int = 0, bn_eps: float = BN_EPS,
                  autotune: Optional[bool] = None, max_plans: Optional[int] = None, precision: str = "fp16", graph: Optional[bool] = None,
                  graph_ring: int = 3, latency: Optional[bool] = None, repconv: Optional[str] = None, max_det: int = 300,
-                 sppf_act: Optional[str] = None, **switches: Optional[bool]):
+                 sppf_act: Optional[str] = None, txt_feats: Optional[torch.Tensor] = None, **switches: Optional[bool]):
         """switches: the fusion switches of plan.SWITCHES (fuse_stem=False, ...), handed to every plan; None or absent = the switch's
         environment variable, on where that is unset.  max_det: the rows a v10Detect head's top-k keeps (1 .. 4096; other heads ignore it).
         state_dict: a mapping, or the reference model itself (its state_dict() is taken).  sppf_act: Plan's parameter of that name, what
         SPPF's two convs apply in a graph under `activation: nn.ReLU()` (YOLOv6) -- "silu" in a model this fork built from the yaml, "relu"
         in an upstream-pickled one.  None reads it off the model (sppf_form below) where `state_dict` is one; a bare state dict does not
-        say which form it came from, so None then means "silu": pass "relu" for an upstream checkpoint's state dict."""
+        say which form it came from, so None then means "silu": pass "relu" for an upstream checkpoint's state dict.
+        txt_feats: a YOLO-World graph's text features, (nc, E) or (1, nc, E): this tensor, else the model's `txt_feats` attribute where
+        `state_dict` is a model, else the state dict's key "txt_feats".  Their row count is the number of classes the engine scores
+        (Plan's text_nc, `engine.nc`); cfg["nc"] keeps sizing the head's hidden width.  Other graphs ignore the argument."""
+        world = (list(cfg.get("head", [])) or [[0, 0, ""]])[-1][2] == "WorldDetect"
         if isinstance(state_dict, torch.nn.Module):
             sppf_act = sppf_act or sppf_form(state_dict, cfg)
+            if txt_feats is None and world:
+                txt_feats = getattr(state_dict, "txt_feats", None)
             state_dict = {k: v.detach().float().cpu() for k, v in state_dict.state_dict().items()}
+        self.text_nc, self.txt_feats = None, None  # (txt_feats: the text the weights in use were folded with, kept for load_weights)
+        if world:
+            state_dict = self._with_text(state_dict, txt_feats)
+            self.text_nc = int(state_dict[TXT_KEY].shape[-2])
         self.sppf_act = sppf_act or "silu"
         if not set(switches) <= set(SWITCHES):
             raise TypeError(f"YoloEngine() got an unexpected keyword argument {sorted(set(switches) - set(SWITCHES))[0]!r}")
@@ -198,6 +212,7 @@ class YoloEngine:
         self.weight_bytes = len(blob)
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         L.check(L.lib.bsy_engine_load_weights(self._h, buf, len(blob)))
+        self.txt_feats = state_dict[TXT_KEY] if world else None
         self.meta = dict(self._packed.meta)
         self.nc = self.meta["nc"]
         self.stride = torch.tensor(self.meta["strides"])
@@ -209,10 +224,31 @@ class YoloEngine:
         self.end2end = bool(self.meta.get("end2end"))  # a v10Detect head: forward returns (rows, {...}), see the module docstring
         self.last_e2e_pre: Optional[torch.Tensor] = None
 
-    def load_weights(self, state_dict: Mapping[str, torch.Tensor], bn_eps: float = BN_EPS) -> None:
+    @staticmethod
+    def _with_text(state_dict: Mapping[str, torch.Tensor], txt_feats) -> Mapping[str, torch.Tensor]:
+        """`state_dict` with the text features under the reserved key (weights.TXT_KEY): `txt_feats` where given, else what it holds."""
+        if txt_feats is not None:
+            state_dict = dict(state_dict)
+            state_dict[TXT_KEY] = torch.as_tensor(txt_feats).detach().float().cpu()
+        if TXT_KEY not in state_dict:
+            raise ValueError("a YOLO-World graph needs its text features: txt_feats=, the model's txt_feats, or state_dict['txt_feats']")
+        t = state_dict[TXT_KEY]
+        if t.dim() == 3 and t.shape[0] != 1:
+            raise NotImplementedError(f"txt_feats of shape {tuple(t.shape)}: per-image text features are not accelerated (one set per call)")
+        if t.dim() not in (2, 3):
+            raise ValueError(f"txt_feats of shape {tuple(t.shape)}: (nc, E) or (1, nc, E)")
+        return state_dict
+
+    def load_weights(self, state_dict: Mapping[str, torch.Tensor], bn_eps: float = BN_EPS, txt_feats: Optional[torch.Tensor] = None) -> None:
         """Replace the engine's weights in place (same graph, new values: an EMA update, a fine-tuned checkpoint).  Plans, tuning and
         the arena are kept; the library synchronises the device before it frees the old blob and drops every captured graph (they
-        hold addresses inside it: include/bsyolo.h, bsy_engine_load_weights)."""
+        hold addresses inside it: include/bsyolo.h, bsy_engine_load_weights).  txt_feats (a YOLO-World engine): new text features of the
+        SAME row count -- the guide and class records are folded again; another row count is another plan and raises ValueError.  Without
+        it, and without the reserved key in `state_dict` (a model's state_dict() never holds it), the text in use is folded into the new weights."""
+        if self.text_nc is not None:
+            if txt_feats is None and TXT_KEY not in state_dict:
+                txt_feats = self.txt_feats
+            state_dict = self._with_text(state_dict, txt_feats)
         with self._lock:
             blob = pack_plan_weights(self._packed, state_dict, bn_eps)
             if len(blob) != self.weight_bytes:
@@ -221,10 +257,12 @@ class YoloEngine:
                 adopt_offsets(plan, self._packed)
             buf = (C.c_char * len(blob)).from_buffer_copy(blob)
             L.check(L.lib.bsy_engine_load_weights(self._h, buf, len(blob)))
+            if self.text_nc is not None:
+                self.txt_feats = state_dict[TXT_KEY]
 
     def _fuse_kw(self):
         return dict(self.switches, precision=self.precision, lanes=True if self.graph else None, latency=self.latency, repconv=self.repconv,
-                    max_det=self.max_det, sppf_act=self.sppf_act)
+                    max_det=self.max_det, sppf_act=self.sppf_act, **({} if self.text_nc is None else {"text_nc": self.text_nc}))
 
     # -- plans --------------------------------------------------------------------------------------------------
     def plan_for(self, B: int, H: int, W: int, in_dtype: torch.dtype, out_dtype: torch.dtype, one2many: bool = False):

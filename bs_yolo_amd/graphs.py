@@ -12,7 +12,8 @@ yolov8-ghost-p2.yaml and yolov8-ghost-p6.yaml (families "yolov8-ghost", "yolov8-
 C3Ghost blocks on the YOLOv8 layouts, detect only), and the YOLOv10 graphs cfg/models/v10/yolov10{n,s,m,b,l,x}.yaml (family
 "yolov10": one layout, a literal table per size of where C2fCIB stands and whether it holds the 7x7 RepVGGDW; a v10Detect head), and the
 YOLOv3 graphs cfg/models/v3/yolov3.yaml, yolov3-spp.yaml and yolov3-tiny.yaml (families "yolov3", "yolov3-spp", "yolov3-tiny": one size
-each, `depth_multiple` / `width_multiple` of 1.0 instead of a scales table; detect only).  They are
+each, `depth_multiple` / `width_multiple` of 1.0 instead of a scales table; detect only), and the open-vocabulary graph
+cfg/models/v8/yolov8-worldv2.yaml (family "yolov8-worldv2": C2fAttn neck blocks, a WorldDetect head; detect only).  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -58,6 +59,21 @@ _YOLOV8 = {
         _UP, _cat(4), [-1, 3, "C2f", [256]],
         [-1, 1, "Conv", [256, 3, 2]], _cat(12), [-1, 3, "C2f", [512]],
         [-1, 1, "Conv", [512, 3, 2]], _cat(9), [-1, 3, "C2f", [1024]],
+    ],
+    "detect_from": [15, 18, 21],
+}
+
+# YOLO-World v2, cfg/models/v8/yolov8-worldv2.yaml:15-46: the YOLOv8 backbone and PAN neck with C2fAttn [c2, ec, nh] (a C2f without shortcuts
+# plus a max-sigmoid attention chunk guided by the text features) for the four neck blocks, and the head WorldDetect [nc, embed, with_bn].
+# Layer 16 names its input (15), which is the layer before it.  Detect only; v1 (yolov8-world.yaml, ImagePoolingAttn) is not restated
+_YOLOV8_WORLDV2 = {
+    "scales": _YOLOV8["scales"],
+    "backbone": _YOLOV8["backbone"],
+    "head": [
+        _UP, _cat(6), [-1, 3, "C2fAttn", [512, 256, 8]],
+        _UP, _cat(4), [-1, 3, "C2fAttn", [256, 128, 4]],
+        [15, 1, "Conv", [256, 3, 2]], _cat(12), [-1, 3, "C2fAttn", [512, 256, 8]],
+        [-1, 1, "Conv", [512, 3, 2]], _cat(9), [-1, 3, "C2fAttn", [1024, 512, 16]],
     ],
     "detect_from": [15, 18, 21],
 }
@@ -393,7 +409,8 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
     given: the four-argument call stock_cfg(family, scale, nc, "pose") raises ValueError for every family, as it always has);
     stock_cfg("yolov10", "s") == 'yolov10s.yaml' (scales n, s, m, b, l, x; detect only);
     stock_cfg("yolov3-tiny", None) == 'yolov3-tiny.yaml' (families "yolov3", "yolov3-spp", "yolov3-tiny": one size each, so `scale` must be
-    None or ""; detect only; the dict carries depth_multiple = width_multiple = 1.0 and no `scales`)."""
+    None or ""; detect only; the dict carries depth_multiple = width_multiple = 1.0 and no `scales`);
+    stock_cfg("yolov8-worldv2", "s") == 'yolov8s-worldv2.yaml' (scales n, s, m, l, x; detect only)."""
     if family in _V3_FAMILIES:
         if scale not in (None, "") or task != "detect":
             raise ValueError(f"{family}: scale {scale!r} / task {task!r} (one size, scale None; detect only)")
@@ -427,6 +444,12 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
         fam = copy.deepcopy(_YOLOV6)
         return {"nc": nc, "activation": "nn.ReLU()", "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"],
                 "head": fam["head"] + [[fam["detect_from"], 1, "Detect", ["nc"]]]}
+    if family == "yolov8-worldv2":  # detect only, under WorldDetect [nc, 512, True] (the BatchNorm contrastive head)
+        if scale not in _YOLOV8_WORLDV2["scales"] or task != "detect":
+            raise ValueError(f"yolov8-worldv2: scale {scale!r} / task {task!r} (detect: n, s, m, l, x)")
+        fam = copy.deepcopy(_YOLOV8_WORLDV2)
+        return {"nc": nc, "scale": scale, "scales": fam["scales"], "backbone": fam["backbone"],
+                "head": fam["head"] + [[fam["detect_from"], 1, "WorldDetect", ["nc", 512, True]]]}
     fam = copy.deepcopy(_FAMILIES[family])
     head = list(fam["head"])
     if task == "detect":

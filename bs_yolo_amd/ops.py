@@ -418,3 +418,32 @@ def classify_tail(logits: torch.Tensor, nc: int, k: int = 0, out_dtype: torch.dt
     L.check(L.lib.bsy_classify_tail(_p(logits), ld, B, int(nc), _p(y), _p(x), L.dtype_code(out_dtype), int(k),
                                     _p(idx) if k else None, _p(val) if k else None, _stream(logits)))
     return y, x, idx, val
+
+
+def maxsig_attn(embed: torch.Tensor, proj: torch.Tensor, G: torch.Tensor, bias: torch.Tensor, scale, nh: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxSigmoidAttnBlock's gate (nn/modules/block.py:3483-3515) in one launch (bsy_maxsig_attn): embed, proj (B,H,W,C) NHWC fp16 or fp32
+    on the device (or channel slices of wider tensors), C = nh * hc; G (nc, C) the guide rows with the block's 1 / sqrt(hc) folded in,
+    bias (nh), scale (nh) or a float.  For pixel p and head m: out[p, m hc + j] = proj[p, m hc + j] * scale[m] * sigmoid(max_n
+    <embed[p, head m], G[n, head m]> + bias[m]).  out: proj itself (in place) or another tensor of its shape; None = a new one.  It must
+    not overlap embed.  fp16: hc a multiple of 16 from 16 to 128 (the guide is rounded to f16, its rows padded by weights.guide)."""
+    from .weights import guide
+    if not embed.is_cuda:
+        raise RuntimeError("bs_yolo_amd.ops.maxsig_attn needs GPU tensors (no CPU fallback)")
+    pe, lde, B, H, W, Cc = _nhwc(embed)
+    pp, ldp, *shape_p = _nhwc(proj)
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=embed.dtype, device=embed.device)
+    po, ldo, *shape_o = _nhwc(out)
+    assert tuple(shape_p) == tuple(shape_o) == (B, H, W, Cc) and proj.dtype == out.dtype == embed.dtype and Cc % int(nh) == 0
+    G = torch.as_tensor(G).detach().cpu()
+    nc = G.shape[0] if G.dim() == 2 else 0
+    assert G.dim() == 2 and G.shape[1] == Cc
+    f32 = embed.dtype == torch.float32
+    gp = guide(G.double(), f32).to(embed.device) if nc else torch.zeros(32, Cc, dtype=embed.dtype, device=embed.device)
+    sc = torch.as_tensor(scale, dtype=torch.float32).reshape(-1).cpu()
+    bs = torch.cat([torch.as_tensor(bias, dtype=torch.float32).reshape(-1).cpu(), sc.expand(int(nh)) if sc.numel() == 1 else sc]).to(embed.device)
+    assert bs.numel() == 2 * int(nh)
+    L.check(L.lib.bsy_maxsig_attn(pe, lde, pp, ldp, po, ldo, B, H, W, int(nh), Cc // int(nh), _p(gp), int(nc), _p(bs), L.dtype_code(embed.dtype),
+                                  _stream(embed)))
+    return out

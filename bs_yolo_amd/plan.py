@@ -94,6 +94,9 @@ class WRec:
     cols: Optional[List[int]] = None   # op input channel j is the module's input channel cols[j] (-1: zero weights) -- PMSFA on padded pieces
     w_off: int = -1
     b_off: int = -1
+    # maxsig / world_cls: the width E of the text features the record folds in (state-dict key "txt_feats").  A plain attribute set by
+    # Plan._wrec, not a dataclass field: a record's field tuple is part of the plan snapshots (tools/plan_snapshot.py)
+    embed = 0
 
 
 def qkv_perm(nh: int, kd: int, hd: int) -> List[int]:
@@ -197,8 +200,11 @@ class Plan:
 
     def __init__(self, cfg: dict, B: int, H: int, W: int, in_dtype: int = L.BSY_F16, out_dtype: int = L.BSY_F16, precision: str = "fp16",
                  lanes: Optional[bool] = None, latency: bool = False, repconv: str = "refconv", max_det: int = 300, one2many: bool = False,
-                 sppf_act: str = "silu", **switches: Optional[bool]):
+                 sppf_act: str = "silu", text_nc: Optional[int] = None, **switches: Optional[bool]):
         """switches: the keys of SWITCHES; None (or absent) = what the switch's environment variable says, on where it is unset.
+        text_nc: read by a YOLO-World graph (a WorldDetect head) alone -- the number of classes SCORED, the rows of the text features; None
+        = cfg["nc"].  It sizes the guide records of the C2fAttn blocks, the folded class convs, meta["nc"] and the A x (4 + nc) prediction;
+        cfg["nc"] keeps sizing the head's hidden width c3 as the constructor did (head.py:313), whatever set_classes chose later.
         max_det, one2many: read by a v10Detect head alone -- the rows its top-k keeps, and whether the one2many branches (cv2 / cv3, raw
         maps only, which a caller who wants the rows alone must not pay for) are part of the plan."""
         if not set(switches) <= set(SWITCHES):
@@ -227,6 +233,9 @@ class Plan:
         if not 1 <= int(max_det) <= 4096:
             raise ValueError(f"max_det must be 1 .. 4096 (the top-k sorts its winners in LDS), not {max_det!r}")
         self.max_det, self.one2many = int(max_det), bool(one2many)
+        if text_nc is not None and (int(text_nc) != text_nc or text_nc < 1):
+            raise ValueError(f"text_nc must be a positive row count, not {text_nc!r}")
+        self.text_nc = None if text_nc is None else int(text_nc)
         self._e2e = ""  # which head copy of a v10Detect is being emitted: "" (not an end2end head), "o2o", "o2m"
         # latency mode (round 4; fp16 path): long-K conv layers with few tiles per image run split-K (split_factors below)
         self.latency = bool(latency) and precision == "fp16"
@@ -339,7 +348,10 @@ class Plan:
     # ---- op emitters -----------------------------------------------------------------------------------------
     def _wrec(self, key: str, **kw) -> str:
         if key not in self.wrecs:
+            embed = kw.pop("embed", 0)
             self.wrecs[key] = WRec(**kw)
+            if embed:
+                self.wrecs[key].embed = embed
         return key
 
     def _emit(self, kind: int, name: str, flops: int = 0, /, **o) -> dict:
@@ -698,6 +710,36 @@ class Plan:
             cur = out
         return self.conv(name + ".cv2", [cur, ab.slice(c, c)], c2, 1, 1)
 
+    def c2f_attn(self, name: str, x, c2: int, n: int, ec: int, nh: int) -> T:
+        """block.py:3518-3535 C2fAttn(c1, c2, n, ec, nh): cv2(cat(y0, y1, m(y1) ..., attn(y[-1], guide))), [y0 | y1] = cv1(x), m = n x
+        Bottleneck(c, c, shortcut False, k=(3,3), e=1), attn = MaxSigmoidAttnBlock(c, c, gc=512, ec, nh) (:3483-3515): proj_conv (3x3, BN, no
+        activation) of the last chunk, every head's channels multiplied by scale * sigmoid(max over the classes of <embedding, guide row> /
+        sqrt(hc) + bias).  One concat buffer of 3 + n chunks as c2f's; proj_conv writes the last chunk and ONE MAXSIG op gates it in place,
+        its embedding the chunk before.  The guide -- gl (nn.Linear(512, ec)) applied to the text features, constant per call -- is folded
+        on the host (weights.py kind "maxsig").  An `attn.ec` conv would exist where ec != c, and the module's own views then do not fit
+        (embed.view(bs, nh, hc, h, w) needs ec = nh * hc = c): no stock scale has one, and it is refused."""
+        xs = [x] if isinstance(x, T) else list(x)
+        c = int(c2 * 0.5)
+        if nh < 1 or c % nh:
+            raise NotImplementedError(f"{name}: C2fAttn with {nh} heads on {c} channels (the heads must divide the hidden width)")
+        hc = c // nh
+        if ec != c:
+            raise NotImplementedError(f"{name}: C2fAttn with ec = {ec} != c = {c} (attn.ec, a 1x1 conv to a width the module's own views do not fit) is not accelerated")
+        if not self.f32_mode and not kernel_takes("maxsig", hc):
+            raise NotImplementedError(f"{name}: C2fAttn heads of hc = {hc} channels are not on the fp16 path (16 to 128 in steps of 16)")
+        H, W = xs[0].H, xs[0].W
+        cat, cs = self.pieces([c] * (3 + n), H, W)
+        assert cs == c and cat.cmap is None  # (fp16: c = nh * hc is a multiple of 16)
+        self.conv(name + ".cv1", xs, 2 * c, 1, 1, dst=cat.slice(0, 2 * c))
+        for i in range(n):
+            self.bottleneck(f"{name}.m.{i}", cat.slice((1 + i) * c, c), cat.slice((2 + i) * c, c), False, (3, 3), 1.0)
+        emb, gated = cat.slice((1 + n) * c, c), cat.slice((2 + n) * c, c)
+        self.conv(name + ".attn.proj_conv", emb, c, 3, 1, act=False, dst=gated)
+        tnc = self.text_nc or self.cfg["nc"]
+        key = self._wrec(name + ".attn", name=name + ".attn", kind="maxsig", cout=tnc, cin=c, k=nh, embed=512)  # (gc = 512: C2fAttn's default)
+        self._emit(L.OP_MAXSIG, name + ".attn", 2 * self.B * H * W * c * tnc, src0=emb, src1=gated, dst=gated, heads=nh, head_dim=hc, nc=tnc, wkey=key)
+        return self.conv(name + ".cv2", cat, c2, 1, 1)
+
     def pmsfa(self, name: str, x: T, dst: T):
         """block.py:3035-3054.  conv1 -> P = [p1 | p2]; depthwise 5x5 on p1 -> Q = [q1 | q2]; the depthwise 7x7 runs on ALL
         of Q with weights extended by an identity kernel for the q2 half (weights.py kind "dwg_ext": exact pass-through,
@@ -959,9 +1001,11 @@ class Plan:
                    stride=1, pad=k // 2, out_f32=mode, dst_scale=1, cout=cout, nl=cout, nc=nc, nm=0, A=A, box=[self._raw(level, nc, src)], cls=[], msk=[], level=level,
                    lvl_h=[src.H, a0], lvl_w=[src.W], lvl_stride=[stride], out_dtype=self.out_dtype, mfma_flops=flops, **fields)
 
-    def _head_conv(self, name: str, src: T, cout: int, mode: int, level: int, a0: int, A: int, nc: int, stride: float, real_cin: int = 0):
-        """Last 1x1 conv of a Detect branch with the decoder fused into its epilogue (out_f32 = mode 2 / 3)."""
-        key = self._wrec(name, name=name, kind="plain", cout=cout, cin=src.C, k=1, perm=None, real_cin=real_cin)
+    def _head_conv(self, name: str, src: T, cout: int, mode: int, level: int, a0: int, A: int, nc: int, stride: float, real_cin: int = 0,
+                   wrec: Optional[dict] = None):
+        """Last 1x1 conv of a Detect branch with the decoder fused into its epilogue (out_f32 = mode 2 / 3).  wrec: fields of the weight
+        record that differ from a plain conv's (WorldDetect's folded class conv: kind, post, embed)."""
+        key = self._wrec(name, **dict(dict(name=name, kind="plain", cout=cout, cin=src.C, k=1, perm=None, real_cin=real_cin), **(wrec or {})))
         self._decoding_conv(name, src, 1, cout=cout, mode=mode, level=level, a0=a0, A=A, nc=nc, stride=stride,
                             flops=2 * self.B * src.H * src.W * cout * src.C, act=0, wkey=key)
 
@@ -976,12 +1020,16 @@ class Plan:
                             flops=2 * self.B * src.H * src.W * 64 * (9 * src.C + 64), act=self.act_id, wkey=k1, wkey2=k2, mid_c=64)
 
     def detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int = 0, npr: int = 0, ne: int = 0, nk: int = 0, kdim: int = 0,
-               end2end: bool = False):
+               end2end: bool = False, world: Optional[Tuple[int, int]] = None):
         """head.py:21-148 (+ Segment :175-197, OBB :200-227 with ne angle channels, Pose :230-279 with nk = nkpt * kdim keypoint
         channels).  end2end: v10Detect (:592-625, forward_end2end :76-98) -- the one2one copy of the branches (one2one_cv2 / one2one_cv3)
         decodes corner boxes into the pre-top-k tensor `pre` and writes the one2one raw maps `o2o{l}`, BSY_OP_E2E_TOPK turns `pre` into the
         rows (B, min(max_det, A), 6); the one2many copy (cv2 / cv3: raw maps `o2m{l}` only, nothing decoded) is emitted in a plan built
-        with one2many=True alone, always through f32 logit maps and the raw-map transposes (the fused epilogues write a prediction tensor)."""
+        with one2many=True alone, always through f32 logit maps and the raw-map transposes (the fused epilogues write a prediction tensor).
+        world = (embed, the yaml's nc): WorldDetect with the BatchNorm contrastive head (head.py:307-320, block.py:3609-3631) -- `nc` is then the
+        number of text rows scored, the hidden width c3 comes from the yaml's nc as the constructor computed it (head.py:313), and the last
+        class conv of every level is cv4.l folded into cv3.l.2 (weights.py kind "world_cls"): BatchNorm, the dot products with the unit text
+        rows, exp(logit_scale) and the bias are all linear in the embedding, itself a biased 1x1 conv.  The legacy Detect lowering otherwise."""
         if end2end:
             assert not (nm or ne or nk or legacy)
             start = len(self.ops)
@@ -1004,9 +1052,10 @@ class Plan:
             self._e2e = ""
             self.meta.update(end2end=True, max_det=self.max_det, K=K, one2many=self.one2many)
             return
-        self._detect(name, xs, nc, legacy, nm, ne, nk, kdim, "")
+        self._detect(name, xs, nc, legacy, nm, ne, nk, kdim, "", world)
 
-    def _detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int, ne: int, nk: int, kdim: int, pfx: str):
+    def _detect(self, name: str, xs: List[T], nc: int, legacy: bool, nm: int, ne: int, nk: int, kdim: int, pfx: str,
+                world: Optional[Tuple[int, int]] = None):
         """One copy of the head's branches: `pfx` in front of cv2 / cv3 ("one2one_" for v10Detect's one2one copy)."""
         cv2, cv3 = f"{name}.{pfx}cv2", f"{name}.{pfx}cv3"
         o2m = self._e2e == "o2m"
@@ -1016,7 +1065,7 @@ class Plan:
         if ne and len(xs) > 3:
             raise NotImplementedError(f"{name}: an OBB head on {len(xs)} levels (the reference ships none) is not accelerated")
         ch = [t.C for t in xs]
-        c2, c3 = max(16, ch[0] // 4, 64), max(ch[0], min(nc, 100))
+        c2, c3 = max(16, ch[0] // 4, 64), max(ch[0], min(world[1] if world else nc, 100))
         boxes, clss, msks = [], [], []
         A = sum(t.H * t.W for t in xs)
         a0 = [sum(t.H * t.W for t in xs[:i]) for i in range(len(xs))]
@@ -1053,9 +1102,13 @@ class Plan:
                 t = self.dwpw(f"{cv3}.{i}.0", x, c3p, real=(r3, 0))
                 t = self.dwpw(f"{cv3}.{i}.1", t, c3p, real=(r3, r3))
             if fused:
-                self._head_conv(f"{cv3}.{i}.2", t, nc, 2, i, a0[i], A, nc, strides[i], real_cin=r3)
+                self._head_conv(f"{cv3}.{i}.2", t, nc, 2, i, a0[i], A, nc, strides[i], real_cin=r3,
+                                wrec=dict(kind="world_cls", post=f"{name}.cv4.{i}", embed=world[0]) if world else None)
             else:
-                clss.append(self.conv(f"{cv3}.{i}.2", t, nc, 1, 1, act=False, plain=True, out_f32=True, real=(0, r3)))
+                clss.append(self.conv(f"{cv3}.{i}.2", t, nc, 1, 1, act=False, plain=True, out_f32=True, real=(0, r3), wkind="world_cls" if world else None))
+                if world:
+                    r = self.wrecs[f"{cv3}.{i}.2"]
+                    r.post, r.embed = f"{name}.cv4.{i}", world[0]
             if nm or ne:
                 # Segment.cv4 (head.py:175-197) / OBB.cv4 (:208-209): Conv(x, c4, 3) -> Conv(c4, c4, 3) -> Conv2d(c4, nm or ne, 1), on lanes
                 # of their own.  OBB's angle logits land in an f32 map 8 channels wide (zero weights and bias past `ne`): the conv kernels
@@ -1121,6 +1174,10 @@ class Plan:
     RELU_MODULES = ("Conv", "SPPF", "nn.ConvTranspose2d", "nn.Upsample", "nn.MaxPool2d", "nn.ZeroPad2d", "Concat", "Detect")
     RELU_KINDS = (L.OP_CONV_FIRST, L.OP_FIRST_POOL, L.OP_STEM, L.OP_CONV, L.OP_COPY, L.OP_S2D, L.OP_SPPF_POOL, L.OP_MAXPOOL, L.OP_DECODE, L.OP_RAW_NCHW)
 
+    # Modules that are refused with a reason of their own (everything else outside LOWERINGS: "not on the accelerated path")
+    REFUSED = {"ImagePoolingAttn": "YOLO-World v1 (yolov8-world.yaml) updates the text features per image from the feature maps; v2 "
+                                   "(yolov8-worldv2.yaml), whose text features are constant per call, is the accelerated graph"}
+
     def _build(self):
         """The bookkeeping every layer shares; what a module lowers to is its entry of LOWERINGS below."""
         d = self.cfg
@@ -1130,6 +1187,8 @@ class Plan:
                 self.scale = next(iter(d["scales"]))
             depth, self.width, self.max_ch = d["scales"][self.scale]
         nc, relu = d["nc"], self.act_id == L.ACT_RELU
+        if self.text_nc is not None and (list(d["head"]) or [[0, 0, ""]])[-1][2] != "WorldDetect":
+            raise ValueError("text_nc is read by a graph under a WorldDetect head alone")
         self.legacy = True  # Detect's class branch is the heavy one (head.py:44-56) until a C3k2 says otherwise (tasks.py:1048)
         self.layers = layers = list(d["backbone"]) + list(d["head"])
         outs: List = []   # per layer: T, or list[T] for a lazy Concat
@@ -1148,6 +1207,8 @@ class Plan:
                 raise NotImplementedError(f"{name}: {m} under activation nn.ReLU() is not accelerated (ReLU graphs: {', '.join(self.RELU_MODULES)})")
             lower, scaled = lowerings.get(m, (None, False))
             if lower is None:
+                if m in self.REFUSED:
+                    raise NotImplementedError(f"{name}: {m} is not accelerated: {self.REFUSED[m]}")
                 raise NotImplementedError(f"module {m} is not on the accelerated path")
             first_op = len(self.ops)
             ly.i, ly.name, ly.m, ly.x, ly.args, ly.n, ly.last = i, name, m, x, args, max(round(n * depth), 1) if n > 1 else n, i == last
@@ -1224,6 +1285,20 @@ class Plan:
     def _m_c2f(self, ly: _Layer):  # C2f [c2, shortcut]; C2fCIB (block.py:4215-4232) [c2, shortcut, lk]; repeat count inserted (tasks.py:1037-1043)
         cib = ly.m == "C2fCIB"
         return self.c2f(ly.name, ly.x, ly.c2, ly.n, bool(ly.arg(1, False)), 0.5, "cib" if cib else "c2f", lk=cib and bool(ly.arg(2, False)))
+
+    def _m_c2fattn(self, ly: _Layer):
+        """C2fAttn [c2, ec, nh] (block.py:3518-3535); parse_model scales ec and nh (tasks.py:1017-1021) and inserts the repeat count.  Its
+        guide is the text the head scores, so it stands in a graph under WorldDetect alone."""
+        if self.layers[-1][2] != "WorldDetect":
+            raise NotImplementedError(f"{ly.name}: C2fAttn in a graph whose head is {self.layers[-1][2]}, not WorldDetect (the text features "
+                                      "that guide it come with that head) is not accelerated")
+        inf = float("inf")
+        half = inf if self.max_ch == inf else self.max_ch // 2
+        ec = make_divisible(min(ly.args[1], half) * self.width, 8)
+        nh = ly.arg(2, 1)
+        if nh > 1:
+            nh = int(max(round(min(nh, inf if half == inf else half // 32)) * self.width, 1))
+        return self.c2f_attn(ly.name, ly.x, ly.c2, ly.n, ec, nh)
 
     def _m_c2(self, ly: _Layer):  # the necks of yolov8-p6.yaml / yolov8-seg-p6.yaml
         return self.c2(ly.name, ly.x, ly.c2, ly.n, bool(ly.arg(1, True)))
@@ -1355,6 +1430,15 @@ class Plan:
                 raise NotImplementedError(f"{name}: Pose with kpt_shape ({nkpt}, {ndim}): 1 to 64 keypoints of 2 or 3 channels are accelerated")
             self.detect(name, xs, args[0], self.legacy, nk=nkpt * ndim, kdim=ndim)
             self.meta.update(task="pose", nk=nkpt * ndim, kpt_shape=(nkpt, ndim))  # (only a pose plan's meta has these keys)
+        elif m == "WorldDetect":
+            # head.py:307-320, args [nc, embed, with_bn].  `nc` sizes c3 (head.py:313); the rows scored are the text features' (text_nc)
+            if not ly.last:
+                raise NotImplementedError(f"{name}: WorldDetect is accelerated as the last layer only")
+            if not bool(arg(2, False)):
+                raise NotImplementedError(f"{name}: WorldDetect with with_bn = False (ContrastiveHead, block.py:3591-3606: its per-pixel L2 "
+                                          "normalisation of the embedding is not linear, so the head does not fold into a conv) is not accelerated")
+            self.detect(name, xs, self.text_nc or args[0], True, world=(int(arg(1, 512)), args[0]))
+            self.meta.update(world=True)
         elif m == "v10Detect":  # head.py:592-625: Detect with end2end = True and the light class branch whatever the graph holds
             if not ly.last:
                 raise NotImplementedError(f"{name}: v10Detect is accelerated as the last layer only")
@@ -1378,12 +1462,13 @@ class Plan:
     LOWERINGS = {
         "Conv": (_m_conv, True), "DWConv": (_m_dwconv, True), "GhostConv": (_m_ghostconv, True), "GhostBottleneck": (_m_ghost_bottleneck, True),
         "C3": (_m_c3, True), "C3Ghost": (_m_c3, True), "C3k2": (_m_c3k2, True), "C3k2_gai": (_m_c3k2, True), "C2f": (_m_c2f, True),
-        "C2fCIB": (_m_c2f, True), "C2": (_m_c2, True), "SCDown": (_m_scdown, True), "C2PSA": (_m_c2psa, True), "PSA": (_m_c2psa, True),
+        "C2fCIB": (_m_c2f, True), "C2fAttn": (_m_c2fattn, True), "C2": (_m_c2, True), "SCDown": (_m_scdown, True), "C2PSA": (_m_c2psa, True), "PSA": (_m_c2psa, True),
         "SPPF": (_m_spp, True), "SPP": (_m_spp, True), "SPPELAN": (_m_spp, True), "Bottleneck": (_m_bottleneck, True),
         "RepNCSPELAN4": (_m_elan, True), "ELAN1": (_m_elan, True), "AConv": (_m_down, True), "ADown": (_m_down, True),
         "MSCAAttention": (_m_attention, False), "ELA": (_m_attention, False), "nn.Upsample": (_m_upsample, False), "Concat": (_m_concat, False),
         "nn.ZeroPad2d": (_m_zeropad, False), "nn.MaxPool2d": (_m_maxpool, False), "nn.ConvTranspose2d": (_m_deconv, False),  # (scales c2 itself)
         "Detect": (_m_head, False), "Segment": (_m_head, False), "OBB": (_m_head, False), "Pose": (_m_head, False), "v10Detect": (_m_head, False),
+        "WorldDetect": (_m_head, False),
         "Classify": (_m_classify, False),
     }
 

@@ -11,6 +11,8 @@ Three hooks, each using an extension point the reference already has (see INTEGR
                            (tasks.py:439-490, a ``Classify`` head) returns ``(y, x)`` as Classify.forward does in eval (head.py:304).
                            A ``PoseModel`` (a ``Pose`` head) returns ``(y, (x_list, kpt))`` as Pose.forward does (head.py:250); with
                            the head's ``export`` flag set it keeps its own forward (kpts_decode's export branch, head.py:255-272).
+                           A ``WorldModel`` of yolov8-worldv2.yaml (tasks.py:606-677; C2fAttn blocks, a ``WorldDetect`` head) runs with
+                           ``model.txt_feats`` folded into the engine's weights; a call that passes ``txt_feats=`` keeps its own forward.
                            Anything else the engine does not cover
                            (training mode, visualize / embed / profile (tasks.py:137-164), augment on other model classes, CPU
                            tensors, unsupported modules) goes to the original forward.
@@ -51,7 +53,7 @@ from .engine import YoloEngine, sppf_form
 from .plan import Plan, qkv_perm
 from .weights import BN_EPS, repconv_form
 
-SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify", "Pose", "v10Detect")
+SUPPORTED_HEADS = ("Detect", "Segment", "OBB", "Classify", "Pose", "v10Detect", "WorldDetect")
 
 
 def _on_device(t) -> bool:
@@ -208,7 +210,13 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     own return value in eval (head.py:96-98); ``max_det`` is read from the head (``model.model[-1].max_det``) when the engine is built.
     e2e_raw: True (default) keeps the raw maps of both head copies in that dict -- the validator's loss reads them during training --;
     False runs the rows-only plan, without the one2many branches, and the dict holds ``None`` for every level.  ``augment=True`` (the
-    reference does not augment an end2end model, tasks.py:356) and a head with ``export`` set keep their own forward."""
+    reference does not augment an end2end model, tasks.py:356) and a head with ``export`` set keep their own forward.
+
+    A YOLO-World v2 model (a ``WorldDetect`` head) returns ``(y, raws)`` as WorldDetect.forward does in eval, scored against
+    ``model.txt_feats`` as it is at the call: the engine's key fingerprints that tensor (storage, version counter, shape), so
+    ``set_classes`` (a new tensor, maybe a new row count: a new plan) or an in-place edit rebuilds the engine, counted in
+    ``state["rebuilds"]``.  A call with a ``txt_feats=`` keyword (per-call text, tasks.py:651) and ``augment=True`` (the class is not
+    ``DetectionModel``) keep their own forward."""
     import os
     cfg = cfg_of(model)
     support, gs = _graph_facts(cfg)  # gs: a P6 graph takes multiples of 64; anything else goes to the reference forward, as non-multiples of 32 do
@@ -216,6 +224,7 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     classify = cfg["head"][-1][2] == "Classify"
     pose = cfg["head"][-1][2] == "Pose"
     e2e = cfg["head"][-1][2] == "v10Detect"
+    world = cfg["head"][-1][2] == "WorldDetect"
     state = {"engine": None, "engine32": None, "key": None, "fallbacks": 0, "engine_calls": 0, "fp32_calls": 0, "rebuilds": 0,
              "tta_calls": 0, "support": support, "failed": set(), "repconv": None, "sppf_act": sppf_form(model, cfg)}
     _check_acts(model, cfg, state["sppf_act"], support)  # raises before anything is rebound: the model keeps its forward
@@ -230,6 +239,15 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
     def _engine_for(dev: torch.device, precision: str = "fp16") -> YoloEngine:
         max_det = int(_head_attr(model, "max_det", 300)) if e2e else 300  # v10Detect.max_det (head.py:601), read at every build
         key = (dev.index or 0, _weights_version(model), max_det)
+        txt = getattr(model, "txt_feats", None) if world else None
+        if world:
+            if not torch.is_tensor(txt):
+                raise NotImplementedError("the model holds no txt_feats tensor: a YOLO-World graph is scored against it")
+            try:
+                ver = txt._version
+            except RuntimeError:  # (an inference tensor: no counter, and no in-place edit outside inference mode)
+                ver = -1
+            key += ((txt.data_ptr(), ver, tuple(txt.shape)),)
         if state["key"] != key:
             for k in ("engine", "engine32"):
                 if state[k] is not None:
@@ -252,7 +270,8 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
             # does not see it, so this holds from the next rebuild on) sends the call to the reference forward, which computes it
             _check_acts(model, cfg, state["sppf_act"], support)
             state[slot] = YoloEngine(cfg, sd, device=dev.index or 0, bn_eps=model_bn_eps(model), precision=precision,
-                                     repconv=state["repconv"], max_det=max_det, sppf_act=state["sppf_act"])
+                                     repconv=state["repconv"], max_det=max_det, sppf_act=state["sppf_act"],
+                                     txt_feats=txt.detach().float().cpu() if world else None)
         return state[slot]
 
     def forward(self, x, *args, **kwargs):
@@ -272,6 +291,9 @@ def accelerate(model, device: Optional[int] = None, verbose: bool = False, fp32_
         # kpts_decode's export branch is other arithmetic
         # v10Detect.export (head.py:98): the rows alone
         if (classify or pose or e2e) and _head_exports(self):
+            state["fallbacks"] += 1
+            return orig_forward(x, *args, **kwargs)
+        if world and kwargs.get("txt_feats") is not None:  # per-call text (tasks.py:651): the engine's is folded into its weights
             state["fallbacks"] += 1
             return orig_forward(x, *args, **kwargs)
         if (self.training or visualize or embed or profile or args or not isinstance(x, torch.Tensor)

@@ -10,14 +10,21 @@
                      dense_f16  : fp16 [CoutPad][Kpad], K order (kh, kw, cin), bias fp32 [CoutPad]  (conv_gemm.hip, conv_first.hip)
                      dense_f32  : f32 [K][Cout] (+ the split-f16 planes of the fp32x mode), bias f32 [Cout]  (ref32.hip, conv32x_mfma.hip)
                      depthwise  : f32 [kh*kw][C], bias f32 [C]  (elementwise.hip, bsyolo_ops.hip)
+                     guide      : a C2fAttn block's text rows behind its Linear, [rows][C] f16 (rows padded to 32 with copies of row 0) or
+                                  f32, and f32 [bias | scale]  (maxsig.hip; record kind "maxsig")
+  * YOLO-World   -- the text features travel in the state dict under the reserved key "txt_feats", (nc, E) or (1, nc, E).  Two record kinds
+                     fold them in, in float64, rounded once to the storage type: "maxsig" (above) and "world_cls", WorldDetect's BatchNorm
+                     contrastive head folded into the class branch's last 1x1 conv.
                      The stand-alone operators (ops.py) and the per-module hooks (plugin.py) pack with the same three functions.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import re
 from typing import Dict, List, Mapping, Tuple
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -28,6 +35,21 @@ BN_EPS = 1e-3  # utils/torch_utils.py:424
 
 def _f32(t) -> torch.Tensor:
     return torch.as_tensor(t).detach().to("cpu", torch.float32)
+
+
+def _f64(t) -> torch.Tensor:
+    return torch.as_tensor(t).detach().to("cpu", torch.float64)
+
+
+def _real(t) -> torch.Tensor:
+    """A record's values on the CPU: float64 stays (the YOLO-World folds, rounded once by the layout), everything else becomes fp32."""
+    t = torch.as_tensor(t).detach().to("cpu")
+    return t if t.dtype == torch.float64 else t.to(torch.float32)
+
+
+def _to_f16(t: torch.Tensor) -> torch.Tensor:
+    """Round to f16 ONCE: torch converts float64 through float32 (two roundings), numpy does not."""
+    return torch.from_numpy(t.contiguous().numpy().astype(np.float16)) if t.dtype == torch.float64 else t.to(torch.float16)
 
 
 def fold_conv_bn(sd: Mapping[str, torch.Tensor], prefix: str, eps: float = BN_EPS):
@@ -117,17 +139,18 @@ def packed_dims(cout: int, cin: int, k: int) -> Tuple[int, int]:
     return cp.value, kp.value
 
 
-def dense_f16(w, b=None):
+def dense_f16(w, b=None, once: bool = False):
     """(Cout, Cin, k, k) [+ bias (Cout)] -> fp16 [CoutPad][Kpad], K order (kh, kw, cin), and bias f32 [CoutPad], zero in the padding
-    (csrc/conv_gemm.hip).  An image conv (Cin = 3) is packed with a zero 4th input channel, K = (kh, kw, c4) (csrc/image_conv.h)."""
-    w = _f32(w)
+    (csrc/conv_gemm.hip).  An image conv (Cin = 3) is packed with a zero 4th input channel, K = (kh, kw, c4) (csrc/image_conv.h).
+    The weights go through fp32 whatever they come as; once (the float64 fold of a "world_cls" record alone): float64 is rounded to f16 ONCE."""
+    w = _real(w) if once else _f32(w)
     cout, cin, k, _ = w.shape
     cp, kp = packed_dims(cout, cin, k)
     if cin == 3:
-        w = torch.cat([w, torch.zeros(cout, 1, k, k)], 1)
+        w = torch.cat([w, torch.zeros(cout, 1, k, k, dtype=w.dtype)], 1)
     K = k * k * w.shape[1]
     wp = torch.zeros(cp, kp, dtype=torch.float16)
-    wp[:cout, :K] = w.permute(0, 2, 3, 1).reshape(cout, K).to(torch.float16)
+    wp[:cout, :K] = _to_f16(w.permute(0, 2, 3, 1).reshape(cout, K))
     bp = torch.zeros(cp, dtype=torch.float32)
     if b is not None:
         bp[:cout] = _f32(b)
@@ -152,7 +175,7 @@ def dense_f32(w, b, split: bool = False):
     """(Cout, Cin, k, k) + bias -> ((matrix,) or (matrix, hi, lo), bias): the fp32 correctness mode's f32 [k*k*cin][cout] matrix (K order
     (kh, kw, cin) as in the fp16 layout, cout fastest) and bias f32 [cout], no padding (csrc/ref32.hip); split (fp32x mode) adds the two
     f16 planes of split_f16_planes, which a record carries behind the matrix (_bytes)."""
-    w = _f32(w)
+    w = _f32(w)  # (a float64 fold is rounded here, once)
     cout = w.shape[0]
     mats = (w.permute(2, 3, 1, 0).reshape(-1, cout).contiguous(),)
     if split:
@@ -180,7 +203,8 @@ def _uni(scale: float, shift: float):
 
 
 def _module_dims(r: WRec):
-    """The module's own (cout, cin, kh, kw): the record's, or real_cout / real_cin where the op runs wider than the module."""
+    """The module's own (cout, cin, kh, kw): the record's, or real_cout / real_cin where the op runs wider than the module.  (A "world_cls"
+    record's module is the FOLDED conv: text rows x c3.)"""
     co = r.real_cout or (r.cout // 2 if r.kind == "dwg_ext" else r.cout)
     return co, 1 if r.kind in DW_KINDS else (r.real_cin or r.cin), r.k, r.kw or r.k
 
@@ -258,13 +282,91 @@ def _read_ela(sd, r, eps):
     return torch.cat([t.reshape(-1) for t in p[3:]]).contiguous(), None
 
 
+# ---- YOLO-World: the text features and the two records that fold them in ----
+TXT_KEY = "txt_feats"  # reserved state-dict key: WorldModel.txt_feats (nn/tasks.py:611), (nc, E) or (1, nc, E)
+
+
+def _unit_rows(g, shape):
+    return torch.nn.functional.normalize(torch.randn(*shape, generator=g), dim=-1)
+
+
+def text_rows(sd, r: WRec) -> torch.Tensor:
+    """The text features of `sd` as float64 (rows, E) for record `r`: E must be the record's, the rows the plan's text_nc."""
+    if TXT_KEY not in sd:
+        raise KeyError(f"{r.name}: the state dict has no {TXT_KEY!r} (a YOLO-World graph reads its text features there: (nc, E) or (1, nc, E))")
+    t = _f64(sd[TXT_KEY])
+    if t.dim() == 3:
+        if t.shape[0] != 1:
+            raise NotImplementedError(f"{TXT_KEY} of shape {tuple(t.shape)}: per-image text features are not accelerated (one set per call)")
+        t = t[0]
+    if t.dim() != 2 or t.shape[1] != r.embed:
+        raise ValueError(f"{r.name}: {TXT_KEY} of shape {tuple(t.shape)}, the layer takes rows of E = {r.embed}")
+    if t.shape[0] != r.cout:
+        raise ValueError(f"{r.name}: {TXT_KEY} has {t.shape[0]} rows, the plan was built to score {r.cout} (text_nc)")
+    return t
+
+
+def _maxsig(r):  # MaxSigmoidAttnBlock (block.py:3483-3515) of a C2fAttn: gl = nn.Linear(E, c), bias (nh); cout = text rows, cin = c, k = nh
+    return [(r.name + ".gl.weight", (r.cin, r.embed), _he(r.embed)), (r.name + ".gl.bias", (r.cin,), _uni(0.4, -0.2)),
+            (r.name + ".bias", (r.k,), _uni(2.0, -1.0)), (TXT_KEY, (r.cout, r.embed), _unit_rows)]
+
+
+def _read_maxsig(sd, r, eps):
+    """-> (G float64 (rows, c), [bias | scale] float64 (2 nh)): G[n] = (gl.weight @ t_n + gl.bias) / sqrt(hc) with t_n the text row AS GIVEN
+    (the block does not normalise it; dividing before the maximum is dividing after it); scale = 1 where the module holds the float."""
+    t = text_rows(sd, r)
+    nh, hc = r.k, r.cin // r.k
+    G = (t @ _f64(sd[r.name + ".gl.weight"]).t() + _f64(sd[r.name + ".gl.bias"])) / math.sqrt(hc)
+    scale = _f64(sd[r.name + ".scale"]).reshape(-1) if r.name + ".scale" in sd else torch.ones(nh, dtype=torch.float64)
+    bias = _f64(sd[r.name + ".bias"]).reshape(-1)
+    assert tuple(G.shape) == (r.cout, r.cin) and bias.numel() == nh and scale.numel() == nh, (r.name, tuple(G.shape), bias.numel(), scale.numel())
+    return G, torch.cat([bias, scale])
+
+
+def guide(G: torch.Tensor, f32: bool) -> torch.Tensor:
+    """The guide rows as csrc/maxsig.hip reads them: f32 [rows][c] as they are, or f16 with the rows padded to a multiple of 32 by REPEATING
+    ROW 0 -- the kernel takes its maximum over whole blocks of 32 rows, and a copy of a real row can never win against the rows themselves
+    (a zero row would: every real dot product may be negative)."""
+    if f32:
+        return _f32(G).contiguous()
+    pad = -G.shape[0] % 32
+    return _to_f16(torch.cat([G, G[:1].expand(pad, -1)]) if pad else G)
+
+
+def _world_cls(r):  # WorldDetect's cv3.l.2 = nn.Conv2d(c3, E, 1) and cv4.l = BNContrastiveHead(E) (head.py:314-315; r.post = "<head>.cv4.<l>")
+    co, ci = r.embed, r.real_cin or r.cin
+    return [(r.name + ".weight", (co, ci, 1, 1), _he(ci)), (r.name + ".bias", (co,), _uni(0.4, -0.2)),
+            (r.post + ".norm.weight", (co,), _uni(0.6, 0.7)), (r.post + ".norm.bias", (co,), _uni(0.6, -0.3)),
+            (r.post + ".norm.running_mean", (co,), _uni(0.6, -0.3)), (r.post + ".norm.running_var", (co,), _uni(1.0, 0.5)),
+            (r.post + ".bias", (1,), lambda g, shape: torch.full(shape, -4.21)), (r.post + ".logit_scale", (), lambda g, shape: torch.full(shape, -1.0)),
+            (TXT_KEY, (r.cout, r.embed), _unit_rows)]
+
+
+def _read_world_cls(sd, r, eps):
+    """BNContrastiveHead(cv3.l.2(x), text) (block.py:3609-3631) as ONE biased 1x1 conv c3 -> rows, float64: with a = gamma / sqrt(var + eps),
+    b = beta - mean a (the eval-mode BatchNorm), w^ = the unit-normalised text rows and s = exp(logit_scale):
+    W' = s w^ diag(a) W3,  b' = s w^ (a o b3 + b) + bias."""
+    t = text_rows(sd, r)
+    W3, b3 = _f64(sd[r.name + ".weight"]).flatten(1), _f64(sd[r.name + ".bias"])
+    g, beta = _f64(sd[r.post + ".norm.weight"]), _f64(sd[r.post + ".norm.bias"])
+    mu, var = _f64(sd[r.post + ".norm.running_mean"]), _f64(sd[r.post + ".norm.running_var"])
+    a = g / torch.sqrt(var + eps)
+    b = beta - mu * a
+    wn = torch.nn.functional.normalize(t, dim=-1)
+    s = torch.exp(_f64(sd[r.post + ".logit_scale"]).reshape(()))
+    W = s * (wn * a) @ W3
+    bias = s * (wn @ (a * b3 + b)) + _f64(sd[r.post + ".bias"]).reshape(())
+    return W[:, :, None, None], bias
+
+
 _CONV_BN = (lambda r: _conv_bn_params(r.name, *_module_dims(r)), lambda sd, r, eps: fold_conv_bn(sd, r.name, eps))
 _BARE = (_bare, _read_bare)
 SOURCES = {"conv": _CONV_BN, "first": _CONV_BN, "first_s2d": _CONV_BN, "dw": _CONV_BN, "dwg": _CONV_BN, "dwg_ext": _CONV_BN,
            "conv2": (_conv2, _read_conv2), "plain": _BARE, "dwg_plain": _BARE, "deconv": (_deconv, _read_deconv),
            "refconv": (_refconv, lambda sd, r, eps: fold_refconv(sd, r.name)),
            "repvgg": (_repvgg, lambda sd, r, eps: fold_repvgg(sd, r.name, eps)),
-           "repvggdw": (_repvggdw, lambda sd, r, eps: fold_repvggdw(sd, r.name, eps)), "ela": (_ela, _read_ela)}
+           "repvggdw": (_repvggdw, lambda sd, r, eps: fold_repvggdw(sd, r.name, eps)), "ela": (_ela, _read_ela),
+           "maxsig": (_maxsig, _read_maxsig), "world_cls": (_world_cls, _read_world_cls)}
 
 
 def record_keys(r: WRec) -> List[str]:
@@ -328,11 +430,13 @@ def pack_record(sd: Mapping[str, torch.Tensor], r: WRec, eps: float = BN_EPS, f3
     w, b = SOURCES[r.kind][1](sd, r, eps)
     if r.kind == "ela":  # one flat f32 vector as it is read, no bias
         return _bytes(w), b""
+    if r.kind == "maxsig":  # the guide rows in the storage type, [bias | scale] f32
+        return _bytes(guide(w, f32)), _bytes(_f32(b).contiguous())
     w, b = op_channels(r, w, b)
     if r.kind not in DW_KINDS and f32:
         mats, bp = dense_f32(w, b, split)
         return _bytes(*mats), _bytes(bp)
-    wp, bp = depthwise(w, b) if r.kind in DW_KINDS else dense_f16(w, b)
+    wp, bp = depthwise(w, b) if r.kind in DW_KINDS else dense_f16(w, b, once=r.kind == "world_cls")
     return _bytes(wp), _bytes(bp)
 
 

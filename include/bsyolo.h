@@ -123,6 +123,13 @@ enum bsy_op_kind {
     BSY_OP_FIRST_POOL = 28, /* image conv 3x3 stride 1 pad 1 + bias + act, then MaxPool2d(2, 2, 0), as one launch (csrc/conv_first.hip; fp16 path
                             * only): CONV_FIRST's record with stride = 1 and (OH, OW) = (H / 2, W / 2), the extent of dst; H, W even
                             * (bsy_first_pool_supported).  The conv's map is never stored; the bits of CONV_FIRST -> MAXPOOL mode 0           */
+    BSY_OP_MAXSIG = 29,    /* MaxSigmoidAttnBlock's gate (block.py:3483-3515, YOLO-World's C2fAttn; csrc/maxsig.hip, bsy_maxsig_attn): src0 = the
+                            * embedding view, src1 = the projection view (proj_conv's output), dst = src1 * gate, all (B, H, W, heads * head_dim),
+                            * f16 views (f32 in the fp32-storage modes).  Per pixel and head m: t = max_n sum_k src0[m hc + k] G[n][m hc + k]
+                            * + bias[m], gate = scale[m] * sigmoid(t).  heads, head_dim = hc, nc = the guide's rows; w_off = G, [rows][C] (f16:
+                            * rows padded to a multiple of 32 by repeating row 0; f32: nc rows), the 1 / sqrt(hc) folded in; b_off = f32
+                            * [bias (heads) | scale (heads)].  dst may be src1's view and must not overlap src0's.  fp16: hc a multiple of 16
+                            * from 16 to 128, C, ld and coff multiples of 8 (bsy_maxsig_supported); the fp32-storage modes take any hc      */
     BSY_OP_ELA = 15      /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
@@ -130,7 +137,7 @@ enum bsy_op_kind {
 };
 /* One more than the largest kind above (21 is retired).  A new kind raises this, and the library's table of kind names (csrc/engine.hip,
  * the text of its error messages) is held to it by a static_assert. */
-#define BSY_OP_KIND_COUNT 29
+#define BSY_OP_KIND_COUNT 30
 
 typedef struct bsy_op {
     int32_t kind;
@@ -184,7 +191,7 @@ typedef struct bsy_op {
     int64_t aux_off[18];    /* MSCA_SPATIAL: (weights, bias) byte offsets of its nine depthwise convs */
     int32_t prec;           /* 0: the fp16-storage product path.  1: fp32 correctness mode -- every workspace view is NHWC f32,
                              * dense conv weights are f32 [k*k*Cin][Cout], arithmetic is fp32 (csrc/ref32.hip); kinds CONV_FIRST,
-                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL, MAXPOOL.
+                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL, MAXPOOL, MAXSIG.
                              * 2: fp32x mode -- storage and every non-conv kernel as in mode 1; dense convs (CONV) multiply on the
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
@@ -391,6 +398,20 @@ int bsy_maxpool2d(const void* x, int ldx, int xoff, void* y, int ldy, int yoff, 
                   bsy_stream stream);
 /* 1: BSY_OP_FIRST_POOL takes an image conv of C2 output channels on an H x W image (C2 a multiple of 8 up to 128; H, W even). */
 int bsy_first_pool_supported(int C2, int H, int W);
+
+/* MaxSigmoidAttnBlock's gate (block.py:3483-3515; csrc/maxsig.hip; BSY_OP_MAXSIG in a plan).  embed, proj, out: NHWC views of B x H x W
+ * pixels and heads * hc channels with row strides lde / ldp / ldo, of `dtype` (BSY_F16 or BSY_F32).  For pixel p and head m:
+ *   t = max_n sum_k embed[p][m hc + k] * G[n][m hc + k] + bias_scale[m],   out[p][m hc + j] = proj[p][m hc + j] * bias_scale[heads + m] * sigmoid(t)
+ * computed in f32 and rounded once.  G: [rows][heads * hc] of `dtype`, the caller's 1 / sqrt(hc) folded in; f16: rows = nc rounded up to
+ * a multiple of 32, the padding rows copies of row 0 (a padded row can then never win the max); f32: rows = nc.  bias_scale: f32
+ * [bias (heads) | scale (heads)].  out may be proj itself and must not overlap embed.  f16: hc a multiple of 16 from 16 to 128
+ * (bsy_maxsig_supported), lde / ldp / ldo multiples of 8 and every pointer 16-byte aligned; f32 takes any hc.  The sums' order depends on
+ * hc and nc alone: a pixel's bits do not depend on the batch or on where in the map it lies.  Null pointers, nc < 1, such an hc and an
+ * overlap of embed and out are BSY_ERR_ARG, before any launch. */
+int bsy_maxsig_attn(const void* embed, int lde, const void* proj, int ldp, void* out, int ldo, int B, int H, int W, int heads, int hc,
+                    const void* G, int nc, const float* bias_scale, int dtype, bsy_stream stream);
+/* 1: the fp16 kernel of BSY_OP_MAXSIG takes heads of hc channels (16, 32, ... 128). */
+int bsy_maxsig_supported(int hc);
 
 /* Attention core (block.py:4267-4286): qkv NHWC f16 with channel order [q(all heads) | k(all heads) | v(all heads)],
  * out[pixel][head*head_dim + d] = sum_j softmax_j(q_i . k_j * scale) v_j[d].  key_dim in {16, 32, 48, 64}, head_dim in {32, 64, 96, 128}

@@ -98,6 +98,34 @@ int main() {
         EXPECT(a.idx == nullptr && a.val == nullptr && a.k == 0 && a.x == nullptr && a.y == ext0.data());
     }
 
+    {   // MAXSIG: both storage types through one builder; what the record alone says is refused before a view is resolved
+        Resolver R = resolver();
+        bsy_op op = blank(BSY_OP_MAXSIG);
+        op.B = 2; op.H = 3; op.W = 5; op.heads = 2; op.head_dim = 32; op.nc = 12; op.w_off = 512; op.b_off = 4096;
+        op.src0 = view(0, 160, 8, 64); op.src1 = view(0, 160, 72, 64); op.dst = op.src1;
+        MaxSigArgs a;
+        clear_error();
+        EXPECT(build_maxsig(a, op, R, wb) && !error_set());
+        EXPECT(a.embed == (half_t*)ws.data() + 8 && a.proj == (half_t*)ws.data() + 72 && a.dst == a.proj && a.dtype == BSY_F16);
+        EXPECT(a.lde == 160 && a.HW == 15 && a.heads == 2 && a.hc == 32 && a.nc == 12 && a.G == wb + 512 && a.bias_scale == (const float*)(wb + 4096));
+        op.prec = 1; op.head_dim = 7; op.src0.C = op.src1.C = op.dst.C = 14;
+        MaxSigArgs b;
+        EXPECT(build_maxsig(b, op, R, wb) && b.dtype == BSY_F32 && b.embed == (float*)ws.data() + 8 && b.hc == 7);
+        op.prec = 0;
+        for (int bad = 0; bad < 4; ++bad) {
+            bsy_op o = op;
+            o.head_dim = 32; o.src0.C = o.src1.C = o.dst.C = 64;
+            if (bad == 0) o.nc = 0;
+            if (bad == 1) { o.head_dim = 8; o.src0.C = o.src1.C = o.dst.C = 16; }
+            if (bad == 2) o.dst = view(0, 160, 40, 64);  // over the embedding's channels
+            if (bad == 3) o.src1.buf = -1;
+            Resolver Rb = resolver();
+            MaxSigArgs c;
+            clear_error();
+            EXPECT(!build_maxsig(c, o, Rb, wb) && error_set() && !Rb.ok && c.embed == nullptr);
+        }
+    }
+
     // ---- the conv record, field by field ----
     {   // two sources (virtual Concat), the second read through nearest-x2
         Resolver R = resolver();
