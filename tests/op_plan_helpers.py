@@ -1,5 +1,5 @@
 """Shared pieces of the one-op plan tests (test_glue_ops.py, test_bsyolo_ops.py, test_fp32_matrix_ops.py, test_fp16_conv_ops.py, test_fp16_head_ops.py,
-test_fp16_block_ops.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every tensor bound as an external slot, poisoned
+test_fp16_block_ops.py, test_fp16_attention_op.py): a single bsy_op run through bsy_plan_create / bsy_plan_run with every tensor bound as an external slot, poisoned
 views and a weight-blob builder.  Not a test module."""
 import ctypes as C
 import math
@@ -214,6 +214,96 @@ def attn32_op(prec, B, H, W, src, dst, heads, key_dim, head_dim, scale):
     op.src0, op.dst = src, dst
     op.heads, op.key_dim, op.head_dim, op.scale = heads, key_dim, head_dim, float(scale)
     return op
+
+
+def attn16_op(B, H, W, src, dst, heads, kd, hd, scale, pe=None):
+    """A fp16 (prec 0) ATTN op, fields as build_attn reads them (csrc/op_args.h): src = the [q | k | v] view, N = H * W;
+    pe = (w_off, b_off): act = 1 and the blob offsets of Attention.pe's depthwise record (attn16_pe_blob), folded into the epilogue."""
+    from bs_yolo_amd import lib as L
+    op = new_op(L.OP_ATTN, 0, B, H, W)
+    op.src0, op.dst = src, dst
+    op.heads, op.key_dim, op.head_dim, op.scale = heads, kd, hd, float(scale)
+    if pe is not None:
+        op.act, op.w_off, op.b_off = 1, pe[0], pe[1]
+    return op
+
+
+def attn16_pe_blob(w, b):
+    """Attention.pe's record for attn16_op in a poisoned blob: ops.pack_dw_weight's f32 [9][heads * hd] matrix of w (heads * hd, 1, 3, 3)
+    and the f32 bias, NaN behind each.  -> (bytes, (w_off, b_off))."""
+    from bs_yolo_amd import ops as O
+    wp, bp = O.pack_dw_weight(w, b, "cpu")
+    blob, offs = poisoned_blob([wp.numpy(), bp.numpy()])
+    return blob, (offs[0], offs[1])
+
+
+def attn_ref64(qkv, heads, kd, hd, scale):
+    """Softmax attention in fp64 on the fp16 ATTN op's layout, with what attn16_bound needs.  qkv (B, ..., heads * (2 kd + hd)) in
+    [q (all heads) | k (all heads) | v (all heads)] order, the axes between the first and the last flattened to N.  ->
+      out   (B, N, heads * hd)  sum_j p_j v_jd / sum_j p_j,  p_j = exp(s_j - max s),  s_j = scale * q . k_j
+      A     (B, N, heads * hd)  sum_j p_j |v_jd| / sum_j p_j
+      Smax  (B, N, heads)       scale * max_j sum_c |q_c| |k_jc|
+      l     (B, N, heads)       sum_j p_j  (>= 1: the maximal key has p = 1)
+      vmax  (B, heads * hd)     max_j |v_jd|
+      v     (B, N, heads * hd)  the v channels (for pe), and N, heads, kd, hd."""
+    from types import SimpleNamespace
+    B, C_ = qkv.shape[0], qkv.shape[-1]
+    assert C_ == heads * (2 * kd + hd)
+    x = qkv.detach().cpu().double().reshape(B, -1, C_)
+    N = x.shape[1]
+    q = x[..., :heads * kd].view(B, N, heads, kd).permute(0, 2, 1, 3)
+    k = x[..., heads * kd:2 * heads * kd].view(B, N, heads, kd).permute(0, 2, 1, 3)
+    v = x[..., 2 * heads * kd:].view(B, N, heads, hd).permute(0, 2, 1, 3)
+    s = (q @ k.transpose(-1, -2)) * scale
+    p = torch.exp(s - s.max(-1, keepdim=True).values)
+    l = p.sum(-1, keepdim=True)
+    flat = lambda t: t.permute(0, 2, 1, 3).reshape(B, N, -1)
+    return SimpleNamespace(out=flat(p @ v / l), A=flat(p @ v.abs() / l), l=flat(l),
+                           Smax=flat((q.abs() @ k.abs().transpose(-1, -2)).max(-1, keepdim=True).values * scale),
+                           vmax=x[..., 2 * heads * kd:].abs().max(1).values, v=x[..., 2 * heads * kd:].contiguous(),
+                           N=N, heads=heads, kd=kd, hd=hd)
+
+
+def attn_pe_ref64(r, w, b, H, W):
+    """Attention.pe on top of attn_ref64's `r`: w (heads * hd, 1, 3, 3), b (heads * hd), the N keys an H x W map.  ->
+      y    (B, N, heads * hd)  r.out + depthwise3x3(v) + bias, in fp64
+      mag  (B, N, heads * hd)  |bias| + sum_taps |w| |v|, the magnitude the depthwise arithmetic's error scales with."""
+    from types import SimpleNamespace
+    B, Cc = r.v.shape[0], r.v.shape[-1]
+    assert H * W == r.N and tuple(w.shape) == (Cc, 1, 3, 3)
+    w9 = w.double().reshape(Cc, 9).t()
+    v = r.v.view(B, H, W, Cc)
+    dw = dw_ref(v, w9, b, False, None).reshape(B, r.N, Cc)
+    mag = dw_ref(v.abs(), w9.abs(), b.abs(), False, None).reshape(B, r.N, Cc)
+    return SimpleNamespace(y=r.out + dw, mag=mag)
+
+
+def attn16_bound(r, pe=None):
+    """Allowed |got - fp64| per output element of the fp16 attention kernel (csrc/attention.hip), from attn_ref64's `r`: derived from
+    the kernel's arithmetic -- 32-key tiles, f32 online softmax, P rounded to f16 for the PV product, the row sum of the unrounded
+    P -- not fitted to its output.  u = 2^-24, nt = ceil(N / 32); the sum of
+      2^-11 A                                          P rounded to f16 for the PV product while the row sum keeps the f32 P
+      N 2^-25 vmax / max(l, 1)                         the f16 subnormal floor of P (subnormals are not flushed in the default mode)
+      2 ((kd + 8) u Smax 1.4427 * 1.45 + 4u) A         the f32 error of the exponent's argument and of v_exp_f32, in the numerator
+                                                       and in the denominator
+      1.1 (N + 2 nt + 8) u A                           the f32 sums of O and l, and the alpha rescales
+      0.5 ulp16(out) + 2u |out|                        o * inv rounded to f32, then to f16
+    and, with pe = attn_pe_ref64(...) (the value compared is then pe.y = out + dw):
+      0.5 ulp16(out)                                   the attention output rounded to f16 before the depthwise sum is added
+      12u (|bias| + sum_taps |w| |v|)                  the depthwise arithmetic: a bias and nine f32 fmas
+      0.5 ulp16(y) + u |y|                             the final f32 sum and its rounding to f16"""
+    nt = (r.N + 31) // 32
+    A, out = r.A, r.out
+    Smax = r.Smax.repeat_interleave(r.hd, -1)
+    l = r.l.repeat_interleave(r.hd, -1)
+    b = 2.0 ** -11 * A
+    b = b + r.N * 2.0 ** -25 * r.vmax[:, None, :] / l.clamp(min=1.0)
+    b = b + 2 * ((r.kd + 8) * U * Smax * 1.4427 * 1.45 + 4 * U) * A
+    b = b + 1.1 * (r.N + 2 * nt + 8) * U * A
+    b = b + 0.5 * _u16(out) + 2 * U * out.abs()
+    if pe is not None:
+        b = b + 0.5 * _u16(out) + 12 * U * pe.mag + 0.5 * _u16(pe.y) + U * pe.y.abs()
+    return b
 
 
 def assert_outside_views_intact(t, before, views):
