@@ -38,6 +38,7 @@ SOURCES = {
     "pool_down.hip": ["-ffp-contract=off"],  # the average must round like ATen's: ordered fp32 sum, one product, one rounding
     "maxpool.hip": [],
     "maxsig.hip": ["-fno-vectorize"],  # (as classify.hip: no packed f32 arithmetic from the loop vectoriser in the gate's multiply loops)
+    "cbfuse.hip": ["-fno-vectorize"],  # (as maxsig.hip: no packed f32 arithmetic from the loop vectoriser in the per-piece sums)
     "attention.hip": [],
     "detect.hip": [],
     "nms.hip": ["-ffp-contract=off"],

@@ -342,6 +342,32 @@ struct MaxSigArgs {
 inline bool maxsig_supported(int hc) { return hc >= 16 && hc <= 128 && hc % 16 == 0; }  // the fp16 kernel's head widths: 1 .. 8 k-steps of 16
 int launch_maxsig(const MaxSigArgs& a, hipStream_t s);
 
+// cbfuse.hip: CBFuse (block.py:3760-3772), dst = tap 0 + ... + tap n-1 + last in f32, in that order; tap i stored at (H >> shift, W >> shift).
+// Pointers include the channel offset; views of `dtype` (BSY_F16 / BSY_F32).  dst may be `last` itself and must not overlap a tap.
+struct CbFuseArgs {
+    const void* tap[BSY_CBFUSE_MAX_TAPS] = {};
+    int ldt[BSY_CBFUSE_MAX_TAPS] = {}, shift[BSY_CBFUSE_MAX_TAPS] = {};
+    int n = 0;
+    const void* last = nullptr;
+    void* dst = nullptr;
+    int ldl = 0, ldd = 0, B = 0, H = 0, W = 0, C = 0, dtype = 0;
+};
+// tap count 1 .. 5, shifts 0 .. 4 that divide H and W; sets the error text.  What both callers check without a pointer (the engine's record
+// through op_args.h cbfuse_record_ok, the launcher for the entry point)
+inline bool cbfuse_shape_ok(int n, const int* shift, int H, int W) {
+    if (n < 1 || n > BSY_CBFUSE_MAX_TAPS) { bsy_set_error("cbfuse: %d taps (1 to %d)", n, BSY_CBFUSE_MAX_TAPS); return false; }
+    if (H < 1 || W < 1) { bsy_set_error("cbfuse: bad map size %d x %d", H, W); return false; }
+    for (int i = 0; i < n; ++i) {
+        if (shift[i] < 0 || shift[i] > 4) { bsy_set_error("cbfuse: tap %d has shift %d (0 to 4)", i, shift[i]); return false; }
+        if (H % (1 << shift[i]) || W % (1 << shift[i])) {
+            bsy_set_error("cbfuse: tap %d: %d x %d is not divisible by %d", i, H, W, 1 << shift[i]);
+            return false;
+        }
+    }
+    return true;
+}
+int launch_cbfuse(const CbFuseArgs& a, hipStream_t s);
+
 struct AttnArgs {
     const half_t* qkv = nullptr;
     int ld = 0;

@@ -78,8 +78,8 @@ static int plan_make_lanes(bsy_plan* p) {
 static int plan_check_acts(const bsy_op* ops, int n_ops, const char* who) {
     static const char* const names[] = {"CONV_FIRST", "CONV", "DWCONV", "SPPF_POOL", "ATTN", "DECODE", "RAW_NCHW", "NHWC2NCHW", "STEM", "BNECK",
                                         "DWCONV_G", "COPY", "GAP", "MSCA_MIX", "MUL", "ELA", "DWPW", "MSCA_SPATIAL", "C3K2", "S2D", "PMSFA_TAIL",
-                                        "CHAIN", "POOL_DOWN", "CLASSIFY_TAIL", "GHOST", "ADD", "E2E_TOPK", "MAXPOOL", "FIRST_POOL", "MAXSIG"};
-    static_assert(sizeof(names) / sizeof(names[0]) == BSY_OP_KIND_COUNT && BSY_OP_MAXSIG == BSY_OP_KIND_COUNT - 1 && BSY_OP_ELA == 15 &&
+                                        "CHAIN", "POOL_DOWN", "CLASSIFY_TAIL", "GHOST", "ADD", "E2E_TOPK", "MAXPOOL", "FIRST_POOL", "MAXSIG", "CBFUSE"};
+    static_assert(sizeof(names) / sizeof(names[0]) == BSY_OP_KIND_COUNT && BSY_OP_CBFUSE == BSY_OP_KIND_COUNT - 1 && BSY_OP_MAXSIG == 29 && BSY_OP_ELA == 15 &&
                   BSY_OP_DWPW == 16 && BSY_OP_GHOST == 24, "names[] is indexed by bsy_op_kind: a new kind adds its name here, in the enum's order");
     for (int i = 0; i < n_ops; ++i) {
         const int kind = ops[i].kind, act = ops[i].act;
@@ -88,6 +88,11 @@ static int plan_check_acts(const bsy_op* ops, int n_ops, const char* who) {
         if (kind == BSY_OP_MAXSIG && !maxsig_record_ok(ops[i])) {
             const std::string why = bsy_last_error();
             BSY_FAIL(BSY_ERR_ARG, "%s: op %d (MAXSIG): %s", who, i, why.c_str());
+        }
+        // CBFUSE: a tap count or shift out of range, a size a shift does not divide, a tap narrower than dst, a dst over a tap's channels
+        if (kind == BSY_OP_CBFUSE && !cbfuse_record_ok(ops[i])) {
+            const std::string why = bsy_last_error();
+            BSY_FAIL(BSY_ERR_ARG, "%s: op %d (CBFUSE): %s", who, i, why.c_str());
         }
         if (kind == BSY_OP_DWCONV_G || kind == BSY_OP_DECODE || kind == BSY_OP_ATTN) continue;
         const bool ids = kind == BSY_OP_CONV_FIRST || kind == BSY_OP_FIRST_POOL || kind == BSY_OP_STEM || kind == BSY_OP_CONV;

@@ -133,6 +133,49 @@ inline bool build_maxsig(MaxSigArgs& a, const bsy_op& op, Resolver& R, const cha
     a.G = wb + op.w_off; a.bias_scale = (const float*)(wb + op.b_off);
     return R.ok;
 }
+// CBFUSE (both storage types): src0 = the last input, dst = the sum (may be src0's view); nl taps, tap i = box[i] (i < 4) / cls[0] (i = 4)
+// with its shift in lvl_h[i] / lvl_w[0].  What needs no pointer is checked in cbfuse_record_ok, which bsy_plan_create asks as well; the
+// launcher checks the rest (alignment, overlap of the resolved addresses)
+inline const bsy_view& cbfuse_tap(const bsy_op& op, int i) { return i < BSY_MAX_LEVELS ? op.box[i] : op.cls[i - BSY_MAX_LEVELS]; }
+inline int cbfuse_shift(const bsy_op& op, int i) { return i < BSY_MAX_LEVELS ? op.lvl_h[i] : op.lvl_w[i - BSY_MAX_LEVELS]; }
+inline bool cbfuse_record_ok(const bsy_op& op) {
+    int shift[BSY_CBFUSE_MAX_TAPS] = {};
+    for (int i = 0; i < BSY_CBFUSE_MAX_TAPS && i < op.nl; ++i) shift[i] = cbfuse_shift(op, i);
+    if (!cbfuse_shape_ok(op.nl, shift, op.H, op.W)) return false;
+    const int C = op.dst.C;
+    if (op.src0.buf < 0 || op.dst.buf < 0 || C < 1) { bsy_set_error("cbfuse: null pointer (src0 and dst are both needed)"); return false; }
+    if (op.src0.C < C) { bsy_set_error("cbfuse: the last input has %d channels, dst %d", op.src0.C, C); return false; }
+    if (op.src0.buf == op.dst.buf && (op.src0.coff != op.dst.coff || op.src0.ld != op.dst.ld) && op.src0.coff < op.dst.coff + C &&
+        op.dst.coff < op.src0.coff + C) {
+        bsy_set_error("cbfuse: the destination overlaps the last input without being its view (in place: the same view)");
+        return false;
+    }
+    for (int i = 0; i < op.nl; ++i) {
+        const bsy_view& t = cbfuse_tap(op, i);
+        if (t.buf < 0) { bsy_set_error("cbfuse: null pointer (tap %d of %d is absent)", i, op.nl); return false; }
+        if (t.C < C) { bsy_set_error("cbfuse: tap %d is narrower (%d channels) than dst (%d)", i, t.C, C); return false; }
+        if (t.buf == op.dst.buf && t.coff < op.dst.coff + C && op.dst.coff < t.coff + C) {
+            bsy_set_error("cbfuse: the destination overlaps tap %d", i);
+            return false;
+        }
+    }
+    return true;
+}
+inline bool build_cbfuse(CbFuseArgs& a, const bsy_op& op, Resolver& R, const char*) {
+    if (!cbfuse_record_ok(op)) { R.ok = false; return false; }
+    const bool f32 = op.prec != 0;
+    a.dtype = f32 ? BSY_F32 : BSY_F16;
+    a.n = op.nl;
+    for (int i = 0; i < op.nl; ++i) {
+        const bsy_view& t = cbfuse_tap(op, i);
+        a.tap[i] = f32 ? (const void*)R.f(t) : (const void*)R.h(t);
+        a.ldt[i] = t.ld; a.shift[i] = cbfuse_shift(op, i);
+    }
+    a.last = f32 ? (const void*)R.f(op.src0) : (const void*)R.h(op.src0);
+    a.dst = f32 ? (void*)R.f(op.dst) : (void*)R.h(op.dst);
+    a.ldl = op.src0.ld; a.ldd = op.dst.ld; a.B = op.B; a.H = op.H; a.W = op.W; a.C = op.dst.C;
+    return R.ok;
+}
 // NHWC2NCHW: dst = the whole BCHW tensor, an optional output -- `skip`: its slot is unbound, nothing is resolved or launched
 template <typename T>
 inline bool build_nhwc2nchw(const T*& src, void*& out, bool& skip, const bsy_op& op, Resolver& R) {

@@ -218,6 +218,16 @@ extern "C" int bsy_maxsig_attn(const void* embed, int lde, const void* proj, int
     return launch_maxsig(a, (hipStream_t)stream);
 }
 
+extern "C" int bsy_cbfuse(const void* const* taps, const int* ld_taps, const int* shifts, int n_taps, const void* last, int ld_last, void* out,
+                          int ld_out, int B, int H, int W, int C, int dtype, bsy_stream stream) {
+    if (n_taps < 1 || n_taps > BSY_CBFUSE_MAX_TAPS) BSY_FAIL(BSY_ERR_ARG, "cbfuse: %d taps (1 to %d)", n_taps, BSY_CBFUSE_MAX_TAPS);
+    if (!taps || !ld_taps || !shifts) BSY_FAIL(BSY_ERR_ARG, "cbfuse: null pointer (the host arrays of the taps)");
+    CbFuseArgs a;
+    for (int i = 0; i < n_taps; ++i) { a.tap[i] = taps[i]; a.ldt[i] = ld_taps[i]; a.shift[i] = shifts[i]; }
+    a.n = n_taps; a.last = last; a.ldl = ld_last; a.dst = out; a.ldd = ld_out; a.B = B; a.H = H; a.W = W; a.C = C; a.dtype = dtype;
+    return launch_cbfuse(a, (hipStream_t)stream);
+}
+
 extern "C" int bsy_maxsig_supported(int hc) { return maxsig_supported(hc) ? 1 : 0; }
 
 extern "C" int bsy_attention(const void* qkv, int ld, int B, int N, int heads, int key_dim, int head_dim, float scale,

@@ -17,7 +17,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
     if (op.prec < 0 || op.prec > 2) BSY_FAIL(BSY_ERR_ARG, "plan_run: unknown precision mode %d", op.prec);
     // fp32 correctness mode (bsy_op.prec == 1, and 2 = fp32x) first: same op records, f32 views, kernels of ref32.hip.  DECODE, RAW_NCHW
     // and CLASSIFY_TAIL consume f32 logit maps in every mode, POOL_DOWN and MAXPOOL take the storage type as an argument, E2E_TOPK reads a tensor of
-    // out_dtype, MAXSIG's launcher takes the storage type as an argument too: they break out of this switch into the common one.
+    // out_dtype, MAXSIG's and CBFUSE's launchers take the storage type as an argument too: they break out of this switch into the common one.
     Views<float> v32;
     if (op.prec) switch (op.kind) {
         case BSY_OP_CONV_FIRST:
@@ -70,6 +70,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
         case BSY_OP_RAW_NCHW:
         case BSY_OP_E2E_TOPK:
         case BSY_OP_MAXSIG:
+        case BSY_OP_CBFUSE:
             break;
         default:
             BSY_FAIL(BSY_ERR_ARG, "fp32 mode: op kind %d has no fp32 implementation (fused kinds are fp16-only)", op.kind);
@@ -92,6 +93,7 @@ int run_op(const bsy_op& op, Resolver& R, const char* wb, hipStream_t s) {
         case BSY_OP_DWCONV: return run(build_dwconv, launch_dwconv, op, R, wb, s);
         case BSY_OP_DECODE: return run(build_decode, launch_decode, op, R, wb, s);
         case BSY_OP_MAXSIG: return run(build_maxsig, launch_maxsig, op, R, wb, s);  // f16 views, f32 in the fp32-storage modes
+        case BSY_OP_CBFUSE: return run(build_cbfuse, launch_cbfuse, op, R, wb, s);  // f16 views, f32 in the fp32-storage modes
         case BSY_OP_ATTN: {
             AttnArgs a;
             return build_attn(a, op, R, wb) ? launch_attention(a, s) : BSY_ERR_ARG;

@@ -13,7 +13,8 @@ C3Ghost blocks on the YOLOv8 layouts, detect only), and the YOLOv10 graphs cfg/m
 "yolov10": one layout, a literal table per size of where C2fCIB stands and whether it holds the 7x7 RepVGGDW; a v10Detect head), and the
 YOLOv3 graphs cfg/models/v3/yolov3.yaml, yolov3-spp.yaml and yolov3-tiny.yaml (families "yolov3", "yolov3-spp", "yolov3-tiny": one size
 each, `depth_multiple` / `width_multiple` of 1.0 instead of a scales table; detect only), and the open-vocabulary graph
-cfg/models/v8/yolov8-worldv2.yaml (family "yolov8-worldv2": C2fAttn neck blocks, a WorldDetect head; detect only).  They are
+cfg/models/v8/yolov8-worldv2.yaml (family "yolov8-worldv2": C2fAttn neck blocks, a WorldDetect head; detect only), and YOLOv9e,
+cfg/models/v9/yolov9e.yaml and yolov9e-seg.yaml (family "yolov9e": one size, two GELAN backbones joined by CBLinear / CBFuse).  They are
 restated here as data so the engine can be built where the reference is not installed (benchmarks, GPU box).
 """
 from __future__ import annotations
@@ -268,6 +269,35 @@ def _yolov9(size: str) -> dict:
     }
 
 
+# YOLOv9e, cfg/models/v9/yolov9e.yaml:9-63 (yolov9e-seg.yaml: the same graph under Segment): an nn.Identity that names the image, a first
+# GELAN backbone (layers 1-9) whose five maps each feed a CBLinear (10-14: a biased 1x1 conv split into one group per stage up to its
+# own), and a second backbone (15-28) of the same stem / ADown / RepNCSPELAN4 steps that starts from the image again and adds, after each
+# step, group s of every CBLinear at stage s or deeper (CBFuse, nearest-upsampled); then SPPELAN and yolov9c's neck layout.  One size,
+# literal widths: the two stem widths, [c2, c3, c4] of the four stages (RepCSP repeats n), SPPELAN's [c2, c3], the neck's four blocks.
+_V9E = dict(stem=(64, 128), stages=([256, 128, 64], [512, 256, 128], [1024, 512, 256], [1024, 512, 256]), n=2, spp=[512, 256],
+            neck=([512, 512, 256], [256, 256, 128], [512, 512, 256], [512, 1024, 512]))
+
+
+def _yolov9e() -> dict:
+    z = _V9E
+    elan = lambda a: [-1, 1, "RepNCSPELAN4", list(a) + [z["n"]]]
+    down = lambda c: [-1, 1, "ADown", [c]]
+    s = [elan(a) for a in z["stages"]]
+    groups = [z["stem"][0], z["stem"][1]] + [a[0] for a in z["stages"][:3]]  # the width of each step's map: what a CBFuse there adds
+    first = [[-1, 1, "Conv", [z["stem"][0], 3, 2]], [-1, 1, "Conv", [z["stem"][1], 3, 2]], s[0], down(groups[2]), s[1], down(groups[3]), s[2],
+             down(groups[4]), s[3]]  # layers 1-9
+    taps = [[src, 1, "CBLinear", [groups[:j + 1]]] for j, src in enumerate((1, 3, 5, 7, 9))]  # layers 10-14
+    fuse = lambda j: [list(range(10 + j, 15)) + [-1], 1, "CBFuse", [[j] * (5 - j)]]
+    second = [[0, 1, "Conv", [z["stem"][0], 3, 2]], fuse(0), [-1, 1, "Conv", [z["stem"][1], 3, 2]], fuse(1), elan(z["stages"][0]), down(groups[2]),
+              fuse(2), elan(z["stages"][1]), down(groups[3]), fuse(3), elan(z["stages"][2]), down(groups[4]), fuse(4), elan(z["stages"][3])]  # 15-28
+    n = [elan(a) for a in z["neck"]]
+    return {
+        "backbone": [[-1, 1, "nn.Identity", []]] + first + taps + second + [[-1, 1, "SPPELAN", list(z["spp"])]],
+        "head": [_UP, _cat(25), n[0], _UP, _cat(22), n[1], down(n[1][3][0]), _cat(32), n[2], down(n[2][3][0]), _cat(29), n[3]],
+        "detect_from": [35, 38, 41],
+    }
+
+
 # YOLOv10, cfg/models/v10/yolov10{n,s,m,b,l,x}.yaml:6-41: the YOLOv8 layout with SCDown for the stride-2 convs of P4 / P5 (and of the neck's
 # last step), PSA behind SPPF and the NMS-free v10Detect head.  Every size is its own file with a one-entry `scales` table; they differ in
 # which of layers 6, 8, 13, 19, 22 are C2fCIB instead of C2f and in C2fCIB's `lk` argument (RepVGGDW 7x7; n and s only).
@@ -410,7 +440,9 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
     stock_cfg("yolov10", "s") == 'yolov10s.yaml' (scales n, s, m, b, l, x; detect only);
     stock_cfg("yolov3-tiny", None) == 'yolov3-tiny.yaml' (families "yolov3", "yolov3-spp", "yolov3-tiny": one size each, so `scale` must be
     None or ""; detect only; the dict carries depth_multiple = width_multiple = 1.0 and no `scales`);
-    stock_cfg("yolov8-worldv2", "s") == 'yolov8s-worldv2.yaml' (scales n, s, m, l, x; detect only)."""
+    stock_cfg("yolov8-worldv2", "s") == 'yolov8s-worldv2.yaml' (scales n, s, m, l, x; detect only);
+    stock_cfg("yolov9e", None) == 'yolov9e.yaml', with task="segment" 'yolov9e-seg.yaml' (family "yolov9e": one size, `scale` None or "";
+    stock_cfg("yolov9", "e") stays a ValueError)."""
     if family in _V3_FAMILIES:
         if scale not in (None, "") or task != "detect":
             raise ValueError(f"{family}: scale {scale!r} / task {task!r} (one size, scale None; detect only)")
@@ -426,6 +458,12 @@ def stock_cfg(family: str = "yolo11", scale: str = "s", nc: int = 80, task: str 
         raise ValueError(f"{family}: no pose graph ({', '.join(_POSE_FAMILIES)})")
     if task == "pose" and kpt_shape is None:
         raise ValueError("pose: kpt_shape=(keypoints, channels of each) is needed (the reference's yamls say (17, 3))")
+    if family == "yolov9e":  # one size: two backbones joined by CBLinear / CBFuse; no `scales`, literal widths like "yolov9"
+        if scale not in (None, "") or task not in ("detect", "segment"):
+            raise ValueError(f"yolov9e: scale {scale!r} / task {task!r} (one size, scale None; detect and segment)")
+        fam = _yolov9e()
+        head = fam["head"] + [[fam["detect_from"], 1, "Detect", ["nc"]] if task == "detect" else [fam["detect_from"], 1, "Segment", ["nc", 32, 256]]]
+        return {"nc": nc, "backbone": fam["backbone"], "head": head}
     if family == "yolov9":
         if scale not in _V9_SIZES or task not in ("detect", "segment") or (task == "segment" and scale != "c"):
             raise ValueError(f"yolov9: scale {scale!r} / task {task!r} (detect: t, s, m, c; segment: c)")

@@ -18,14 +18,15 @@ LIB_PATH = Path(os.environ["BSY_LIB"]) if os.environ.get("BSY_LIB") else PKG / "
 BSY_F16, BSY_F32, BSY_U8 = 0, 1, 2
 BSY_EXT_BASE = 0x100000
 BSY_MAX_LEVELS = 4  # include/bsyolo.h: length of bsy_op's per-level arrays
+BSY_CBFUSE_MAX_TAPS = 5  # include/bsyolo.h: taps of OP_CBFUSE (box[0..3] + cls[0], shifts in lvl_h[0..3] + lvl_w[0])
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2  # bsy_op.act of CONV_FIRST / FIRST_POOL / STEM / CONV
-(OP_CONV_FIRST, OP_CONV, OP_DWCONV, OP_SPPF_POOL, OP_ATTN, OP_DECODE, OP_RAW_NCHW, OP_NHWC2NCHW, OP_STEM, OP_BNECK, OP_DWCONV_G, OP_COPY, OP_GAP, OP_MSCA_MIX, OP_MUL, OP_ELA, OP_DWPW, OP_MSCA_SPATIAL, OP_C3K2, OP_S2D, OP_PMSFA_TAIL, OP_CHAIN, OP_POOL_DOWN, OP_CLASSIFY_TAIL, OP_GHOST, OP_ADD, OP_E2E_TOPK, OP_MAXPOOL, OP_FIRST_POOL, OP_MAXSIG) = range(30)
+(OP_CONV_FIRST, OP_CONV, OP_DWCONV, OP_SPPF_POOL, OP_ATTN, OP_DECODE, OP_RAW_NCHW, OP_NHWC2NCHW, OP_STEM, OP_BNECK, OP_DWCONV_G, OP_COPY, OP_GAP, OP_MSCA_MIX, OP_MUL, OP_ELA, OP_DWPW, OP_MSCA_SPATIAL, OP_C3K2, OP_S2D, OP_PMSFA_TAIL, OP_CHAIN, OP_POOL_DOWN, OP_CLASSIFY_TAIL, OP_GHOST, OP_ADD, OP_E2E_TOPK, OP_MAXPOOL, OP_FIRST_POOL, OP_MAXSIG, OP_CBFUSE) = range(31)
 # OP_CHAIN (21): retired kind, kept in the unpacking only because bench.py still names it; plans never contain it
 
 SYMBOLS = [
     "bsy_engine_create", "bsy_engine_destroy", "bsy_engine_load_weights", "bsy_plan_create", "bsy_plan_create_arena", "bsy_engine_arena_bytes", "bsy_plan_set_tuning", "bsy_plan_destroy",
     "bsy_plan_run", "bsy_plan_graph_launch", "bsy_plan_profile", "bsy_plan_copy_buffer", "bsy_plan_check_guards", "bsy_plan_autotune", "bsy_plan_get_tuning", "bsy_plan_check_tuning", "bsy_plan_autotune_in_place", "bsy_conv2d", "bsy_conv2d_f32", "bsy_conv2d_f32x", "bsy_conv_first_f32", "bsy_attention_f32", "bsy_conv_packed_dims", "bsy_conv_first", "bsy_stem_fused", "bsy_stem_fused_supported", "bsy_bottleneck_fused", "bsy_bottleneck_fused_supported", "bsy_c3k2_fused", "bsy_c3k2_fused_supported", "bsy_dwconv", "bsy_dwpw_fused", "bsy_dwpw_fused_supported", "bsy_attention_supported", "bsy_pmsfa_tail_supported", "bsy_msca_spatial_supported", "bsy_ghost_fused_supported", "bsy_ela", "bsy_ela_scratch_bytes", "bsy_dwconv3x3",
-    "bsy_sppf_pool", "bsy_pool_down", "bsy_maxpool2d", "bsy_first_pool_supported", "bsy_maxsig_attn", "bsy_maxsig_supported", "bsy_attention", "bsy_attention_pe", "bsy_detect_decode", "bsy_detect_decode_fmt", "bsy_nms_workspace_bytes", "bsy_nms", "bsy_scale_boxes",
+    "bsy_sppf_pool", "bsy_pool_down", "bsy_maxpool2d", "bsy_first_pool_supported", "bsy_maxsig_attn", "bsy_maxsig_supported", "bsy_cbfuse", "bsy_attention", "bsy_attention_pe", "bsy_detect_decode", "bsy_detect_decode_fmt", "bsy_nms_workspace_bytes", "bsy_nms", "bsy_scale_boxes",
     "bsy_letterbox", "bsy_process_mask", "bsy_process_mask_native", "bsy_scale_masks", "bsy_val_match", "bsy_pack_masks", "bsy_val_match_masks_workspace_bytes", "bsy_val_match_masks", "bsy_val_match_rotated", "bsy_slice_tiles", "bsy_sahi_merge_workspace_bytes",
     "bsy_sahi_merge", "bsy_scale_img", "bsy_tta_merge", "bsy_nms_rotated_workspace_bytes", "bsy_nms_rotated", "bsy_obb_scale", "bsy_end2end_topk_workspace_bytes", "bsy_end2end_topk", "bsy_classify_tail", "bsy_ap_workspace_bytes", "bsy_ap_per_class",
     "bsy_kpts_decode", "bsy_pose_scale", "bsy_val_match_kpts", "bsy_last_error", "bsy_version", "bsy_sizeof_op",
@@ -153,6 +154,7 @@ def _load() -> C.CDLL:
     lib.bsy_first_pool_supported.argtypes = [i32, i32, i32]
     lib.bsy_maxsig_attn.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp]
     lib.bsy_maxsig_supported.argtypes = [i32]
+    lib.bsy_cbfuse.argtypes = [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.bsy_attention.argtypes = [vp, i32, i32, i32, i32, i32, i32, f32, vp, i32, vp]
     lib.bsy_attention_pe.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp]
     lib.bsy_detect_decode.argtypes = [C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), C.POINTER(vp),

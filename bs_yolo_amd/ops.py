@@ -447,3 +447,41 @@ def maxsig_attn(embed: torch.Tensor, proj: torch.Tensor, G: torch.Tensor, bias: 
     L.check(L.lib.bsy_maxsig_attn(pe, lde, pp, ldp, po, ldo, B, H, W, int(nh), Cc // int(nh), _p(gp), int(nc), _p(bs), L.dtype_code(embed.dtype),
                                   _stream(embed)))
     return out
+
+
+def cbfuse(taps: Sequence[torch.Tensor], shifts: Sequence[int], last: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CBFuse (nn/modules/block.py:3760-3772) in one launch (bsy_cbfuse): last (B,H,W,C) NHWC fp16 or fp32 on the device (or a channel
+    slice of a wider tensor); taps: 1 to 5 NHWC tensors or channel slices, tap i of (B, H >> shifts[i], W >> shifts[i], >= C), of which the
+    first C channels are read through nearest upsampling by 2^shifts[i] (0 .. 4).  out = tap 0 + ... + tap n-1 + last, summed in f32 in
+    that order and rounded once.  out: `last` itself (in place) or another tensor of its shape; None = a new one.  It must not overlap a
+    tap.  Every argument is checked before anything is launched."""
+    taps, shifts = list(taps), [int(k) for k in shifts]
+    if not last.is_cuda or not all(t.is_cuda for t in taps):
+        raise RuntimeError("bs_yolo_amd.ops.cbfuse needs GPU tensors (no CPU fallback)")
+    if not 1 <= len(taps) <= L.BSY_CBFUSE_MAX_TAPS or len(shifts) != len(taps):
+        raise ValueError(f"cbfuse: {len(taps)} taps with {len(shifts)} shifts (1 to {L.BSY_CBFUSE_MAX_TAPS} taps, a shift each)")
+    pl, ldl, B, H, W, Cc = _nhwc(last)
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=last.dtype, device=last.device)
+    po, ldo, *shape_o = _nhwc(out)
+    if tuple(shape_o) != (B, H, W, Cc):
+        raise ValueError(f"cbfuse: out is {tuple(out.shape)}, last {tuple(last.shape)}")
+    if last.dtype not in (torch.float16, torch.float32) or any(t.dtype != last.dtype for t in taps + [out]):
+        raise ValueError(f"cbfuse: mixed storage types {[str(t.dtype) for t in taps + [last, out]]} (all fp16 or all fp32)")
+    ptrs, lds = [], []
+    for i, (t, k) in enumerate(zip(taps, shifts)):
+        if not 0 <= k <= 4:
+            raise ValueError(f"cbfuse: tap {i} has shift {k} (0 to 4)")
+        if H % (1 << k) or W % (1 << k):
+            raise ValueError(f"cbfuse: tap {i}: {H} x {W} is not divisible by {1 << k}")
+        pt, ldt, Bt, Ht, Wt, Ct = _nhwc(t)
+        if (Bt, Ht, Wt) != (B, H >> k, W >> k):
+            raise ValueError(f"cbfuse: tap {i} is {tuple(t.shape)}, the target {tuple(last.shape)} over 2^{k}")
+        if Ct < Cc:
+            raise ValueError(f"cbfuse: tap {i} is narrower ({Ct} channels) than the target ({Cc})")
+        ptrs.append(pt.value)
+        lds.append(ldt)
+    n = len(taps)
+    L.check(L.lib.bsy_cbfuse((C.c_void_p * n)(*ptrs), (C.c_int * n)(*lds), (C.c_int * n)(*shifts), n, pl, ldl, po, ldo, B, H, W, Cc,
+                             L.dtype_code(last.dtype), _stream(last)))
+    return out

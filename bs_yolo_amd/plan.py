@@ -153,9 +153,18 @@ class _ZeroPadded:
             raise NotImplementedError(f"model.{i - 1}: nn.ZeroPad2d is accelerated only in front of nn.MaxPool2d [2, 1, 0] (model.{i} is {m})")
 
 
+@dataclass
+class _Slices:
+    """What a CBLinear layer (block.py:3740-3757) hands on: the channel groups of its one conv's output, as views of that buffer.  Only a
+    CBFuse may read it (Plan._build refuses every other consumer by name)."""
+    parts: List[T]
+    layer: int
+
+
 class _Layer:
     """What the graph walk hands to a layer's lowering (Plan.LOWERINGS): the layer's index, its name "model.i", its module, its input x
-    (`f` resolved: a T, a list of T behind a Concat, a _ZeroPadded, or None for the image), its arguments with "nc" resolved, its repeat
+    (`f` resolved: a T, a list of T behind a Concat, a _ZeroPadded, a _Slices or a list that holds some in front of a CBFuse, or None for
+    the image), its arguments with "nc" resolved, its repeat
     count depth-scaled, args[0] width-scaled where the table says the module's is (else None), and whether it is the graph's last.
     ONE record per walk, refilled for every layer (a fresh one each was 5 % of plan construction): a lowering reads it and keeps none."""
     __slots__ = ("i", "name", "m", "x", "args", "n", "c2", "last")
@@ -1192,6 +1201,7 @@ class Plan:
         self.legacy = True  # Detect's class branch is the heavy one (head.py:44-56) until a C3k2 says otherwise (tasks.py:1048)
         self.layers = layers = list(d["backbone"]) + list(d["head"])
         outs: List = []   # per layer: T, or list[T] for a lazy Concat
+        self._first_layer = 0  # the layer that emits op 0, the first reader of the image: 0, or 1 behind an accepted nn.Identity
         x, ly, last, lowerings = None, _Layer(), len(layers) - 1, self.LOWERINGS
         for i, (f, n, m, args) in enumerate(layers):
             name = f"model.{i}"
@@ -1200,6 +1210,11 @@ class Plan:
                 x = outs[f] if isinstance(f, int) else [x if j == -1 else outs[j] for j in f]
             if isinstance(x, _ZeroPadded):
                 x.gate(i, m)
+            if m != "CBFuse":
+                for t in x if isinstance(x, list) else [x]:
+                    if isinstance(t, _Slices):
+                        raise NotImplementedError(f"{name}: {m} reads the output of CBLinear model.{t.layer}: its channel groups are views that "
+                                                  "only a CBFuse may read")
             if relu and m not in self.RELU_MODULES:
                 # ReLU exists in the kernels of CONV_FIRST / FIRST_POOL / STEM / CONV alone; every block module lowers to other kinds as
                 # well (and, in this fork, would keep SiLU anyway: block.py:13 shadows Conv there).  No silent SiLU where the reference
@@ -1214,12 +1229,14 @@ class Plan:
             ly.i, ly.name, ly.m, ly.x, ly.args, ly.n, ly.last = i, name, m, x, args, max(round(n * depth), 1) if n > 1 else n, i == last
             ly.c2 = self._scaled(args[0]) if scaled else None
             x = lower(self, ly)
+            if first_op == 0 and self.ops:
+                self._first_layer = i
             if relu:  # what RELU_MODULES promises, checked on the ops themselves
                 for o in self.ops[first_op:]:
                     if o["kind"] not in self.RELU_KINDS:
                         raise NotImplementedError(f"{name}: {m} lowers to op {o['name']} of kind {o['kind']}, which has no ReLU (activation nn.ReLU())")
             outs.append(x)
-        self.layer_out = [None if isinstance(t, _ZeroPadded) else t for t in outs]
+        self.layer_out = [t if isinstance(t, (T, list)) else None for t in outs]  # (a _ZeroPadded, a _Slices, the image, a head: no map)
         self.meta.update(scale=self.scale, n_layers=len(layers), legacy=self.legacy)
         self._fuse_stem()
         self._fuse_first_pool()
@@ -1232,7 +1249,7 @@ class Plan:
     def _m_conv(self, ly: _Layer):
         name, x, n, c2, k, s = ly.name, ly.x, ly.n, ly.c2, ly.arg(1, 1), ly.arg(2, 1)
         pad = k // 2 if ly.arg(3, None) is None else ly.args[3]
-        if ly.i == 0:
+        if x is None:  # the image: layer 0, or a layer that reads an accepted nn.Identity at layer 0 (yolov9e's layers 1 and 15)
             if n > 1:
                 raise NotImplementedError(f"{name}: an image conv repeated {n} times is not accelerated")
             if (k, s, pad) not in ((3, 2, 1), (3, 1, 1), (6, 2, 2)):
@@ -1384,6 +1401,75 @@ class Plan:
                                       "with bias, once, is accelerated)")
         return self.deconv(name, x, self._scaled(ly.args[0]))
 
+    def _m_identity(self, ly: _Layer):
+        """nn.Identity at layer 0 names the image so that a second backbone can read it (yolov9e.yaml: layer 15 reads layer 0).  Its output is
+        the image itself (None, as layer 0's input is); accepted only where some layer reads layer 0 by its index -- behind an Identity that
+        layer 1 alone reads, every index of a checkpoint's graph is shifted by one for nothing, and the graph stays on the reference."""
+        if ly.i != 0:
+            raise NotImplementedError(f"{ly.name}: nn.Identity is accelerated as layer 0 (a name for the image) only")
+        readers = [j for j, (fj, _, _, _) in enumerate(self.layers) if j and 0 in ([fj] if isinstance(fj, int) else list(fj))]
+        if not readers:
+            raise NotImplementedError(f"{ly.name}: nn.Identity that no layer reads by index (model.1 alone reads it) is not accelerated")
+        for j in sorted(set(readers + [1])):
+            fj, _, mj, _ = self.layers[j]
+            if (j in readers or fj == -1) and (mj != "Conv" or not isinstance(fj, int)):
+                raise NotImplementedError(f"{ly.name}: the image behind nn.Identity is read by model.{j} ({mj}); only a Conv of its own may")
+        return None
+
+    def _m_cblinear(self, ly: _Layer):
+        """CBLinear [c2s, k, s, p, g] (block.py:3740-3757; tasks.py: c1 = ch[f], the widths literal): a biased nn.Conv2d without BN or
+        activation whose output is split into groups of c2s channels.  k = 1: one plain 1x1 CONV into a sum(c2s)-wide buffer; the layer's
+        output is the groups as views of it (_Slices)."""
+        name, x, arg = ly.name, ly.x, ly.arg
+        c2s = arg(0, None)
+        if not isinstance(c2s, (list, tuple)) or not c2s or any(not isinstance(c, int) or c < 1 for c in c2s):
+            raise NotImplementedError(f"{name}: CBLinear with the widths {c2s!r} (a list of channel counts is accelerated)")
+        if (arg(1, 1), arg(2, 1), arg(3, None), arg(4, 1)) != (1, 1, None, 1) or ly.n != 1:
+            raise NotImplementedError(f"{name}: CBLinear with k, s, p, g = {ly.args[1:5]} (the default 1x1 conv, once, is accelerated)")
+        if not isinstance(x, T) or x.up or x.cmap is not None:
+            raise NotImplementedError(f"{name}: CBLinear on a Concat, an upsampled view or zero-padded pieces is not accelerated")
+        for c in c2s:
+            self._fp16_mult8(c, f"{name}: CBLinear with a group of {c} channels is not on the fp16 path (multiples of 8)")
+        y = self.conv(name + ".conv", x, sum(c2s), 1, 1, act=False, plain=True)
+        parts, c0 = [], 0
+        for c in c2s:
+            parts.append(y.slice(c0, c))
+            c0 += c
+        return _Slices(parts, ly.i)
+
+    def _m_cbfuse(self, ly: _Layer):
+        """CBFuse [idx] (block.py:3760-3772): the last input plus group idx[i] of the i-th CBLinear, nearest-upsampled to the last input's
+        size -- one OP_CBFUSE into a fresh map (csrc/cbfuse.hip; the sum's order is the reference's: the taps in order, then the last)."""
+        name, x = ly.name, ly.x
+        idx = ly.arg(0, None)
+        if not isinstance(x, list) or len(x) < 2 or not all(isinstance(t, _Slices) for t in x[:-1]):
+            raise NotImplementedError(f"{name}: CBFuse reads CBLinear outputs and, last, one map; its inputs are {self.layers[ly.i][0]}")
+        last = x[-1]
+        if not isinstance(last, T) or last.up or last.cmap is not None:
+            raise NotImplementedError(f"{name}: the last input of CBFuse must be a plain map (not a CBLinear output, a Concat, an upsampled "
+                                      "view or zero-padded pieces)")
+        if not isinstance(idx, (list, tuple)) or len(idx) != len(x) - 1:
+            raise NotImplementedError(f"{name}: CBFuse with idx = {idx!r} for {len(x) - 1} CBLinear inputs (one index each)")
+        if len(idx) > L.BSY_CBFUSE_MAX_TAPS:
+            raise NotImplementedError(f"{name}: CBFuse of {len(idx)} CBLinear inputs (up to {L.BSY_CBFUSE_MAX_TAPS} are accelerated)")
+        taps, shifts = [], []
+        for s, j in zip(x[:-1], idx):
+            if not isinstance(j, int) or not 0 <= j < len(s.parts):
+                raise NotImplementedError(f"{name}: idx {j!r} is out of range for CBLinear model.{s.layer} ({len(s.parts)} groups)")
+            t = s.parts[j]
+            if t.C != last.C:
+                raise NotImplementedError(f"{name}: group {j} of CBLinear model.{s.layer} has {t.C} channels, the last input {last.C}")
+            k = next((k for k in range(5) if (t.H << k, t.W << k) == (last.H, last.W)), None)
+            if k is None:
+                raise NotImplementedError(f"{name}: CBLinear model.{s.layer} is {t.H} x {t.W}, the target {last.H} x {last.W}: a tap is "
+                                          "upsampled by 1, 2, 4, 8 or 16 (never down)")
+            taps.append(t)
+            shifts.append(k)
+        dst = self.alloc(last.C, last.H, last.W)
+        self._emit(L.OP_CBFUSE, name, src0=last, dst=dst, nl=len(taps), box=taps[:L.BSY_MAX_LEVELS], cls=taps[L.BSY_MAX_LEVELS:],
+                   lvl_h=shifts[:L.BSY_MAX_LEVELS], lvl_w=shifts[L.BSY_MAX_LEVELS:])
+        return dst
+
     def _m_upsample(self, ly: _Layer):
         x = ly.x
         assert isinstance(x, T) and not x.up and ly.args[1] == 2 and ly.args[2] == "nearest"
@@ -1470,6 +1556,7 @@ class Plan:
         "Detect": (_m_head, False), "Segment": (_m_head, False), "OBB": (_m_head, False), "Pose": (_m_head, False), "v10Detect": (_m_head, False),
         "WorldDetect": (_m_head, False),
         "Classify": (_m_classify, False),
+        "nn.Identity": (_m_identity, False), "CBLinear": (_m_cblinear, False), "CBFuse": (_m_cbfuse, False),  # YOLOv9e (the widths are literal)
     }
 
     def _fuse_layer0(self, on: bool, kind: int, match):
@@ -1482,7 +1569,10 @@ class Plan:
         fields = match(a, b) if b.get("src0") is mid else None
         if fields is None:
             return
-        for o in self.ops[2:]:  # layer 0 must have no other reader
+        # layer 0 must have no other reader.  A layer's map reaches an op through src0 / src1 / res alone: the list fields hold head maps,
+        # scratch and, for CBFUSE, CBLinear outputs, which are no layer's map (only a CBFuse reads them) -- a kind that reads a layer's map
+        # through box / cls would have to be looked at here as well
+        for o in self.ops[2:]:
             for t in (o.get("src0"), o.get("src1"), o.get("res")):
                 if t is not None and t.buf == mid.buf:
                     return
@@ -1490,7 +1580,7 @@ class Plan:
         self._emit(kind, a["name"] + "+" + b["name"].split(".")[-1], src0=a["src0"], dst=b["dst"], act=a["act"], wkey=a["wkey"],
                    in_dtype=self.in_dtype, **fields)
         self.ops[0:2] = [self.ops.pop()]  # (the two layers' flops are counted already)
-        self.layer_out[0] = None
+        self.layer_out[self._first_layer] = None
 
     def _fuse_first_pool(self):
         """Peephole: layer 0 (image conv 3x3 s1 p1) + layer 1 (MaxPool2d(2, 2, 0)) -> one OP_FIRST_POOL launch (csrc/conv_first.hip)."""

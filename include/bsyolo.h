@@ -130,6 +130,14 @@ enum bsy_op_kind {
                             * rows padded to a multiple of 32 by repeating row 0; f32: nc rows), the 1 / sqrt(hc) folded in; b_off = f32
                             * [bias (heads) | scale (heads)].  dst may be src1's view and must not overlap src0's.  fp16: hc a multiple of 16
                             * from 16 to 128, C, ld and coff multiples of 8 (bsy_maxsig_supported); the fp32-storage modes take any hc      */
+    BSY_OP_CBFUSE = 30,    /* CBFuse (block.py:3760-3772, YOLOv9e; csrc/cbfuse.hip, bsy_cbfuse), one launch, f16 views (f32 in the fp32-storage
+                            * modes): dst = tap 0 + tap 1 + ... + tap nl-1 + src0, summed in f32 IN THAT ORDER from +0.0 and rounded once.
+                            * src0 = the last input, (B, H, W, dst.C) like dst; nl = tap count, 1 .. 5; tap i is the view box[i] for i < 4,
+                            * cls[0] for i = 4, its first dst.C channels; its shift k is lvl_h[i] for i < 4, lvl_w[0] for i = 4, 0 .. 4: the
+                            * tap is stored at (H >> k, W >> k) and read at pixel (y >> k, x >> k) (nearest upsampling by 2^k; H and W are
+                            * divisible by 2^k).  dst may be src0's view (in place); it must not overlap a tap.  bsy_plan_create refuses
+                            * a tap count or shift out of range, an H or W that a shift does not divide, a tap (or src0) narrower than
+                            * dst.C, and a dst that shares channels of a buffer with a tap, with BSY_ERR_ARG, naming the op                */
     BSY_OP_ELA = 15      /* ELA (nn/Addmodules/ELA.py:77-101): ksize = Conv1d taps; w_off -> f32 blob [spatial_conv C*k]
                             * [ch_att conv C*k][gn.weight C][gn.bias C]; scale, lvl_stride[0], lvl_stride[1] =
                             * sigmoid(ch_weight), sigmoid(sp_weight), sigmoid(res_weight);
@@ -137,7 +145,8 @@ enum bsy_op_kind {
 };
 /* One more than the largest kind above (21 is retired).  A new kind raises this, and the library's table of kind names (csrc/engine.hip,
  * the text of its error messages) is held to it by a static_assert. */
-#define BSY_OP_KIND_COUNT 30
+#define BSY_OP_KIND_COUNT 31
+#define BSY_CBFUSE_MAX_TAPS 5 /* BSY_OP_CBFUSE / bsy_cbfuse: CBLinear outputs summed besides the last input */
 
 typedef struct bsy_op {
     int32_t kind;
@@ -191,7 +200,7 @@ typedef struct bsy_op {
     int64_t aux_off[18];    /* MSCA_SPATIAL: (weights, bias) byte offsets of its nine depthwise convs */
     int32_t prec;           /* 0: the fp16-storage product path.  1: fp32 correctness mode -- every workspace view is NHWC f32,
                              * dense conv weights are f32 [k*k*Cin][Cout], arithmetic is fp32 (csrc/ref32.hip); kinds CONV_FIRST,
-                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL, MAXPOOL, MAXSIG.
+                             * CONV, DWCONV, DWCONV_G, SPPF_POOL, ATTN, DECODE, RAW_NCHW, NHWC2NCHW, COPY, GAP, MSCA_MIX, MUL, ADD, ELA, POOL_DOWN, CLASSIFY_TAIL, MAXPOOL, MAXSIG, CBFUSE.
                              * 2: fp32x mode -- storage and every non-conv kernel as in mode 1; dense convs (CONV) multiply on the
                              * fp16 matrix pipe with both operands split into f16 pairs (csrc/conv32x_mfma.hip: ~2^-21 relative
                              * operand error instead of the exact fp32 chain); their weight record is the mode-1 f32 matrix followed
@@ -412,6 +421,18 @@ int bsy_maxsig_attn(const void* embed, int lde, const void* proj, int ldp, void*
                     const void* G, int nc, const float* bias_scale, int dtype, bsy_stream stream);
 /* 1: the fp16 kernel of BSY_OP_MAXSIG takes heads of hc channels (16, 32, ... 128). */
 int bsy_maxsig_supported(int hc);
+
+/* CBFuse (block.py:3760-3772; csrc/cbfuse.hip; BSY_OP_CBFUSE in a plan) in one launch.  out, last: NHWC views of B x H x W pixels and C
+ * channels with row strides ld_out / ld_last; taps, ld_taps, shifts: HOST arrays of n_taps entries (1 .. BSY_CBFUSE_MAX_TAPS): tap i is
+ * a device view of B x (H >> shifts[i]) x (W >> shifts[i]) pixels, row stride ld_taps[i], of which the first C channels are read.  All
+ * views are of `dtype` (BSY_F16 or BSY_F32) and include their channel offset.
+ *   out[n][y][x][c] = tap_0[n][y >> s0][x >> s0][c] + ... + tap_{n-1}[...][c] + last[n][y][x][c]
+ * summed in f32 in that order, starting from +0.0, and rounded once.  out may be `last` itself (the same pointer and stride) and must
+ * not overlap a tap.  Views whose strides and addresses are multiples of 16 bytes (and C of 8 f16 / 4 f32 channels) take the 16-byte
+ * form, anything else an element-wise form of the same bits.  A tap count outside 1 .. 5, a shift outside 0 .. 4 or one that does not
+ * divide H and W, a row stride below C, a null pointer and such an overlap are BSY_ERR_ARG, before any launch. */
+int bsy_cbfuse(const void* const* taps, const int* ld_taps, const int* shifts, int n_taps, const void* last, int ld_last, void* out,
+               int ld_out, int B, int H, int W, int C, int dtype, bsy_stream stream);
 
 /* Attention core (block.py:4267-4286): qkv NHWC f16 with channel order [q(all heads) | k(all heads) | v(all heads)],
  * out[pixel][head*head_dim + d] = sum_j softmax_j(q_i . k_j * scale) v_j[d].  key_dim in {16, 32, 48, 64}, head_dim in {32, 64, 96, 128}
