@@ -2,20 +2,18 @@
 (csrc/classify.hip: softmax, logit copy and top-k in one launch), the forward against fixtures made by running the reference
 (tests/golden/make_cls_fixtures.py), and the plugin hooks.  The CPU oracle has no Classify: parity is against the fixtures only."""
 import ctypes as C
-import functools
-import json
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, synth_state_dict
-from oracle.yolo_ref import synth_param
+from graph_helpers import fixture, state_dict, x_of
 
 DEV = "cuda:0"
 GRAPHS = ["yolo11n_cls", "yolov8n_cls", "yolo11n_cls1000"]
@@ -27,28 +25,9 @@ PRECISIONS = ["fp16", "fp32x", "fp32"]
 FP16_LOGIT_BOUND = 2 * 3.502e-3
 
 
-@functools.lru_cache(maxsize=None)
-def _fixture(tag):
-    z = np.load(GOLDEN / f"graph_{tag}.npz")
-    return {k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"]))
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def _sd_cached(tag):
-    _, meta = _fixture(tag)
-    return {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-
-
 def _sd(tag):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated."""
-    return dict(_sd_cached(tag))
+    """A copy of the reference's un-fused state dict (no damping rule), for the callers that add or drop keys."""
+    return dict(state_dict(tag, None))
 
 
 def _cfg(meta):
@@ -65,7 +44,7 @@ def _stable_topk(y, k):
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tag", ["yolo11n_cls", "yolov8n_cls"])
 def test_stock_cfg_restates_the_reference_yaml(tag):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     cfg = _cfg(meta)
     want = meta["yaml"]  # yaml.safe_load of the reference's file, recorded by make_cls_fixtures.py
     assert cfg["backbone"] == want["backbone"] and cfg["scales"] == want["scales"]
@@ -116,7 +95,7 @@ def test_classify_plan(family, nc, precision):
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_classify_weights_pack_from_the_reference_state_dict(tag):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     sd = _sd(tag)
     seen = set()
 
@@ -315,12 +294,12 @@ def test_classify_tail_ranks_nan_first():
 # ---- device: the forward ---------------------------------------------------------------------------------------------------
 def _engine(tag, precision, **kw):
     from bs_yolo_amd.engine import YoloEngine
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     return YoloEngine(_cfg(meta), _sd(tag), precision=precision, bn_eps=meta["bn_eps"], **kw)  # 1e-5, not DetectionModel's 1e-3
 
 
 def _input(tag, si, precision):
-    x = _x(_fixture(tag)[1], si)
+    x = x_of(fixture(tag)[1], si)
     return (x.half() if precision == "fp16" else x).to(DEV)
 
 
@@ -331,7 +310,7 @@ def test_classify_graph_matches_reference(tag, precision):
     """fp32x / fp32: the project's 1e-3 on y and on the logits (O(1) on these fixtures), and the fixture's own top-k order (its
     smallest top-5 logit gap is 3e-3).  fp16: the project's 1e-2 on y; FP16_LOGIT_BOUND on the logits; the top-k against a stable sort
     of the engine's own y (fp16 error is not small against the fixtures' gaps)."""
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     nc, k = meta["nc"], min(meta["nc"], 5)
     assert eng.task == "classify" and eng.max_stride == 32 and eng.nc == nc
@@ -364,7 +343,7 @@ def test_classify_pooled_vector_and_guards(tag, precision, monkeypatch):
     """The (B, 1280) mean behind OP_GAP, read back from the plan's buffer, against the reference's (a forward hook on Classify.pool),
     under the logits' bound of the mode.  The plan runs in a private workspace with guard bands: no op of it stores out of bounds."""
     monkeypatch.setenv("BSY_PLAN_GUARD", "4096")
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision, autotune=False)
     for si, (b, h, w) in enumerate(meta["shapes"]):
         xin = _input(tag, si, precision)
@@ -431,7 +410,7 @@ class ClassificationModel(torch.nn.Module):
 
     def __init__(self, tag):
         super().__init__()
-        meta = _fixture(tag)[1]
+        meta = fixture(tag)[1]
         self.yaml = _cfg(meta)
         for name, t in _sd(tag).items():
             mod = self
@@ -457,10 +436,10 @@ class ClassificationModel(torch.nn.Module):
 def test_accelerate_classification_model_and_validator_hook():
     from bs_yolo_amd import plugin
     tag = "yolo11n_cls"
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     m = ClassificationModel(tag).to(DEV)
     assert plugin.accelerate(m) is m
-    x = _x(meta, 1).to(DEV)
+    x = x_of(meta, 1).to(DEV)
     y, lg = m(x)  # fp32 input: the fp32x engine
     torch.cuda.synchronize()
     assert m.calls == 0 and m._bsy_state["fp32_calls"] == 1

@@ -25,7 +25,6 @@ fp32 / fp32x 1e-3 and 1e-3 * imgsz.
 
 Run on the MI355X box with ``pytest -m gpu``; everything else runs anywhere."""
 import ctypes as C
-import json
 import re
 from functools import lru_cache
 from types import SimpleNamespace
@@ -35,14 +34,15 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan, make_divisible
 from bs_yolo_amd.weights import fold_conv_bn, pack_plan_weights, synth_state_dict
+from graph_helpers import (RawBounds, RefModel, YBounds, all_equal, cfg_of, check_nms, check_raw, check_y, engine, fixture, kinds, level_of_anchor,
+                           outputs, state_dict, x_of)
 from op_plan_helpers import (DEV, NAN, POISON16, POISON32, _bound, _worst, assert_poison_intact, bits, conv1x1_op, dw_ref, dwg_op, new_op,
                              packed_1x1, poisoned, poisoned_blob, run_ops, view)
-from oracle.yolo_ref import synth_param
 
 gpu = pytest.mark.gpu
 NC = 12
@@ -52,46 +52,21 @@ STRIDES = {"yolov8-ghost": (8, 16, 32), "yolov8-ghost-p2": (4, 8, 16, 32), "yolo
 SHAPES = {"yolov8-ghost": [(1, 64, 64), (2, 96, 128)], "yolov8-ghost-p2": [(1, 64, 64), (2, 96, 128)],
           "yolov8-ghost-p6": [(1, 64, 64), (2, 128, 192)]}  # the fixtures' shapes; p6 (no fixture) needs multiples of 64
 GRAPHS = ["yolov8s_ghost", "yolov8n_ghost_p2", "yolov8x_ghost"]
-_CACHE = {}
-
-
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=None, box16=1.0, score32=1e-3, box32=1e-3)  # the graph bounds of the module docstring
+RAW_BOUNDS = RawBounds(rel16=3e-2, strict16=False, floor16=True, rel32=1e-3)
 
 
 def _damped(name, suffixes):
     return re.search(r"\.m\.\d+\.", name) is not None and any(name.endswith(s) for s in suffixes)
 
 
-@lru_cache(maxsize=None)
+def _damp(name, meta):
+    """The rule the generator wrote into meta["damp"] (make_ghost_fixtures.py)."""
+    return meta["damp"]["factor"] if _damped(name, meta["damp"]["suffixes"]) else 1.0
+
+
 def _sd_of(tag):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated from synth_param and damped by the
-    rule the generator wrote into meta["damp"] (make_ghost_fixtures.py)."""
-    meta = _fixture(tag)[1]
-    sd = {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-    d = meta["damp"]
-    for n in sd:
-        if _damped(n, d["suffixes"]):
-            sd[n] = sd[n] * d["factor"]
-    return sd
-
-
-def _cfg(meta):
-    return stock_cfg(meta["family"], meta["scale"], meta["nc"], meta["task"])
-
-
-def _kinds(plan, kind):
-    return [o for o in plan.ops if o["kind"] == kind]
+    return state_dict(tag, _damp)
 
 
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
@@ -128,9 +103,9 @@ def test_ghost_plans(family, scale, precision, monkeypatch):
         assert m["strides"] == [float(s) for s in strides] and m["levels"] == [(h // s, w // s) for s in strides]
         assert m["A"] == sum((h // s) * (w // s) for s in strides) and m["legacy"] and m["nm"] == 0
         nb = sum(max(round(l[1] * depth), 1) for l in cfg["backbone"] + cfg["head"] if l[2] == "C3Ghost")  # GhostBottlenecks
-        ghosts, adds = _kinds(plan, L.OP_GHOST), _kinds(plan, L.OP_ADD)
+        ghosts, adds = kinds(plan, L.OP_GHOST), kinds(plan, L.OP_ADD)
         assert (len(ghosts), len(adds)) == ((2 * nb, 0) if precision == "fp16" else (0, nb))
-        assert not _kinds(plan, L.OP_BNECK) and len(_kinds(plan, L.OP_SPPF_POOL)) == 1
+        assert not kinds(plan, L.OP_BNECK) and len(kinds(plan, L.OP_SPPF_POOL)) == 1
         for o in ghosts:
             assert o["dst"].C == 2 * o["mid_c"] and not o["src0"].C % 8 and not o["mid_c"] % 8 and o["lane"] == 0
             assert (o["res"] is not None) == o["name"].endswith(".conv.2") and o["act"] == int(o["name"].endswith(".conv.0"))
@@ -156,15 +131,15 @@ def test_conv_flops_at_640(family):
     reference's own convs (make_ghost_fixtures.py conv_gflops_640, stored in every fixture's meta) -- test_yolov9.py's tolerance.  The
     fp16 plans of n, m and x carry their 4-, 12- and 20-channel pieces on 8, 16 and 24 and multiply 0.1 - 0.3 % more; the fp32 plans
     have no padding.  mfma_flops holds the dense part only, as for DWPW."""
-    ref = _fixture("yolov8s_ghost")[1]["ref_conv_gflops_640"][family]
+    ref = fixture("yolov8s_ghost")[1]["ref_conv_gflops_640"][family]
     for scale in "nsmlx":
         for precision in ("fp16", "fp32"):
             plan = Plan(stock_cfg(family, scale, 80), 1, 640, 640, precision=precision)
             got = plan.flops / 1e9
             print(family, scale, precision, f"plan {got:.4f} reference convs {ref[scale]:.4f}")
             assert abs(got - ref[scale]) <= 0.01 * ref[scale]
-            dw = sum(2 * o["OH"] * o["OW"] * o["src0"].C * 25 for o in _kinds(plan, L.OP_DWCONV_G))
-            dw += sum(2 * o["OH"] * o["OW"] * o["mid_c"] * 25 for o in _kinds(plan, L.OP_GHOST))
+            dw = sum(2 * o["OH"] * o["OW"] * o["src0"].C * 25 for o in kinds(plan, L.OP_DWCONV_G))
+            dw += sum(2 * o["OH"] * o["OW"] * o["mid_c"] * 25 for o in kinds(plan, L.OP_GHOST))
             assert sum(o.get("mfma_flops", 0) for o in plan.ops) == plan.flops - dw
         if scale in "sl":
             assert abs(got - ref[scale]) <= 1e-4 * ref[scale]  # no padding anywhere: the same count
@@ -174,13 +149,13 @@ def test_fuse_ghost_switch(monkeypatch):
     cfg = stock_cfg("yolov8-ghost", "s", NC)
     monkeypatch.setenv("BSY_FUSE_GHOST", "0")
     off = Plan(cfg, 1, 64, 64)
-    assert not off.fuse_ghost and not _kinds(off, L.OP_GHOST) and len(_kinds(off, L.OP_ADD)) == 10
+    assert not off.fuse_ghost and not kinds(off, L.OP_GHOST) and len(kinds(off, L.OP_ADD)) == 10
     for env in (None, "1"):
         monkeypatch.delenv("BSY_FUSE_GHOST", raising=False)
         if env:
             monkeypatch.setenv("BSY_FUSE_GHOST", env)
         on = Plan(cfg, 1, 64, 64)
-        assert on.fuse_ghost and len(_kinds(on, L.OP_GHOST)) == 20 and not _kinds(on, L.OP_ADD)
+        assert on.fuse_ghost and len(kinds(on, L.OP_GHOST)) == 20 and not kinds(on, L.OP_ADD)
     assert not Plan(cfg, 1, 64, 64, precision="fp32").fuse_ghost and not Plan(cfg, 1, 64, 64, precision="fp32x").fuse_ghost
     with pytest.raises(TypeError):  # a plan attribute read from the environment like fuse_boxtail, not a keyword of SWITCHES
         Plan(cfg, 1, 64, 64, fuse_ghost=False)
@@ -239,7 +214,7 @@ def _unpack16(blob, r, cout, cin):
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_weights_pack_from_the_reference_state_dict(tag):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     sd = _sd_of(tag)
     assert meta["damp"]["factor"] == {"yolov8s_ghost": 0.5, "yolov8n_ghost_p2": 0.5, "yolov8x_ghost": 0.25}[tag]
     assert sum(_damped(n, meta["damp"]["suffixes"]) for n in sd) == 2 * sum(n.endswith(".conv.2.cv1.bn.weight") for n in sd) > 0
@@ -251,7 +226,7 @@ def test_weights_pack_from_the_reference_state_dict(tag):
             return dict.__getitem__(self, k)
 
     for precision in ("fp16", "fp32x"):
-        plan = Plan(_cfg(meta), 1, 64, 64, precision=precision)
+        plan = Plan(cfg_of(meta), 1, 64, 64, precision=precision)
         blob = pack_plan_weights(plan, Recording(sd))
         assert set(synth_state_dict(plan)) == {n for n in sd if not n.endswith(".dfl.conv.weight") and not n.endswith("num_batches_tracked")}
         if precision != "fp16":
@@ -290,13 +265,13 @@ def test_weights_pack_from_the_reference_state_dict(tag):
         if tag == "yolov8x_ghost":  # C3Ghost(160): c_ = 80, halves of 20 channels on 24; C3Ghost(640): GhostConvs of 320 -> 80 and 160 -> 160
             a = plan.wrecs["model.2.m.0.conv.0.cv1"]
             assert a.rows == list(range(20)) + [-1] * 4 and (a.cout, a.cin) == (24, 80)
-            shapes = {(o["src0"].C, o["mid_c"]) for o in _kinds(plan, L.OP_GHOST)}
+            shapes = {(o["src0"].C, o["mid_c"]) for o in kinds(plan, L.OP_GHOST)}
             assert {(320, 80), (160, 160), (80, 24), (48, 40)} <= shapes
     assert {n for n in sd if n not in seen and not n.endswith("num_batches_tracked")} == {n for n in sd if n.endswith(".dfl.conv.weight")}
     gone = dict(sd)
     del gone[next(n for n in sd if _damped(n, meta["damp"]["suffixes"]))]
     with pytest.raises(KeyError):
-        pack_plan_weights(Plan(_cfg(meta), 1, 64, 64), gone)
+        pack_plan_weights(Plan(cfg_of(meta), 1, 64, 64), gone)
 
 
 def test_abi():
@@ -537,33 +512,7 @@ def test_ghost_op_refuses_what_is_not_supported(cin, ch):
 # the graphs
 # ------------------------------------------------------------------------------------------------------------
 def _engine(tag, precision, **kw):
-    from bs_yolo_amd.engine import YoloEngine
-    meta = _fixture(tag)[1]
-    return YoloEngine(_cfg(meta), _sd_of(tag), precision=precision, **kw)
-
-
-def _level_of_anchor(levels):
-    return np.concatenate([np.full(h * w, l) for l, (h, w) in enumerate(levels)])
-
-
-def _check_y(y, yref, strides, lvl, imgsz, precision, what):
-    """The project's parity bounds, stated once (module docstring)."""
-    es = np.abs(y[:, 4:4 + NC] - yref[:, 4:4 + NC]).max()
-    eb = np.abs(y[:, :4] - yref[:, :4]).max(axis=(0, 1))  # per anchor
-    per_level = [float(eb[lvl == l].max()) for l in range(len(strides))]
-    print(what, precision, f"score {es:.2e} box per level {['%.2e' % e for e in per_level]}")
-    if precision == "fp16":
-        assert es < 1e-2, (what, "score", es)
-        assert (eb < np.array([max(1.0, s / 32.0) for s in strides])[lvl]).all(), (what, "box", per_level)
-    else:
-        assert es <= 1e-3, (what, "score", es)
-        assert eb.max() <= 1e-3 * imgsz, (what, "box", per_level)
-
-
-def _check_raw(got, ref, precision, what):
-    e, mx = np.abs(got - ref).max(), np.abs(ref).max()
-    print(what, precision, f"err {e:.2e} of max {mx:.3f}")
-    assert got.shape == ref.shape and e <= (3e-2 if precision == "fp16" else 1e-3) * max(1.0, mx), (what, e, mx)
+    return engine(tag, precision, _damp, **kw)
 
 
 @gpu
@@ -573,43 +522,26 @@ def test_ghost_graph_matches_reference(tag, precision, monkeypatch):
     """y, the raw maps of every level and NMS at the fixture's conf, as test_yolov9.py compares them: on the fixture's own y the device
     NMS returns the fixture's rows; on the engine's y it is the oracle's NMS of that y bit for bit; in the fp32-storage modes the rows
     it keeps are the fixture's within the modes' bounds."""
-    from bs_yolo_amd import nms as HN
-    from oracle import postproc_ref as PP
     monkeypatch.delenv("BSY_FUSE_GHOST", raising=False)
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     kept = 0
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         y, raws = eng((x.half() if precision == "fp16" else x).to(DEV))
         torch.cuda.synchronize()
         plan = eng.plan_for(b, h, w, *(2 * [F16 if precision == "fp16" else F32]))[0]
-        assert bool(_kinds(plan, L.OP_GHOST)) == (precision == "fp16") and bool(_kinds(plan, L.OP_ADD)) == (precision != "fp16")
+        assert bool(kinds(plan, L.OP_GHOST)) == (precision == "fp16") and bool(kinds(plan, L.OP_ADD)) == (precision != "fp16")
         levels = [(h // int(s), w // int(s)) for s in meta["stride"]]
         assert tuple(y.shape) == (b, 4 + NC, sum(lh * lw for lh, lw in levels)) and len(raws) == len(levels)
         assert [tuple(r.shape) for r in raws] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
         yr = y.float().cpu().numpy()
         assert np.isfinite(yr).all()
-        _check_y(yr, z[f"y{si}"], meta["stride"], _level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}")
+        check_y(yr, z[f"y{si}"], meta["stride"], level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}", NC, Y_BOUNDS)
         assert si in meta["raw_shapes"]
         for l, r in enumerate(raws):
-            _check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}")
-        conf, iou = meta["nms_conf"], meta["nms_iou"]
-        pinned = HN.non_max_suppression(torch.from_numpy(z[f"y{si}"]).to(DEV), conf, iou, nc=NC)
-        mine = HN.non_max_suppression(y.float().clone(), conf, iou, nc=NC)  # (both convert xywh in place)
-        oracle = PP.non_max_suppression(y.float().cpu().clone(), conf, iou, nc=NC)
-        for bi in range(b):
-            want = z[f"nms{si}_{bi}"]
-            assert tuple(pinned[bi].shape) == want.shape and np.allclose(pinned[bi].cpu().numpy(), want, atol=1e-5, rtol=0), (tag, si, bi)
-            assert torch.equal(mine[bi].cpu(), oracle[bi]), (tag, si, bi)
-            if precision != "fp16":
-                g = mine[bi].cpu().numpy()
-                assert g.shape == want.shape, (tag, precision, si, bi, g.shape, want.shape)
-                if len(g):
-                    print(tag, precision, si, bi, f"nms rows {len(g)} box {np.abs(g[:, :4] - want[:, :4]).max():.2e} conf {np.abs(g[:, 4] - want[:, 4]).max():.2e}")
-                    assert np.abs(g[:, :4] - want[:, :4]).max() <= 1e-3 * max(h, w) and np.abs(g[:, 4] - want[:, 4]).max() <= 1e-3
-                    assert np.array_equal(g[:, 5], want[:, 5])
-            kept += len(want)
+            check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}", RAW_BOUNDS)
+        kept += check_nms(z, meta, si, y, b, h, w, precision, NC, what=tag)
     assert kept > 0
     eng.close()
 
@@ -618,52 +550,17 @@ def test_ghost_graph_matches_reference(tag, precision, monkeypatch):
 @pytest.mark.parametrize("tag", ["yolov8s_ghost", "yolov8n_ghost_p2"])
 def test_fusion_is_not_a_different_answer(tag, monkeypatch):
     """BSY_FUSE_GHOST = 0 and = 1 on the fp16 path: y and the raw maps are the same bits (torch.equal)."""
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     outs = {}
     for env in ("0", "1"):
         monkeypatch.setenv("BSY_FUSE_GHOST", env)
         eng = _engine(tag, "fp16")
-        outs[env] = []
-        for si, (b, h, w) in enumerate(meta["shapes"]):
-            y, raws = eng(_x(meta, si).half().to(DEV))
-            torch.cuda.synchronize()
+        outs[env] = outputs(eng, meta, F16)
+        for b, h, w in meta["shapes"]:
             plan = eng.plan_for(b, h, w, F16, F16)[0]
-            assert bool(_kinds(plan, L.OP_GHOST)) == (env == "1") and bool(_kinds(plan, L.OP_ADD)) == (env == "0")
-            outs[env].append([y.clone()] + [r.clone() for r in raws])
+            assert bool(kinds(plan, L.OP_GHOST)) == (env == "1") and bool(kinds(plan, L.OP_ADD)) == (env == "0")
         eng.close()
-    same = True
-    for si, (a, b) in enumerate(zip(outs["0"], outs["1"])):
-        for what, u, v in zip(["y"] + [f"raw{l}" for l in range(len(a) - 1)], a, b):  # every figure is printed before anything is asserted
-            d = (u.float() - v.float()).abs()
-            print(tag, "shape", si, what, f"differing {int((d > 0).sum())} of {d.numel()}, max {float(d.max()):.3e}")
-            same = same and torch.equal(u, v)
-    assert same, tag
-
-
-class RefModel(torch.nn.Module):
-    """Stand-in for the reference's DetectionModel (as test_yolov9.py's): `.yaml`, the reference's parameter names with the fixture's
-    values, and an original forward that only counts its calls."""
-
-    def __init__(self, cfg, sd):
-        super().__init__()
-        self.yaml = cfg
-        for name, t in sd.items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, torch.nn.Module())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked"):
-                mod.register_buffer(leaf, t.clone())
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
-        self.calls = 0
-        self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
+    assert all_equal(outs["0"], outs["1"], tag), tag
 
 
 @gpu
@@ -671,25 +568,25 @@ def test_accelerate_a_ghost_model(monkeypatch):
     from bs_yolo_amd import plugin
     monkeypatch.delenv("BSY_FUSE_GHOST", raising=False)
     tag = "yolov8n_ghost_p2"
-    z, meta = _fixture(tag)
-    m = RefModel(_cfg(meta), _sd_of(tag)).to(DEV)
+    z, meta = fixture(tag)
+    m = RefModel(cfg_of(meta), _sd_of(tag)).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 1)
+    x = x_of(meta, 1)
     b, h, w = meta["shapes"][1]
-    lvl = _level_of_anchor([(h // int(s), w // int(s)) for s in meta["stride"]])
+    lvl = level_of_anchor([(h // int(s), w // int(s)) for s in meta["stride"]])
     y, raws = m(x.to(DEV))  # fp32 input: the fp32x engine
     st = m._bsy_state
     assert m.calls == 0 and len(raws) == 4 and st["fp32_calls"] == 1 and st["support"] == {"fp16": True, "fp32": True}
-    _check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", f"accelerate {tag}")
+    check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", f"accelerate {tag}", NC, Y_BOUNDS)
     y16, raws16 = m(x.half().to(DEV))  # fp16 input: the product path, which is the engine's own output
     assert st["engine_calls"] == 1 and m.calls == 0
     eng = _engine(tag, "fp16")
     ye, re_ = eng(x.half().to(DEV))
     torch.cuda.synchronize()
     assert torch.equal(y16, ye) and all(torch.equal(a, c) for a, c in zip(raws16, re_))
-    assert _kinds(st["engine"].plan_for(b, h, w, F16, F16)[0], L.OP_GHOST)
-    _check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", f"accelerate {tag}")
+    assert kinds(st["engine"].plan_for(b, h, w, F16, F16)[0], L.OP_GHOST)
+    check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", f"accelerate {tag}", NC, Y_BOUNDS)
     for l, r in enumerate(raws16):
-        _check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} raw {l}")
+        check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} raw {l}", RAW_BOUNDS)
     eng.close()
     plugin.restore(m)

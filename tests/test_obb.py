@@ -15,28 +15,11 @@ from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, synth_state_dict
-from oracle.yolo_ref import synth_param
+from graph_helpers import RefModel, engine, fixture, state_dict, x_of
 
 DEV = "cuda:0"
 GRAPHS = ["yolo11n_obb", "yolov8n_obb"]
 HEAD = {"yolo11": 23, "yolov8": 22}  # index of the OBB layer
-
-
-def _fixture(tag):
-    z = np.load(GOLDEN / f"graph_{tag}.npz")
-    return z, json.loads(str(z["meta"]))
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
-
-
-def _sd(meta):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated."""
-    return {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
 
 
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
@@ -69,8 +52,8 @@ def test_detect_and_segment_plans_carry_no_angle():
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_obb_weights_pack_from_the_reference_state_dict(tag):
-    _, meta = _fixture(tag)
-    sd = _sd(meta)
+    _, meta = fixture(tag)
+    sd = state_dict(tag, None)
     seen = set()
 
     class Recording(dict):
@@ -122,9 +105,12 @@ def test_rotated_nms_and_obb_scale_are_declared_and_check_their_arguments():
 
 
 # ---- device ---------------------------------------------------------------------------------------------------------------
-def _engine(meta, precision):
-    from bs_yolo_amd.engine import YoloEngine
-    return YoloEngine(stock_cfg(meta["family"], meta["scale"], meta["nc"], "obb"), _sd(meta), precision=precision)
+def _cfg(meta):
+    return stock_cfg(meta["family"], meta["scale"], meta["nc"], "obb")
+
+
+def _engine(tag, precision):
+    return engine(tag, precision, None, cfg=_cfg(fixture(tag)[1]))
 
 
 TOL = {"fp16": (1e-2, 1.0, 2e-2), "fp32x": (1e-3, None, 1e-3), "fp32": (1e-3, None, 1e-3)}  # score, box (None: 1e-3 imgsz), angle
@@ -134,12 +120,12 @@ TOL = {"fp16": (1e-2, 1.0, 2e-2), "fp32x": (1e-3, None, 1e-3), "fp32": (1e-3, No
 @pytest.mark.parametrize("precision", ["fp16", "fp32x", "fp32"])
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_obb_graph_matches_reference(tag, precision):
-    z, meta = _fixture(tag)
-    eng = _engine(meta, precision)
+    z, meta = fixture(tag)
+    eng = _engine(tag, precision)
     nc = meta["nc"]
     ts, tb, ta = TOL[precision]
     for si in range(len(meta["shapes"])):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         xin = (x.half() if precision == "fp16" else x).to(DEV)
         y, (raws, angle) = eng(xin)
         y = y.clone()
@@ -168,9 +154,9 @@ def test_obb_graph_matches_reference(tag, precision):
 
 @pytest.mark.gpu
 def test_obb_graph_without_raw_maps_and_in_chunks(monkeypatch):
-    z, meta = _fixture("yolo11n_obb")
-    eng = _engine(meta, "fp32")
-    x = _x(meta, 1).to(DEV)
+    z, meta = fixture("yolo11n_obb")
+    eng = _engine("yolo11n_obb", "fp32")
+    x = x_of(meta, 1).to(DEV)
     y, (raws, angle) = eng(x, want_raw=False)
     assert raws == [None, None, None] and torch.equal(angle, y[:, -1:])
     y_full = y.clone()
@@ -260,7 +246,7 @@ def test_rotated_nms_matches_reference():
 def test_rotated_nms_on_the_graph_output_matches_reference():
     from bs_yolo_amd import nms as HN
     for tag in GRAPHS:
-        z, meta = _fixture(tag)
+        z, meta = fixture(tag)
         y = torch.from_numpy(z["y1"]).to(DEV)
         got = HN.non_max_suppression(y, meta["nms_conf"], meta["nms_iou"], nc=meta["nc"], rotated=True)
         for b, g in enumerate(got):
@@ -288,40 +274,14 @@ def test_obb_postprocess_matches_reference():
         assert not bad.any(), (ci, np.argwhere(bad)[:4], g[bad][:4], w[bad][:4])
 
 
-class OBBModel(torch.nn.Module):
-    """Stand-in for the reference's OBBModel: `.yaml`, the reference's parameter names with synthetic values, and an original forward
-    that only counts its calls (the engine must not reach it)."""
-
-    def __init__(self, meta):
-        super().__init__()
-        self.yaml = stock_cfg(meta["family"], meta["scale"], meta["nc"], "obb")
-        for name, t in _sd(meta).items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, torch.nn.Module())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked"):
-                mod.register_buffer(leaf, t.clone())
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
-        self.calls = 0
-        self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
-
-
 @pytest.mark.gpu
 def test_accelerate_obb_model_and_rotated_nms_hook():
     from bs_yolo_amd import nms as HN
     from bs_yolo_amd import plugin
-    z, meta = _fixture("yolo11n_obb")
-    m = OBBModel(meta).to(DEV)
+    z, meta = fixture("yolo11n_obb")
+    m = RefModel(_cfg(meta), state_dict("yolo11n_obb", None)).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 1).to(DEV)
+    x = x_of(meta, 1).to(DEV)
     y, (raws, angle) = m(x)  # fp32 input: the fp32x engine
     assert m.calls == 0 and len(raws) == 3
     nc = meta["nc"]

@@ -2,7 +2,6 @@
 plan, external slots, C ABI, decode / raw-map kernels, the fused head, host-side plumbing and the plugin hooks, against fixtures made
 by running the reference (tests/golden/make_p2p6_fixtures.py).  The P6 shapes put a 1 x 1 and a 2 x 3 map on the stride-64 level."""
 import ctypes as C
-import json
 import shutil
 import subprocess
 
@@ -10,14 +9,14 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, synth_state_dict
-from oracle.yolo_ref import synth_param
+from graph_helpers import RawBounds, RefModel, YBounds, cfg_of, check_raw, check_y, engine, fixture, level_of_anchor, state_dict, x_of
+from op_plan_helpers import DEV
 
-DEV = "cuda:0"
 GRAPHS = ["yolov8n_p2", "yolov8n_p6", "yolov5n_p6", "yolov8n_seg_p6"]
 DETECT = GRAPHS[:3]
 FAMILIES = ["yolov8-p2", "yolov8-p6", "yolov5-p6"]
@@ -25,30 +24,13 @@ STRIDES = {"yolov8-p2": [4, 8, 16, 32], "yolov8-p6": [8, 16, 32, 64], "yolov5-p6
 SHAPES = {"yolov8-p2": [(1, 64, 64), (2, 96, 128)], "yolov8-p6": [(1, 64, 64), (2, 128, 192)], "yolov5-p6": [(1, 64, 64), (2, 128, 192)]}
 ANCHORS = {"yolov8-p2": [340, 1020], "yolov8-p6": [85, 510], "yolov5-p6": [85, 510]}
 NC = 12
-_CACHE = {}
-
-
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
-
-
-def _sd(meta):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated."""
-    return {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-
-
-def _cfg(meta):
-    return stock_cfg(meta["family"], meta["scale"], meta["nc"], meta["task"])
+# The project's parity bounds (test_obb.py TOL, README).  fp32 / fp32x: score <= 1e-3, box <= 1e-3 imgsz.  fp16: score < 1e-2, box the
+# project's 1 px at stride 32 restated per level as stride / 32 px -- the error is a DFL distance in grid units times the stride -- so
+# 2 px on a stride-64 level and 1 px on every other.  Raw maps: 3e-2 (fp16) or 1e-3 of max(1, maximum).
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=None, box16=1.0, score32=1e-3, box32=1e-3)
+RAW_BOUNDS = RawBounds(rel16=3e-2, strict16=False, floor16=True, rel32=1e-3)
+# mask coefficients and prototypes: the bounds test_gpu_parity.py holds the three-level Segment graphs to
+MASK_BOUNDS = RawBounds(rel16=2e-2, strict16=True, floor16=False, rel32=1e-3)
 
 
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
@@ -116,9 +98,9 @@ def _ext_roles(plan):
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_external_slots_are_distinct(tag):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     for kw in ({}, {"fuse_head": False}, {"precision": "fp32"}):
-        roles = _ext_roles(Plan(_cfg(meta), 1, 64, 64, **kw))
+        roles = _ext_roles(Plan(cfg_of(meta), 1, 64, 64, **kw))
         assert all(len(r) == 1 for r in roles.values()), roles  # no two external views share a slot
         by_role = {next(iter(r)): s for s, r in roles.items()}
         want = {"image", "y"} | {("raw", l) for l in range(4)} | ({"proto"} if meta["task"] == "segment" else set())
@@ -132,8 +114,8 @@ def test_external_slots_are_distinct(tag):
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_weights_pack_from_the_reference_state_dict(tag):
-    _, meta = _fixture(tag)
-    sd = _sd(meta)
+    _, meta = fixture(tag)
+    sd = state_dict(tag, None)
     seen = set()
 
     class Recording(dict):
@@ -142,7 +124,7 @@ def test_weights_pack_from_the_reference_state_dict(tag):
             return dict.__getitem__(self, k)
 
     for precision in ("fp16", "fp32x"):
-        pack_plan_weights(Plan(_cfg(meta), 1, 64, 64, precision=precision), Recording(sd))  # a missing key raises KeyError
+        pack_plan_weights(Plan(cfg_of(meta), 1, 64, 64, precision=precision), Recording(sd))  # a missing key raises KeyError
     branches = ("cv2", "cv3", "cv4") if meta["task"] == "segment" else ("cv2", "cv3")
     fourth = {n for n in sd if any(f".{b}.3." in n for b in branches) and not n.endswith("num_batches_tracked")}
     assert len(fourth) == len(branches) * (2 * 5 + 2) and fourth <= seen
@@ -164,9 +146,9 @@ def test_c_ops_carry_four_levels():
 def test_graph_support_and_what_is_refused():
     from bs_yolo_amd.plugin import graph_support, max_stride
     for tag in GRAPHS:
-        _, meta = _fixture(tag)
-        assert graph_support(_cfg(meta)) == {"fp16": True, "fp32": True}
-        assert max_stride(_cfg(meta)) == max(STRIDES[meta["family"]])
+        _, meta = fixture(tag)
+        assert graph_support(cfg_of(meta)) == {"fp16": True, "fp32": True}
+        assert max_stride(cfg_of(meta)) == max(STRIDES[meta["family"]])
     assert max_stride(stock_cfg("yolo11", "n")) == 32
     five = stock_cfg("yolov8-p6", "n", NC, "detect")
     five["head"][-1] = [[20, 23, 26, 29, 29], 1, "Detect", ["nc"]]
@@ -199,41 +181,19 @@ def test_header_declares_the_level_count(tmp_path):
 
 
 # ---- device ---------------------------------------------------------------------------------------------------------------
-def _engine(meta, precision, **kw):
-    from bs_yolo_amd.engine import YoloEngine
-    return YoloEngine(_cfg(meta), _sd(meta), precision=precision, **kw)
-
-
-def _level_of_anchor(levels):
-    return np.concatenate([np.full(h * w, l) for l, (h, w) in enumerate(levels)])
-
-
-def _check_y(y, yref, strides, lvl, imgsz, precision, what):
-    """The project's parity bounds (test_obb.py TOL, README).  fp32 / fp32x: score <= 1e-3, box <= 1e-3 imgsz.  fp16: score < 1e-2, box
-    the project's 1 px at stride 32 restated per level as stride / 32 px -- the error is a DFL distance in grid units times the
-    stride -- so 2 px on a stride-64 level and 1 px on every other."""
-    es = np.abs(y[:, 4:4 + NC] - yref[:, 4:4 + NC]).max()
-    eb = np.abs(y[:, :4] - yref[:, :4]).max(axis=(0, 1))  # per anchor
-    per_level = [float(eb[lvl == l].max()) for l in range(len(strides)) if (lvl == l).any()]
-    print(what, precision, f"score {es:.2e} box per level {['%.2e' % e for e in per_level]}")
-    if precision == "fp16":
-        assert es < 1e-2, (what, "score", es)
-        bound = np.array([max(1.0, s / 32.0) for s in strides])[lvl]
-        assert (eb < bound).all(), (what, "box", per_level)
-    else:
-        assert es <= 1e-3, (what, "score", es)
-        assert eb.max() <= 1e-3 * imgsz, (what, "box", per_level)
+def _engine(tag, precision, **kw):
+    return engine(tag, precision, None, **kw)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("precision", ["fp16", "fp32x", "fp32"])
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_four_level_graph_matches_reference(tag, precision):
-    z, meta = _fixture(tag)
-    eng = _engine(meta, precision)
+    z, meta = fixture(tag)
+    eng = _engine(tag, precision)
     seg = meta["task"] == "segment"
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         xin = (x.half() if precision == "fp16" else x).to(DEV)
         y, aux = eng(xin)
         raws = aux[0] if seg else aux
@@ -248,21 +208,14 @@ def test_four_level_graph_matches_reference(tag, precision):
         assert tuple(y1.shape) == (b, 4 + NC + (32 if seg else 0), A) and len(r1) == 4
         assert [tuple(r.shape) for r in r1] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
         yr, yref = y1.float().cpu().numpy(), z[f"y{si}"]
-        _check_y(yr, yref, meta["stride"], _level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}")
+        check_y(yr, yref, meta["stride"], level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}", NC, Y_BOUNDS)
         if si in meta["raw_shapes"]:
             for l, r in enumerate(r1):
-                rr = z[f"raw{si}_{l}"]
-                rel = 3e-2 if precision == "fp16" else 1e-3
-                assert np.abs(r.float().cpu().numpy() - rr).max() <= rel * max(1.0, np.abs(rr).max()), (tag, precision, si, "raw", l)
-        if seg:  # the bounds test_gpu_parity.py holds the three-level Segment graphs to
+                check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}", RAW_BOUNDS)
+        if seg:
             assert torch.equal(aux[1], y[:, 4 + NC:]) and torch.equal(p1, aux2[2])
-            mref, pref = z[f"mc{si}"], z[f"proto{si}"]
-            em, ep = np.abs(yr[:, 4 + NC:] - mref).max(), np.abs(p1.float().cpu().numpy() - pref).max()
-            assert tuple(p1.shape) == pref.shape
-            if precision == "fp16":
-                assert em < 2e-2 * np.abs(mref).max() and ep < 2e-2 * np.abs(pref).max(), (tag, si, em, ep)
-            else:
-                assert em <= 1e-3 * max(1.0, np.abs(mref).max()) and ep <= 1e-3 * max(1.0, np.abs(pref).max()), (tag, si, em, ep)
+            check_raw(yr[:, 4 + NC:], z[f"mc{si}"], precision, f"{tag} shape {si} mc", MASK_BOUNDS)
+            check_raw(p1.float().cpu().numpy(), z[f"proto{si}"], precision, f"{tag} shape {si} proto", MASK_BOUNDS)
     eng.close()
 
 
@@ -271,10 +224,10 @@ def test_four_level_graph_matches_reference(tag, precision):
 def test_fused_head_is_not_a_different_answer(tag):
     """fp16 path: the fused head (default), the same untuned, and the decode launch return the same bits (for heads of four levels the
     decode kernel sums the DFL in the fused epilogue's order, csrc/detect.hip HALVES)."""
-    _, meta = _fixture(tag)
-    engines = [_engine(meta, "fp16"), _engine(meta, "fp16", autotune=False), _engine(meta, "fp16", fuse_head=False)]
+    _, meta = fixture(tag)
+    engines = [_engine(tag, "fp16"), _engine(tag, "fp16", autotune=False), _engine(tag, "fp16", fuse_head=False)]
     for si in range(len(meta["shapes"])):
-        x = _x(meta, si).half().to(DEV)
+        x = x_of(meta, si).half().to(DEV)
         outs = [e(x) for e in engines]
         torch.cuda.synchronize()
         plans = [e.plan_for(x.shape[0], x.shape[2], x.shape[3], x.dtype, x.dtype)[0] for e in engines]
@@ -291,13 +244,13 @@ def test_fused_head_is_not_a_different_answer(tag):
 def test_head_lanes_hold_four_levels(tag, precision, monkeypatch):
     """Every (level, branch) chain on a stream of its own -- 2 x 4 lanes for Detect, 3 x 4 for Segment -- joined before the raw outputs:
     the bits of the serial schedule."""
-    _, meta = _fixture(tag)
-    x = _x(meta, 1).half().to(DEV)
+    _, meta = fixture(tag)
+    x = x_of(meta, 1).half().to(DEV)
     monkeypatch.setenv("BSY_LANES", "0")
-    serial = _engine(meta, precision)
+    serial = _engine(tag, precision)
     y0, aux0 = serial(x)
     monkeypatch.setenv("BSY_LANES", "1")
-    eng = _engine(meta, precision)
+    eng = _engine(tag, precision)
     plan = eng.plan_for(x.shape[0], x.shape[2], x.shape[3], x.dtype, x.dtype)[0]
     assert len({o.get("lane", 0) for o in plan.ops} - {0}) == (3 * 4 - 1 if meta["task"] == "segment" else 2 * 4 - 1)
     for _ in range(2):
@@ -313,11 +266,11 @@ def test_head_lanes_hold_four_levels(tag, precision, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag", ["yolov8n_p2", "yolov8n_seg_p6"])
 def test_without_raw_maps_and_in_chunks(tag, monkeypatch):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     seg = meta["task"] == "segment"
     for precision in ("fp16", "fp32"):
-        eng = _engine(meta, precision)
-        x = _x(meta, 1)
+        eng = _engine(tag, precision)
+        x = x_of(meta, 1)
         x = (x.half() if precision == "fp16" else x).to(DEV)
         y_full, aux_full = eng(x)
         y_full = y_full.clone()
@@ -339,7 +292,7 @@ def test_nms_on_the_graph_outputs_matches_reference():
     from bs_yolo_amd import nms as HN
     total = 0
     for tag in GRAPHS:
-        z, meta = _fixture(tag)
+        z, meta = fixture(tag)
         for si in range(len(meta["shapes"])):
             got = HN.non_max_suppression(torch.from_numpy(z[f"y{si}"]).to(DEV), meta["nms_conf"], meta["nms_iou"], nc=NC)
             assert len(got) == meta["shapes"][si][0]
@@ -354,9 +307,9 @@ def test_nms_on_the_graph_outputs_matches_reference():
 @pytest.mark.parametrize("precision", ["fp16", "fp32x", "fp32"])
 def test_augment_on_a_p6_graph_matches_reference(precision):
     from bs_yolo_amd import tta as T
-    z, meta = _fixture("yolov8n_p6")
-    eng = _engine(meta, precision)
-    x = _x(meta, 1)
+    z, meta = fixture("yolov8n_p6")
+    eng = _engine("yolov8n_p6", precision)
+    x = x_of(meta, 1)
     b, h, w = meta["shapes"][1]
     y, aux = eng((x.half() if precision == "fp16" else x).to(DEV), augment=True)
     torch.cuda.synchronize()
@@ -365,49 +318,23 @@ def test_augment_on_a_p6_graph_matches_reference(precision):
     # the level of every merged anchor: each pass's window of its own levels (gs = 64: all three passes run at 128 x 192)
     lvl = []
     for p in eng.tta_geometry(h, w):
-        lv = _level_of_anchor([(p.padded[0] // int(s), p.padded[1] // int(s)) for s in meta["stride"]])
+        lv = level_of_anchor([(p.padded[0] // int(s), p.padded[1] // int(s)) for s in meta["stride"]])
         lvl.append(lv[p.window[0]:p.window[1]])
     lvl = np.concatenate(lvl)
     assert len(lvl) == want.shape[-1] and [p.padded for p in eng.tta_geometry(h, w)] == [(128, 192)] * 3
     assert [p.window for p in eng.tta_geometry(h, w)] == T.reference_windows([510] * 3, 4)
-    _check_y(y.float().cpu().numpy(), want, meta["stride"], lvl, max(h, w), precision, "augment")
+    check_y(y.float().cpu().numpy(), want, meta["stride"], lvl, max(h, w), precision, "augment", NC, Y_BOUNDS)
     eng.close()
-
-
-class RefModel(torch.nn.Module):
-    """Stand-in for the reference's DetectionModel: `.yaml`, the reference's parameter names with synthetic values, and an original
-    forward that only counts its calls."""
-
-    def __init__(self, meta):
-        super().__init__()
-        self.yaml = _cfg(meta)
-        for name, t in _sd(meta).items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, torch.nn.Module())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked"):
-                mod.register_buffer(leaf, t.clone())
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
-        self.calls = 0
-        self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag", ["yolov8n_p2", "yolov8n_p6"])
 def test_accelerate_a_four_level_model(tag):
     from bs_yolo_amd import plugin
-    z, meta = _fixture(tag)
-    m = RefModel(meta).to(DEV)
+    z, meta = fixture(tag)
+    m = RefModel(cfg_of(meta), state_dict(tag, None)).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 1).to(DEV)
+    x = x_of(meta, 1).to(DEV)
     y, raws = m(x)  # fp32 input: the fp32x engine
     assert m.calls == 0 and len(raws) == 4 and m._bsy_state["fp32_calls"] == 1
     yr = y.cpu().numpy()
@@ -427,10 +354,10 @@ def test_accelerate_a_four_level_model(tag):
 @pytest.mark.parametrize("tag", ["yolov8n_p2", "yolov5n_p6"])
 def test_stand_alone_decode_on_four_levels(tag):
     from bs_yolo_amd import ops as O
-    z, meta = _fixture(tag)
-    eng = _engine(meta, "fp32")
+    z, meta = fixture(tag)
+    eng = _engine(tag, "fp32")
     b, h, w = meta["shapes"][0]
-    y, raws = eng(_x(meta, 0).to(DEV))
+    y, raws = eng(x_of(meta, 0).to(DEV))
 
     def split(maps):
         maps = [m.to(DEV).float().permute(0, 2, 3, 1) for m in maps]
@@ -467,7 +394,7 @@ class Detect(torch.nn.Module):
 @pytest.mark.gpu
 def test_per_module_detect_hook_takes_four_levels():
     from bs_yolo_amd import plugin
-    z, meta = _fixture("yolov8n_p6")
+    z, meta = fixture("yolov8n_p6")
     head = Detect(meta["stride"]).eval()
     model = torch.nn.Sequential(head)
     assert plugin.install(model) == 1
@@ -484,8 +411,7 @@ def test_sliced_inference_admits_native_tiles_by_the_models_stride():
     """Slices of 96 px are multiples of 32 but not of a P6 graph's stride 64: they take the letterbox route (imgsz 640), not the native
     one (which the engine would refuse); 128-px slices run natively.  The full-image pass is padded to a multiple of 64."""
     from bs_yolo_amd import sahi as HS
-    _, meta = _fixture("yolov8n_p6")
-    eng = _engine(meta, "fp16", autotune=False)
+    eng = _engine("yolov8n_p6", "fp16", autotune=False)
     assert eng.max_stride == 64 and eng.nl == 4
     seen = []
     model = lambda t, want_raw=False: (seen.append(tuple(t.shape[2:])), eng(t, want_raw=False))[1]  # noqa: E731

@@ -2,21 +2,18 @@
 decode launch (csrc/detect.hip, DEC_KPT) alone and inside the graphs, the engine's (y, (raws, kpt)) output and plugin.accelerate --
 against fixtures made by running the reference (tests/golden/make_pose_graph_fixtures.py)."""
 import ctypes
-import functools
-import json
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, synth_state_dict
+from graph_helpers import fixture, state_dict, x_of
 from op_plan_helpers import NAN, POISON16, POISON32, bits, new_op, poisoned, run_op, view
 from oracle import postproc_ref as PP
-from oracle.yolo_ref import synth_param
 
 DEV = "cuda:0"
 GRAPHS = ["yolo11n_pose", "yolov8n_pose", "yolo11n_pose_k5", "yolo11m_pose", "yolov8n_pose_p6"]
@@ -27,32 +24,13 @@ YOLO11S_KINDS = [8, 18, 1, 1, 9, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
                  1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 16, 16, 1, 1, 1, 16, 16, 1, 1, 1, 2, 1, 16, 1]
 
 
-@functools.lru_cache(maxsize=None)
-def _fixture(tag):
-    z = np.load(GOLDEN / f"graph_{tag}.npz")
-    return {k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"]))
-
-
 def _cfg(meta):
     return stock_cfg(meta["family"], meta["scale"], meta["nc"], "pose", kpt_shape=tuple(meta["kpt_shape"]))
 
 
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def _sd_cached(tag):
-    meta = _fixture(tag)[1]
-    return {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-
-
 def _sd(tag):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated once per graph."""
-    return dict(_sd_cached(tag))
+    """A copy of the reference's un-fused state dict (no damping rule), for the callers that add or drop keys."""
+    return dict(state_dict(tag, None))
 
 
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
@@ -64,7 +42,7 @@ def _parsed(layers):
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_stock_cfg_restates_the_pose_yaml(tag):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     cfg, want = _cfg(meta), meta["yaml"]  # yaml.safe_load of the reference's file, recorded by make_pose_graph_fixtures.py
     assert cfg["scales"] == want["scales"] and cfg["backbone"] == _parsed(want["backbone"]) and cfg["head"] == _parsed(want["head"])
     assert cfg["head"][-1][2:] == ["Pose", ["nc", "kpt_shape"]] and want["kpt_shape"] == [17, 3]
@@ -157,7 +135,7 @@ def test_pose_plan_refusals():
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_pose_weights_pack_from_the_reference_state_dict(tag):
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     sd = _sd(tag)
     seen = set()
 
@@ -310,7 +288,7 @@ def test_decode_keypoint_mode_refuses_bad_arguments():
 # ---- device: the graphs against the reference ---------------------------------------------------------------------------------
 def _engine(tag, precision, **kw):
     from bs_yolo_amd.engine import YoloEngine
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     return YoloEngine(_cfg(meta), _sd(tag), bn_eps=meta["bn_eps"], precision=precision, **kw)
 
 
@@ -324,10 +302,10 @@ KPT_XY_FP16 = 0.9158  # measured 9.157410e-01 (yolo11n_pose, the (2, 96, 128) in
 def _graph_errors(tag, precision, eng, si):
     """One input through the engine: the structural identities asserted, the errors against the fixture returned."""
     from bs_yolo_amd import ops as O
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     nc, (nkpt, kdim) = meta["nc"], meta["kpt_shape"]
     nk = nkpt * kdim
-    x = _x(meta, si)
+    x = x_of(meta, si)
     xin = (x.half() if precision == "fp16" else x).to(DEV)
     y, (raws, kpt) = eng(xin)
     y, kpt = y.clone(), kpt.clone()
@@ -361,7 +339,7 @@ def _graph_errors(tag, precision, eng, si):
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_pose_graph_matches_reference(tag, precision):
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     eng = _engine(tag, precision)
     assert eng.task == "pose" and eng.meta["nk"] == meta["kpt_shape"][0] * meta["kpt_shape"][1] and eng.nl == len(meta["stride"])
     ts, tb = TOL[precision]
@@ -382,9 +360,9 @@ def test_pose_graph_matches_reference(tag, precision):
 @pytest.mark.gpu
 def test_pose_graph_without_raw_outputs_and_in_chunks(monkeypatch):
     tag = "yolo11n_pose"
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     eng = _engine(tag, "fp32")
-    x = _x(meta, 1).to(DEV)
+    x = x_of(meta, 1).to(DEV)
     y, (raws, kpt) = eng(x)
     y_full, kpt_full, raw_full = y.clone(), kpt.clone(), [r.clone() for r in raws]
     yn, (rn, kn) = eng(x, want_raw=False)
@@ -407,8 +385,8 @@ def test_pose_graph_without_raw_outputs_and_in_chunks(monkeypatch):
 @pytest.mark.gpu
 def test_pose_graph_mode_replays_the_eager_bits():
     tag = "yolo11n_pose"
-    meta = _fixture(tag)[1]
-    xin = _x(meta, 1).half().to(DEV)
+    meta = fixture(tag)[1]
+    xin = x_of(meta, 1).half().to(DEV)
     plain = _engine(tag, "fp16", autotune=False)
     y, (raws, kpt) = plain(xin)
     y, kpt, raws = y.clone(), kpt.clone(), [r.clone() for r in raws]
@@ -436,11 +414,11 @@ def test_nms_on_the_pose_graph_output_matches_the_oracle():
     """The nk keypoint rows ride through bsy_nms as extra columns: on the fp32 engine's own y the device rows are the oracle's."""
     from bs_yolo_amd import nms as HN
     tag = "yolo11n_pose"
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     nk = meta["kpt_shape"][0] * meta["kpt_shape"][1]
     eng = _engine(tag, "fp32")
     for si in range(len(meta["shapes"])):
-        y, _ = eng(_x(meta, si).to(DEV), want_raw=False)
+        y, _ = eng(x_of(meta, si).to(DEV), want_raw=False)
         ref = PP.non_max_suppression(y.cpu().clone(), meta["nms_conf"], meta["nms_iou"], nc=meta["nc"])
         det, counts = HN.nms_batched(y.clone(), meta["nms_conf"], meta["nms_iou"], nc=meta["nc"])
         torch.cuda.synchronize()
@@ -459,7 +437,7 @@ class PoseModel(torch.nn.Module):
 
     def __init__(self, tag):
         super().__init__()
-        meta = _fixture(tag)[1]
+        meta = fixture(tag)[1]
         self.yaml = _cfg(meta)
         for name, t in _sd(tag).items():
             mod = self
@@ -485,11 +463,11 @@ class PoseModel(torch.nn.Module):
 def test_accelerate_pose_model():
     from bs_yolo_amd import plugin
     tag = "yolo11n_pose"
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     nc = meta["nc"]
     m = PoseModel(tag).to(DEV)
     assert plugin.accelerate(m) is m
-    x = _x(meta, 1).to(DEV)
+    x = x_of(meta, 1).to(DEV)
     y, (raws, kpt) = m(x)  # fp32 input: the fp32x engine
     torch.cuda.synchronize()
     assert m.calls == 0 and m._bsy_state["fp32_calls"] == 1 and len(raws) == 3 and y.dtype == torch.float32

@@ -27,7 +27,6 @@ max(1, maximum)).  The reference's own fp16 run is within half of the fp16 bound
 """
 import ctypes as C
 import copy
-import json
 import math
 import re
 from functools import lru_cache
@@ -41,8 +40,8 @@ from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan, WRec
 from bs_yolo_amd import weights as Wt
+from graph_helpers import RawBounds, RefModel, YBounds, cfg_of, check_raw, check_y, fixture, kinds, level_of_anchor, outputs, state_dict, x_of
 from op_plan_helpers import DEV, NAN, POISON16, POISON32, U, assert_outside_views_intact, bits, new_op, poisoned, poisoned_blob, run_ops, ulp16, ulp32, view
-from oracle.yolo_ref import synth_param
 
 gpu = pytest.mark.gpu
 ROOT = GOLDEN.parent.parent
@@ -53,21 +52,9 @@ SCALES = ["n", "s", "m", "l", "x"]
 PRECISIONS = ["fp16", "fp32x", "fp32"]
 ATTN = (12, 15, 18, 21)
 HEADS = {"n": [2, 1, 2, 4], "s": [4, 2, 4, 8], "m": [6, 3, 6, 9]}
-_CACHE = {}
-
-
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
+# fp16: score < 1e-2, box < max(1, stride / 32) px per level, raw maps 3e-2 of max(1, maximum); fp32 / fp32x: 1e-3 and 1e-3 * imgsz
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=None, box16=1.0, score32=1e-3, box32=1e-3)
+RAW_BOUNDS = RawBounds(rel16=3e-2, strict16=False, floor16=True, rel32=1e-3)
 
 
 @lru_cache(maxsize=None)
@@ -75,7 +62,7 @@ def _texts():
     """The two text sets of make_world_fixtures.py: 12 unit rows from seed 7, 5 from seed 8."""
     t1 = torch.nn.functional.normalize(torch.randn(1, NC, E, generator=torch.Generator().manual_seed(7)), dim=-1)
     t2 = torch.nn.functional.normalize(torch.randn(1, NC2, E, generator=torch.Generator().manual_seed(8)), dim=-1)
-    for t, want in zip((t1, t2), _fixture(GRAPHS[0])[1]["txt"]):
+    for t, want in zip((t1, t2), fixture(GRAPHS[0])[1]["txt"]):
         assert abs(float(t.double().sum()) - want["sum"]) < 1e-9 * t.numel() and t.flatten()[:8].tolist() == want["first"]
     return t1, t2
 
@@ -84,26 +71,19 @@ def _hit(name, rule):  # make_world_fixtures.py's `hit`
     return rule["contains"] in name and name.endswith(rule["suffix"]) and not name.endswith("norm.bias")
 
 
-@lru_cache(maxsize=None)
+def _damp(name, meta):
+    """The factor the generator wrote into meta["damp"] for this name (its rules apply in turn; no two hit the same name)."""
+    factors = [rule["factor"] for rule in meta["damp"] if _hit(name, rule)]
+    assert len(factors) <= 1, name
+    return factors[0] if factors else 1.0
+
+
 def _sd_of(tag):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated from synth_param and multiplied by the
-    factors the generator wrote into meta["damp"]."""
-    meta = _fixture(tag)[1]
-    sd = {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
+    """state_dict under the generator's rules, each of which must hit something."""
+    meta = fixture(tag)[1]
     for rule in meta["damp"]:
-        hits = [n for n in sd if _hit(n, rule)]
-        assert hits, rule
-        for n in hits:
-            sd[n] = sd[n] * rule["factor"]
-    return sd
-
-
-def _cfg(meta, nc=None):
-    return stock_cfg(meta["family"], meta["scale"], meta["nc"] if nc is None else nc, meta["task"])
-
-
-def _kinds(plan, kind):
-    return [o for o in plan.ops if o["kind"] == kind]
+        assert any(_hit(n, rule) for n, _ in meta["names"]), rule
+    return state_dict(tag, _damp)
 
 
 def _hw(dtype):
@@ -114,7 +94,7 @@ def _hw(dtype):
 @pytest.mark.parametrize("scale", SCALES)
 def test_stock_cfg_is_the_reference_yaml(scale):
     for tag in GRAPHS:
-        want = dict(_fixture(tag)[1]["yaml"])
+        want = dict(fixture(tag)[1]["yaml"])
         assert [l[3] for l in want["head"] if l[2] == "nn.Upsample"][0] == ["None", 2, "nearest"]  # yaml's string; parse_model evaluates it (tasks.py:981-985)
         want["head"] = [[f, n, m, [None if a == "None" else a for a in args]] for f, n, m, args in want["head"]]
         assert want["nc"] == 80 and "scale" not in want and want["head"][-1][2] == "WorldDetect"
@@ -148,7 +128,7 @@ def test_world_plans(scale, precision):
         A = sum(lh * lw for lh, lw in m["levels"])
         assert plan.outputs["y"].shape == (2, 4 + nc, A)
         assert [plan.outputs[f"raw{l}"].shape for l in range(3)] == [(2, 64 + nc, lh, lw) for lh, lw in m["levels"]]
-        ms = _kinds(plan, L.OP_MAXSIG)
+        ms = kinds(plan, L.OP_MAXSIG)
         assert len(ms) == 4 and [o["name"] for o in ms] == [f"model.{i}.attn" for i in ATTN]
         for o, i in zip(ms, ATTN):
             prev = plan.ops[plan.ops.index(o) - 1]
@@ -181,7 +161,7 @@ def test_fixture_plans_flops_and_weight_names():
     parameter name the reference's model holds but the DFL conv and num_batches_tracked, un-fused and after fuse()-style folding alike."""
     t1, _ = _texts()
     for tag in GRAPHS:
-        meta = _fixture(tag)[1]
+        meta = fixture(tag)[1]
         sd = _sd_of(tag)
         assert meta["heads"] == HEADS[meta["scale"]] and meta["hc"] == [32] * 4 and meta["n"] == [2 if meta["scale"] == "m" else 1] * 4
         assert meta["bn_eps"] == Wt.BN_EPS and meta["stride"] == [8.0, 16.0, 32.0]
@@ -200,10 +180,10 @@ def test_fixture_plans_flops_and_weight_names():
         assert len(fused) < len(sd) and "model.12.attn.proj_conv.bn.weight" in fused and "model.0.bn.weight" not in fused
         for precision in PRECISIONS:
             for si, (b, h, w) in enumerate(meta["shapes"]):
-                plan = Plan(_cfg(meta), b, h, w, precision=precision)
+                plan = Plan(cfg_of(meta), b, h, w, precision=precision)
                 dense = sum(o.get("mfma_flops", 0) for o in plan.ops if o["kind"] != L.OP_MAXSIG)
                 assert abs(dense - meta["conv_flops"][si]) <= 0.01 * meta["conv_flops"][si], (tag, precision, si, dense, meta["conv_flops"][si])
-                gate = sum(2 * b * o["H"] * o["W"] * o["src0"].C * NC for o in _kinds(plan, L.OP_MAXSIG))
+                gate = sum(2 * b * o["H"] * o["W"] * o["src0"].C * NC for o in kinds(plan, L.OP_MAXSIG))
                 assert plan.flops >= dense + gate
             skip = lambda n: n.endswith(".dfl.conv.weight") or n.endswith("num_batches_tracked")  # noqa: E731
             blobs = []
@@ -215,7 +195,7 @@ def test_fixture_plans_flops_and_weight_names():
                         seen.add(k)
                         return dict.__getitem__(self, k)
 
-                plan = Plan(_cfg(meta), 1, 64, 64, precision=precision)
+                plan = Plan(cfg_of(meta), 1, 64, 64, precision=precision)
                 blobs.append(Wt.pack_plan_weights(plan, Recording(dict(form, txt_feats=t1))))
                 assert seen == {n for n in form if not skip(n)} | {"txt_feats"}, (tag, precision, sorted(seen ^ {n for n in form if not skip(n)})[:6])
                 assert len(plan.c_ops()) == len(plan.ops)
@@ -277,7 +257,7 @@ def test_refusals():
     with pytest.raises(NotImplementedError, match=r"model\.15: C2fAttn heads of hc = 8 channels are not on the fp16 path"):
         Plan(c, 1, 64, 64)
     p = Plan(c, 1, 64, 64, precision="fp32")
-    assert [(o["heads"], o["head_dim"]) for o in _kinds(p, L.OP_MAXSIG)][1] == (4, 8) and graph_support(c) == {"fp16": False, "fp32": True}
+    assert [(o["heads"], o["head_dim"]) for o in kinds(p, L.OP_MAXSIG)][1] == (4, 8) and graph_support(c) == {"fp16": False, "fp32": True}
     c["head"][5][3] = [256, 128, 12]  # 3 heads on 32 channels
     with pytest.raises(NotImplementedError, match=r"model\.15: C2fAttn with 3 heads on 32 channels"):
         Plan(c, 1, 64, 64, precision="fp32")
@@ -608,32 +588,7 @@ def test_ops_maxsig_attn_wrapper():
 # ------------------------------------------------------------------------------------------------------------
 def _engine(tag, precision, txt=None, **kw):
     from bs_yolo_amd.engine import YoloEngine
-    meta = _fixture(tag)[1]
-    return YoloEngine(_cfg(meta), _sd_of(tag), precision=precision, txt_feats=_texts()[0] if txt is None else txt, **kw)
-
-
-def _level_of_anchor(levels):
-    return np.concatenate([np.full(h * w, l) for l, (h, w) in enumerate(levels)])
-
-
-def _check_y(y, yref, strides, lvl, imgsz, precision, what):
-    """fp16: score < 1e-2, box < max(1, stride / 32) px per level; fp32 / fp32x: 1e-3 and 1e-3 * imgsz."""
-    es = float(np.abs(y[:, 4:] - yref[:, 4:]).max())
-    eb = np.abs(y[:, :4] - yref[:, :4]).max(axis=(0, 1))
-    per_level = [float(eb[lvl == l].max()) for l in range(len(strides))]
-    print(what, precision, f"score max {es:.2e} box per level {['%.2e' % e for e in per_level]}")
-    if precision == "fp16":
-        assert es < 1e-2, (what, "score", es)
-        assert (eb < np.array([max(1.0, s / 32.0) for s in strides])[lvl]).all(), (what, "box", per_level)
-    else:
-        assert es <= 1e-3, (what, "score", es)
-        assert eb.max() <= 1e-3 * imgsz, (what, "box", per_level)
-
-
-def _check_raw(got, ref, precision, what):
-    e, mx = np.abs(got - ref).max(), np.abs(ref).max()
-    print(what, precision, f"err {e:.2e} of max {mx:.3f}")
-    assert got.shape == ref.shape and e <= (3e-2 if precision == "fp16" else 1e-3) * max(1.0, mx), (what, e, mx)
+    return YoloEngine(cfg_of(fixture(tag)[1]), _sd_of(tag), precision=precision, txt_feats=_texts()[0] if txt is None else txt, **kw)
 
 
 def _compare(eng, z, meta, precision, nc, ykey, rawkey, what, nms=True):
@@ -641,19 +596,19 @@ def _compare(eng, z, meta, precision, nc, ykey, rawkey, what, nms=True):
     from oracle import postproc_ref as PP
     kept = 0
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         y, raws = eng((x.half() if precision == "fp16" else x).to(DEV))
         torch.cuda.synchronize()
         plan = eng.plan_for(b, h, w, *(2 * [_hw(precision)]))[0]
-        assert len(_kinds(plan, L.OP_MAXSIG)) == 4 and plan.meta["nc"] == nc
+        assert len(kinds(plan, L.OP_MAXSIG)) == 4 and plan.meta["nc"] == nc
         levels = [(h // int(s), w // int(s)) for s in meta["stride"]]
         assert tuple(y.shape) == (b, 4 + nc, sum(lh * lw for lh, lw in levels)) and len(raws) == len(levels)
         assert [tuple(r.shape) for r in raws] == [(b, 64 + nc, lh, lw) for lh, lw in levels]
         yr = y.float().cpu().numpy()
         assert np.isfinite(yr).all()
-        _check_y(yr, z[ykey % si], meta["stride"], _level_of_anchor(levels), max(h, w), precision, f"{what} shape {si}")
+        check_y(yr, z[ykey % si], meta["stride"], level_of_anchor(levels), max(h, w), precision, f"{what} shape {si}", nc, Y_BOUNDS)
         for l, r in enumerate(raws):
-            _check_raw(r.float().cpu().numpy(), z[rawkey % (si, l)], precision, f"{what} shape {si} raw {l}")
+            check_raw(r.float().cpu().numpy(), z[rawkey % (si, l)], precision, f"{what} shape {si} raw {l}", RAW_BOUNDS)
         if not nms:
             continue
         conf, iou = meta["nms_conf"], meta["nms_iou"]
@@ -677,7 +632,7 @@ def test_world_graph_matches_reference(tag, precision):
     kept of the engine's y are NOT compared with the stored rows, in any precision: under the synthetic fill every anchor passes conf 0.25
     and some two dozen of the 504 anchors of the larger shape have their two best classes within 1e-3 of each other, so two predictions
     that agree to 1e-3 legitimately keep different rows (the oracle's NMS of a stored y moved by 1e-5 kept 42 rows where it had kept 41)."""
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     assert eng.nc == NC and eng.text_nc == NC and eng.meta["world"] and eng.task == "detect"
     _compare(eng, z, meta, precision, NC, "y%d", "raw%d_%d", tag)
@@ -689,21 +644,11 @@ def test_world_graph_matches_reference(tag, precision):
 def test_world_graph_under_five_rows(precision):
     """Scale n scored against the 5-row text (what set_classes leaves behind): cfg["nc"] = 12 still sizes c3, the outputs have 5 classes."""
     tag = GRAPHS[0]
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision, txt=_texts()[1])
     assert eng.nc == NC2 and eng.names == {i: str(i) for i in range(NC2)}
     _compare(eng, z, meta, precision, NC2, "y5_%d", "raw5_%d_%d", tag + " 5 rows", nms=False)
     eng.close()
-
-
-def _outputs(eng, meta, precision="fp16"):
-    outs = []
-    for si in range(len(meta["shapes"])):
-        x = _x(meta, si)
-        y, raws = eng((x.half() if precision == "fp16" else x).to(DEV))
-        torch.cuda.synchronize()
-        outs.append([y.clone()] + [r.clone() for r in raws])
-    return outs
 
 
 @gpu
@@ -712,39 +657,39 @@ def test_text_replacement(precision):
     """load_weights(sd, txt_feats=t2) with the same row count returns the bits of a fresh engine built with t2, which differ from those under
     t1; another row count raises ValueError and leaves the engine as it was."""
     tag = GRAPHS[0]
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     t1 = _texts()[0]
     t2 = torch.nn.functional.normalize(torch.randn(NC, E, generator=torch.Generator().manual_seed(9)), dim=-1)  # (nc, E): the other accepted shape
     eng = _engine(tag, precision)
-    under1 = _outputs(eng, meta, precision)
+    under1 = outputs(eng, meta, _hw(precision))
     eng.load_weights(_sd_of(tag), txt_feats=t2)
-    under2 = _outputs(eng, meta, precision)
+    under2 = outputs(eng, meta, _hw(precision))
     fresh = _engine(tag, precision, txt=t2)
-    want2 = _outputs(fresh, meta, precision)
+    want2 = outputs(fresh, meta, _hw(precision))
     fresh.close()
     for a, b, c in zip(under2, want2, under1):
         assert all(torch.equal(u, v) for u, v in zip(a, b)) and not torch.equal(a[0], c[0])
     with pytest.raises(ValueError, match="has 5 rows"):
         eng.load_weights(_sd_of(tag), txt_feats=_texts()[1])
-    again = _outputs(eng, meta, precision)
+    again = outputs(eng, meta, _hw(precision))
     assert all(torch.equal(u, v) for a, b in zip(again, under2) for u, v in zip(a, b))
     eng.load_weights(dict(_sd_of(tag), txt_feats=t1))  # the reserved key of the state dict
-    back = _outputs(eng, meta, precision)
+    back = outputs(eng, meta, _hw(precision))
     assert all(torch.equal(u, v) for a, b in zip(back, under1) for u, v in zip(a, b))
     eng.load_weights(_sd_of(tag))  # a model's state dict holds no text: the text in use stays
-    assert torch.equal(eng.txt_feats, t1) and all(torch.equal(u, v) for a, b in zip(_outputs(eng, meta, precision), under1) for u, v in zip(a, b))
+    assert torch.equal(eng.txt_feats, t1) and all(torch.equal(u, v) for a, b in zip(outputs(eng, meta, _hw(precision)), under1) for u, v in zip(a, b))
     eng.load_weights(_sd_of(tag), txt_feats=t2)
     eng.load_weights({k: v * (0.5 if k == "model.16.conv.weight" else 1.0) for k, v in _sd_of(tag).items()})  # new weights, t2 kept
-    moved = _outputs(eng, meta, precision)
+    moved = outputs(eng, meta, _hw(precision))
     assert torch.equal(eng.txt_feats, t2) and not torch.equal(moved[0][0], under2[0][0]) and not torch.equal(moved[0][0], under1[0][0])
     eng.close()
     from bs_yolo_amd.engine import YoloEngine
     with pytest.raises(ValueError, match="needs its text features"):
-        YoloEngine(_cfg(meta), _sd_of(tag), precision=precision)
+        YoloEngine(cfg_of(meta), _sd_of(tag), precision=precision)
     with pytest.raises(NotImplementedError, match="per-image text features"):
-        YoloEngine(_cfg(meta), _sd_of(tag), precision=precision, txt_feats=t1.repeat(2, 1, 1))
+        YoloEngine(cfg_of(meta), _sd_of(tag), precision=precision, txt_feats=t1.repeat(2, 1, 1))
     with pytest.raises(ValueError, match="rows of E = 512"):
-        YoloEngine(_cfg(meta), _sd_of(tag), precision=precision, txt_feats=t1[..., :256])
+        YoloEngine(cfg_of(meta), _sd_of(tag), precision=precision, txt_feats=t1[..., :256])
 
 
 class _Seq(torch.nn.Module):
@@ -752,26 +697,13 @@ class _Seq(torch.nn.Module):
         return getattr(self, str(i) if i >= 0 else str(max(int(k) for k in self._modules if k.isdigit())))
 
 
-class WorldModel(torch.nn.Module):
-    """Stand-in for the reference's WorldModel of yolov8-worldv2.yaml (tests/test_yolov6.py's V6Model): `.yaml`, the reference's parameter
-    names with the fixture's values, `txt_feats` as a plain attribute (not in the state dict), an `act` on every Conv module (nn.Identity()
-    on the C2fAttn blocks' proj_conv, nn.SiLU() elsewhere), layers indexable as model.model[i], a head with `nc`, and an original forward
-    that counts its calls and says which keywords it got."""
+class WorldModel(RefModel):
+    """RefModel for the reference's WorldModel of yolov8-worldv2.yaml (tests/test_yolov6.py's V6Model): `txt_feats` as a plain attribute (not
+    in the state dict), an `act` on every Conv module (nn.Identity() on the C2fAttn blocks' proj_conv, nn.SiLU() elsewhere), layers
+    indexable as model.model[i], a head with `nc`, and an original forward that says which keywords each call got."""
 
     def __init__(self, cfg, sd, txt):
-        super().__init__()
-        self.yaml = cfg
-        for name, t in sd.items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, _Seq())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked"):
-                mod.register_buffer(leaf, t.clone())
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
+        super().__init__(cfg, sd, module_cls=_Seq)
         for name, mod in list(self.named_modules()):
             if hasattr(mod, "conv") and hasattr(mod, "bn"):
                 mod.act = torch.nn.Identity() if name.endswith("attn.proj_conv") else torch.nn.SiLU()
@@ -789,27 +721,27 @@ class WorldModel(torch.nn.Module):
 def test_accelerate_a_world_model():
     from bs_yolo_amd import plugin
     tag = GRAPHS[0]
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     t1, t2 = _texts()
-    m = WorldModel(_cfg(meta), _sd_of(tag), t1).to(DEV)
+    m = WorldModel(cfg_of(meta), _sd_of(tag), t1).to(DEV)
     assert "txt_feats" not in m.state_dict() and m.model[-1].nc == NC
     plugin.accelerate(m)
     st = m._bsy_state
     assert st["support"] == {"fp16": True, "fp32": True}
-    x = _x(meta, 1)
+    x = x_of(meta, 1)
     b, h, w = meta["shapes"][1]
     levels = [(h // int(s), w // int(s)) for s in meta["stride"]]
-    lvl, A = _level_of_anchor(levels), sum(lh * lw for lh, lw in levels)
+    lvl, A = level_of_anchor(levels), sum(lh * lw for lh, lw in levels)
     out = m(x.to(DEV))  # fp32 input: the fp32x engine
     assert isinstance(out, tuple) and len(out) == 2 and isinstance(out[1], list) and len(out[1]) == 3 and not m.calls and st["fp32_calls"] == 1
     y, raws = out
     assert tuple(y.shape) == (b, 4 + NC, A) and [tuple(r.shape) for r in raws] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
-    _check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", "accelerate")
+    check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", "accelerate", NC, Y_BOUNDS)
     y16, raws16 = m(x.half().to(DEV))
     assert st["engine_calls"] == 1 and not m.calls and st["engine"].nc == NC
-    _check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", "accelerate")
+    check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", "accelerate", NC, Y_BOUNDS)
     for l, r in enumerate(raws16):
-        _check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate raw {l}")
+        check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate raw {l}", RAW_BOUNDS)
     # a call with its own text goes to the original forward; so does augment (the class is not DetectionModel)
     n_fb = st["fallbacks"]
     assert m(x.half().to(DEV), txt_feats=t2.to(DEV)) == "original" and m.calls == [["txt_feats"]] and st["fallbacks"] == n_fb + 1
@@ -820,7 +752,7 @@ def test_accelerate_a_world_model():
     m.txt_feats, m.model[-1].nc = t2.clone(), NC2
     y5, raws5 = m(x.half().to(DEV))
     assert st["rebuilds"] == n + 1 and tuple(y5.shape) == (b, 4 + NC2, A) and [r.shape[1] for r in raws5] == [64 + NC2] * 3 and st["engine"].nc == NC2
-    _check_y(y5.float().cpu().numpy(), z["y5_1"], meta["stride"], lvl, max(h, w), "fp16", "accelerate 5 rows")
+    check_y(y5.float().cpu().numpy(), z["y5_1"], meta["stride"], lvl, max(h, w), "fp16", "accelerate 5 rows", NC2, Y_BOUNDS)
     m(x.half().to(DEV))
     assert st["rebuilds"] == n + 1  # nothing changed: no rebuild
     # an in-place edit of the text rebuilds too

@@ -25,7 +25,6 @@ max(1, maximum); fp32 / fp32x 1e-3 and 1e-3 * imgsz.
 
 Run on the MI355X box with ``pytest -m gpu``; everything else runs anywhere."""
 import ctypes as C
-import json
 import re
 from functools import lru_cache
 from types import SimpleNamespace
@@ -35,14 +34,15 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, synth_state_dict
+from graph_helpers import (RawBounds, RefModel, YBounds, all_equal, cfg_of, check_nms, check_raw, check_y, engine, fixture, kinds, level_of_anchor,
+                           outputs, state_dict, x_of)
 from op_plan_helpers import (DEV, NAN, POISON16, POISON32, _bound, _worst, assert_poison_intact, bits, conv16_op, conv16_records, conv32_op,
                              conv32_record, conv_first16_op, nchw, nhwc, new_op, poisoned, poisoned_blob, poisoned_image, run_ops, view)
-from oracle.yolo_ref import synth_param
 
 gpu = pytest.mark.gpu
 NC = 12
@@ -51,21 +51,8 @@ FAMILIES = {"yolov3_tiny": "yolov3-tiny", "yolov3": "yolov3", "yolov3_spp": "yol
 STRIDES = {"yolov3-tiny": (16, 32), "yolov3": (8, 16, 32), "yolov3-spp": (8, 16, 32)}
 GRAPHS = list(FAMILIES)
 PRECISIONS = ["fp16", "fp32x", "fp32"]
-_CACHE = {}
-
-
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=None, box16=1.0, score32=1e-3, box32=1e-3)  # the graph bounds of the module docstring
+RAW_BOUNDS = RawBounds(rel16=3e-2, strict16=False, floor16=True, rel32=1e-3)
 
 
 def _damped(name, d):
@@ -73,26 +60,17 @@ def _damped(name, d):
     return name.endswith(d["suffix"]) and parts[0] == "model" and int(parts[1]) in d["layers"]
 
 
-@lru_cache(maxsize=None)
+def _damp(name, meta):
+    """The rule the generator wrote into meta["damp"] (make_v3_fixtures.py)."""
+    return meta["damp"]["factor"] if _damped(name, meta["damp"]) else 1.0
+
+
 def _sd_of(tag):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated from synth_param and damped by the
-    rule the generator wrote into meta["damp"] (make_v3_fixtures.py)."""
-    meta = _fixture(tag)[1]
-    sd = {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-    for n in sd:
-        if _damped(n, meta["damp"]):
-            sd[n] = sd[n] * meta["damp"]["factor"]
-    return sd
+    return state_dict(tag, _damp)
 
 
 def _cfg(meta):
-    cfg = stock_cfg(meta["family"], meta["scale"], meta["nc"], meta["task"])
-    cfg["width_multiple"] = meta["width_multiple"]
-    return cfg
-
-
-def _kinds(plan, kind):
-    return [o for o in plan.ops if o["kind"] == kind]
+    return cfg_of(meta, width_multiple=meta["width_multiple"])
 
 
 def _evaluated(d):
@@ -117,7 +95,7 @@ def _evaluated(d):
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_stock_cfg_is_the_reference_yaml(tag):
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     fam = meta["family"]
     assert fam == FAMILIES[tag] and meta["scale"] is None
     for scale in (None, ""):
@@ -141,7 +119,7 @@ def test_v3_plans(tag, precision, monkeypatch):
     reference's own conv count within 1 % (test_ghost.py's and test_yolov9.py's margin for zero-padded pieces; these graphs have none);
     the weight records read exactly the parameter names the reference's model holds."""
     monkeypatch.delenv("BSY_FUSE_FIRST_POOL", raising=False)
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     fam, strides = meta["family"], STRIDES[meta["family"]]
     assert meta["stride"] == [float(s) for s in strides]
     for h in (64, 640):
@@ -186,8 +164,8 @@ def test_tiny_op_counts(monkeypatch):
     cfg = stock_cfg("yolov3-tiny", None, NC)
 
     def census(plan):
-        pools = _kinds(plan, L.OP_MAXPOOL)
-        return (len(_kinds(plan, L.OP_FIRST_POOL)), len(_kinds(plan, L.OP_CONV_FIRST)), sum(o["level"] == 0 for o in pools),
+        pools = kinds(plan, L.OP_MAXPOOL)
+        return (len(kinds(plan, L.OP_FIRST_POOL)), len(kinds(plan, L.OP_CONV_FIRST)), sum(o["level"] == 0 for o in pools),
                 sum(o["level"] == 1 for o in pools))
 
     monkeypatch.delenv("BSY_FUSE_FIRST_POOL", raising=False)
@@ -214,7 +192,7 @@ def test_tiny_op_counts(monkeypatch):
     # the mode-1 pool reads layer 10's map and keeps its size; layer 19: one COPY through up0, then a two-source 3x3 conv
     last = next(o for o in on.ops if o["kind"] == L.OP_MAXPOOL and o["level"] == 1)
     assert last["name"] == "model.12" and (last["H"], last["W"], last["OH"], last["OW"]) == (2, 2, 2, 2) and last["src0"].C == 512
-    copies = _kinds(on, L.OP_COPY)
+    copies = kinds(on, L.OP_COPY)
     c19 = next(o for o in on.ops if o["name"] == "model.19")
     assert len(copies) == 1 and copies[0]["src0"].up and not copies[0]["dst"].up and copies[0]["name"] == "model.19.up0"
     assert c19["ksize"] == 3 and c19["src0"] is copies[0]["dst"] and not c19["src0"].up and not c19["src1"].up and (c19["src0"].C, c19["src1"].C) == (128, 256)
@@ -228,19 +206,19 @@ def test_tiny_op_counts(monkeypatch):
 def test_spp_op_counts(precision):
     spp = Plan(stock_cfg("yolov3-spp", None, NC), 1, 64, 64, precision=precision)
     v3 = Plan(stock_cfg("yolov3", None, NC), 1, 64, 64, precision=precision)
-    assert len(_kinds(spp, L.OP_SPPF_POOL)) == 1 and not _kinds(v3, L.OP_SPPF_POOL)
-    pool = _kinds(spp, L.OP_SPPF_POOL)[0]
+    assert len(kinds(spp, L.OP_SPPF_POOL)) == 1 and not kinds(v3, L.OP_SPPF_POOL)
+    pool = kinds(spp, L.OP_SPPF_POOL)[0]
     assert pool["name"] == "model.12.m" and pool["src0"].C == 512 and {"model.12.cv1", "model.12.cv2"} <= set(spp.wrecs)
     assert (spp.wrecs["model.12.cv1"].cin, spp.wrecs["model.12.cv2"].cin, spp.wrecs["model.12.cv2"].cout) == (1024, 2048, 512)
     for plan in (spp, v3):  # one COPY with up0 per head Concat (layers 18 and 25), in front of cv1 of the Bottleneck that reads it
-        copies = _kinds(plan, L.OP_COPY)
+        copies = kinds(plan, L.OP_COPY)
         assert [o["name"] for o in copies] == ["model.19.cv1.up0", "model.26.cv1.up0"] and all(o["src0"].up for o in copies)
         for c, name in zip(copies, ("model.19.cv1", "model.26.cv1")):
             cv1 = next(o for o in plan.ops if o["name"] == name)
             assert cv1["ksize"] == 3 and cv1["src0"] is c["dst"] and cv1["src1"] is not None and not cv1["src1"].up
         assert not any(o["kind"] == L.OP_CONV and o["ksize"] == 3 and (o["src0"].up or (o.get("src1") is not None and o["src1"].up)) for o in plan.ops)
-        assert len(_kinds(plan, L.OP_BNECK)) == (1 if precision == "fp16" else 0)  # model.2 (64 -> 32 -> 64); the rest are too wide
-        assert plan.ops[0]["kind"] == L.OP_CONV_FIRST and plan.ops[0]["stride"] == 1 and not _kinds(plan, L.OP_STEM)
+        assert len(kinds(plan, L.OP_BNECK)) == (1 if precision == "fp16" else 0)  # model.2 (64 -> 32 -> 64); the rest are too wide
+        assert plan.ops[0]["kind"] == L.OP_CONV_FIRST and plan.ops[0]["stride"] == 1 and not kinds(plan, L.OP_STEM)
 
 
 def test_what_is_refused():
@@ -602,33 +580,7 @@ def test_two_source_3x3_after_materialised_upsample(prec):
 # the graphs
 # ------------------------------------------------------------------------------------------------------------
 def _engine(tag, precision, **kw):
-    from bs_yolo_amd.engine import YoloEngine
-    meta = _fixture(tag)[1]
-    return YoloEngine(_cfg(meta), _sd_of(tag), precision=precision, **kw)
-
-
-def _level_of_anchor(levels):
-    return np.concatenate([np.full(h * w, l) for l, (h, w) in enumerate(levels)])
-
-
-def _check_y(y, yref, strides, lvl, imgsz, precision, what):
-    """The project's parity bounds, stated once (module docstring; test_ghost.py's, unchanged)."""
-    es = np.abs(y[:, 4:4 + NC] - yref[:, 4:4 + NC]).max()
-    eb = np.abs(y[:, :4] - yref[:, :4]).max(axis=(0, 1))  # per anchor
-    per_level = [float(eb[lvl == l].max()) for l in range(len(strides))]
-    print(what, precision, f"score {es:.2e} box per level {['%.2e' % e for e in per_level]}")
-    if precision == "fp16":
-        assert es < 1e-2, (what, "score", es)
-        assert (eb < np.array([max(1.0, s / 32.0) for s in strides])[lvl]).all(), (what, "box", per_level)
-    else:
-        assert es <= 1e-3, (what, "score", es)
-        assert eb.max() <= 1e-3 * imgsz, (what, "box", per_level)
-
-
-def _check_raw(got, ref, precision, what):
-    e, mx = np.abs(got - ref).max(), np.abs(ref).max()
-    print(what, precision, f"err {e:.2e} of max {mx:.3f}")
-    assert got.shape == ref.shape and e <= (3e-2 if precision == "fp16" else 1e-3) * max(1.0, mx), (what, e, mx)
+    return engine(tag, precision, _damp, cfg=_cfg(fixture(tag)[1]), **kw)
 
 
 @gpu
@@ -638,45 +590,28 @@ def test_v3_graph_matches_reference(tag, precision, monkeypatch):
     """ONE engine over both shapes: y, the raw maps of every level and NMS at the fixture's conf, as test_ghost.py compares them: on the
     fixture's own y the device NMS returns the fixture's rows; on the engine's y it is the oracle's NMS of that y bit for bit; in the
     fp32-storage modes the rows it keeps are the fixture's within the modes' bounds."""
-    from bs_yolo_amd import nms as HN
-    from oracle import postproc_ref as PP
     monkeypatch.delenv("BSY_FUSE_FIRST_POOL", raising=False)
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     kept = 0
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         y, raws = eng((x.half() if precision == "fp16" else x).to(DEV))
         torch.cuda.synchronize()
         plan = eng.plan_for(b, h, w, *(2 * [F16 if precision == "fp16" else F32]))[0]
-        assert bool(_kinds(plan, L.OP_FIRST_POOL)) == (precision == "fp16" and tag == "yolov3_tiny")
-        assert bool(_kinds(plan, L.OP_MAXPOOL)) == (tag == "yolov3_tiny") and bool(_kinds(plan, L.OP_SPPF_POOL)) == (tag == "yolov3_spp")
-        assert _kinds(plan, L.OP_COPY) and (tag == "yolov3_tiny" or plan.ops[0]["stride"] == 1)
+        assert bool(kinds(plan, L.OP_FIRST_POOL)) == (precision == "fp16" and tag == "yolov3_tiny")
+        assert bool(kinds(plan, L.OP_MAXPOOL)) == (tag == "yolov3_tiny") and bool(kinds(plan, L.OP_SPPF_POOL)) == (tag == "yolov3_spp")
+        assert kinds(plan, L.OP_COPY) and (tag == "yolov3_tiny" or plan.ops[0]["stride"] == 1)
         levels = [(h // int(s), w // int(s)) for s in meta["stride"]]
         assert tuple(y.shape) == (b, 4 + NC, sum(lh * lw for lh, lw in levels)) and len(raws) == len(levels)
         assert [tuple(r.shape) for r in raws] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
         yr = y.float().cpu().numpy()
         assert np.isfinite(yr).all()
-        _check_y(yr, z[f"y{si}"], meta["stride"], _level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}")
+        check_y(yr, z[f"y{si}"], meta["stride"], level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}", NC, Y_BOUNDS)
         assert si in meta["raw_shapes"]
         for l, r in enumerate(raws):
-            _check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}")
-        conf, iou = meta["nms_conf"], meta["nms_iou"]
-        pinned = HN.non_max_suppression(torch.from_numpy(z[f"y{si}"]).to(DEV), conf, iou, nc=NC)
-        mine = HN.non_max_suppression(y.float().clone(), conf, iou, nc=NC)  # (both convert xywh in place)
-        oracle = PP.non_max_suppression(y.float().cpu().clone(), conf, iou, nc=NC)
-        for bi in range(b):
-            want = z[f"nms{si}_{bi}"]
-            assert tuple(pinned[bi].shape) == want.shape and np.allclose(pinned[bi].cpu().numpy(), want, atol=1e-5, rtol=0), (tag, si, bi)
-            assert torch.equal(mine[bi].cpu(), oracle[bi]), (tag, si, bi)
-            if precision != "fp16":
-                g = mine[bi].cpu().numpy()
-                assert g.shape == want.shape, (tag, precision, si, bi, g.shape, want.shape)
-                if len(g):
-                    print(tag, precision, si, bi, f"nms rows {len(g)} box {np.abs(g[:, :4] - want[:, :4]).max():.2e} conf {np.abs(g[:, 4] - want[:, 4]).max():.2e}")
-                    assert np.abs(g[:, :4] - want[:, :4]).max() <= 1e-3 * max(h, w) and np.abs(g[:, 4] - want[:, 4]).max() <= 1e-3
-                    assert np.array_equal(g[:, 5], want[:, 5])
-            kept += len(want)
+            check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}", RAW_BOUNDS)
+        kept += check_nms(z, meta, si, y, b, h, w, precision, NC, what=tag)
     assert kept > 0
     eng.close()
 
@@ -685,52 +620,17 @@ def test_v3_graph_matches_reference(tag, precision, monkeypatch):
 def test_fusion_is_not_a_different_answer(monkeypatch):
     """BSY_FUSE_FIRST_POOL = 0 and = 1 on the fp16 path of yolov3-tiny: y and the raw maps are the same bits (torch.equal)."""
     tag = "yolov3_tiny"
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     outs = {}
     for env in ("0", "1"):
         monkeypatch.setenv("BSY_FUSE_FIRST_POOL", env)
         eng = _engine(tag, "fp16")
-        outs[env] = []
-        for si, (b, h, w) in enumerate(meta["shapes"]):
-            y, raws = eng(_x(meta, si).half().to(DEV))
-            torch.cuda.synchronize()
+        outs[env] = outputs(eng, meta, F16)
+        for b, h, w in meta["shapes"]:
             plan = eng.plan_for(b, h, w, F16, F16)[0]
-            assert bool(_kinds(plan, L.OP_FIRST_POOL)) == (env == "1") and bool(_kinds(plan, L.OP_CONV_FIRST)) == (env == "0")
-            outs[env].append([y.clone()] + [r.clone() for r in raws])
+            assert bool(kinds(plan, L.OP_FIRST_POOL)) == (env == "1") and bool(kinds(plan, L.OP_CONV_FIRST)) == (env == "0")
         eng.close()
-    same = True
-    for si, (a, b) in enumerate(zip(outs["0"], outs["1"])):
-        for what, u, v in zip(["y"] + [f"raw{l}" for l in range(len(a) - 1)], a, b):  # every figure is printed before anything is asserted
-            d = (u.float() - v.float()).abs()
-            print(tag, "shape", si, what, f"differing {int((d > 0).sum())} of {d.numel()}, max {float(d.max()):.3e}")
-            same = same and torch.equal(u, v)
-    assert same, tag
-
-
-class RefModel(torch.nn.Module):
-    """Stand-in for the reference's DetectionModel (as test_ghost.py's): `.yaml`, the reference's parameter names with the fixture's
-    values, and an original forward that only counts its calls."""
-
-    def __init__(self, cfg, sd):
-        super().__init__()
-        self.yaml = cfg
-        for name, t in sd.items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, torch.nn.Module())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked"):
-                mod.register_buffer(leaf, t.clone())
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
-        self.calls = 0
-        self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
+    assert all_equal(outs["0"], outs["1"], tag), tag
 
 
 @gpu
@@ -738,25 +638,25 @@ def test_accelerate_a_yolov3_tiny_model(monkeypatch):
     from bs_yolo_amd import plugin
     monkeypatch.delenv("BSY_FUSE_FIRST_POOL", raising=False)
     tag = "yolov3_tiny"
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     m = RefModel(_cfg(meta), _sd_of(tag)).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 1)
+    x = x_of(meta, 1)
     b, h, w = meta["shapes"][1]
-    lvl = _level_of_anchor([(h // int(s), w // int(s)) for s in meta["stride"]])
+    lvl = level_of_anchor([(h // int(s), w // int(s)) for s in meta["stride"]])
     y, raws = m(x.to(DEV))  # fp32 input: the fp32x engine
     st = m._bsy_state
     assert m.calls == 0 and len(raws) == 2 and st["fp32_calls"] == 1 and st["support"] == {"fp16": True, "fp32": True}
-    _check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", f"accelerate {tag}")
+    check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", f"accelerate {tag}", NC, Y_BOUNDS)
     y16, raws16 = m(x.half().to(DEV))  # fp16 input: the product path, which is the engine's own output
     assert st["engine_calls"] == 1 and m.calls == 0
     eng = _engine(tag, "fp16")
     ye, re_ = eng(x.half().to(DEV))
     torch.cuda.synchronize()
     assert torch.equal(y16, ye) and all(torch.equal(a, c) for a, c in zip(raws16, re_))
-    assert _kinds(st["engine"].plan_for(b, h, w, F16, F16)[0], L.OP_FIRST_POOL)
-    _check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", f"accelerate {tag}")
+    assert kinds(st["engine"].plan_for(b, h, w, F16, F16)[0], L.OP_FIRST_POOL)
+    check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", f"accelerate {tag}", NC, Y_BOUNDS)
     for l, r in enumerate(raws16):
-        _check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} raw {l}")
+        check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} raw {l}", RAW_BOUNDS)
     eng.close()
     plugin.restore(m)

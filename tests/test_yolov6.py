@@ -22,8 +22,6 @@ weights differ by 6.2e-2 in a score and 14 px in a box on the larger shape (prin
 sppf_act must MISS the bounds there.
 """
 import ctypes as C
-import json
-from functools import lru_cache
 from types import SimpleNamespace
 
 import numpy as np
@@ -33,13 +31,13 @@ import torch
 import test_fp16_block_ops as TB
 import test_fp16_conv_ops as T16
 import test_fp32_matrix_ops as T32
-from conftest import GOLDEN
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, synth_state_dict
+from graph_helpers import (RawBounds, RefModel, YBounds, all_equal, cfg_of, check_nms, check_raw, check_y, engine, fixture, kinds, level_of_anchor,
+                           outputs, state_dict, x_of)
 from op_plan_helpers import (DEV, POISON16, bits, bneck_op, conv16_records, conv_first16_op, new_op, poisoned, poisoned_image, run_ops, view)
-from oracle.yolo_ref import synth_param
 
 gpu = pytest.mark.gpu
 NC = 12
@@ -50,48 +48,29 @@ PRECISIONS = ["fp16", "fp32x", "fp32"]
 REPEATS = {2: 6, 4: 12, 6: 18, 8: 6, 14: 9, 19: 9, 23: 9, 27: 9}  # the yaml's repeated Convs: layer -> repeats before depth scaling
 DEPTH = {"n": 0.33, "s": 0.33, "m": 0.67, "l": 1.0, "x": 1.0}
 ACT_KINDS = (L.OP_CONV_FIRST, L.OP_FIRST_POOL, L.OP_STEM, L.OP_CONV)
-_CACHE = {}
-
-
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
+# the graph bounds of the module docstring (the box bound of 1 px is max(1, stride / 32) of every level here)
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=5e-3, box16=1.0, score32=1e-3, box32=1e-3)
+RAW_BOUNDS = RawBounds(rel16=1e-2, strict16=False, floor16=False, rel32=1e-3)
 
 
 def _damped(name, d):
     return name.startswith(d["prefix"]) and name.endswith(d["suffix"])
 
 
-@lru_cache(maxsize=None)
+def _damp(name, meta):
+    """The rule the generator wrote into meta["damp"] (make_v6_fixtures.py).  The two yolov6n fixtures hold the same weights."""
+    return meta["damp"]["factor"] if _damped(name, meta["damp"]) else 1.0
+
+
 def _sd_of(tag):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated from synth_param and damped by the
-    rule the generator wrote into meta["damp"] (make_v6_fixtures.py).  The two yolov6n fixtures hold the same weights."""
-    meta = _fixture(tag)[1]
-    sd = {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-    for n in sd:
-        if _damped(n, meta["damp"]):
-            sd[n] = sd[n] * meta["damp"]["factor"]
-    return sd
+    return state_dict(tag, _damp)
 
 
 def _cfg(meta):
-    cfg = stock_cfg(meta["family"], meta["scale"], meta["nc"], meta["task"])
+    cfg = cfg_of(meta)
     if meta["width_multiple"] is not None:
         cfg["scales"][meta["scale"]][1] = meta["width_multiple"]
     return cfg
-
-
-def _kinds(plan, kind):
-    return [o for o in plan.ops if o["kind"] == kind]
 
 
 def _chain_len(i, scale):
@@ -113,7 +92,7 @@ def _want_act(name, sppf):
 @pytest.mark.parametrize("scale", SCALES)
 def test_stock_cfg_is_the_reference_yaml(scale):
     for tag in GRAPHS:
-        meta = _fixture(tag)[1]
+        meta = fixture(tag)[1]
         want = dict(meta["yaml"])
         assert want["activation"] == "nn.ReLU()" and want["nc"] == 80 and "scale" not in want
         cfg = stock_cfg("yolov6", scale, 80)
@@ -142,7 +121,7 @@ def test_v6_plans(scale, precision):
             m = plan.meta
             assert m["strides"] == [8.0, 16.0, 32.0] and m["levels"] == [(h // s, h // s) for s in (8, 16, 32)] and m["legacy"] and m["scale"] == scale
             glue = {L.OP_SPPF_POOL, L.OP_DECODE, L.OP_RAW_NCHW}
-            assert {o["kind"] for o in plan.ops} <= set(ACT_KINDS) | glue and len(_kinds(plan, L.OP_SPPF_POOL)) == 1
+            assert {o["kind"] for o in plan.ops} <= set(ACT_KINDS) | glue and len(kinds(plan, L.OP_SPPF_POOL)) == 1
             acts = [(o["name"], o["act"]) for o in plan.ops if o["kind"] in ACT_KINDS]
             assert acts and all(a == _want_act(n, sppf) for n, a in acts), [(n, a) for n, a in acts if a != _want_act(n, sppf)]
             assert [a for n, a in acts if n.startswith("model.9.")] == [sppf, sppf]
@@ -178,7 +157,7 @@ def test_fixture_plans_and_weight_names():
     """The fixtures' graphs (nc = 12): the weight records read exactly the parameter names the reference's model holds, through the
     kinds weights.py already had."""
     for tag in GRAPHS:
-        meta = _fixture(tag)[1]
+        meta = fixture(tag)[1]
         sd = _sd_of(tag)
         assert meta["sppf_act"] == ("relu" if tag.endswith("upstream") else "silu") and meta["stride"] == [8.0, 16.0, 32.0]
         for precision in PRECISIONS:
@@ -490,39 +469,14 @@ def test_act_2_is_refused_where_act_is_a_switch():
 # the graphs
 # ------------------------------------------------------------------------------------------------------------
 def _engine(tag, precision, **kw):
-    from bs_yolo_amd.engine import YoloEngine
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     kw.setdefault("sppf_act", meta["sppf_act"])
-    return YoloEngine(_cfg(meta), _sd_of(tag), precision=precision, **kw)
-
-
-def _level_of_anchor(levels):
-    return np.concatenate([np.full(h * w, l) for l, (h, w) in enumerate(levels)])
+    return engine(tag, precision, _damp, cfg=_cfg(meta), **kw)
 
 
 def _errors(y, yref):
     ds = np.abs(y[:, 4:4 + NC] - yref[:, 4:4 + NC])
     return float(ds.max()), float(np.quantile(ds, 0.999)), np.abs(y[:, :4] - yref[:, :4]).max(axis=(0, 1))
-
-
-def _check_y(y, yref, strides, lvl, imgsz, precision, what):
-    """test_yolov3.py's _check_y with the bounds of this module's docstring: fp16 score max 1e-2 and p99.9 5e-3, box 1 px (max(1, stride / 32)
-    of every level here); fp32 / fp32x 1e-3 and 1e-3 * imgsz."""
-    es, e999, eb = _errors(y, yref)
-    per_level = [float(eb[lvl == l].max()) for l in range(len(strides))]
-    print(what, precision, f"score max {es:.2e} p99.9 {e999:.2e} box per level {['%.2e' % e for e in per_level]}")
-    if precision == "fp16":
-        assert es < 1e-2 and e999 < 5e-3, (what, "score", es, e999)
-        assert (eb < np.array([max(1.0, s / 32.0) for s in strides])[lvl]).all(), (what, "box", per_level)
-    else:
-        assert es <= 1e-3, (what, "score", es)
-        assert eb.max() <= 1e-3 * imgsz, (what, "box", per_level)
-
-
-def _check_raw(got, ref, precision, what):
-    e, mx = np.abs(got - ref).max(), np.abs(ref).max()
-    print(what, precision, f"err {e:.2e} of max {mx:.3f}")
-    assert got.shape == ref.shape and e <= (1e-2 * mx if precision == "fp16" else 1e-3 * max(1.0, mx)), (what, e, mx)
 
 
 @gpu
@@ -533,42 +487,26 @@ def test_v6_graph_matches_reference(tag, precision):
     fixture's own y the device NMS returns the stored rows in every precision; on the engine's y it is the oracle's NMS of that y bit for
     bit; and the rows it keeps of the engine's y are the stored rows (count, classes, boxes and confidences within the modes' bounds) in
     the fp32-storage modes.  In fp16 that last comparison is not made: a score within 1e-2 of the threshold may fall on either side."""
-    from bs_yolo_amd import nms as HN
-    from oracle import postproc_ref as PP
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     assert eng.sppf_act == meta["sppf_act"]
     kept = 0
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         y, raws = eng((x.half() if precision == "fp16" else x).to(DEV))
         torch.cuda.synchronize()
         plan = eng.plan_for(b, h, w, *(2 * [F16 if precision == "fp16" else F32]))[0]
-        assert bool(_kinds(plan, L.OP_STEM)) == (precision == "fp16") and len([o for o in plan.ops if o.get("dst_scale") == 2]) == 8
+        assert bool(kinds(plan, L.OP_STEM)) == (precision == "fp16") and len([o for o in plan.ops if o.get("dst_scale") == 2]) == 8
         assert [o["act"] for o in plan.ops if o["name"] in ("model.9.cv1", "model.9.cv2")] == 2 * [2 if meta["sppf_act"] == "relu" else 1]
         levels = [(h // int(s), w // int(s)) for s in meta["stride"]]
         assert tuple(y.shape) == (b, 4 + NC, sum(lh * lw for lh, lw in levels)) and len(raws) == len(levels)
         assert [tuple(r.shape) for r in raws] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
         yr = y.float().cpu().numpy()
         assert np.isfinite(yr).all()
-        _check_y(yr, z[f"y{si}"], meta["stride"], _level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}")
+        check_y(yr, z[f"y{si}"], meta["stride"], level_of_anchor(levels), max(h, w), precision, f"{tag} shape {si}", NC, Y_BOUNDS)
         for l, r in enumerate(raws):
-            _check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}")
-        conf, iou = meta["nms_conf"], meta["nms_iou"]
-        pinned = HN.non_max_suppression(torch.from_numpy(z[f"y{si}"]).to(DEV), conf, iou, nc=NC)
-        mine = HN.non_max_suppression(y.float().clone(), conf, iou, nc=NC)  # (both convert xywh in place)
-        oracle = PP.non_max_suppression(y.float().cpu().clone(), conf, iou, nc=NC)
-        for bi in range(b):
-            want = z[f"nms{si}_{bi}"]
-            assert tuple(pinned[bi].shape) == want.shape and np.allclose(pinned[bi].cpu().numpy(), want, atol=1e-5, rtol=0), (tag, si, bi)
-            assert torch.equal(mine[bi].cpu(), oracle[bi]), (tag, si, bi)
-            if precision != "fp16":
-                g = mine[bi].cpu().numpy()
-                assert g.shape == want.shape, (tag, precision, si, bi, g.shape, want.shape)
-                if len(g):
-                    assert np.abs(g[:, :4] - want[:, :4]).max() <= 1e-3 * max(h, w) and np.abs(g[:, 4] - want[:, 4]).max() <= 1e-3
-                    assert np.array_equal(g[:, 5], want[:, 5])
-            kept += len(want)
+            check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}", RAW_BOUNDS)
+        kept += check_nms(z, meta, si, y, b, h, w, precision, NC, what=tag)
     assert kept > 0
     eng.close()
 
@@ -579,10 +517,10 @@ def test_v6_graph_matches_reference(tag, precision):
 def test_wrong_sppf_form_misses(tag, wrong, precision):
     """The flag does something: the upstream-form fixture under sppf_act = "silu", and the fork's under "relu", are outside the bounds
     on the larger shape (the two references differ by 6.2e-2 in a score and 14 px in a box there), in every precision."""
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     assert meta["sppf_act"] != wrong
     eng = _engine(tag, precision, sppf_act=wrong)
-    x = _x(meta, 1)
+    x = x_of(meta, 1)
     y, _ = eng((x.half() if precision == "fp16" else x).to(DEV))
     torch.cuda.synchronize()
     es, e999, eb = _errors(y.float().cpu().numpy(), z["y1"])
@@ -591,40 +529,21 @@ def test_wrong_sppf_form_misses(tag, wrong, precision):
     eng.close()
 
 
-def _outputs(eng, meta):
-    outs = []
-    for si in range(len(meta["shapes"])):
-        y, raws = eng(_x(meta, si).half().to(DEV))
-        torch.cuda.synchronize()
-        outs.append([y.clone()] + [r.clone() for r in raws])
-    return outs
-
-
-def _all_equal(a, b, what):
-    same = True
-    for si, (u, v) in enumerate(zip(a, b)):
-        for k, (s, t) in enumerate(zip(u, v)):  # every figure is printed before anything is asserted
-            d = (s.float() - t.float()).abs()
-            print(what, "shape", si, "y" if k == 0 else f"raw{k - 1}", f"differing {int((d > 0).sum())} of {d.numel()}, max {float(d.max()):.3e}")
-            same = same and torch.equal(s, t)
-    return same
-
-
 @gpu
 @pytest.mark.parametrize("switch", ["fuse_stem", "fuse_head"])
 def test_fusion_is_not_a_different_answer(switch):
     """Stem and head fusion carry the ReLU id: on and off return the same bits on the fp16 path."""
     tag = "yolov6n"
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     outs = {}
     for on in (False, True):
         eng = _engine(tag, "fp16", **{switch: on})
-        outs[on] = _outputs(eng, meta)
+        outs[on] = outputs(eng, meta, F16)
         plan = eng.plan_for(*meta["shapes"][1], F16, F16)[0]
-        assert (bool(_kinds(plan, L.OP_STEM)) == on) if switch == "fuse_stem" else (bool(_kinds(plan, L.OP_DECODE)) != on)
+        assert (bool(kinds(plan, L.OP_STEM)) == on) if switch == "fuse_stem" else (bool(kinds(plan, L.OP_DECODE)) != on)
         assert all(o["act"] == _want_act(o["name"], 1) for o in plan.ops if o["kind"] in ACT_KINDS)
         eng.close()
-    assert _all_equal(outs[False], outs[True], f"{tag} {switch}")
+    assert all_equal(outs[False], outs[True], f"{tag} {switch}")
 
 
 @gpu
@@ -633,29 +552,29 @@ def test_first_pool_fusion_under_relu(monkeypatch):
     from bs_yolo_amd.engine import YoloEngine
     cfg = dict(stock_cfg("yolov3-tiny", None, NC), activation="nn.ReLU()")
     sd = synth_state_dict(Plan(cfg, 1, 64, 64))
-    meta = _fixture("yolov6n")[1]
+    meta = fixture("yolov6n")[1]
     outs = {}
     for env in ("0", "1"):
         monkeypatch.setenv("BSY_FUSE_FIRST_POOL", env)
         eng = YoloEngine(cfg, sd)
-        outs[env] = _outputs(eng, meta)
+        outs[env] = outputs(eng, meta, F16)
         plan = eng.plan_for(*meta["shapes"][1], F16, F16)[0]
-        assert bool(_kinds(plan, L.OP_FIRST_POOL)) == (env == "1") and plan.ops[0]["act"] == 2
+        assert bool(kinds(plan, L.OP_FIRST_POOL)) == (env == "1") and plan.ops[0]["act"] == 2
         eng.close()
-    assert _all_equal(outs["0"], outs["1"], "yolov3-tiny under ReLU, first pool")
+    assert all_equal(outs["0"], outs["1"], "yolov3-tiny under ReLU, first pool")
     assert float(outs["1"][1][0][:, 4:].float().max()) > 0 and bool(torch.isfinite(outs["1"][1][0].float()).all())
 
 
 @gpu
 @pytest.mark.parametrize("tag", ["yolov6n", "yolov6m"])
 def test_tuned_equals_untuned(tag):
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     outs = {}
     for tune in (False, True):
         eng = _engine(tag, "fp16", autotune=tune)
-        outs[tune] = _outputs(eng, meta)
+        outs[tune] = outputs(eng, meta, F16)
         eng.close()
-    assert _all_equal(outs[False], outs[True], f"{tag} tuned / untuned")
+    assert all_equal(outs[False], outs[True], f"{tag} tuned / untuned")
 
 
 class _Seq(torch.nn.Module):
@@ -663,58 +582,40 @@ class _Seq(torch.nn.Module):
         return getattr(self, str(i))
 
 
-class V6Model(torch.nn.Module):
-    """Stand-in for the reference's DetectionModel of yolov6.yaml (test_yolov3.py's RefModel with activations): `.yaml`, the reference's
-    parameter names with the fixture's values, an `act` on every Conv module (a module holding `conv` and `bn`) -- nn.ReLU(), SPPF's
-    cv1 / cv2 nn.SiLU() unless sppf_act = "relu" --, layers indexable as model.model[i], and an original forward that counts its calls."""
+class V6Model(RefModel):
+    """RefModel for yolov6.yaml: an `act` on every Conv module (a module holding `conv` and `bn`) -- nn.ReLU(), SPPF's cv1 / cv2 nn.SiLU()
+    unless sppf_act = "relu" --, and layers indexable as model.model[i]."""
 
     def __init__(self, cfg, sd, sppf_act="silu"):
-        super().__init__()
-        self.yaml = cfg
-        for name, t in sd.items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, _Seq())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked"):
-                mod.register_buffer(leaf, t.clone())
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
+        super().__init__(cfg, sd, module_cls=_Seq)
         for name, mod in list(self.named_modules()):
             if hasattr(mod, "conv") and hasattr(mod, "bn"):
                 mod.act = torch.nn.SiLU() if name.startswith("model.9.") and sppf_act == "silu" else torch.nn.ReLU()
-        self.calls = 0
         self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
 
 
 @gpu
 @pytest.mark.parametrize("tag", ["yolov6n", "yolov6n_upstream"])
 def test_accelerate_a_yolov6_model(tag):
     from bs_yolo_amd import plugin
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     form = meta["sppf_act"]
     m = V6Model(_cfg(meta), _sd_of(tag), form).to(DEV)
     assert isinstance(m.model[9].cv1.act, torch.nn.ReLU if form == "relu" else torch.nn.SiLU) and isinstance(m.model[0].act, torch.nn.ReLU)
     plugin.accelerate(m)
     st = m._bsy_state
     assert st["sppf_act"] == form and st["support"] == {"fp16": True, "fp32": True}
-    x = _x(meta, 1)
+    x = x_of(meta, 1)
     b, h, w = meta["shapes"][1]
-    lvl = _level_of_anchor([(h // int(s), w // int(s)) for s in meta["stride"]])
+    lvl = level_of_anchor([(h // int(s), w // int(s)) for s in meta["stride"]])
     y, raws = m(x.to(DEV))  # fp32 input: the fp32x engine
     assert m.calls == 0 and len(raws) == 3 and st["fp32_calls"] == 1 and st["sppf_act"] == form and st["engine32"].sppf_act == form
-    _check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", f"accelerate {tag}")
+    check_y(y.cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp32x", f"accelerate {tag}", NC, Y_BOUNDS)
     y16, raws16 = m(x.half().to(DEV))  # fp16 input: the product path
     assert st["engine_calls"] == 1 and m.calls == 0 and st["engine"].sppf_act == form
-    _check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", f"accelerate {tag}")
+    check_y(y16.float().cpu().numpy(), z["y1"], meta["stride"], lvl, max(h, w), "fp16", f"accelerate {tag}", NC, Y_BOUNDS)
     for l, r in enumerate(raws16):
-        _check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} raw {l}")
+        check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} raw {l}", RAW_BOUNDS)
     # an in-place weight change rebuilds the engine, and the new weights are the ones that run
     n = st["rebuilds"]
     with torch.no_grad():
@@ -729,7 +630,7 @@ def test_accelerate_a_yolov6_model(tag):
 def test_accelerate_refuses_a_swapped_activation():
     """One top-level Conv's act swapped to nn.SiLU(), or SPPF's two convs disagreeing: NotImplementedError before anything is rebound."""
     from bs_yolo_amd import plugin
-    meta = _fixture("yolov6n")[1]
+    meta = fixture("yolov6n")[1]
     for where, msg in (("model.4.1", r"model\.4\.1: the module's activation is SiLU\(\), the plan runs act = 2"),
                        ("model.9.cv2", r"SPPF convs disagree on their activation"),
                        ("model.28.cv3.1.0", r"model\.28\.cv3\.1\.0: the module's activation is SiLU")):
@@ -740,7 +641,7 @@ def test_accelerate_refuses_a_swapped_activation():
         with pytest.raises(NotImplementedError, match=msg):
             plugin.accelerate(m)
         assert not hasattr(m, "_bsy_state") and not hasattr(m, "_bsy_orig_forward") and m.forward == fwd
-        assert m(_x(meta, 0).to(DEV)) == "original" and m.calls == 1
+        assert m(x_of(meta, 0).to(DEV)) == "original" and m.calls == 1
 
 
 @gpu
@@ -748,10 +649,10 @@ def test_a_swap_after_accelerate_is_caught_at_the_next_rebuild():
     """accelerate() checked the activations once; every engine build checks them again, so after a swap the next rebuild (here: an
     in-place weight change) sends the call to the reference forward instead of computing the yaml's function for another model."""
     from bs_yolo_amd import plugin
-    meta = _fixture("yolov6n")[1]
+    meta = fixture("yolov6n")[1]
     m = V6Model(_cfg(meta), _sd_of("yolov6n")).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 0).half().to(DEV)
+    x = x_of(meta, 0).half().to(DEV)
     y, _ = m(x)
     st = m._bsy_state
     assert m.calls == 0 and st["engine_calls"] == 1
@@ -764,7 +665,7 @@ def test_a_swap_after_accelerate_is_caught_at_the_next_rebuild():
 
 def test_sppf_form_reads_both_convs():
     from bs_yolo_amd.engine import sppf_form
-    meta = _fixture("yolov6n")[1]
+    meta = fixture("yolov6n")[1]
     cfg, sd = _cfg(meta), _sd_of("yolov6n")
     assert sppf_form(V6Model(cfg, sd, "silu"), cfg) == "silu" and sppf_form(V6Model(cfg, sd, "relu"), cfg) == "relu"
     m = V6Model(cfg, sd, "silu")
@@ -782,7 +683,7 @@ def test_sppf_form_reads_both_convs():
 @gpu
 def test_engine_reads_the_sppf_form_off_a_model():
     from bs_yolo_amd.engine import YoloEngine
-    meta = _fixture("yolov6n_upstream")[1]
+    meta = fixture("yolov6n_upstream")[1]
     cfg, sd = _cfg(meta), _sd_of("yolov6n_upstream")
     for form in ("relu", "silu"):
         eng = YoloEngine(cfg, V6Model(cfg, sd, form))

@@ -6,7 +6,6 @@ the two RepConv weight folds, the arena, the C ABI and plugin.accelerate -- agai
 Synthetic head scores are far below the score tolerance here (max ~0.005 - 0.01), so the raw level maps (the logits) carry the
 engine-against-reference check; every fixture's meta["ref_fp16"] records how far the reference's own fp16 run is from its fp32 run."""
 import ctypes as C
-import json
 import re
 
 import numpy as np
@@ -14,14 +13,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import fold_refconv, fold_repvgg, pack_plan_weights, repconv_form, synth_state_dict
-from oracle.yolo_ref import synth_param
+from graph_helpers import RawBounds, RefModel, YBounds, all_equal, cfg_of, check_nms, check_raw, check_y, engine, fixture, outputs, state_dict, x_of
+from op_plan_helpers import DEV
 
-DEV = "cuda:0"
 NC = 12
 GRAPHS = ["yolov9c", "yolov9c_seg", "yolov9m", "yolov9t", "yolov9t_repvgg"]
 SHAPES = [(1, 64, 64), (2, 96, 128)]
@@ -29,40 +28,23 @@ ANCHORS = [84, 252]
 SIZES = [("t", "detect"), ("s", "detect"), ("c", "detect"), ("c", "segment")]
 # RepNCSPELAN4 / ELAN1 arguments [c2, c3, c4] of layer 4 (cfg/models/v9/*.yaml), for the cv4 check
 L4 = {"t": (64, 64, 32), "s": (128, 128, 64), "m": (240, 240, 120), "c": (512, 256, 128)}
-_CACHE = {}
-
-
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
+# The bounds test_p2p6.py applies, over the whole of a three-level map.  fp16: score < 1e-2, box < 1 px; fp32x / fp32: 1e-3, 1e-3 * imgsz.
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=None, box16=1.0, score32=1e-3, box32=1e-3)
+# Raw maps, mask coefficients, prototypes.  fp16: 2e-2 of the map's maximum; fp32x / fp32: 1e-3 * max(1, maximum).
+MAP_BOUNDS = RawBounds(rel16=2e-2, strict16=True, floor16=False, rel32=1e-3)
 
 
 def _damped(name, suffixes):
     return re.search(r"\.m\.\d+\.", name) is not None and any(name.endswith(s) for s in suffixes)
 
 
-def _sd(meta):
-    """The reference's un-fused state dict (names as the fixture recorded them), values regenerated from synth_param and damped by the
-    rule the generator wrote into meta["damp"] (make_v9_fixtures.py: the tensors that feed the residual gain, times one factor)."""
-    sd = {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-    d = meta["damp"]
-    for n in sd:
-        if _damped(n, d["suffixes"]):
-            sd[n] = sd[n] * d["factor"]
-    return sd
+def _damp(name, meta):
+    """The rule the generator wrote into meta["damp"] (make_v9_fixtures.py: the tensors that feed the residual gain, times one factor)."""
+    return meta["damp"]["factor"] if _damped(name, meta["damp"]["suffixes"]) else 1.0
 
 
-def _cfg(meta):
-    return stock_cfg(meta["family"], meta["scale"], meta["nc"], meta["task"])
+def _sd_of(tag):
+    return state_dict(tag, _damp)
 
 
 # ---- host side (no GPU) ------------------------------------------------------------------------------------------------
@@ -119,7 +101,7 @@ def test_conv_flops_at_640(size, header):
     another counter: the reference's convs give 8.23 / 26.89 / 76.82 / 102.65, so only c is within 1 % of its header.  yolov9m's
     fp16 plan carries its 180- and 90-channel pieces on 184 and 96 (zero weights in the padding) and so multiplies 1.8 % more:
     it is counted in the fp32 plan, which has no padding."""
-    want = _fixture("yolov9t")[1]["ref_conv_gflops_640"][size]
+    want = fixture("yolov9t")[1]["ref_conv_gflops_640"][size]
     for precision in ("fp32",) if size == "m" else ("fp16", "fp32"):
         plan = Plan(stock_cfg("yolov9", size, 80), 1, 640, 640, precision=precision)
         got = sum(o.get("mfma_flops", 0) for o in plan.ops) / 1e9
@@ -173,8 +155,8 @@ def test_what_is_refused_and_yolov9m():
 
 @pytest.mark.parametrize("tag", GRAPHS)
 def test_weights_pack_from_the_reference_state_dict(tag):
-    _, meta = _fixture(tag)
-    sd = _sd(meta)
+    _, meta = fixture(tag)
+    sd = _sd_of(tag)
     assert repconv_form(sd) == meta["repconv"]
     seen = set()
 
@@ -184,7 +166,7 @@ def test_weights_pack_from_the_reference_state_dict(tag):
             return dict.__getitem__(self, k)
 
     for precision in ("fp16", "fp32x"):
-        plan = Plan(_cfg(meta), 1, 64, 64, precision=precision, repconv=meta["repconv"])
+        plan = Plan(cfg_of(meta), 1, 64, 64, precision=precision, repconv=meta["repconv"])
         pack_plan_weights(plan, Recording(sd))
         kinds = {r.kind for r in plan.wrecs.values()}
         assert meta["repconv"] in kinds and ({"refconv", "repvgg"} - {meta["repconv"]}).isdisjoint(kinds)
@@ -193,16 +175,15 @@ def test_weights_pack_from_the_reference_state_dict(tag):
     gone = dict(sd)
     del gone[next(n for n in sd if _damped(n, meta["damp"]["suffixes"]))]
     with pytest.raises(KeyError):
-        pack_plan_weights(Plan(_cfg(meta), 1, 64, 64, repconv=meta["repconv"]), gone)
+        pack_plan_weights(Plan(cfg_of(meta), 1, 64, 64, repconv=meta["repconv"]), gone)
     other = "repvgg" if meta["repconv"] == "refconv" else "refconv"
     with pytest.raises(KeyError):  # the other form's keys are not in this model
-        pack_plan_weights(Plan(_cfg(meta), 1, 64, 64, repconv=other), sd)
+        pack_plan_weights(Plan(cfg_of(meta), 1, 64, 64, repconv=other), sd)
 
 
 def test_refconv_fold():
     """weights.py "refconv" against this test's fp64 restatement of the fork's RepConv.forward (block.py:813-815)."""
-    _, meta = _fixture("yolov9t")
-    sd = _sd(meta)
+    sd = _sd_of("yolov9t")
     names = [n[:-len(".convmap.weight")] for n in sd if n.endswith(".convmap.weight")]
     assert len(names) == 7 * 2 * 3  # seven RepNCSPELAN4 blocks, two RepCSPs each, n = 3
     for p in names:
@@ -217,8 +198,8 @@ def test_refconv_fold():
 def test_repvgg_fold():
     """weights.py "repvgg" from un-fused keys against the fold from keys fused by this test's fp64 restatement of
     RepConv.get_equivalent_kernel_bias / _fuse_bn_tensor (conv.py:328-369)."""
-    _, meta = _fixture("yolov9t_repvgg")
-    sd = _sd(meta)
+    _, meta = fixture("yolov9t_repvgg")
+    sd = _sd_of("yolov9t_repvgg")
     names = [n[:-len(".conv1.conv.weight")] for n in sd if n.endswith(".cv1.conv1.conv.weight")]
     assert len(names) == 7 * 2 * 3
     eps = 1e-3
@@ -241,7 +222,7 @@ def test_repvgg_fold():
     # a whole fused model packs through the same records
     full = {n: t for n, t in sd.items() if ".cv1.conv1." not in n and ".cv1.conv2." not in n}
     full.update(fused)
-    a, b = (Plan(_cfg(meta), 1, 64, 64, repconv="repvgg") for _ in range(2))
+    a, b = (Plan(cfg_of(meta), 1, 64, 64, repconv="repvgg") for _ in range(2))
     blob_u, blob_f = pack_plan_weights(a, sd), pack_plan_weights(b, full)
     assert len(blob_u) == len(blob_f)
     for key, r in a.wrecs.items():
@@ -257,9 +238,9 @@ def test_arena_keeps_live_buffers_apart(tag, monkeypatch):
     """No op writes into a buffer that is still live: any two buffers whose lifetimes meet have disjoint address ranges, and every op's
     buffers (the pool-down ops' source and destination among them) are alive at that op."""
     monkeypatch.delenv("BSY_LANES", raising=False)
-    _, meta = _fixture(tag)
+    _, meta = fixture(tag)
     for precision in ("fp16", "fp32"):
-        plan = Plan(_cfg(meta), 2, 96, 128, precision=precision, repconv=meta["repconv"])
+        plan = Plan(cfg_of(meta), 2, 96, 128, precision=precision, repconv=meta["repconv"])
         offs, top = plan.assign_offsets()
         life = plan.buffer_lifetimes()
         size = [(b + 255) & ~255 for b in plan.buf_bytes]
@@ -361,30 +342,8 @@ def test_pool_down_refuses_bad_arguments():
     assert bool((y == SENTINEL).all())  # nothing was launched
 
 
-def _engine(meta, precision, **kw):
-    from bs_yolo_amd.engine import YoloEngine
-    return YoloEngine(_cfg(meta), _sd(meta), precision=precision, **kw)
-
-
-def _check(got, ref, precision, imgsz, what):
-    """The bounds test_p2p6.py applies to three-level maps.  fp16: score < 1e-2, box < 1 px; fp32x / fp32: 1e-3, 1e-3 * imgsz."""
-    es, eb = np.abs(got[:, 4:4 + NC] - ref[:, 4:4 + NC]).max(), np.abs(got[:, :4] - ref[:, :4]).max()
-    print(what, precision, f"score {es:.2e} box {eb:.2e}")
-    if precision == "fp16":
-        assert es < 1e-2 and eb < 1.0, (what, es, eb)
-    else:
-        assert es <= 1e-3 and eb <= 1e-3 * imgsz, (what, es, eb)
-
-
-def _check_map(got, ref, precision, what):
-    """Raw maps, mask coefficients, prototypes.  fp16: 2e-2 of the map's maximum; fp32x / fp32: 1e-3 * max(1, maximum)."""
-    e, mx = np.abs(got - ref).max(), np.abs(ref).max()
-    print(what, precision, f"err {e:.2e} of max {mx:.3f}")
-    assert got.shape == ref.shape
-    if precision == "fp16":
-        assert e < 2e-2 * mx, (what, e, mx)
-    else:
-        assert e <= 1e-3 * max(1.0, mx), (what, e, mx)
+def _engine(tag, precision, **kw):
+    return engine(tag, precision, _damp, **kw)
 
 
 @pytest.mark.gpu
@@ -396,16 +355,14 @@ def test_v9_graph_matches_reference(tag, precision):
     test_p2p6.py); on the engine's y it is the oracle's NMS of that same y bit for bit; and in the fp32-storage modes, whose y is
     within 1e-3 / 1e-3 * imgsz of the reference's, the rows it keeps are the fixture's: the same count, the same classes, boxes and
     scores within those bounds (the scores nearest the threshold are 8e-6 away from it, the modes' score error here is below 1e-6)."""
-    from bs_yolo_amd import nms as HN
-    from oracle import postproc_ref as PP
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     assert meta["repconv"] == ("repvgg" if tag.endswith("repvgg") else "refconv")
-    eng = _engine(meta, precision)
+    eng = _engine(tag, precision)
     assert eng.repconv == meta["repconv"]
     seg = meta["task"] == "segment"
     kept = 0
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         y, aux = eng((x.half() if precision == "fp16" else x).to(DEV))
         raws = aux[0] if seg else aux
         torch.cuda.synchronize()
@@ -414,30 +371,15 @@ def test_v9_graph_matches_reference(tag, precision):
         assert [tuple(r.shape) for r in raws] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
         yr = y.float().cpu().numpy()
         assert np.isfinite(yr).all()
-        _check(yr, z[f"y{si}"], precision, max(h, w), f"{tag} shape {si}")
+        check_y(yr, z[f"y{si}"], None, None, max(h, w), precision, f"{tag} shape {si}", NC, Y_BOUNDS)
         assert si in meta["raw_shapes"]
         for l, r in enumerate(raws):
-            _check_map(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}")
+            check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}", MAP_BOUNDS)
         if seg:
             assert torch.equal(aux[1], y[:, 4 + NC:])
-            _check_map(yr[:, 4 + NC:], z[f"mc{si}"], precision, f"{tag} shape {si} mc")
-            _check_map(aux[2].float().cpu().numpy(), z[f"proto{si}"], precision, f"{tag} shape {si} proto")
-        conf, iou = meta["nms_conf"], meta["nms_iou"]
-        pinned = HN.non_max_suppression(torch.from_numpy(z[f"y{si}"]).to(DEV), conf, iou, nc=NC)
-        mine = HN.non_max_suppression(y.float().clone(), conf, iou, nc=NC)  # (both convert xywh in place)
-        oracle = PP.non_max_suppression(y.float().cpu().clone(), conf, iou, nc=NC)
-        for bi in range(b):
-            want = z[f"nms{si}_{bi}"]
-            assert tuple(pinned[bi].shape) == want.shape and np.allclose(pinned[bi].cpu().numpy(), want, atol=1e-5, rtol=0), (tag, si, bi)
-            assert torch.equal(mine[bi].cpu(), oracle[bi]), (tag, si, bi)
-            if precision != "fp16":
-                g = mine[bi].cpu().numpy()
-                assert g.shape == want.shape, (tag, precision, si, bi, g.shape, want.shape)
-                if len(g):
-                    print(tag, precision, si, bi, f"nms rows {len(g)} box {np.abs(g[:, :4] - want[:, :4]).max():.2e} conf {np.abs(g[:, 4] - want[:, 4]).max():.2e}")
-                    assert np.abs(g[:, :4] - want[:, :4]).max() <= 1e-3 * max(h, w) and np.abs(g[:, 4] - want[:, 4]).max() <= 1e-3
-                    assert np.array_equal(g[:, 5], want[:, 5]) and (not seg or np.abs(g[:, 6:] - want[:, 6:]).max() <= 1e-3 * max(1.0, np.abs(want[:, 6:]).max()))
-            kept += len(want)
+            check_raw(yr[:, 4 + NC:], z[f"mc{si}"], precision, f"{tag} shape {si} mc", MAP_BOUNDS)
+            check_raw(aux[2].float().cpu().numpy(), z[f"proto{si}"], precision, f"{tag} shape {si} proto", MAP_BOUNDS)
+        kept += check_nms(z, meta, si, y, b, h, w, precision, NC, seg=seg, what=tag)
     assert kept > 0
     eng.close()
 
@@ -452,73 +394,46 @@ def test_fusion_switches_are_not_a_different_answer(tag, switch):
     """Tuned and untuned, fuse_bneck on and off, fuse_head on and off: the same bits (torch.equal), in both RepConv forms.  With
     fuse_head off a Detect plan's decode launch sums the DFL in the fused epilogue's order (plan.py detect(), bsy_op.act), so the
     switch returns the fused head's bits at three levels as it does at four."""
-    _, meta = _fixture(tag)
-    base, other = _engine(meta, "fp16"), _engine(meta, "fp16", **SWITCHES[switch])
-    same = True
-    for si in range(len(meta["shapes"])):
-        x = _x(meta, si).half().to(DEV)
-        (y0, r0), (y1, r1) = base(x), other(x)
-        torch.cuda.synchronize()
-        p0, p1 = (e.plan_for(x.shape[0], x.shape[2], x.shape[3], x.dtype, x.dtype)[0] for e in (base, other))
+    _, meta = fixture(tag)
+    base, other = _engine(tag, "fp16"), _engine(tag, "fp16", **SWITCHES[switch])
+    outs = [outputs(e, meta, torch.float16) for e in (base, other)]
+    for b, h, w in meta["shapes"]:
+        p0, p1 = (e.plan_for(b, h, w, torch.float16, torch.float16)[0] for e in (base, other))
         assert [sum(o["kind"] == L.OP_DECODE for o in p.ops) for p in (p0, p1)] == [0, int(switch == "fuse_head_off")]
-        assert all(sum(o["kind"] == L.OP_POOL_DOWN for o in p.ops) == 5 for p in (p0, p1)) and len(r0) == len(r1) == 3
-        parts = [("box", y0[:, :4], y1[:, :4]), ("score", y0[:, 4:], y1[:, 4:])] + [(f"raw{l}", a, b) for l, (a, b) in enumerate(zip(r0, r1))]
-        for what, a, b in parts:  # every figure is printed before anything is asserted
-            d = (a.float() - b.float()).abs()
-            print(tag, switch, "shape", si, what, f"differing {int((d > 0).sum())} of {d.numel()}, max {float(d.max()):.3e}")
-            same = same and torch.equal(a, b)
+        assert all(sum(o["kind"] == L.OP_POOL_DOWN for o in p.ops) == 5 for p in (p0, p1))
+    assert all(len(o) == 1 + 3 for o in outs[0] + outs[1])
+    same = all_equal(outs[0], outs[1], f"{tag} {switch}")
     assert base.tuning(*meta["shapes"][1]) and not other.tuning(*meta["shapes"][1])
     base.close()
     other.close()
     assert same, (tag, switch)
 
 
-class RefModel(torch.nn.Module):
-    """Stand-in for the reference's DetectionModel: `.yaml`, the reference's parameter names with the fixture's values, and an original
-    forward that only counts its calls."""
-
-    def __init__(self, cfg, sd):
-        super().__init__()
-        self.yaml = cfg
-        for name, t in sd.items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, torch.nn.Module())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked") or (leaf == "weight" and name + ".convmap.weight" in sd):
-                mod.register_buffer(leaf, t.clone())  # (the fork's RepConv keeps its kernel in a buffer)
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
-        self.calls = 0
-        self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
+def convmap_buffer(name, leaf, sd):
+    """RefModel's buffer rule of the v9 graphs: the fork's RepConv keeps its kernel in a buffer."""
+    return leaf == "weight" and name + ".convmap.weight" in sd
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag", ["yolov9t", "yolov9t_repvgg"])
 def test_accelerate_a_v9_model(tag):
     from bs_yolo_amd import plugin
-    z, meta = _fixture(tag)
-    m = RefModel(_cfg(meta), _sd(meta)).to(DEV)
+    z, meta = fixture(tag)
+    m = RefModel(cfg_of(meta), _sd_of(tag), buffer=convmap_buffer).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 1)
+    x = x_of(meta, 1)
     y, raws = m(x.to(DEV))  # fp32 input: the fp32x engine
     st = m._bsy_state
     assert m.calls == 0 and len(raws) == 3 and st["fp32_calls"] == 1 and st["rebuilds"] == 1 and st["repconv"] == meta["repconv"]
     assert st["engine32"].repconv == meta["repconv"] and st["support"] == {"fp16": True, "fp32": True}
-    _check(y.cpu().numpy(), z["y1"], "fp32x", max(x.shape[2:]), f"accelerate {tag} fp32x")
+    check_y(y.cpu().numpy(), z["y1"], None, None, max(x.shape[2:]), "fp32x", f"accelerate {tag} fp32x", NC, Y_BOUNDS)
     for l, r in enumerate(raws):
-        _check_map(r.cpu().numpy(), z[f"raw1_{l}"], "fp32x", f"accelerate {tag} raw {l}")
+        check_raw(r.cpu().numpy(), z[f"raw1_{l}"], "fp32x", f"accelerate {tag} raw {l}", MAP_BOUNDS)
     y16, raws16 = m(x.half().to(DEV))  # fp16 input: the product path
     assert st["engine_calls"] == 1 and st["rebuilds"] == 2 and st["engine"].repconv == meta["repconv"]
-    _check(y16.float().cpu().numpy(), z["y1"], "fp16", max(x.shape[2:]), f"accelerate {tag} fp16")
+    check_y(y16.float().cpu().numpy(), z["y1"], None, None, max(x.shape[2:]), "fp16", f"accelerate {tag} fp16", NC, Y_BOUNDS)
     for l, r in enumerate(raws16):
-        _check_map(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} fp16 raw {l}")
+        check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate {tag} fp16 raw {l}", MAP_BOUNDS)
     # a weight change (in place, as an EMA update or load_state_dict's copy_ makes it): the engines are rebuilt, in the same form
     with torch.no_grad():
         m.get_submodule("model.22.cv3.0.2").bias.add_(1.0)  # the class bias of level 0
@@ -531,10 +446,10 @@ def test_accelerate_a_v9_model(tag):
 
 def test_accelerate_refuses_yolov9e_layers():
     from bs_yolo_amd import plugin
-    _, meta = _fixture("yolov9c")
-    cfg = _cfg(meta)
+    _, meta = fixture("yolov9c")
+    cfg = cfg_of(meta)
     cfg["backbone"] = [[-1, 1, "nn.Identity", []]] + cfg["backbone"][:3] + [[1, 1, "CBLinear", [[64]]]] + cfg["backbone"][3:]
-    m = RefModel(cfg, {"model.0.conv.weight": torch.zeros(64, 3, 3, 3)})
+    m = RefModel(cfg, {"model.0.conv.weight": torch.zeros(64, 3, 3, 3)}, buffer=convmap_buffer)
     with pytest.raises(NotImplementedError):
         plugin.accelerate(m)
     assert not hasattr(m, "_bsy_state") and m(torch.zeros(1, 3, 64, 64)) == "original"

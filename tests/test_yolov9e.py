@@ -3,13 +3,12 @@ all three precisions, BSY_OP_CBFUSE alone on poisoned views (csrc/cbfuse.hip), o
 plugin.accelerate -- against fixtures made by running the reference (tests/golden/make_v9e_fixtures.py: yolov9e, yolov9e-seg, and yolov9e
 with every width divided by 4, "yolov9e_q", on which the three-precision sweep runs).
 
-Bounds.  The graphs: the project's own (tests/test_yolov9.py _check / _check_map) -- fp16: score < 1e-2, box < 1 px, maps < 2e-2 of the map's
+Bounds.  The graphs: the project's own (tests/test_yolov9.py Y_BOUNDS / MAP_BOUNDS) -- fp16: score < 1e-2, box < 1 px, maps < 2e-2 of the map's
 maximum; fp32x / fp32: 1e-3, 1e-3 * imgsz, maps <= 1e-3 * max(1, maximum).  The op alone: dyadic payloads bit for bit; random payloads
 against float64 within n * 2^-24 * sum|terms| per element, n = the additions that can round (one per tap: the first lands on +0.0), plus
 half an f16 ulp of the result for f16 storage."""
 import copy
 import ctypes as C
-import json
 import re
 
 import numpy as np
@@ -17,15 +16,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, ROOT
+from conftest import ROOT
 from bs_yolo_amd import lib as L
 from bs_yolo_amd.graphs import stock_cfg
 from bs_yolo_amd.plan import Plan
 from bs_yolo_amd.weights import pack_plan_weights, repconv_form, synth_state_dict
-from op_plan_helpers import POISON16, POISON32, assert_poison_intact, bits, new_op, poisoned, run_ops, ulp16, view
-from oracle.yolo_ref import synth_param
+from graph_helpers import RawBounds, RefModel, YBounds, all_equal, check_raw, check_y, engine, fixture, kinds, outputs, state_dict, x_of
+from op_plan_helpers import DEV, POISON16, POISON32, assert_poison_intact, bits, new_op, poisoned, run_ops, ulp16, view
 
-DEV = "cuda:0"
 NC = 12
 SHAPES = [(1, 64, 64), (2, 96, 128)]
 ANCHORS = [84, 252]
@@ -33,39 +31,27 @@ FUSE_LAYERS = (16, 18, 21, 24, 27)
 F16, F32 = torch.float16, torch.float32
 PRECISIONS = ["fp16", "fp32x", "fp32"]
 WIDTH_ARGS = {"Conv": 1, "ADown": 1, "RepNCSPELAN4": 3, "SPPELAN": 2}  # leading arguments that are channel counts (make_v9e_fixtures.py)
-_CACHE, _SD = {}, {}
+# tests/test_yolov9.py's bounds.  fp16: score < 1e-2, box < 1 px over the whole map; fp32x / fp32: 1e-3, 1e-3 * imgsz.
+Y_BOUNDS = YBounds(score16=1e-2, p999_16=None, box16=1.0, score32=1e-3, box32=1e-3)
+# Raw maps, mask coefficients, prototypes, CBFuse maps.  fp16: 2e-2 of the map's maximum; fp32x / fp32: 1e-3 * max(1, maximum).
+MAP_BOUNDS = RawBounds(rel16=2e-2, strict16=True, floor16=False, rel32=1e-3)
 
 
-def _fixture(tag):
-    if tag not in _CACHE:
-        z = np.load(GOLDEN / f"graph_{tag}.npz")
-        _CACHE[tag] = ({k: z[k] for k in z.files if k != "meta"}, json.loads(str(z["meta"])))
-    return _CACHE[tag]
-
-
-def _x(meta, si):
-    b, h, w = meta["shapes"][si]
-    x = torch.rand(b, 3, h, w, generator=torch.Generator().manual_seed(100 + si))
-    assert abs(float(x.double().sum()) - meta["x"][si]["sum"]) < 1e-6 * x.numel() and x.flatten()[:8].tolist() == meta["x"][si]["first"]
-    return x
+def _damp(name, meta):
+    """The two rules of meta["damp"] (make_v9e_fixtures.py): the tensors that feed the RepBottlenecks' residual gain times `factor`, every
+    CBLinear conv's weight and bias times `cblinear` (no name falls under both)."""
+    d = meta["damp"]
+    if re.search(r"\.m\.\d+\.", name) and any(name.endswith(s) for s in d["suffixes"]):
+        return d["factor"]
+    m = re.fullmatch(r"(model\.\d+)\.conv\.(weight|bias)", name)
+    if m and any(n == m.group(1) + ".conv.bias" for n, _ in meta["names"]):  # a CBLinear's nn.Conv2d (a Conv's conv has no bias)
+        return d["cblinear"]
+    return 1.0
 
 
 def _sd(tag):
-    """The reference's un-fused state dict, regenerated from synth_param and damped by the two rules of meta["damp"] (make_v9e_fixtures.py):
-    the tensors that feed the RepBottlenecks' residual gain times `factor`, every CBLinear conv's weight and bias times `cblinear`.  Made
-    once per fixture (58 M values for the full width) and never changed."""
-    if tag not in _SD:
-        meta = _fixture(tag)[1]
-        sd = {n: synth_param(n, s, meta["seed"]) for n, s in meta["names"]}
-        d = meta["damp"]
-        for n in sd:
-            if re.search(r"\.m\.\d+\.", n) and any(n.endswith(s) for s in d["suffixes"]):
-                sd[n] = sd[n] * d["factor"]
-            m = re.fullmatch(r"(model\.\d+)\.conv\.(weight|bias)", n)
-            if m and m.group(1) + ".conv.bias" in sd:  # a CBLinear's nn.Conv2d (a Conv's conv has no bias)
-                sd[n] = sd[n] * d["cblinear"]
-        _SD[tag] = sd
-    return _SD[tag]
+    """Made once per fixture (58 M values for the full width) and never changed."""
+    return state_dict(tag, _damp)
 
 
 def _quarter(cfg, div):
@@ -81,10 +67,6 @@ def _quarter(cfg, div):
 
 def _cfg(meta):
     return _quarter(stock_cfg("yolov9e", None, meta["nc"], meta["task"]), meta["div"])
-
-
-def _kinds(plan, kind):
-    return [o for o in plan.ops if o["kind"] == kind]
 
 
 def _taps(o):
@@ -126,7 +108,7 @@ def test_v9e_plans(div, task, precision):
         assert [o["name"] for o in lin] == [f"model.{i}.conv" for i in range(10, 15)] and all(o["kind"] == L.OP_CONV for o in lin)
         assert [o["dst"].C for o in lin] == [c // div for c in (64, 192, 448, 960, 1984)]
         assert all(o["act"] == 0 and o["ksize"] == 1 and o["stride"] == 1 and plan.wrecs[o["wkey"]].kind == "plain" for o in lin)
-        fuse = _kinds(plan, L.OP_CBFUSE)
+        fuse = kinds(plan, L.OP_CBFUSE)
         assert [o["name"] for o in fuse] == [f"model.{i}" for i in FUSE_LAYERS] and [o["nl"] for o in fuse] == [5, 4, 3, 2, 1]
         assert _taps(fuse[0])[1] == [0, 1, 2, 3, 4]
         groups = [c // div for c in (64, 128, 256, 512, 1024)]
@@ -138,8 +120,8 @@ def test_v9e_plans(div, task, precision):
                 assert (t.buf, t.ld, t.coff, t.C) == (conv["dst"].buf, conv["dst"].ld, sum(groups[:j]), groups[j])
                 assert (t.H << k, t.W << k) == (o["H"], o["W"])
             assert set(plan.op_buffers(o)) == {t.buf for t in taps} | {o["src0"].buf, o["dst"].buf}
-        first = _kinds(plan, L.OP_CONV_FIRST)
-        assert [o["name"] for o in first] == ["model.1", "model.15"] and not _kinds(plan, L.OP_STEM)
+        first = kinds(plan, L.OP_CONV_FIRST)
+        assert [o["name"] for o in first] == ["model.1", "model.15"] and not kinds(plan, L.OP_STEM)
         assert all(o["src0"].buf == L.BSY_EXT_BASE + Plan.EXT_IMG and (o["ksize"], o["stride"], o["pad"]) == (3, 2, 1) for o in first)
         assert plan.layer_out[0] is None and all(plan.layer_out[i] is None for i in range(10, 15)) and plan.layer_out[1].buf == first[0]["dst"].buf
         assert all(plan.layer_out[i].buf == o["dst"].buf for i, o in zip(FUSE_LAYERS, fuse))
@@ -182,7 +164,7 @@ def test_arena_keeps_the_cblinear_buffers(div, monkeypatch):
 def test_conv_flops_at_640():
     """Dense-conv FLOPs of the plan at 1 x 640 x 640, nc = 80, within 1 % of the count of the reference's own convs (make_v9e_fixtures.py).
     The yaml header's 193.0 comes from another counter and is printed, not asserted."""
-    meta = _fixture("yolov9e")[1]
+    meta = fixture("yolov9e")[1]
     want = meta["ref_conv_gflops_640"]
     for precision in ("fp16", "fp32"):
         plan = Plan(stock_cfg("yolov9e", None, 80), 1, 640, 640, precision=precision)
@@ -193,7 +175,7 @@ def test_conv_flops_at_640():
 
 @pytest.mark.parametrize("tag", ["yolov9e_q", "yolov9e_seg"])
 def test_weights_pack_from_the_reference_state_dict(tag):
-    meta, sd = _fixture(tag)[1], _sd(tag)
+    meta, sd = fixture(tag)[1], _sd(tag)
     assert repconv_form(sd) == "refconv" == meta["repconv"]
     seen = set()
 
@@ -234,12 +216,12 @@ def test_plans_and_packs_in_upstreams_repconv_form(div):
         sd = synth_state_dict(plan)
         assert repconv_form(sd) == "repvgg" and not any(k.endswith(".convmap.weight") for k in sd)
         blob = pack_plan_weights(plan, sd)
-        kinds = {r.kind for r in plan.wrecs.values()}
-        assert "repvgg" in kinds and "refconv" not in kinds and len(blob) > 0
+        rec_kinds = {r.kind for r in plan.wrecs.values()}
+        assert "repvgg" in rec_kinds and "refconv" not in rec_kinds and len(blob) > 0
         for i in range(10, 15):
             r = plan.wrecs[f"model.{i}.conv"]
             assert r.kind == "plain" and r.w_off >= 0 and r.b_off > r.w_off and f"model.{i}.conv.bias" in sd
-        assert [o["nl"] for o in _kinds(plan, L.OP_CBFUSE)] == [5, 4, 3, 2, 1] and len(plan.c_ops()) == len(plan.ops)
+        assert [o["nl"] for o in kinds(plan, L.OP_CBFUSE)] == [5, 4, 3, 2, 1] and len(plan.c_ops()) == len(plan.ops)
         ref = Plan(cfg, 2, 96, 128, precision=precision)
         assert [(o["kind"], o["name"]) for o in plan.ops] == [(o["kind"], o["name"]) for o in ref.ops]  # the same launches in both forms
 
@@ -283,8 +265,8 @@ def test_refusals_by_precision_and_activation():
         Plan(cfg, 1, 64, 64)
     for precision in ("fp32x", "fp32"):
         plan = Plan(cfg, 1, 64, 64, precision=precision)
-        first = _kinds(plan, L.OP_CBFUSE)[0]
-        assert [o["nl"] for o in _kinds(plan, L.OP_CBFUSE)] == [5, 4, 3, 2, 1] and (first["box"][0].coff, first["box"][0].C, first["box"][0].ld) == (12, 16, 32)
+        first = kinds(plan, L.OP_CBFUSE)[0]
+        assert [o["nl"] for o in kinds(plan, L.OP_CBFUSE)] == [5, 4, 3, 2, 1] and (first["box"][0].coff, first["box"][0].C, first["box"][0].ld) == (12, 16, 32)
     assert graph_support(cfg) == {"fp16": False, "fp32": True} and max_stride(cfg) == 32
     # under activation: nn.ReLU() the three modules stay refused (they are not in RELU_MODULES)
     relu = _quarter(stock_cfg("yolov9e", None, NC), 4)
@@ -305,7 +287,7 @@ def test_refusals_by_precision_and_activation():
         Plan(fuse_only, 1, 64, 64)
     del small["activation"]  # under SiLU the same graph reaches the lowering: the CBLinear plans, the one-tap CBFuse adds it to layer 1
     plan = Plan(small, 1, 64, 64)
-    assert [o["nl"] for o in _kinds(plan, L.OP_CBFUSE)] == [1] and _taps(_kinds(plan, L.OP_CBFUSE)[0])[1] == [0]
+    assert [o["nl"] for o in kinds(plan, L.OP_CBFUSE)] == [1] and _taps(kinds(plan, L.OP_CBFUSE)[0])[1] == [0]
     # nn.Identity anywhere else, or read by layer 1 alone
     late = _edited({2: [-1, 1, "nn.Identity", []]})
     with pytest.raises(NotImplementedError, match=r"model\.2\b"):
@@ -538,30 +520,8 @@ def test_ops_cbfuse_and_the_entry_point():
 
 
 # ---- the graphs against the reference -----------------------------------------------------------------------------------------
-def _check(got, ref, precision, imgsz, what):
-    """tests/test_yolov9.py _check.  fp16: score < 1e-2, box < 1 px; fp32x / fp32: 1e-3, 1e-3 * imgsz."""
-    es, eb = np.abs(got[:, 4:4 + NC] - ref[:, 4:4 + NC]).max(), np.abs(got[:, :4] - ref[:, :4]).max()
-    print(what, precision, f"score {es:.2e} box {eb:.2e}")
-    if precision == "fp16":
-        assert es < 1e-2 and eb < 1.0, (what, es, eb)
-    else:
-        assert es <= 1e-3 and eb <= 1e-3 * imgsz, (what, es, eb)
-
-
-def _check_map(got, ref, precision, what):
-    """tests/test_yolov9.py _check_map.  fp16: 2e-2 of the map's maximum; fp32x / fp32: 1e-3 * max(1, maximum)."""
-    e, mx = np.abs(got - ref).max(), np.abs(ref).max()
-    print(what, precision, f"err {e:.2e} of max {mx:.3f}")
-    assert got.shape == ref.shape
-    if precision == "fp16":
-        assert e < 2e-2 * mx, (what, e, mx)
-    else:
-        assert e <= 1e-3 * max(1.0, mx), (what, e, mx)
-
-
 def _engine(tag, precision, **kw):
-    from bs_yolo_amd.engine import YoloEngine
-    return YoloEngine(_cfg(_fixture(tag)[1]), _sd(tag), precision=precision, **kw)
+    return engine(tag, precision, _damp, cfg=_cfg(fixture(tag)[1]), **kw)
 
 
 GRAPH_CASES = [("yolov9e_q", p) for p in PRECISIONS] + [("yolov9e", "fp16"), ("yolov9e", "fp32x"), ("yolov9e_seg", "fp16")]
@@ -573,13 +533,13 @@ def test_v9e_graph_matches_reference(tag, precision):
     """y, the raw maps of every level, mc and proto of the segment graph against the fixture, from an engine under the suite's own settings:
     the arena hands buffers out again (the CBLinear buffers live across fifteen layers, the last input's buffer is free right behind a
     CBFUSE), the convs are tuned."""
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     assert eng.repconv == "refconv" and eng.reuse
     seg = meta["task"] == "segment"
     dt = F16 if precision == "fp16" else F32
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si)
+        x = x_of(meta, si)
         y, aux = eng(x.to(dt).to(DEV))
         raws = aux[0] if seg else aux
         torch.cuda.synchronize()
@@ -588,15 +548,15 @@ def test_v9e_graph_matches_reference(tag, precision):
         assert [tuple(r.shape) for r in raws] == [(b, 64 + NC, lh, lw) for lh, lw in levels]
         yr = y.float().cpu().numpy()
         assert np.isfinite(yr).all()
-        _check(yr, z[f"y{si}"], precision, max(h, w), f"{tag} shape {si}")
+        check_y(yr, z[f"y{si}"], None, None, max(h, w), precision, f"{tag} shape {si}", NC, Y_BOUNDS)
         for l, r in enumerate(raws):
-            _check_map(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}")
+            check_raw(r.float().cpu().numpy(), z[f"raw{si}_{l}"], precision, f"{tag} shape {si} raw {l}", MAP_BOUNDS)
         if seg:
             assert torch.equal(aux[1], y[:, 4 + NC:])
-            _check_map(yr[:, 4 + NC:], z[f"mc{si}"], precision, f"{tag} shape {si} mc")
-            _check_map(aux[2].float().cpu().numpy(), z[f"proto{si}"], precision, f"{tag} shape {si} proto")
+            check_raw(yr[:, 4 + NC:], z[f"mc{si}"], precision, f"{tag} shape {si} mc", MAP_BOUNDS)
+            check_raw(aux[2].float().cpu().numpy(), z[f"proto{si}"], precision, f"{tag} shape {si} proto", MAP_BOUNDS)
         plan, hnd = eng.plan_for(b, h, w, dt, dt)
-        assert [o["nl"] for o in _kinds(plan, L.OP_CBFUSE)] == [5, 4, 3, 2, 1]
+        assert [o["nl"] for o in kinds(plan, L.OP_CBFUSE)] == [5, 4, 3, 2, 1]
         offs, top = plan.assign_offsets(True)
         assert top < sum((n + 255) & ~255 for n in plan.buf_bytes)  # buffers do share addresses in this run
     eng.close()
@@ -609,18 +569,18 @@ def test_v9e_cbfuse_layers_match_reference(tag, precision, monkeypatch):
     buffer until the end of the forward (BSY_ARENA_REUSE=0, for this read-back alone); the fixture holds every meta["fuse_step"]-th
     channel of them, an odd step.  y is that of the engine under the default settings, bit for bit."""
     monkeypatch.setenv("BSY_ARENA_REUSE", "0")
-    z, meta = _fixture(tag)
+    z, meta = fixture(tag)
     eng = _engine(tag, precision)
     assert not eng.reuse
     dt = F16 if precision == "fp16" else F32
     for si, (b, h, w) in enumerate(meta["shapes"]):
-        x = _x(meta, si).to(dt).to(DEV)
+        x = x_of(meta, si).to(dt).to(DEV)
         y, _ = eng(x)
         torch.cuda.synchronize()
         plan, hnd = eng.plan_for(b, h, w, dt, dt)
         for i in meta["fuse_layers"]:
             got = eng.read_view(plan, hnd, plan.layer_out[i])[:, ::meta["fuse_step"][si]].numpy()
-            _check_map(got, z[f"fuse{si}_{i}"], precision, f"{tag} shape {si} CBFuse model.{i}")
+            check_raw(got, z[f"fuse{si}_{i}"], precision, f"{tag} shape {si} CBFuse model.{i}", MAP_BOUNDS)
         monkeypatch.setenv("BSY_ARENA_REUSE", "1")
         shared = _engine(tag, precision)
         monkeypatch.setenv("BSY_ARENA_REUSE", "0")
@@ -634,59 +594,30 @@ def test_v9e_cbfuse_layers_match_reference(tag, precision, monkeypatch):
 @gpu
 def test_tuned_and_untuned_are_the_same_bits():
     tag = "yolov9e_q"
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     base, other = _engine(tag, "fp16"), _engine(tag, "fp16", autotune=False)
-    same = True
-    for si in range(len(meta["shapes"])):
-        x = _x(meta, si).half().to(DEV)
-        (y0, r0), (y1, r1) = base(x), other(x)
-        torch.cuda.synchronize()
-        for what, a, b in [("y", y0, y1)] + [(f"raw{l}", a, b) for l, (a, b) in enumerate(zip(r0, r1))]:
-            d = (a.float() - b.float()).abs()
-            print(tag, "shape", si, what, f"differing {int((d > 0).sum())} of {d.numel()}, max {float(d.max()):.3e}")
-            same = same and torch.equal(a, b)
+    same = all_equal(outputs(base, meta, F16), outputs(other, meta, F16), tag)
     assert base.tuning(*meta["shapes"][1]) and not other.tuning(*meta["shapes"][1])
     base.close()
     other.close()
     assert same
 
 
-class RefModel(torch.nn.Module):
-    """Stand-in for the reference's DetectionModel (tests/test_yolov9.py RefModel): `.yaml`, the reference's parameter names with the
-    fixture's values, and an original forward that only counts its calls."""
-
-    def __init__(self, cfg, sd):
-        super().__init__()
-        self.yaml = cfg
-        for name, t in sd.items():
-            mod = self
-            *path, leaf = name.split(".")
-            for p in path:
-                if not hasattr(mod, p):
-                    mod.add_module(p, torch.nn.Module())
-                mod = getattr(mod, p)
-            if leaf in ("running_mean", "running_var", "num_batches_tracked") or (leaf == "weight" and name + ".convmap.weight" in sd):
-                mod.register_buffer(leaf, t.clone())  # (the fork's RepConv keeps its kernel in a buffer)
-            else:
-                mod.register_parameter(leaf, torch.nn.Parameter(t.clone(), requires_grad=False))
-        self.calls = 0
-        self.eval()
-
-    def forward(self, x, *args, **kwargs):
-        self.calls += 1
-        return "original"
+def convmap_buffer(name, leaf, sd):
+    """RefModel's buffer rule (tests/test_yolov9.py): the fork's RepConv keeps its kernel in a buffer."""
+    return leaf == "weight" and name + ".convmap.weight" in sd
 
 
 @gpu
 def test_accelerate_a_v9e_model():
     from bs_yolo_amd import plugin
     tag = "yolov9e_q"
-    meta = _fixture(tag)[1]
+    meta = fixture(tag)[1]
     cfg = _cfg(meta)
-    assert plugin.cfg_of(RefModel(cfg, {}))["backbone"][14][3] == [[16, 32, 64, 128, 256]]  # the nested list arguments come back as they are
-    m = RefModel(cfg, _sd(tag)).to(DEV)
+    assert plugin.cfg_of(RefModel(cfg, {}, buffer=convmap_buffer))["backbone"][14][3] == [[16, 32, 64, 128, 256]]  # the nested list arguments come back as they are
+    m = RefModel(cfg, _sd(tag), buffer=convmap_buffer).to(DEV)
     plugin.accelerate(m)
-    x = _x(meta, 1).half().to(DEV)
+    x = x_of(meta, 1).half().to(DEV)
     y, raws = m(x)
     st = m._bsy_state
     assert m.calls == 0 and len(raws) == 3 and st["support"] == {"fp16": True, "fp32": True} and st["engine_calls"] == 1
@@ -694,10 +625,10 @@ def test_accelerate_a_v9e_model():
     y0, r0 = eng(x)
     torch.cuda.synchronize()
     assert torch.equal(y, y0) and all(torch.equal(a, b) for a, b in zip(raws, r0))
-    z = _fixture(tag)[0]
-    _check(y.float().cpu().numpy(), z["y1"], "fp16", max(x.shape[2:]), "accelerate yolov9e_q")
+    z = fixture(tag)[0]
+    check_y(y.float().cpu().numpy(), z["y1"], None, None, max(x.shape[2:]), "fp16", "accelerate yolov9e_q", NC, Y_BOUNDS)
     for l, r in enumerate(raws):
-        _check_map(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate yolov9e_q raw {l}")
+        check_raw(r.float().cpu().numpy(), z[f"raw1_{l}"], "fp16", f"accelerate yolov9e_q raw {l}", MAP_BOUNDS)
     eng.close()
     plugin.restore(m)
     assert m(x) == "original" and m.calls == 1
